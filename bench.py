@@ -126,7 +126,36 @@ def parse_args(argv=None):
     ap.add_argument("--overlap", choices=["on", "off"], default="off",
                     help="several GPUs: exchanges on their own stream beside the aggregation of the locally owned columns (HIPGCN_OVERLAP_EXCHANGE)")
     ap.add_argument("--selftest", action="store_true", help="several GPUs: run gcnhost_rccl_selftest_world on every rank and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the K timed steps, write what the headline path computed in its last step as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args(argv)
+
+
+DUMP_LOGIT_ROWS = 4096        # seeded sample of the training rows of the logits written by --dump-outputs
+
+
+def dump_outputs(out_dir, model, ds, trace):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 / float64 .npy files (< 3 MB at
+    the headline size), so that two builds run with the same arguments can be compared output for output:
+      trace                       [K x 4] f32: train loss, train accuracy, validation loss, validation accuracy of every timed
+                                  step (run_epochs' return value; the last row is the last step)
+      w1, w2                      the weights the last step's Adam wrote ([F x h], [h x C])
+      train_logits_sample         the logits Z of the last step's training forward on DUMP_LOGIT_ROWS training rows, drawn
+                                  with a fixed seed from the dataset's training split (this rank's rows only)
+      train_logits_sample_rows    their node ids in the dataset, as float64"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ids, _ = model.row_ids()
+    local = np.full(ds["num_nodes"], -1, np.int64)
+    local[ids] = np.arange(ids.size)
+    train = np.flatnonzero(ds["split"] == 1)
+    rows = np.sort(np.random.default_rng(0).choice(train, min(DUMP_LOGIT_ROWS, train.size), replace=False))
+    rows = rows[local[rows] >= 0]
+    arrays = {"trace": np.asarray(trace, np.float32), "w1": model.var(2), "w2": model.var(5),
+              "train_logits_sample": model.var(6)[local[rows]], "train_logits_sample_rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in arrays.items()))
 
 
 # ----------------------------------------------------------------------------------------------- launcher (N > 1)
@@ -215,6 +244,19 @@ def _run_ranks(n_gpus, extra, timeout, env=None):
     return rc, line
 
 
+def _without_dump(argv):
+    """argv without --dump-outputs: the outputs written are those of the plain schedule, whichever schedule is printed last"""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif not a.startswith("--dump-outputs="):
+            out.append(a)
+    return out
+
+
 def launch_ranks(n_gpus, argv):
     """Parent of an N-rank run.  Runs before torch or any native library is imported: this process never
     initialises the GPU, it only starts children, so nothing here is an exec from a GPU process.
@@ -283,7 +325,7 @@ def launch_ranks(n_gpus, argv):
             log(f"schedule {extra} skipped: {left():.0f} s left of the deadline, a run needs ~{estimate:.0f} s")
             others.append({"schedule": " ".join(extra), "value": None, "skipped": f"{left():.0f} s left, ~{estimate:.0f} s needed"})
             continue
-        rc2, line2 = _run_ranks(n_gpus, argv + extra + ["--no-cpu-baseline"], min(t_try, left()), env)
+        rc2, line2 = _run_ranks(n_gpus, _without_dump(argv) + extra + ["--no-cpu-baseline"], min(t_try, left()), env)
         if rc2 == 0:
             lines.append(json.loads(line2))
         else:
@@ -684,6 +726,8 @@ def main():
     transport = model.transport() if world > 1 else None
     model.run_epochs(args.warmup, want_trace=False)
     dt, trace = timed_region(model, args.steps)      # <- the headline: default product path, per-op timers off
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, ds, trace)
     burst_eps = [args.steps / dt]
     for _ in range(args.bursts):
         d, _tr = timed_region(model, args.steps)

@@ -182,6 +182,16 @@ def test_launcher_retries_pinned_and_reports_plain_failure(monkeypatch, capsys):
     assert rc == 1 and lines == []
 
 
+def test_optional_schedules_do_not_overwrite_the_dumped_outputs():
+    """N > 1: only the plain schedule's ranks get --dump-outputs; the optional schedules run without it"""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    assert bench._without_dump(["--steps", "3", "--dump-outputs", "d", "--warmup", "1"]) == ["--steps", "3", "--warmup", "1"]
+    assert bench._without_dump(["--dump-outputs=d", "--steps", "3"]) == ["--steps", "3"]
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d" and bench.parse_args([]).dump_outputs is None
+
+
 CONTRACT = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"]
 
@@ -202,6 +212,33 @@ def test_bench_one_gpu_line():
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
     assert r["launches"] > 0 and r["avg_launch_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_step_outputs(tmp_path):
+    """--dump-outputs: the timed path's trace (one row per timed step, the last one = the line's `final`), the weights and a
+    seeded sample of the training logits, all float32 / float64 and small; the sampled rows are training rows"""
+    import numpy as np
+    d = tmp_path / "out"
+    p = run_bench(["--dataset", "reddit-mini", "--steps", 3, "--warmup", 1, "--bursts", 0, "--no-cpu-baseline", "--no-extras",
+                   "--dump-outputs", d])
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json_lines(p.stdout)[0]
+    arrays = {f.stem: np.load(f) for f in d.glob("*.npy")}
+    assert set(arrays) == {"trace", "w1", "w2", "train_logits_sample", "train_logits_sample_rows"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    tr = arrays["trace"]
+    assert tr.shape == (3, 4) and np.isfinite(tr).all()
+    f = out["final"]
+    assert tr[-1].tolist() == [np.float32(f[k]) for k in ("train_loss", "train_acc", "val_loss", "val_acc")]
+    assert arrays["w1"].shape == (602, 128) and arrays["w2"].shape == (128, 41)
+    from cuda_gcn_amd import datagen
+    ds = datagen.make_dataset("reddit-mini")
+    rows = arrays["train_logits_sample_rows"].astype(np.int64)
+    z = arrays["train_logits_sample"]
+    assert z.shape == (rows.size, 41) and rows.size == min(4096, int((ds["split"] == 1).sum()))
+    assert (ds["split"][rows] == 1).all() and np.isfinite(z).all() and np.abs(z).max() > 0
 
 
 @pytest.mark.gpu
