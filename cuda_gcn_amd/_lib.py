@@ -103,6 +103,8 @@ GCNHIP_SYMBOLS = {
     "gcnhip_graphsum_relu_dropout": (I, [P, P, P, I, P, I, I, I, F, U64, P, U64, P]),
     "gcnhip_graphsum_relu_dropout_bits": (I, [P, P, P, I, P, I, I, I, F, U64, P, U64, P, P, I]),
     "gcnhip_graphsum_ex": (I, [P, P, P, P, I, P, I, I]),
+    "gcnhip_graphsum_predict": (I, [P, P, P, P, P, I, P, I, I, I, P, P, P, I]),
+    "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
     "gcnhip_xent_fwd_rows_scaled": (I, [P, P, I, P, I, P, P, I, I, I, I, I, P, P, P]),
@@ -205,6 +207,11 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_row_scale": (I, [P, P, C.POINTER(I)]),
     "gcnhost_model_get_var": (I, [P, I, I, P, C.POINTER(I), C.POINTER(I)]),
     "gcnhost_model_set_weights": (I, [P, P, P]),
+    "gcnhost_model_predict": (I, [P, P, I, P, P, P]),
+    "gcnhost_model_save_weights": (I, [P, C.c_char_p]),
+    "gcnhost_model_load_weights": (I, [P, C.c_char_p]),
+    "gcnhost_weights_write": (I, [C.c_char_p, I, I, I, P, P]),
+    "gcnhost_weights_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), C.POINTER(I), P, P]),
     "gcnhost_model_timer": (I, [P, I, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
     "gcnhost_model_timers_reset": (I, [P]),
     "gcnhost_model_set_timers": (I, [P, I]),

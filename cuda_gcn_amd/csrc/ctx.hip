@@ -661,6 +661,19 @@ int gcnhip_graph_add_rowset(gcnhip_ctx *c, gcnhip_graph *g, const uint32_t *h_ro
     *out = rs;
     return 0;
 }
+int gcnhip_graph_remove_rowset(gcnhip_ctx *c, gcnhip_graph *g, gcnhip_rowset *rs) {
+    if (!c || !g || !rs) return -1;
+    if (rs->owner != g || !g->rowsets) return gcnhip_fail("gcnhip_graph_remove_rowset: the row subset was registered on another adjacency object");
+    auto it = std::find(g->rowsets->begin(), g->rowsets->end(), rs);
+    if (it == g->rowsets->end()) return -1;
+    GCNHIP_TRY(hipSetDevice(c->device));
+    GCNHIP_TRY(hipStreamSynchronize(c->stream));       // no aggregation of this context may still be reading its task list
+    g->rowsets->erase(it);
+    if (rs->tasks) hipFree(rs->tasks);
+    if (rs->split_rows) hipFree(rs->split_rows);
+    delete rs;
+    return 0;
+}
 int gcnhip_rowset_size(const gcnhip_rowset *rs, int *n_rows_tasks) {
     if (!rs || !n_rows_tasks) return -1;
     *n_rows_tasks = rs->n_tasks;

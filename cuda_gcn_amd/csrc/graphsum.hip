@@ -691,6 +691,231 @@ __global__ __launch_bounds__(256) void graphsum_bf16_kernel(GsArgs a) {
     }
 }
 
+// ---- prediction epilogue (gcnhip_graphsum_predict) ------------------------------------------------------------------
+// The row reduction of the loss epilogue with a different output: pred[r] = argmax of the logit row (the LOWEST column on a
+// tie, numpy.argmax's rule), prob[r] = 1 / sum_j exp(z_j - max) — max and the left-to-right sum are the loss epilogue's, so
+// the bits of the sum are those of xent_row_epilogue*'s `se` — and optionally logp[r, :] = (z - max) - log(sum), the whole
+// log-softmax row.  Never part of an existing kernel: separate instantiations (graphsum_predict_*) carry it.
+struct PredArgs {
+    int32_t *pred;          // [rows of out]
+    float *prob;            // [rows of out]
+    float *logp;            // NULL, or [rows of out x ld_logp]
+    int ld_logp;
+};
+
+// (value, column) of the larger logit; on equal values the lower column
+__device__ __forceinline__ void argmax_merge(float &bv, int &bi, float ov, int oi) {
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+}
+
+// Layouts A (f32 vector kernel, K = 4) and C (bf16 kernel, K = 8): lane l of group 0 holds columns K*l .. K*l+K-1 of the
+// row in z (one column chunk: dim <= 64, launch site); every lane of the wave calls.
+template <int L, int K>
+__device__ __forceinline__ void predict_row_epilogue(const GsArgs &a, const PredArgs &p, int row, const float (&z)[K], int lane, int l,
+                                                     int g, int col0) {
+#pragma clang fp contract(off)
+    const int nvk = (a.dim + K - 1) / K;                    // lanes of group 0 that hold columns
+    float x[K];
+    float mx = -1e30f;                                      // as xent_row_epilogue4
+    float bv = -INFINITY;
+    int bi = 0x7FFFFFFF;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        x[i] = z[i];
+        if (col0 + i < a.dim) {
+            mx = fmaxf(mx, x[i]);
+            if (bi == 0x7FFFFFFF || x[i] > bv) { bv = x[i]; bi = col0 + i; }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, m, WAVE));
+        argmax_merge(bv, bi, __shfl_xor(bv, m, WAVE), __shfl_xor(bi, m, WAVE));
+    }
+    mx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mx)));       // lane 0 is in group 0
+    bi = __builtin_amdgcn_readfirstlane(bi);
+    float ex[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        x[i] -= mx;
+        ex[i] = col0 + i < a.dim ? expf(x[i]) : 0.f;
+    }
+    float se = 0.f;
+    for (int q = 0; q < nvk; q++) {                         // columns K*q .. K*q+K-1 live in lane q (group 0): left to right
+#pragma unroll
+        for (int i = 0; i < K; i++) se += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ex[i]), q));
+    }
+    if (lane == 0) { p.pred[row] = bi; p.prob[row] = 1.f / se; }
+    if (p.logp && g == 0 && l < nvk) {
+        const float ls = logf(se);
+        float *o = p.logp + (size_t)row * p.ld_logp + col0;
+#pragma unroll
+        for (int i = 0; i < K; i++) if (col0 + i < a.dim) o[i] = x[i] - ls;
+    }
+}
+// Layout B (finalize kernel, split rows): lane c of the block's first wave holds column c in v; that whole wave calls.
+__device__ __forceinline__ void predict_row_epilogue1(const GsArgs &a, const PredArgs &p, int row, float v, int lane) {
+#pragma clang fp contract(off)
+    const int nv4 = (a.dim + 3) >> 2;
+    const bool in_row = lane < a.dim;
+    float mx = in_row ? fmaxf(-1e30f, v) : -1e30f;          // as xent_row_epilogue1
+    float bv = in_row ? v : -INFINITY;
+    int bi = in_row ? lane : 0x7FFFFFFF;
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, m, WAVE));
+        argmax_merge(bv, bi, __shfl_xor(bv, m, WAVE), __shfl_xor(bi, m, WAVE));
+    }
+    const float x = v - mx;
+    const float ex = in_row ? expf(x) : 0.f;
+    float se = 0.f;
+    for (int j = 0; j < 4 * nv4; j++) se += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ex), j));
+    if (lane == 0) { p.pred[row] = bi; p.prob[row] = 1.f / se; }
+    if (p.logp && in_row) p.logp[(size_t)row * p.ld_logp + lane] = x - logf(se);
+}
+
+// Prediction kernels: the gathers of graphsum_vec_kernel (one column chunk, not sliced), graphsum_bf16_kernel and
+// graphsum_finalize_kernel — same lane groups, same edge order, same reduction tree and post factor, so the logits have the
+// bits of those kernels — with the prediction epilogue in place of the ReLU / dropout / mask / loss options (which a
+// prediction never takes).  Kept apart so that no existing kernel changes.  `out` may be NULL: the logits are not stored.
+template <int L, int U>
+__global__ __launch_bounds__(256) void graphsum_predict_vec_kernel(GsArgs a, PredArgs p) {
+    const int lane = threadIdx.x & 63;
+    int t;
+    {
+        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if (t >= a.bounds[xcd + 1]) return;                // wave-uniform
+    }
+    int row, e0, e1, slot;
+    if (a.n_tasks) {
+        const int4 tk = a.tasks[t];
+        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
+    } else {
+        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
+    }
+    const int g = lane / L, l = lane % L;
+    const int col0 = l * 4;
+    const bool active = col0 < a.dim;
+    const float *in = a.in + (active ? col0 : 0);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = e0; base < e1; base += WAVE) {
+        const int cnt = min(WAVE, e1 - base);
+        int my_idx = 0;
+        float my_c = 0.f;
+        if (lane < cnt) {
+            my_idx = a.indices[base + lane];
+            my_c = a.coef ? a.coef[base + lane] : 1.f;
+        }
+        acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
+    }
+#pragma unroll
+    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
+    if (slot >= 0) {                                        // the finalize launch adds the segments and predicts
+        if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+        return;
+    }
+    if (g == 0 && active) {
+        if (a.post) { const float ps = a.post[row]; acc.x *= ps; acc.y *= ps; acc.z *= ps; acc.w *= ps; }
+        if (a.out) {
+            float *o = a.out + (size_t)row * a.ld_out + col0;
+            if (col0 + 4 <= a.dim) {
+                *reinterpret_cast<float4 *>(o) = acc;
+            } else {
+                const float x[4] = {acc.x, acc.y, acc.z, acc.w};
+                for (int i = 0; col0 + i < a.dim; i++) o[i] = x[i];
+            }
+        }
+    }
+    const float z[4] = {acc.x, acc.y, acc.z, acc.w};
+    predict_row_epilogue<L, 4>(a, p, row, z, lane, l, g, col0);
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void graphsum_predict_bf16_kernel(GsArgs a, PredArgs p) {
+    constexpr int G = WAVE / L;
+    const int lane = threadIdx.x & 63;
+    int t;
+    {
+        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if (t >= a.bounds[xcd + 1]) return;
+    }
+    int row, e0, e1, slot;
+    if (a.n_tasks) {
+        const int4 tk = a.tasks[t];
+        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
+    } else {
+        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
+    }
+    const int g = lane / L, l = lane % L;
+    const int col0 = l * 8;
+    const bool active = col0 < a.dim;
+    const uint16_t *in = a.in_bf + (active ? col0 : 0);
+    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+    for (int base = e0; base < e1; base += WAVE) {          // graphsum_bf16_kernel's batches, without an input row mask
+        const int cnt = min(WAVE, e1 - base);
+        int my_idx = 0;
+        float my_c = 0.f;
+        if (lane < cnt) {
+            my_idx = a.indices[base + lane];
+            my_c = a.coef[base + lane];
+        }
+        const int iters = (cnt + G - 1) / G;
+        int k = 0;
+        for (; (k + GS_U) * G <= cnt; k += GS_U) {
+            uint4 v[GS_U];
+            float cc[GS_U];
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) {
+                const int src = (k + u) * G + g;
+                const int j = __shfl(my_idx, src, WAVE);
+                cc[u] = __shfl(my_c, src, WAVE);
+                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)j * a.ld_in);
+            }
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) bf8_fma(cc[u], v[u], lo, hi);
+        }
+        const int j_safe = __shfl(my_idx, 0, WAVE);
+        for (; k < iters; k += GS_U) {
+            uint4 v[GS_U];
+            float cc[GS_U];
+            bool on[GS_U];
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) {
+                const int src = (k + u) * G + g;
+                const int j = __shfl(my_idx, src & 63, WAVE);
+                cc[u] = __shfl(my_c, src & 63, WAVE);
+                on[u] = src < cnt && cc[u] != 0.f;
+                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
+            }
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) {
+                float4 nlo = lo, nhi = hi;
+                bf8_fma(cc[u], v[u], nlo, nhi);
+                lo.x = on[u] ? nlo.x : lo.x; lo.y = on[u] ? nlo.y : lo.y; lo.z = on[u] ? nlo.z : lo.z; lo.w = on[u] ? nlo.w : lo.w;
+                hi.x = on[u] ? nhi.x : hi.x; hi.y = on[u] ? nhi.y : hi.y; hi.z = on[u] ? nhi.z : hi.z; hi.w = on[u] ? nhi.w : hi.w;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = L; m < WAVE; m <<= 1) { lo = f4_add(lo, f4_shfl_xor(lo, m)); hi = f4_add(hi, f4_shfl_xor(hi, m)); }
+    if (slot >= 0) {
+        if (g == 0 && active) {
+            float *pp = a.partials + (size_t)slot * a.part_ld + col0;
+            *reinterpret_cast<float4 *>(pp) = lo;
+            *reinterpret_cast<float4 *>(pp + 4) = hi;
+        }
+        return;
+    }
+    const float z[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    if (g == 0 && active && a.out) {
+        float *o = a.out + (size_t)row * a.ld_out + col0;
+        for (int i = 0; i < 8 && col0 + i < a.dim; i++) o[i] = z[i];
+    }
+    predict_row_epilogue<L, 8>(a, p, row, z, lane, l, g, col0);
+}
+
 // f32 -> bf16 (round to nearest even; NaN stays NaN), columns dim..ld_dst-1 of every row written as 0
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restrict__ src, int ld_src, uint16_t *__restrict__ dst, int ld_dst,
                                                           int64_t rows, int dim) {
@@ -714,7 +939,7 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restric
 }
 
 template <int L>
-static void launch_bf16(GsArgs a, const int (*xb)[9], hipStream_t s) {
+static void launch_bf16(GsArgs a, const int (*xb)[9], hipStream_t s, const PredArgs *pred = nullptr) {
     const int ychunks = ceil_div(a.dim, L * 8);
     const bool sliced = ychunks > 1 && 8 % ychunks == 0;
     a.n_slices = sliced ? ychunks : 1;
@@ -723,6 +948,9 @@ static void launch_bf16(GsArgs a, const int (*xb)[9], hipStream_t s) {
     int max_blocks = 1;
     for (int k = 0; k <= 8; k++) a.bounds[k] = xb[lg][k];
     for (int k = 0; k < G; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
+    if constexpr (L <= 8) {
+        if (pred) { graphsum_predict_bf16_kernel<L><<<max_blocks * 8, 256, 0, s>>>(a, *pred); return; }   // dim <= 64: one chunk
+    }
     graphsum_bf16_kernel<L><<<dim3(max_blocks * 8, sliced ? 1 : ychunks), 256, 0, s>>>(a);
 }
 
@@ -849,8 +1077,31 @@ __global__ __launch_bounds__(256) void graphsum_finalize_kernel(GsArgs a, const 
     }
 }
 
+// graphsum_finalize_kernel's segment sum (dim <= 64: one pass, the first wave holds the row) with the prediction epilogue
+__global__ __launch_bounds__(256) void graphsum_finalize_predict_kernel(GsArgs a, PredArgs p, const int4 *split_rows, int n_split_rows) {
+    const int s = blockIdx.x;
+    if (s >= n_split_rows || threadIdx.x >= WAVE) return;  // whole wave 0 stays
+    const int4 sr = split_rows[s];
+    const int row = sr.x, first = sr.y, ns = sr.z;
+    const int col = threadIdx.x;
+    float v = 0.f;
+    if (col < a.dim) {
+        const float *pp = a.partials + (size_t)first * a.part_ld + col;
+        int k = 0;
+        for (; k + 4 <= ns; k += 4) {
+            const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
+            const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
+            v += p0; v += p1; v += p2; v += p3;
+        }
+        for (; k < ns; k++) v += pp[(size_t)k * a.part_ld];
+        if (a.post) v *= a.post[row];
+        if (a.out) a.out[(size_t)row * a.ld_out + col] = v;
+    }
+    predict_row_epilogue1(a, p, row, v, col);
+}
+
 template <int L>
-static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c) {
+static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c, const PredArgs *pred = nullptr) {
     hipStream_t s = c->stream;
     const int ychunks = ceil_div(a.dim, L * 4);
     const bool sliced = ychunks > 1 && 8 % ychunks == 0;   // XCD-sliced columns (1-D grid)
@@ -866,7 +1117,7 @@ static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c) {
     // task order keep the XCD's window of active rows tight, statically strided persistent waves drift apart.
 #ifdef GCNHIP_EXPERIMENTS
     const bool pipe = c->opt.gs_pipe != 0;
-    if (pipe && a.n_tasks && !a.out_bits && !a.accumulate && !a.pos_bits && a.coef) {
+    if (pipe && !pred && a.n_tasks && !a.out_bits && !a.accumulate && !a.pos_bits && a.coef) {
         a.seg_count = nullptr; a.slot_info = nullptr;      // the experiment keeps the finalize launch
         const int per_xcd = std::min(max_blocks, 32 * 8);
         graphsum_pipe_kernel<L><<<dim3(per_xcd * 8, sliced ? 1 : ychunks), 256, 0, s>>>(a);
@@ -879,6 +1130,13 @@ static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c) {
     const int force_u = c->opt.gs_u;
     const int u = force_u ? force_u : (a.table_bytes > ((size_t)256 << 20) ? 2 : 4);
     const dim3 grid(max_blocks * 8, sliced ? 1 : ychunks);
+    if constexpr (L <= 16) {
+        if (pred) {                                         // dim <= 64: one column chunk, never sliced; 1 or 2 loads in flight: same bits
+            if (u >= 4) graphsum_predict_vec_kernel<L, 4><<<grid, 256, 0, s>>>(a, *pred);
+            else graphsum_predict_vec_kernel<L, 2><<<grid, 256, 0, s>>>(a, *pred);
+            return;
+        }
+    }
 #ifdef GCNHIP_EXPERIMENTS
     const bool nt_all = c->opt.gs_nt != 0;                            // EXPERIMENT: every row load non-temporal
     if (sliced && nt_all && L == 16 && a.coef) { graphsum_vec_kernel<16, 4, true, true><<<grid, 256, 0, s>>>(a); return; }
@@ -903,8 +1161,8 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
                          uint64_t elem_offset, const uint8_t *keep_mask, const uint32_t *row_bits = nullptr,
                          const uint16_t *in_bf = nullptr, const uint32_t *out_bits = nullptr,
                          const gcnhip_rowset *rs = nullptr, int accumulate = 0, uint32_t *pos_bits = nullptr, int wpr = 0, int scaling = 0,
-                         const gcnhip_gs_loss *loss = nullptr) {
-    if (!c || !g || (!in && !in_bf) || !out || dim <= 0 || ld_in < dim || ld_out < dim) return -1;
+                         const gcnhip_gs_loss *loss = nullptr, const PredArgs *pred = nullptr) {
+    if (!c || !g || (!in && !in_bf) || (!out && !pred) || dim <= 0 || ld_in < dim || ld_out < dim) return -1;
     if (scaling < 0 || scaling > 3) return -1;
     if (accumulate && in_bf) return -1;                     // the bf16 kernel has no accumulating store
     if (rs && rs->owner != g)                                // a subset brings task lists and segment slots of ITS adjacency object
@@ -947,6 +1205,8 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         a.xe_truth = loss->truth; a.xe_grad = loss->training ? loss->grad : nullptr; a.xe_ld_grad = loss->ld_grad; a.xe_training = loss->training ? 1 : 0;
         a.xe_count = (float)loss->count; a.xe_grad_scale = loss->grad_row_scale; a.xe_terms = loss->row_terms;
     }
+    if (pred && (dim > 64 || fuse || pos_bits || loss || accumulate || row_bits || out_bits || (!in_bf && !vec)))
+        return gcnhip_fail("gcnhip_graphsum_predict: needs dim <= 64 and f32 rows that are 16-byte aligned (ld % 4 == 0) or a bf16 table");
     if (scaling) {
         // the factored operator runs in the 16-byte-row f32 kernel only (what the model's layouts always are)
         if (in_bf || !vec) return gcnhip_fail("gcnhip_graphsum_ex: scaling != 0 needs f32 rows that are 16-byte aligned (ld % 4 == 0)");
@@ -959,11 +1219,11 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
     a.n_slices = 1;
     if (in_bf) {
         const int d8 = (dim + 7) / 8;                       // 16-byte pieces per row
-        if (d8 <= 1) launch_bf16<1>(a, xb, c->stream);
-        else if (d8 <= 2) launch_bf16<2>(a, xb, c->stream);
-        else if (d8 <= 4) launch_bf16<4>(a, xb, c->stream);
+        if (d8 <= 1) launch_bf16<1>(a, xb, c->stream, pred);
+        else if (d8 <= 2) launch_bf16<2>(a, xb, c->stream, pred);
+        else if (d8 <= 4) launch_bf16<4>(a, xb, c->stream, pred);
         else if (d8 % 16 == 0) launch_bf16<16>(a, xb, c->stream);   // 128-column (two-line) slices as in the f32 kernel: 305 -> 322 epochs/s
-        else launch_bf16<8>(a, xb, c->stream);               // 64-column (one line) slices, one per XCD group when 8 % slices == 0
+        else launch_bf16<8>(a, xb, c->stream, pred);               // 64-column (one line) slices, one per XCD group when 8 % slices == 0
     }
     // GCNHIP_GS_FOLD (opt-in, round 3): the vector kernel adds the segments of a split row itself (the last segment to finish
     // does) and no finalize launch follows.  Same bits; measured no faster at 5 K segments and slower as their number grows
@@ -974,13 +1234,13 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
 #else
     const bool fold = false;
 #endif
-    if (!in_bf && vec && n_split_rows && g->seg_count && fold) {
+    if (!in_bf && vec && n_split_rows && g->seg_count && fold && !pred) {
         a.slot_info = g->slot_info; a.seg_count = g->seg_count;
         a.n_slots_bytes = (int)std::min<size_t>((size_t)g->n_slots * g->part_ld * sizeof(float), 0x7FFFFFFFu);
     }
     const int gl = c->opt.gs_l;                             // narrower column slices than 64 floats (8: 32 floats, 4: 16 floats), round 5
     if (in_bf) {
-    } else if (vec && !loss && (gl == 8 || (gl == 4 && !pos_bits)) && dim % (gl * 4) == 0 && dim / (gl * 4) > 1 && 8 % (dim / (gl * 4)) == 0) {
+    } else if (vec && !loss && !pred && (gl == 8 || (gl == 4 && !pos_bits)) && dim % (gl * 4) == 0 && dim / (gl * 4) > 1 && 8 % (dim / (gl * 4)) == 0) {
         // More slices = a smaller share of the table per XCD's L2 (what a structure-free graph's hub rows need) against more
         // re-reads of the index stream and shorter requests.  Measured per graph (tools/exp_structure.py); never the default.
         // (16-float slices hold half a mask word per lane group: with pos_bits they fall through to the 64-float slices below)
@@ -990,13 +1250,13 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         // 1/slices of the table and the (index, coef) stream is re-read only once per slice.  Measured at Reddit scale
         // with 4 row loads in flight, 32- / 64- / 128-float slices: d = 64: 0.434 / 0.403 / - ms; d = 128: 0.843 / 0.760 /
         // 0.874; d = 256: 2.36 / 1.77 / 1.78; R-MAT scale 21 (HBM regime), d = 128: 5.20 / 4.57 ms.
-        launch_vec<16>(a, xb, c);
+        launch_vec<16>(a, xb, c, pred);
     } else if (vec) {
-        if (d4 <= 1) launch_vec<1>(a, xb, c);
-        else if (d4 <= 2) launch_vec<2>(a, xb, c);
-        else if (d4 <= 4) launch_vec<4>(a, xb, c);
-        else if (d4 <= 8) launch_vec<8>(a, xb, c);
-        else if (d4 <= 16) launch_vec<16>(a, xb, c);
+        if (d4 <= 1) launch_vec<1>(a, xb, c, pred);
+        else if (d4 <= 2) launch_vec<2>(a, xb, c, pred);
+        else if (d4 <= 4) launch_vec<4>(a, xb, c, pred);
+        else if (d4 <= 8) launch_vec<8>(a, xb, c, pred);
+        else if (d4 <= 16) launch_vec<16>(a, xb, c, pred);
         else if (d4 <= 32) launch_vec<32>(a, xb, c);
         else launch_vec<64>(a, xb, c);
     } else {
@@ -1010,7 +1270,8 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
     }
     GCNHIP_LAUNCH_CHECK();
     if (n_split_rows && !a.seg_count) {
-        graphsum_finalize_kernel<<<n_split_rows, 256, 0, c->stream>>>(a, split_rows, n_split_rows);
+        if (pred) graphsum_finalize_predict_kernel<<<n_split_rows, WAVE, 0, c->stream>>>(a, *pred, split_rows, n_split_rows);
+        else graphsum_finalize_kernel<<<n_split_rows, 256, 0, c->stream>>>(a, split_rows, n_split_rows);
         GCNHIP_LAUNCH_CHECK();
     }
     return 0;
@@ -1073,6 +1334,17 @@ int gcnhip_graphsum_ex(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_gs_opt
     return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, o->relu_dropout ? 1 : 0, o->relu_dropout ? o->training : 0, o->relu_dropout ? o->p : 0.f,
                          o->seed, o->d_epoch, o->elem_offset, o->keep_mask, o->in_row_bits, nullptr, nullptr, o->rows, o->accumulate ? 1 : 0,
                          o->pos_bits, o->words_per_row, o->scaling, o->loss);
+}
+
+int gcnhip_graphsum_predict(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, const uint16_t *in_bf16,
+                            int ld_in, float *out, int ld_out, int dim, int scaling, int32_t *pred, float *prob, float *logp, int ld_logp) {
+    if (!pred || !prob || (in != nullptr) == (in_bf16 != nullptr)) return -1;
+    if (logp && ld_logp < dim) return -1;
+    if (in_bf16 && scaling) return gcnhip_fail("gcnhip_graphsum_predict: the factored operator (scaling != 0) gathers f32 rows only");
+    const PredArgs pa = {pred, prob, logp, ld_logp};
+    // (no logits stored: a stride that passes the 16-byte row test; nothing is written through it)
+    return graphsum_impl(c, g, in, ld_in, out, out ? ld_out : (dim + 3) / 4 * 4, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, in_bf16, nullptr, rows, 0,
+                         nullptr, 0, scaling, nullptr, &pa);
 }
 
 #ifndef GCNHIP_EXPERIMENTS

@@ -8,6 +8,7 @@
 #include "cluster.h"
 #include "hip_check.h"
 #include "parser.h"
+#include "weights.h"
 
 static thread_local std::string g_err;
 
@@ -156,6 +157,23 @@ int gcnhost_model_get_var(gcnhost_model *m, int k, int grad, float *out, int *ro
     })
 }
 int gcnhost_model_set_weights(gcnhost_model *m, const float *w1, const float *w2) { API_TRY({ m->gcn->set_weights(w1, w2); }) }
+int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
+    API_TRY({ m->gcn->predict(nodes, n, pred, prob, logp); })
+}
+int gcnhost_model_save_weights(gcnhost_model *m, const char *path) {
+    if (!m || !path) { g_err = "gcnhost_model_save_weights: invalid argument"; return -1; }
+    API_TRY({ m->gcn->save_weights(path); })
+}
+int gcnhost_model_load_weights(gcnhost_model *m, const char *path) {
+    if (!m || !path) { g_err = "gcnhost_model_load_weights: invalid argument"; return -1; }
+    API_TRY({ m->gcn->load_weights(path); })
+}
+int gcnhost_weights_write(const char *path, int input_dim, int hidden_dim, int output_dim, const float *w1, const float *w2) {
+    return gcn_weights_write(path, input_dim, hidden_dim, output_dim, w1, w2, &g_err);
+}
+int gcnhost_weights_read(const char *path, int *input_dim, int *hidden_dim, int *output_dim, float *w1, float *w2) {
+    return gcn_weights_read(path, input_dim, hidden_dim, output_dim, w1, w2, &g_err);
+}
 int gcnhost_model_timer(gcnhost_model *m, int id, double *seconds, long *count) {
     if (id < 0 || id >= __NUM_TMR) { g_err = "bad timer id"; return -1; }
     API_TRY({ *seconds = m->gcn->timer_total((timer_instance)id, count); })

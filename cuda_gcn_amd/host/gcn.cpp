@@ -1,4 +1,5 @@
 #include "gcn.h"
+#include "weights.h"
 #include "cluster.h"
 #include <chrono>
 #include <deque>
@@ -595,7 +596,7 @@ void HipGCN::build_modules() {
         modules.push_back(new HipReLU(&env, H1));
         modules.push_back(new HipDropout(&env, H1, p, KEY_HIDDEN_DROPOUT, hid_off, (flags & HIPGCN_HOST_MASKS) ? &env.keep_hidden : &no_mask));
         modules.push_back(new HipMatmul(&env, H1, W2, Z0, N, H, C));
-        { auto *gs = new HipGraphSum(&env, Z0, Z, graph, C); gs->bwd_row_bits = &bwd_bits; gs->bwd_graph = graph_bwd_out; gs->fwd_out_rows = &cur_out_rows; wire_overlap(gs, true); modules.push_back(gs); }
+        { auto *gs = new HipGraphSum(&env, Z0, Z, graph, C); gs->bwd_row_bits = &bwd_bits; gs->bwd_graph = graph_bwd_out; gs->fwd_out_rows = &cur_out_rows; wire_overlap(gs, true); modules.push_back(gs); logits_gs = gs; }
         modules.push_back(new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, true));
     } else {
         const float scale = 1 / (1 - p);
@@ -650,6 +651,7 @@ void HipGCN::build_modules() {
             wire_overlap(gs, true);
             modules.push_back(gs);
             gs_logits = gs;
+            logits_gs = gs;
         }
         auto *ce = new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, false);
         ce->rows_list = &cur_rows; ce->rows_n = &cur_rows_n;
@@ -896,6 +898,9 @@ void HipGCN::release() {
     gcnhip_free(env.ctx, d_train_bits);
     for (int s = 1; s <= 3; s++) gcnhip_free(env.ctx, d_split_list[s]);
     gcnhip_free(env.ctx, d_pos_bits);
+    gcnhip_free(env.ctx, d_pred);
+    gcnhip_free(env.ctx, d_prob);
+    gcnhip_free(env.ctx, d_logp);
     if (dh1_pack) gcnhip_rowpack_destroy(env.ctx, dh1_pack);
     timers.reset();
     exchange_buffers_destroy(&xbuf);
@@ -1384,4 +1389,103 @@ void HipGCN::set_weights(const float *w1, const float *w2) {
     variables[5]->upload(w2);
     GCNHIP_CHECK(gcnhip_sumsq(env.ctx, variables[2]->data, (int64_t)variables[2]->elems(), optimizer->d_sumsq));
     sync();
+}
+
+// ---- prediction and the weights file (beyond the reference) ------------------------------------------------------------
+
+void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
+    const int N = params.num_nodes, C = params.output_dim;
+    if (!logits_gs) throw GcnHipFailure(-1, "predict: this model has no class-width aggregation");
+    if (C > 64) throw GcnHipFailure(-1, "predict: at most 64 classes (the logit row of a node sits in one wave)");
+    if ((n > 0 && (!pred || !prob)) || n < 0) throw GcnHipFailure(-1, "predict: invalid argument");
+    if (!nodes) n = n_local;
+    // dataset node id -> local row of this rank
+    std::vector<int> rows(n);
+    if (nodes) {
+        std::vector<int> pos;
+        if (!node_order_.empty()) {
+            pos.assign(N, -1);
+            for (int p = 0; p < N; p++) pos[node_order_[p]] = p;
+        }
+        const int r0 = row_start();
+        for (int i = 0; i < n; i++) {
+            const int id = nodes[i];
+            if (id < 0 || id >= N) throw GcnHipFailure(-1, "predict: node " + std::to_string(id) + " is not a node of the dataset (0.." + std::to_string(N - 1) + ")");
+            const int r = (pos.empty() ? id : pos[id]) - r0;
+            if (r < 0 || r >= n_local)
+                throw GcnHipFailure(-1, "predict: node " + std::to_string(id) + " is not a row of rank " + std::to_string(env.comm->rank()) + " (each rank predicts its own rows)");
+            rows[i] = r;
+        }
+    } else {
+        for (int i = 0; i < n; i++) rows[i] = i;
+    }
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    const gcnhip_rowset *subset = nullptr;
+    if (nodes) {                                               // a registered subset of `graph`: the same query reuses it
+        std::vector<uint32_t> bits(((size_t)n_local + 31) / 32 + 1, 0u);
+        for (int r : rows) bits[r >> 5] |= 1u << (r & 31);
+        if (!pred_rows || bits != pred_bits) {
+            if (pred_rows) { GCNHIP_CHECK(gcnhip_graph_remove_rowset(env.ctx, graph, pred_rows)); pred_rows = nullptr; }
+            GCNHIP_CHECK(gcnhip_graph_add_rowset(env.ctx, graph, bits.data(), &pred_rows));
+            pred_bits.swap(bits);
+        }
+        subset = pred_rows;
+    }
+    const size_t nl = (size_t)std::max(n_local, 1);
+    if (!d_pred) {
+        void *p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * sizeof(int32_t))); d_pred = (int32_t *)p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * sizeof(float))); d_prob = (float *)p;
+    }
+    if (logp && !d_logp) {
+        void *p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * C * sizeof(float))); d_logp = (float *)p;
+    }
+    // an evaluation forward (eval_async's module list without the loss) on the main stream; the logit aggregation runs the
+    // prediction epilogue instead of its usual launch and stores no logits
+    if (flags & HIPGCN_MODULAR)
+        GCNHIP_CHECK(gcnhip_d2d_async(env.ctx, input->data, gcnhip_feat_values(feat), (size_t)gcnhip_feat_nnz(feat) * sizeof(float)));
+    HipGraphSum::Prediction req;
+    req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = logp ? d_logp : nullptr; req.ld_logp = C;
+    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
+    logits_gs->predict = &req;
+    try {
+        for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);       // the last module is the loss
+    } catch (...) {
+        logits_gs->predict = nullptr;
+        throw;
+    }
+    logits_gs->predict = nullptr;
+    // variable 3: a fused evaluation keeps H1 in registers (what it held stays); otherwise the forward stored it
+    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+    if (n == 0) { sync(); return; }
+    std::vector<int32_t> hp(nl);
+    std::vector<float> hq(nl), hl;
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, hp.data(), d_pred, nl * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, hq.data(), d_prob, nl * sizeof(float)));
+    if (logp) {
+        hl.resize(nl * C);
+        GCNHIP_CHECK(gcnhip_d2h(env.ctx, hl.data(), d_logp, nl * C * sizeof(float)));
+    }
+    for (int i = 0; i < n; i++) {
+        pred[i] = hp[rows[i]];
+        prob[i] = hq[rows[i]];
+        if (logp) std::copy(hl.begin() + (size_t)rows[i] * C, hl.begin() + (size_t)(rows[i] + 1) * C, logp + (size_t)i * C);
+    }
+}
+
+void HipGCN::save_weights(const char *path) {
+    std::vector<float> w1, w2;
+    get_var(2, false, w1, nullptr, nullptr);
+    get_var(5, false, w2, nullptr, nullptr);
+    std::string err;
+    if (gcn_weights_write(path, params.input_dim, params.hidden_dim, params.output_dim, w1.data(), w2.data(), &err) != 0) throw GcnHipFailure(-1, err);
+}
+
+void HipGCN::load_weights(const char *path) {
+    int F = params.input_dim, h = params.hidden_dim, C = params.output_dim;
+    std::vector<float> w1((size_t)F * h), w2((size_t)h * C);
+    std::string err;
+    if (gcn_weights_read(path, &F, &h, &C, w1.data(), w2.data(), &err) != 0) throw GcnHipFailure(-1, err);
+    set_weights(w1.data(), w2.data());
 }

@@ -161,6 +161,23 @@ public:
     bool factored() const { return factored_; }
     void row_scale(std::vector<float> &dinv);                 // 1/sqrt(deg) of this rank's rows (deg of the full graph, self loop included)
     void set_weights(const float *w1, const float *w2);       // [F x h], [h x C] row-major
+
+    // Prediction (beyond the reference, which only prints accuracy): an evaluation forward with the current weights — no
+    // dropout, the model's usual evaluation order (aggregate-first when that is on) — whose logit aggregation carries the
+    // prediction epilogue (gcnhip_graphsum_predict) on the requested rows.  nodes: n DATASET node ids, each a row of this
+    // rank (repeats allowed); NULL: every row of this rank, in the order of local rows (node_order()/row_start() name
+    // them).  pred[i] = argmax of node i's logits (lowest class on a tie), prob[i] = its softmax probability, logp
+    // (may be NULL) [n x C] = the log-softmax rows.  Several GPUs: a collective (the logit aggregation's exchange) —
+    // every rank calls it, each with its own nodes.  Training state is not touched: the metrics ring, the current split,
+    // the logits (variable 6) and the captured epoch graph are left as they were; a train_epoch() after it has the
+    // same bits as one without it.  Synchronises.
+    void predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp);
+    // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
+    // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
+    // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
+    // Adam afresh (resuming a run exactly is out of scope).
+    void save_weights(const char *path);
+    void load_weights(const char *path);
     DeviceTimers &device_timers() { return *timers; }
     double timer_total(timer_instance t, long *count);        // both lanes
     void timers_reset();
@@ -204,6 +221,12 @@ private:
     std::vector<Module *> eval_modules;                        // [0] owned (the GEMM on A^.X); the rest are modules[2..]
     bool h1_from_fused_eval = false;                           // the last forward on the main stream kept its hidden matrix in registers (get_var(3) rebuilds it)
     void build_agg_first_eval();
+    HipGraphSum *logits_gs = nullptr;                          // the class-width aggregation (producer of Z): predict() hooks it
+    // predict(): the last node query's row subset (registered on `graph`, removed when the next query differs) and scratch
+    std::vector<uint32_t> pred_bits;
+    gcnhip_rowset *pred_rows = nullptr;
+    int32_t *d_pred = nullptr;
+    float *d_prob = nullptr, *d_logp = nullptr;
     const float *full_vals = nullptr;
     bool replicate_l1 = false;
     bool rebuild_dh1 = false;                                  // multi-GPU backward: gather dZ0 + mask bits, rebuild dH1 everywhere

@@ -30,6 +30,15 @@
 // GCN_WRITE_CACHE=1: after parsing the text files, write data/<name>.gcnbin for the next run.
 // Overrides: GCN_SYNC_EPOCHS=1 (reference loop, `time=` = that epoch's own latency), GCN_EVAL_LANE=0|1,
 // GCN_REFERENCE_ORDER=0|1.
+// Trained weights and predictions (beyond the reference, whose program keeps nothing; stdout is unchanged, notes go to stderr):
+//   GCN_LOAD_WEIGHTS=<file>  after the model is built, before the run, its weights come from the file (host/weights.h; the widths
+//                            must match the dataset and hidden_dim).  With epochs = 0 (positional argument 9) the run is
+//                            inference only: `total training time=0.00000` and the test line of the loaded weights.
+//   GCN_SAVE_WEIGHTS=<file>  after the run, rank 0 writes the final weights.
+//   GCN_PREDICT=<file>       after the test line, one line per node of the dataset in id order: `node class probability`
+//                            (class = argmax of the node's logits, lowest on a tie; its softmax probability).  With several
+//                            GPUs each worker predicts its own rows into an array indexed by node id; the file is written
+//                            after the join.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -109,6 +118,12 @@ int main(int argc, char **argv) {
     std::cout << "RUNNING ON GPU" << std::endl;
 
     int rc = EXIT_SUCCESS;
+    const char *load_path = getenv("GCN_LOAD_WEIGHTS"), *save_path = getenv("GCN_SAVE_WEIGHTS"), *predict_path = getenv("GCN_PREDICT");
+    if (load_path && !*load_path) load_path = nullptr;
+    if (save_path && !*save_path) save_path = nullptr;
+    if (predict_path && !*predict_path) predict_path = nullptr;
+    std::vector<int32_t> all_pred(predict_path ? params.num_nodes : 0, -1);   // by node id, filled by the workers
+    std::vector<float> all_prob(predict_path ? params.num_nodes : 0, 0.f);
     auto worker = [&](int rank, const char *id) {
         try {
             HipGCNOptions o = base;
@@ -118,7 +133,27 @@ int main(int argc, char **argv) {
             if (rank == 0)      // stderr: stdout stays the reference's lines (src/seq/gcn.cpp:133-158)
                 fprintf(stderr, "gcn-hip: dataset loaded in %.3f s, model built in %.3f s (host preparation + every H2D copy)\n", load_s,
                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build0).count());
+            if (load_path) {
+                gcn.load_weights(load_path);
+                if (rank == 0) fprintf(stderr, "gcn-hip: weights loaded from %s\n", load_path);
+            }
             gcn.run();
+            if (save_path && rank == 0) {
+                gcn.save_weights(save_path);
+                fprintf(stderr, "gcn-hip: weights written to %s\n", save_path);
+            }
+            if (predict_path) {                                // every rank: the logit aggregation exchanges rows
+                const int n = gcn.local_rows(), r0 = gcn.row_start();
+                std::vector<int32_t> p(std::max(n, 1));
+                std::vector<float> q(std::max(n, 1));
+                gcn.predict(nullptr, n, p.data(), q.data(), nullptr);
+                const std::vector<int> &order = gcn.node_order();
+                for (int r = 0; r < n; r++) {
+                    const int id = order.empty() ? r0 + r : order[r0 + r];
+                    all_pred[id] = p[r];
+                    all_prob[id] = q[r];
+                }
+            }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",
                                               "graphsum_bw", "loss_fw", "relu_fw", "relu_bw", "dropout_fw", "dropout_bw", "adam", "comm", "graphsum_wide"};
@@ -151,6 +186,17 @@ int main(int argc, char **argv) {
         std::vector<std::thread> th;
         for (int r = 0; r < world; r++) th.emplace_back(worker, r, id);
         for (auto &t : th) t.join();
+    }
+    if (predict_path) {
+        FILE *f = fopen(predict_path, "w");
+        bool ok = f != nullptr;
+        for (int i = 0; ok && i < params.num_nodes; i++) ok = fprintf(f, "%d %d %.6g\n", i, all_pred[i], all_prob[i]) > 0;
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) {
+            fprintf(stderr, "gcn-hip: could not write the predictions to %s\n", predict_path);
+            return EXIT_FAILURE;
+        }
+        fprintf(stderr, "gcn-hip: predictions of %d nodes written to %s\n", params.num_nodes, predict_path);
     }
     return rc;
 }

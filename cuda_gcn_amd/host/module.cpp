@@ -186,12 +186,16 @@ void HipGraphSum::forward(bool training) {
         }
         if (dim > 64) env->timers->start(TMR_GRAPHSUM_WIDE);
         const bool fused = fused_relu_dropout >= 0.f;
-        GCNHIP_CHECK(gcnhip_graphsum_bf16(env->ctx, graph, tab, ld_bf, out->data, out->ld, dim, nullptr, out_rows, fused ? 1 : 0, training ? 1 : 0,
-                                          fused ? fused_relu_dropout : 0.f, env->seed ^ KEY_HIDDEN_DROPOUT, env->d_epoch, elem_offset,
-                                          training ? env->keep_hidden : nullptr));
+        if (predict)
+            GCNHIP_CHECK(gcnhip_graphsum_predict(env->ctx, graph, predict->rows, nullptr, tab, ld_bf, nullptr, 0, dim, 0, predict->pred,
+                                                 predict->prob, predict->logp, predict->ld_logp));
+        else
+            GCNHIP_CHECK(gcnhip_graphsum_bf16(env->ctx, graph, tab, ld_bf, out->data, out->ld, dim, nullptr, out_rows, fused ? 1 : 0, training ? 1 : 0,
+                                              fused ? fused_relu_dropout : 0.f, env->seed ^ KEY_HIDDEN_DROPOUT, env->d_epoch, elem_offset,
+                                              training ? env->keep_hidden : nullptr));
         if (dim > 64) env->timers->stop(TMR_GRAPHSUM_WIDE);
         env->timers->stop(TMR_GRAPHSUM_FW);
-    } else if (env->xlane && !replicated && world > 1) {
+    } else if (env->xlane && !replicated && world > 1 && !predict) {
         // exchange on its own stream; meanwhile the edges that point at this rank's own rows, then the others on top.
         // (A rank that owns no rows has no operators to cut — split_loc is NULL — but takes part in the exchange all the same:
         // it runs on the lane's communicator on EVERY rank.)
@@ -230,7 +234,10 @@ void HipGraphSum::forward(bool training) {
         uint32_t *bits_here = nullptr;
         if (training && fused_relu_dropout >= 0.f && dim % 32 == 0)
             bits_here = mask_bits_out ? mask_bits_out : (pos_bits_full ? pos_bits_full + (size_t)env->plan->own_offset * wpr : nullptr);
-        {
+        if (predict) {
+            GCNHIP_CHECK(gcnhip_graphsum_predict(env->ctx, graph, predict->rows, src, nullptr, in->ld, nullptr, 0, dim, fwd_scaling, predict->pred,
+                                                 predict->prob, predict->logp, predict->ld_logp));
+        } else {
             gcnhip_gs_opts o = {};
             o.scaling = fwd_scaling;
             if (fused_relu_dropout >= 0.f) {

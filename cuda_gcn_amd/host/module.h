@@ -162,6 +162,15 @@ public:
     // model: hidden layer forward 2 (result x dinv^2: already scaled for the class-width aggregation), class layer forward 1
     // (true logits), every backward 3 (the consumer's operand carries the factor)
     int fwd_scaling = 0, bwd_scaling = 0;
+    // set for one forward by HipGCN::predict: the aggregation runs gcnhip_graphsum_predict on these rows (NULL: all) instead
+    // of its usual launch — no ReLU / loss options, logits not stored, the exchange (several GPUs) on the main stream
+    struct Prediction {
+        const gcnhip_rowset *rows = nullptr;
+        int32_t *pred = nullptr;
+        float *prob = nullptr, *logp = nullptr;
+        int ld_logp = 0;
+    };
+    const Prediction *predict = nullptr;
     HipGraphSum(HipEnv *env, HipVariable *in, HipVariable *out, gcnhip_graph *graph, int dim,
                 float fused_relu_dropout = -1.f, uint64_t elem_offset = 0);
     ~HipGraphSum() override;

@@ -145,6 +145,31 @@ class HipGCNModel:
         w1, w2 = np.ascontiguousarray(w1, np.float32), np.ascontiguousarray(w2, np.float32)
         _ck(self.lib, self.lib.gcnhost_model_set_weights(self.h, w1.ctypes.data, w2.ctypes.data), "set_weights")
 
+    def predict(self, nodes=None, logp=False):
+        """(pred int32[n], prob f32[n]) — the class with the largest logit (the lowest on a tie, numpy.argmax's rule) and its softmax
+        probability, from an evaluation forward with the current weights (no dropout) whose logit aggregation carries the
+        prediction epilogue.  nodes: dataset node ids, each a row of this rank (repeats allowed); None: every row of this rank in
+        local-row order (row_ids() names them).  logp=True: a third array [n, output_dim] with the log-softmax rows.  Several
+        ranks: every rank calls it.  Training state is not touched."""
+        if nodes is None:
+            q, n, qp = None, self.info()["local_rows"], None
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n, qp = q.size, q.ctypes.data
+        pred = np.zeros(max(n, 1), np.int32)
+        prob = np.zeros(max(n, 1), np.float32)
+        lp = np.zeros((max(n, 1), self.params.output_dim), np.float32) if logp else None
+        _ck(self.lib, self.lib.gcnhost_model_predict(self.h, qp, n, pred.ctypes.data, prob.ctypes.data, lp.ctypes.data if logp else None), "predict")
+        return (pred[:n], prob[:n], lp[:n]) if logp else (pred[:n], prob[:n])
+
+    def save_weights(self, path):
+        """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
+        _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")
+
+    def load_weights(self, path):
+        """W1, W2 from a weights file whose widths match this model (else GcnHostError); Adam starts afresh"""
+        _ck(self.lib, self.lib.gcnhost_model_load_weights(self.h, os.fsencode(path)), "load_weights")
+
     def schedule(self):
         """row schedule of the aggregation picked at construction: 'degree', 'label-major', 'dealt-<G>' or
         'structure-major (<G> groups)' — groups found in the graph by modularity local moving"""
@@ -186,6 +211,26 @@ class HipGCNModel:
             self.close()
         except Exception:
             pass
+
+
+def read_weights(path):
+    """(W1 [F, h], W2 [h, C]) of a weights file (HipGCNModel.save_weights, gcn-hip GCN_SAVE_WEIGHTS) — host only, no GPU"""
+    lib = _lib.gcnhost()
+    F, h, c = C.c_int(), C.c_int(), C.c_int()
+    _ck(lib, lib.gcnhost_weights_read(os.fsencode(path), C.byref(F), C.byref(h), C.byref(c), None, None), "weights_read")
+    w1 = np.zeros((F.value, h.value), np.float32)
+    w2 = np.zeros((h.value, c.value), np.float32)
+    _ck(lib, lib.gcnhost_weights_read(os.fsencode(path), C.byref(F), C.byref(h), C.byref(c), w1.ctypes.data, w2.ctypes.data), "weights_read")
+    return w1, w2
+
+
+def write_weights(path, w1, w2):
+    """a weights file from two arrays W1 [F, h], W2 [h, C] — host only, no GPU"""
+    w1, w2 = np.ascontiguousarray(w1, np.float32), np.ascontiguousarray(w2, np.float32)
+    if w1.ndim != 2 or w2.ndim != 2 or w1.shape[1] != w2.shape[0]:
+        raise ValueError(f"write_weights: shapes {w1.shape} and {w2.shape} do not chain")
+    lib = _lib.gcnhost()
+    _ck(lib, lib.gcnhost_weights_write(os.fsencode(path), w1.shape[0], w1.shape[1], w2.shape[1], w1.ctypes.data, w2.ctypes.data), "weights_write")
 
 
 def load_dataset(root, name):

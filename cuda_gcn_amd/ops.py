@@ -214,6 +214,34 @@ class Device:
         return dict(logits=out.download()[:, :dim], grad=gb.download(), loss_sum=float(r[0]), count=float(r[1]), correct=int(ri[0]), total=int(ri[1]),
                     res=r, terms=terms.download() if epilogue else None)
 
+    def graphsum_predict(self, g: "Graph", x=None, scaling=0, rows=None, table_bf16=None, dim=None, ld=None, logp=True, store_logits=True):
+        """gcnhip_graphsum_predict: the logits' aggregation with the prediction epilogue.  Either f32 rows `x` (scaling as in
+        graphsum_ex) or a bf16 table `table_bf16` (uint16 [n_cols, ld], with `dim` columns).  rows: a handle from Graph.add_rowset
+        (None: every row).  Returns dict(pred int32 [n_rows], prob, logp [n_rows, dim] or None, logits or None); rows not
+        computed hold pred = -1 and NaN."""
+        if (x is None) == (table_bf16 is None):
+            raise ValueError("graphsum_predict: pass exactly one of x and table_bf16")
+        if x is not None:
+            x = np.asarray(x, np.float32)
+            dim = x.shape[1]
+            ld = ld or (dim + 3) // 4 * 4
+            xin, tin, ld_in = self.padded(x, ld), None, ld
+        else:
+            t = np.ascontiguousarray(table_bf16, np.uint16)
+            xin, tin, ld_in = None, self.buf(t), t.shape[1]
+        ld_out = (dim + 3) // 4 * 4
+        out = self.buf(np.full((g.n_rows, ld_out), np.nan, np.float32)) if store_logits else None
+        pb = self.buf(np.full(max(g.n_rows, 1), -1, np.int32))
+        qb = self.buf(np.full(max(g.n_rows, 1), np.nan, np.float32))
+        lb = self.buf(np.full((max(g.n_rows, 1), dim), np.nan, np.float32)) if logp else None
+        g.reserve(dim)
+        _ck(self.lib, self.lib.gcnhip_graphsum_predict(self.ctx, g.h, rows, xin.ptr if xin else None, tin.ptr if tin else None, ld_in,
+                                                        out.ptr if out else None, ld_out, dim, int(scaling), pb.ptr, qb.ptr,
+                                                        lb.ptr if lb else None, dim), "gcnhip_graphsum_predict")
+        n = g.n_rows
+        return dict(pred=pb.download()[:n], prob=qb.download()[:n], logp=lb.download()[:n] if lb else None,
+                    logits=out.download()[:, :dim] if out else None)
+
     def graphsum(self, g: "Graph", x, ld_in=None, ld_out=None, row_nonzero=None):
         x = np.asarray(x, np.float32)
         dim = x.shape[1]
@@ -614,6 +642,10 @@ class Graph:
         rg = np.ascontiguousarray(row_group, np.int32) if row_group is not None else None
         _ck(self.dev.lib, self.dev.lib.gcnhip_graph_set_schedule(self.dev.ctx, self.h, mode, rg.ctypes.data if rg is not None else None,
                                                                   n_groups), "gcnhip_graph_set_schedule")
+
+    def remove_rowset(self, h):
+        """gcnhip_graph_remove_rowset: unregister a subset made by add_rowset"""
+        _ck(self.dev.lib, self.dev.lib.gcnhip_graph_remove_rowset(self.dev.ctx, self.h, h), "gcnhip_graph_remove_rowset")
 
     def add_rowset(self, wanted):
         """register a subset of the rows (boolean per row); returns the handle gcnhip_graphsum_rowset takes"""

@@ -170,6 +170,24 @@ typedef struct gcnhip_gs_loss {
 } gcnhip_gs_loss;
 int gcnhip_graphsum_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const gcnhip_gs_opts *opts, const float *in, int ld_in,
                        float *out, int ld_out, int dim);
+/* Prediction epilogue of the aggregation that produces the logits: for every computed row r (all rows, or the rows of
+ * `rows`) the same launch that sums the row writes
+ *   pred[r] (int32) = the column of the largest logit — on a tie the LOWEST column, numpy.argmax's rule.  The reference's
+ *                     accuracy test (GCN::get_accuracy, src/seq/gcn.cpp:86-93) instead counts a row as correct when no logit
+ *                     is above the true one, i.e. a tie with the true class counts for it wherever the true class sits;
+ *   prob[r] (f32)   = the softmax probability of that class, 1 / sum_j exp(z_j - max): the max and the left-to-right sum
+ *                     of the loss epilogue above (gcnhip_gs_loss), so the sum has the bits of CrossEntropyLoss's;
+ *   logp[r * ld_logp + c] (optional, may be NULL) = (z_c - max) - log(sum), the whole log-softmax row.
+ * pred and prob have n_rows entries (rows outside `rows` are left untouched).  The gathered table is either f32 rows
+ * `in` (16-byte aligned, ld_in % 4 == 0; scaling as in gcnhip_graphsum_ex, the factored path) or a bf16 table `in_bf16`
+ * (as gcnhip_graphsum_bf16; scaling must be 0) — exactly one of the two.  out (may be NULL: the logits are not stored)
+ * receives the logits themselves, bit-identical to gcnhip_graphsum_ex / gcnhip_graphsum_bf16 on the same operands.
+ * dim <= 64 (the row then sits in one wave).  Separate kernels: no existing launch changes. */
+int gcnhip_graphsum_predict(gcnhip_ctx *ctx, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, const uint16_t *in_bf16,
+                            int ld_in, float *out, int ld_out, int dim, int scaling, int32_t *pred, float *prob, float *logp, int ld_logp);
+/* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
+ * subsets made at call time, such as the node queries of a prediction. */
+int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);
 /* device pointers of the factor arrays of a prepared adjacency: dinv / dinv^2 per row ([n_rows]) and per column ([n_cols]);
  * degrees are those of the full graph also for objects made by gcnhip_graph_create_restricted */
 int gcnhip_graph_scales(const gcnhip_graph *g, const float **d_dinv_row, const float **d_dinv2_row,

@@ -121,6 +121,25 @@ int gcnhost_model_slice_floats(gcnhost_model *m, int *floats);
  * default path does not compute rows nobody reads; the reference fills every row. */
 int gcnhost_model_get_var(gcnhost_model *m, int k, int grad, float *out, int *rows, int *cols);
 int gcnhost_model_set_weights(gcnhost_model *m, const float *w1, const float *w2);
+/* Prediction (beyond the reference): an evaluation forward with the current weights whose logit aggregation writes, per node,
+ * the class with the largest logit (the lowest class on a tie: numpy.argmax's rule; the reference's accuracy test counts a tie
+ * with the true class as correct) and its softmax probability.  nodes: n dataset node ids, each a row of this rank (repeats
+ * allowed); NULL: every row of this rank in local-row order (gcnhost_model_row_ids names them).  pred / prob [n]; logp
+ * (may be NULL) [n x output_dim] the log-softmax rows.  Several ranks: every rank calls it (the logit aggregation exchanges
+ * rows).  Training state is not touched: a train_epoch after it gives the same bits as one without it.  Synchronises. */
+int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pred, float *prob, float *logp);
+/* The weights file: "GCNW", format version, input / hidden / output widths (int32), W1 [F x h], W2 [h x C] (f32 row-major),
+ * CRC-32; little-endian (host/weights.h).  save writes this model's W1, W2 (several ranks hold the same weights: one of them
+ * writes).  load refuses a file whose widths differ from the model's (an error with a message, never a reshape) and goes
+ * through gcnhost_model_set_weights.  Adam's moments and step count are not in the file: a loaded model that trains further
+ * starts Adam afresh. */
+int gcnhost_model_save_weights(gcnhost_model *m, const char *path);
+int gcnhost_model_load_weights(gcnhost_model *m, const char *path);
+/* the same file from the host alone (no GPU).  read: w1 == w2 == NULL reports the file's widths; otherwise the widths passed
+ * in are those of the caller's buffers and must equal the file's.  A truncated or damaged file, a wrong magic or version is
+ * an error (gcnhost_last_error). */
+int gcnhost_weights_write(const char *path, int input_dim, int hidden_dim, int output_dim, const float *w1, const float *w2);
+int gcnhost_weights_read(const char *path, int *input_dim, int *hidden_dim, int *output_dim, float *w1, float *w2);
 /* device-event timer `id` (host/timer.h, ids of src/common/timer.h:5-20 plus 13 Adam, 14 comm,
  * 15 GraphSum at the hidden width): accumulated seconds and number of intervals */
 int gcnhost_model_timer(gcnhost_model *m, int id, double *seconds, long *count);
