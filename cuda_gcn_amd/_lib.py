@@ -168,6 +168,8 @@ GCNHIP_SYMBOLS = {
     "gcnhip_stream_wait_event": (I, [P, P]),
     "gcnhip_event_elapsed_ms": (I, [P, P, C.POINTER(F)]),
     "gcnhip_event_sync": (I, [P]),
+    "gcnhip_bce_fwd_rows": (I, [P, P, I, P, I, P, I, P, I, I, I, I, P, P, P]),
+    "gcnhip_bce_predict_rows": (I, [P, P, I, P, I, I, P, I, P, I]),
 }
 
 
@@ -193,6 +195,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_nccl_unique_id": (I, [C.c_char_p]),
     "gcnhost_model_create": (I, [PP, C.POINTER(HostParams), P, P, P, P, P, P, P, C.c_long, I, I, I, I, C.c_char_p,
                                  ALLGATHER_FN, ALLREDUCE_FN, P]),
+    "gcnhost_model_create_multilabel": (I, [PP, C.POINTER(HostParams), P, P, P, P, P, P, P, P, C.c_long, I, I, I, I, C.c_char_p,
+                                            ALLGATHER_FN, ALLREDUCE_FN, P]),
     "gcnhost_model_destroy": (I, [P]),
     "gcnhost_model_train_epoch": (I, [P, C.POINTER(F), C.POINTER(F)]),
     "gcnhost_model_eval": (I, [P, I, C.POINTER(F), C.POINTER(F)]),
@@ -208,6 +212,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_get_var": (I, [P, I, I, P, C.POINTER(I), C.POINTER(I)]),
     "gcnhost_model_set_weights": (I, [P, P, P]),
     "gcnhost_model_predict": (I, [P, P, I, P, P, P]),
+    "gcnhost_model_predict_multilabel": (I, [P, P, I, P, P]),
+    "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),
     "gcnhost_model_save_weights": (I, [P, C.c_char_p]),
     "gcnhost_model_load_weights": (I, [P, C.c_char_p]),
     "gcnhost_weights_write": (I, [C.c_char_p, I, I, I, P, P]),

@@ -240,6 +240,7 @@ __attribute__((visibility("hidden"))) int gcnhip_preload_graphsum();
 __attribute__((visibility("hidden"))) int gcnhip_preload_matmul();
 __attribute__((visibility("hidden"))) int gcnhip_preload_spmm();
 __attribute__((visibility("hidden"))) int gcnhip_preload_xent();
+__attribute__((visibility("hidden"))) int gcnhip_preload_bce();
 #define GCNHIP_DEFINE_PRELOAD(NAME, KERNEL)                                      \
     int gcnhip_preload_##NAME() {                                                \
         hipFuncAttributes attr;                                                  \

@@ -107,6 +107,7 @@ int gcnhip_ctx_create(gcnhip_ctx **out, int device, void *stream) {
                 GCNHIP_TRY((hipError_t)gcnhip_preload_matmul());
                 GCNHIP_TRY((hipError_t)gcnhip_preload_spmm());
                 GCNHIP_TRY((hipError_t)gcnhip_preload_xent());
+                GCNHIP_TRY((hipError_t)gcnhip_preload_bce());
                 preloaded[device] = true;
             }
         }

@@ -306,3 +306,31 @@ def planted_communities(n_comm=16, size=512, deg=16, p_in=0.95, feats=32, classe
     return dict(name="planted", num_nodes=N, input_dim=feats, output_dim=classes, g_indptr=g_indptr, g_indices=g_indices,
                 f_indptr=(np.arange(N + 1, dtype=np.int64) * feats).astype(np.int32), f_indices=np.tile(np.arange(feats, dtype=np.int32), N),
                 f_val=f_val.reshape(-1), split=split, label=label)
+
+
+def multilabel_from_communities(comm, classes=121, per_comm=3, p_extra=0.02, seed=DEFAULT_SEED):
+    """A multi-hot truth [N, classes] (bool) that the graph can teach: community k owns a fixed set of `per_comm` classes —
+    class k % classes and per_comm - 1 more drawn once per community — and every node carries its community's set plus random
+    extra classes, each with probability p_extra (noise no model can learn).  Deterministic in (comm, classes, per_comm,
+    p_extra, seed)."""
+    comm = np.asarray(comm, np.int64)
+    rng = np.random.default_rng(seed)
+    n_comm = int(comm.max()) + 1 if comm.size else 0
+    owned = np.zeros((n_comm, classes), bool)
+    owned[np.arange(n_comm), np.arange(n_comm) % classes] = True
+    for k in range(n_comm):
+        if per_comm > 1:
+            owned[k, rng.choice(classes, size=min(per_comm - 1, classes), replace=False)] = True
+    y = owned[comm] if n_comm else np.zeros((0, classes), bool)
+    return y | (rng.random((comm.size, classes)) < p_extra)
+
+
+def planted_multilabel(n_comm=16, size=512, deg=16, p_in=0.95, feats=32, classes=41, per_comm=3, p_extra=0.02,
+                       seed=DEFAULT_SEED, shuffle=True):
+    """planted_communities with a multi-label truth (multilabel_from_communities of the community of every node) in
+    ds["multilabel"] (bool [N, classes]); ds["label"] stays the community's single class (the schedule hint reads it)."""
+    ds = planted_communities(n_comm=n_comm, size=size, deg=deg, p_in=p_in, feats=feats, classes=n_comm, seed=seed, shuffle=shuffle)
+    ds["multilabel"] = multilabel_from_communities(ds["label"], classes=classes, per_comm=per_comm, p_extra=p_extra, seed=seed + 1)
+    ds["output_dim"] = classes
+    ds["name"] = "planted-multilabel"
+    return ds

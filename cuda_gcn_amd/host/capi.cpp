@@ -8,6 +8,7 @@
 #include "cluster.h"
 #include "hip_check.h"
 #include "parser.h"
+#include "labels.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -45,13 +46,12 @@ gcnhost_params gcnhost_params_default(void) {
 
 int gcnhost_nccl_unique_id(char id[GCNHOST_NCCL_ID_BYTES]) { return rccl_get_unique_id(id); }
 
-int gcnhost_model_create(gcnhost_model **out, const gcnhost_params *p,
-                         const int *g_indptr, const int *g_indices,
-                         const int *f_indptr, const int *f_indices, const float *f_val,
-                         const int *split, const int *label,
-                         long seed, int device, int flags, int rank, int world, const char *nccl_id,
-                         gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
-    if (!out || !p || !g_indptr || !g_indices || !f_indptr || !f_val || !split || !label) { g_err = "null argument"; return -1; }
+static int model_create(gcnhost_model **out, const gcnhost_params *p,
+                        const int *g_indptr, const int *g_indices,
+                        const int *f_indptr, const int *f_indices, const float *f_val,
+                        const int *split, const int *label, const uint32_t *multihot,
+                        long seed, int device, int flags, int rank, int world, const char *nccl_id,
+                        gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
     API_TRY({
         gcnhost_model *m = new gcnhost_model();
         const int N = p->num_nodes;
@@ -61,7 +61,9 @@ int gcnhost_model_create(gcnhost_model **out, const gcnhost_params *p,
         if (f_indices) m->data.feature_index.indices.assign(f_indices, f_indices + f_indptr[N]);
         m->data.feature_value.assign(f_val, f_val + f_indptr[N]);
         m->data.split.assign(split, split + N);
-        m->data.label.assign(label, label + N);
+        if (label) m->data.label.assign(label, label + N);
+        else m->data.label.assign(N, -1);
+        if (multihot) m->data.multihot.assign(multihot, multihot + (size_t)N * ((p->output_dim + 31) / 32));
         GCNParams gp;
         static_assert(sizeof(GCNParams) == sizeof(gcnhost_params), "params layout");
         memcpy(&gp, p, sizeof gp);
@@ -69,6 +71,7 @@ int gcnhost_model_create(gcnhost_model **out, const gcnhost_params *p,
         o.device = device; o.seed = seed; o.flags = flags; o.rank = rank; o.world = world; o.nccl_id = nccl_id;
         o.host_allgather = host_ag; o.host_allreduce = host_ar; o.host_user = host_user;
         o = HipGCNOptions::from_environment(o);                 // every HIPGCN_* variable, read once (host/options.cpp)
+        o.multilabel = multihot != nullptr;
         try {
             m->gcn = new HipGCN(gp, &m->data, o);
         } catch (...) {
@@ -77,6 +80,29 @@ int gcnhost_model_create(gcnhost_model **out, const gcnhost_params *p,
         }
         *out = m;
     })
+}
+
+int gcnhost_model_create(gcnhost_model **out, const gcnhost_params *p,
+                         const int *g_indptr, const int *g_indices,
+                         const int *f_indptr, const int *f_indices, const float *f_val,
+                         const int *split, const int *label,
+                         long seed, int device, int flags, int rank, int world, const char *nccl_id,
+                         gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
+    if (!out || !p || !g_indptr || !g_indices || !f_indptr || !f_val || !split || !label) { g_err = "null argument"; return -1; }
+    return model_create(out, p, g_indptr, g_indices, f_indptr, f_indices, f_val, split, label, nullptr, seed, device, flags, rank, world,
+                        nccl_id, host_ag, host_ar, host_user);
+}
+
+int gcnhost_model_create_multilabel(gcnhost_model **out, const gcnhost_params *p,
+                                    const int *g_indptr, const int *g_indices,
+                                    const int *f_indptr, const int *f_indices, const float *f_val,
+                                    const int *split, const int *label, const uint32_t *multihot,
+                                    long seed, int device, int flags, int rank, int world, const char *nccl_id,
+                                    gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
+    if (!out || !p || !g_indptr || !g_indices || !f_indptr || !f_val || !split || !multihot) { g_err = "null argument"; return -1; }
+    if (p->output_dim < 1 || p->output_dim > 256) { g_err = "multi-label mode takes 1 to 256 classes"; return -1; }
+    return model_create(out, p, g_indptr, g_indices, f_indptr, f_indices, f_val, split, label, multihot, seed, device, flags, rank, world,
+                        nccl_id, host_ag, host_ar, host_user);
 }
 
 int gcnhost_model_destroy(gcnhost_model *m) {
@@ -159,6 +185,19 @@ int gcnhost_model_get_var(gcnhost_model *m, int k, int grad, float *out, int *ro
 int gcnhost_model_set_weights(gcnhost_model *m, const float *w1, const float *w2) { API_TRY({ m->gcn->set_weights(w1, w2); }) }
 int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
     API_TRY({ m->gcn->predict(nodes, n, pred, prob, logp); })
+}
+int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob) {
+    API_TRY({ m->gcn->predict_multilabel(nodes, n, bits, prob); })
+}
+int gcnhost_labels_read(const char *path, int *num_nodes, int *num_classes, uint32_t *bits) {
+    if (!path || !num_nodes || !num_classes) { g_err = "gcnhost_labels_read: invalid argument"; return -1; }
+    std::vector<uint32_t> b;
+    int n = *num_nodes, c = *num_classes;
+    if (gcn_labels_read(path, &n, &c, b, &g_err) != 0) return -1;
+    *num_nodes = n;
+    *num_classes = c;
+    if (bits) memcpy(bits, b.data(), b.size() * sizeof(uint32_t));
+    return 0;
 }
 int gcnhost_model_save_weights(gcnhost_model *m, const char *path) {
     if (!m || !path) { g_err = "gcnhost_model_save_weights: invalid argument"; return -1; }

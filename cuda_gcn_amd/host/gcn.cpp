@@ -74,6 +74,11 @@ void HipGCN::init(const HipGCNOptions &opt) {
     if ((int)data->graph.indptr.size() != params.num_nodes + 1 || (int)data->split.size() != params.num_nodes ||
         (int)data->label.size() != params.num_nodes || (int)data->feature_index.indptr.size() != params.num_nodes + 1)
         throw GcnHipFailure(-1, "HipGCN: GCNData arrays do not match num_nodes");
+    if (opt.multilabel) {
+        if (params.output_dim > 256) throw GcnHipFailure(-1, "HipGCN: multi-label mode takes at most 256 classes");
+        if (data->multihot.size() != (size_t)params.num_nodes * ((params.output_dim + 31) / 32))
+            throw GcnHipFailure(-1, "HipGCN: the multi-hot label matrix does not hold num_nodes rows of ceil(output_dim / 32) words");
+    }
     GCNHIP_CHECK(gcnhip_ctx_create(&env.ctx, opt.device, nullptr));
     if (opt.gemm >= 0) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gemm_bf16x3", opt.gemm ? 2 : 0));   // HIPGCN_GEMM; else the library's default
     if (opt.fold_training) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gs_fold", 1));                  // (ignored by a library built without the experiments)
@@ -205,13 +210,19 @@ void HipGCN::init(const HipGCNOptions &opt) {
         gcnhip_free(env.ctx, d_label);
         env.comm->allreduce_sum_host(cnt, 4);
         for (int s = 1; s <= 3; s++) split_count[s] = (int)cnt[s];
+        if (opt.multilabel) {                          // this rank's rows, in the (possibly renumbered) row order of `data`
+            ml_wpr = (C + 31) / 32;
+            std::vector<uint32_t> mine(data->multihot.begin() + (size_t)r0 * ml_wpr, data->multihot.begin() + (size_t)r1 * ml_wpr);
+            if (mine.empty()) mine.assign(ml_wpr, 0u);
+            d_ml_truth = dev_upload(env.ctx, mine.data(), mine.size());
+        }
     }
 
     // The last aggregation of a forward computes only the rows the loss and the accuracy read
     // (CrossEntropyLoss::forward skips truth < 0, module.cpp:131-133; get_accuracy, gcn.cpp:86-88):
     // one registered row subset per split.
     if (!(flags & HIPGCN_ALL_ROWS)) add_split_rowsets(env.ctx, graph, split_rows);
-    if (!(flags & HIPGCN_MODULAR)) {
+    if (!(flags & HIPGCN_MODULAR) || opt.multilabel) {
         // the loss walks the rows of the scored split only (it skips the others anyway, module.cpp:131-133)
         for (int s = 1; s <= 3; s++) {
             std::vector<int32_t> rows;
@@ -271,7 +282,7 @@ void HipGCN::init(const HipGCNOptions &opt) {
         W1->grad = gradbuf; W1->requires_grad = true;
         W2->grad = gradbuf + W1->elems(); W2->requires_grad = true;
         d_result = gradbuf + W1->elems() + W2->elems();
-        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &q, 2 * sizeof(int32_t)));
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &q, 4 * sizeof(int32_t)));    // {correct, total}, or the multi-label {TP, FP, FN, rows}
         d_result_i = (int32_t *)q;
         GCNHIP_CHECK(gcnhip_malloc(env.ctx, &q, (size_t)RING * 4 * 8 * sizeof(float)));
         d_ring = (float *)q;
@@ -402,6 +413,13 @@ void HipGCN::renumber_nodes(int world) {
         if (n && !fi.empty()) memcpy(&d.feature_index.indices[dst], &fi[(size_t)fp[o]], n * sizeof(int));
         d.split[k] = data->split[o];
         d.label[k] = data->label[o];
+    }
+    if (!data->multihot.empty()) {                     // multi-label rows follow their node
+        const size_t wpr = data->multihot.size() / N;
+        d.multihot.resize(data->multihot.size());
+        for (int k = 0; k < N; k++)
+            std::copy(data->multihot.begin() + (size_t)ch.order[k] * wpr, data->multihot.begin() + ((size_t)ch.order[k] + 1) * wpr,
+                      d.multihot.begin() + (size_t)k * wpr);
     }
     node_order_ = std::move(ch.order);
     node_order_name_ = ch.name;
@@ -597,6 +615,11 @@ void HipGCN::build_modules() {
         modules.push_back(new HipDropout(&env, H1, p, KEY_HIDDEN_DROPOUT, hid_off, (flags & HIPGCN_HOST_MASKS) ? &env.keep_hidden : &no_mask));
         modules.push_back(new HipMatmul(&env, H1, W2, Z0, N, H, C));
         { auto *gs = new HipGraphSum(&env, Z0, Z, graph, C); gs->bwd_row_bits = &bwd_bits; gs->bwd_graph = graph_bwd_out; gs->fwd_out_rows = &cur_out_rows; wire_overlap(gs, true); modules.push_back(gs); logits_gs = gs; }
+        if (opt_.multilabel) {
+            auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
+            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
+            modules.push_back(bce);
+        } else
         modules.push_back(new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, true));
     } else {
         const float scale = 1 / (1 - p);
@@ -652,6 +675,13 @@ void HipGCN::build_modules() {
             modules.push_back(gs);
             gs_logits = gs;
             logits_gs = gs;
+        }
+        if (opt_.multilabel) {                         // the loss kernel on the stored logits (no loss epilogue)
+            auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
+            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
+            if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &bce->grad_row_scale, nullptr, nullptr, nullptr));
+            modules.push_back(bce);
+            return;
         }
         auto *ce = new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, false);
         ce->rows_list = &cur_rows; ce->rows_n = &cur_rows_n;
@@ -770,7 +800,7 @@ void HipGCN::build_eval_lane() {
     L.env.d_epoch = (uint32_t *)q;
     GCNHIP_CHECK(gcnhip_memset_async(L.env.ctx, q, 0xFF, sizeof(uint32_t)));
     GCNHIP_CHECK(gcnhip_malloc(L.env.ctx, &q, 4 * sizeof(float))); L.d_result = (float *)q;
-    GCNHIP_CHECK(gcnhip_malloc(L.env.ctx, &q, 2 * sizeof(int32_t))); L.d_result_i = (int32_t *)q;
+    GCNHIP_CHECK(gcnhip_malloc(L.env.ctx, &q, 4 * sizeof(int32_t))); L.d_result_i = (int32_t *)q;
     // same adjacency, own scratch for split rows: a device-side clone of the training lane's object, in the row schedule that
     // lane measured as fastest (round 4: rebuilding it from the host lists was 0.67 s of a 1.8 s model build at Reddit scale)
     const std::vector<int> &gp = data->graph.indptr, &gi = data->graph.indices;
@@ -819,7 +849,11 @@ void HipGCN::build_eval_lane() {
     gs_logits->fwd_out_rows = &L.out_rows;
     if (factored_) gs_logits->fwd_scaling = 1;
     L.modules.push_back(gs_logits);
-    {
+    if (opt_.multilabel) {
+        auto *bce = new HipBCELoss(&L.env, L.Z.get(), d_ml_truth, ml_wpr, &L.count, L.d_result, L.d_result_i, C);
+        bce->rows_list = &L.rows; bce->rows_n = &L.rows_n;
+        L.modules.push_back(bce);
+    } else {
         auto *ce = new HipCrossEntropyLoss(&L.env, L.Z.get(), &L.truth, &L.count, L.d_result, L.d_result_i, C, false);
         ce->rows_list = &L.rows; ce->rows_n = &L.rows_n;
         if (opt_.loss_epilogue && C <= 64 && !L.env.bf16_tables) {     // as on the training context
@@ -889,6 +923,8 @@ void HipGCN::release() {
     if (feat_agg) gcnhip_feat_destroy(env.ctx, feat_agg);
     if (graph_l1) gcnhip_graph_destroy(env.ctx, graph_l1);
     for (int s = 1; s <= 3; s++) gcnhip_free(env.ctx, d_truth[s]);
+    gcnhip_free(env.ctx, d_ml_truth); gcnhip_free(env.ctx, d_ml_logits); gcnhip_free(env.ctx, d_ml_bits);
+    gcnhip_free(env.ctx, d_ml_prob); gcnhip_free(env.ctx, d_ml_rows);
     gcnhip_free(env.ctx, gradbuf);
     gcnhip_free(env.ctx, d_result_i);
     gcnhip_free(env.ctx, d_ring);
@@ -1099,8 +1135,14 @@ std::pair<float, float> HipGCN::read_metrics(long epoch_index, int slot) {
     if (lane) GCNHIP_CHECK(gcnhip_ctx_sync(lane->env.ctx));
     const uint32_t e = (uint32_t)epoch_index;   // epoch_index == -1 (eval before any training) wraps like the device word
     GCNHIP_CHECK(gcnhip_d2h(env.ctx, row, d_ring + ((size_t)(e % RING) * 4 + slot) * 8, sizeof row));
-    const float loss = row[0] / (int)row[1];                                    // module.cpp:154
+    return ring_metrics(row);
+}
+
+std::pair<float, float> HipGCN::ring_metrics(const float *row) const {
     const float l2 = params.weight_decay * row[4] / 2;                          // gcn.cpp:104
+    if (opt_.multilabel)                                                        // {loss_sum, rows * C, 2 TP, 2 TP + FP + FN}
+        return {row[0] / row[1] + l2, row[3] > 0.f ? row[2] / row[3] : 0.f};
+    const float loss = row[0] / (int)row[1];                                    // module.cpp:154
     const float acc = (float)row[2] / (int)row[3];                              // gcn.cpp:95
     return {loss + l2, acc};
 }
@@ -1174,8 +1216,9 @@ void HipGCN::run_epochs(int n, float *trace) {
                 const uint32_t e = (uint32_t)(first + i);
                 for (int slot = 0; slot < 2; slot++) {
                     const float *row = &ring[((size_t)(e % RING) * 4 + slot) * 8];
-                    trace[(size_t)(done + i) * 4 + slot * 2] = row[0] / (int)row[1] + params.weight_decay * row[4] / 2;
-                    trace[(size_t)(done + i) * 4 + slot * 2 + 1] = (float)row[2] / (int)row[3];
+                    const std::pair<float, float> m = ring_metrics(row);
+                    trace[(size_t)(done + i) * 4 + slot * 2] = m.first;
+                    trace[(size_t)(done + i) * 4 + slot * 2 + 1] = m.second;
                 }
             }
         }
@@ -1303,10 +1346,12 @@ void HipGCN::run_pipelined() {
         const float dt = (float)(dt_group / g.n);
         for (int i = 0; i < g.n; i++) {
             const float *tr = R.host + ((size_t)g.slot * READBACK_GROUP_MAX + i) * 32, *va = tr + 8;
-            const float train_loss = tr[0] / (int)tr[1] + params.weight_decay * tr[4] / 2, train_acc = (float)tr[2] / (int)tr[3];
-            const float val_loss = va[0] / (int)va[1] + params.weight_decay * va[4] / 2, val_acc = (float)va[2] / (int)va[3];
+            float train_loss, train_acc, val_loss, val_acc;
+            std::tie(train_loss, train_acc) = ring_metrics(tr);
+            std::tie(val_loss, val_acc) = ring_metrics(va);
             if (talk)
-                printf("epoch=%ld train_loss=%.5f train_acc=%.5f val_loss=%.5f val_acc=%.5f time=%.5f\n",
+                printf(opt_.multilabel ? "epoch=%ld train_loss=%.5f train_f1=%.5f val_loss=%.5f val_f1=%.5f time=%.5f\n"
+                                       : "epoch=%ld train_loss=%.5f train_acc=%.5f val_loss=%.5f val_acc=%.5f time=%.5f\n",
                        g.e0 + i + 1, train_loss, train_acc, val_loss, val_acc, dt);
         }
         printed += g.n;
@@ -1341,7 +1386,8 @@ void HipGCN::run_synchronous() {
         const float dt = std::chrono::duration_cast<std::chrono::duration<float>>(std::chrono::high_resolution_clock::now() - t0).count();
         total_train += dt;
         if (talk)
-            printf("epoch=%d train_loss=%.5f train_acc=%.5f val_loss=%.5f val_acc=%.5f time=%.5f\n",
+            printf(opt_.multilabel ? "epoch=%d train_loss=%.5f train_f1=%.5f val_loss=%.5f val_f1=%.5f time=%.5f\n"
+                                   : "epoch=%d train_loss=%.5f train_acc=%.5f val_loss=%.5f val_acc=%.5f time=%.5f\n",
                    epoch, train_loss, train_acc, val_loss, val_acc, dt);
         loss_history.push_back(val_loss);
         if (params.early_stopping > 0 && epoch >= params.early_stopping) {
@@ -1362,7 +1408,7 @@ void HipGCN::report_test() {
     auto t0 = std::chrono::high_resolution_clock::now();
     std::tie(test_loss, test_acc) = eval(3);
     const float dt = std::chrono::duration_cast<std::chrono::duration<float>>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (talk) printf("test_loss=%.5f test_acc=%.5f time=%.5f\n", test_loss, test_acc, dt);
+    if (talk) printf(opt_.multilabel ? "test_loss=%.5f test_f1=%.5f time=%.5f\n" : "test_loss=%.5f test_acc=%.5f time=%.5f\n", test_loss, test_acc, dt);
 }
 
 void HipGCN::get_var(int k, bool grad, std::vector<float> &out, int *rows, int *cols) {
@@ -1393,44 +1439,53 @@ void HipGCN::set_weights(const float *w1, const float *w2) {
 
 // ---- prediction and the weights file (beyond the reference) ------------------------------------------------------------
 
+// dataset node ids -> local rows of this rank (node_order() undone); NULL: every local row
+void HipGCN::query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows) {
+    const int N = params.num_nodes;
+    rows.resize(n);
+    if (!nodes) {
+        for (int i = 0; i < n; i++) rows[i] = i;
+        return;
+    }
+    std::vector<int> pos;
+    if (!node_order_.empty()) {
+        pos.assign(N, -1);
+        for (int p = 0; p < N; p++) pos[node_order_[p]] = p;
+    }
+    const int r0 = row_start();
+    for (int i = 0; i < n; i++) {
+        const int id = nodes[i];
+        if (id < 0 || id >= N) throw GcnHipFailure(-1, std::string(what) + ": node " + std::to_string(id) + " is not a node of the dataset (0.." + std::to_string(N - 1) + ")");
+        const int r = (pos.empty() ? id : pos[id]) - r0;
+        if (r < 0 || r >= n_local)
+            throw GcnHipFailure(-1, std::string(what) + ": node " + std::to_string(id) + " is not a row of rank " + std::to_string(env.comm->rank()) + " (each rank predicts its own rows)");
+        rows[i] = r;
+    }
+}
+
+// a registered subset of `graph` holding these rows: the same query reuses it
+const gcnhip_rowset *HipGCN::query_subset(const std::vector<int> &rows) {
+    std::vector<uint32_t> bits(((size_t)n_local + 31) / 32 + 1, 0u);
+    for (int r : rows) bits[r >> 5] |= 1u << (r & 31);
+    if (!pred_rows || bits != pred_bits) {
+        if (pred_rows) { GCNHIP_CHECK(gcnhip_graph_remove_rowset(env.ctx, graph, pred_rows)); pred_rows = nullptr; }
+        GCNHIP_CHECK(gcnhip_graph_add_rowset(env.ctx, graph, bits.data(), &pred_rows));
+        pred_bits.swap(bits);
+    }
+    return pred_rows;
+}
+
 void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
-    const int N = params.num_nodes, C = params.output_dim;
+    const int C = params.output_dim;
+    if (opt_.multilabel) throw GcnHipFailure(-1, "predict: this is a multi-label model: use predict_multilabel");
     if (!logits_gs) throw GcnHipFailure(-1, "predict: this model has no class-width aggregation");
     if (C > 64) throw GcnHipFailure(-1, "predict: at most 64 classes (the logit row of a node sits in one wave)");
     if ((n > 0 && (!pred || !prob)) || n < 0) throw GcnHipFailure(-1, "predict: invalid argument");
     if (!nodes) n = n_local;
-    // dataset node id -> local row of this rank
-    std::vector<int> rows(n);
-    if (nodes) {
-        std::vector<int> pos;
-        if (!node_order_.empty()) {
-            pos.assign(N, -1);
-            for (int p = 0; p < N; p++) pos[node_order_[p]] = p;
-        }
-        const int r0 = row_start();
-        for (int i = 0; i < n; i++) {
-            const int id = nodes[i];
-            if (id < 0 || id >= N) throw GcnHipFailure(-1, "predict: node " + std::to_string(id) + " is not a node of the dataset (0.." + std::to_string(N - 1) + ")");
-            const int r = (pos.empty() ? id : pos[id]) - r0;
-            if (r < 0 || r >= n_local)
-                throw GcnHipFailure(-1, "predict: node " + std::to_string(id) + " is not a row of rank " + std::to_string(env.comm->rank()) + " (each rank predicts its own rows)");
-            rows[i] = r;
-        }
-    } else {
-        for (int i = 0; i < n; i++) rows[i] = i;
-    }
+    std::vector<int> rows;
+    query_rows("predict", nodes, n, rows);
     sync();                                                    // run()'s epochs in flight, the validation lane's pass
-    const gcnhip_rowset *subset = nullptr;
-    if (nodes) {                                               // a registered subset of `graph`: the same query reuses it
-        std::vector<uint32_t> bits(((size_t)n_local + 31) / 32 + 1, 0u);
-        for (int r : rows) bits[r >> 5] |= 1u << (r & 31);
-        if (!pred_rows || bits != pred_bits) {
-            if (pred_rows) { GCNHIP_CHECK(gcnhip_graph_remove_rowset(env.ctx, graph, pred_rows)); pred_rows = nullptr; }
-            GCNHIP_CHECK(gcnhip_graph_add_rowset(env.ctx, graph, bits.data(), &pred_rows));
-            pred_bits.swap(bits);
-        }
-        subset = pred_rows;
-    }
+    const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
     const size_t nl = (size_t)std::max(n_local, 1);
     if (!d_pred) {
         void *p;
@@ -1472,6 +1527,56 @@ void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float 
         prob[i] = hq[rows[i]];
         if (logp) std::copy(hl.begin() + (size_t)rows[i] * C, hl.begin() + (size_t)(rows[i] + 1) * C, logp + (size_t)i * C);
     }
+}
+
+void HipGCN::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob) {
+    const int C = params.output_dim;
+    if (!opt_.multilabel) throw GcnHipFailure(-1, "predict_multilabel: this is a single-label model: use predict");
+    if (!logits_gs) throw GcnHipFailure(-1, "predict_multilabel: this model has no class-width aggregation");
+    if ((n > 0 && !bits) || n < 0) throw GcnHipFailure(-1, "predict_multilabel: invalid argument");
+    if (!nodes) n = n_local;
+    std::vector<int> rows;
+    query_rows("predict_multilabel", nodes, n, rows);
+    sync();
+    const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
+    HipVariable *Z = variables[6].get();
+    const size_t nl = (size_t)std::max(n_local, 1), nq = (size_t)std::max(n, 1);
+    if (!d_ml_logits) {
+        void *p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * Z->ld * sizeof(float)));
+        GCNHIP_CHECK(gcnhip_memset_async(env.ctx, p, 0, nl * Z->ld * sizeof(float)));
+        d_ml_logits = (float *)p;
+    }
+    if (nq > ml_query_cap) {
+        gcnhip_free(env.ctx, d_ml_bits); gcnhip_free(env.ctx, d_ml_prob); gcnhip_free(env.ctx, d_ml_rows);
+        d_ml_bits = nullptr; d_ml_prob = nullptr; d_ml_rows = nullptr;
+        void *p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nq * ml_wpr * sizeof(uint32_t))); d_ml_bits = (uint32_t *)p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nq * C * sizeof(float))); d_ml_prob = (float *)p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nq * sizeof(int32_t))); d_ml_rows = (int32_t *)p;
+        ml_query_cap = nq;
+    }
+    // an evaluation forward (eval_async's module list without the loss) on the main stream; the logit aggregation stores the
+    // requested rows into the scratch table instead of variable 6
+    if (flags & HIPGCN_MODULAR)
+        GCNHIP_CHECK(gcnhip_d2d_async(env.ctx, input->data, gcnhip_feat_values(feat), (size_t)gcnhip_feat_nnz(feat) * sizeof(float)));
+    HipGraphSum::Redirect req;
+    req.data = d_ml_logits; req.ld = Z->ld; req.rows = subset;
+    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
+    logits_gs->redirect = &req;
+    try {
+        for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);       // the last module is the loss
+    } catch (...) {
+        logits_gs->redirect = nullptr;
+        throw;
+    }
+    logits_gs->redirect = nullptr;
+    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+    if (n == 0) { sync(); return; }
+    GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_ml_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_bce_predict_rows(env.ctx, d_ml_logits, Z->ld, d_ml_rows, n, C, d_ml_bits, ml_wpr, prob ? d_ml_prob : nullptr, C));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, bits, d_ml_bits, (size_t)n * ml_wpr * sizeof(uint32_t)));
+    if (prob) GCNHIP_CHECK(gcnhip_d2h(env.ctx, prob, d_ml_prob, (size_t)n * C * sizeof(float)));
 }
 
 void HipGCN::save_weights(const char *path) {

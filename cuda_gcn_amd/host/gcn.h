@@ -28,6 +28,9 @@ public:
     std::vector<int> split;
     std::vector<int> label;
     std::vector<float> feature_value;
+    // multi-label truth (beyond the reference): num_nodes rows of ceil(output_dim / 32) words, bit (c & 31) of word c >> 5 =
+    // class c (host/labels.h).  Read by HipGCN only when HipGCNOptions::multilabel is set; `label` is then unused for the loss.
+    std::vector<uint32_t> multihot;
 };
 
 enum HipGCNFlags {
@@ -105,6 +108,10 @@ struct HipGCNOptions {
     // HIPGCN_GEMM=f32|bf16x3: arithmetic of the dense first-layer products (0: exact-f32 MFMA, 1: three-plane bf16 split on the
     // bf16 MFMA pipe, same f32 error bound; -1: the library's default)
     int gemm = -1;
+    // Multi-label mode (beyond the reference; chosen here, never from the environment): the truth is GCNData::multihot, the loss
+    // the per-class sigmoid cross-entropy on the stored logits (gcnhip_bce_fwd_rows), and the accuracy column of every metric
+    // micro-F1.  1 <= output_dim <= 256.
+    bool multilabel = false;
 
     // `base` with every HIPGCN_* variable of the process environment applied (flag variables OR their bit in)
     static HipGCNOptions from_environment(HipGCNOptions base);
@@ -172,6 +179,12 @@ public:
     // the logits (variable 6) and the captured epoch graph are left as they were; a train_epoch() after it has the
     // same bits as one without it.  Synchronises.
     void predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp);
+    // Multi-label prediction, the same contract as predict() (dataset ids, NULL = every row of this rank, a collective, training
+    // state untouched, synchronises): one evaluation forward whose logits go to scratch (not variable 6), then
+    // gcnhip_bce_predict_rows.  bits [n x ceil(C / 32)]: bit (c & 31) of word c >> 5 = (z_c > 0); prob (may be NULL) [n x C] =
+    // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
+    void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
+    bool multilabel() const { return opt_.multilabel; }
     // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
     // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
     // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
@@ -244,6 +257,16 @@ private:
     int32_t *d_result_i = nullptr;
     int32_t *d_truth[4] = {};                                  // per split code 1..3
     int32_t *cur_truth = nullptr;
+    uint32_t *d_ml_truth = nullptr;                            // multi-label: this rank's rows of GCNData::multihot
+    int ml_wpr = 0;
+    float *d_ml_logits = nullptr;                              // predict_multilabel: scratch logits [local rows x ld of Z]
+    uint32_t *d_ml_bits = nullptr;
+    float *d_ml_prob = nullptr;
+    int32_t *d_ml_rows = nullptr;
+    size_t ml_query_cap = 0;
+    std::pair<float, float> ring_metrics(const float *row) const;   // (loss + L2, accuracy or micro-F1) of a metrics-ring row
+    void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows (predict*)
+    const gcnhip_rowset *query_subset(const std::vector<int> &rows);
     std::unique_ptr<BackwardPipeline> bwd_pipe;                 // hidden-layer backward aggregation || dW1 product, in row blocks
     void build_bwd_pipeline(HipSparseMatmul *sm, HipGraphSum *gs);
     void destroy_bwd_pipeline();

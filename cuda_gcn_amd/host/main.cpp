@@ -39,6 +39,12 @@
 //                            (class = argmax of the node's logits, lowest on a tie; its softmax probability).  With several
 //                            GPUs each worker predicts its own rows into an array indexed by node id; the file is written
 //                            after the join.
+// Multi-label training (beyond the reference):
+//   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
+//                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
+//                            the per-class sigmoid cross-entropy; the lines carry train_f1= / val_f1= / test_f1= (micro-F1) in
+//                            place of the _acc fields.  GCN_PREDICT then writes `node c1,c2,...` per node (the classes whose
+//                            logit is above 0; the node alone for an empty set).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +57,7 @@
 #include <vector>
 #include "gcn.h"
 #include "hip_check.h"
+#include "labels.h"
 #include "parser.h"
 
 static int env_int(const char *name, int dflt) {
@@ -90,6 +97,21 @@ int main(int argc, char **argv) {
     if (ARG(8)) params.weight_decay = (float)atof(argv[8]);
     if (ARG(9)) params.epochs = atoi(argv[9]);
     if (ARG(10)) params.early_stopping = atoi(argv[10]);
+    const char *multilabel_path = getenv("GCN_MULTILABEL");
+    if (multilabel_path && !*multilabel_path) multilabel_path = nullptr;
+    if (multilabel_path) {
+        int n = params.num_nodes, c = 0;
+        std::string err;
+        if (gcn_labels_read(multilabel_path, &n, &c, data.multihot, &err) != 0) {
+            std::cerr << "gcn-hip: GCN_MULTILABEL: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (c > 256) {
+            std::cerr << "gcn-hip: GCN_MULTILABEL: " << c << " classes; multi-label mode takes at most 256" << std::endl;
+            return EXIT_FAILURE;
+        }
+        params.output_dim = c;
+    }
 
     int n_dev = 0;
     if (gcnhip_device_count(&n_dev) != 0 || n_dev < 1) {
@@ -115,6 +137,7 @@ int main(int argc, char **argv) {
     if (env_int("GCN_REFERENCE_ORDER", feedback ? 1 : 0)) base.flags |= HIPGCN_NO_AGG_FIRST_EVAL;
     if (env_int("GCN_SYNC_EPOCHS", 0)) base.flags |= HIPGCN_SYNC_EPOCHS;
     base = HipGCNOptions::from_environment(base);             // every HIPGCN_* variable, read once (host/options.cpp)
+    base.multilabel = multilabel_path != nullptr;
     std::cout << "RUNNING ON GPU" << std::endl;
 
     int rc = EXIT_SUCCESS;
@@ -124,6 +147,8 @@ int main(int argc, char **argv) {
     if (predict_path && !*predict_path) predict_path = nullptr;
     std::vector<int32_t> all_pred(predict_path ? params.num_nodes : 0, -1);   // by node id, filled by the workers
     std::vector<float> all_prob(predict_path ? params.num_nodes : 0, 0.f);
+    const int ml_wpr = gcn_label_words(params.output_dim);
+    std::vector<uint32_t> all_bits(predict_path && multilabel_path ? (size_t)params.num_nodes * ml_wpr : 0, 0u);
     auto worker = [&](int rank, const char *id) {
         try {
             HipGCNOptions o = base;
@@ -142,7 +167,16 @@ int main(int argc, char **argv) {
                 gcn.save_weights(save_path);
                 fprintf(stderr, "gcn-hip: weights written to %s\n", save_path);
             }
-            if (predict_path) {                                // every rank: the logit aggregation exchanges rows
+            if (predict_path && multilabel_path) {             // the same, as class sets
+                const int n = gcn.local_rows(), r0 = gcn.row_start();
+                std::vector<uint32_t> b((size_t)std::max(n, 1) * ml_wpr);
+                gcn.predict_multilabel(nullptr, n, b.data(), nullptr);
+                const std::vector<int> &order = gcn.node_order();
+                for (int r = 0; r < n; r++) {
+                    const int id = order.empty() ? r0 + r : order[r0 + r];
+                    std::copy(b.begin() + (size_t)r * ml_wpr, b.begin() + (size_t)(r + 1) * ml_wpr, all_bits.begin() + (size_t)id * ml_wpr);
+                }
+            } else if (predict_path) {                         // every rank: the logit aggregation exchanges rows
                 const int n = gcn.local_rows(), r0 = gcn.row_start();
                 std::vector<int32_t> p(std::max(n, 1));
                 std::vector<float> q(std::max(n, 1));
@@ -190,7 +224,17 @@ int main(int argc, char **argv) {
     if (predict_path) {
         FILE *f = fopen(predict_path, "w");
         bool ok = f != nullptr;
-        for (int i = 0; ok && i < params.num_nodes; i++) ok = fprintf(f, "%d %d %.6g\n", i, all_pred[i], all_prob[i]) > 0;
+        for (int i = 0; ok && i < params.num_nodes; i++) {
+            if (!multilabel_path) {
+                ok = fprintf(f, "%d %d %.6g\n", i, all_pred[i], all_prob[i]) > 0;
+                continue;
+            }
+            std::string line = std::to_string(i);
+            char sep = ' ';
+            for (int c = 0; c < params.output_dim; c++)
+                if ((all_bits[(size_t)i * ml_wpr + (c >> 5)] >> (c & 31)) & 1u) { line += sep; line += std::to_string(c); sep = ','; }
+            ok = fprintf(f, "%s\n", line.c_str()) > 0;
+        }
         if (f && fclose(f) != 0) ok = false;
         if (!ok) {
             fprintf(stderr, "gcn-hip: could not write the predictions to %s\n", predict_path);

@@ -190,12 +190,13 @@ void HipGraphSum::forward(bool training) {
             GCNHIP_CHECK(gcnhip_graphsum_predict(env->ctx, graph, predict->rows, nullptr, tab, ld_bf, nullptr, 0, dim, 0, predict->pred,
                                                  predict->prob, predict->logp, predict->ld_logp));
         else
-            GCNHIP_CHECK(gcnhip_graphsum_bf16(env->ctx, graph, tab, ld_bf, out->data, out->ld, dim, nullptr, out_rows, fused ? 1 : 0, training ? 1 : 0,
+            GCNHIP_CHECK(gcnhip_graphsum_bf16(env->ctx, graph, tab, ld_bf, redirect ? redirect->data : out->data, redirect ? redirect->ld : out->ld, dim,
+                                              nullptr, redirect ? redirect->rows : out_rows, fused ? 1 : 0, training ? 1 : 0,
                                               fused ? fused_relu_dropout : 0.f, env->seed ^ KEY_HIDDEN_DROPOUT, env->d_epoch, elem_offset,
                                               training ? env->keep_hidden : nullptr));
         if (dim > 64) env->timers->stop(TMR_GRAPHSUM_WIDE);
         env->timers->stop(TMR_GRAPHSUM_FW);
-    } else if (env->xlane && !replicated && world > 1 && !predict) {
+    } else if (env->xlane && !replicated && world > 1 && !predict && !redirect) {
         // exchange on its own stream; meanwhile the edges that point at this rank's own rows, then the others on top.
         // (A rank that owns no rows has no operators to cut — split_loc is NULL — but takes part in the exchange all the same:
         // it runs on the lane's communicator on EVERY rank.)
@@ -246,11 +247,11 @@ void HipGraphSum::forward(bool training) {
                 o.keep_mask = training ? env->keep_hidden : nullptr;
                 if (bits_here) { o.pos_bits = bits_here; o.words_per_row = mask_bits_out ? (dim + 31) / 32 : wpr; bits_written = true; }
             } else {
-                o.rows = out_rows;
+                o.rows = redirect ? redirect->rows : out_rows;
             }
             gcnhip_gs_loss lo = {};
-            if (loss && fused_relu_dropout < 0.f && loss->epilogue_opts(training, &lo)) { o.loss = &lo; loss->terms_fresh = true; }
-            GCNHIP_CHECK(gcnhip_graphsum_ex(env->ctx, graph, &o, src, in->ld, out->data, out->ld, dim));
+            if (loss && !redirect && fused_relu_dropout < 0.f && loss->epilogue_opts(training, &lo)) { o.loss = &lo; loss->terms_fresh = true; }
+            GCNHIP_CHECK(gcnhip_graphsum_ex(env->ctx, graph, &o, src, in->ld, redirect ? redirect->data : out->data, redirect ? redirect->ld : out->ld, dim));
         }
         if (dim > 64) env->timers->stop(TMR_GRAPHSUM_WIDE);
         env->timers->stop(TMR_GRAPHSUM_FW);
@@ -371,6 +372,20 @@ void HipCrossEntropyLoss::forward(bool training) {
     else
     GCNHIP_CHECK(gcnhip_xent_fwd(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, *truth, logits->rows,
                                  num_classes, training ? 1 : 0, *count, shift_in_place ? 1 : 0, d_result, d_result_i));
+    env->timers->stop(TMR_LOSS_FW);
+}
+
+// ------------------------------------------------------------- multi-label
+HipBCELoss::HipBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count,
+                       float *d_result, int32_t *d_result_i, int num_classes)
+    : env(env), logits(logits), truth(truth), wpr(wpr), count(count), d_result(d_result), d_result_i(d_result_i),
+      num_classes(num_classes) {}
+
+void HipBCELoss::forward(bool training) {
+    env->timers->start(TMR_LOSS_FW);
+    const int n = rows_n ? *rows_n : 0;
+    GCNHIP_CHECK(gcnhip_bce_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, truth, wpr, *rows_list, n, num_classes,
+                                     training && *count > 0 ? 1 : 0, *count, grad_row_scale, d_result, d_result_i));
     env->timers->stop(TMR_LOSS_FW);
 }
 

@@ -171,6 +171,14 @@ public:
         int ld_logp = 0;
     };
     const Prediction *predict = nullptr;
+    // set for one forward by HipGCN::predict_multilabel: the logits of these rows (NULL: all) go to `data` (ld floats per row)
+    // instead of `out` — no loss epilogue, the exchange (several GPUs) on the main stream
+    struct Redirect {
+        float *data = nullptr;
+        int ld = 0;
+        const gcnhip_rowset *rows = nullptr;
+    };
+    const Redirect *redirect = nullptr;
     HipGraphSum(HipEnv *env, HipVariable *in, HipVariable *out, gcnhip_graph *graph, int dim,
                 float fused_relu_dropout = -1.f, uint64_t elem_offset = 0);
     ~HipGraphSum() override;
@@ -210,6 +218,28 @@ public:
     ~HipCrossEntropyLoss() override;
     HipCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count,
                         float *d_result, int32_t *d_result_i, int num_classes, bool shift_in_place);
+    void forward(bool) override;
+    void backward() override {}
+};
+
+// Multi-label loss (beyond the reference): per-class sigmoid cross-entropy and micro-F1 counts over the rows of the current
+// split, on the stored logits (gcnhip_bce_fwd_rows).  d_result receives {loss_sum, rows * C, 2 TP, 2 TP + FP + FN} — the
+// metrics row of the ring then reads loss = [0] / [1] and F1 = [2] / [3], and several ranks add the four floats.
+class HipBCELoss : public Module {
+    HipEnv *env;
+    HipVariable *logits;
+    const uint32_t *truth;          // [local rows x wpr] multi-hot bits
+    int wpr;
+    const int *count;               // rows of the current split, all ranks
+    float *d_result;
+    int32_t *d_result_i;            // [4] {TP, FP, FN, rows}
+    int num_classes;
+public:
+    int32_t *const *rows_list = nullptr;        // rows of the current split on this rank (ascending) and their number
+    const int *rows_n = nullptr;
+    const float *grad_row_scale = nullptr;      // factored aggregation: dZ' = dinv . dZ
+    HipBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count,
+               float *d_result, int32_t *d_result_i, int num_classes);
     void forward(bool) override;
     void backward() override {}
 };

@@ -49,25 +49,48 @@ def nccl_unique_id() -> bytes:
 
 class HipGCNModel:
     """ds: dict with num_nodes, input_dim, output_dim, g_indptr, g_indices, f_indptr, f_indices (or None
-    for a dense X), f_val, split, label (the reference's GCNData)"""
+    for a dense X), f_val, split, label (the reference's GCNData).
+
+    multilabel: a bool/uint8 [num_nodes, C] matrix (1 <= C <= 256) switches the model to multi-label mode: output_dim = C,
+    the loss is the per-class sigmoid cross-entropy, and train_epoch / eval / run_epochs report micro-F1 where they report
+    accuracy otherwise.  ds["label"] may then be absent."""
 
     def __init__(self, ds, seed=0, device=0, flags=0, rank=0, world=1, nccl_id: bytes | None = None,
-                 host_allgather=None, host_allreduce=None, **hyper):
+                 host_allgather=None, host_allreduce=None, multilabel=None, **hyper):
         self.lib = lib = _lib.gcnhost()
-        p = default_params(num_nodes=ds["num_nodes"], input_dim=ds["input_dim"], output_dim=ds["output_dim"], **hyper)
+        out_dim = ds["output_dim"]
+        words = None
+        if multilabel is not None:
+            from .ops import pack_multihot
+            y = np.asarray(multilabel)
+            if y.ndim != 2 or y.shape[0] != ds["num_nodes"] or not 1 <= y.shape[1] <= 256:
+                raise ValueError(f"multilabel: expected a [num_nodes={ds['num_nodes']}, C] matrix with 1 <= C <= 256, got {y.shape}")
+            out_dim = y.shape[1]
+            words = pack_multihot(y != 0)
+        self.multilabel = words is not None
+        p = default_params(num_nodes=ds["num_nodes"], input_dim=ds["input_dim"], output_dim=out_dim, **hyper)
         self.params = p
         self._keep = [_i32(ds["g_indptr"]), _i32(ds["g_indices"]), _i32(ds["f_indptr"]),
                       _i32(ds["f_indices"]) if ds.get("f_indices") is not None else None,
-                      np.ascontiguousarray(ds["f_val"], np.float32), _i32(ds["split"]), _i32(ds["label"])]
+                      np.ascontiguousarray(ds["f_val"], np.float32), _i32(ds["split"]),
+                      _i32(ds["label"]) if ds.get("label") is not None else None, words]
         k = self._keep
         self._ag = _lib.ALLGATHER_FN(host_allgather) if host_allgather else C.cast(None, _lib.ALLGATHER_FN)
         self._ar = _lib.ALLREDUCE_FN(host_allreduce) if host_allreduce else C.cast(None, _lib.ALLREDUCE_FN)
         h = C.c_void_p()
-        rc = lib.gcnhost_model_create(C.byref(h), C.byref(p), k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data,
-                                      k[3].ctypes.data if k[3] is not None else None, k[4].ctypes.data,
-                                      k[5].ctypes.data, k[6].ctypes.data, int(seed), int(device), int(flags),
-                                      int(rank), int(world), nccl_id, self._ag, self._ar, None)
-        _ck(lib, rc, "gcnhost_model_create")
+        if words is None:
+            rc = lib.gcnhost_model_create(C.byref(h), C.byref(p), k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data,
+                                          k[3].ctypes.data if k[3] is not None else None, k[4].ctypes.data,
+                                          k[5].ctypes.data, k[6].ctypes.data, int(seed), int(device), int(flags),
+                                          int(rank), int(world), nccl_id, self._ag, self._ar, None)
+            _ck(lib, rc, "gcnhost_model_create")
+        else:
+            rc = lib.gcnhost_model_create_multilabel(C.byref(h), C.byref(p), k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data,
+                                                     k[3].ctypes.data if k[3] is not None else None, k[4].ctypes.data,
+                                                     k[5].ctypes.data, k[6].ctypes.data if k[6] is not None else None,
+                                                     k[7].ctypes.data, int(seed), int(device), int(flags),
+                                                     int(rank), int(world), nccl_id, self._ag, self._ar, None)
+            _ck(lib, rc, "gcnhost_model_create_multilabel")
         self.h = h
         self._keep = None           # the C++ side copied everything it needs
 
@@ -162,6 +185,24 @@ class HipGCNModel:
         _ck(self.lib, self.lib.gcnhost_model_predict(self.h, qp, n, pred.ctypes.data, prob.ctypes.data, lp.ctypes.data if logp else None), "predict")
         return (pred[:n], prob[:n], lp[:n]) if logp else (pred[:n], prob[:n])
 
+    def predict_multilabel(self, nodes=None, prob=False):
+        """bool [n, C] — the classes whose logit is above 0 (the rule micro-F1 counts with), from an evaluation forward with the
+        current weights whose logits go to scratch; prob=True: also the sigmoid of every logit, f32 [n, C].  nodes as in
+        predict(); only on a model built with multilabel=.  Several ranks: every rank calls it.  Training state is not touched."""
+        from .ops import unpack_multihot
+        if nodes is None:
+            n, qp = self.info()["local_rows"], None
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n, qp = q.size, q.ctypes.data
+        c = self.params.output_dim
+        words = np.zeros((max(n, 1), (c + 31) // 32), np.uint32)
+        pr = np.zeros((max(n, 1), c), np.float32) if prob else None
+        _ck(self.lib, self.lib.gcnhost_model_predict_multilabel(self.h, qp, n, words.ctypes.data, pr.ctypes.data if prob else None),
+            "predict_multilabel")
+        sets = unpack_multihot(words[:n], c)
+        return (sets, pr[:n]) if prob else sets
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")
@@ -222,6 +263,27 @@ def read_weights(path):
     w2 = np.zeros((h.value, c.value), np.float32)
     _ck(lib, lib.gcnhost_weights_read(os.fsencode(path), C.byref(F), C.byref(h), C.byref(c), w1.ctypes.data, w2.ctypes.data), "weights_read")
     return w1, w2
+
+
+def read_labels(path, num_nodes=None, num_classes=None):
+    """bool [N, C] from a multi-label truth file (one line per node, comma-separated class ids, empty for none; host/labels.h) —
+    host only, no GPU.  num_nodes: the line count the file must have; num_classes: fixes C (else the largest id + 1).  A wrong
+    line count, a bad token or a negative id raises GcnHostError with the file's line."""
+    from .ops import unpack_multihot
+    lib = _lib.gcnhost()
+    n, c = C.c_int(int(num_nodes or 0)), C.c_int(int(num_classes or 0))
+    _ck(lib, lib.gcnhost_labels_read(os.fsencode(path), C.byref(n), C.byref(c), None), "labels_read")
+    words = np.zeros((n.value, (c.value + 31) // 32), np.uint32)
+    _ck(lib, lib.gcnhost_labels_read(os.fsencode(path), C.byref(n), C.byref(c), words.ctypes.data), "labels_read")
+    return unpack_multihot(words, c.value)
+
+
+def write_labels(path, y):
+    """the inverse of read_labels: one line per row of the bool [N, C] matrix y, its class ids ascending"""
+    y = np.asarray(y).astype(bool)
+    with open(path, "w") as f:
+        for row in y:
+            f.write(",".join(str(int(c)) for c in np.flatnonzero(row)) + "\n")
 
 
 def write_weights(path, w1, w2):

@@ -575,6 +575,44 @@ class Device:
         return dict(loss_sum=float(r[0]), count=float(r[1]), correct=int(ri[0]), total=int(ri[1]),
                     logits=lb.download()[:, :c], grad=gb.download()[:, :c] if training else None)
 
+    def bce_fwd_rows(self, logits, truth, rows=None, training=True, count=None, grad_row_scale=None, ld=None, grad_fill=np.nan):
+        """gcnhip_bce_fwd_rows: per-class sigmoid cross-entropy over the listed rows (None: every row).  truth: bool [n, C] (packed
+        here into multi-hot words).  Returns dict(loss_sum, denom (rows * C), f1_num (2 TP), f1_den (2 TP + FP + FN), tp, fp, fn,
+        rows, loss, f1, grad [n, C] or None); grad rows outside the list keep grad_fill."""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
+        words = pack_multihot(truth)
+        lb = self.padded(logits, ld)
+        gb = self.buf(np.full((n, ld), grad_fill, np.float32))
+        tb, rb = self.buf(words), self.buf(rows if rows.size else np.zeros(1, np.int32))
+        sb = self.buf(np.ascontiguousarray(grad_row_scale, np.float32)) if grad_row_scale is not None else None
+        res, resi = self.buf(np.zeros(4, np.float32)), self.buf(np.zeros(4, np.int32))
+        _ck(self.lib, self.lib.gcnhip_bce_fwd_rows(self.ctx, lb.ptr, ld, gb.ptr, ld, tb.ptr, words.shape[1], rb.ptr, int(rows.size), c,
+                                                    int(training), int(count if count is not None else max(rows.size, 1)),
+                                                    sb.ptr if sb else None, res.ptr, resi.ptr), "gcnhip_bce_fwd_rows")
+        r, ri = res.download(), resi.download()
+        return dict(loss_sum=float(r[0]), denom=float(r[1]), f1_num=float(r[2]), f1_den=float(r[3]),
+                    tp=int(ri[0]), fp=int(ri[1]), fn=int(ri[2]), rows=int(ri[3]),
+                    loss=float(r[0]) / float(r[1]) if r[1] else 0.0, f1=float(r[2]) / float(r[3]) if r[3] else 0.0,
+                    grad=gb.download()[:, :c] if training else None)
+
+    def bce_predict_rows(self, logits, rows=None, prob=True, ld=None):
+        """gcnhip_bce_predict_rows: (bool [len(rows), C] = logit > 0, sigmoid [len(rows), C] or None)"""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
+        m, wpr = rows.size, (c + 31) // 32
+        lb = self.padded(logits, ld)
+        rb = self.buf(rows if m else np.zeros(1, np.int32))
+        bb = self.buf(np.full((max(m, 1), wpr), 0xFFFFFFFF, np.uint32))
+        qb = self.buf(np.full((max(m, 1), c), np.nan, np.float32)) if prob else None
+        _ck(self.lib, self.lib.gcnhip_bce_predict_rows(self.ctx, lb.ptr, ld, rb.ptr, m, c, bb.ptr, wpr, qb.ptr if qb else None, c),
+            "gcnhip_bce_predict_rows")
+        return unpack_multihot(bb.download()[:m], c), (qb.download()[:m] if qb else None)
+
     def accuracy(self, logits, truth, ld=None):
         logits = np.asarray(logits, np.float32)
         n, c = logits.shape
@@ -621,6 +659,24 @@ class Device:
             else:
                 _ck(self.lib, self.lib.gcnhip_adam_step(self.ctx, arr, len(ws), float(step), None, None, beta1, beta2, eps, weight_decay, sq.ptr), "gcnhip_adam_step")
         return [b["w"].download() for b in bufs], float(sq.download()[0])
+
+
+def pack_multihot(y):
+    """bool [n, C] -> uint32 [n, ceil(C / 32)]: bit (c & 31) of word c >> 5 = y[:, c] (the layout of gcnhip_bce_fwd_rows)"""
+    y = np.asarray(y).astype(bool)
+    n, c = y.shape
+    wpr = (c + 31) // 32
+    pad = np.zeros((n, wpr * 32), bool)
+    pad[:, :c] = y
+    b = np.packbits(pad.reshape(n, wpr, 4, 8)[..., ::-1], axis=-1).reshape(n, wpr, 4)   # byte k of a word = bits 8k .. 8k+7
+    return np.ascontiguousarray(b.astype(np.uint32) @ (1 << (8 * np.arange(4, dtype=np.uint32)))).astype(np.uint32)
+
+
+def unpack_multihot(words, c):
+    """uint32 [n, ceil(C / 32)] -> bool [n, C]"""
+    w = np.ascontiguousarray(words, np.uint32)
+    bits = (w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
+    return bits.reshape(w.shape[0], -1)[:, :c].astype(bool)
 
 
 class Graph:

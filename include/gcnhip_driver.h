@@ -302,6 +302,26 @@ int gcnhip_xent_fwd_rows_scaled(gcnhip_ctx *ctx, float *logits, int ld, float *g
  * partials, same final reduction — bit for bit), an armed metrics record included. */
 int gcnhip_xent_from_row_terms(gcnhip_ctx *ctx, const float *d_row_terms, const int32_t *truth, const int32_t *d_rows, int n_listed,
                                float *d_result, int32_t *d_result_i);
+/* ---- multi-label (beyond the reference, which is single-label) ----------------------------------------------------
+ * Per-class sigmoid cross-entropy over a list of rows (bce.hip).  Truth: multi-hot bit rows, bit (c & 31) of word
+ * truth_bits[r * words_per_row + (c >> 5)] = class c of row r, words_per_row >= ceil(C / 32).  For every listed row r and
+ * class c (y in {0, 1}): the term max(z, 0) - z y + log(1 + exp(-|z|)) (finite for every finite z); when training,
+ * grad[r, c] = (sigmoid(z) - y) / (count * C), times d_grad_row_scale[r] when given (the factored form), and no other row
+ * of grad is written; the counts TP (z > 0, y = 1), FP (z > 0, y = 0), FN (z <= 0, y = 1).  count = listed rows over all
+ * ranks (> 0 when training).  d_result[4] = {sum of terms, n_listed * C, 2 TP, 2 TP + FP + FN} — every entry additive
+ * across ranks, so an all-reduce of the four floats is enough: loss = [0] / [1], micro-F1 = [2] / [3] (0 when [3] is 0).
+ * d_result_i (may be NULL) [4] = {TP, FP, FN, n_listed}, exact.  The sums are deterministic (block partials added in
+ * block order: two launches give the same bits).  An armed gcnhip_metrics_record_with_next_loss is honoured: the ring row
+ * receives d_result's four floats.  1 <= num_classes <= 256, else -1.  Graph-capturable. */
+int gcnhip_bce_fwd_rows(gcnhip_ctx *ctx, const float *logits, int ld, float *grad, int ld_grad,
+                        const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
+                        int num_classes, int training, int count, const float *d_grad_row_scale,
+                        float *d_result, int32_t *d_result_i);
+/* Predicted class sets of n_rows rows (d_rows[i], or row i when d_rows is NULL) of a logit table: bits[i * words_per_row
+ * + (c >> 5)] bit (c & 31) = (z_c > 0), the rule of the counts above (bits past C are 0); prob (may be NULL)
+ * [i * ld_prob + c] = sigmoid(z_c).  1 <= num_classes <= 256. */
+int gcnhip_bce_predict_rows(gcnhip_ctx *ctx, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes,
+                            uint32_t *bits, int words_per_row, float *prob, int ld_prob);
 /* The same update, and the epoch word advanced behind it in the same launch (the block that finishes last, after every
  * block has read the word): *d_epoch_done = e, *d_epoch_counter = e + 1 with e the counter's value during the launch.
  * The training pass of epoch e + 1 then reads its epoch from d_epoch_counter without a launch of its own

@@ -82,6 +82,17 @@ int gcnhost_model_create(gcnhost_model **m, const gcnhost_params *p,
                          long seed, int device, int flags,
                          int rank, int world, const char *nccl_id,
                          gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user);
+/* The same model in multi-label mode (beyond the reference): multihot = the truth as num_nodes rows of ceil(output_dim / 32)
+ * uint32 words, bit (c & 31) of word c >> 5 = class c of the node (1 <= output_dim <= 256).  label may be NULL (it then only
+ * serves the aggregation's schedule hint, which it skips).  The loss is the per-class sigmoid cross-entropy, and the
+ * accuracy of train_epoch / eval / run_epochs / run is micro-F1 (gcnhip_bce_fwd_rows). */
+int gcnhost_model_create_multilabel(gcnhost_model **m, const gcnhost_params *p,
+                                    const int *g_indptr, const int *g_indices,
+                                    const int *f_indptr, const int *f_indices, const float *f_val,
+                                    const int *split, const int *label, const uint32_t *multihot,
+                                    long seed, int device, int flags,
+                                    int rank, int world, const char *nccl_id,
+                                    gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user);
 int gcnhost_model_destroy(gcnhost_model *m);
 
 int gcnhost_model_train_epoch(gcnhost_model *m, float *loss, float *acc);      /* gcn.cpp:107-118; synchronises */
@@ -128,6 +139,15 @@ int gcnhost_model_set_weights(gcnhost_model *m, const float *w1, const float *w2
  * (may be NULL) [n x output_dim] the log-softmax rows.  Several ranks: every rank calls it (the logit aggregation exchanges
  * rows).  Training state is not touched: a train_epoch after it gives the same bits as one without it.  Synchronises. */
 int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pred, float *prob, float *logp);
+/* Multi-label prediction, the same contract as gcnhost_model_predict: bits [n x ceil(output_dim / 32)] the predicted class
+ * sets (bit c = logit c > 0), prob (may be NULL) [n x output_dim] the sigmoid of every logit.  Only on a model made by
+ * gcnhost_model_create_multilabel (and gcnhost_model_predict only on one that was not). */
+int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob);
+/* The multi-label truth file (host/labels.h), host only: one line per node, comma-separated class ids, empty for none.
+ * *num_nodes > 0: the file must have that many lines; *num_classes > 0: every id must be below it (else C = largest id + 1).
+ * Both receive the values used.  bits (may be NULL: check and report the sizes only) [num_nodes x ceil(C / 32)].  A wrong
+ * line count, a bad token or a negative id is an error with a message naming the line. */
+int gcnhost_labels_read(const char *path, int *num_nodes, int *num_classes, uint32_t *bits);
 /* The weights file: "GCNW", format version, input / hidden / output widths (int32), W1 [F x h], W2 [h x C] (f32 row-major),
  * CRC-32; little-endian (host/weights.h).  save writes this model's W1, W2 (several ranks hold the same weights: one of them
  * writes).  load refuses a file whose widths differ from the model's (an error with a message, never a reshape) and goes
