@@ -6,12 +6,8 @@ PKG      = cuda_gcn_amd
 LIBDIR   = $(PKG)/lib
 BINDIR   = $(PKG)/bin
 OBJDIR   = build/obj
-# EXPERIMENTS=1: also compile the variants DESIGN.md records as built, bit-identical and slower (packed dH1 rows, the
-# persistent index-prefetching aggregation, non-temporal row loads, the in-launch segment sum, the persistent weight
-# gradient, W staged in LDS for the sparse forward, the backward pipeline of the host).  Their tests skip without it.
-EXPFLAG  = $(if $(EXPERIMENTS),-DGCNHIP_EXPERIMENTS,)
-HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed -Iinclude $(EXPFLAG)
-CXXFLAGS = -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-sign-compare -Iinclude -I$(PKG)/host -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ $(EXPFLAG)
+HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed -Iinclude
+CXXFLAGS = -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-sign-compare -Iinclude -I$(PKG)/host -I/opt/rocm/include -D__HIP_PLATFORM_AMD__
 
 KSRC = $(wildcard $(PKG)/csrc/*.hip)
 KOBJ = $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(KSRC))
@@ -20,18 +16,10 @@ HOBJ = $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HSRC))
 
 all: kernels host oracle
 
-# the flavour the objects were compiled in: switching EXPERIMENTS rebuilds them (make does not see a changed flag by itself,
-# and a library mixing the two flavours reports gcnhip_experiments() of whichever ctx.hip it happened to keep)
-FLAVOUR = $(OBJDIR)/.flavour
-$(FLAVOUR): FORCE
-	@mkdir -p $(OBJDIR)
-	@echo '$(EXPFLAG)' | cmp -s - $@ || echo '$(EXPFLAG)' > $@
-FORCE:
-
 kernels: $(LIBDIR)/libgcnhip.so
 host: $(LIBDIR)/libgcnhost.so $(BINDIR)/gcn-hip
 
-$(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(wildcard $(PKG)/csrc/*.h) $(wildcard include/*.h) $(FLAVOUR)
+$(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(wildcard $(PKG)/csrc/*.h) $(wildcard include/*.h)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -39,7 +27,7 @@ $(LIBDIR)/libgcnhip.so: $(KOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(KOBJ) -o $@
 
-$(OBJDIR)/host_%.o: $(PKG)/host/%.cpp $(wildcard $(PKG)/host/*.h) $(wildcard include/*.h) $(FLAVOUR)
+$(OBJDIR)/host_%.o: $(PKG)/host/%.cpp $(wildcard $(PKG)/host/*.h) $(wildcard include/*.h)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
@@ -49,7 +37,7 @@ $(LIBDIR)/libgcnhost.so: $(HOBJ) $(LIBDIR)/libgcnhip.so
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib -o $@
 
 # the program links the host objects directly (libgcnhost.so exports only its C entry points)
-$(BINDIR)/gcn-hip: $(PKG)/host/main.cpp $(HOBJ) $(LIBDIR)/libgcnhip.so $(FLAVOUR)
+$(BINDIR)/gcn-hip: $(PKG)/host/main.cpp $(HOBJ) $(LIBDIR)/libgcnhip.so
 	@mkdir -p $(BINDIR)
 	$(CXX) $(CXXFLAGS) $< $(HOBJ) -L$(LIBDIR) -lgcnhip -L/opt/rocm/lib -lrccl -lamdhip64 -lpthread \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib -o $@

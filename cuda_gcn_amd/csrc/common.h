@@ -7,7 +7,6 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/gcnhip_driver.h"
-#include "../../include/gcnhip_experimental.h"
 
 #define GCNHIP_TRY(expr)                                   \
     do {                                                   \
@@ -25,10 +24,7 @@ int gcnhip_fail(const char *detail);
 // GCNHIP_<NAME IN CAPITALS>, read ONCE when the context is created — never at launch time — so a call's behaviour does not
 // depend on what the process environment holds at that moment.  Most are A/B aids for measurements DESIGN.md records.
 struct GcnOptions {
-    int gs_pipe;            // 1: persistent index-prefetching aggregation kernel (measured slower)
     int gs_u;               // > 0: row loads in flight per lane group of the aggregation (0: by table size)
-    int gs_nt;              // 1: non-temporal row loads in the sliced aggregation (measured slower)
-    int gs_fold;            // 1: split rows are summed inside the aggregation launch (same bits; no faster)
     int gs_l;               // 8 / 4: column slices of 32 / 16 floats in the XCD-sliced aggregation (default 0: 64 floats)
     int gemm_tiles;         // 1: first-layer forward by the tile kernels instead of the persistent form
     int gemm_bf16x3;        // dense first-layer products (p = 128) from three bf16 planes on the bf16 MFMA pipe: 2 (default) on, also on a
@@ -40,14 +36,11 @@ struct GcnOptions {
     int gemm_lane_wgs;      // workgroups (= CUs) of that launch; 0: one per CU
     int spmm_slices;        // 1 (default): sparse X, W past an XCD's L2, h % 32 == 0: XCD-bound 32-float column slices of W; 0: the unsliced row kernel
     int cls_fwd;            // 1 (default): H1.W2 through class_bf16x3.h when gemm_bf16x3 >= 1; 0: through the f32-MFMA row stream
-    int gemm_persist_bwd;   // 1: persistent first-layer weight gradient (measured slower)
-    int dbg_linear;         // timing experiment only: the persistent forward reads X as if tile-major (wrong results)
     int xent_finalize;      // 1: the loss's final reduction as its own launch
     int xent_wave;          // 1: wave-per-row loss kernel for any width
     int adam_sum_launch;    // 1: Adam's sum of squares by a second launch
     int atb_cap_mb;         // split-K slab budget of A^T.B in MiB
     int rs_wgs;             // > 0: workgroups per CU of the row-streaming GEMM
-    int spmm_lds;           // 1: sparse forward with W staged in LDS whenever it fits (measured slower: opt-in)
     int spmm_general;       // 1: narrow rows also take the general (shuffle-based) sparse kernels; -1: narrow kernels at any size (A/B, tests)
     int spmm_rows;          // > 0: rows per wave of the sparse forward (default: by row count, 1 .. 8)
     int spmm_nw;            // > 0: waves per column task of the sparse weight gradient (1, 4, 16), read by gcnhip_feat_create
@@ -113,22 +106,12 @@ struct gcnhip_graph {
     float *partials;    // [n_slots * part_ld]
     int part_ld;
     int n_slots;
-    // in-kernel segment sum (graphsum.hip): per segment slot {first slot of its row, number of segments}; per split row
-    // and column slice an arrival counter (index first_slot * 8 + slice), zero between launches
-    int2 *slot_info;    // [n_slots]
-    uint32_t *seg_count; // [n_slots * 8]
     // task ranges of equal edge count for 1, 2, 4 or 8 XCD groups: bounds[log2 G][g] .. bounds[log2 G][g+1]
     int bounds[4][9];
     int *tmp_col_deg;   // only during construction
     std::vector<int> *h_indptr;   // host copy of the row pointers (the schedule can be rebuilt)
     std::vector<int4> *h_tasks, *h_srows;   // host copies of the full schedule (row subsets are cut from them)
     std::vector<gcnhip_rowset *> *rowsets;   // owned
-};
-
-// packed rows (dense_kernels.h "packed rows"): one 128-byte slot per (row, 64-column half)
-struct gcnhip_rowpack {
-    int rows, cols, halves;
-    uint32_t *slots;    // [rows x halves x 32]
 };
 
 struct gcnhip_feat {

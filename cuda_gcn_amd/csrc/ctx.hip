@@ -19,11 +19,11 @@ int gcnhip_fail(const char *detail) {
 }
 
 const GcnOptionEntry GCN_OPTION_TABLE[] = {
-    {"gs_pipe", &GcnOptions::gs_pipe, 0}, {"gs_u", &GcnOptions::gs_u, 0}, {"gs_nt", &GcnOptions::gs_nt, 0}, {"gs_fold", &GcnOptions::gs_fold, 0}, {"gs_l", &GcnOptions::gs_l, 0},
-    {"gemm_tiles", &GcnOptions::gemm_tiles, 0}, {"gemm_bf16x3", &GcnOptions::gemm_bf16x3, 2}, {"gemm_w4", &GcnOptions::gemm_w4, 0}, {"cls_abl", &GcnOptions::cls_abl, 0}, {"cls_wgs", &GcnOptions::cls_wgs, 0}, {"cls_fwd", &GcnOptions::cls_fwd, 1}, {"spmm_slices", &GcnOptions::spmm_slices, 1}, {"gemm_lane_waves", &GcnOptions::gemm_lane_waves, 8}, {"gemm_lane_wgs", &GcnOptions::gemm_lane_wgs, 0}, {"gemm_persist_bwd", &GcnOptions::gemm_persist_bwd, 0},
-    {"dbg_linear", &GcnOptions::dbg_linear, 0}, {"xent_finalize", &GcnOptions::xent_finalize, 0}, {"xent_wave", &GcnOptions::xent_wave, 0},
+    {"gs_u", &GcnOptions::gs_u, 0}, {"gs_l", &GcnOptions::gs_l, 0},
+    {"gemm_tiles", &GcnOptions::gemm_tiles, 0}, {"gemm_bf16x3", &GcnOptions::gemm_bf16x3, 2}, {"gemm_w4", &GcnOptions::gemm_w4, 0}, {"cls_abl", &GcnOptions::cls_abl, 0}, {"cls_wgs", &GcnOptions::cls_wgs, 0}, {"cls_fwd", &GcnOptions::cls_fwd, 1}, {"spmm_slices", &GcnOptions::spmm_slices, 1}, {"gemm_lane_waves", &GcnOptions::gemm_lane_waves, 8}, {"gemm_lane_wgs", &GcnOptions::gemm_lane_wgs, 0},
+    {"xent_finalize", &GcnOptions::xent_finalize, 0}, {"xent_wave", &GcnOptions::xent_wave, 0},
     {"adam_sum_launch", &GcnOptions::adam_sum_launch, 0}, {"atb_cap_mb", &GcnOptions::atb_cap_mb, 12}, {"rs_wgs", &GcnOptions::rs_wgs, 0},
-    {"spmm_lds", &GcnOptions::spmm_lds, 0}, {"spmm_rows", &GcnOptions::spmm_rows, 0}, {"spmm_general", &GcnOptions::spmm_general, 0}, {"spmm_nw", &GcnOptions::spmm_nw, 0}, {"split_edges", &GcnOptions::split_edges, 0},
+    {"spmm_rows", &GcnOptions::spmm_rows, 0}, {"spmm_general", &GcnOptions::spmm_general, 0}, {"spmm_nw", &GcnOptions::spmm_nw, 0}, {"split_edges", &GcnOptions::split_edges, 0},
 };
 const int GCN_OPTION_COUNT = (int)(sizeof GCN_OPTION_TABLE / sizeof GCN_OPTION_TABLE[0]);
 
@@ -73,13 +73,7 @@ const char *gcnhip_error_string(int code) {
 }
 
 const char *gcnhip_version(void) { return "gcnhip 0.1 (gfx950)"; }
-int gcnhip_experiments(void) {
-#ifdef GCNHIP_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
+int gcnhip_experiments(void) { return 0; }
 
 int gcnhip_ctx_create(gcnhip_ctx **out, int device, void *stream) {
     if (!out) return -1;
@@ -360,19 +354,8 @@ static int build_tasks(gcnhip_graph *g, const std::vector<int> &order) {
     // segment scratch for the widest aggregation this object will serve: sized HERE (and by
     // gcnhip_graph_reserve_width), never inside a launch path
     if (g->partials) { GCNHIP_TRY(hipFree(g->partials)); g->partials = nullptr; }
-    if (g->slot_info) { GCNHIP_TRY(hipFree(g->slot_info)); g->slot_info = nullptr; }
-    if (g->seg_count) { GCNHIP_TRY(hipFree(g->seg_count)); g->seg_count = nullptr; }
     if (g->part_ld < 256) g->part_ld = 256;
-    if (n_slots) {
-        GCNHIP_TRY(hipMalloc((void **)&g->partials, (size_t)n_slots * g->part_ld * sizeof(float)));
-        std::vector<int2> info((size_t)n_slots);
-        for (const int4 &sr : srows)
-            for (int q = 0; q < sr.z; q++) info[(size_t)sr.y + q] = make_int2(sr.y, sr.z);
-        GCNHIP_TRY(hipMalloc((void **)&g->slot_info, (size_t)n_slots * sizeof(int2)));
-        GCNHIP_TRY(hipMemcpy(g->slot_info, info.data(), (size_t)n_slots * sizeof(int2), hipMemcpyHostToDevice));
-        GCNHIP_TRY(hipMalloc((void **)&g->seg_count, (size_t)n_slots * 8 * sizeof(uint32_t)));
-        GCNHIP_TRY(hipMemset(g->seg_count, 0, (size_t)n_slots * 8 * sizeof(uint32_t)));
-    }
+    if (n_slots) GCNHIP_TRY(hipMalloc((void **)&g->partials, (size_t)n_slots * g->part_ld * sizeof(float)));
     xcd_bounds(tasks, g->bounds);
     if (!g->h_tasks) g->h_tasks = new std::vector<int4>();
     if (!g->h_srows) g->h_srows = new std::vector<int4>();
@@ -616,8 +599,6 @@ int gcnhip_graph_destroy(gcnhip_ctx *c, gcnhip_graph *g) {
     if (g->tasks) hipFree(g->tasks);
     if (g->split_rows) hipFree(g->split_rows);
     if (g->partials) hipFree(g->partials);
-    if (g->slot_info) hipFree(g->slot_info);
-    if (g->seg_count) hipFree(g->seg_count);
     delete g;
     return 0;
 }

@@ -1,14 +1,14 @@
-// dense_persist.h — persistent, LDS-DMA-fed forms of the two compute-bound GEMMs of a dense-X first layer at
-// p = 128 output columns (replace cuda_SparseMatmul_forward/_backward, /root/reference/src/cuda/cuda_kernel.cu:100-122):
+// dense_persist.h — persistent, LDS-DMA-fed form of the compute-bound forward GEMM of a dense-X first layer at
+// p = 128 output columns (replaces the reference's cuda_SparseMatmul_forward, src/cuda/cuda_kernel.cu:100-110):
 //     forward   H0[m x 128]  = X~[m x K] . W[K x 128]
-//     backward  dW[K x 128]  = X~^T[K x m] . dH0[m x 128]
+// (The weight gradient stays on dense_tile128.h's split tiles: this form of it measured slower, docs/NOTEBOOK_r1-r4.md §4.4.)
 // Why a second form of dense_tile128.h's kernels (which stay: other widths, unaligned inputs, A/B runs).  Round 2 measured
 // where the 128 x 128 tile's 0.36 ms go: 19 % is the tail of 1821 equal tiles on 512 slots, and inside a
 // tile the staging pipeline (global -> registers -> wait -> LDS -> barrier, ONE chunk ahead) is as long as the MFMA
 // pipeline and only half overlapped.  Both are structural:
 //  * one workgroup per CU for the whole launch, given a CONTIGUOUS share of the rows that is balanced to one 32-row MFMA
-//    block (forward) / one row (backward): no tile quantisation.  The forward's last, partial tile deals its (row block,
-//    column block) units over the four SIMDs, so a partial tile costs its share of a full one;
+//    block: no tile quantisation.  The last, partial tile deals its (row block, column block) units over the four SIMDs,
+//    so a partial tile costs its share of a full one;
 //  * operands reach LDS by LDS-DMA (global_load_lds_dwordx4) into a ring of three stages, two K chunks ahead of the
 //    MFMAs, with counted vmcnt waits and ONE barrier per chunk; no staging registers, so depth costs only LDS;
 //  * the input dropout moves from the staging pass to the operand read (a select on the A fragment), the keep bits of a
@@ -24,7 +24,7 @@
 #include "dense_tile128.h"
 
 constexpr int PG_STAGES = 3;
-constexpr int PG_BK = 32;                                   // K (forward) / rows (backward) per chunk
+constexpr int PG_BK = 32;                                   // K per chunk
 constexpr int PG_ROWS = 256;                                // rows of a full forward tile: 8 waves x 32
 constexpr int PG_A_BYTES = PG_ROWS * PG_BK * 4;             // 32768
 constexpr int PG_B_BYTES = PG_BK * 128 * 4;                 // 16384
@@ -86,7 +86,6 @@ struct PersistFwdArgs {
     int m, K, n_chunks, n_rb;         // n_rb = ceil(m / 32)
     const uint32_t *bits;             // keep bits of the stored elements (element row*K + col), NULL: no dropout
     int relu;
-    int dbg_linear;                   // EXPERIMENT: read A as if X were stored tile-major (wrong results, right traffic shape)
 };
 
 struct PgFrag { float4 x; float4 y[4]; };
@@ -131,7 +130,6 @@ __global__ __launch_bounds__(512, 2) void dense_fwd_persist_kernel(PersistFwdArg
             const int row = min(tile_row0 + r, a.m - 1);
             const int g = slot ^ ((r >> 1) & 7);                 // which 4-float group of the chunk this LDS slot holds
             const float *src = a.x + (size_t)row * a.ldx + k0 + 4 * g;
-            if (a.dbg_linear) src = a.x + ((size_t)((rb_lo + 8 * t) >> 3) * a.n_chunks + c) * 8192 + q * 256 + lane * 4;
             pg_glds16(src, sA + q * 1024);
         } else if (u < 6) {                                      // B: a straight copy of the packed chunk
             const int q = wave + 8 * (u - 4);
@@ -350,145 +348,3 @@ __global__ __launch_bounds__(512, 2) void dense_fwd_persist_kernel(PersistFwdArg
             if (q < nq) store_block(acc[q], tile_row0 + 32 * (half + 2 * q), 32 * cb + li);
     }
 }
-
-#ifdef GCNHIP_EXPERIMENTS   // the persistent weight gradient: built, correct, measured slower
-// ------------------------------------------------------------------------------------------------ backward
-// dW[K x 128] = X~^T . dH0 over this workgroup's contiguous share of the m rows (the reduction dimension), ALL of the
-// output held in the accumulators of its eight waves: ceil(K/32) x 4 blocks of 32 x 32, block b -> wave b % 8 (so a wave
-// owns ONE column block of dH0 and every other 32-column block of X: one B read and up to ten A reads per k step, and
-// the two waves of a SIMD carry 10 + 9 blocks whatever K is — balanced to the block).  One slab per workgroup, summed in
-// workgroup order by slab_reduce_kernel (no atomics: the same bits every run).
-// A chunk is 16 rows: the LDS images are straight copies of 16 rows of X (row stride ldx, zero padded past K) and of dH0,
-// both k-major exactly as the MFMA operands want them (a half-wave reads 32 consecutive floats of one row).
-constexpr int PB_ROWS = 16;
-constexpr int PB_MAX_LDX = 640;
-constexpr int PB_A_BYTES = PB_ROWS * PB_MAX_LDX * 4;        // 40960
-constexpr int PB_B_BYTES = PB_ROWS * 128 * 4;               // 8192
-constexpr int PB_K_WORDS = 24;                              // keep-bit words per row: ceil(ldx/32) + 1 <= 21, padded
-constexpr int PB_K_BYTES = PB_ROWS * PB_K_WORDS * 4;        // 1536
-constexpr int PB_STAGE_BYTES = PB_A_BYTES + PB_B_BYTES + PB_K_BYTES;   // 50688; x3 = 152064
-constexpr int PB_NACC = 10;
-
-struct PersistBwdArgs {
-    const float *x; int ldx;          // X, 16-byte aligned rows, ldx % 16 == 0, ldx <= 640, ldx >= round_up(K, 32), zero padded
-    const float *dout; int ldd;       // dH0 [m x 128], ldd % 4 == 0
-    float *slab; int lds;             // [gridDim.x][K][lds]
-    int m, K, n_xb;                   // n_xb = ceil(K / 32) <= 20
-    int rows_per_wg;                  // multiple of 2
-    const uint32_t *bits;
-    float scale;
-};
-
-template <bool DROP>
-__global__ __launch_bounds__(512, 2) void dense_bwd_persist_kernel(PersistBwdArgs a) {
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[PG_STAGES * PB_STAGE_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, kq = lane >> 5;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;
-    if (a.m < 0) smem[tid] = 0;       // never taken (see the forward kernel)
-
-    const int r_lo = blockIdx.x * a.rows_per_wg, r_hi = min(a.m, r_lo + a.rows_per_wg);
-    const int pb = wave & 3, xb0 = wave >> 2;                // blocks (xb0 + 2n, pb), n < nacc
-    const int nacc = (a.n_xb - xb0 + 1) >> 1;
-    float *slab = a.slab + (size_t)blockIdx.x * a.K * a.lds;
-    f32x16 acc[PB_NACC];
-#pragma unroll
-    for (int n = 0; n < PB_NACC; n++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[n][r] = 0.f;
-
-    const int n_items = r_lo < r_hi ? (r_hi - r_lo + PB_ROWS - 1) / PB_ROWS : 0;
-    const int a_bytes = PB_ROWS * a.ldx * 4;                 // bytes of the A image actually used (multiple of 1024)
-    const int a_instr = a_bytes >> 10;                       // <= 40
-    const int kwords = (a.ldx >> 5) + 1;                     // keep-bit words staged per row
-    constexpr int NL = DROP ? 7 : 6;
-
-    // per-lane source coordinates of this wave's five A pieces (piece q = wave + 8u, clamped: a duplicate piece rewrites
-    // the same bytes), fixed for the whole launch
-    int a_row[5], a_col[5], a_q[5];
-#pragma unroll
-    for (int u = 0; u < 5; u++) {
-        const int q = min(wave + 8 * u, a_instr - 1);
-        const int off = q * 1024 + lane * 16;
-        a_q[u] = q; a_row[u] = off / (a.ldx * 4); a_col[u] = (off % (a.ldx * 4)) >> 2;
-    }
-    auto issue = [&](int item, int stage) {
-        const int r0 = r_lo + item * PB_ROWS;
-        const uint32_t sA = lds0 + stage * PB_STAGE_BYTES, sB = sA + PB_A_BYTES, sK = sB + PB_B_BYTES;
-#pragma unroll
-        for (int u = 0; u < 5; u++)
-            pg_glds16(a.x + (size_t)min(r0 + a_row[u], a.m - 1) * a.ldx + a_col[u], sA + a_q[u] * 1024);
-        pg_glds16(a.dout + (size_t)min(r0 + 2 * wave + (lane >> 5), a.m - 1) * a.ldd + (lane & 31) * 4, sB + wave * 1024);
-        if (DROP) {
-            // word w of row rr: bits [32w, 32w+32) counted from the word that holds the row's first element
-            const int total = PB_ROWS * kwords;
-            const int q = min(wave, (total - 1) >> 6);
-            const int d = min(q * 64 + lane, total - 1);
-            const int rr = d / kwords, w = d - rr * kwords;
-            const uint64_t e0 = (uint64_t)min(r0 + rr, a.m - 1) * a.K;
-            // LDS-DMA lands at base + 4 * lane: the image is [rr][kwords] densely packed, lane order = d order (d clamped
-            // only in the last instruction's tail, whose lanes then rewrite the final word)
-            pg_glds4(a.bits + (e0 >> 5) + w, sK + q * 256);
-        }
-    };
-
-    if (n_items > 0) issue(0, 0);
-    if (n_items > 1) issue(1, 1);
-    int stage = 0, lstage = 2;
-    const uint32_t scale_bits = __float_as_uint(a.scale);
-    for (int g = 0; g < n_items; g++) {
-        if (g + 1 < n_items) {
-            if (DROP) PG_WAIT_BARRIER(7);
-            else PG_WAIT_BARRIER(6);
-        } else {
-            PG_WAIT_BARRIER(0);
-        }
-        if (g + 2 < n_items) { issue(g + 2, lstage); lstage = lstage == 2 ? 0 : lstage + 1; }
-        const unsigned char *st = smem + stage * PB_STAGE_BYTES;
-        const int r0 = r_lo + g * PB_ROWS;
-        const unsigned char *Ap = st + kq * (a.ldx * 4) + (xb0 * 32 + li) * 4;
-        const unsigned char *Bp = st + PB_A_BYTES + kq * 512 + (pb * 32 + li) * 4;
-        const unsigned char *Kp = st + PB_A_BYTES + PB_B_BYTES + kq * (kwords * 4) + xb0 * 4;
-#pragma unroll 2
-        for (int s = 0; s < PB_ROWS / 2; s++) {
-            const int row = r0 + 2 * s + kq;
-            const float bval = *reinterpret_cast<const float *>(Bp + s * 1024);
-            const float live = row < r_hi ? 1.f : 0.f;
-            const uint32_t sh = (uint32_t)(((uint64_t)row * a.K) & 31);
-            float av[PB_NACC];
-#pragma unroll
-            for (int n = 0; n < PB_NACC; n++) {
-                av[n] = 0.f;
-                if (n < nacc) {                              // wave-uniform
-                    const float x = *reinterpret_cast<const float *>(Ap + s * 2 * (a.ldx * 4) + n * 256);
-                    float f = live;
-                    if (DROP) {
-                        const uint32_t *kw = reinterpret_cast<const uint32_t *>(Kp + s * 2 * (kwords * 4) + n * 8);
-                        const uint32_t m32 = __builtin_amdgcn_alignbit(kw[1], kw[0], sh);
-                        const uint32_t keep = (uint32_t)(((int32_t)(m32 << (31 - li))) >> 31);       // bit li -> 0 or ~0
-                        f = __uint_as_float(__float_as_uint(live) == 0u ? 0u : (keep & scale_bits));
-                    }
-                    av[n] = x * f;
-                }
-            }
-#pragma unroll
-            for (int n = 0; n < PB_NACC; n++)
-                if (n < nacc) acc[n] = MFMA32(av[n], bval, acc[n]);
-        }
-        stage = stage == 2 ? 0 : stage + 1;
-    }
-    // this workgroup's partial [K x 128] (all zero when it had no rows)
-#pragma unroll
-    for (int n = 0; n < PB_NACC; n++) {
-        if (n < nacc) {
-            const int pc = pb * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int xc = (xb0 + 2 * n) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq;
-                if (xc < a.K) slab[(size_t)xc * a.lds + pc] = acc[n][r];
-            }
-        }
-    }
-}
-#endif  // GCNHIP_EXPERIMENTS

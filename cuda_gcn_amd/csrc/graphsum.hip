@@ -25,7 +25,6 @@
 // global read-modify-write per edge (cuda_kernel.cu:126-143).
 #include "dense_kernels.h"
 #include <algorithm>
-#include <string.h>
 #include <stdlib.h>
 
 struct GsArgs {
@@ -52,11 +51,6 @@ struct GsArgs {
     uint32_t *pos_bits;         // optional (fuse, dim % 32 == 0, vector kernel): bit (c & 31) of pos_bits[r * wpr + (c >> 5)] =
     int wpr;                    // (out[r, c] > 0) AFTER the ReLU/dropout epilogue — the mask their backward needs, so that it
                                 // does not have to read the activations again (gcnhip_matmul_bwd_fused_bits)
-    // in-kernel segment sum (vector kernel): the wave that finishes a split row's LAST outstanding segment adds the row's
-    // partials in segment order and runs the store epilogue itself — no second launch.  NULL: a finalize launch follows.
-    const int2 *slot_info;      // [slot] = {first slot of the row, segments of the row}
-    uint32_t *seg_count;        // [first_slot * 8 + column slice] arrivals; zero before and after every launch
-    int n_slots_bytes;          // size of `partials` in bytes (buffer descriptor of the write-through stores)
     int accumulate;             // 1: out[r,:] = out[r,:] + sum (the second of two operators that share the rows of `out`:
                                 // the remote-column part of a row-partitioned aggregation, gcnhip_graphsum_part)
     // factored coefficients (gcnhip_graphsum_ex): coef == NULL -> every edge counts 1 and the row's total is multiplied by
@@ -199,16 +193,8 @@ __device__ __forceinline__ void xent_row_epilogue1(const GsArgs &a, int row, flo
 constexpr int GS_U = 4;        // row loads in flight per lane group when the table is cache resident (bf16 kernel: always)
 // One chunk of <= 64 edges whose (index, coef) pairs sit in the wave's lanes: acc += sum over the chunk, lane group g
 // taking edges g, g + G, ... in order (the order every form of the kernel keeps, so all of them agree bit for bit).
-// NT: the row loads carry the non-temporal hint (the line is not to be kept in L2 / Infinity Cache at the expense of others)
-template <int L, int GS_U, bool NT = false>
+template <int L, int GS_U>
 __device__ __forceinline__ float4 gather_chunk(const GsArgs &a, const float *in, int my_idx, float my_c, int cnt, int g, float4 acc) {
-    auto ldrow = [&](const float *p) __attribute__((always_inline)) -> float4 {
-        if (NT) {
-            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-            return make_float4(v[0], v[1], v[2], v[3]);
-        }
-        return *reinterpret_cast<const float4 *>(p);
-    };
     constexpr int G = WAVE / L;
     const int iters = (cnt + G - 1) / G;
     // GS_U row loads per lane group are in flight together whenever the next GS_U iterations are all real edges
@@ -226,7 +212,7 @@ __device__ __forceinline__ float4 gather_chunk(const GsArgs &a, const float *in,
                 const int src = (k + u) * G + g;
                 const int j = __shfl(my_idx, src, WAVE);
                 cc[u] = __shfl(my_c, src, WAVE);
-                v[u] = ldrow(in + (size_t)j * a.ld_in);
+                v[u] = *reinterpret_cast<const float4 *>(in + (size_t)j * a.ld_in);
             }
 #pragma unroll
             for (int u = 0; u < GS_U; u++) acc = f4_fma(cc[u], v[u], acc);
@@ -245,7 +231,7 @@ __device__ __forceinline__ float4 gather_chunk(const GsArgs &a, const float *in,
             const int j = __shfl(my_idx, src & 63, WAVE);
             cc[u] = __shfl(my_c, src & 63, WAVE);
             on[u] = src < cnt && cc[u] != 0.f;         // padded lanes and known-zero rows contribute nothing
-            v[u] = ldrow(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
+            v[u] = *reinterpret_cast<const float4 *>(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
         }
 #pragma unroll
         for (int u = 0; u < GS_U; u++) {
@@ -259,7 +245,7 @@ __device__ __forceinline__ float4 gather_chunk(const GsArgs &a, const float *in,
 // L lanes per feature row (float4 each), G = 64/L rows per wave instruction.
 // SLICED: the launch binds one column slice to each XCD group (it only changes the block -> (tasks, columns) mapping; the
 // flag is a template argument so that profiles name the hidden-width launches apart from the class-width ones).
-template <int L, int U = GS_U, bool SLICED = false, bool NT = false>
+template <int L, int U = GS_U, bool SLICED = false>
 __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
     constexpr int G = WAVE / L;
     const int lane = threadIdx.x & 63;
@@ -301,61 +287,14 @@ __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
             my_c = a.coef ? a.coef[base + lane] : 1.f;
             if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;
         }
-        acc = gather_chunk<L, U, NT>(a, in, my_idx, my_c, cnt, g, acc);
+        acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
     }
 #pragma unroll
     for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
-#ifndef GCNHIP_EXPERIMENTS
     if (slot >= 0) {                                        // a finalize launch will add the segments
-#else
-    if (slot >= 0 && !a.seg_count) {                        // a finalize launch will add the segments (seg_count: the in-launch sum, an experiment)
-#endif
         if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
         return;
     }
-#ifdef GCNHIP_EXPERIMENTS
-    if (slot >= 0) {
-        // Hand-off between workgroups on any XCDs (cdna guide, Guideline 16): the partial leaves WRITE-THROUGH (sc1: no
-        // release fence, which would write back this XCD's whole dirty L2), the wave drains its stores, one lane takes a
-        // ticket; the wave that draws the last ticket invalidates its CU's L1 (agent-scope acquire) and reads every
-        // segment's partial — in segment order, so the row's sum has the bits the finalize kernel gives it.
-        typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(a.partials, 0, a.n_slots_bytes, 0x00020000);
-        if (g == 0 && active) {
-            const v4u raw = {__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), __float_as_uint(acc.w)};
-            __builtin_amdgcn_raw_buffer_store_b128(raw, prsrc, (int)(((uint32_t)slot * (uint32_t)a.part_ld + (uint32_t)col0) * 4u), 0, 16 /* sc1 */);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int2 info = a.slot_info[slot];
-        uint32_t *cnt = a.seg_count + (size_t)info.x * 8 + cslice;
-        unsigned prev = 0;
-        if (lane == 0) prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // (the write-through store + drain above
-                                                                                                              //  make the release cheap: nothing of this wave is left dirty)
-        prev = __builtin_amdgcn_readfirstlane(prev);
-        if ((int)prev != info.y - 1) return;                // other segments of this row are still on their way
-        if (lane == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // as the next launch expects it
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g == 0 && active) {
-            if (a.accumulate) {                            // (what the first operator left) + p0 + p1 + ..., as the finalize kernel adds
-                const float *o = a.out + (size_t)row * a.ld_out + col0;
-                float x[4] = {0.f, 0.f, 0.f, 0.f};
-                for (int i = 0; i < 4 && col0 + i < a.dim; i++) x[i] = o[i];
-                acc = make_float4(x[0], x[1], x[2], x[3]);
-            }
-            const float *pp = a.partials + (size_t)info.x * a.part_ld + col0;
-            int k = 0;
-            for (; k + 4 <= info.y; k += 4) {               // four partials in flight; left-to-right sum
-                const float4 p0 = *reinterpret_cast<const float4 *>(pp + (size_t)k * a.part_ld);
-                const float4 p1 = *reinterpret_cast<const float4 *>(pp + (size_t)(k + 1) * a.part_ld);
-                const float4 p2 = *reinterpret_cast<const float4 *>(pp + (size_t)(k + 2) * a.part_ld);
-                const float4 p3 = *reinterpret_cast<const float4 *>(pp + (size_t)(k + 3) * a.part_ld);
-                acc = f4_add(acc, p0); acc = f4_add(acc, p1); acc = f4_add(acc, p2); acc = f4_add(acc, p3);
-            }
-            for (; k < info.y; k++) acc = f4_add(acc, *reinterpret_cast<const float4 *>(pp + (size_t)k * a.part_ld));
-        }
-    }
-#endif
     uint32_t nib = 0;                                       // this lane's four (out > 0) bits, at their place in the row's word
     if (g == 0 && active) {
         float *o = a.out + (size_t)row * a.ld_out + col0;
@@ -387,202 +326,6 @@ __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
         if (g == 0 && active && (l & 7) == 0) a.pos_bits[(size_t)row * a.wpr + (col0 >> 5)] = nib;
     }
 }
-
-#ifdef GCNHIP_EXPERIMENTS   // measured-slower variants: compiled only by `make EXPERIMENTS=1`
-// ---- EXPERIMENT: persistent form that also keeps the next chunk's (index, coef) pairs in flight -------------------
-// A wave walks tasks t, t + stride, ... of its XCD group's range; while the rows of chunk k are gathered, the pairs of
-// chunk k+1 (of the same task, or the first chunk of the wave's next task, whose record was fetched a task earlier) are
-// on their way, so one round trip per batch of rows remains.  Same lane groups, same edge order, same reduction tree:
-// bit-identical results.  Measured SLOWER than a wave per task (1.15 vs 0.85 ms, hidden width, Reddit scale) and
-// therefore not the default (GCNHIP_GS_PIPE selects it): see the launch site.
-template <int L>
-__global__ __launch_bounds__(256, 8) void graphsum_pipe_kernel(GsArgs a) {
-    constexpr int G = WAVE / L;
-    const int lane = threadIdx.x & 63;
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int cslice = a.n_slices > 1 ? xcd % a.n_slices : blockIdx.y;
-    const int g_id = xcd / a.n_slices;
-    const int t_end = a.bounds[g_id + 1];
-    const int stride = (gridDim.x >> 3) * 4;                // waves of this XCD
-    // wave-uniform by construction; saying so lets the task records live in scalar registers
-    int t = __builtin_amdgcn_readfirstlane(a.bounds[g_id] + q * 4 + (int)(threadIdx.x >> 6));
-    if (t >= t_end) return;
-    const int g = lane / L, l = lane % L;
-    const int col0 = (cslice * L + l) * 4;
-    const bool active = col0 < a.dim;
-    const float *in = a.in + (active ? col0 : 0);
-    const int last_edge = a.nnz - 1;
-
-    // every prefetch below is an UNCONDITIONAL load from a clamped address: a load inside a branch makes the compiler
-    // wait for it at the end of that branch, which would put the round trip back on the critical path
-    int4 tk = a.tasks[t];
-    int t_nx = t + stride;
-    int4 tk_nx = a.tasks[min(t_nx, t_end - 1)];
-    int base = tk.y;
-    int cnt = min(WAVE, tk.z - base);
-    int my_idx = a.indices[min(base + lane, last_edge)];
-    float my_c = a.coef[min(base + lane, last_edge)];
-    if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (;;) {
-        // ---- the item after this one: next chunk of the task, or first chunk of the wave's next task
-        const bool last = base + WAVE >= tk.z;
-        const bool more = !last || t_nx < t_end;
-        const int nbase = last ? tk_nx.y : base + WAVE;
-        const int nend = last ? tk_nx.z : tk.z;
-        const int ncnt = more ? min(WAVE, nend - nbase) : 0;
-        const int n_idx = a.indices[min(max(nbase + lane, 0), last_edge)];      // in flight while this chunk's rows are gathered
-        float n_c = a.coef[min(max(nbase + lane, 0), last_edge)];
-        // ---- this chunk
-        acc = gather_chunk<L, GS_U>(a, in, my_idx, my_c, cnt, g, acc);
-        if (a.row_bits && !((a.row_bits[n_idx >> 5] >> (n_idx & 31)) & 1u)) n_c = 0.f;
-        if (last) {
-#pragma unroll
-            for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
-            if (g == 0 && active) {
-                if (tk.w >= 0) {
-                    *reinterpret_cast<float4 *>(a.partials + (size_t)tk.w * a.part_ld + col0) = acc;
-                } else {
-                    if (a.fuse) acc = relu_dropout4(acc, a, tk.x, col0);
-                    float *o = a.out + (size_t)tk.x * a.ld_out + col0;
-                    if (col0 + 4 <= a.dim) {
-                        *reinterpret_cast<float4 *>(o) = acc;
-                    } else {
-                        const float x[4] = {acc.x, acc.y, acc.z, acc.w};
-                        for (int i = 0; col0 + i < a.dim; i++) o[i] = x[i];
-                    }
-                }
-            }
-            if (!more) break;
-            acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            tk = tk_nx;
-            t_nx += stride;
-            tk_nx = a.tasks[min(t_nx, t_end - 1)];             // needed at the new task's last chunk, one round trip away at least
-        }
-        base = nbase; cnt = ncnt; my_idx = n_idx; my_c = n_c;
-    }
-}
-
-// ---- packed rows, exact f32 (the backward of the hidden layer) ---------------------------------------
-// The gathered matrix is dH1 = mask . (dZ0 . W2^T): three quarters of it are zeros whose positions are known
-// (ReLU and dropout of H1).  Its producer (gemm_rowstream, PACK) writes every 64-column half of a row as one
-// 128-byte slot — 64-bit mask + the masked-in values in column order — so an edge costs ONE line per half
-// instead of two, with the f32 values untouched.  Edges are split as in graphsum_vec_kernel<16> (the dense gather
-// at widths that are multiples of 64): edge k*4+g of a 64-edge chunk goes to group g of FOUR, the four sums are
-// combined by the same xor tree — so every output element sees the same non-zero terms in the same order and the
-// result is bit-identical to the dense gather (adding c * 0 never changes a sum that started at +0).  A wave covers a
-// PAIR of halves: lane groups 0-3 (8 lanes each) take the even half, groups 4-7 the odd one.
-// A group loads its slot as 8 x 16 bytes (one request), parks it in the wave's LDS scratch, reads the mask back
-// (broadcast) and then each lane picks the values of its 8 columns: position = popcount of the mask below them.
-__global__ __launch_bounds__(256) void graphsum_packed_kernel(GsArgs a, const uint32_t *__restrict__ slots, int halves) {
-    __shared__ uint4 stage[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int t, pair;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        pair = a.n_slices > 1 ? xcd % a.n_slices : blockIdx.y;
-        const int g_id = xcd / a.n_slices;
-        t = a.bounds[g_id] + q * 4 + wave;
-        if (t >= a.bounds[g_id + 1]) return;               // wave-uniform
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
-    const int g8 = lane >> 3, g = g8 & 3, l = lane & 7;
-    const int half = pair * 2 + (g8 >> 2);
-    const bool live = half < halves;                       // an odd number of halves: the last wave's upper groups idle
-    const uint32_t *sbase = slots + (size_t)(live ? half : 0) * 32 + l * 4;
-    const size_t row_stride = (size_t)halves * 32;
-    const uint32_t *mine = reinterpret_cast<const uint32_t *>(&stage[wave][g8 * 8]);
-    const uint32_t sh8 = 8u * (l & 3);                                            // this lane's byte inside its mask word
-    const uint32_t below_lo = l < 4 ? (1u << (8 * l)) - 1u : 0xFFFFFFFFu;         // mask bits of the columns before this lane's
-    const uint32_t below_hi = l < 4 ? 0u : (1u << (8 * (l - 4))) - 1u;
-    float acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) acc[i] = 0.f;
-    for (int base = e0; base < e1; base += WAVE) {
-        const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            my_c = a.coef[base + lane];
-        }
-        const int iters = (cnt + 3) >> 2;
-        // PACKED_U edges per lane group in flight: their slot loads are issued together, then each is parked in LDS and
-        // decoded without branches (a branch per column serialises the loop: one load in flight per wave)
-        constexpr int PACKED_U = 4;
-        for (int k0 = 0; k0 < iters; k0 += PACKED_U) {
-            uint4 piece[PACKED_U];
-            int jj[PACKED_U];
-            float cc[PACKED_U];
-#pragma unroll
-            for (int u = 0; u < PACKED_U; u++) {
-                const int src = (k0 + u) * 4 + g;              // >= 64 wraps in the shuffle; masked by `on`
-                jj[u] = __shfl(my_idx, src & 63, WAVE);
-                cc[u] = __shfl(my_c, src & 63, WAVE);
-                const bool on = src < cnt && live;
-                piece[u] = make_uint4(0u, 0u, 0u, 0u);         // empty mask: contributes nothing
-                if (on) piece[u] = *reinterpret_cast<const uint4 *>(sbase + (size_t)jj[u] * row_stride);
-            }
-#pragma unroll
-            for (int u = 0; u < PACKED_U; u++) {
-                stage[wave][lane] = piece[u];
-                __builtin_amdgcn_wave_barrier();
-                // 32-bit arithmetic only; per column: rank below it (and + bcnt), LDS address, read, bit -> all-ones,
-                // and, fmac.  A masked-out column adds c * (+0), exactly what the dense gather adds there.
-                const uint32_t mlo = mine[0], mhi = mine[1];
-                const int n_half = __popc(mlo) + __popc(mhi);
-                const bool fits = n_half <= PACK_CAP;
-                const uint32_t bits8 = fits ? ((l < 4 ? mlo : mhi) >> sh8) & 0xFFu : 0u;
-                const int off0 = fits ? 2 + __popc(mlo & below_lo) + __popc(mhi & below_hi) : 0;
-                const float c = cc[u];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int off = off0 + __popc(bits8 & ((1u << i) - 1u));          // <= 31 when the half fits
-                    const uint32_t keep = (uint32_t)(((int32_t)(bits8 << (31 - i))) >> 31);   // bit i -> 0 or ~0
-                    acc[i] = fmaf(c, __uint_as_float(mine[off] & keep), acc[i]);
-                }
-                if (!fits) {                                   // this half did not fit its slot: dense image (rare)
-                    const float *d = a.in + (size_t)jj[u] * a.ld_in + half * 64 + 8 * l;
-                    const float4 v0 = *reinterpret_cast<const float4 *>(d), v1 = *reinterpret_cast<const float4 *>(d + 4);
-                    acc[0] = fmaf(c, v0.x, acc[0]); acc[1] = fmaf(c, v0.y, acc[1]); acc[2] = fmaf(c, v0.z, acc[2]); acc[3] = fmaf(c, v0.w, acc[3]);
-                    acc[4] = fmaf(c, v1.x, acc[4]); acc[5] = fmaf(c, v1.y, acc[5]); acc[6] = fmaf(c, v1.z, acc[6]); acc[7] = fmaf(c, v1.w, acc[7]);
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int m = 8; m < 32; m <<= 1) acc[i] += __shfl_xor(acc[i], m, WAVE);
-    if (g == 0 && live) {
-        const int col0 = half * 64 + 8 * l;
-        float *o = slot >= 0 ? a.partials + (size_t)slot * a.part_ld + col0 : a.out + (size_t)row * a.ld_out + col0;
-        *reinterpret_cast<float4 *>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        *reinterpret_cast<float4 *>(o + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    }
-}
-
-// slots -> dense image (tests, introspection): halves that fit are written from their slot, the others are already dense
-__global__ __launch_bounds__(256) void rowpack_expand_kernel(const uint32_t *__restrict__ slots, int halves, int64_t n_half_rows,
-                                                             float *__restrict__ dense, int ld) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_half_rows) return;
-    const uint32_t *s = slots + i * 32;
-    const uint64_t m = (uint64_t)s[0] | ((uint64_t)s[1] << 32);
-    if (__popcll(m) > PACK_CAP) return;
-    float *d = dense + (i / halves) * ld + (i % halves) * 64;
-    int off = 2;
-    for (int c = 0; c < 64; c++) d[c] = ((m >> c) & 1ull) ? __uint_as_float(s[off++]) : 0.f;
-}
-
-#endif  // GCNHIP_EXPERIMENTS
 
 // ---- bf16 table, f32 accumulate (opt-in storage format) ------------------------
 // The gathered rows are stored as bfloat16 (round-to-nearest-even of the f32 values, made by
@@ -1106,24 +849,11 @@ static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c, const
     const int ychunks = ceil_div(a.dim, L * 4);
     const bool sliced = ychunks > 1 && 8 % ychunks == 0;   // XCD-sliced columns (1-D grid)
     a.n_slices = sliced ? ychunks : 1;
-    if (ychunks > 8) { a.seg_count = nullptr; a.slot_info = nullptr; }   // one arrival counter per (split row, column chunk), 8 per row
     const int G = 8 / a.n_slices;                          // XCD groups that share the task list
     const int lg = G == 8 ? 3 : (G == 4 ? 2 : (G == 2 ? 1 : 0));
     int max_blocks = 1;
     for (int k = 0; k <= 8; k++) a.bounds[k] = xb[lg][k];
     for (int k = 0; k < G; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
-    // EXPERIMENT (GCNHIP_GS_PIPE): the persistent form that also prefetches the next chunk's indices.  Measured slower
-    // than a wave per task once the row loads are batched (1.15 vs 0.85 ms at Reddit scale): fresh waves arriving in
-    // task order keep the XCD's window of active rows tight, statically strided persistent waves drift apart.
-#ifdef GCNHIP_EXPERIMENTS
-    const bool pipe = c->opt.gs_pipe != 0;
-    if (pipe && !pred && a.n_tasks && !a.out_bits && !a.accumulate && !a.pos_bits && a.coef) {
-        a.seg_count = nullptr; a.slot_info = nullptr;      // the experiment keeps the finalize launch
-        const int per_xcd = std::min(max_blocks, 32 * 8);
-        graphsum_pipe_kernel<L><<<dim3(per_xcd * 8, sliced ? 1 : ychunks), 256, 0, s>>>(a);
-        return;
-    }
-#endif
     // Batch depth by regime.  A table that fits the 256 MiB Infinity Cache is gathered with 4 row loads in flight per lane
     // group (latency-bound otherwise: 1.08 -> 0.85 ms at Reddit scale).  Past it the kernel is HBM-bound and 2 is the
     // optimum (R-MAT scale 21, 1 GiB table, d = 128: 5.33 / 5.16 / 5.51 ms with 1 / 2 / 4 in flight).
@@ -1137,10 +867,6 @@ static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c, const
             return;
         }
     }
-#ifdef GCNHIP_EXPERIMENTS
-    const bool nt_all = c->opt.gs_nt != 0;                            // EXPERIMENT: every row load non-temporal
-    if (sliced && nt_all && L == 16 && a.coef) { graphsum_vec_kernel<16, 4, true, true><<<grid, 256, 0, s>>>(a); return; }
-#endif
     if (sliced) {
         if (u >= 4) graphsum_vec_kernel<L, 4, true><<<grid, 256, 0, s>>>(a);
         else if (u >= 2) graphsum_vec_kernel<L, 2, true><<<grid, 256, 0, s>>>(a);
@@ -1191,7 +917,6 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
     a.out_bits = out_bits;
     a.accumulate = accumulate;
     a.pos_bits = pos_bits; a.wpr = wpr;
-    a.slot_info = nullptr; a.seg_count = nullptr; a.n_slots_bytes = 0;
     a.post = nullptr;
     const int nt = a.n_tasks ? a.n_tasks : g->n_rows;
     const bool vec = (ld_in % 4 == 0) && (ld_out % 4 == 0) && aligned16(in) && aligned16(out);
@@ -1225,19 +950,6 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         else if (d8 % 16 == 0) launch_bf16<16>(a, xb, c->stream);   // 128-column (two-line) slices as in the f32 kernel: 305 -> 322 epochs/s
         else launch_bf16<8>(a, xb, c->stream, pred);               // 64-column (one line) slices, one per XCD group when 8 % slices == 0
     }
-    // GCNHIP_GS_FOLD (opt-in, round 3): the vector kernel adds the segments of a split row itself (the last segment to finish
-    // does) and no finalize launch follows.  Same bits; measured no faster at 5 K segments and slower as their number grows
-    // (every segment wave keeps its slot through a store drain and an atomic round trip: 0.835 vs 0.774 ms at 20 K segments),
-    // so the default stays the fire-and-forget partial store plus one 8 us launch.  (Context option gs_fold.)
-#ifdef GCNHIP_EXPERIMENTS
-    const bool fold = c->opt.gs_fold != 0;
-#else
-    const bool fold = false;
-#endif
-    if (!in_bf && vec && n_split_rows && g->seg_count && fold && !pred) {
-        a.slot_info = g->slot_info; a.seg_count = g->seg_count;
-        a.n_slots_bytes = (int)std::min<size_t>((size_t)g->n_slots * g->part_ld * sizeof(float), 0x7FFFFFFFu);
-    }
     const int gl = c->opt.gs_l;                             // narrower column slices than 64 floats (8: 32 floats, 4: 16 floats), round 5
     if (in_bf) {
     } else if (vec && !loss && !pred && (gl == 8 || (gl == 4 && !pos_bits)) && dim % (gl * 4) == 0 && dim / (gl * 4) > 1 && 8 % (dim / (gl * 4)) == 0) {
@@ -1269,7 +981,7 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         else launch_scalar<64>(a, nt, c->stream);
     }
     GCNHIP_LAUNCH_CHECK();
-    if (n_split_rows && !a.seg_count) {
+    if (n_split_rows) {
         if (pred) graphsum_finalize_predict_kernel<<<n_split_rows, WAVE, 0, c->stream>>>(a, *pred, split_rows, n_split_rows);
         else graphsum_finalize_kernel<<<n_split_rows, 256, 0, c->stream>>>(a, split_rows, n_split_rows);
         GCNHIP_LAUNCH_CHECK();
@@ -1346,72 +1058,6 @@ int gcnhip_graphsum_predict(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_r
     return graphsum_impl(c, g, in, ld_in, out, out ? ld_out : (dim + 3) / 4 * 4, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, in_bf16, nullptr, rows, 0,
                          nullptr, 0, scaling, nullptr, &pa);
 }
-
-#ifndef GCNHIP_EXPERIMENTS
-int gcnhip_rowpack_create(gcnhip_ctx *, gcnhip_rowpack **, int, int) { return gcnhip_fail("this entry point is a measured-slower experiment: build the library with `make EXPERIMENTS=1`"); }
-int gcnhip_rowpack_destroy(gcnhip_ctx *, gcnhip_rowpack *) { return 0; }
-int gcnhip_rowpack_expand(gcnhip_ctx *, const gcnhip_rowpack *, float *, int) { return gcnhip_fail("this entry point is a measured-slower experiment: build the library with `make EXPERIMENTS=1`"); }
-int gcnhip_graphsum_packed(gcnhip_ctx *, const gcnhip_graph *, const gcnhip_rowpack *, const float *, int, float *, int) { return gcnhip_fail("this entry point is a measured-slower experiment: build the library with `make EXPERIMENTS=1`"); }
-#else
-int gcnhip_rowpack_create(gcnhip_ctx *c, gcnhip_rowpack **out, int rows, int cols) {
-    if (!c || !out || rows < 0 || cols < 64 || cols % 64 != 0) return -1;
-    GCNHIP_TRY(hipSetDevice(c->device));
-    gcnhip_rowpack *p = new gcnhip_rowpack();
-    p->rows = rows; p->cols = cols; p->halves = cols / 64; p->slots = nullptr;
-    const size_t bytes = (size_t)std::max(rows, 1) * p->halves * 128;
-    hipError_t e = hipMalloc((void **)&p->slots, bytes);
-    if (e != hipSuccess) { delete p; return (int)e; }
-    e = hipMemsetAsync(p->slots, 0, bytes, c->stream);      // empty masks: every row reads as zero until it is written
-    if (e != hipSuccess) { hipFree(p->slots); delete p; return (int)e; }
-    *out = p;
-    return 0;
-}
-int gcnhip_rowpack_destroy(gcnhip_ctx *c, gcnhip_rowpack *p) {
-    if (!p) return 0;
-    hipSetDevice(c->device);
-    if (p->slots) hipFree(p->slots);
-    delete p;
-    return 0;
-}
-int gcnhip_rowpack_expand(gcnhip_ctx *c, const gcnhip_rowpack *p, float *dense, int ld) {
-    if (!c || !p || !dense || ld < p->cols) return -1;
-    const int64_t n = (int64_t)p->rows * p->halves;
-    if (n == 0) return 0;
-    rowpack_expand_kernel<<<ceil_div(n, 256), 256, 0, c->stream>>>(p->slots, p->halves, n, dense, ld);
-    GCNHIP_LAUNCH_CHECK();
-    return 0;
-}
-
-int gcnhip_graphsum_packed(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rowpack *p, const float *dense, int ld_dense,
-                           float *out, int ld_out) {
-    if (!c || !g || !p || !dense || !out || p->rows != g->n_cols || ld_dense < p->cols || ld_out < p->cols) return -1;
-    if (ld_dense % 4 != 0 || ld_out % 4 != 0 || !aligned16(dense) || !aligned16(out)) return -1;
-    if (g->n_rows == 0) return 0;
-    if (g->n_slots && g->part_ld < p->cols) return -1;
-    GsArgs a;
-    memset(&a, 0, sizeof a);
-    a.indptr = g->indptr; a.indices = g->indices; a.coef = g->coef;
-    a.tasks = g->tasks; a.n_tasks = g->n_tasks; a.n_rows = g->n_rows; a.nnz = g->nnz;
-    a.in = dense; a.out = out; a.partials = g->partials;
-    a.ld_in = ld_dense; a.ld_out = ld_out; a.part_ld = g->part_ld; a.dim = p->cols;
-    const int pairs = (p->halves + 1) / 2;                  // a wave covers two halves
-    const bool sliced = pairs > 1 && 8 % pairs == 0;
-    a.n_slices = sliced ? pairs : 1;
-    const int G = 8 / a.n_slices;
-    const int lg = G == 8 ? 3 : (G == 4 ? 2 : (G == 2 ? 1 : 0));
-    int max_blocks = 1;
-    for (int k = 0; k <= 8; k++) a.bounds[k] = g->bounds[lg][k];
-    for (int k = 0; k < G; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
-    graphsum_packed_kernel<<<dim3(max_blocks * 8, sliced ? 1 : pairs), 256, 0, c->stream>>>(a, p->slots, p->halves);
-    GCNHIP_LAUNCH_CHECK();
-    if (g->n_split_rows) {
-        graphsum_finalize_kernel<<<g->n_split_rows, 256, 0, c->stream>>>(a, g->split_rows, g->n_split_rows);
-        GCNHIP_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-#endif  // GCNHIP_EXPERIMENTS
 
 int gcnhip_f32_to_bf16(gcnhip_ctx *c, const float *src, int ld_src, uint16_t *dst, int ld_dst, int64_t rows, int dim) {
     if (!c || !src || !dst || rows < 0 || dim <= 0 || ld_src < dim || ld_dst < dim || ld_dst % 8 != 0 || !aligned16(dst)) return -1;

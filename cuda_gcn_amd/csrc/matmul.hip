@@ -103,28 +103,6 @@ int gcnhip_matmul_bwd_fused_bits(gcnhip_ctx *c, const float *a, int lda, const f
     return launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, nullptr, 0, relu_dropout_scale, pos_bits, words_per_row);
 }
 
-// the same with da leaving as packed rows (dense_kernels.h): da_dense receives only the halves that do not fit a slot
-#ifndef GCNHIP_EXPERIMENTS
-int gcnhip_matmul_bwd_packed(gcnhip_ctx *, const float *, int, const float *, int, const float *, int, float *, int, gcnhip_rowpack *,
-                             float *, int, int, int, int, float) {
-    return gcnhip_fail("gcnhip_matmul_bwd_packed is a measured-slower experiment: build the library with `make EXPERIMENTS=1`");
-}
-#else
-int gcnhip_matmul_bwd_packed(gcnhip_ctx *c, const float *a, int lda, const float *b, int ldb,
-                             const float *dc, int lddc, float *da_dense, int ldda, gcnhip_rowpack *pack,
-                             float *db, int lddb, int m, int n, int p, float relu_dropout_scale) {
-    if (!c || !a || !b || !dc || !da_dense || !pack || m < 0 || n <= 0 || p <= 0 || lda < n || ldb < p || lddc < p || ldda < n) return -1;
-    if (pack->rows != m || pack->cols != n) return -1;
-    if (db && lddb < p) return -1;
-    if (m == 0) return matmul_bwd_impl(c, a, lda, b, ldb, dc, lddc, nullptr, 0, db, lddb, m, n, p, 0, 1.f);
-    if (db) {
-        const int rc = launch_atb(c, a, lda, dc, lddc, db, lddb, m, n, p, 0, 0.f, 0, nullptr, 0, nullptr);
-        if (rc) return rc;
-    }
-    return launch_rowstream(c, dc, lddc, b, ldb, 1, da_dense, ldda, m, p, n, a, lda, relu_dropout_scale, nullptr, 0, pack->slots, pack->halves);
-}
-#endif
-
 // Every form of the fused backward behind one call, with an optional factor per row of da (the factored aggregation,
 // gcnhip_graphsum_ex: dH1' = dinv^2 . dH1):  db = a^T . dc when db != NULL (a is then required);
 // da[r, :] = mask . (relu_dropout_scale * da_row_scale[r]) . (dc . b^T)[r, :], mask = pos_bits when given, else a > 0.
@@ -148,7 +126,7 @@ int gcnhip_matmul_bwd_ex(gcnhip_ctx *c, const float *a, int lda, const float *b,
         if (rc) return rc;
     }
     return launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, pos_bits ? nullptr : a, lda, relu_dropout_scale, pos_bits, words_per_row,
-                            nullptr, 0, d_da_row_scale);
+                            d_da_row_scale);
 }
 
 // da for ALL m rows from a bit mask instead of the forward activations (multi-GPU: every rank rebuilds the

@@ -145,7 +145,6 @@ __global__ __launch_bounds__(256) void spmm_dense_fwd_kernel(DenseFwdArgs a) {
 }
 
 constexpr int64_t SPMM_NARROW_MIN_NNZ = 262144;     // below this the general sparse kernels run (option spmm_general = -1: narrow kernels always)
-constexpr size_t SPMM_LDS_MAX_BYTES = 128 * 1024;   // W1 in LDS: Cora 92 KB and Pubmed 32 KB fit (gfx950: 160 KB per CU)
 
 static DropSpec make_drop(float p_drop, uint64_t seed, const uint32_t *d_epoch, uint64_t off, const uint8_t *keep_mask) {
     DropSpec d;
@@ -294,11 +293,6 @@ static int spmm_fwd_impl(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals,
             pa.x = t.x; pa.ldx = t.ldx; pa.wp = c->wpack; pa.out = out; pa.ldo = ld_out;
             pa.m = t.m; pa.K = t.K; pa.n_chunks = n_chunks; pa.n_rb = ceil_div(t.m, 32);
             pa.bits = t.bits; pa.relu = relu;
-#ifdef GCNHIP_EXPERIMENTS
-            pa.dbg_linear = c->opt.dbg_linear ? 1 : 0;
-#else
-            pa.dbg_linear = 0;
-#endif
             const int wgs = std::max(1, std::min(c->n_cu, pa.n_rb));
             if (pa.bits) dense_fwd_persist_kernel<true><<<wgs, 512, 0, c->stream>>>(pa);
             else dense_fwd_persist_kernel<false><<<wgs, 512, 0, c->stream>>>(pa);
@@ -343,49 +337,7 @@ static int spmm_fwd_impl(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals,
     a.rows_per_wave = 1;
     const bool vec = ld_w % 4 == 0 && aligned16(w);
     const int units = vec ? (p + 3) / 4 : p;              // lanes needed for one row of W
-    // W staged in LDS (one 1024-thread workgroup per CU walks rows; north_star's "LDS staging of the feature tile"): built,
-    // bit-identical to the general kernel, and measured SLOWER wherever W fits (round 4, profiles/r04_spmm_lds.log: pubmed-syn
-    // 11.7 vs 9.0 us; 2 M rows x 50 values, F = 500 / 2000, h = 16: 0.91 vs 0.72 / 0.87 ms) — a W that fits LDS also sits in
-    // every XCD's L2, and the rows were never what bound these kernels (spmm_sparse.h).  Opt-in: context option spmm_lds = 1.
-    const size_t w_bytes = (size_t)a.w_floats * sizeof(float);
-    const int wgs = std::max(1, std::min(c->n_cu, ceil_div(f->n_rows, 16)));
-#ifdef GCNHIP_EXPERIMENTS
-    const bool lds_form = c->opt.spmm_lds == 1 && vec && units <= 64 && p <= 256 && w_bytes <= SPMM_LDS_MAX_BYTES && f->n_rows > 0;
-#else
-    const bool lds_form = false;
-    (void)w_bytes; (void)wgs;
-#endif
     a.nnz_bytes = (int)std::min<int64_t>(f->nnz * 4, 0x7FFFFFFF);
-#ifdef GCNHIP_EXPERIMENTS
-    if (lds_form && units <= 16 && f->nnz * 4 < 0x7FFFFFFF && !c->opt.spmm_general) {      // narrow rows: the shuffle-free kernel over LDS
-        const int per_cu = w_bytes <= 32 * 1024 ? 2 : 1;                                    // 1024-thread workgroups: at most two per CU
-        const int wq = std::max(1, std::min(c->n_cu * per_cu, ceil_div(f->n_rows, 16)));
-        a.rows_per_wave = std::max(1, std::min(8, (int)(f->n_rows / ((int64_t)wq * 16 * 4))));
-#define SPLQ(L_)                                                                                                         \
-    do {                                                                                                                 \
-        auto kern = spmm_csr_fwd_q_lds_kernel<L_>;                                                                       \
-        if (w_bytes > 64 * 1024) GCNHIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_bytes)); \
-        kern<<<wq, 1024, w_bytes, c->stream>>>(a);                                                                       \
-    } while (0)
-        if (units <= 1) SPLQ(1); else if (units <= 2) SPLQ(2); else if (units <= 4) SPLQ(4); else if (units <= 8) SPLQ(8); else SPLQ(16);
-#undef SPLQ
-        GCNHIP_LAUNCH_CHECK();
-        return 0;
-    }
-    if (lds_form) {
-#define SPL(L_)                                                                                                          \
-    do {                                                                                                                 \
-        auto kern = spmm_csr_fwd_lds_kernel<L_>;                                                                         \
-        if (w_bytes > 64 * 1024) GCNHIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_bytes)); \
-        kern<<<wgs, 1024, w_bytes, c->stream>>>(a);                                                                      \
-    } while (0)
-        if (units <= 1) SPL(1); else if (units <= 2) SPL(2); else if (units <= 4) SPL(4);
-        else if (units <= 8) SPL(8); else if (units <= 16) SPL(16); else if (units <= 32) SPL(32); else SPL(64);
-#undef SPL
-        GCNHIP_LAUNCH_CHECK();
-        return 0;
-    }
-#endif
     // rows per wave: enough waves to fill every slot about twice, at most 8 rows each (one wave per row on small inputs)
     a.rows_per_wave = std::max(1, std::min(8, (int)(f->n_rows / ((int64_t)c->n_cu * 64))));
     if (c->opt.spmm_rows > 0) a.rows_per_wave = std::min(32, c->opt.spmm_rows);
@@ -462,38 +414,6 @@ static bool dense_bwd_plan(const gcnhip_ctx *c, const gcnhip_feat *f, int p, int
     return true;
 }
 
-// The whole product by the persistent form (dense_persist.h): one workgroup per CU, each with a contiguous share of the rows
-// and ALL of dW in its accumulators; one slab per workgroup.  Returns 1 when the shape is not its (then the split tiles run).
-#ifndef GCNHIP_EXPERIMENTS
-static int dense_bwd_persist(gcnhip_ctx *, const gcnhip_feat *, const float *, const float *, int, int, const DropSpec &) { return 1; }
-#else
-static int dense_bwd_persist(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, const float *dout, int ld_dout, int p, const DropSpec &d) {
-    // EXPERIMENT, opt-in (GCNHIP_GEMM_PERSIST_BWD): measured SLOWER than the split tiles at Reddit scale (0.50 ms without,
-    // 0.61 ms with dropout against 0.387 ms; profiles/r03_gemm_pmc.json: the pipes 41-53 % busy, 37 % of the wave cycles
-    // parked) — ten k-major A reads + ten keep-word pairs per k step and wave make the VALU/LDS side as long as the MFMAs
-    const bool persist_bwd = c->opt.gemm_persist_bwd != 0;
-    if (!persist_bwd || p != 128 || f->n_rows < 1) return 1;
-    const float *x = vals; int ldx = f->n_cols;
-    if (vals == f->values && f->values_pad) { x = f->values_pad; ldx = f->ld_pad; }
-    const int n_xb = ceil_div(f->n_cols, 32);
-    if (ldx % 16 != 0 || ldx > PB_MAX_LDX || n_xb * 32 > ldx || n_xb > 2 * PB_NACC || !aligned16(x) || ld_dout % 4 != 0 || !aligned16(dout)) return 1;
-    const int G = std::max(1, std::min(c->n_cu, ceil_div(f->n_rows, PB_ROWS)));
-    const int p_ld = 128;
-    const int rc = ensure_slab(c, (size_t)G * f->n_cols * p_ld * sizeof(float));
-    if (rc) return rc;
-    PersistBwdArgs a;
-    a.x = x; a.ldx = ldx; a.dout = dout; a.ldd = ld_dout; a.slab = c->slab; a.lds = p_ld;
-    a.m = f->n_rows; a.K = f->n_cols; a.n_xb = n_xb;
-    a.rows_per_wg = ceil_div(f->n_rows, G);
-    a.bits = d.on ? f->keep_bits : nullptr; a.scale = d.scale;
-    if (a.bits) dense_bwd_persist_kernel<true><<<G, 512, 0, c->stream>>>(a);
-    else dense_bwd_persist_kernel<false><<<G, 512, 0, c->stream>>>(a);
-    GCNHIP_LAUNCH_CHECK();
-    c->slab_n = G;
-    return 0;
-}
-#endif
-
 // splits [s0, s1) of the plan into their slabs
 // fresh: the keep decisions of this call have not been made yet (else: whoever made them left them in f->keep_bits)
 static int dense_bwd_part(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, const float *dout, int ld_dout, int p,
@@ -502,13 +422,6 @@ static int dense_bwd_part(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals
     if (!dense_bwd_plan(c, f, p, &rps, &S) || s0 < 0 || s1 > S || s0 > s1) return -1;
     if (s0 == s1) return 0;
     if (d.on && !f->keep_bits) return gcnhip_fail("input dropout on a feature object without a keep-bit array");
-    if (s0 == 0 && s1 == S) {                    // every split at once: the persistent form when the shape is its
-#ifdef GCNHIP_EXPERIMENTS
-        if (c->opt.gemm_persist_bwd != 0) { const int rl = want_keep_layout(c, f, d, 0, fresh); if (rl) return rl; fresh = false; }
-#endif
-        const int rc = dense_bwd_persist(c, f, vals, dout, ld_dout, p, d);
-        if (rc <= 0) return rc;
-    }
     c->slab_n = S;
     const int kt = ceil_div(f->n_cols, 128), pt = ceil_div(p, 128);
     const int p_ld = (p + 3) / 4 * 4;

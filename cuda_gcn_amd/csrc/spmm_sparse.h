@@ -12,9 +12,7 @@
 //  * the backward no longer gives a whole column to ONE wave (Pubmed: 500 waves walking ~2 000 entries each on a 256-CU
 //    chip, 62 us): a column is a task of NW waves (1, 4 or 16 by the mean column length), each wave sums a contiguous
 //    share and the workgroup adds the NW partials IN WAVE ORDER through LDS — deterministic, no atomics; columns longer
-//    than the segment length become several tasks whose partial rows a fold launch adds in order (only then);
-//  * spmm_csr_fwd_lds_kernel: W1 staged once per workgroup into LDS when it fits (north_star's "LDS staging of the
-//    feature tile"), rows then gathered by ds_read — taken when measured faster (launch site).
+//    than the segment length become several tasks whose partial rows a fold launch adds in order (only then).
 #pragma once
 #include "common.h"
 
@@ -97,7 +95,8 @@ struct SpFwdArgs {
     int n_rows, ld_w, ld_out, p;
     DropSpec d;
     int relu;                       // store max(x, 0) (module.cpp:175-185 folded into the producer)
-    int w_floats;                   // LDS form: floats of W to stage (n_cols * ld_w)
+    int w_floats;                   // n_cols * ld_w.  Read by no kernel; dropping it moves the fields below and reorders the
+                                    // sparse forward kernels' argument loads, so it stays until that is measured
     int rows_per_wave;              // consecutive rows a wave of spmm_csr_fwd_kernel walks (1 .. 32)
     int nnz_bytes;                  // size of indices[] and vals[] in bytes (bounds of the narrow-row kernel's buffer loads)
     int n_slices;                   // SLICED kernel: p = n_slices * L * 4 columns, one slice of L * 4 per XCD group (1, 2, 4 or 8)
@@ -236,21 +235,6 @@ __global__ __launch_bounds__(256) void spmm_csr_fwd_kernel(SpFwdArgs a) {
         r = nrow; rb = nrb; re = nre; base = nbase; cnt = ncnt; cur_idx = nxt_idx; cur_v = nxt_v;
     }
 }
-
-#ifdef GCNHIP_EXPERIMENTS   // W staged in LDS: built, bit-identical, measured slower wherever W fits
-// W staged in LDS once per workgroup (16 waves); the workgroup then walks rows wave by wave.  16-byte aligned rows only.
-template <int L>
-__global__ __launch_bounds__(1024) void spmm_csr_fwd_lds_kernel(SpFwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sp_ws[];
-    for (int i = threadIdx.x * 4; i < a.w_floats; i += 1024 * 4)
-        *reinterpret_cast<float4 *>(sp_ws + i) = *reinterpret_cast<const float4 *>(a.w + i);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const uint32_t epoch = (a.d.on && a.d.d_epoch) ? *a.d.d_epoch : 0u;
-    for (int row = blockIdx.x * 16 + (threadIdx.x >> 6); row < a.n_rows; row += gridDim.x * 16)
-        sp_fwd_row<L, true>(a, sp_ws, row, lane, epoch);
-}
-#endif  // GCNHIP_EXPERIMENTS
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The narrow-row kernels (16-byte aligned rows of at most 64 floats: L <= 16 lanes per row — hidden 16 is the reference's
@@ -419,22 +403,6 @@ __global__ __launch_bounds__(256) void spmm_csr_fwd_q_kernel(SpFwdArgs a) {
     const uint32_t epoch = (a.d.on && a.d.d_epoch) ? *a.d.d_epoch : 0u;
     sp_fwd_q_rows<L>(a, a.w, row0, min(K, a.n_rows - row0), lane, epoch);
 }
-
-#ifdef GCNHIP_EXPERIMENTS
-// ... with W staged in LDS once per (persistent) workgroup: the W rows then cost no L2 traffic at all
-template <int L>
-__global__ __launch_bounds__(1024) void spmm_csr_fwd_q_lds_kernel(SpFwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sp_wq[];
-    for (int i = threadIdx.x * 4; i < a.w_floats; i += 1024 * 4)
-        *reinterpret_cast<float4 *>(sp_wq + i) = *reinterpret_cast<const float4 *>(a.w + i);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int K = a.rows_per_wave;
-    const uint32_t epoch = (a.d.on && a.d.d_epoch) ? *a.d.d_epoch : 0u;
-    for (int row0 = (blockIdx.x * 16 + (threadIdx.x >> 6)) * K; row0 < a.n_rows; row0 += gridDim.x * 16 * K)
-        sp_fwd_q_rows<L>(a, sp_wq, row0, min(K, a.n_rows - row0), lane, epoch);
-}
-#endif  // GCNHIP_EXPERIMENTS
 
 // ----------------------------------------------------------- sparse backward
 // A task = (column j of X, entries [q0, q1) of its CSC list, partial slot or -1): dW[j, :] (or the slot's partial row)

@@ -81,7 +81,6 @@ void HipGCN::init(const HipGCNOptions &opt) {
     }
     GCNHIP_CHECK(gcnhip_ctx_create(&env.ctx, opt.device, nullptr));
     if (opt.gemm >= 0) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gemm_bf16x3", opt.gemm ? 2 : 0));   // HIPGCN_GEMM; else the library's default
-    if (opt.fold_training) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gs_fold", 1));                  // (ignored by a library built without the experiments)
     timers.reset(new DeviceTimers(env.ctx));
     timers->enabled = (flags & HIPGCN_TIMERS) != 0;
     env.timers = timers.get();
@@ -107,12 +106,7 @@ void HipGCN::init(const HipGCNOptions &opt) {
     // The factored aggregation (gcnhip_graphsum_ex): no per-edge coefficient stream; the gathered matrices are stored
     // pre-multiplied by dinv of their row (the producers fold the factor into a row-wise epilogue or a value array).  The
     // fused f32 path only; HIPGCN_EDGE_COEF restores the reference's per-edge coefficients.
-    if ((flags & (HIPGCN_PACKED_DH1 | HIPGCN_BWD_PIPELINE)) && !gcnhip_experiments()) {
-        // measured-slower variants live behind the library's compile-time switch (make EXPERIMENTS=1)
-        fprintf(stderr, "gcn-hip: HIPGCN_PACKED_DH1 / HIPGCN_BWD_PIPELINE ignored: libgcnhip.so was built without GCNHIP_EXPERIMENTS\n");
-        flags &= ~(HIPGCN_PACKED_DH1 | HIPGCN_BWD_PIPELINE);
-    }
-    factored_ = !(flags & (HIPGCN_MODULAR | HIPGCN_BF16_TABLES | HIPGCN_PACKED_DH1 | HIPGCN_EDGE_COEF));
+    factored_ = !(flags & (HIPGCN_MODULAR | HIPGCN_BF16_TABLES | HIPGCN_EDGE_COEF));
     const int world = env.comm->size(), rank = env.comm->rank();
     const int N = params.num_nodes, F = params.input_dim, H = params.hidden_dim, C = params.output_dim;
 
@@ -635,19 +629,9 @@ void HipGCN::build_modules() {
             mm->da_row_scale = dinv2_row;                      // dH1' = dinv^2 . mask . (T . W2^T)
             mm->da_row_scale_full = dinv2_col;                 // rows of the gathered table (several GPUs: dH1 rebuilt for all of them)
         }
-        // Opt-in (single GPU, hidden % 64 == 0, dropout >= 0.3 so that a 64-column half averages <= 22 values against
-        // the slot's 30).  dH1 = mask . (dZ0 . W2^T) is ~3/4 zeros at positions known from H1: packed rows halve the
-        // lines per edge of the backward gather with identical bits — but on gfx950 the unpacking (per column: rank,
-        // LDS read, select, fma) costs more issue slots than the halved gather saves: 1.13 ms against 1.075 ms dense
-        // at Reddit scale, so the dense gather stays the default.
-        if (env.comm->size() == 1 && H % 64 == 0 && p >= 0.3f && !env.bf16_tables && (flags & HIPGCN_PACKED_DH1)) {
-            GCNHIP_CHECK(gcnhip_rowpack_create(env.ctx, &dh1_pack, N, H));
-            mm->da_pack = dh1_pack;
-            gs->out_grad_pack = dh1_pack;
-        }
         // single GPU: the ReLU/dropout mask of H1 leaves the aggregation's store epilogue as one bit per element and the
         // Matmul backward reads those instead of H1 (-119 MB per epoch at Reddit scale); HIPGCN_NO_MASK_BITS: re-read H1
-        if (env.comm->size() == 1 && H % 32 == 0 && !env.bf16_tables && !dh1_pack && opt_.mask_bits) {
+        if (env.comm->size() == 1 && H % 32 == 0 && !env.bf16_tables && opt_.mask_bits) {
             const int wpr = H / 32;
             d_pos_bits = dev_upload(env.ctx, std::vector<uint32_t>((size_t)N * wpr, 0u).data(), (size_t)N * wpr);
             gs->mask_bits_out = d_pos_bits;
@@ -660,9 +644,6 @@ void HipGCN::build_modules() {
             gs->pos_bits_full = d_pos_bits; gs->wpr = wpr; gs->out_grad_complete = true;
             mm->pos_bits_full = d_pos_bits; mm->wpr = wpr; mm->all_rows = xplan.table_rows;
         }
-        // Opt-in: measured at Reddit scale, 2 / 4 / 8 blocks: 254 / 240 / 237 epochs/s against 277 on one stream — the
-        // split-K product next to the gather takes the gather's wave slots, and each block launch has its own tail.
-        if ((flags & HIPGCN_BWD_PIPELINE) && !env.bf16_tables && !dh1_pack) build_bwd_pipeline(sm, gs);
         modules.push_back(sm);
         modules.push_back(gs);
         modules.push_back(mm);
@@ -694,44 +675,6 @@ void HipGCN::build_modules() {
         }
         modules.push_back(ce);
     }
-}
-
-// Row blocks for the backward pipeline (module.h, BackwardPipeline): the split ranges of the dense weight gradient are cut
-// into HIPGCN_BWD_CHUNKS (default 4) runs of whole splits, each registered as a row subset of the adjacency object.
-void HipGCN::build_bwd_pipeline(HipSparseMatmul *sm, HipGraphSum *gs) {
-    int rps = 0, n_splits = 0;
-    GCNHIP_CHECK(gcnhip_spmm_bwd_plan(env.ctx, feat, params.hidden_dim, &rps, &n_splits));
-    const int chunks = opt_.bwd_chunks;
-    if (n_splits < 2 * chunks || chunks < 2) return;
-    bwd_pipe.reset(new BackwardPipeline());
-    BackwardPipeline &P = *bwd_pipe;
-    GCNHIP_CHECK(gcnhip_ctx_create(&P.side, device_, nullptr));
-    GCNHIP_CHECK(gcnhip_event_create_sync(&P.ev_done));
-    for (int k = 0; k <= chunks; k++) P.cuts.push_back((int)((int64_t)n_splits * k / chunks));
-    for (int k = 0; k < chunks; k++) {
-        const int r_lo = std::min(n_local, P.cuts[k] * rps), r_hi = std::min(n_local, P.cuts[k + 1] * rps);
-        std::vector<uint32_t> bits((size_t)n_local / 32 + 2, 0u);
-        for (int r = r_lo; r < r_hi; r++) bits[r >> 5] |= 1u << (r & 31);
-        gcnhip_rowset *rs = nullptr;
-        GCNHIP_CHECK(gcnhip_graph_add_rowset(env.ctx, graph, bits.data(), &rs));
-        P.blocks.push_back(rs);
-        void *ev = nullptr;
-        GCNHIP_CHECK(gcnhip_event_create_sync(&ev));
-        P.ev_block.push_back(ev);
-    }
-    sm->pipe = &P;
-    gs->pipe = &P;
-    gs->pipe_consumer = sm;
-}
-
-void HipGCN::destroy_bwd_pipeline() {
-    if (!bwd_pipe) return;
-    BackwardPipeline &P = *bwd_pipe;
-    if (P.side) gcnhip_ctx_sync(P.side);
-    for (void *ev : P.ev_block) gcnhip_event_destroy(ev);
-    if (P.ev_done) gcnhip_event_destroy(P.ev_done);
-    if (P.side) gcnhip_ctx_destroy(P.side);
-    bwd_pipe.reset();                       // the row subsets belong to the adjacency object
 }
 
 // A^.X for this rank's rows (needs every column of the adjacency and the matching rows of X: with several GPUs
@@ -910,7 +853,6 @@ void HipGCN::release() {
     optimizer.reset();
     if (epoch_graph) { gcnhip_graph_exec_destroy(epoch_graph); epoch_graph = nullptr; }
     readback_destroy();
-    destroy_bwd_pipeline();
     env.xlane = nullptr;
     xlane.reset();                                            // its communicator goes before the parent's
     for (gcnhip_graph *g : {graph_loc, graph_rem, graph_bwd_loc, graph_bwd_rem})
@@ -937,7 +879,6 @@ void HipGCN::release() {
     gcnhip_free(env.ctx, d_pred);
     gcnhip_free(env.ctx, d_prob);
     gcnhip_free(env.ctx, d_logp);
-    if (dh1_pack) gcnhip_rowpack_destroy(env.ctx, dh1_pack);
     timers.reset();
     exchange_buffers_destroy(&xbuf);
     owned_comm.reset();
@@ -1418,10 +1359,6 @@ void HipGCN::get_var(int k, bool grad, std::vector<float> &out, int *rows, int *
         // the last forward on this stream was an evaluation whose hidden matrix stayed in registers: run it as its own launch
         static_cast<HipSparseMatmul *>(eval_modules[0])->forward_stored();
         h1_from_fused_eval = false;
-        sync();
-    }
-    if (k == 3 && grad && dh1_pack) {           // introspection: rebuild the dense image of the packed gradient
-        GCNHIP_CHECK(gcnhip_rowpack_expand(env.ctx, dh1_pack, v->grad, v->ld));
         sync();
     }
     out.resize((size_t)v->rows * v->cols);

@@ -49,13 +49,11 @@ enum HipGCNFlags {
     HIPGCN_NO_AGG_FIRST_EVAL = 8192, // evaluation forwards keep the reference's order A^.(X.W1) instead of (A^.X).W1 with A^.X built once
     HIPGCN_EXCHANGE_ALLGATHER = 16384, // multi-GPU: always all-gather whole row blocks before an aggregation
     HIPGCN_EXCHANGE_HALO = 32768,      // ... or always exchange only the rows some local edge points at (default: decided per graph)
-    HIPGCN_BWD_PIPELINE = 262144,      // opt-in: the hidden layer's backward aggregation in row blocks, each block's share of the first
-                                       // layer's weight gradient on a second stream (same bits; measured slower)
     HIPGCN_NO_LABEL_HINT = 524288,     // never use the dataset's labels as row groups of the aggregation's schedule (groups are then
                                        // looked for in the graph itself, cluster.h)
     HIPGCN_MASKED_BWD = 131072,        // the output layer's backward masks the known-zero rows of dZ at every launch instead of
                                        // aggregating through an operator that has lost the edges pointing at them
-    HIPGCN_PACKED_DH1 = 65536,         // opt-in: dH1 reaches the hidden layer's backward gather as packed rows (same bits; measured slower)
+    // 65536 and 262144 are retired (measured-slower variants, removed): not to be reused; a caller that sets them gets the default path
     HIPGCN_NULL_COMM = 1024,     // world > 1 without transport: collectives are no-ops (per-rank compute timing only)
     HIPGCN_NO_ROW_GROUPS = 512,  // keep the aggregation's plain descending-degree row schedule (no timing of alternatives)
     HIPGCN_OVERLAP_EXCHANGE = 1048576,  // multi-GPU: exchanges on their own stream; each aggregation starts on the edges that point at
@@ -95,14 +93,11 @@ struct HipGCNOptions {
     bool loss_epilogue = true;            // HIPGCN_NO_LOSS_EPILOGUE clears: the loss kernel reads the stored logits (round 4) instead of riding in the class-width aggregation's epilogue
     bool mask_bits = true;                // HIPGCN_NO_MASK_BITS clears: the Matmul backward re-reads H1 instead of one bit per element
     bool loss_records_metrics = true;     // HIPGCN_RECORD_LAUNCH clears: the metrics row gets a launch of its own (A/B)
-    int bwd_chunks = 4;                   // HIPGCN_BWD_CHUNKS: row blocks of the opt-in backward pipeline
     bool readback_stream = false;         // HIPGCN_READBACK_STREAM: run()'s read-back copies on a stream of their own (measured slower)
     int readback_group = 0;               // HIPGCN_READBACK_GROUP: epochs per read-back group (0: calibrated)
     // HIPGCN_SCHEDULE=degree|label|dealt[-G]|structure: pin the aggregation's row schedule instead of timing the candidates at
     // load (-1: timed).  A pinned run launches no tuning kernels, so a kernel-trace profile of it holds the epochs' launches only.
     int schedule = -1, schedule_groups = 256;
-    bool fold_training = false;           // HIPGCN_FOLD_TRAINING (experiments build): the TRAINING context's aggregations add split rows' segments
-                                          // inside the launch (context option gs_fold) — no finalize launch to queue behind the validation lane's kernels
     bool slice_tuning = true;             // HIPGCN_NO_SLICE_TUNING clears: the hidden-width aggregation keeps 64-float column slices
                                           // (default: chosen per graph by a rule on its structure, HipGCN::choose_slice_width)
     // HIPGCN_GEMM=f32|bf16x3: arithmetic of the dense first-layer products (0: exact-f32 MFMA, 1: three-plane bf16 split on the
@@ -244,7 +239,6 @@ private:
     bool replicate_l1 = false;
     bool rebuild_dh1 = false;                                  // multi-GPU backward: gather dZ0 + mask bits, rebuild dH1 everywhere
     uint32_t *d_pos_bits = nullptr;                            // [table_rows * wpr]
-    gcnhip_rowpack *dh1_pack = nullptr;                        // dH1 as packed rows (single GPU, hidden % 64 == 0)
     std::vector<std::unique_ptr<HipVariable>> variables;       // index = reference variable number
     HipVariable *input = nullptr, *output = nullptr;
     const float *input_vals = nullptr;                         // what SparseMatmul reads
@@ -267,9 +261,6 @@ private:
     std::pair<float, float> ring_metrics(const float *row) const;   // (loss + L2, accuracy or micro-F1) of a metrics-ring row
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows (predict*)
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
-    std::unique_ptr<BackwardPipeline> bwd_pipe;                 // hidden-layer backward aggregation || dW1 product, in row blocks
-    void build_bwd_pipeline(HipSparseMatmul *sm, HipGraphSum *gs);
-    void destroy_bwd_pipeline();
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

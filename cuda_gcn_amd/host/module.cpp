@@ -47,10 +47,7 @@ void HipMatmul::backward() {
         env->timers->stop(TMR_COMM);
         env->timers->start(TMR_MATMUL_BW);
         rebuild_da(0, all_rows);
-    } else if (fused_bwd_scale > 0.f && da_pack)
-        GCNHIP_CHECK(gcnhip_matmul_bwd_packed(env->ctx, a->data, a->ld, b->data, b->ld, c->grad, c->ld,
-                                              a->grad, a->ld, da_pack, b->grad, b->ld, m, n, p, fused_bwd_scale));
-    else if (fused_bwd_scale > 0.f)             // mask from the bits the aggregation left, else from a > 0; da rows x dinv^2 when factored
+    } else if (fused_bwd_scale > 0.f)             // mask from the bits the aggregation left, else from a > 0; da rows x dinv^2 when factored
         GCNHIP_CHECK(gcnhip_matmul_bwd_ex(env->ctx, a->data, a->ld, b->data, b->ld, c->grad, c->ld, a->grad, a->ld, b->grad, b->ld, m, n, p,
                                           fused_bwd_scale, mask_bits, mask_bits ? mask_wpr : 0, da_row_scale));
     else
@@ -100,23 +97,7 @@ void HipSparseMatmul::forward_stored() {
     hidden_not_stored = false;
 }
 
-void HipSparseMatmul::backward_part(int k) {
-    const float pd = last_training ? fused_dropout : 0.f;
-    GCNHIP_CHECK(gcnhip_spmm_bwd_part(pipe->side, sp, *vals, c->grad, c->ld, p, pd, env->seed ^ KEY_INPUT_DROPOUT, env->d_epoch,
-                                      nnz_offset, pd > 0.f ? env->keep_input_bwd : nullptr, pipe->cuts[k], pipe->cuts[k + 1], k == 0));
-}
-
-void HipSparseMatmul::backward_finish() {
-    GCNHIP_CHECK(gcnhip_spmm_bwd_finish(pipe->side, sp, b->grad, b->ld, p));
-    GCNHIP_CHECK(gcnhip_event_record(pipe->side, pipe->ev_done));
-}
-
 void HipSparseMatmul::backward() {
-    if (pipe && pipe->armed) {                  // the producer of c->grad has already run this product on the second stream
-        GCNHIP_CHECK(gcnhip_stream_wait_event(env->ctx, pipe->ev_done));
-        pipe->armed = false;
-        return;
-    }
     env->timers->start(TMR_SPMATMUL_BW);
     const float pd = last_training ? fused_dropout : 0.f;     // the same X~ the forward saw (module.cpp:72)
     int rps = 0, n_splits = 0;
@@ -321,26 +302,9 @@ void HipGraphSum::backward() {
     const float *src = out->full_grad ? out->full_grad : out->grad;
     env->timers->start(TMR_GRAPHSUM_BW);
     if (dim > 64) env->timers->start(TMR_GRAPHSUM_WIDE);
-    if (pipe && pipe_consumer && !env->timers->enabled && !out_grad_pack && !row_bits && !bwd_graph) {
-        // (with per-op timers on, every launch runs alone on the main stream: the branches below)
-        const size_t nb = pipe->blocks.size();
-        for (size_t k = 0; k < nb; k++) {
-            gcnhip_gs_opts ob = {};
-            ob.rows = pipe->blocks[k]; ob.scaling = bwd_scaling;
-            GCNHIP_CHECK(gcnhip_graphsum_ex(env->ctx, graph, &ob, src, out->ld, in->grad, in->ld, dim));
-            GCNHIP_CHECK(gcnhip_event_record(env->ctx, pipe->ev_block[k]));
-            GCNHIP_CHECK(gcnhip_stream_wait_event(pipe->side, pipe->ev_block[k]));
-            pipe_consumer->backward_part((int)k);
-        }
-        pipe_consumer->backward_finish();
-        pipe->armed = true;
-    } else if (out_grad_pack)
-        GCNHIP_CHECK(gcnhip_graphsum_packed(env->ctx, graph, out_grad_pack, src, out->ld, in->grad, in->ld));
-    else {
-        gcnhip_gs_opts o = {};
-        o.in_row_bits = row_bits; o.scaling = bwd_scaling;
-        GCNHIP_CHECK(gcnhip_graphsum_ex(env->ctx, graph, &o, src, out->ld, in->grad, in->ld, dim));
-    }
+    gcnhip_gs_opts o = {};
+    o.in_row_bits = row_bits; o.scaling = bwd_scaling;
+    GCNHIP_CHECK(gcnhip_graphsum_ex(env->ctx, graph, &o, src, out->ld, in->grad, in->ld, dim));
     if (dim > 64) env->timers->stop(TMR_GRAPHSUM_WIDE);
     env->timers->stop(TMR_GRAPHSUM_BW);
 }

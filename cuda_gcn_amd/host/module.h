@@ -14,7 +14,6 @@
 #include <cstdint>
 #include "comm.h"
 #include "gcnhip_driver.h"
-#include "gcnhip_experimental.h"   // the opt-in packed-dH1 path (HIPGCN_PACKED_DH1, experiments build only)
 #include "timer.h"
 #include "variable.h"
 
@@ -41,19 +40,6 @@ struct HipEnv {
     void *pos_bits_ready = nullptr;          // event of the in-flight exchange of the H1 > 0 bits (forward -> Matmul backward)
 };
 
-// The hidden layer's backward aggregation hands dH0 to the weight gradient dW1 = X~^T . dH0 in row blocks: the
-// aggregation of block k+1 (gather-bound) runs beside the split-K product of block k (MFMA-bound) on a second stream.
-// Same kernels on the same rows and the same split ranges as the one-stream order: not a bit changes.  OPT-IN
-// (HIPGCN_BWD_PIPELINE): on one MI355X it measured slower than the one-stream order (gcn.cpp, build_modules).
-struct BackwardPipeline {
-    gcnhip_ctx *side = nullptr;              // the second stream (it owns the split-K slabs of the product)
-    std::vector<gcnhip_rowset *> blocks;     // row blocks, registered on the hidden layer's adjacency object
-    std::vector<int> cuts;                   // block k = splits [cuts[k], cuts[k+1]) of gcnhip_spmm_bwd_plan
-    std::vector<void *> ev_block;            // main stream: block k of dH0 is complete
-    void *ev_done = nullptr;                 // side stream: dW1 is complete
-    bool armed = false;                      // the backward in progress went through the pipeline
-};
-
 class Module {
 public:
     virtual void forward(bool) = 0;
@@ -71,9 +57,6 @@ public:
     // one bit per element of a > 0, and every rank rebuilds da for ALL rows (gcnhip_matmul_bwd_da_bits)
     const uint32_t *pos_bits_full = nullptr;    // [all_rows x wpr], gathered by the producer of `a`
     int wpr = 0, all_rows = 0;
-    // single GPU, fused backward: da leaves as packed rows (gcnhip_matmul_bwd_packed); a->grad keeps only the halves
-    // that do not fit a slot.  The consumer is the GraphSum that owns the same pack.
-    gcnhip_rowpack *da_pack = nullptr;
     // single GPU, fused backward: the ReLU/dropout mask as one bit per element, left by the producer of `a`
     // (gcnhip_graphsum_relu_dropout_bits): da does not read `a` again
     const uint32_t *mask_bits = nullptr;
@@ -112,9 +95,6 @@ public:
     HipMatmul *fuse_next = nullptr; // relu_out: the Matmul that consumes `c` and nothing else does — both products in one launch
     bool hidden_not_stored = false; // the last forward was that fused launch: `c` does not hold this forward's hidden matrix
     void forward_stored();          // the evaluation forward as its own launch, `c` stored (what get_var(3) asks for after a fused one)
-    BackwardPipeline *pipe = nullptr;       // set: the producer of c->grad may run backward_part/_finish block by block
-    void backward_part(int block);
-    void backward_finish();
     HipSparseMatmul(HipEnv *env, const float *const *vals, HipVariable *b, HipVariable *c, gcnhip_feat *sp,
                     int m, int n, int p, float fused_dropout, uint64_t nnz_offset);
     void forward(bool) override;
@@ -146,8 +126,6 @@ public:
     // rows of `out` that the consumer reads in forward() (bit = 1); the others are not computed.  NULL: all rows.
     // The last aggregation sets it: loss and accuracy read only rows of the scored split (module.cpp:131-133).
     gcnhip_rowset *const *fwd_out_rows = nullptr;
-    // backward(): out->grad arrives as packed rows (written by HipMatmul::backward into the same pack)
-    gcnhip_rowpack *out_grad_pack = nullptr;              // a subset registered on `graph` (gcnhip_graph_add_rowset)
     // HIPGCN_OVERLAP_EXCHANGE: `graph` cut in two by the owner of the column (gcnhip_graph_create_restricted, twice): the
     // edges that point at this rank's own rows, and the rest.  forward()/backward() then start the exchange on the
     // exchange stream, aggregate through `loc` meanwhile, wait, and add the terms of `rem` (gcnhip_graphsum_part).
@@ -155,9 +133,6 @@ public:
     const gcnhip_graph *split_loc = nullptr, *split_rem = nullptr;
     const gcnhip_graph *bwd_split_loc = nullptr, *bwd_split_rem = nullptr;
     gcnhip_rowset *const *fwd_out_rows_loc = nullptr, *const *fwd_out_rows_rem = nullptr;
-    // backward(): in->grad is produced block by block and handed to this consumer's weight gradient (BackwardPipeline)
-    BackwardPipeline *pipe = nullptr;
-    HipSparseMatmul *pipe_consumer = nullptr;
     // gcnhip_graphsum_ex scaling of the forward / backward aggregation: 0 = the reference's per-edge coefficients; factored
     // model: hidden layer forward 2 (result x dinv^2: already scaled for the class-width aggregation), class layer forward 1
     // (true logits), every backward 3 (the consumer's operand carries the factor)

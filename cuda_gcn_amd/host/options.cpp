@@ -7,8 +7,6 @@
 HipGCNOptions HipGCNOptions::from_environment(HipGCNOptions o) {
     static const struct { const char *name; int bit; } flag_vars[] = {
         {"HIPGCN_EDGE_COEF", HIPGCN_EDGE_COEF},
-        {"HIPGCN_PACKED_DH1", HIPGCN_PACKED_DH1},
-        {"HIPGCN_BWD_PIPELINE", HIPGCN_BWD_PIPELINE},
         {"HIPGCN_STRUCTURE_PARTITION", HIPGCN_STRUCTURE_PARTITION},
         {"HIPGCN_ID_PARTITION", HIPGCN_ID_PARTITION},
         {"HIPGCN_NO_LABEL_HINT", HIPGCN_NO_LABEL_HINT},
@@ -29,9 +27,7 @@ HipGCNOptions HipGCNOptions::from_environment(HipGCNOptions o) {
     if (getenv("HIPGCN_NO_LOSS_EPILOGUE")) o.loss_epilogue = false;
     if (getenv("HIPGCN_NO_EVAL_FUSION")) o.eval_fusion = false;
     if (getenv("HIPGCN_NO_SLICE_TUNING")) o.slice_tuning = false;
-    if (getenv("HIPGCN_FOLD_TRAINING")) o.fold_training = true;
     if (getenv("HIPGCN_RECORD_LAUNCH")) o.loss_records_metrics = false;
-    if (const char *e = getenv("HIPGCN_BWD_CHUNKS")) o.bwd_chunks = atoi(e);
     if (const char *e = getenv("HIPGCN_READBACK_STREAM")) o.readback_stream = atoi(e) != 0;
     if (const char *e = getenv("HIPGCN_READBACK_GROUP")) o.readback_group = atoi(e);
     if (const char *e = getenv("HIPGCN_SCHEDULE")) {

@@ -12,7 +12,7 @@
  *
  * This header is the 1:1 surface: what such a binding calls.  The fused, restricted, row-subset,
  * mask-bit, factored and graph-replay variants that THIS repository's host driver (cuda_gcn_amd/host) adds on top are
- * its private protocol and live in gcnhip_driver.h; measured-slower experiments in gcnhip_experimental.h.
+ * its private protocol and live in gcnhip_driver.h.
  *
  * Conventions
  *  - extern "C", plain pointers and sizes, no C++/torch types.
@@ -60,11 +60,9 @@ int  gcnhip_ctx_destroy(gcnhip_ctx *ctx);
  * from the environment variable GCNHIP_<NAME IN CAPITALS>, which is read ONCE, when the context is created: no entry point
  * consults the environment at call time, so a call's behaviour is a function of its arguments and its context.  Most are
  * A/B aids behind measurements DESIGN.md records; results are the same bits unless the option's line says otherwise:
- *   gs_u (0: by table size; 1/2/4 row loads in flight per lane group of the aggregation), gs_fold (1: split rows summed inside
- *   the aggregation launch), gs_pipe, gs_nt (measured-slower aggregation variants), gemm_tiles / gemm_w4 / gemm_persist_bwd
+ *   gs_u (0: by table size; 1/2/4 row loads in flight per lane group of the aggregation), gemm_tiles / gemm_w4
  *   (first-layer GEMM forms), xent_finalize / adam_sum_launch (final reductions as their own launches), xent_wave,
- *   atb_cap_mb, rs_wgs, spmm_lds (1: the sparse forward stages W in LDS whenever
- *   it fits — measured slower, opt-in), spmm_rows (rows per wave of the sparse forward; 0: by row count), spmm_general (1: narrow
+ *   atb_cap_mb, rs_wgs, spmm_rows (rows per wave of the sparse forward; 0: by row count), spmm_general (1: narrow
  *   rows take the general sparse kernels too — a differently associated f32 sum), spmm_nw and split_edges (read by gcnhip_feat_create / gcnhip_graph_create*: set them BEFORE building objects). */
 int  gcnhip_ctx_set_option(gcnhip_ctx *ctx, const char *name, int value);
 int  gcnhip_ctx_get_option(const gcnhip_ctx *ctx, const char *name, int *value);
@@ -74,10 +72,7 @@ const char *gcnhip_error_string(int code);
 /* detail of the calling thread's most recent -1 (argument error) where the library has one to give, else "" */
 const char *gcnhip_last_error(void);
 const char *gcnhip_version(void);
-/* 1 when the library was built with `make EXPERIMENTS=1`: the variants DESIGN.md records as built, bit-identical and SLOWER
- * (packed rows: gcnhip_rowpack_*, gcnhip_matmul_bwd_packed, gcnhip_graphsum_packed; the options gs_pipe, gs_nt, gs_fold,
- * gemm_persist_bwd, spmm_lds, dbg_linear) are compiled in.  The default build leaves them out: those entry points then
- * return -1 (gcnhip_last_error() says why) and those options are ignored. */
+/* Always 0: the separate experiments build of the library no longer exists (kept so that existing callers still link). */
 int gcnhip_experiments(void);
 
 /* ---- memory (CUDAVariable ctor/dtor/zero: src/cuda/cuda_variable.cu:3-31) ---- */

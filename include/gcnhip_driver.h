@@ -19,7 +19,6 @@ extern "C" {
 #endif
 
 typedef struct gcnhip_rowset gcnhip_rowset;   /* a registered subset of an adjacency object's rows */
-typedef struct gcnhip_rowpack gcnhip_rowpack; /* a mostly-zero matrix stored as packed rows (gcnhip_experimental.h) */
 
 /* Hint: the launches of this context are meant to run BESIDE another stream's kernels (HipGCN's validation lane next to
  * the training pass).  Ops that have a whole-chip persistent form (the dense first-layer GEMM: one 512-thread workgroup
@@ -264,9 +263,6 @@ int gcnhip_matmul_bwd_ex(gcnhip_ctx *ctx, const float *a, int lda, const float *
                          const float *dc, int lddc, float *da, int ldda, float *db, int lddb,
                          int m, int n, int p, float relu_dropout_scale, const uint32_t *pos_bits, int words_per_row,
                          const float *d_da_row_scale);
-
-/* (The packed-dH1 entry points — gcnhip_rowpack_*, gcnhip_matmul_bwd_packed, gcnhip_graphsum_packed: built, bit-identical,
- * measured slower, compiled only by `make EXPERIMENTS=1` — are declared in gcnhip_experimental.h, not in this header.) */
 
 /* Multi-GPU form of the same backward.  dH1 = mask . (dZ0 . W2^T) is cheap to recompute and 128 floats wide,
  * while its inputs are 48 floats (dZ0) and 1 bit per element (mask = H1 > 0): ranks all-gather those and each

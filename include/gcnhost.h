@@ -48,11 +48,7 @@ enum {
     GCNHOST_EXCHANGE_ALLGATHER = 16384, /* multi-GPU: always all-gather whole row blocks before an aggregation */
     GCNHOST_EXCHANGE_HALO = 32768,      /* ... or always exchange only the needed rows, peer to peer (default: decided per graph;
                                            env HIPGCN_EXCHANGE=halo|allgather) */
-    GCNHOST_PACKED_DH1 = 65536,       /* opt-in: dH1 travels to the hidden layer's backward gather as packed rows (bit-identical to the
-                                         dense gather, measured slower on gfx950; env HIPGCN_PACKED_DH1=1 does the same) */
-    GCNHOST_BWD_PIPELINE = 262144,    /* opt-in: hidden-layer backward aggregation in row blocks, each block's share of the first layer's
-                                         weight gradient on a second stream (bit-identical; measured slower on one MI355X; env
-                                         HIPGCN_BWD_PIPELINE=1; HIPGCN_BWD_CHUNKS sets the number of blocks, default 4) */
+    /* 65536 and 262144 are retired (measured-slower variants, removed): not to be reused; setting them selects the default path */
     GCNHOST_NO_LABEL_HINT = 524288,   /* the labels are never used as row groups of the aggregation's schedule; groups are looked for in the
                                          graph itself (modularity local moving) and used if they time faster (env HIPGCN_NO_LABEL_HINT=1) */
     GCNHOST_MASKED_BWD = 131072,      /* the output layer's backward masks the rows of dZ outside the training split at every launch

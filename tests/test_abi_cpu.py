@@ -15,10 +15,9 @@ def header_functions(path):
     return sorted(set(re.findall(r"\b(gcn(?:hip|host)_\w+)\s*\(", txt)))
 
 
-def test_gcnhip_exports_every_declared_symbol():
+def test_gcnhip_exports_the_symbols_of_both_headers():
     """gcnhip.h = the 1:1 surface a binding into the reference calls; gcnhip_driver.h = the protocol of this
-    repository's host driver; gcnhip_experimental.h = measured-slower variants.  The library exports all three sets and the
-    python binding table covers them exactly."""
+    repository's host driver.  The library exports both sets and the python binding table covers them exactly."""
     from cuda_gcn_amd import _lib
     lib = _lib.gcnhip()
     names = header_functions(os.path.join(ROOT, "include", "gcnhip.h"))
@@ -29,13 +28,7 @@ def test_gcnhip_exports_every_declared_symbol():
     assert len(drv) >= 30
     for n in drv:
         assert hasattr(lib, n), f"{n} declared in gcnhip_driver.h but not exported"
-    # the measured-slower variants live in their own header (not part of the drop-in surface); their symbols exist in every
-    # build (they return -1 with a message unless the library was built with EXPERIMENTS=1)
-    exp = [n for n in header_functions(os.path.join(ROOT, "include", "gcnhip_experimental.h")) if n not in names and n not in drv]
-    assert exp and all("rowpack" in n or "packed" in n for n in exp), exp
-    for n in exp:
-        assert hasattr(lib, n), f"{n} declared in gcnhip_experimental.h but not exported"
-    assert sorted(_lib.GCNHIP_SYMBOLS) == sorted(names + drv + exp)
+    assert sorted(_lib.GCNHIP_SYMBOLS) == sorted(names + drv)
 
 
 def test_integration_binding_needs_only_the_stable_header():

@@ -375,27 +375,6 @@ def test_aggregate_first_eval_matches_reference_order(name, hidden):
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("name,hidden", [("reddit-mini", 128), ("cora-syn", 64)])
-def test_packed_dh1_is_bit_identical_to_dense(name, hidden, experiments, monkeypatch):
-    """dH1 travelling as packed rows from the Matmul backward to the hidden layer's backward aggregation changes
-    no bit of any weight or reported number.  (Both models on the exact-f32 MFMA kernels: the packed producer
-    gcnhip_matmul_bwd_packed is an f32 row-stream kernel, while the default class-layer backward has been the bf16x3 kernel
-    since round 5 — another, equally bounded, rounding of the same dH1.  Found in round 6, the first full run of the
-    experiments build since then: ten epochs of identical traces, the eleventh training loss one ulp apart.)"""
-    from cuda_gcn_amd.model import HipGCNModel, PACKED_DH1, EDGE_COEF
-    monkeypatch.setenv("HIPGCN_GEMM", "f32")
-    ds = datagen.make_dataset(name)
-    a = HipGCNModel(ds, seed=8, flags=EDGE_COEF, hidden_dim=hidden, dropout=0.5, epochs=12)   # (packed rows imply the per-edge coefficients)
-    b = HipGCNModel(ds, seed=8, flags=PACKED_DH1, hidden_dim=hidden, dropout=0.5, epochs=12)
-    ta, tb = a.run_epochs(10), b.run_epochs(10)
-    assert np.array_equal(ta.view(np.uint32), tb.view(np.uint32))
-    assert a.train_epoch() == b.train_epoch()
-    assert np.array_equal(a.var(2).view(np.uint32), b.var(2).view(np.uint32))
-    assert np.array_equal(a.var(3, True).view(np.uint32), b.var(3, True).view(np.uint32))     # dH1 itself (expanded)
-    assert np.array_equal(a.var(1, True).view(np.uint32), b.var(1, True).view(np.uint32))     # dH0 = A^ . dH1
-    a.close(); b.close()
-
-
 @pytest.mark.parametrize("name,hidden", [("reddit-mini", 128), ("cora-syn", 16)])
 def test_restricted_backward_operator_matches_masked_launch(name, hidden):
     """the output layer's backward through the operator that has lost the edges pointing outside the training split
@@ -410,27 +389,6 @@ def test_restricted_backward_operator_matches_masked_launch(name, hidden):
     assert np.allclose(ga, gb, rtol=1e-4, atol=1e-5 * float(np.abs(gb).max()))
     ta, tb = a.run_epochs(10), b.run_epochs(10)
     assert np.allclose(ta, tb, rtol=2e-4, atol=2e-5)
-    a.close(); b.close()
-
-
-@pytest.mark.parametrize("extra", ["graph", "no_graph", "lane"])
-def test_backward_pipeline_is_bit_identical(extra, monkeypatch, experiments):
-    """opt-in BWD_PIPELINE: hidden-layer backward aggregation in row blocks with each block's share of dW1 on a second
-    stream against the one-stream order: same kernels, same rows, same split ranges — not a bit of any trace or
-    weight differs, replayed from a captured hipGraph, eagerly, or beside the validation lane"""
-    from cuda_gcn_amd.model import HipGCNModel, BWD_PIPELINE, NO_GRAPH, EVAL_LANE
-    monkeypatch.setenv("HIPGCN_BWD_CHUNKS", "3")
-    fl = {"graph": 0, "no_graph": NO_GRAPH, "lane": EVAL_LANE}[extra]
-    ds = datagen.make_dataset("reddit-mini")
-    a = HipGCNModel(ds, seed=8, flags=fl | BWD_PIPELINE, hidden_dim=128, dropout=0.5, epochs=16)
-    b = HipGCNModel(ds, seed=8, flags=fl, hidden_dim=128, dropout=0.5, epochs=16)
-    ta, tb = a.run_epochs(12), b.run_epochs(12)
-    assert np.array_equal(ta.view(np.uint32), tb.view(np.uint32))
-    assert a.train_epoch() == b.train_epoch()
-    for v in (2, 5):
-        assert np.array_equal(a.var(v).view(np.uint32), b.var(v).view(np.uint32))
-        assert np.array_equal(a.var(v, True).view(np.uint32), b.var(v, True).view(np.uint32))
-    assert np.array_equal(a.var(1, True).view(np.uint32), b.var(1, True).view(np.uint32))       # dH0, block by block
     a.close(); b.close()
 
 

@@ -1,15 +1,15 @@
-"""400 epochs of the full-size workload on one GPU, three ways: one stream replaying the captured hipGraph epoch, the
-validation lane on a second stream (bench.py's default with one GPU), and the opt-in two-stream backward pipeline.
-Stream ordering is what this checks at full size: the three traces must agree to the bit, epoch by epoch.
+"""400 epochs of the full-size workload on one GPU, two ways: one stream replaying the captured hipGraph epoch, and the
+validation lane on a second stream (bench.py's default with one GPU).
+Stream ordering is what this checks at full size: the two traces must agree to the bit, epoch by epoch.
 Run on the GPU box:  python tests/validation/soak_400_epochs.py"""
 import sys; sys.path.insert(0, '.')
 import numpy as np
 from cuda_gcn_amd import datagen
-from cuda_gcn_amd.model import HipGCNModel, EVAL_LANE, BWD_PIPELINE
+from cuda_gcn_amd.model import HipGCNModel, EVAL_LANE
 
 ds = datagen.make_dataset("reddit-syn")
 traces = {}
-for name, flags in (("one stream", 0), ("validation lane", EVAL_LANE), ("backward pipeline + lane", EVAL_LANE | BWD_PIPELINE)):
+for name, flags in (("one stream", 0), ("validation lane", EVAL_LANE)):
     m = HipGCNModel(ds, seed=11, flags=flags, hidden_dim=128, dropout=0.5, epochs=400)
     tr = m.run_epochs(400)
     test = m.eval(3)

@@ -98,7 +98,7 @@ def main():
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--nnz-row", type=int, default=50)
     ap.add_argument("--cols", type=int, default=50_000)
-    ap.add_argument("--only", choices=["big", "small", "skew", "lds", "rows"], default=None)
+    ap.add_argument("--only", choices=["big", "small", "skew", "rows"], default=None)
     ap.add_argument("--hidden", type=int, nargs="*", default=[128, 16])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
@@ -121,24 +121,6 @@ def main():
         print(f"skewed X: longest column {cnt.max()} entries, median {int(np.median(cnt))}", flush=True)
         for h in a.hidden:
             doc[f"skew_h{h}"] = dict(leg(dev, "skew", ip, ix, v, a.cols, h, a.iters), longest_column=int(cnt.max()))
-    if a.only == "lds":
-        # W staged in LDS (option spmm_lds = 1) against rows gathered through L1/L2 (0): shapes whose W fits LDS
-        for name in ("pubmed-syn", "cora-syn"):
-            ds = datagen.make_dataset(name)
-            for lds, general in ((0, 1), (1, 1), (0, -1), (1, -1)):
-                dev.set_option("spmm_lds", lds)
-                dev.set_option("spmm_general", general)
-                tag = ("general" if general == 1 else "narrow") + ("+lds" if lds else "")
-                doc[f"{name}_{tag}"] = leg(dev, f"{name} {tag}", ds["f_indptr"], ds["f_indices"], ds["f_val"], ds["input_dim"], 16, 300)
-        for F in (500, 2000):
-            ip, ix, v = synthetic_x(a.rows, a.nnz_row, F)
-            for lds, general in ((0, 1), (1, 1), (0, 0), (1, 0)):
-                dev.set_option("spmm_lds", lds)
-                dev.set_option("spmm_general", general)
-                tag = ("general" if general else "narrow") + ("+lds" if lds else "")
-                doc[f"F{F}_{tag}"] = leg(dev, f"N={a.rows} F={F} {tag}", ip, ix, v, F, 16, a.iters)
-        dev.set_option("spmm_lds", 0)
-        dev.set_option("spmm_general", 0)
     if a.only == "rows":
         ip, ix, v = synthetic_x(a.rows, a.nnz_row, a.cols)
         for h in a.hidden:
