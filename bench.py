@@ -26,13 +26,21 @@ valid line last.
 Prints ONE JSON line on rank 0 (contract fields + "roofline" + "cpu_baseline").
   * `value` / `ms_per_step`: exactly K epochs, barrier + synchronize on both sides, max over ranks,
     on the product's default path (per-op timers OFF: one GPU replays the captured hipGraph epoch);
+  * `final`, `config`, `setup_s`: the last timed step's metrics, what ran, the dataset's and the model's set-up time.
+A plain run stops there (`full`: false; `roofline` and `cpu_baseline` are null): set up, warm up, the K timed steps,
+`--dump-outputs`, the line.  With `--full` the same process goes on, after the headline and without changing it, to:
   * `bursts`: the same timed region repeated, median / min / max epochs/s;
+  * `sustained`, `breakdown_ms_per_epoch`, `train_only_ms_per_epoch`: a long back-to-back region, a per-op timers pass,
+    train-only epochs;
   * `roofline`: the dominant kernel (GraphSum at the hidden width) timed with HIP events on its own
     stream in a separate pass of the same process (timers ON), against the bound that binds it;
   * `roofline.hbm_regime`: the same kernel on an R-MAT graph whose table (1 GiB) is far beyond the
     Infinity Cache — the fraction of the HBM roofline proper;
   * `value_no_label_hint`: the headline with the dataset's labels withheld from the aggregation's row schedule (row
-    groups are then found in the graph itself by modularity local moving); `value_no_row_groups`: no row groups at all.
+    groups are then found in the graph itself by modularity local moving); `value_no_row_groups`: no row groups at all;
+  * `value_reference_op_order_all_rows`, `value_f32_products`, `structure_legs`, `roofline_dense`, `cli`, `cpu_baseline`.
+With N > 1 the launcher above picks the schedule the same way in both modes (its best line is the headline); `--full`
+reaches every rank of every schedule.
 """
 import argparse
 import json
@@ -104,20 +112,24 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--dataset", default="reddit-syn")
-    ap.add_argument("--bursts", type=int, default=4, help="extra repetitions of the K-step timed region (median/min/max)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cli", action="store_true", help="skip the `cli` block (the shipped gcn-hip binary on the same workload from its .gcnbin cache)")
-    ap.add_argument("--cli-epochs", type=int, default=100, help="epochs of the `cli` block's run (the reference's default epoch count)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the HBM-regime leg, the structure legs, the structure-blind reruns and the `cli` block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: bursts, the sustained region, the per-op timers pass and the rooflines, "
+                         "the other models and graphs, the `cli` block and the CPU baseline (the options below marked --full trim it)")
+    ap.add_argument("--bursts", type=int, default=4, help="--full: extra repetitions of the K-step timed region (median/min/max)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cli", action="store_true", help="--full: skip the `cli` block (the shipped gcn-hip binary on the same workload from its .gcnbin cache)")
+    ap.add_argument("--cli-epochs", type=int, default=100, help="--full: epochs of the `cli` block's run (the reference's default epoch count)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the sustained region, the HBM-regime leg, the dense leg, the structure legs, the structure-blind reruns and the `cli` block")
     ap.add_argument("--no-structure-legs", action="store_true",
-                    help="skip the Reddit-shaped graphs with other planted structure (homophily 0 / 0.3, Zipf class sizes)")
+                    help="--full: skip the Reddit-shaped graphs with other planted structure (homophily 0 / 0.3, Zipf class sizes)")
     ap.add_argument("--pin-schedule", default="label", help="--profile-run: the row schedule to pin (label | degree | dealt-256 | structure)")
     ap.add_argument("--profile-run", action="store_true",
                     help="the run to put under rocprofv3 --kernel-trace --stats: one stream (no validation lane), the aggregation's row schedule "
                          "pinned (HIPGCN_SCHEDULE, no tuning launches), no extras / cli / CPU baseline, so that the summary's average per kernel "
                          "is the average of the timed launches")
-    ap.add_argument("--sustain", type=int, default=1500, help="epochs of the long back-to-back region of the extras (0: skip)")
-    ap.add_argument("--hbm-scale", type=int, default=21, help="R-MAT scale of the HBM-regime leg (21: 1 GiB table at d=128)")
+    ap.add_argument("--sustain", type=int, default=1500, help="--full: epochs of the long back-to-back region of the extras (0: skip)")
+    ap.add_argument("--hbm-scale", type=int, default=21, help="--full: R-MAT scale of the HBM-regime leg (21: 1 GiB table at d=128)")
     ap.add_argument("--no-row-groups", action="store_true", help="plain descending-degree aggregation schedule (no label hint)")
     ap.add_argument("--bf16-tables", action="store_true",
                     help="opt-in, NOT the headline: GraphSum gathers bfloat16 copies of its inputs (f32 sums); reported as dtype f32+bf16-tables")
@@ -728,6 +740,49 @@ def main():
     dt, trace = timed_region(model, args.steps)      # <- the headline: default product path, per-op timers off
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, model, ds, trace)
+    schedule = model.schedule()
+    slice_floats = model.slice_floats()
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "epochs_per_sec", "value": args.steps / dt, "unit": "epochs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32+bf16-tables" if args.bf16_tables else "f32", "data": "synthetic",
+            "config": {"workload": f"{args.dataset} full-batch 2-layer GCN, N={ds['num_nodes']}, "
+                                   f"{(ds['g_indices'].size - ds['num_nodes']) // 2} undirected edges, "
+                                   f"{ds['input_dim']}->{args.hidden}->{ds['output_dim']}, dropout 0.5, Adam; "
+                                   "step = train_epoch + eval(val)" + structure_note(ds),
+                       "graph_structure": graph_structure(ds),
+                       "parallelism": f"row-partition x{world}" if world > 1 else "single GPU",
+                       "train_nodes": int((ds["split"] == 1).sum()), "aggregation_schedule": schedule, "aggregation_slice_floats": slice_floats,
+                       "first_layer_products": first_layer_method(ds, args.hidden),
+                       "class_layer_products": class_layer_method(ds, args.hidden),
+                       "eval_lane": "on" if lane_on else "off",
+                       "overlap_exchange": "on" if overlap_on else "off",
+                       "schedule": ("plain one-stream" if not (lane_on or overlap_on) else
+                                    " + ".join(x for x in ["exchange overlap" if overlap_on else "", "validation lane" if lane_on else ""] if x)),
+                       "exchange": exchange,       # rank 0's view: all-gather of row blocks or halo lists, rows moved per exchange
+                       "transport": transport[0] if transport else None,
+                       "rccl_ranks": transport[1] if (transport and transport[0] == "rccl") else None,     # ncclCommCount of the model's communicator
+                       "eval_forward": "reference order A^.(X.W1)" if os.environ.get("HIPGCN_NO_AGG_FIRST_EVAL") else
+                                       ("aggregate-first ReLU((A^.X).W1), A^.X built once at load (dense X)" +
+                                        ("" if os.environ.get("HIPGCN_NO_EVAL_FUSION") or args.hidden != 128 else "; .W2 in the same launch, H1 not stored")),
+                       "logit_rows": "all" if os.environ.get("HIPGCN_ALL_ROWS") else "rows of the scored split only"},
+            "final": {"train_loss": float(trace[-1, 0]), "train_acc": float(trace[-1, 1]),
+                      "val_loss": float(trace[-1, 2]), "val_acc": float(trace[-1, 3])},
+            "setup_s": {"dataset": round(t_data, 2), "model_build_incl_h2d": round(t_build, 2)},
+            "full": args.full,
+        }
+    if not args.full:
+        # a plain run ends here: the headline and nothing else (no repeats of the region, no timers pass, no other models, no CPU)
+        model.close()
+        if rank == 0:
+            out.update({"roofline": None, "cpu_baseline": None})
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     burst_eps = [args.steps / dt]
     for _ in range(args.bursts):
         d, _tr = timed_region(model, args.steps)
@@ -794,11 +849,8 @@ def main():
         model.train_epoch()
     torch.cuda.synchronize(); barrier()
     train_only_ms = 1e3 * (time.perf_counter() - t1) / n_tr
-    schedule = model.schedule()
-    slice_floats = model.slice_floats()
     model.close()
 
-    out = None
     if rank == 0:
         ib = 2 if args.bf16_tables else 4
         if args.hidden > 64:
@@ -898,41 +950,14 @@ def main():
                          "collectives_per_epoch": comm_calls / max(n_tm, 1),
                          "comm_us_per_collective": 1e3 * comm_ms / max(comm_calls / max(n_tm, 1), 1e-9),
                          "per_rank": "rank 0's launches on its row block"})
-        n_lab = int((ds["split"] == 1).sum())
-        out = {
-            "metric": "epochs_per_sec", "value": args.steps / dt, "unit": "epochs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32+bf16-tables" if args.bf16_tables else "f32", "data": "synthetic",
-            "config": {"workload": f"{args.dataset} full-batch 2-layer GCN, N={ds['num_nodes']}, "
-                                   f"{(ds['g_indices'].size - ds['num_nodes']) // 2} undirected edges, "
-                                   f"{ds['input_dim']}->{args.hidden}->{ds['output_dim']}, dropout 0.5, Adam; "
-                                   "step = train_epoch + eval(val)" + structure_note(ds),
-                       "graph_structure": graph_structure(ds),
-                       "parallelism": f"row-partition x{world}" if world > 1 else "single GPU",
-                       "train_nodes": n_lab, "aggregation_schedule": schedule, "aggregation_slice_floats": slice_floats,
-                       "first_layer_products": first_layer_method(ds, args.hidden),
-                       "class_layer_products": class_layer_method(ds, args.hidden),
-                       "eval_lane": "on" if lane_on else "off",
-                       "overlap_exchange": "on" if overlap_on else "off",
-                       "schedule": ("plain one-stream" if not (lane_on or overlap_on) else
-                                    " + ".join(x for x in ["exchange overlap" if overlap_on else "", "validation lane" if lane_on else ""] if x)),
-                       "exchange": exchange,       # rank 0's view: all-gather of row blocks or halo lists, rows moved per exchange
-                       "transport": transport[0] if transport else None,
-                       "rccl_ranks": transport[1] if (transport and transport[0] == "rccl") else None,     # ncclCommCount of the model's communicator
-                       "eval_forward": "reference order A^.(X.W1)" if os.environ.get("HIPGCN_NO_AGG_FIRST_EVAL") else
-                                       ("aggregate-first ReLU((A^.X).W1), A^.X built once at load (dense X)" +
-                                        ("" if os.environ.get("HIPGCN_NO_EVAL_FUSION") or args.hidden != 128 else "; .W2 in the same launch, H1 not stored")),
-                       "logit_rows": "all" if os.environ.get("HIPGCN_ALL_ROWS") else "rows of the scored split only"},
+        out.update({
             "bursts": {"epochs_per_s": [round(b, 2) for b in burst_eps], "median": statistics.median(burst_eps), "min": min(burst_eps),
                        "max": max(burst_eps), "steps_each": args.steps},
             "sustained": sustained,
             "roofline": roof,
             "breakdown_ms_per_epoch": breakdown, "timers_pass_ms_per_epoch": round(1e3 * dt_tm / n_tm, 4),
             "train_only_ms_per_epoch": round(train_only_ms, 4),
-            "final": {"train_loss": float(trace[-1, 0]), "train_acc": float(trace[-1, 1]),
-                      "val_loss": float(trace[-1, 2]), "val_acc": float(trace[-1, 3])},
-            "setup_s": {"dataset": round(t_data, 2), "model_build_incl_h2d": round(t_build, 2)},
-        }
+        })
 
     extras = world == 1 and not args.no_extras
     if extras and not args.no_row_groups and schedule == "label-major":

@@ -3,9 +3,9 @@
 CPU: `python bench.py --gpus 2` with no WORLD_SIZE must start its own ranks as child processes (never exec
 from a process that touched the GPU) and hand back their failure as a non-zero exit — here the children stop at
 "no GPU visible".
-GPU (-m gpu): the 1-GPU line carries the contract fields with a roofline fraction <= 1 against the bound that
-binds; `--gpus 2` self-launches two ranks (both on GPU 0, host-staged transport: the one-GPU box has no second
-device for RCCL) and prints ONE JSON line with n_gpus = 2.
+GPU (-m gpu): a plain 1-GPU line carries the contract fields and nothing measured after the headline; with `--full`
+it carries a roofline fraction <= 1 against the bound that binds; `--gpus 2 --full` self-launches two ranks (both on
+GPU 0, host-staged transport: the one-GPU box has no second device for RCCL) and prints ONE JSON line with n_gpus = 2.
 """
 import json
 import os
@@ -196,9 +196,31 @@ CONTRACT = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"]
 
 
+def test_full_is_off_by_default_and_reaches_every_rank(monkeypatch, capsys):
+    """a plain run measures the headline alone; --full (what used to run by default) is passed on to the ranks of every
+    schedule the N > 1 launcher starts, the self-test excepted"""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    calls = []
+
+    def fake(n_gpus, extra, timeout, env=None):
+        calls.append(list(extra))
+        return (0, json.dumps({"selftest": "ok"})) if "--selftest" in extra else (0, _fake_line(100.0, "plain one-stream"))
+    monkeypatch.setattr(bench, "_run_ranks", fake)
+    monkeypatch.setenv("GCN_BENCH_DEADLINE", "420")
+    for argv, full in ((["--gpus", "8", "--steps", "3"], False), (["--gpus", "8", "--steps", "3", "--full"], True)):
+        calls.clear()
+        assert bench.launch_ranks(8, argv) == 0
+        assert [_kind(c) for c in calls] == ["selftest", "plain", "overlap", "lane"]
+        assert all(("--full" in c) == (full and _kind(c) != "selftest") for c in calls), calls
+    capsys.readouterr()
+
+
 @pytest.mark.gpu
 def test_bench_one_gpu_line():
-    p = run_bench(["--dataset", "reddit-mini", "--steps", 4, "--warmup", 1, "--bursts", 1, "--no-cpu-baseline", "--no-extras"])
+    p = run_bench(["--dataset", "reddit-mini", "--steps", 4, "--warmup", 1, "--full", "--bursts", 1, "--no-cpu-baseline", "--no-extras"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = json_lines(p.stdout)
     assert len(lines) == 1
@@ -207,11 +229,31 @@ def test_bench_one_gpu_line():
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 4 and out["value"] > 0
     assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-6 * 1e3
-    assert len(out["bursts"]["epochs_per_s"]) == 2
+    assert out["full"] is True and len(out["bursts"]["epochs_per_s"]) == 2
     r = out["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
     assert r["launches"] > 0 and r["avg_launch_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line():
+    """no --full: the headline line with its contract fields, and nothing that takes a run of its own after the timed steps"""
+    p = run_bench(["--dataset", "reddit-mini", "--steps", 4, "--warmup", 1])
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = json_lines(p.stdout)
+    assert len(lines) == 1
+    out = lines[0]
+    for k in CONTRACT:
+        assert k in out, k
+    assert out["metric"] == "epochs_per_sec" and out["unit"] == "epochs/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 1 and out["value"] > 0
+    assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-6 * 1e3
+    assert out["full"] is False and out["roofline"] is None and out["cpu_baseline"] is None
+    assert out["config"]["eval_lane"] == "on" and 0 < out["final"]["train_loss"] < 10
+    for k in ("bursts", "sustained", "breakdown_ms_per_epoch", "train_only_ms_per_epoch", "value_reference_op_order_all_rows",
+              "value_no_row_groups", "value_no_label_hint", "value_f32_products", "structure_legs", "roofline_dense", "cli"):
+        assert k not in out, k
 
 
 @pytest.mark.gpu
@@ -245,7 +287,7 @@ def test_bench_dumps_the_last_step_outputs(tmp_path):
 def test_bench_extras_on_a_small_graph():
     """the extra legs of the one-GPU line (label hint withheld, no row groups, reference operation order, the R-MAT leg of
     the roofline — here at a small scale, so the code path and not the HBM regime is what is exercised)"""
-    p = run_bench(["--dataset", "reddit-mini", "--steps", 4, "--warmup", 1, "--bursts", 0, "--no-cpu-baseline", "--hbm-scale", 15])
+    p = run_bench(["--dataset", "reddit-mini", "--steps", 4, "--warmup", 1, "--full", "--bursts", 0, "--no-cpu-baseline", "--hbm-scale", 15])
     assert p.returncode == 0, p.stderr[-3000:]
     out = json_lines(p.stdout)[0]
     assert out["config"]["eval_lane"] == "on"                  # one GPU: validation forward on the second stream
@@ -261,7 +303,7 @@ def test_bench_extras_on_a_small_graph():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_self_launched():
-    p = run_bench(["--gpus", 2, "--dataset", "reddit-mini", "--steps", 3, "--warmup", 1, "--bursts", 0, "--no-cpu-baseline"],
+    p = run_bench(["--gpus", 2, "--dataset", "reddit-mini", "--steps", 3, "--warmup", 1, "--full", "--bursts", 0, "--no-cpu-baseline"],
                   env={"GCN_BENCH_TRANSPORT": "host", "GCN_BENCH_DEVICE": "0", "GCN_BENCH_TIMEOUT": "600", "GCN_BENCH_DEADLINE": "600"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = json_lines(p.stdout)
@@ -285,7 +327,7 @@ def test_bench_safe_line_survives_a_hung_optional_schedule():
     deadline = 200
     t0 = time.monotonic()
     # (the hung schedule's own limit, 45 s, ends it long before the deadline would: the suite need not wait for that)
-    p = run_bench(["--gpus", 4, "--dataset", "reddit-mini", "--steps", 3, "--warmup", 1, "--bursts", 0],
+    p = run_bench(["--gpus", 4, "--dataset", "reddit-mini", "--steps", 3, "--warmup", 1, "--full", "--bursts", 0],
                   env={"GCN_BENCH_TRANSPORT": "host", "GCN_BENCH_DEVICE": "0", "GCN_BENCH_DEADLINE": str(deadline), "GCN_BENCH_LANE_TIMEOUT": "45",
                        "GCN_BENCH_TEST_HANG": "overlap"},
                   timeout=deadline + 60)

@@ -19,5 +19,5 @@ timeout -k 10 200 python tools/bench_class.py > $O/class_layer_bench.log 2>&1 ||
 step "the command line on reddit-syn"
 timeout -k 10 400 python tools/run_cli_reddit.py --out $O/cli_reddit.json > $O/cli_reddit.log 2>&1 || echo "FAILED cli"
 step "rmat-22 as a whole model"
-timeout -k 10 500 python bench.py --dataset rmat-22 --steps 10 --warmup 2 --bursts 1 --no-cpu-baseline --no-extras > $O/bench_rmat22.json 2> $O/bench_rmat22.err || echo "FAILED rmat22"
+timeout -k 10 500 python bench.py --full --dataset rmat-22 --steps 10 --warmup 2 --bursts 1 --no-cpu-baseline --no-extras > $O/bench_rmat22.json 2> $O/bench_rmat22.err || echo "FAILED rmat22"
 step "done"

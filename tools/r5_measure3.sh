@@ -8,7 +8,7 @@ export GCN_COMMIT=$(cat $R/.commit_for_profiles 2>/dev/null || echo unknown)
 cd $R
 step() { echo "== $1 ($(date +%T))"; }
 step "bench.py as the driver runs it"
-timeout -k 10 500 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || echo "FAILED bench"
+timeout -k 10 500 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || echo "FAILED bench"
 step "kernel-trace stats of the timed region (bench.py --profile-run)"
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_run -- python3 $R/bench.py --profile-run --steps 50 --warmup 5 > $O/profile_run.json 2> $O/profile_run.err) || echo "FAILED profile run"
 python tools/kernel_stats.py $O/prof_run > $O/bench_n1_kernels.txt 2>&1 || echo "FAILED kernel_stats"

@@ -26,5 +26,5 @@ python3 tools/epoch_timeline.py $(find $O/timeline -name "ks_kernel_trace.csv" |
 step "the command line on reddit-syn"
 timeout -k 10 400 python3 tools/run_cli_reddit.py --out $O/cli_reddit.json > $O/cli_reddit.log 2>&1 || echo "FAILED cli"
 step "rmat-22 as a whole model"
-timeout -k 10 500 python3 bench.py --dataset rmat-22 --steps 10 --warmup 2 --bursts 1 --no-cpu-baseline --no-extras > $O/bench_rmat22.json 2> $O/bench_rmat22.err || echo "FAILED rmat22"
+timeout -k 10 500 python3 bench.py --full --dataset rmat-22 --steps 10 --warmup 2 --bursts 1 --no-cpu-baseline --no-extras > $O/bench_rmat22.json 2> $O/bench_rmat22.err || echo "FAILED rmat22"
 step "done"
