@@ -82,7 +82,6 @@ __device__ __forceinline__ void cls_fwd_issue(f32x4 (&R)[16], uint32_t vo, u32x4
 // (A version with two whole register sets and no load in flight at the back edge is immune by construction and was measured:
 // 158 registers, two waves per SIMD, 48.5 us against 36.7.  As plain C++ loads, before all that, hipcc issued each k-step's pair
 // right before its use and waited: eight dependent round trips per block, 49 us.)
-template <int ABL>
 __global__ __launch_bounds__(256) void class_fwd_bf16x3_kernel(ClsFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 cls_img[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, hh = lane >> 5;
@@ -121,31 +120,22 @@ __global__ __launch_bounds__(256) void class_fwd_bf16x3_kernel(ClsFwdArgs a) {
         {                                                                                                                    \
             CLS_WAIT2(14, R[2 * S], R[2 * S + 1]);                                                                           \
             const float v[8] = {R[2 * S][0], R[2 * S][1], R[2 * S][2], R[2 * S][3], R[2 * S + 1][0], R[2 * S + 1][1], R[2 * S + 1][2], R[2 * S + 1][3]}; \
-            if constexpr (ABL & 1) {                                                                                         \
-                float sum = v[0] + v[1] + v[2] + v[3] + v[4] + v[5] + v[6] + v[7];                                             \
-                asm volatile("" : "+v"(sum));                                                                                \
-                acc[0][S] += sum;                                                                                            \
-                cls_fwd_issue<S>(R, vn, rs_h);                                                                               \
-            } else {                                                                                                         \
-                ClsB3 A = cls_planes(v);                                                                                     \
-                asm volatile("" : "+v"(A.h), "+v"(A.m), "+v"(A.l));        /* the k-step's floats are dead from here on */    \
-                cls_fwd_issue<S>(R, vn, rs_h);                                                                               \
-                cls_mac(acc[0], A, cls_lds(cls_img, S * 2, lane));                                                           \
-                if (a.p > 32) cls_mac(acc[1], A, cls_lds(cls_img, S * 2 + 1, lane));                                         \
-            }                                                                                                                \
+            ClsB3 A = cls_planes(v);                                                                                         \
+            asm volatile("" : "+v"(A.h), "+v"(A.m), "+v"(A.l));            /* the k-step's floats are dead from here on */    \
+            cls_fwd_issue<S>(R, vn, rs_h);                                                                                   \
+            cls_mac(acc[0], A, cls_lds(cls_img, S * 2, lane));                                                               \
+            if (a.p > 32) cls_mac(acc[1], A, cls_lds(cls_img, S * 2 + 1, lane));                                             \
         }
         CLS_FWD_STEP(0) CLS_FWD_STEP(1) CLS_FWD_STEP(2) CLS_FWD_STEP(3) CLS_FWD_STEP(4) CLS_FWD_STEP(5) CLS_FWD_STEP(6) CLS_FWD_STEP(7)
 #undef CLS_FWD_STEP
         // D[row = (r & 3) + 8 (r >> 2) + 4 hh][class = 32 cb + li]: a store instruction writes 32 consecutive classes of two rows
-        if (!(ABL & 2) || acc[0][0] == 123.456f) {
 #pragma unroll
-            for (int cb = 0; cb < 2; cb++)
+        for (int cb = 0; cb < 2; cb++)
 #pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int orow = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, c = 32 * cb + li;
-                    if (orow < a.m && c < a.p) a.z0[(size_t)orow * a.ldz + c] = acc[cb][r];
-                }
-        }
+            for (int r = 0; r < 16; r++) {
+                const int orow = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, c = 32 * cb + li;
+                if (orow < a.m && c < a.p) a.z0[(size_t)orow * a.ldz + c] = acc[cb][r];
+            }
     }
     // the loads issued for the block after the last: their registers stay allocated until they have landed
     CLS_WAIT_ALL16(R);
@@ -175,7 +165,7 @@ struct ClsCol { float z[2][8], h[2][8]; };                  // one k-step of 16 
 //   L1(b): 2 NKS row pieces of dZ0, the row's 4 mask words, its factor   (2 NKS + 2 loads)   — issued during block b-1, landed by its end
 //   C0(b): k-step 0 column-wise: 16 + 16 dwords                          (32)                — issued at the top of block b
 //   C1(b): k-step 1, into C0's registers once those are planes            (32)
-template <int NKS, int ABL = 0>
+template <int NKS>
 __global__ __launch_bounds__(512) void class_bwd_bf16x3_kernel(ClsBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 cls_img[];
     float *red = reinterpret_cast<float *>(cls_img) + CLS_BWD_IMG / 4;
@@ -209,12 +199,11 @@ __global__ __launch_bounds__(512) void class_bwd_bf16x3_kernel(ClsBwdArgs a) {
     auto issue_l1 = [&](int b) __attribute__((always_inline)) {
         const uint32_t row = (uint32_t)(b * 32 + li);
         const uint32_t vz = (row * (uint32_t)a.lddz + 8u * hh) * 4u;
-        if constexpr (ABL & 4) { bx_bload16<0>(KB, row * 16u, rs_b); bx_bload4(RSC, row * 4u, rs_s, 0u); }      // (experiment: the small loads first)
         bx_bload16<0>(Z[0], vz, rs_z); bx_bload16<16>(Z[1], vz, rs_z);
         if constexpr (NKS > 1) { bx_bload16<64>(Z[2], vz, rs_z); bx_bload16<80>(Z[3], vz, rs_z); }
         if constexpr (NKS > 2) { bx_bload16<128>(Z[4], vz, rs_z); bx_bload16<144>(Z[5], vz, rs_z); }
         if constexpr (NKS > 3) { bx_bload16<192>(Z[6], vz, rs_z); bx_bload16<208>(Z[7], vz, rs_z); }
-        if constexpr (!(ABL & 4)) { bx_bload16<0>(KB, row * 16u, rs_b); bx_bload4(RSC, row * 4u, rs_s, 0u); }
+        bx_bload16<0>(KB, row * 16u, rs_b); bx_bload4(RSC, row * 4u, rs_s, 0u);
     };
     constexpr int NL1 = 2 * NKS + 2;
     ClsCol Cc;
@@ -266,25 +255,22 @@ __global__ __launch_bounds__(512) void class_bwd_bf16x3_kernel(ClsBwdArgs a) {
             const int c0 = 16 * s + 8 * hh;
 #pragma unroll
             for (int j = 0; j < 8; j++) v[j] = c0 + j < a.p ? v[j] : 0.f;              // padding columns may hold anything
-            if constexpr (ABL & 1) { acc[0][s] += v[0] + v[1] + v[2] + v[3] + v[4] + v[5] + v[6] + v[7]; continue; }
             const ClsB3 B = cls_planes(v);
 #pragma unroll
             for (int f2 = 0; f2 < 2; f2++) cls_mac(acc[f2], B, cls_lds(cls_img, s * 4 + 2 * half + f2, lane));
         }
-        if ((ABL & 2) ? (acc[0][0] == 123.456f) : true) {
-            // D[row = (r & 3) + 8 (r >> 2) + 4 hh][feature = 32 fb + li]: lane li holds the mask words and the factor of row li
-            // (both halves of the wave); a store instruction writes 32 consecutive features — one full line — of two rows.
-            // (As 16-byte lane stores of a transposed tile the 119 MB of dH1 left in 7.4 M separate requests: 40 us of a 95 us launch.)
+        // D[row = (r & 3) + 8 (r >> 2) + 4 hh][feature = 32 fb + li]: lane li holds the mask words and the factor of row li
+        // (both halves of the wave); a store instruction writes 32 consecutive features — one full line — of two rows.
+        // (As 16-byte lane stores of a transposed tile the 119 MB of dH1 left in 7.4 M separate requests: 40 us of a 95 us launch.)
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, orow = rb * 32 + rl;
-                const float scr = __shfl(sc, rl, WAVE);
-                const uint32_t w0 = __shfl(kw[0], rl, WAVE), w1 = __shfl(kw[1], rl, WAVE);
-                if (orow < a.m) {
-                    float *dp = a.da + (size_t)orow * a.ldda + 64 * half + li;
-                    dp[0] = ((w0 >> li) & 1u) ? acc[0][r] * scr : 0.f;
-                    dp[32] = ((w1 >> li) & 1u) ? acc[1][r] * scr : 0.f;
-                }
+        for (int r = 0; r < 16; r++) {
+            const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, orow = rb * 32 + rl;
+            const float scr = __shfl(sc, rl, WAVE);
+            const uint32_t w0 = __shfl(kw[0], rl, WAVE), w1 = __shfl(kw[1], rl, WAVE);
+            if (orow < a.m) {
+                float *dp = a.da + (size_t)orow * a.ldda + 64 * half + li;
+                dp[0] = ((w0 >> li) & 1u) ? acc[0][r] * scr : 0.f;
+                dp[32] = ((w1 >> li) & 1u) ? acc[1][r] * scr : 0.f;
             }
         }
         issue_l1(rb + stride);                               // the next block's row pieces travel under the second phase
@@ -293,12 +279,6 @@ __global__ __launch_bounds__(512) void class_bwd_bf16x3_kernel(ClsBwdArgs a) {
         for (int s2 = 0; s2 < 2; s2++) {
             if (s2 == 0) CLS_WAIT_COL(NL1, Cc);              // younger than C0: the next block's L1
             else CLS_WAIT_COL(0, Cc);
-            if constexpr (ABL & 1) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) dw[0][0][j] += Cc.z[0][j] + Cc.z[1][j] + Cc.h[0][j] + Cc.h[1][j];
-                if (s2 == 0) issue_col(rb, 1);
-                continue;
-            }
             ClsB3 Bz[2], Ah[2];
 #pragma unroll
             for (int cb = 0; cb < 2; cb++) {
@@ -364,14 +344,8 @@ static int launch_class_fwd(gcnhip_ctx *c, const float *a, int lda, const float 
     ClsFwdArgs k;
     k.h1 = a; k.ldh = lda; k.w2 = b; k.ldw = ldb; k.z0 = z; k.ldz = ldz; k.m = m; k.p = p; k.n_rb = ceil_div(m, 32);
     int grid = ceil_div(k.n_rb, 4);
-    const int per_cu = c->opt.cls_wgs > 0 ? c->opt.cls_wgs : 3;     // 48 KB of LDS per workgroup: three per CU
-    if (grid > c->n_cu * per_cu) grid = c->n_cu * per_cu;
-    switch (c->opt.cls_abl & 3) {
-        case 1: class_fwd_bf16x3_kernel<1><<<grid, 256, CLS_FWD_LDS, c->stream>>>(k); break;
-        case 2: class_fwd_bf16x3_kernel<2><<<grid, 256, CLS_FWD_LDS, c->stream>>>(k); break;
-        case 3: class_fwd_bf16x3_kernel<3><<<grid, 256, CLS_FWD_LDS, c->stream>>>(k); break;
-        default: class_fwd_bf16x3_kernel<0><<<grid, 256, CLS_FWD_LDS, c->stream>>>(k); break;
-    }
+    if (grid > c->n_cu * 3) grid = c->n_cu * 3;              // 48 KB of LDS per workgroup: three per CU
+    class_fwd_bf16x3_kernel<<<grid, 256, CLS_FWD_LDS, c->stream>>>(k);
     GCNHIP_LAUNCH_CHECK();
     return 0;
 }

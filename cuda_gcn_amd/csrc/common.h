@@ -22,25 +22,17 @@ int gcnhip_fail(const char *detail);
 
 // Options of a context (gcnhip_ctx_set_option / _get_option).  Each starts from the environment variable
 // GCNHIP_<NAME IN CAPITALS>, read ONCE when the context is created — never at launch time — so a call's behaviour does not
-// depend on what the process environment holds at that moment.  Most are A/B aids for measurements DESIGN.md records.
+// depend on what the process environment holds at that moment.  gemm_bf16x3 and gs_l are the host driver's; spmm_slices,
+// spmm_general, spmm_nw, xent_finalize and adam_sum_launch let tests reach or compare paths; the rest are shape parameters of a
+// graph or a launch that tools sweep.
 struct GcnOptions {
     int gs_u;               // > 0: row loads in flight per lane group of the aggregation (0: by table size)
     int gs_l;               // 8 / 4: column slices of 32 / 16 floats in the XCD-sliced aggregation (default 0: 64 floats)
-    int gemm_tiles;         // 1: first-layer forward by the tile kernels instead of the persistent form
     int gemm_bf16x3;        // dense first-layer products (p = 128) from three bf16 planes on the bf16 MFMA pipe: 2 (default) on, also on a
                             // co-running stream; 1 on, the co-running stream keeps the f32 tiles; 0 off: the exact-f32 MFMA kernels
-    int gemm_w4;            // 1: four-wave forward tiles
-    int cls_abl;            // measurement aid (tools/bench_class.py): class_bf16x3.h kernels without 1: matrix work, 2: stores, 4: the column-wise operand loads
-    int cls_wgs;            // measurement aid: workgroups per CU of the class-layer forward (0: default)
-    int gemm_lane_waves;    // waves per workgroup of the bf16x3 first-layer forward on a co-running context: 8 (default) or 4 (measured: no gain)
-    int gemm_lane_wgs;      // workgroups (= CUs) of that launch; 0: one per CU
     int spmm_slices;        // 1 (default): sparse X, W past an XCD's L2, h % 32 == 0: XCD-bound 32-float column slices of W; 0: the unsliced row kernel
-    int cls_fwd;            // 1 (default): H1.W2 through class_bf16x3.h when gemm_bf16x3 >= 1; 0: through the f32-MFMA row stream
     int xent_finalize;      // 1: the loss's final reduction as its own launch
-    int xent_wave;          // 1: wave-per-row loss kernel for any width
     int adam_sum_launch;    // 1: Adam's sum of squares by a second launch
-    int atb_cap_mb;         // split-K slab budget of A^T.B in MiB
-    int rs_wgs;             // > 0: workgroups per CU of the row-streaming GEMM
     int spmm_general;       // 1: narrow rows also take the general (shuffle-based) sparse kernels; -1: narrow kernels at any size (A/B, tests)
     int spmm_rows;          // > 0: rows per wave of the sparse forward (default: by row count, 1 .. 8)
     int spmm_nw;            // > 0: waves per column task of the sparse weight gradient (1, 4, 16), read by gcnhip_feat_create

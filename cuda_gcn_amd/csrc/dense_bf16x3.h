@@ -211,17 +211,9 @@ __device__ __forceinline__ void bx_ldsread16(bf16x8 &dst, uint32_t addr) {
 //    group are read while this group's MFMAs run, the barrier (W k-step h+1 landed, ring slot free) sits between G1 and G2.
 // The last round of a workgroup may have fewer than 8 row blocks: waves without one run the same instruction stream on the
 // share's last row and store nothing (the counted waits need every wave to issue the same operations).
-// ABL (timing experiments of tools/gemm_bf16x3.hip only; 1-8, 32 and 64 give wrong results): 1 no X loads, 2 no W DMA, 4 no split,
-// 8 no W LDS reads, 16 every wait vmcnt(0), 32 keep words loaded but not applied, 64 applied but not loaded, 128 keep word after the
-// X loads (+9 us), 256 X loads ahead of the chunk's W pieces (+40 us), 512 X loads at the top of the chunk (+9..14 us),
-// 1024 no workgroup barrier (round 6: what the per-half-item barrier costs the MFMA skeleton).
-// PD_: W k-steps in flight (6..9 measure the same).
-// NW = waves per workgroup.  8: the whole-chip form (two waves per SIMD fill the CU's register file).  4 (round 5, for a context
-// that runs BESIDE another stream's kernels — the validation lane): one wave per SIMD and half the register file, so that a
-// gather-bound kernel's waves can be resident on the same CU at the same time.  The eight-wave workgroup needs an EMPTY CU to
-// start: beside the training pass's hidden-width aggregation it is handed CUs only as they drain and runs 895 us instead of
-// 198 (kernel timeline, docs/NOTEBOOK_r5.md §7).  Measured: co-residency costs the aggregation half its waves on those CUs and
-// the epoch gains nothing (option gemm_lane_waves, default 8).
+// Eight waves: two per SIMD fill the CU's register file, so the workgroup needs an EMPTY CU to start — beside another stream's
+// kernels it is handed CUs only as they drain (895 us instead of 198 beside the hidden-width aggregation; a four-wave form that
+// could share a CU gained the epoch nothing: docs/NOTEBOOK_r5.md §7).
 // ZOUT (round 5, evaluation forwards; verdict r04 item 4c): the product is computed TRANSPOSED (W planes as the A operand, the X
 // planes as B: the same plane products in the same order), so that a lane ends up with ONE ROW and, in its accumulator
 // registers, that row's features — which is the layout the B operand of a second product Z0^T = W2^T . relu(H)^T wants: register
@@ -229,14 +221,12 @@ __device__ __forceinline__ void bx_ldsread16(bf16x8 &dst, uint32_t addr) {
 // 4 h of the 16) exactly as bx_pack_w2_body lays W2 out.  At the end of a round the 32 x 128 tile of H is clamped at zero, split
 // into planes in registers and multiplied by the W2 image (48 KB of LDS beside a ring of 8 instead of 10 W k-steps); Z0's 32 x p2
 // tile is stored, H is not: 119 MB less written, 119 MB less read, one launch less per evaluation forward.
-template <bool DROP, int NP, int ABL = 0, int NW = 8, bool ZOUT = false, int PD_ = 0>
-__global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs a) {
-    constexpr int PD = PD_ ? PD_ : BX_PD;                        // W k-steps in flight ahead of their use
-    static_assert(NW == 8 || NW == 4, "12 W pieces per k-step: two per wave of eight (four of them duplicates) or three per wave of four");
+template <bool DROP, int NP, bool ZOUT = false>
+__global__ __launch_bounds__(512, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs a) {
     // ring slots: k-step h + BX_PD is written (after the barrier of half-item h) into the slot of k-step h + BX_PD - NBV, which
     // every wave has finished reading once it is past half-item h - 1: NBV >= BX_PD + 1
     constexpr int NBV = ZOUT ? 8 : BX_NB;
-    static_assert(NBV >= PD + 1, "ring too short for the prefetch distance");
+    static_assert(NBV >= BX_PD + 1, "ring too short for the prefetch distance");
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NBV * BX_BH_BYTES + (ZOUT ? BX_W2_BYTES : 0)];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,44 +238,32 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
     const int nb = (int)((int64_t)(blockIdx.x + 1) * a.n_rb / gridDim.x) - rb_lo;
     if (nb <= 0) return;
     const int row_last = min(a.m, (rb_lo + nb) * 32) - 1;       // rows past this workgroup's share are read as its last row (cache hits, no HBM traffic)
-    const int n_rounds = (nb + NW - 1) / NW;
+    const int n_rounds = (nb + 7) / 8;
     const int n_items = n_rounds * a.n_chunks;                   // chunks of this wave, all rounds
     const int n_hs = 2 * a.n_chunks;
-    const int piece2 = NW == 4 ? wave + 4 : (wave < 4 ? wave + 8 : wave - 4);   // second DMA piece of this wave (eight waves: waves 4-7 repeat one of pieces 0-3)
+    const int piece2 = wave < 4 ? wave + 8 : wave - 4;           // second DMA piece of this wave (waves 4-7 repeat one of pieces 0-3)
 
     // the X values (and keep words) of chunk (round t, chunk c) of this lane's row
     auto load_raw = [&](BxRaw &r, int t, int c) __attribute__((always_inline)) {
-        const int row = min((rb_lo + NW * t + wave) * 32 + li, row_last);
+        const int row = min((rb_lo + 8 * t + wave) * 32 + li, row_last);
         const float *p = a.x + (size_t)row * a.ldx + c * BX_BK + 16 * hh;
-        if (ABL & 1) p = a.x + lane * 16;
         // the keep word FIRST: 32 consecutive rows = one line (both lane halves read the same words).  Issued after the four
-        // X loads the same load cost 9 us more per launch (tools/gemm_bf16x3.hip, ablation 128)
-        if (DROP && !(ABL & 64) && !(ABL & 128)) bx_gload4(r.kw, a.bits + (size_t)c * a.m + row);
+        // X loads the same load cost 9 us more per launch (docs/NOTEBOOK_r5.md §2)
+        if (DROP) bx_gload4(r.kw, a.bits + (size_t)c * a.m + row);
         bx_gload16<0>(r.v[0], p); bx_gload16<16>(r.v[1], p); bx_gload16<32>(r.v[2], p); bx_gload16<48>(r.v[3], p);
-        if (DROP && !(ABL & 64)) {
-            if (ABL & 128) bx_gload4(r.kw, a.bits + (size_t)c * a.m + row);
-        } else {
-            r.kw = 0u;
-        }
+        if (!DROP) r.kw = 0u;
     };
-    constexpr int LA = (DROP && !(ABL & 64)) ? 5 : 4;                             // vector-memory operations of one load_raw
     // the W k-step of half-item hq (its index inside the round repeats with every round) into ring slot hq % BX_NB
     auto issue_b = [&](int hq) __attribute__((always_inline)) {
-        if (ABL & 2) return;
         int hs = hq % n_hs;
         const uint32_t dst = lds0 + (hq % NBV) * BX_BH_BYTES;
         const uint4 *src = a.wp + (size_t)hs * (BX_BH_BYTES / 16);
         pg_glds16(src + wave * 64 + lane, dst + wave * 1024);
         pg_glds16(src + piece2 * 64 + lane, dst + piece2 * 1024);
-        if (NW == 4) pg_glds16(src + (wave + 8) * 64 + lane, dst + (wave + 8) * 1024);
     };
-    // what the W wait allows: the younger W pieces of this wave, BX_PD - 2 k-steps of 2 (eight waves) or 3 (four waves) pieces
-    static_assert(PD >= 5 && PD <= 9, "BX_WAIT_W spells the counts out");
-#define BX_WAIT_W() do { constexpr int n_ = (NW == 4 ? 3 : 2) * (PD - 2); \
-        if (ABL & 1024) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); else \
-        if (ABL & 16) PG_WAIT_BARRIER(0); else if (n_ == 6) PG_WAIT_BARRIER(6); else if (n_ == 8) PG_WAIT_BARRIER(8); else if (n_ == 9) PG_WAIT_BARRIER(9); \
-        else if (n_ == 10) PG_WAIT_BARRIER(10); else if (n_ == 12) PG_WAIT_BARRIER(12); else if (n_ == 14) PG_WAIT_BARRIER(14); \
-        else if (n_ == 15) PG_WAIT_BARRIER(15); else if (n_ == 18) PG_WAIT_BARRIER(18); else if (n_ == 21) PG_WAIT_BARRIER(21); else PG_WAIT_BARRIER(0); } while (0)
+    // what the W wait allows: the younger W pieces of this wave, BX_PD - 2 k-steps of 2 pieces
+    static_assert(2 * (BX_PD - 2) == 8, "BX_WAIT_W spells the count out");
+#define BX_WAIT_W() PG_WAIT_BARRIER(8)
 
     f32x16 acc[4];
 #pragma unroll
@@ -310,12 +288,11 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
     auto split_pair = [&](BxPlanes &P, const BxRaw &r, uint32_t win, int s, int i) __attribute__((always_inline)) {
         const f32x4 v = r.v[2 * s + (i >> 1)];
         float x0 = (i & 1) ? v[2] : v[0], x1 = (i & 1) ? v[3] : v[1];
-        if (DROP && !(ABL & 32)) {
+        if (DROP) {
             const int j = 8 * s + 2 * i;                         // bit j of the window <-> this lane's k value j of the chunk
             x0 = __uint_as_float(__float_as_uint(x0) & (uint32_t)(((int32_t)(win << (31 - j))) >> 31));
             x1 = __uint_as_float(__float_as_uint(x1) & (uint32_t)(((int32_t)(win << (30 - j))) >> 31));
         }
-        if (ABL & 4) { P.w[0][i] = __float_as_uint(x0); P.w[1][i] = __float_as_uint(x1); P.w[2][i] = P.w[0][i]; return; }
         bx_split2(x0, x1, P.w[0][i], P.w[1][i], P.w[2][i]);
     };
     auto window = [&](const BxRaw &r, int t, int c) __attribute__((always_inline)) -> uint32_t {
@@ -324,7 +301,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
     };
     // the three planes of column block N of the W k-step in ring slot hq % BX_NB: issued, not waited for
     auto read_b = [&](BxB3 &b, int hq, auto n_tag) __attribute__((always_inline)) {
-        constexpr int N = (ABL & 8) ? 0 : decltype(n_tag)::value;
+        constexpr int N = decltype(n_tag)::value;
         const uint32_t addr = lds0 + (hq % NBV) * BX_BH_BYTES + lane * 16;
         bx_ldsread16<(0 * 4 + N) * 1024>(b.h, addr);
         bx_ldsread16<(1 * 4 + N) * 1024>(b.m, addr);
@@ -416,13 +393,13 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
 
     if (ZOUT) {                                                  // the W2 image, before any hand-counted operation is issued
         uint4 *img = reinterpret_cast<uint4 *>(smem + NBV * BX_BH_BYTES);
-        for (int i = tid; i < BX_W2_BYTES / 16; i += 64 * NW) img[i] = a.w2p[i];
+        for (int i = tid; i < BX_W2_BYTES / 16; i += 512) img[i] = a.w2p[i];
         __syncthreads();
     }
     // ---- prologue: W k-steps 0 .. BX_PD-1, X chunks 0 and 1; everything landed
     BxRaw R0, R1, R2;
 #pragma unroll
-    for (int q = 0; q < PD; q++) issue_b(q);
+    for (int q = 0; q < BX_PD; q++) issue_b(q);
     load_raw(R0, 0, 0);
     {
         const int t1 = a.n_chunks > 1 ? 0 : 1, c1 = a.n_chunks > 1 ? 1 : 0;
@@ -452,7 +429,6 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
         const int h0 = 2 * g;
         const uint32_t wa = window(Ra, t, c);
         // ================= half-item (g, 0): MFMAs on P0; raw[g]'s second half -> P1; raw[g+2] issued
-        if (ABL & 512) load_raw(Rc, t2, c2);                     // (experiment: the X loads at the top of the chunk)
         read_b(Bn, h0, BxN<1>());
         __builtin_amdgcn_sched_barrier(0);
         split_pair(P1, Ra, wa, 1, 0);
@@ -472,9 +448,8 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
         // W k-step h0+1 has landed: issued BX_PD-1 half-items ago, BX_PD-2 younger k-steps of two pieces each.  Every wave is past
         // half-item h0-1: its ring slot takes k-step h0+BX_PD
         BX_WAIT_W();
-        if (ABL & 256) { load_raw(Rc, t2, c2); issue_b(h0 + PD); }      // (experiment: the X loads ahead of the W pieces)
-        else if (ABL & 512) issue_b(h0 + PD);
-        else { issue_b(h0 + PD); load_raw(Rc, t2, c2); }
+        issue_b(h0 + BX_PD);                                     // (the X loads ahead of the W pieces: +40 us; at the top of the chunk: +9..14 us)
+        load_raw(Rc, t2, c2);
         read_b(Bn, h0, BxN<3>());
         __builtin_amdgcn_sched_barrier(0);
         split_pair(P1, Ra, wa, 1, 2);
@@ -493,9 +468,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
         BX_WAIT_LDS(Bc);
         // ================= half-item (g, 1): MFMAs on P1; raw[g+1]'s first half -> P0
         // raw[g+1] has landed: issued three half-items ago; the younger loads of its kind are raw[g+2]'s
-        if (ABL & 16) BX_WAIT_RAW(0, Rb);
-        else if (DROP && !(ABL & 64)) BX_WAIT_RAW(5, Rb);
-        else BX_WAIT_RAW(4, Rb);
+        if (DROP) BX_WAIT_RAW(5, Rb); else BX_WAIT_RAW(4, Rb);
         const uint32_t wb = window(Rb, t1, c1);
         read_b(Bn, h0 + 1, BxN<1>());
         __builtin_amdgcn_sched_barrier(0);
@@ -514,7 +487,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
         __builtin_amdgcn_sched_barrier(0);
         BX_WAIT_LDS(Bc);
         BX_WAIT_W();
-        issue_b(h0 + 1 + PD);
+        issue_b(h0 + 1 + BX_PD);
         read_b(Bn, h0 + 1, BxN<3>());
         __builtin_amdgcn_sched_barrier(0);
         split_pair(P0, Rb, wb, 0, 2);
@@ -532,12 +505,12 @@ __global__ __launch_bounds__(64 * NW, 2) void dense_fwd_bf16x3_kernel(Bx3FwdArgs
         __builtin_amdgcn_sched_barrier(0);
         BX_WAIT_LDS(Bc);
         if (c == a.n_chunks - 1) {
-            const bool live = NW * t + wave < nb;
+            const bool live = 8 * t + wave < nb;
             if (ZOUT) {
-                second_product((rb_lo + NW * t + wave) * 32, live);
+                second_product((rb_lo + 8 * t + wave) * 32, live);
             } else {
 #pragma unroll
-                for (int n = 0; n < 4; n++) store_block(acc[n], (rb_lo + NW * t + wave) * 32, 32 * n + li, live);
+                for (int n = 0; n < 4; n++) store_block(acc[n], (rb_lo + 8 * t + wave) * 32, 32 * n + li, live);
             }
         }
     };
@@ -598,7 +571,7 @@ struct BxRaw8 { float a[8], b[8]; uint32_t k; };             // k: with dropout,
                                                                    "+v"((r).b[0]), "+v"((r).b[1]), "+v"((r).b[2]), "+v"((r).b[3]), "+v"((r).b[4]), "+v"((r).b[5]), "+v"((r).b[6]), "+v"((r).b[7]), \
                                                                    "+v"((r).k) :: "memory")
 
-template <bool DROP, int NP, int ORD = 0>      // ORD: load-order experiments of tools/gemm_bf16x3.hip (1: keep word first, 2: dH0 before X, 4: X and dH0 interleaved)
+template <bool DROP, int NP>
 __global__ __launch_bounds__(256, 2) void dense_bwd_bf16x3_kernel(Bx3BwdArgs a) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BX_BH_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -622,31 +595,20 @@ __global__ __launch_bounds__(256, 2) void dense_bwd_bf16x3_kernel(Bx3BwdArgs a) 
     // chunk-major keep words: this wave's 32 features are chunk F0 / 32 (a chunk past the matrix: out of the buffer's range, zeros)
     const u32x4 rs_k = bx_make_rsrc(a.bits, (uint32_t)((a.K + 31) / 32) * (uint32_t)a.m * 4u);
     const uint32_t vo_k0 = ((uint32_t)(F0 >> 5) * (uint32_t)a.m + (uint32_t)(r_lo + (lane & 15))) * 4u;   // (4 * chunks * m < 2^32: checked at the launch site)
-    constexpr int LR = DROP ? 17 : 16;                           // vector-memory operations of one load_raw
     auto load_raw = [&](BxRaw8 &r, int s) __attribute__((always_inline)) {
         const uint32_t vx = vo_x0 + (uint32_t)s * step_x, vd = vo_d0 + (uint32_t)s * step_d;
-        auto load_k = [&]() __attribute__((always_inline)) {
-            uint32_t w;
-            asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(w) : "v"(vo_k0 + (uint32_t)s * 64u), "s"(rs_k) : "memory");
-            r.k = w;
-        };
-        if (DROP && (ORD & 1)) load_k();
-        if (ORD & 4) {
+        // with dropout: the keep word first, X and dH0 loads interleaved (0.230 vs 0.236 ms for X, dH0, keep word); without: X, then dH0
+        if (DROP) {
+            asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(r.k) : "v"(vo_k0 + (uint32_t)s * 64u), "s"(rs_k) : "memory");
 #pragma unroll
             for (int j = 0; j < 8; j++) { bx_bload4(r.a[j], vx, rs_x, so_x[j]); bx_bload4(r.b[j], vd, rs_d, so_d[j]); }
-        } else if (ORD & 2) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) bx_bload4(r.b[j], vd, rs_d, so_d[j]);
-#pragma unroll
-            for (int j = 0; j < 8; j++) bx_bload4(r.a[j], vx, rs_x, so_x[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; j++) bx_bload4(r.a[j], vx, rs_x, so_x[j]);
 #pragma unroll
             for (int j = 0; j < 8; j++) bx_bload4(r.b[j], vd, rs_d, so_d[j]);
+            r.k = 0u;
         }
-        if (DROP && !(ORD & 1)) load_k();
-        if (!DROP) r.k = 0u;
     };
     // lane masks of step s: bit l of M[j] = value j of lane l counts (its row is inside the split; with dropout: and is kept)
     struct Masks { uint64_t m[8]; };

@@ -14,7 +14,7 @@ int gcnhip_matmul_fwd(gcnhip_ctx *c, const float *a, int lda, const float *b, in
     if (!c || !a || !b || !cc || m < 0 || n <= 0 || p <= 0 || lda < n || ldb < p || ldc < p) return -1;
     if (m == 0) return 0;
     // option gemm_bf16x3 (round 5): hidden width 128, at most 64 classes — the product from three bf16 planes per operand
-    if (c->opt.gemm_bf16x3 >= 1 && c->opt.cls_fwd && cls_fwd_fits(a, lda, cc, ldc, m, n, p)) return launch_class_fwd(c, a, lda, b, ldb, cc, ldc, m, p);
+    if (c->opt.gemm_bf16x3 >= 1 && cls_fwd_fits(a, lda, cc, ldc, m, n, p)) return launch_class_fwd(c, a, lda, b, ldb, cc, ldc, m, p);
     return launch_rowstream(c, a, lda, b, ldb, 0, cc, ldc, m, n, p, nullptr, 0, 1.f);
 }
 
@@ -32,21 +32,16 @@ static int launch_class_bwd(gcnhip_ctx *c, const float *a, int lda, const float 
     k.slab = c->slab;
     // (the attribute is set per launch, as the other kernels with more than 64 KB of LDS do: it belongs to the function on the
     //  CURRENT device, and a process may drive several — gcn-hip with GCN_GPUS=N runs one host thread per GPU)
-#define CLS_BWD(...)                                                                                                              \
+#define CLS_BWD(NKS)                                                                                                              \
     do {                                                                                                                          \
-        GCNHIP_TRY(hipFuncSetAttribute((const void *)class_bwd_bf16x3_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, CLS_BWD_LDS)); \
-        class_bwd_bf16x3_kernel<__VA_ARGS__><<<grid, 512, CLS_BWD_LDS, c->stream>>>(k);                                          \
+        GCNHIP_TRY(hipFuncSetAttribute((const void *)class_bwd_bf16x3_kernel<NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, CLS_BWD_LDS)); \
+        class_bwd_bf16x3_kernel<NKS><<<grid, 512, CLS_BWD_LDS, c->stream>>>(k);                                                  \
     } while (0)
-    const int abl = c->opt.cls_abl & 7;                       // measurement aid (tools/bench_class.py), p = 33..48 only
-    if (abl && nks == 3) {
-        if (abl == 1) CLS_BWD(3, 1); else if (abl == 2) CLS_BWD(3, 2); else if (abl == 3) CLS_BWD(3, 3); else CLS_BWD(3, 4);
-    } else {
-        switch (nks) {
-            case 1: CLS_BWD(1); break;
-            case 2: CLS_BWD(2); break;
-            case 3: CLS_BWD(3); break;
-            default: CLS_BWD(4); break;
-        }
+    switch (nks) {
+        case 1: CLS_BWD(1); break;
+        case 2: CLS_BWD(2); break;
+        case 3: CLS_BWD(3); break;
+        default: CLS_BWD(4); break;
     }
 #undef CLS_BWD
     GCNHIP_LAUNCH_CHECK();

@@ -16,6 +16,7 @@
 #include "dense_persist.h"
 #include "dense_bf16x3.h"
 #include "spmm_sparse.h"
+#include <limits.h>
 
 // ------------------------------------------------------------- dense forward
 // out[m x p] = X~[m x K] . W[K x p].  Workgroup tile 128 rows x (NT*16) cols,
@@ -211,6 +212,103 @@ extern "C" {
 // the second layer's product in the epilogue of the evaluation forward (dense_bf16x3.h, ZOUT): Z0 = relu(X.W) . W2
 struct Z0Fuse { const float *w2; int ld_w2, p2; float *z0; int ld_z0; };
 
+// ---- the dense first-layer product at p > 64 (128 x 128 MFMA tiles): three forms, below in the order they are tried.  Each
+// takes the prepared operands t (fast: 16-byte aligned rows of X whose stride covers round_up(K, 32) columns, ld_w % 4 == 0,
+// W aligned, full 128-column output tiles) and returns NOT_MINE, with nothing launched, when its predicate does not hold.
+constexpr int NOT_MINE = INT_MIN;
+
+// (1) option gemm_bf16x3 (1: wherever the persistent f32 form would run, 2: also on a co-running stream): the product on the
+// bf16 matrix pipe from three exact bf16 planes per f32 operand (dense_bf16x3.h) — f32 results inside the f32 summation bound,
+// 0.21 ms instead of 0.35 at Reddit scale.  0 keeps the exact-f32 MFMA kernels.
+static bool dense_fwd_bf16x3_fits(const gcnhip_ctx *c, const gcnhip_feat *f, const Tile128Args &t, const DropSpec &d, bool fast, bool fused) {
+    const int n_chunks = (t.K + PG_BK - 1) / PG_BK;
+    return fast && t.p == 128 && c->opt.gemm_bf16x3 && (!d.on || keep_bits_cm_fit(f)) &&
+           (fused || ((c->opt.gemm_bf16x3 >= 2 || !c->corun) && aligned16(t.out) && (uint64_t)(t.m + 256) * (uint64_t)t.ldo * 4u < (1ull << 32))) &&
+           aligned16(t.x) && (size_t)n_chunks * 2 * BX_BH_BYTES <= c->wpack_bytes;
+}
+// ... with the second layer's product in its epilogue
+static bool dense_fwd_bf16x3_z0_fits(const gcnhip_ctx *c, const Tile128Args &t, const DropSpec &d, bool fast, const Z0Fuse &zf) {
+    const int n_chunks = (t.K + PG_BK - 1) / PG_BK;
+    return fast && t.p == 128 && c->opt.gemm_bf16x3 && !d.on && aligned16(t.x) && zf.p2 >= 1 && zf.p2 <= 64 && zf.ld_z0 % 4 == 0 &&
+           zf.ld_z0 >= zf.p2 && zf.ld_w2 >= zf.p2 && aligned16(zf.z0) && (size_t)n_chunks * 2 * BX_BH_BYTES + BX_W2_BYTES <= c->wpack_bytes;
+}
+static int dense_fwd_bf16x3(gcnhip_ctx *c, const gcnhip_feat *f, const Tile128Args &t, const DropSpec &d, bool fast, const Z0Fuse *zf) {
+    if (zf && !dense_fwd_bf16x3_z0_fits(c, t, d, fast, *zf)) return GCNHIP_NOT_AVAILABLE;   // the caller runs the two products one after the other
+    if (!dense_fwd_bf16x3_fits(c, f, t, d, fast, zf != nullptr)) return NOT_MINE;
+    const int n_chunks = (t.K + PG_BK - 1) / PG_BK, n_hs = 2 * n_chunks;
+    uint4 *wp3 = reinterpret_cast<uint4 *>(c->wpack);
+    uint4 *w2img = wp3 + (size_t)n_hs * (BX_BH_BYTES / 16);
+    if (d.on) {                                  // keep words (chunk-major) and the packed planes of W from one launch
+        const BxBitsArgs kb = keep_bits_cm_args(f, d);
+        const int n_bits_wgs = ceil_div(kb.m, kb.R);
+        const_cast<gcnhip_feat *>(f)->keep_layout = 1;
+        dropbits_bx_pack_w_kernel<<<n_bits_wgs + n_hs, 256, 0, c->stream>>>(kb, n_bits_wgs, t.w, t.ldw, t.K, n_hs, wp3, t.scale);
+    } else {
+        if (zf) bx_pack_w_kernel<<<n_hs + 4, 256, 0, c->stream>>>(t.w, t.ldw, t.K, n_hs, wp3, 1.f, zf->w2, zf->ld_w2, zf->p2, w2img);
+        else bx_pack_w_kernel<<<n_hs, 256, 0, c->stream>>>(t.w, t.ldw, t.K, n_hs, wp3, t.bits ? t.scale : 1.f);
+    }
+    GCNHIP_LAUNCH_CHECK();
+    Bx3FwdArgs ba;
+    ba.x = t.x; ba.ldx = t.ldx; ba.wp = wp3; ba.out = t.out; ba.ldo = t.ldo;
+    ba.m = t.m; ba.K = t.K; ba.n_chunks = n_chunks; ba.n_rb = ceil_div(t.m, 32);
+    ba.bits = t.bits; ba.relu = t.relu;
+    ba.w2p = nullptr; ba.z0 = nullptr; ba.ldz = 0; ba.p2 = 0;
+    const int wgs = std::max(1, std::min(c->n_cu, ba.n_rb));
+    if (zf) {
+        ba.w2p = w2img; ba.z0 = zf->z0; ba.ldz = zf->ld_z0; ba.p2 = zf->p2;
+        dense_fwd_bf16x3_kernel<false, 6, true><<<wgs, 512, 0, c->stream>>>(ba);      // (144 KB of static LDS: one workgroup per CU)
+    } else if (ba.bits) {
+        dense_fwd_bf16x3_kernel<true, 6><<<wgs, 512, 0, c->stream>>>(ba);
+    } else {
+        dense_fwd_bf16x3_kernel<false, 6><<<wgs, 512, 0, c->stream>>>(ba);
+    }
+    GCNHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// (2) p = 128, exact f32: the persistent LDS-DMA form (dense_persist.h) — one workgroup per CU for the whole launch, rows dealt
+// in 32-row blocks, three-stage ring.  Not on a co-running stream: its workgroup needs a whole CU.
+static bool dense_fwd_persist_fits(const gcnhip_ctx *c, const Tile128Args &t, bool fast) {
+    const int n_chunks = (t.K + PG_BK - 1) / PG_BK;
+    return fast && t.p == 128 && !c->corun && aligned16(t.x) && aligned16(t.out) &&
+           (uint64_t)(t.m + PG_ROWS) * (uint64_t)t.ldo * 4u < (1ull << 32) && (size_t)n_chunks * 4096 * sizeof(float) <= c->wpack_bytes;
+}
+static int dense_fwd_persist(gcnhip_ctx *c, const gcnhip_feat *f, const Tile128Args &t, const DropSpec &d, bool fast) {
+    if (!dense_fwd_persist_fits(c, t, fast)) return NOT_MINE;
+    const int n_chunks = (t.K + PG_BK - 1) / PG_BK;
+    if (d.on && keep_bits_by_block(d)) {         // keep bits and the packed W from one launch
+        const int n_bits_wgs = (int)ceil_div(((f->nnz + 31) / 32 + 3) / 4, (int64_t)256);
+        const_cast<gcnhip_feat *>(f)->keep_layout = 0;
+        dropbits_pack_w_kernel<<<n_bits_wgs + n_chunks * 4, 256, 0, c->stream>>>(f->keep_bits, f->nnz, d.thr, d.seed, d.d_epoch, d.off >> 7, n_bits_wgs,
+                                                                               t.w, t.ldw, t.K, n_chunks * 4, c->wpack, t.scale);
+    } else {
+        if (d.on) { const int rc = make_keep_bits(c, f, d); if (rc) return rc; }
+        pg_pack_w_kernel<<<ceil_div(n_chunks * 4 * 256, 256), 256, 0, c->stream>>>(t.w, t.ldw, t.K, n_chunks * 4, c->wpack, t.bits ? t.scale : 1.f);
+    }
+    GCNHIP_LAUNCH_CHECK();
+    PersistFwdArgs pa;
+    pa.x = t.x; pa.ldx = t.ldx; pa.wp = c->wpack; pa.out = t.out; pa.ldo = t.ldo;
+    pa.m = t.m; pa.K = t.K; pa.n_chunks = n_chunks; pa.n_rb = ceil_div(t.m, 32);
+    pa.bits = t.bits; pa.relu = t.relu;
+    const int wgs = std::max(1, std::min(c->n_cu, pa.n_rb));
+    if (pa.bits) dense_fwd_persist_kernel<true><<<wgs, 512, 0, c->stream>>>(pa);
+    else dense_fwd_persist_kernel<false><<<wgs, 512, 0, c->stream>>>(pa);
+    GCNHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+// (3) the tile kernels (dense_tile128.h) take every shape: eight waves per tile when `fast`, else the guarded four-wave tile
+static int dense_fwd_tiles(gcnhip_ctx *c, const gcnhip_feat *f, const Tile128Args &t, const DropSpec &d, bool fast, int vx) {
+    if (d.on) { const int rc = make_keep_bits(c, f, d); if (rc) return rc; }
+    const dim3 grid(ceil_div(t.m, T_BM), ceil_div(t.p, T_BN));
+    if (fast) dense_fwd_t128w8_kernel<<<grid, 512, 0, c->stream>>>(t);
+    else if (vx == 4) dense_fwd_t128_kernel<4><<<grid, 256, 0, c->stream>>>(t);
+    else if (vx == 2) dense_fwd_t128_kernel<2><<<grid, 256, 0, c->stream>>>(t);
+    else dense_fwd_t128_kernel<1><<<grid, 256, 0, c->stream>>>(t);
+    GCNHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 static int spmm_fwd_impl(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, const float *w, int ld_w,
                          float *out, int ld_out, int p, float p_drop, uint64_t seed, const uint32_t *d_epoch,
                          uint64_t nnz_offset, const uint8_t *keep_mask, int relu, const Z0Fuse *zf = nullptr) {
@@ -219,97 +317,18 @@ static int spmm_fwd_impl(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals,
     if (zf && !(f->dense && p == 128)) return GCNHIP_NOT_AVAILABLE;   // (the other forms below store `out`, which a fused call does not have)
     if (f->n_rows == 0) return 0;
     const DropSpec d = make_drop(p_drop, seed, d_epoch, nnz_offset, keep_mask);
-    if (f->dense && p > 64) {                 // 128 x 128 MFMA tiles
+    if (f->dense && p > 64) {
         if (d.on && !f->keep_bits) return gcnhip_fail("input dropout on a feature object without a keep-bit array (gcnhip_feat_create_aggregated builds evaluation-only objects)");
         Tile128Args t;
         t.x = vals; t.ldx = f->n_cols; t.w = w; t.ldw = ld_w; t.out = out; t.ldo = ld_out;
         int vx = x_vec_width(f, vals);
         if (vals == f->values && f->values_pad) { t.x = f->values_pad; t.ldx = f->ld_pad; vx = 4; }   // aligned copy of the pristine X
         t.m = f->n_rows; t.K = f->n_cols; t.p = p; t.bits = d.on ? f->keep_bits : nullptr; t.scale = d.scale; t.rows_per_split = 0; t.relu = relu;
-        dim3 grid(ceil_div(f->n_rows, T_BM), ceil_div(p, T_BN));
         const bool fast = vx == 4 && t.ldx % 4 == 0 && (t.K + 31) / 32 * 32 <= t.ldx && ld_w % 4 == 0 && p % T_BN == 0 && aligned16(w);
-        // p = 128: the persistent LDS-DMA form (dense_persist.h) — one workgroup per CU for the whole launch, rows dealt in
-        // 32-row blocks, three-stage ring.  GCNHIP_GEMM_TILES keeps the tile kernels below for A/B runs.
-        const bool tiles_only = c->opt.gemm_tiles != 0;
-        const int n_chunks = (t.K + PG_BK - 1) / PG_BK;
-        // Option gemm_bf16x3 (round 5; 1: wherever the persistent f32 form would run, 2: also on a co-running stream): the same
-        // product on the bf16 matrix pipe from three exact bf16 planes per f32 operand (dense_bf16x3.h) — f32 results inside the
-        // f32 summation bound, 0.21 ms instead of 0.35 at Reddit scale.  0 keeps the exact-f32 MFMA kernels.
-        const int bx = c->opt.gemm_bf16x3;
-        if (zf && !(fast && p == 128 && !tiles_only && bx && !d.on && aligned16(t.x) && zf->p2 >= 1 && zf->p2 <= 64 && zf->ld_z0 % 4 == 0 &&
-                    zf->ld_z0 >= zf->p2 && zf->ld_w2 >= zf->p2 && aligned16(zf->z0) && (size_t)n_chunks * 2 * BX_BH_BYTES + BX_W2_BYTES <= c->wpack_bytes))
-            return GCNHIP_NOT_AVAILABLE;                          // the caller runs the two products one after the other
-        if (fast && p == 128 && !tiles_only && bx && (!d.on || keep_bits_cm_fit(f)) && (zf || ((bx >= 2 || !c->corun) && aligned16(out) &&
-            (uint64_t)(t.m + 256) * (uint64_t)ld_out * 4u < (1ull << 32))) && aligned16(t.x) && (size_t)n_chunks * 2 * BX_BH_BYTES <= c->wpack_bytes) {
-            const int n_hs = 2 * n_chunks;
-            uint4 *wp3 = reinterpret_cast<uint4 *>(c->wpack);
-            uint4 *w2img = wp3 + (size_t)n_hs * (BX_BH_BYTES / 16);
-            if (d.on) {                                  // keep words (chunk-major) and the packed planes of W from one launch
-                const BxBitsArgs kb = keep_bits_cm_args(f, d);
-                const int n_bits_wgs = ceil_div(kb.m, kb.R);
-                const_cast<gcnhip_feat *>(f)->keep_layout = 1;
-                dropbits_bx_pack_w_kernel<<<n_bits_wgs + n_hs, 256, 0, c->stream>>>(kb, n_bits_wgs, w, ld_w, t.K, n_hs, wp3, t.scale);
-            } else {
-                if (zf) bx_pack_w_kernel<<<n_hs + 4, 256, 0, c->stream>>>(w, ld_w, t.K, n_hs, wp3, 1.f, zf->w2, zf->ld_w2, zf->p2, w2img);
-                else bx_pack_w_kernel<<<n_hs, 256, 0, c->stream>>>(w, ld_w, t.K, n_hs, wp3, t.bits ? t.scale : 1.f);
-            }
-            GCNHIP_LAUNCH_CHECK();
-            Bx3FwdArgs ba;
-            ba.x = t.x; ba.ldx = t.ldx; ba.wp = wp3; ba.out = out; ba.ldo = ld_out;
-            ba.m = t.m; ba.K = t.K; ba.n_chunks = n_chunks; ba.n_rb = ceil_div(t.m, 32);
-            ba.bits = t.bits; ba.relu = relu;
-            ba.w2p = nullptr; ba.z0 = nullptr; ba.ldz = 0; ba.p2 = 0;
-            int wgs = std::max(1, std::min(c->n_cu, ba.n_rb));
-            if (zf) {
-                ba.w2p = w2img; ba.z0 = zf->z0; ba.ldz = zf->ld_z0; ba.p2 = zf->p2;
-                dense_fwd_bf16x3_kernel<false, 6, 0, 8, true><<<wgs, 512, 0, c->stream>>>(ba);      // (144 KB of static LDS: one workgroup per CU)
-                GCNHIP_LAUNCH_CHECK();
-                return 0;
-            }
-            if (c->corun && c->opt.gemm_lane_wgs > 0) wgs = std::max(1, std::min(wgs, c->opt.gemm_lane_wgs));   // fewer CUs host the lane's product
-            // option gemm_lane_waves = 4: a context that runs beside another stream's kernels takes the four-wave form (half a CU's
-            // registers: co-resident with a gather-bound kernel's waves).  Measured (docs/NOTEBOOK_r5.md §7): the lane's product is
-            // then truly concurrent with the training pass's aggregation, which loses half its resident waves on those CUs —
-            // 347.5 (256 CUs), 351.5 (128), 340 (64) epochs/s against 351.0 for the eight-wave form: not the default
-            const bool four = c->corun && c->opt.gemm_lane_waves == 4;
-            if (ba.bits) { if (four) dense_fwd_bf16x3_kernel<true, 6, 0, 4><<<wgs, 256, 0, c->stream>>>(ba); else dense_fwd_bf16x3_kernel<true, 6><<<wgs, 512, 0, c->stream>>>(ba); }
-            else { if (four) dense_fwd_bf16x3_kernel<false, 6, 0, 4><<<wgs, 256, 0, c->stream>>>(ba); else dense_fwd_bf16x3_kernel<false, 6><<<wgs, 512, 0, c->stream>>>(ba); }
-            GCNHIP_LAUNCH_CHECK();
-            return 0;
-        }
-        if (fast && p == 128 && !tiles_only && !c->corun && aligned16(t.x) && aligned16(out) &&
-            (uint64_t)(t.m + PG_ROWS) * (uint64_t)ld_out * 4u < (1ull << 32) && (size_t)n_chunks * 4096 * sizeof(float) <= c->wpack_bytes) {
-            if (d.on && keep_bits_by_block(d)) {         // keep bits and the packed W from one launch
-                const int n_bits_wgs = (int)ceil_div(((f->nnz + 31) / 32 + 3) / 4, (int64_t)256);
-                const_cast<gcnhip_feat *>(f)->keep_layout = 0;
-                dropbits_pack_w_kernel<<<n_bits_wgs + n_chunks * 4, 256, 0, c->stream>>>(f->keep_bits, f->nnz, d.thr, d.seed, d.d_epoch, d.off >> 7, n_bits_wgs,
-                                                                                       w, ld_w, t.K, n_chunks * 4, c->wpack, t.scale);
-            } else {
-                if (d.on) { const int rc = make_keep_bits(c, f, d); if (rc) return rc; }
-                pg_pack_w_kernel<<<ceil_div(n_chunks * 4 * 256, 256), 256, 0, c->stream>>>(w, ld_w, t.K, n_chunks * 4, c->wpack, t.bits ? t.scale : 1.f);
-            }
-            GCNHIP_LAUNCH_CHECK();
-            PersistFwdArgs pa;
-            pa.x = t.x; pa.ldx = t.ldx; pa.wp = c->wpack; pa.out = out; pa.ldo = ld_out;
-            pa.m = t.m; pa.K = t.K; pa.n_chunks = n_chunks; pa.n_rb = ceil_div(t.m, 32);
-            pa.bits = t.bits; pa.relu = relu;
-            const int wgs = std::max(1, std::min(c->n_cu, pa.n_rb));
-            if (pa.bits) dense_fwd_persist_kernel<true><<<wgs, 512, 0, c->stream>>>(pa);
-            else dense_fwd_persist_kernel<false><<<wgs, 512, 0, c->stream>>>(pa);
-            GCNHIP_LAUNCH_CHECK();
-            return 0;
-        }
-        if (d.on) { const int rc = make_keep_bits(c, f, d); if (rc) return rc; }
-        // eight waves per tile: same bits, 4 % faster than the four-wave form (0.383 -> 0.367 ms at Reddit scale);
-        // GCNHIP_GEMM_W4 selects the four-wave kernel for A/B runs
-        const bool w4 = c->opt.gemm_w4 != 0;
-        if (fast && !w4) dense_fwd_t128w8_kernel<<<grid, 512, 0, c->stream>>>(t);
-        else if (fast) dense_fwd_t128_kernel<4, true><<<grid, 256, 0, c->stream>>>(t);
-        else if (vx == 4) dense_fwd_t128_kernel<4><<<grid, 256, 0, c->stream>>>(t);
-        else if (vx == 2) dense_fwd_t128_kernel<2><<<grid, 256, 0, c->stream>>>(t);
-        else dense_fwd_t128_kernel<1><<<grid, 256, 0, c->stream>>>(t);
-        GCNHIP_LAUNCH_CHECK();
-        return 0;
+        int rc = dense_fwd_bf16x3(c, f, t, d, fast, zf);
+        if (rc == NOT_MINE) rc = dense_fwd_persist(c, f, t, d, fast);
+        if (rc == NOT_MINE) rc = dense_fwd_tiles(c, f, t, d, fast, vx);
+        return rc;
     }
     if (f->dense) {
         if (d.on) { const int rc = make_keep_bits(c, f, d); if (rc) return rc; }
@@ -413,6 +432,17 @@ static bool dense_bwd_plan(const gcnhip_ctx *c, const gcnhip_feat *f, int p, int
     *S_out = ceil_div(f->n_rows, rps);
     return true;
 }
+// that plan's products from three bf16 planes per operand (option gemm_bf16x3; dense_bf16x3.h): p = 128 and the padded copy of X
+// (row stride a multiple of 128, zeros past K), every byte offset and the keep-word index inside 32 bits
+static bool dense_bwd_bf16x3_fits(const gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, const float *dout, int ld_dout, int p,
+                                  const DropSpec &d, int rps) {
+    const int bx = c->opt.gemm_bf16x3, kt = ceil_div(f->n_cols, 128);
+    const bool padded = vals == f->values && f->values_pad && f->ld_pad >= kt * 128;
+    return bx && (bx >= 2 || !c->corun) && p == 128 && padded && rps % 16 == 0 && ld_dout % 4 == 0 && aligned16(dout) &&
+           (uint64_t)f->n_rows * (uint64_t)f->ld_pad * 4u < (1ull << 32) && (uint64_t)f->n_rows * (uint64_t)ld_dout * 4u < (1ull << 32) &&
+           (uint64_t)f->n_rows * (uint64_t)f->n_cols < (1ull << 32) && (uint64_t)kt * 16u * (uint64_t)f->n_rows < (1ull << 32) &&
+           (!d.on || keep_bits_cm_fit(f));
+}
 
 // splits [s0, s1) of the plan into their slabs
 // fresh: the keep decisions of this call have not been made yet (else: whoever made them left them in f->keep_bits)
@@ -427,26 +457,16 @@ static int dense_bwd_part(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals
     const int p_ld = (p + 3) / 4 * 4;
     const int rc = ensure_slab(c, (size_t)S * f->n_cols * p_ld * sizeof(float));
     if (rc) return rc;
-    // Option gemm_bf16x3: the same split-K product from three bf16 planes per operand (dense_bf16x3.h): every split's slab,
-    // then the same ordered slab sum.  The padded copy of X (row stride a multiple of 128, zeros past K) is what it reads.
-    {
-        const int bx = c->opt.gemm_bf16x3;
-        const bool padded = vals == f->values && f->values_pad && f->ld_pad >= kt * 128;
-        if (bx && (bx >= 2 || !c->corun) && p == 128 && padded && rps % 16 == 0 && ld_dout % 4 == 0 && aligned16(dout) &&
-            (uint64_t)f->n_rows * (uint64_t)f->ld_pad * 4u < (1ull << 32) && (uint64_t)f->n_rows * (uint64_t)ld_dout * 4u < (1ull << 32) &&
-            (uint64_t)f->n_rows * (uint64_t)f->n_cols < (1ull << 32) && (uint64_t)kt * 16u * (uint64_t)f->n_rows < (1ull << 32) &&
-            (!d.on || keep_bits_cm_fit(f))) {
-            { const int rl = want_keep_layout(c, f, d, 1, fresh); if (rl) return rl; }
-            Bx3BwdArgs b;
-            b.x = f->values_pad; b.ldx = f->ld_pad; b.dout = dout; b.ldd = ld_dout; b.slab = c->slab; b.p_ld = p_ld;
-            b.m = f->n_rows; b.K = f->n_cols; b.rps = rps; b.split0 = s0; b.bits = d.on ? f->keep_bits : nullptr; b.scale = d.on ? d.scale : 1.f;
-            const dim3 grid(kt, s1 - s0);
-            // (load order 5: keep word first, X and dH0 loads interleaved: 0.230 vs 0.236 ms in the rotated runs of tools/gemm_bf16x3.hip)
-            if (b.bits) dense_bwd_bf16x3_kernel<true, 6, 5><<<grid, 256, 0, c->stream>>>(b);
-            else dense_bwd_bf16x3_kernel<false, 6><<<grid, 256, 0, c->stream>>>(b);
-            GCNHIP_LAUNCH_CHECK();
-            return 0;
-        }
+    if (dense_bwd_bf16x3_fits(c, f, vals, dout, ld_dout, p, d, rps)) {      // every split's slab, then the same ordered slab sum
+        { const int rl = want_keep_layout(c, f, d, 1, fresh); if (rl) return rl; }
+        Bx3BwdArgs b;
+        b.x = f->values_pad; b.ldx = f->ld_pad; b.dout = dout; b.ldd = ld_dout; b.slab = c->slab; b.p_ld = p_ld;
+        b.m = f->n_rows; b.K = f->n_cols; b.rps = rps; b.split0 = s0; b.bits = d.on ? f->keep_bits : nullptr; b.scale = d.on ? d.scale : 1.f;
+        const dim3 grid(kt, s1 - s0);
+        if (b.bits) dense_bwd_bf16x3_kernel<true, 6><<<grid, 256, 0, c->stream>>>(b);
+        else dense_bwd_bf16x3_kernel<false, 6><<<grid, 256, 0, c->stream>>>(b);
+        GCNHIP_LAUNCH_CHECK();
+        return 0;
     }
     { const int rl = want_keep_layout(c, f, d, 0, fresh); if (rl) return rl; }
     Tile128Args t;

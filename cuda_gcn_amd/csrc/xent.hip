@@ -388,8 +388,7 @@ static int xent_launch(gcnhip_ctx *c, XentArgs a, float *d_result, int32_t *d_re
     }
     // a lane per row when the rows are whole, aligned float4 pieces of at most 64 classes
     const int nv4 = (a.C + 3) / 4;
-    const bool force_wave = c->opt.xent_wave != 0;                            // A/B aid
-    const bool lanes = !force_wave && a.C <= 64 && a.n_rows > 0 && a.ld % 4 == 0 && a.ld >= 4 * nv4 && aligned16(a.logits) &&
+    const bool lanes = a.C <= 64 && a.n_rows > 0 && a.ld % 4 == 0 && a.ld >= 4 * nv4 && aligned16(a.logits) &&
                        (!a.grad || (a.ld_grad % 4 == 0 && a.ld_grad >= 4 * nv4 && aligned16(a.grad)));
     if (lanes) {
         blocks = ceil_div(a.n_rows, 256);

@@ -58,12 +58,16 @@ int  gcnhip_ctx_create(gcnhip_ctx **ctx, int device, void *stream);
 int  gcnhip_ctx_destroy(gcnhip_ctx *ctx);
 /* Options of a context, by name (argument error -1 for an unknown name; gcnhip_last_error() says so).  Every option starts
  * from the environment variable GCNHIP_<NAME IN CAPITALS>, which is read ONCE, when the context is created: no entry point
- * consults the environment at call time, so a call's behaviour is a function of its arguments and its context.  Most are
- * A/B aids behind measurements DESIGN.md records; results are the same bits unless the option's line says otherwise:
- *   gs_u (0: by table size; 1/2/4 row loads in flight per lane group of the aggregation), gemm_tiles / gemm_w4
- *   (first-layer GEMM forms), xent_finalize / adam_sum_launch (final reductions as their own launches), xent_wave,
- *   atb_cap_mb, rs_wgs, spmm_rows (rows per wave of the sparse forward; 0: by row count), spmm_general (1: narrow
- *   rows take the general sparse kernels too — a differently associated f32 sum), spmm_nw and split_edges (read by gcnhip_feat_create / gcnhip_graph_create*: set them BEFORE building objects). */
+ * consults the environment at call time, so a call's behaviour is a function of its arguments and its context.  Results
+ * are the same bits unless the option's line says otherwise.  The ten options:
+ *   gemm_bf16x3 (2: the dense first-layer and class-layer products from three bf16 planes per f32 operand, also on a
+ *   co-running stream; 1: not on a co-running stream; 0: the exact-f32 MFMA kernels — a differently rounded f32 sum),
+ *   gs_l (8 / 4: column slices of 32 / 16 floats in the hidden-width aggregation; 0: 64), gs_u (0: by table size; 1/2/4
+ *   row loads in flight per lane group of the aggregation), xent_finalize / adam_sum_launch (final reductions as their
+ *   own launches), spmm_slices (0: no XCD-bound column slices in the sparse forward), spmm_rows (rows per wave of the
+ *   sparse forward; 0: by row count), spmm_general (1: narrow rows take the general sparse kernels too — a differently
+ *   associated f32 sum), spmm_nw and split_edges (read by gcnhip_feat_create / gcnhip_graph_create*: set them BEFORE
+ *   building objects). */
 int  gcnhip_ctx_set_option(gcnhip_ctx *ctx, const char *name, int value);
 int  gcnhip_ctx_get_option(const gcnhip_ctx *ctx, const char *name, int *value);
 int  gcnhip_ctx_sync(gcnhip_ctx *ctx);                 /* synchronises the stream */

@@ -15,8 +15,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
 @pytest.mark.parametrize("src,patterns,min_kernels", [
-    ("cuda_gcn_amd/csrc/matmul.hip", ["class_fwd_bf16x3_kernelILi0", "class_bwd_bf16x3_kernelILi"], 5),
-    ("cuda_gcn_amd/csrc/spmm.hip", ["dense_fwd_bf16x3", "dense_bwd_bf16x3"], 4),
+    ("cuda_gcn_amd/csrc/matmul.hip", ["class_fwd_bf16x3_kernel10ClsFwdArgs", "class_bwd_bf16x3_kernelILi"], 5),
+    ("cuda_gcn_amd/csrc/spmm.hip", ["dense_fwd_bf16x3_kernelILb", "dense_bwd_bf16x3_kernelILb"], 5),
 ])
 def test_no_access_to_registers_of_loads_in_flight(src, patterns, min_kernels):
     import check_asm_loads as chk

@@ -3,8 +3,10 @@
 gcnhip_matmul_fwd and gcnhip_matmul_bwd_ex (mask bits + row factors, as HipGCN calls them), with the bf16x3 kernels of
 csrc/class_bf16x3.h (option gemm_bf16x3 = 2) and with the f32-MFMA kernels of csrc/dense_kernels.h (0).
 
-    python tools/bench_class.py [N] [iters] [noabl]   (run on the GPU box; counter passes: PMC_PROG="tools/bench_class.py 232965 10 noabl"
-                                                       PMC_MATCH="class_,slab_reduce,rowstream,atb" tools/pmc_gemm.sh <out>)
+    python tools/bench_class.py [N] [iters]   (run on the GPU box; counter passes: PMC_PROG="tools/bench_class.py 232965 10"
+                                               PMC_MATCH="class_,slab_reduce,rowstream,atb" tools/pmc_gemm.sh <out>)
+The ablation, load-order and workgroups-per-CU legs this script once had are recorded in docs/NOTEBOOK_r5.md; the kernel variants
+they ran are at commit 46288b1.
 """
 import ctypes as C
 import json
@@ -20,7 +22,6 @@ from cuda_gcn_amd.ops import Device, _ck  # noqa: E402
 def main():
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 232965
     iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-    noabl = "noabl" in sys.argv[3:]                      # counter passes: only the product's kernels
     h, Cc, ldc = 128, 41, 48
     dev = Device(0)
     lib = dev.lib
@@ -57,29 +58,6 @@ def main():
         print(f"[bench_class] {name}: H1.W2 {f * 1e3:.1f} us ({by_f / f / 1e6:.0f} GB/s of {by_f / 1e6:.0f} MB), "
               f"dH1 + dW2 {b * 1e3:.1f} us ({by_b / b / 1e6:.0f} GB/s of {by_b / 1e6:.0f} MB)", flush=True)
     lib.gcnhip_ctx_set_option(dev.ctx, b"gemm_bf16x3", 2)
-    if noabl:
-        print(json.dumps(res)); return
-    for abl, what in ((1, "no matrix work (loads, stores)"), (2, "no stores"), (3, "loads only")):
-        lib.gcnhip_ctx_set_option(dev.ctx, b"cls_abl", abl)
-        f = timeit(lambda: _ck(lib, lib.gcnhip_matmul_fwd(dev.ctx, h1.ptr, h, w2.ptr, ldc, z0.ptr, ldc, N, h, Cc), "fwd"))
-        b = timeit(lambda: _ck(lib, lib.gcnhip_matmul_bwd_ex(dev.ctx, h1.ptr, h, w2.ptr, ldc, dz.ptr, ldc, dh.ptr, h, dw2.ptr, ldc, N, h, Cc, 2.0,
-                                                             bits.ptr, 4, rs.ptr), "bwd"))
-        res[f"ablation_{abl}"] = {"what": what, "fwd_ms": f, "bwd_ms": b}
-        print(f"[bench_class] bf16x3, {what}: H1.W2 {f * 1e3:.1f} us, dH1 + dW2 {b * 1e3:.1f} us", flush=True)
-    for rep in range(3):                                  # load order of the backward's row loads (rotated: the clock drifts)
-        for abl, what in ((0, "dZ0 row, mask words, row factor"), (4, "mask words and row factor first")):
-            lib.gcnhip_ctx_set_option(dev.ctx, b"cls_abl", abl)
-            b = timeit(lambda: _ck(lib, lib.gcnhip_matmul_bwd_ex(dev.ctx, h1.ptr, h, w2.ptr, ldc, dz.ptr, ldc, dh.ptr, h, dw2.ptr, ldc, N, h, Cc, 2.0,
-                                                                 bits.ptr, 4, rs.ptr), "bwd"))
-            res.setdefault(f"bwd_load_order_{abl}", []).append(b)
-            print(f"[bench_class] bf16x3 backward, {what}: {b * 1e3:.1f} us", flush=True)
-    lib.gcnhip_ctx_set_option(dev.ctx, b"cls_abl", 0)
-    for wgs in (1, 2, 3):
-        lib.gcnhip_ctx_set_option(dev.ctx, b"cls_wgs", wgs)
-        f = timeit(lambda: _ck(lib, lib.gcnhip_matmul_fwd(dev.ctx, h1.ptr, h, w2.ptr, ldc, z0.ptr, ldc, N, h, Cc), "fwd"))
-        res[f"fwd_wgs_{wgs}"] = f
-        print(f"[bench_class] bf16x3, {wgs} workgroups per CU: H1.W2 {f * 1e3:.1f} us", flush=True)
-    lib.gcnhip_ctx_set_option(dev.ctx, b"cls_wgs", 0)
     print(json.dumps(res))
 
 

@@ -3,10 +3,10 @@
 // (m = 232 965, K = 602, p = 128; reference: SparseMatmul::forward, /root/reference/src/seq/module.cpp:47-61):
 // time per launch (HIP events, back to back) and the error of both against a float64 product on sampled rows, in units of
 // eps_f32 * sum_k |x_k w_k| (the bound the parity tests use is 8 of those units).
-// Also here: the template ablations of the forward (which stream costs what), the dropout ablations that led to the chunk-major
-// keep words, the W prefetch distance, and the load-ORDER experiments of both kernels (runs rotated: the clock drifts with what ran
-// before) — docs/NOTEBOOK_r5.md §2.  The bf16x3 kernels read keep words chunk-major; the tool derives them from the flat bits the
-// f32 kernels and the float64 check use.
+// Also here: the forward beside a co-running kernel (bit-identical to the run alone?) and the global_load_lds_dwordx3 probe.
+// The bf16x3 kernels read keep words chunk-major; the tool derives them from the flat bits the f32 kernels and the float64 check use.
+// The ablation, prefetch-distance and load-order timings this tool once produced are recorded in DESIGN.md 4.1-4.3 and
+// docs/NOTEBOOK_r5.md §2, docs/NOTEBOOK_r6.md §2; the kernel variants that produced them are at commit 46288b1.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Icuda_gcn_amd/csrc tools/gemm_bf16x3.hip -o build/gemm_bf16x3
 //   build/gemm_bf16x3 [m] [K] [iters]
 #include <hip/hip_runtime.h>
@@ -147,7 +147,7 @@ int main(int argc, char **argv) {
     // ---- exact-f32 MFMA, persistent LDS-DMA kernel (the product's default since round 3)
     {
         const int n_kg = n_chunks * 4;
-        PersistFwdArgs a{dx, ldx, dwp32, dout2, p, m, K, n_chunks, n_rb, nullptr, 0, 0};
+        PersistFwdArgs a{dx, ldx, dwp32, dout2, p, m, K, n_chunks, n_rb, nullptr, 0};
         for (int drop = 0; drop < 2; drop++) {
             a.bits = drop ? dbits : nullptr;
             const float scale = drop ? 2.f : 1.f;
@@ -164,45 +164,6 @@ int main(int argc, char **argv) {
     // ---- three bf16 planes
     {
         Bx3FwdArgs a{dx, ldx, dwp, dout, p, m, K, n_chunks, n_rb, nullptr, 0};
-        if (argc > 4 && !strcmp(argv[4], "price")) {
-            // round 6: what bounds the MFMA skeleton (results wrong in every ablation; the full kernel first and last)
-            for (int rep = 0; rep < 2; rep++) {
-                printf("  full kernel, no dropout:                      %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0><<<n_cu, 512>>>(a); }));
-                printf("  skeleton (ablation 15: MFMAs + barriers):     %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 15><<<n_cu, 512>>>(a); }));
-                printf("  skeleton without the barriers (15 + 1024):    %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 15 + 1024><<<n_cu, 512>>>(a); }));
-                printf("  full kernel without the barriers (1024):      %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 1024><<<n_cu, 512>>>(a); }));
-                printf("  no W LDS reads, no barriers (8 + 1024):       %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 8 + 1024><<<n_cu, 512>>>(a); }));
-                printf("  no split (4):                                 %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 4><<<n_cu, 512>>>(a); }));
-            }
-            return 0;
-        }
-        // where the time goes: each ablation drops one cost (results wrong): 1 no X loads, 2 no W DMA, 4 no split, 8 no W LDS reads
-        printf("  ablation  1 (no X loads):     %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 1><<<n_cu, 512>>>(a); }));
-        printf("  ablation  2 (no W DMA):       %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 2><<<n_cu, 512>>>(a); }));
-        printf("  ablation  4 (no split):       %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 4><<<n_cu, 512>>>(a); }));
-        printf("  ablation  8 (no W LDS reads): %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 8><<<n_cu, 512>>>(a); }));
-        a.bits = dcm;
-        printf("  dropout, full:                %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0><<<n_cu, 512>>>(a); }));
-        printf("  dropout, keep word loaded last:  %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 128><<<n_cu, 512>>>(a); }));
-        printf("  dropout, full (again):        %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0><<<n_cu, 512>>>(a); }));
-        printf("  X loads ahead of the W pieces: dropout %.4f, none %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 256><<<n_cu, 512>>>(a); }),
-               time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 256><<<n_cu, 512>>>(a); }));
-        for (int rep = 0; rep < 2; rep++)
-            printf("  X loads at the top of the chunk: dropout %.4f (default %.4f), none %.4f (default %.4f) ms\n",
-                   time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 512><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0><<<n_cu, 512>>>(a); }),
-                   time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 512><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0><<<n_cu, 512>>>(a); }));
-        printf("  dropout, mask not applied:    %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 32><<<n_cu, 512>>>(a); }));
-        printf("  dropout, keep words not read: %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 64><<<n_cu, 512>>>(a); }));
-        printf("  dropout, neither:             %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 96><<<n_cu, 512>>>(a); }));
-        printf("  no dropout:                   %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0><<<n_cu, 512>>>(a); }));
-        // W k-steps in flight ahead of use (the W wait counts this wave's YOUNGER W pieces; X loads still in flight count against it)
-        printf("  prefetch distance 6 / 7 / 8 / 9, no dropout: %.4f %.4f %.4f %.4f ms\n",
-               time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0, 8, false, 6><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0, 8, false, 7><<<n_cu, 512>>>(a); }),
-               time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0, 8, false, 8><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 0, 8, false, 9><<<n_cu, 512>>>(a); }));
-        printf("  prefetch distance 6 / 7 / 8 / 9, dropout:    %.4f %.4f %.4f %.4f ms\n",
-               time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0, 8, false, 6><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0, 8, false, 7><<<n_cu, 512>>>(a); }),
-               time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0, 8, false, 8><<<n_cu, 512>>>(a); }), time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<true, 6, 0, 8, false, 9><<<n_cu, 512>>>(a); }));
-        printf("  ablation 15 (all of them):    %.4f ms\n", time_ms(iters, [&]() { dense_fwd_bf16x3_kernel<false, 6, 15><<<n_cu, 512>>>(a); }));
         for (int np = 6; np <= 8; np += 2)
             for (int drop = 0; drop < 2; drop++) {
                 a.bits = drop ? dcm : nullptr;
@@ -234,21 +195,20 @@ int main(int argc, char **argv) {
         CK(hipDeviceSynchronize());
         std::vector<float> ref((size_t)m * p), got((size_t)m * p);
         CK(hipMemcpy(ref.data(), dout, ref.size() * 4, hipMemcpyDeviceToHost));
-        for (int use_lds = 0; use_lds < 4; use_lds++) {
+        for (int use_lds = 0; use_lds < 2; use_lds++) {
             int bad_runs = 0; long bad_vals = 0; int first_bad_row = -1;
             for (int it = 0; it < 20; it++) {
                 CK(hipMemsetAsync(dout, 0xFF, (size_t)m * p * 4, s1));
-                hog_kernel<<<2048, 256, 0, s2>>>(hog, hog_n, use_lds & 1);
-                if (use_lds & 2) dense_fwd_bf16x3_kernel<false, 6, 16><<<n_cu, 512, 0, s1>>>(a);
-                else dense_fwd_bf16x3_kernel<false, 6><<<n_cu, 512, 0, s1>>>(a);
+                hog_kernel<<<2048, 256, 0, s2>>>(hog, hog_n, use_lds);
+                dense_fwd_bf16x3_kernel<false, 6><<<n_cu, 512, 0, s1>>>(a);
                 CK(hipDeviceSynchronize());
                 CK(hipMemcpy(got.data(), dout, got.size() * 4, hipMemcpyDeviceToHost));
                 long nb = 0;
                 for (size_t i = 0; i < got.size(); i++) if (memcmp(&got[i], &ref[i], 4)) { nb++; if (first_bad_row < 0) first_bad_row = (int)(i / p); }
                 bad_runs += nb > 0; bad_vals += nb;
             }
-            printf("forward beside a co-running kernel (%s%s): %d of 20 runs differ from the run alone (%ld values, first in row %d)\n",
-                   (use_lds & 1) ? "holding LDS" : "no LDS", (use_lds & 2) ? ", every wait vmcnt(0)" : "", bad_runs, bad_vals, first_bad_row);
+            printf("forward beside a co-running kernel (%s): %d of 20 runs differ from the run alone (%ld values, first in row %d)\n",
+                   use_lds ? "holding LDS" : "no LDS", bad_runs, bad_vals, first_bad_row);
         }
         CK(hipFree(hog));
     }
@@ -328,19 +288,6 @@ int main(int argc, char **argv) {
             CK(hipGetLastError());
             printf("bf16x3 weight gradient, 6 plane products, dropout %d: %.4f ms  %.1f TF/s algorithmic\n", drop, ms, 2.0 * m * K * p / ms / 1e9);
             check_dw(ddw, "bf16x3, 6 plane products", drop, b.scale);
-        }
-        {   // the order in which a step's loads are issued (kernel alone, no slab sum)
-            Bx3BwdArgs b{dxp, ldp, dd, p, dslab, p, m, K, rps, 0, dcm, 2.f};
-            dim3 grid(n_fr, S);
-            for (int rep = 0; rep < 3; rep++)    // (rotated: the clock drifts with what ran before)
-                printf("  weight gradient with dropout, kernel alone; X, dH0, keep word: %.4f  keep word first: %.4f  dH0 first: %.4f  interleaved: %.4f  interleaved + keep word first: %.4f ms\n",
-                       time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<true, 6, 0><<<grid, 256>>>(b); }),
-                       time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<true, 6, 1><<<grid, 256>>>(b); }), time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<true, 6, 2><<<grid, 256>>>(b); }),
-                       time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<true, 6, 4><<<grid, 256>>>(b); }), time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<true, 6, 5><<<grid, 256>>>(b); }));
-            b.bits = nullptr; b.scale = 1.f;
-            printf("  weight gradient without dropout, kernel alone; X, dH0: %.4f  dH0 first: %.4f  interleaved: %.4f ms\n",
-                   time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<false, 6, 0><<<grid, 256>>>(b); }), time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<false, 6, 2><<<grid, 256>>>(b); }),
-                   time_ms(iters, [&]() { dense_bwd_bf16x3_kernel<false, 6, 4><<<grid, 256>>>(b); }));
         }
     }
     return 0;

@@ -2,7 +2,7 @@
 # PMC passes for the GraphSum kernels (run on the GPU box through gpurun):
 #   tools/pmc_graphsum.sh <out_dir> [dataset] [hidden] [mode of tools/bench_ops.py: only_h | only_c | only_c64 | only_split ...]
 # The same three memory-side passes for any other program / kernels:
-#   PMC_PROG="tools/bench_class.py 232965 10 noabl" PMC_MATCH="class_,gemm_,slab_reduce" tools/pmc_graphsum.sh <out_dir>
+#   PMC_PROG="tools/bench_class.py 232965 10" PMC_MATCH="class_,gemm_,slab_reduce" tools/pmc_graphsum.sh <out_dir>
 # One rocprofv3 run per counter group (FETCH_SIZE and WRITE_SIZE do not fit one pass,
 # MI355X_MICROARCH.md §rocprofv3 PMC slots); --pmc is combined with --kernel-trace only.
 set -e
