@@ -165,6 +165,8 @@ GCNHIP_SYMBOLS = {
     "gcnhip_event_sync": (I, [P]),
     "gcnhip_bce_fwd_rows": (I, [P, P, I, P, I, P, I, P, I, I, I, I, P, P, P]),
     "gcnhip_bce_predict_rows": (I, [P, P, I, P, I, I, P, I, P, I]),
+    "gcnhip_confusion_rows": (I, [P, P, P, I, P, I, I, P, P]),
+    "gcnhip_bce_class_counts_rows": (I, [P, P, I, P, I, P, I, I, P]),
 }
 
 
@@ -208,6 +210,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_set_weights": (I, [P, P, P]),
     "gcnhost_model_predict": (I, [P, P, I, P, P, P]),
     "gcnhost_model_predict_multilabel": (I, [P, P, I, P, P]),
+    "gcnhost_model_evaluate": (I, [P, I, P, I, P, C.POINTER(I64), C.POINTER(I64)]),
+    "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),
     "gcnhost_model_save_weights": (I, [P, C.c_char_p]),
     "gcnhost_model_load_weights": (I, [P, C.c_char_p]),

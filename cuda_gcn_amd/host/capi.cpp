@@ -1,5 +1,6 @@
 // capi.cpp — extern "C" surface of the host library (include/gcnhost.h).
 #include "gcnhost.h"
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -9,6 +10,7 @@
 #include "hip_check.h"
 #include "parser.h"
 #include "labels.h"
+#include "report.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -188,6 +190,27 @@ int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pr
 }
 int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob) {
     API_TRY({ m->gcn->predict_multilabel(nodes, n, bits, prob); })
+}
+int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
+    if (!m || !counts) { g_err = "gcnhost_model_evaluate: invalid argument"; return -1; }
+    API_TRY({ m->gcn->evaluate(split, nodes, n, counts, rows_counted, unlabelled); })
+}
+int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
+                         int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {
+    ClassReport r;
+    if (gcn_class_report(num_classes, confusion, tp, fp, fn, &r, &g_err) != 0) return -1;
+    const size_t C = (size_t)num_classes;
+    if (tp_fp_fn) {
+        std::copy(r.tp.begin(), r.tp.end(), tp_fp_fn);
+        std::copy(r.fp.begin(), r.fp.end(), tp_fp_fn + C);
+        std::copy(r.fn.begin(), r.fn.end(), tp_fp_fn + 2 * C);
+    }
+    if (support) std::copy(r.support.begin(), r.support.end(), support);
+    if (precision) std::copy(r.precision.begin(), r.precision.end(), precision);
+    if (recall) std::copy(r.recall.begin(), r.recall.end(), recall);
+    if (f1) std::copy(r.f1.begin(), r.f1.end(), f1);
+    if (summary) { summary[0] = r.macro_f1; summary[1] = r.micro_f1; summary[2] = r.accuracy; }
+    return 0;
 }
 int gcnhost_labels_read(const char *path, int *num_nodes, int *num_classes, uint32_t *bits) {
     if (!path || !num_nodes || !num_classes) { g_err = "gcnhost_labels_read: invalid argument"; return -1; }

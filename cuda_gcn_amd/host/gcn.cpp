@@ -879,6 +879,9 @@ void HipGCN::release() {
     gcnhip_free(env.ctx, d_pred);
     gcnhip_free(env.ctx, d_prob);
     gcnhip_free(env.ctx, d_logp);
+    gcnhip_free(env.ctx, d_eval_counts);
+    gcnhip_free(env.ctx, d_eval_rows);
+    gcnhip_free(env.ctx, d_label_all);
     timers.reset();
     exchange_buffers_destroy(&xbuf);
     owned_comm.reset();
@@ -1412,6 +1415,39 @@ const gcnhip_rowset *HipGCN::query_subset(const std::vector<int> &rows) {
     return pred_rows;
 }
 
+// An evaluation forward (eval_async's module list without the loss) on the main stream with one hook set on the logit
+// aggregation: the prediction epilogue, or the logits redirected to a scratch table.  Training state stays as it was.
+void HipGCN::forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect) {
+    if (flags & HIPGCN_MODULAR)
+        GCNHIP_CHECK(gcnhip_d2d_async(env.ctx, input->data, gcnhip_feat_values(feat), (size_t)gcnhip_feat_nnz(feat) * sizeof(float)));
+    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
+    logits_gs->predict = prediction;
+    logits_gs->redirect = redirect;
+    try {
+        for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);       // the last module is the loss
+    } catch (...) {
+        logits_gs->predict = nullptr;
+        logits_gs->redirect = nullptr;
+        throw;
+    }
+    logits_gs->predict = nullptr;
+    logits_gs->redirect = nullptr;
+    // variable 3: a fused evaluation keeps H1 in registers (what it held stays); otherwise the forward stored it
+    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+}
+
+// scratch logits of the multi-label prediction and evaluation [local rows x ld of Z], zeroed once
+float *HipGCN::ml_logits_scratch() {
+    if (!d_ml_logits) {
+        const size_t bytes = (size_t)std::max(n_local, 1) * variables[6]->ld * sizeof(float);
+        void *p;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, bytes));
+        GCNHIP_CHECK(gcnhip_memset_async(env.ctx, p, 0, bytes));
+        d_ml_logits = (float *)p;
+    }
+    return d_ml_logits;
+}
+
 void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
     const int C = params.output_dim;
     if (opt_.multilabel) throw GcnHipFailure(-1, "predict: this is a multi-label model: use predict_multilabel");
@@ -1433,23 +1469,10 @@ void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float 
         void *p;
         GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * C * sizeof(float))); d_logp = (float *)p;
     }
-    // an evaluation forward (eval_async's module list without the loss) on the main stream; the logit aggregation runs the
-    // prediction epilogue instead of its usual launch and stores no logits
-    if (flags & HIPGCN_MODULAR)
-        GCNHIP_CHECK(gcnhip_d2d_async(env.ctx, input->data, gcnhip_feat_values(feat), (size_t)gcnhip_feat_nnz(feat) * sizeof(float)));
+    // the logit aggregation runs the prediction epilogue instead of its usual launch and stores no logits
     HipGraphSum::Prediction req;
     req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = logp ? d_logp : nullptr; req.ld_logp = C;
-    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
-    logits_gs->predict = &req;
-    try {
-        for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);       // the last module is the loss
-    } catch (...) {
-        logits_gs->predict = nullptr;
-        throw;
-    }
-    logits_gs->predict = nullptr;
-    // variable 3: a fused evaluation keeps H1 in registers (what it held stays); otherwise the forward stored it
-    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+    forward_hooked(&req, nullptr);
     if (n == 0) { sync(); return; }
     std::vector<int32_t> hp(nl);
     std::vector<float> hq(nl), hl;
@@ -1477,13 +1500,8 @@ void HipGCN::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *
     sync();
     const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
     HipVariable *Z = variables[6].get();
-    const size_t nl = (size_t)std::max(n_local, 1), nq = (size_t)std::max(n, 1);
-    if (!d_ml_logits) {
-        void *p;
-        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * Z->ld * sizeof(float)));
-        GCNHIP_CHECK(gcnhip_memset_async(env.ctx, p, 0, nl * Z->ld * sizeof(float)));
-        d_ml_logits = (float *)p;
-    }
+    const size_t nq = (size_t)std::max(n, 1);
+    ml_logits_scratch();
     if (nq > ml_query_cap) {
         gcnhip_free(env.ctx, d_ml_bits); gcnhip_free(env.ctx, d_ml_prob); gcnhip_free(env.ctx, d_ml_rows);
         d_ml_bits = nullptr; d_ml_prob = nullptr; d_ml_rows = nullptr;
@@ -1493,27 +1511,119 @@ void HipGCN::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *
         GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nq * sizeof(int32_t))); d_ml_rows = (int32_t *)p;
         ml_query_cap = nq;
     }
-    // an evaluation forward (eval_async's module list without the loss) on the main stream; the logit aggregation stores the
-    // requested rows into the scratch table instead of variable 6
-    if (flags & HIPGCN_MODULAR)
-        GCNHIP_CHECK(gcnhip_d2d_async(env.ctx, input->data, gcnhip_feat_values(feat), (size_t)gcnhip_feat_nnz(feat) * sizeof(float)));
+    // the logit aggregation stores the requested rows into the scratch table instead of variable 6
     HipGraphSum::Redirect req;
     req.data = d_ml_logits; req.ld = Z->ld; req.rows = subset;
-    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
-    logits_gs->redirect = &req;
-    try {
-        for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);       // the last module is the loss
-    } catch (...) {
-        logits_gs->redirect = nullptr;
-        throw;
-    }
-    logits_gs->redirect = nullptr;
-    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+    forward_hooked(nullptr, &req);
     if (n == 0) { sync(); return; }
     GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_ml_rows, rows.data(), (size_t)n * sizeof(int32_t)));
     GCNHIP_CHECK(gcnhip_bce_predict_rows(env.ctx, d_ml_logits, Z->ld, d_ml_rows, n, C, d_ml_bits, ml_wpr, prob ? d_ml_prob : nullptr, C));
     GCNHIP_CHECK(gcnhip_d2h(env.ctx, bits, d_ml_bits, (size_t)n * ml_wpr * sizeof(uint32_t)));
     if (prob) GCNHIP_CHECK(gcnhip_d2h(env.ctx, prob, d_ml_prob, (size_t)n * C * sizeof(float)));
+}
+
+void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
+    const int C = params.output_dim;
+    const bool ml = opt_.multilabel;
+    if (!logits_gs) throw GcnHipFailure(-1, "evaluate: this model has no class-width aggregation");
+    if (!ml && C > 64) throw GcnHipFailure(-1, "evaluate: at most 64 classes on a single-label model (the logit row of a node sits in one wave)");
+    if (ml && C > 256) throw GcnHipFailure(-1, "evaluate: at most 256 classes on a multi-label model");
+    if (split < 0 || split > 3 || !counts || n < 0) throw GcnHipFailure(-1, "evaluate: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
+    // the rows to score: the split's list (already on the device on the fused path), or the query
+    std::vector<int> rows;
+    const int32_t *d_list = nullptr;
+    bool upload = false;
+    if (split) {
+        if (d_split_list[split]) {
+            d_list = d_split_list[split];
+            n = split_local_n[split];
+        } else {
+            const int r0 = row_start();
+            for (int r = 0; r < n_local; r++)
+                if (data->split[r0 + r] == split) rows.push_back(r);
+            n = (int)rows.size();
+            upload = true;
+        }
+    } else {
+        if (!nodes) n = n_local;
+        query_rows("evaluate", nodes, n, rows);
+        upload = nodes != nullptr;                             // NULL: rows 0 .. n_local - 1, no list
+    }
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    const gcnhip_rowset *subset = split ? split_rows[split] : (nodes ? query_subset(rows) : nullptr);
+    const size_t nl = (size_t)std::max(n_local, 1);
+    const int m = ml ? 3 * C : C * C + 1;                      // all that crosses to the host
+    void *p;
+    if (!d_eval_counts) {
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, ((size_t)std::max(3 * C, C * C + 1) + 1) * 2 * sizeof(float)));
+        d_eval_counts = (int32_t *)p;
+    }
+    if (upload && (size_t)std::max(n, 1) > eval_rows_cap) {
+        gcnhip_free(env.ctx, d_eval_rows); d_eval_rows = nullptr;
+        GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, (size_t)std::max(n, 1) * sizeof(int32_t))); d_eval_rows = (int32_t *)p;
+        eval_rows_cap = (size_t)std::max(n, 1);
+    }
+    if (upload) {
+        if (n) GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_eval_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+        d_list = d_eval_rows;
+    }
+    if (ml) {
+        HipVariable *Z = variables[6].get();
+        HipGraphSum::Redirect req;
+        req.data = ml_logits_scratch(); req.ld = Z->ld; req.rows = subset;
+        forward_hooked(nullptr, &req);
+        GCNHIP_CHECK(gcnhip_bce_class_counts_rows(env.ctx, d_ml_logits, Z->ld, d_ml_truth, ml_wpr, d_list, n, C, d_eval_counts));
+    } else {
+        if (!d_pred) {
+            GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * sizeof(int32_t))); d_pred = (int32_t *)p;
+            GCNHIP_CHECK(gcnhip_malloc(env.ctx, &p, nl * sizeof(float))); d_prob = (float *)p;
+        }
+        const int32_t *truth = d_truth[split];
+        if (!split) {                                          // a query is scored against the labels themselves
+            if (!d_label_all) {
+                std::vector<int32_t> lab(data->label.begin() + row_start(), data->label.begin() + row_start() + n_local);
+                if (lab.empty()) lab.assign(1, -1);
+                d_label_all = dev_upload(env.ctx, lab.data(), lab.size());
+            }
+            truth = d_label_all;
+        }
+        HipGraphSum::Prediction req;
+        req.rows = subset; req.pred = d_pred; req.prob = d_prob;
+        forward_hooked(&req, nullptr);
+        GCNHIP_CHECK(gcnhip_confusion_rows(env.ctx, d_pred, truth, n_local, d_list, n, C, d_eval_counts, d_eval_counts + C * C));
+    }
+    std::vector<int32_t> h(m);
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, h.data(), d_eval_counts, (size_t)m * sizeof(int32_t)));
+    std::vector<int64_t> total(h.begin(), h.end());
+    int64_t listed = n;
+    if (world() > 1) {
+        // The counts are additive across ranks, like the four metric floats of an epoch, and go through the same float
+        // all-reduce — as two limbs each, so that the sum is exact: a rank's count is below 2^31, so its high limb (count >> 12)
+        // is below 2^19 and its low limb below 2^12; up to 32 ranks every partial sum of either stays below 2^24, where f32
+        // holds every integer.  (One float per count would round silently from 2^24 rows in a cell.)
+        if (world() > 32) throw GcnHipFailure(-1, "evaluate: the exact sum of the counts is laid out for at most 32 ranks");
+        std::vector<float> limbs(2 * (size_t)(m + 1));
+        for (int i = 0; i <= m; i++) {
+            const int64_t v = i < m ? (int64_t)h[i] : listed;
+            limbs[2 * i] = (float)(v & 4095);
+            limbs[2 * i + 1] = (float)(v >> 12);
+        }
+        float *d_limbs = (float *)d_eval_counts;               // sized for it above; the counts are on the host already
+        GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_limbs, limbs.data(), limbs.size() * sizeof(float)));
+        env.comm->allreduce_sum(d_limbs, limbs.size());
+        GCNHIP_CHECK(gcnhip_d2h(env.ctx, limbs.data(), d_limbs, limbs.size() * sizeof(float)));
+        for (int i = 0; i < m; i++) total[i] = (int64_t)limbs[2 * i + 1] * 4096 + (int64_t)limbs[2 * i];
+        listed = (int64_t)limbs[2 * m + 1] * 4096 + (int64_t)limbs[2 * m];
+    }
+    sync();
+    std::copy(total.begin(), total.begin() + (ml ? 3 * C : C * C), counts);
+    if (ml) {
+        if (rows_counted) *rows_counted = listed;
+        if (unlabelled) *unlabelled = 0;
+    } else {
+        if (rows_counted) *rows_counted = listed - total[C * C];
+        if (unlabelled) *unlabelled = total[C * C];
+    }
 }
 
 void HipGCN::save_weights(const char *path) {

@@ -180,6 +180,20 @@ public:
     // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
     void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
     bool multilabel() const { return opt_.multilabel; }
+    // Per-class evaluation (beyond the reference): one evaluation forward with the current weights (no dropout) over a set of
+    // rows, and integer counts per class formed on the GPU behind it.  Rows: the nodes of `split` (1 train, 2 validation,
+    // 3 test — eval's codes) on this rank, `nodes` then ignored; or, with split == 0, the `nodes` query with predict()'s
+    // conventions (n dataset ids, each a row of this rank, repeats counted as often as listed; NULL: every row of this rank).
+    // Single-label model: the logit aggregation runs gcnhip_graphsum_predict on those rows only, then gcnhip_confusion_rows;
+    // counts [C x C], counts[t * C + p] = rows with truth t predicted as p; *unlabelled = rows whose truth is outside [0, C)
+    // (not in the matrix), *rows_counted = rows in the matrix.  Multi-label model: predict_multilabel's forward (logits to
+    // scratch), then gcnhip_bce_class_counts_rows; counts [3 x C] = TP, FP, FN per class (z > 0 predicts the class),
+    // *rows_counted = the rows, *unlabelled = 0.  Several GPUs: a collective like predict(); each rank counts its own rows, the
+    // counts are summed exactly over the ranks and every rank returns the same totals.  Only the counts cross to the host.
+    // Training state is not touched: the metrics ring, the current split, the logits (variable 6) and the captured epoch
+    // graph are left as they were; a train_epoch() after it has the same bits as one without it.  Synchronises.  More than
+    // 64 (single-label) or 256 (multi-label) classes: an error.  host/report.h derives precision / recall / F1 from the counts.
+    void evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
     // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
     // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
     // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
@@ -261,6 +275,11 @@ private:
     std::pair<float, float> ring_metrics(const float *row) const;   // (loss + L2, accuracy or micro-F1) of a metrics-ring row
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows (predict*)
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
+    void forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect);
+    float *ml_logits_scratch();
+    // evaluate(): the counts on the device (also the float limbs of their all-reduce), an uploaded row list, every local label
+    int32_t *d_eval_counts = nullptr, *d_eval_rows = nullptr, *d_label_all = nullptr;
+    size_t eval_rows_cap = 0;
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

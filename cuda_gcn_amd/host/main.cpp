@@ -39,6 +39,11 @@
 //                            (class = argmax of the node's logits, lowest on a tie; its softmax probability).  With several
 //                            GPUs each worker predicts its own rows into an array indexed by node id; the file is written
 //                            after the join.
+//   GCN_REPORT=<file>        after the test line, the TEST split is evaluated per class (HipGCN::evaluate: counts formed on the GPU) and
+//                            a text report written: `class <c> support <n> precision <p> recall <r> f1 <f>` per class, a line
+//                            `macro_f1 <x> micro_f1 <y>`, and for a single-label model a line `confusion` followed by the matrix
+//                            (row = truth, column = prediction) as C lines of C integers.  With several GPUs every worker takes
+//                            part, all receive the same totals, and the file is written once after the join.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -59,6 +64,7 @@
 #include "hip_check.h"
 #include "labels.h"
 #include "parser.h"
+#include "report.h"
 
 static int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
@@ -145,6 +151,10 @@ int main(int argc, char **argv) {
     if (load_path && !*load_path) load_path = nullptr;
     if (save_path && !*save_path) save_path = nullptr;
     if (predict_path && !*predict_path) predict_path = nullptr;
+    const char *report_path = getenv("GCN_REPORT");
+    if (report_path && !*report_path) report_path = nullptr;
+    const int C_out = params.output_dim;
+    std::vector<int64_t> report_counts(report_path ? (size_t)(multilabel_path ? 3 * C_out : C_out * C_out) : 0, 0);   // rank 0's copy of the totals
     std::vector<int32_t> all_pred(predict_path ? params.num_nodes : 0, -1);   // by node id, filled by the workers
     std::vector<float> all_prob(predict_path ? params.num_nodes : 0, 0.f);
     const int ml_wpr = gcn_label_words(params.output_dim);
@@ -187,6 +197,11 @@ int main(int argc, char **argv) {
                     all_pred[id] = p[r];
                     all_prob[id] = q[r];
                 }
+            }
+            if (report_path) {                                 // every rank: a collective; the totals are the same everywhere
+                std::vector<int64_t> cnt(report_counts.size());
+                gcn.evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
+                if (rank == 0) report_counts = cnt;
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",
@@ -241,6 +256,19 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
         fprintf(stderr, "gcn-hip: predictions of %d nodes written to %s\n", params.num_nodes, predict_path);
+    }
+    if (report_path) {
+        ClassReport rep;
+        std::string err;
+        const int64_t *cm = multilabel_path ? nullptr : report_counts.data();
+        int bad = multilabel_path ? gcn_class_report(C_out, nullptr, report_counts.data(), report_counts.data() + C_out, report_counts.data() + 2 * C_out, &rep, &err)
+                                  : gcn_class_report(C_out, cm, nullptr, nullptr, nullptr, &rep, &err);
+        if (!bad) bad = gcn_class_report_write(report_path, C_out, rep, cm, &err);
+        if (bad) {
+            fprintf(stderr, "gcn-hip: GCN_REPORT: %s\n", err.c_str());
+            return EXIT_FAILURE;
+        }
+        fprintf(stderr, "gcn-hip: per-class report of the test split (macro-F1 %.5f, micro-F1 %.5f) written to %s\n", rep.macro_f1, rep.micro_f1, report_path);
     }
     return rc;
 }

@@ -204,6 +204,41 @@ class HipGCNModel:
         sets = unpack_multihot(words[:n], c)
         return (sets, pr[:n]) if prob else sets
 
+    def evaluate(self, split=None, nodes=None):
+        """Per-class evaluation: one evaluation forward with the current weights (no dropout) over a set of rows, integer counts
+        per class formed on the GPU behind it, and the metrics class_report() derives from them.  Rows: the nodes of `split`
+        (1 train, 2 validation, 3 test) on this rank; or, with split=None, the `nodes` query with predict()'s conventions
+        (repeats counted as often as listed; None: every row of this rank).  Returns a dict: rows, support, precision, recall, f1
+        (float64 [C]), macro_f1, micro_f1; a single-label model adds confusion (int64 [C, C], row = truth, column = prediction),
+        accuracy, unlabelled (rows whose label is outside [0, C): in no cell); a multi-label model adds tp, fp, fn (int64 [C]).
+        Several ranks: every rank calls it and every rank gets the totals over all ranks.  Training state is not touched."""
+        if split is not None and nodes is not None:
+            raise ValueError("evaluate: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise ValueError(f"evaluate: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if nodes is None:
+            n, qp = 0, None
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = q.size
+            q = q if n else np.zeros(1, np.int32)              # an empty query is still a query (not "every row")
+            qp = q.ctypes.data
+        c = self.params.output_dim
+        counts = np.zeros((3, c) if self.multilabel else (c, c), np.int64)
+        rows, unl = C.c_int64(), C.c_int64()
+        _ck(self.lib, self.lib.gcnhost_model_evaluate(self.h, int(split or 0), qp, n, counts.ctypes.data, C.byref(rows), C.byref(unl)), "evaluate")
+        if self.multilabel:
+            out = class_report(tp=counts[0], fp=counts[1], fn=counts[2])
+            out.pop("accuracy")
+        else:
+            out = class_report(confusion=counts)
+            out["confusion"] = counts
+            out["unlabelled"] = unl.value
+            for k in ("tp", "fp", "fn"):
+                out.pop(k)
+        out["rows"] = rows.value
+        return out
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")
@@ -253,6 +288,38 @@ class HipGCNModel:
             self.close()
         except Exception:
             pass
+
+
+def class_report(confusion=None, tp=None, fp=None, fn=None):
+    """Per-class metrics from integer counts — host only, no GPU; the one place they are derived (host/report.h).  Either a
+    confusion matrix [C, C] (row = truth, column = prediction) or the vectors tp, fp, fn [C].  Returns a dict: tp, fp, fn (int64
+    [C]), support (= tp + fn), precision = tp / (tp + fp), recall = tp / (tp + fn), f1 = 2 tp / (2 tp + fp + fn) (float64 [C], each
+    0 when its denominator is 0), macro_f1 (mean of f1 over all C classes, those without support included), micro_f1 =
+    2 sum(tp) / (2 sum(tp) + sum(fp) + sum(fn)), accuracy (trace / sum of the matrix; 0.0 from vectors) and rows (sum of the
+    matrix; 0 from vectors).  A non-square matrix or vectors of different lengths raise ValueError, a negative count GcnHostError."""
+    vectors = [v for v in (tp, fp, fn) if v is not None]
+    if (confusion is None) == (not vectors):
+        raise ValueError("class_report: give either a confusion matrix or tp, fp and fn")
+    if vectors and len(vectors) != 3:
+        raise ValueError("class_report: tp, fp and fn go together")
+    lib = _lib.gcnhost()
+    if confusion is not None:
+        m = np.ascontiguousarray(confusion, np.int64)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+            raise ValueError(f"class_report: expected a square matrix [C, C] with C >= 1, got {m.shape}")
+        c, args, rows = m.shape[0], (m.ctypes.data, None, None, None), int(m.sum()) if (m >= 0).all() else 0
+    else:
+        v = [np.ascontiguousarray(x, np.int64).ravel() for x in (tp, fp, fn)]
+        if not (v[0].size == v[1].size == v[2].size) or v[0].size < 1:
+            raise ValueError(f"class_report: tp, fp and fn must have one length C >= 1, got {[x.size for x in v]}")
+        c, args, rows = v[0].size, (None, v[0].ctypes.data, v[1].ctypes.data, v[2].ctypes.data), 0
+    cnt = np.zeros((3, c), np.int64)
+    sup, pre, rec, f1 = (np.zeros(c, np.float64) for _ in range(4))
+    summ = np.zeros(3, np.float64)
+    _ck(lib, lib.gcnhost_class_report(c, *args, cnt.ctypes.data, sup.ctypes.data, pre.ctypes.data, rec.ctypes.data, f1.ctypes.data,
+                                      summ.ctypes.data), "class_report")
+    return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
+                macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
 
 
 def read_weights(path):

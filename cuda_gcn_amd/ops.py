@@ -587,6 +587,38 @@ class Device:
             "gcnhip_bce_predict_rows")
         return unpack_multihot(bb.download()[:m], c), (qb.download()[:m] if qb else None)
 
+    def confusion_rows(self, pred, truth, c, rows=None):
+        """gcnhip_confusion_rows: (int32 [C, C] with [t, p] = listed rows of truth t predicted as p, listed rows in no cell).  pred,
+        truth: int32 [n_table]; rows: the listed rows (repeats allowed), None: every row.  The output buffers are uploaded as
+        garbage: the launch zeroes them."""
+        pred, truth = np.ascontiguousarray(pred, np.int32), np.ascontiguousarray(truth, np.int32)
+        assert pred.shape == truth.shape and pred.ndim == 1
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        n = pred.size if rows is None else rows.size
+        pb, tb = self.buf(pred if pred.size else np.zeros(1, np.int32)), self.buf(truth if truth.size else np.zeros(1, np.int32))
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        cb = self.buf(np.full(max(c * c, 1), 0x5A5A5A5A, np.int32))
+        ob = self.buf(np.full(1, 0x5A5A5A5A, np.int32))
+        _ck(self.lib, self.lib.gcnhip_confusion_rows(self.ctx, pb.ptr, tb.ptr, int(pred.size), rb.ptr if rb else None, int(n), int(c),
+                                                      cb.ptr, ob.ptr), "gcnhip_confusion_rows")
+        return cb.download()[:c * c].reshape(c, c), int(ob.download()[0])
+
+    def bce_class_counts_rows(self, logits, truth, rows=None, ld=None):
+        """gcnhip_bce_class_counts_rows: int32 [3, C] = TP, FP, FN per class over the listed rows (None: every row) of a logit
+        table; truth: bool [n, C] (packed here into multi-hot words); class c is predicted when its logit is above 0."""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        m = n if rows is None else rows.size
+        words = pack_multihot(truth)
+        lb, tb = self.padded(logits, ld), self.buf(words)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        cb = self.buf(np.full(3 * c, 0x5A5A5A5A, np.int32))
+        _ck(self.lib, self.lib.gcnhip_bce_class_counts_rows(self.ctx, lb.ptr, ld, tb.ptr, words.shape[1], rb.ptr if rb else None, int(m), c,
+                                                             cb.ptr), "gcnhip_bce_class_counts_rows")
+        return cb.download().reshape(3, c)
+
     def accuracy(self, logits, truth, ld=None):
         logits = np.asarray(logits, np.float32)
         n, c = logits.shape

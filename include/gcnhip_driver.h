@@ -318,6 +318,27 @@ int gcnhip_bce_fwd_rows(gcnhip_ctx *ctx, const float *logits, int ld, float *gra
  * [i * ld_prob + c] = sigmoid(z_c).  1 <= num_classes <= 256. */
 int gcnhip_bce_predict_rows(gcnhip_ctx *ctx, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes,
                             uint32_t *bits, int words_per_row, float *prob, int ld_prob);
+/* ---- per-class evaluation counts (report.hip; beyond the reference, which reports one accuracy per split) -----------
+ * Both entry points ZERO their outputs on ctx's stream and then count, so a call with n == 0 leaves zeros.  All counts are
+ * integers and integer addition commutes and associates: the result depends neither on the order of the blocks nor on the
+ * order in which their atomic adds arrive, and two launches on the same inputs give identical output.  Not part of any
+ * captured epoch.
+ *
+ * Confusion matrix of a single-label model: for each of the n listed rows r = d_rows[i] (repeats count as often as they are
+ * listed; d_rows == NULL: rows 0 .. n - 1), counts[t * C + p] += 1 with t = truth[r] (an array as gcnhip_set_truth makes) and
+ * p = pred[r] (the array gcnhip_graphsum_predict writes); pred and truth have n_table entries.  *out_of_range = listed rows
+ * that are NOT in the matrix: truth outside [0, C) (an unlabelled row, -1) — and, so that no input can index past the
+ * matrix, a row id outside [0, n_table) or a prediction outside [0, C), which the producers above never write.
+ * counts [C * C] and out_of_range [1] are int32 device arrays.  1 <= num_classes <= 64 (gcnhip_graphsum_predict's limit: the
+ * block's matrix is 16 KB of LDS at most); a larger C returns -1 with a message (gcnhip_last_error). */
+int gcnhip_confusion_rows(gcnhip_ctx *ctx, const int32_t *pred, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
+                          int num_classes, int32_t *counts, int32_t *out_of_range);
+/* TP / FP / FN of every class of a multi-label model over n listed rows of a logit table (layouts, row list and limits of
+ * gcnhip_bce_fwd_rows; d_rows == NULL: rows 0 .. n - 1): counts [3 * C] int32 = {TP[C], FP[C], FN[C]} with the rule the loss
+ * kernel counts by — class c is predicted for a row when z_c > 0.  Their sums over the classes are d_result_i[0..2] of
+ * gcnhip_bce_fwd_rows on the same inputs.  1 <= num_classes <= 256, else -1 with a message. */
+int gcnhip_bce_class_counts_rows(gcnhip_ctx *ctx, const float *logits, int ld, const uint32_t *truth_bits, int words_per_row,
+                                 const int32_t *d_rows, int n, int num_classes, int32_t *counts);
 /* The same update, and the epoch word advanced behind it in the same launch (the block that finishes last, after every
  * block has read the word): *d_epoch_done = e, *d_epoch_counter = e + 1 with e the counter's value during the launch.
  * The training pass of epoch e + 1 then reads its epoch from d_epoch_counter without a launch of its own

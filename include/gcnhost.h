@@ -139,6 +139,24 @@ int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pr
  * sets (bit c = logit c > 0), prob (may be NULL) [n x output_dim] the sigmoid of every logit.  Only on a model made by
  * gcnhost_model_create_multilabel (and gcnhost_model_predict only on one that was not). */
 int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob);
+/* Per-class evaluation (beyond the reference): one evaluation forward with the current weights over a set of rows, and integer
+ * counts per class formed on the GPU behind it (gcnhip_confusion_rows / gcnhip_bce_class_counts_rows).  Rows: the nodes of
+ * split 1 (train), 2 (validation) or 3 (test) on this rank; or, with split == 0, the `nodes` query with
+ * gcnhost_model_predict's conventions (repeats are counted as often as listed; NULL: every row of this rank).
+ * Single-label model: counts [output_dim x output_dim], counts[t * C + p] = rows with truth t predicted as p (the lowest class
+ * on a logit tie), *rows_counted = the rows in the matrix, *unlabelled = rows whose truth is outside [0, C) (in no cell).
+ * Multi-label model: counts [3 x output_dim] = TP, FP, FN per class (logit > 0 predicts the class), *rows_counted = the rows,
+ * *unlabelled = 0.  Several ranks: every rank calls it; the counts are summed exactly over the ranks and every rank receives
+ * the same totals.  Only the counts cross to the host.  Training state is not touched, as for gcnhost_model_predict.
+ * More than 64 (single-label) or 256 (multi-label) classes is an error.  Synchronises. */
+int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+/* Per-class metrics from integer counts, host only (host/report.h): either confusion [C x C] (row = truth, column =
+ * prediction) or tp / fp / fn [C] (the other form NULL).  Every output may be NULL: tp_fp_fn [3 x C] the counts used; support
+ * (TP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), f1 = 2 TP / (2 TP + FP + FN) [C], float64, each 0 when
+ * its denominator is 0; summary [3] = {macro_f1 (mean of f1 over all C classes), micro_f1 = 2 sum TP / (2 sum TP + sum FP +
+ * sum FN), accuracy = trace / sum of the matrix (0 from vectors)}.  A negative count or C < 1 is an error. */
+int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
+                         int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary);
 /* The multi-label truth file (host/labels.h), host only: one line per node, comma-separated class ids, empty for none.
  * *num_nodes > 0: the file must have that many lines; *num_classes > 0: every id must be below it (else C = largest id + 1).
  * Both receive the values used.  bits (may be NULL: check and report the sizes only) [num_nodes x ceil(C / 32)].  A wrong
