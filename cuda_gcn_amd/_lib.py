@@ -167,6 +167,8 @@ GCNHIP_SYMBOLS = {
     "gcnhip_bce_predict_rows": (I, [P, P, I, P, I, I, P, I, P, I]),
     "gcnhip_confusion_rows": (I, [P, P, P, I, P, I, I, P, P]),
     "gcnhip_bce_class_counts_rows": (I, [P, P, I, P, I, P, I, I, P]),
+    "gcnhip_wxent_fwd_rows": (I, [P, P, I, P, I, P, P, I, I, I, I, I, P, P, P, P, F]),
+    "gcnhip_wbce_fwd_rows": (I, [P, P, I, P, I, P, I, P, I, I, I, I, P, P, P, P]),
 }
 
 
@@ -194,6 +196,10 @@ GCNHOST_SYMBOLS = {
                                  ALLGATHER_FN, ALLREDUCE_FN, P]),
     "gcnhost_model_create_multilabel": (I, [PP, C.POINTER(HostParams), P, P, P, P, P, P, P, P, C.c_long, I, I, I, I, C.c_char_p,
                                             ALLGATHER_FN, ALLREDUCE_FN, P]),
+    "gcnhost_model_create_weighted": (I, [PP, C.POINTER(HostParams), P, P, P, P, P, P, P, P, P, C.c_long, I, I, I, I, C.c_char_p,
+                                          ALLGATHER_FN, ALLREDUCE_FN, P]),
+    "gcnhost_balanced_class_weights": (I, [I, I, P, P, P, I, P]),
+    "gcnhost_class_weights_read": (I, [C.c_char_p, C.POINTER(I), P]),
     "gcnhost_model_destroy": (I, [P]),
     "gcnhost_model_train_epoch": (I, [P, C.POINTER(F), C.POINTER(F)]),
     "gcnhost_model_eval": (I, [P, I, C.POINTER(F), C.POINTER(F)]),

@@ -9,6 +9,7 @@
 #include "cluster.h"
 #include "hip_check.h"
 #include "parser.h"
+#include "class_weights.h"
 #include "labels.h"
 #include "report.h"
 #include "weights.h"
@@ -53,7 +54,8 @@ static int model_create(gcnhost_model **out, const gcnhost_params *p,
                         const int *f_indptr, const int *f_indices, const float *f_val,
                         const int *split, const int *label, const uint32_t *multihot,
                         long seed, int device, int flags, int rank, int world, const char *nccl_id,
-                        gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
+                        gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user,
+                        const float *class_weights = nullptr) {
     API_TRY({
         gcnhost_model *m = new gcnhost_model();
         const int N = p->num_nodes;
@@ -74,6 +76,7 @@ static int model_create(gcnhost_model **out, const gcnhost_params *p,
         o.host_allgather = host_ag; o.host_allreduce = host_ar; o.host_user = host_user;
         o = HipGCNOptions::from_environment(o);                 // every HIPGCN_* variable, read once (host/options.cpp)
         o.multilabel = multihot != nullptr;
+        if (class_weights) o.class_weights.assign(class_weights, class_weights + std::max(p->output_dim, 0));
         try {
             m->gcn = new HipGCN(gp, &m->data, o);
         } catch (...) {
@@ -105,6 +108,32 @@ int gcnhost_model_create_multilabel(gcnhost_model **out, const gcnhost_params *p
     if (p->output_dim < 1 || p->output_dim > 256) { g_err = "multi-label mode takes 1 to 256 classes"; return -1; }
     return model_create(out, p, g_indptr, g_indices, f_indptr, f_indices, f_val, split, label, multihot, seed, device, flags, rank, world,
                         nccl_id, host_ag, host_ar, host_user);
+}
+
+int gcnhost_model_create_weighted(gcnhost_model **out, const gcnhost_params *p,
+                                  const int *g_indptr, const int *g_indices,
+                                  const int *f_indptr, const int *f_indices, const float *f_val,
+                                  const int *split, const int *label, const uint32_t *multihot, const float *class_weights,
+                                  long seed, int device, int flags, int rank, int world, const char *nccl_id,
+                                  gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user) {
+    if (!out || !p || !g_indptr || !g_indices || !f_indptr || !f_val || !split || (!multihot && !label)) { g_err = "null argument"; return -1; }
+    if (multihot && (p->output_dim < 1 || p->output_dim > 256)) { g_err = "multi-label mode takes 1 to 256 classes"; return -1; }
+    if (class_weights && (p->output_dim < 1 || p->output_dim > 256)) { g_err = "class weights take 1 to 256 classes"; return -1; }
+    return model_create(out, p, g_indptr, g_indices, f_indptr, f_indices, f_val, split, label, multihot, seed, device, flags, rank, world,
+                        nccl_id, host_ag, host_ar, host_user, class_weights);
+}
+
+int gcnhost_balanced_class_weights(int num_nodes, int num_classes, const int *split, const int *label, const uint32_t *multihot,
+                                   int which_split, float *weights) {
+    return gcn_balanced_class_weights(num_nodes, num_classes, split, label, multihot, which_split, weights, &g_err);
+}
+int gcnhost_class_weights_read(const char *path, int *num_classes, float *weights) {
+    if (!path || !num_classes) { g_err = "gcnhost_class_weights_read: invalid argument"; return -1; }
+    std::vector<float> w;
+    if (gcn_class_weights_read(path, *num_classes, w, &g_err) != 0) return -1;
+    *num_classes = (int)w.size();
+    if (weights) memcpy(weights, w.data(), w.size() * sizeof(float));
+    return 0;
 }
 
 int gcnhost_model_destroy(gcnhost_model *m) {

@@ -1,5 +1,6 @@
 #include "gcn.h"
 #include "weights.h"
+#include "class_weights.h"
 #include "cluster.h"
 #include <chrono>
 #include <deque>
@@ -78,6 +79,22 @@ void HipGCN::init(const HipGCNOptions &opt) {
         if (params.output_dim > 256) throw GcnHipFailure(-1, "HipGCN: multi-label mode takes at most 256 classes");
         if (data->multihot.size() != (size_t)params.num_nodes * ((params.output_dim + 31) / 32))
             throw GcnHipFailure(-1, "HipGCN: the multi-hot label matrix does not hold num_nodes rows of ceil(output_dim / 32) words");
+    }
+    if (!opt.class_weights.empty()) {
+        std::string why;
+        if (params.output_dim > 256) throw GcnHipFailure(-1, "HipGCN: class weights take at most 256 classes");
+        if (gcn_class_weights_check(opt.class_weights.data(), opt.class_weights.size(), params.output_dim, &why) != 0)
+            throw GcnHipFailure(-1, "HipGCN: " + why);
+        if (!opt.multilabel)                           // every rank holds the whole dataset: the sums are global and the same everywhere
+            for (int s = 1; s <= 3; s++) {
+                bool any = false;
+                for (int i = 0; i < params.num_nodes && !any; i++) any = data->split[i] == s;
+                const double ws = gcn_class_weight_sum(params.num_nodes, params.output_dim, data->split.data(), data->label.data(), s,
+                                                       opt.class_weights.data());
+                if (any && !(ws > 0))
+                    throw GcnHipFailure(-1, "HipGCN: the class weights of split " + std::to_string(s) + "'s rows sum to 0 (its weighted mean is undefined)");
+                split_wsum[s] = (float)ws;
+            }
     }
     GCNHIP_CHECK(gcnhip_ctx_create(&env.ctx, opt.device, nullptr));
     if (opt.gemm >= 0) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gemm_bf16x3", opt.gemm ? 2 : 0));   // HIPGCN_GEMM; else the library's default
@@ -210,13 +227,14 @@ void HipGCN::init(const HipGCNOptions &opt) {
             if (mine.empty()) mine.assign(ml_wpr, 0u);
             d_ml_truth = dev_upload(env.ctx, mine.data(), mine.size());
         }
+        if (!opt.class_weights.empty()) d_class_w = dev_upload(env.ctx, opt.class_weights.data(), opt.class_weights.size());
     }
 
     // The last aggregation of a forward computes only the rows the loss and the accuracy read
     // (CrossEntropyLoss::forward skips truth < 0, module.cpp:131-133; get_accuracy, gcn.cpp:86-88):
     // one registered row subset per split.
     if (!(flags & HIPGCN_ALL_ROWS)) add_split_rowsets(env.ctx, graph, split_rows);
-    if (!(flags & HIPGCN_MODULAR) || opt.multilabel) {
+    if (!(flags & HIPGCN_MODULAR) || opt.multilabel || !opt.class_weights.empty()) {
         // the loss walks the rows of the scored split only (it skips the others anyway, module.cpp:131-133)
         for (int s = 1; s <= 3; s++) {
             std::vector<int32_t> rows;
@@ -609,10 +627,18 @@ void HipGCN::build_modules() {
         modules.push_back(new HipDropout(&env, H1, p, KEY_HIDDEN_DROPOUT, hid_off, (flags & HIPGCN_HOST_MASKS) ? &env.keep_hidden : &no_mask));
         modules.push_back(new HipMatmul(&env, H1, W2, Z0, N, H, C));
         { auto *gs = new HipGraphSum(&env, Z0, Z, graph, C); gs->bwd_row_bits = &bwd_bits; gs->bwd_graph = graph_bwd_out; gs->fwd_out_rows = &cur_out_rows; wire_overlap(gs, true); modules.push_back(gs); logits_gs = gs; }
-        if (opt_.multilabel) {
+        if (opt_.multilabel && d_class_w) {
+            auto *bce = new HipWeightedBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_class_w, d_result, d_result_i, C);
+            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
+            modules.push_back(bce);
+        } else if (opt_.multilabel) {
             auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
             bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
             modules.push_back(bce);
+        } else if (d_class_w) {
+            auto *wce = new HipWeightedCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, &cur_wsum, d_class_w, d_result, d_result_i, C, true);
+            wce->rows_list = &cur_rows; wce->rows_n = &cur_rows_n;
+            modules.push_back(wce);
         } else
         modules.push_back(new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, true));
     } else {
@@ -656,6 +682,20 @@ void HipGCN::build_modules() {
             modules.push_back(gs);
             gs_logits = gs;
             logits_gs = gs;
+        }
+        if (d_class_w) {                               // class-weighted: the loss kernels of wloss.hip on the stored logits (no loss epilogue)
+            const float *dinv = nullptr;
+            if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &dinv, nullptr, nullptr, nullptr));
+            if (opt_.multilabel) {
+                auto *bce = new HipWeightedBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_class_w, d_result, d_result_i, C);
+                bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n; bce->grad_row_scale = dinv;
+                modules.push_back(bce);
+            } else {
+                auto *wce = new HipWeightedCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, &cur_wsum, d_class_w, d_result, d_result_i, C, false);
+                wce->rows_list = &cur_rows; wce->rows_n = &cur_rows_n; wce->grad_row_scale = dinv;
+                modules.push_back(wce);
+            }
+            return;
         }
         if (opt_.multilabel) {                         // the loss kernel on the stored logits (no loss epilogue)
             auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
@@ -792,7 +832,15 @@ void HipGCN::build_eval_lane() {
     gs_logits->fwd_out_rows = &L.out_rows;
     if (factored_) gs_logits->fwd_scaling = 1;
     L.modules.push_back(gs_logits);
-    if (opt_.multilabel) {
+    if (d_class_w && opt_.multilabel) {
+        auto *bce = new HipWeightedBCELoss(&L.env, L.Z.get(), d_ml_truth, ml_wpr, &L.count, d_class_w, L.d_result, L.d_result_i, C);
+        bce->rows_list = &L.rows; bce->rows_n = &L.rows_n;
+        L.modules.push_back(bce);
+    } else if (d_class_w) {
+        auto *wce = new HipWeightedCrossEntropyLoss(&L.env, L.Z.get(), &L.truth, &L.count, &L.wsum, d_class_w, L.d_result, L.d_result_i, C, false);
+        wce->rows_list = &L.rows; wce->rows_n = &L.rows_n;
+        L.modules.push_back(wce);
+    } else if (opt_.multilabel) {
         auto *bce = new HipBCELoss(&L.env, L.Z.get(), d_ml_truth, ml_wpr, &L.count, L.d_result, L.d_result_i, C);
         bce->rows_list = &L.rows; bce->rows_n = &L.rows_n;
         L.modules.push_back(bce);
@@ -867,6 +915,7 @@ void HipGCN::release() {
     for (int s = 1; s <= 3; s++) gcnhip_free(env.ctx, d_truth[s]);
     gcnhip_free(env.ctx, d_ml_truth); gcnhip_free(env.ctx, d_ml_logits); gcnhip_free(env.ctx, d_ml_bits);
     gcnhip_free(env.ctx, d_ml_prob); gcnhip_free(env.ctx, d_ml_rows);
+    gcnhip_free(env.ctx, d_class_w);
     gcnhip_free(env.ctx, gradbuf);
     gcnhip_free(env.ctx, d_result_i);
     gcnhip_free(env.ctx, d_ring);
@@ -919,6 +968,7 @@ void HipGCN::set_timers(bool on) {
 void HipGCN::set_truth(int s) {                 // gcn.cpp:78-81: here a pointer switch
     cur_truth = d_truth[s];
     cur_count = split_count[s];
+    cur_wsum = split_wsum[s];
     cur_out_rows = split_rows[s];
     cur_out_rows_loc = split_rows_loc[s];
     cur_out_rows_rem = split_rows_rem[s];
@@ -998,6 +1048,7 @@ void HipGCN::lane_begin(int s) {
     L.epoch_word = want;
     L.truth = d_truth[s];
     L.count = split_count[s];
+    L.wsum = split_wsum[s];
     L.out_rows = L.split_rows[s];
     L.rows = d_split_list[s];
     L.rows_n = split_local_n[s];
@@ -1086,6 +1137,8 @@ std::pair<float, float> HipGCN::ring_metrics(const float *row) const {
     const float l2 = params.weight_decay * row[4] / 2;                          // gcn.cpp:104
     if (opt_.multilabel)                                                        // {loss_sum, rows * C, 2 TP, 2 TP + FP + FN}
         return {row[0] / row[1] + l2, row[3] > 0.f ? row[2] / row[3] : 0.f};
+    if (!opt_.class_weights.empty())                                            // {sum of w . term, sum of w, correct, total}: the weighted mean
+        return {row[0] / row[1] + l2, (float)row[2] / (int)row[3]};
     const float loss = row[0] / (int)row[1];                                    // module.cpp:154
     const float acc = (float)row[2] / (int)row[3];                              // gcn.cpp:95
     return {loss + l2, acc};

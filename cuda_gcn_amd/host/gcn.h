@@ -107,6 +107,12 @@ struct HipGCNOptions {
     // the per-class sigmoid cross-entropy on the stored logits (gcnhip_bce_fwd_rows), and the accuracy column of every metric
     // micro-F1.  1 <= output_dim <= 256.
     bool multilabel = false;
+    // Class weights of the loss (beyond the reference; chosen here, never from the environment; host/class_weights.h).  Empty: off,
+    // every path is the unweighted one.  Single-label: w[output_dim], the loss is the weighted mean sum(w . term) / sum(w) of
+    // gcnhip_wxent_fwd_rows (accuracy is not weighted).  Multi-label: pos_weight[output_dim] on the positive term
+    // (gcnhip_wbce_fwd_rows).  The loss then always runs on the stored logits (no loss epilogue).  Refused: a wrong length, a
+    // negative / NaN / infinite weight, more than 256 classes, a scored split whose weights sum to 0 (single-label).
+    std::vector<float> class_weights;
 
     // `base` with every HIPGCN_* variable of the process environment applied (flag variables OR their bit in)
     static HipGCNOptions from_environment(HipGCNOptions base);
@@ -180,6 +186,7 @@ public:
     // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
     void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
     bool multilabel() const { return opt_.multilabel; }
+    bool weighted() const { return !opt_.class_weights.empty(); }
     // Per-class evaluation (beyond the reference): one evaluation forward with the current weights (no dropout) over a set of
     // rows, and integer counts per class formed on the GPU behind it.  Rows: the nodes of `split` (1 train, 2 validation,
     // 3 test — eval's codes) on this rank, `nodes` then ignored; or, with split == 0, the `nodes` query with predict()'s
@@ -300,6 +307,9 @@ private:
     int cur_rows_n = 0;
     int split_count[4] = {};
     int cur_count = 0;
+    float *d_class_w = nullptr;                                // class weights [C] (HipGCNOptions::class_weights), else NULL
+    float split_wsum[4] = {};                                  // single-label: sum of w[label] over split s, all ranks (the weighted gradient's divisor)
+    float cur_wsum = 0.f;                                      // follows set_truth
     float *d_ring = nullptr;
     static constexpr int RING = 1024;
     uint8_t *d_keep0 = nullptr, *d_keep1 = nullptr;
@@ -347,6 +357,7 @@ private:
         int32_t *rows = nullptr;
         int rows_n = 0;
         int count = 0;
+        float wsum = 0.f;                                      // split_wsum of the lane's split
         void *ev_weights = nullptr, *ev_done = nullptr;        // Adam(e) -> eval(e);  eval(e) -> Adam(e+1)
         void *ev_fork = nullptr;                               // one GPU: training GEMM done -> the validation pass may start
         bool pending = false;

@@ -50,6 +50,11 @@
 //                            the per-class sigmoid cross-entropy; the lines carry train_f1= / val_f1= / test_f1= (micro-F1) in
 //                            place of the _acc fields.  GCN_PREDICT then writes `node c1,c2,...` per node (the classes whose
 //                            logit is above 0; the node alone for an empty set).
+// Class-weighted loss (beyond the reference; host/class_weights.h):
+//   GCN_CLASS_WEIGHTS=balanced|<file>  a weight per class in the loss, read and checked before the GPU is touched.  `balanced`:
+//                            from the training split (single-label n / (C n_c); with GCN_MULTILABEL the positive-term weight
+//                            (n - pos_c) / pos_c).  <file>: one float per line, one line per class.  The lines keep their
+//                            format; the loss columns are the weighted loss.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +65,7 @@
 #include <thread>
 #include <unistd.h>
 #include <vector>
+#include "class_weights.h"
 #include "gcn.h"
 #include "hip_check.h"
 #include "labels.h"
@@ -119,6 +125,28 @@ int main(int argc, char **argv) {
         params.output_dim = c;
     }
 
+    std::vector<float> class_weights;
+    const char *cw_spec = getenv("GCN_CLASS_WEIGHTS");
+    if (cw_spec && *cw_spec) {
+        std::string err;
+        int bad = 0;
+        if (strcmp(cw_spec, "balanced") == 0) {
+            class_weights.resize(params.output_dim);
+            bad = gcn_balanced_class_weights(params.num_nodes, params.output_dim, data.split.data(), data.label.data(),
+                                             multilabel_path ? data.multihot.data() : nullptr, 1, class_weights.data(), &err);
+        } else {
+            bad = gcn_class_weights_read(cw_spec, params.output_dim, class_weights, &err);
+        }
+        if (bad) {
+            std::cerr << "gcn-hip: GCN_CLASS_WEIGHTS: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (params.output_dim > 256) {
+            std::cerr << "gcn-hip: GCN_CLASS_WEIGHTS: " << params.output_dim << " classes; class weights take at most 256" << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     int n_dev = 0;
     if (gcnhip_device_count(&n_dev) != 0 || n_dev < 1) {
         std::cerr << "gcn-hip: no GPU available (this backend has no CPU path; use gcn-seq)" << std::endl;
@@ -144,6 +172,7 @@ int main(int argc, char **argv) {
     if (env_int("GCN_SYNC_EPOCHS", 0)) base.flags |= HIPGCN_SYNC_EPOCHS;
     base = HipGCNOptions::from_environment(base);             // every HIPGCN_* variable, read once (host/options.cpp)
     base.multilabel = multilabel_path != nullptr;
+    base.class_weights = class_weights;
     std::cout << "RUNNING ON GPU" << std::endl;
 
     int rc = EXIT_SUCCESS;

@@ -353,6 +353,35 @@ void HipBCELoss::forward(bool training) {
     env->timers->stop(TMR_LOSS_FW);
 }
 
+// ---------------------------------------------------------- class-weighted
+HipWeightedCrossEntropyLoss::HipWeightedCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count,
+                                                         const float *weight_sum, const float *d_weight, float *d_result,
+                                                         int32_t *d_result_i, int num_classes, bool shift)
+    : env(env), logits(logits), truth(truth), count(count), weight_sum(weight_sum), d_weight(d_weight), d_result(d_result),
+      d_result_i(d_result_i), num_classes(num_classes), shift_in_place(shift) {}
+
+void HipWeightedCrossEntropyLoss::forward(bool training) {
+    env->timers->start(TMR_LOSS_FW);
+    const int n = rows_n ? *rows_n : 0;
+    GCNHIP_CHECK(gcnhip_wxent_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, *truth, *rows_list, n, num_classes,
+                                       training && *count > 0 ? 1 : 0, *count > 0 ? *count : 1, shift_in_place ? 1 : 0, d_result, d_result_i,
+                                       grad_row_scale, d_weight, *weight_sum));
+    env->timers->stop(TMR_LOSS_FW);
+}
+
+HipWeightedBCELoss::HipWeightedBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count,
+                                       const float *d_pos_weight, float *d_result, int32_t *d_result_i, int num_classes)
+    : env(env), logits(logits), truth(truth), wpr(wpr), count(count), d_pos_weight(d_pos_weight), d_result(d_result),
+      d_result_i(d_result_i), num_classes(num_classes) {}
+
+void HipWeightedBCELoss::forward(bool training) {
+    env->timers->start(TMR_LOSS_FW);
+    const int n = rows_n ? *rows_n : 0;
+    GCNHIP_CHECK(gcnhip_wbce_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, truth, wpr, *rows_list, n, num_classes,
+                                      training && *count > 0 ? 1 : 0, *count, grad_row_scale, d_result, d_result_i, d_pos_weight));
+    env->timers->stop(TMR_LOSS_FW);
+}
+
 // --------------------------------------------------------------------- ReLU
 HipReLU::HipReLU(HipEnv *env, HipVariable *in) : env(env), in(in), mask(nullptr) {
     void *p;

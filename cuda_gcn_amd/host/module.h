@@ -219,6 +219,52 @@ public:
     void backward() override {}
 };
 
+// Class-weighted losses (beyond the reference; HipGCNOptions::class_weights): the loss kernels of wloss.hip on the stored logits
+// of the scored split's rows, wired as HipBCELoss is — row lists always, grad_row_scale in the factored form, no loss
+// epilogue.  Single-label: d_result = {sum of w . term, sum of w, correct, total}; weight_sum points at the current split's
+// sum of w[truth] over ALL ranks (the gradient's divisor).
+class HipWeightedCrossEntropyLoss : public Module {
+    HipEnv *env;
+    HipVariable *logits;
+    int32_t *const *truth;
+    const int *count;
+    const float *weight_sum;
+    const float *d_weight;          // [C]
+    float *d_result;
+    int32_t *d_result_i;
+    int num_classes;
+    bool shift_in_place;
+public:
+    int32_t *const *rows_list = nullptr;
+    const int *rows_n = nullptr;
+    const float *grad_row_scale = nullptr;
+    HipWeightedCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count, const float *weight_sum,
+                                const float *d_weight, float *d_result, int32_t *d_result_i, int num_classes, bool shift_in_place);
+    void forward(bool) override;
+    void backward() override {}
+};
+
+// multi-label: HipBCELoss with a weight per class on the positive term (gcnhip_wbce_fwd_rows)
+class HipWeightedBCELoss : public Module {
+    HipEnv *env;
+    HipVariable *logits;
+    const uint32_t *truth;
+    int wpr;
+    const int *count;
+    const float *d_pos_weight;      // [C]
+    float *d_result;
+    int32_t *d_result_i;
+    int num_classes;
+public:
+    int32_t *const *rows_list = nullptr;
+    const int *rows_n = nullptr;
+    const float *grad_row_scale = nullptr;
+    HipWeightedBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count, const float *d_pos_weight,
+                       float *d_result, int32_t *d_result_i, int num_classes);
+    void forward(bool) override;
+    void backward() override {}
+};
+
 class HipReLU : public Module {
     HipEnv *env;
     HipVariable *in;

@@ -54,10 +54,15 @@ class HipGCNModel:
 
     multilabel: a bool/uint8 [num_nodes, C] matrix (1 <= C <= 256) switches the model to multi-label mode: output_dim = C,
     the loss is the per-class sigmoid cross-entropy, and train_epoch / eval / run_epochs report micro-F1 where they report
-    accuracy otherwise.  ds["label"] may then be absent."""
+    accuracy otherwise.  ds["label"] may then be absent.
+
+    class_weights: a float [C] array, or "balanced" (balanced_class_weights of the training split).  Single-label: the weight of
+    every class in the loss, which becomes the weighted mean sum(w[t] . term) / sum(w[t]) (torch's cross_entropy(weight=));
+    accuracy stays unweighted.  With multilabel=Y: the weight of every class's positive term (BCEWithLogitsLoss(pos_weight=)).
+    None: the unweighted model, bit for bit."""
 
     def __init__(self, ds, seed=0, device=0, flags=0, rank=0, world=1, nccl_id: bytes | None = None,
-                 host_allgather=None, host_allreduce=None, multilabel=None, **hyper):
+                 host_allgather=None, host_allreduce=None, multilabel=None, class_weights=None, **hyper):
         self.lib = lib = _lib.gcnhost()
         out_dim = ds["output_dim"]
         words = None
@@ -69,6 +74,17 @@ class HipGCNModel:
             out_dim = y.shape[1]
             words = pack_multihot(y != 0)
         self.multilabel = words is not None
+        cw = None
+        if class_weights is not None:
+            if isinstance(class_weights, str):
+                if class_weights != "balanced":
+                    raise ValueError(f"class_weights: an array of {out_dim} floats or 'balanced', got {class_weights!r}")
+                cw = balanced_class_weights(np.asarray(multilabel) != 0 if words is not None else ds["label"], ds["split"], out_dim)
+            else:
+                cw = np.ascontiguousarray(class_weights, np.float32).ravel()
+                if cw.size != out_dim:
+                    raise ValueError(f"class_weights: {cw.size} weights for {out_dim} classes")
+        self.class_weights = cw
         p = default_params(num_nodes=ds["num_nodes"], input_dim=ds["input_dim"], output_dim=out_dim, **hyper)
         self.params = p
         self._keep = [_i32(ds["g_indptr"]), _i32(ds["g_indices"]), _i32(ds["f_indptr"]),
@@ -79,7 +95,15 @@ class HipGCNModel:
         self._ag = _lib.ALLGATHER_FN(host_allgather) if host_allgather else C.cast(None, _lib.ALLGATHER_FN)
         self._ar = _lib.ALLREDUCE_FN(host_allreduce) if host_allreduce else C.cast(None, _lib.ALLREDUCE_FN)
         h = C.c_void_p()
-        if words is None:
+        if cw is not None:
+            rc = lib.gcnhost_model_create_weighted(C.byref(h), C.byref(p), k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data,
+                                                   k[3].ctypes.data if k[3] is not None else None, k[4].ctypes.data,
+                                                   k[5].ctypes.data, k[6].ctypes.data if k[6] is not None else None,
+                                                   k[7].ctypes.data if k[7] is not None else None, cw.ctypes.data,
+                                                   int(seed), int(device), int(flags),
+                                                   int(rank), int(world), nccl_id, self._ag, self._ar, None)
+            _ck(lib, rc, "gcnhost_model_create_weighted")
+        elif words is None:
             rc = lib.gcnhost_model_create(C.byref(h), C.byref(p), k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data,
                                           k[3].ctypes.data if k[3] is not None else None, k[4].ctypes.data,
                                           k[5].ctypes.data, k[6].ctypes.data, int(seed), int(device), int(flags),
@@ -320,6 +344,42 @@ def class_report(confusion=None, tp=None, fp=None, fn=None):
                                       summ.ctypes.data), "class_report")
     return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
                 macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
+
+
+def balanced_class_weights(labels_or_y, split, num_classes, which_split=1):
+    """f32 [C] "balanced" class weights from the rows of one split (1 = train) — host only, no GPU (host/class_weights.h).
+    labels_or_y 1-D int labels: w_c = n / (C n_c) over the split's rows whose label is in [0, C) (0 for a class without rows;
+    scikit-learn's class_weight="balanced").  2-D bool [N, C]: pw_c = (n - pos_c) / pos_c over the split's rows (1 for a class
+    without positives; PyTorch's pos_weight rule)."""
+    lib = _lib.gcnhost()
+    y = np.asarray(labels_or_y)
+    sp = _i32(split)
+    w = np.zeros(int(num_classes), np.float32)
+    if y.ndim == 2:
+        from .ops import pack_multihot
+        if y.shape != (sp.size, int(num_classes)):
+            raise ValueError(f"balanced_class_weights: expected a [{sp.size}, {num_classes}] matrix, got {y.shape}")
+        words = pack_multihot(y != 0)
+        rc = lib.gcnhost_balanced_class_weights(sp.size, int(num_classes), sp.ctypes.data, None, words.ctypes.data, int(which_split), w.ctypes.data)
+    else:
+        lab = _i32(y)
+        if lab.shape != sp.shape:
+            raise ValueError(f"balanced_class_weights: {lab.size} labels for {sp.size} nodes")
+        rc = lib.gcnhost_balanced_class_weights(sp.size, int(num_classes), sp.ctypes.data, lab.ctypes.data, None, int(which_split), w.ctypes.data)
+    _ck(lib, rc, "balanced_class_weights")
+    return w
+
+
+def read_class_weights(path, num_classes=None):
+    """f32 [C] from a class weights text file (one float per line, one line per class; gcn-hip's GCN_CLASS_WEIGHTS=<file>) — host
+    only.  num_classes: the line count the file must have.  A wrong count, a bad token, a negative, nan or inf raises
+    GcnHostError naming the line."""
+    lib = _lib.gcnhost()
+    c = C.c_int(int(num_classes or 0))
+    _ck(lib, lib.gcnhost_class_weights_read(os.fsencode(path), C.byref(c), None), "class_weights_read")
+    w = np.zeros(c.value, np.float32)
+    _ck(lib, lib.gcnhost_class_weights_read(os.fsencode(path), C.byref(c), w.ctypes.data), "class_weights_read")
+    return w
 
 
 def read_weights(path):

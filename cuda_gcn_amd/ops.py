@@ -572,6 +572,58 @@ class Device:
                     loss=float(r[0]) / float(r[1]) if r[1] else 0.0, f1=float(r[2]) / float(r[3]) if r[3] else 0.0,
                     grad=gb.download()[:, :c] if training else None)
 
+    def wxent_fwd_rows(self, logits, truth, weight, rows=None, weight_sum=None, training=True, count=None, grad_row_scale=None,
+                       shift_in_place=False, ld=None, grad_fill=np.nan):
+        """gcnhip_wxent_fwd_rows: class-weighted softmax cross-entropy over the listed rows (None: the rows with truth >= 0).
+        weight: f32 [C]; weight_sum: the gradient's divisor (None: sum of weight[truth] over the listed rows, in float64).
+        Returns dict(loss_sum, weight_sum (of this call's rows), correct, total, loss, result (f32 [4]), result_i (int32 [2]),
+        logits, grad [n, C] or None); grad rows outside the list keep grad_fill."""
+        logits = np.asarray(logits, np.float32)
+        truth = np.ascontiguousarray(truth, np.int32)
+        weight = np.ascontiguousarray(weight, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = np.flatnonzero(truth >= 0).astype(np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
+        if weight_sum is None:
+            t = truth[rows]
+            weight_sum = float(weight.astype(np.float64)[t[(t >= 0) & (t < c)]].sum())
+        lb = self.padded(logits, ld)
+        gb = self.buf(np.full((n, ld), grad_fill, np.float32))
+        tb, rb, wb = self.buf(truth), self.buf(rows if rows.size else np.zeros(1, np.int32)), self.buf(weight)
+        sb = self.buf(np.ascontiguousarray(grad_row_scale, np.float32)) if grad_row_scale is not None else None
+        res, resi = self.buf(np.zeros(4, np.float32)), self.buf(np.zeros(2, np.int32))
+        _ck(self.lib, self.lib.gcnhip_wxent_fwd_rows(self.ctx, lb.ptr, ld, gb.ptr, ld, tb.ptr, rb.ptr, int(rows.size), c, int(training),
+                                                      int(count if count is not None else max(rows.size, 1)), int(shift_in_place),
+                                                      res.ptr, resi.ptr, sb.ptr if sb else None, wb.ptr, float(weight_sum)),
+            "gcnhip_wxent_fwd_rows")
+        r, ri = res.download(), resi.download()
+        return dict(loss_sum=float(r[0]), weight_sum=float(r[1]), correct=int(ri[0]), total=int(ri[1]),
+                    loss=float(r[0]) / float(r[1]) if r[1] else 0.0, result=r, result_i=ri,
+                    logits=lb.download()[:, :c], grad=gb.download()[:, :c] if training else None)
+
+    def wbce_fwd_rows(self, logits, truth, pos_weight, rows=None, training=True, count=None, grad_row_scale=None, ld=None,
+                      grad_fill=np.nan):
+        """gcnhip_wbce_fwd_rows: bce_fwd_rows with a weight per class on the positive term (pos_weight: f32 [C]); the same dict"""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
+        words = pack_multihot(truth)
+        lb = self.padded(logits, ld)
+        gb = self.buf(np.full((n, ld), grad_fill, np.float32))
+        tb, rb = self.buf(words), self.buf(rows if rows.size else np.zeros(1, np.int32))
+        wb = self.buf(np.ascontiguousarray(pos_weight, np.float32))
+        sb = self.buf(np.ascontiguousarray(grad_row_scale, np.float32)) if grad_row_scale is not None else None
+        res, resi = self.buf(np.zeros(4, np.float32)), self.buf(np.zeros(4, np.int32))
+        _ck(self.lib, self.lib.gcnhip_wbce_fwd_rows(self.ctx, lb.ptr, ld, gb.ptr, ld, tb.ptr, words.shape[1], rb.ptr, int(rows.size), c,
+                                                     int(training), int(count if count is not None else max(rows.size, 1)),
+                                                     sb.ptr if sb else None, res.ptr, resi.ptr, wb.ptr), "gcnhip_wbce_fwd_rows")
+        r, ri = res.download(), resi.download()
+        return dict(loss_sum=float(r[0]), denom=float(r[1]), f1_num=float(r[2]), f1_den=float(r[3]),
+                    tp=int(ri[0]), fp=int(ri[1]), fn=int(ri[2]), rows=int(ri[3]),
+                    loss=float(r[0]) / float(r[1]) if r[1] else 0.0, f1=float(r[2]) / float(r[3]) if r[3] else 0.0,
+                    grad=gb.download()[:, :c] if training else None)
+
     def bce_predict_rows(self, logits, rows=None, prob=True, ld=None):
         """gcnhip_bce_predict_rows: (bool [len(rows), C] = logit > 0, sigmoid [len(rows), C] or None)"""
         logits = np.asarray(logits, np.float32)

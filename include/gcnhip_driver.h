@@ -318,6 +318,31 @@ int gcnhip_bce_fwd_rows(gcnhip_ctx *ctx, const float *logits, int ld, float *gra
  * [i * ld_prob + c] = sigmoid(z_c).  1 <= num_classes <= 256. */
 int gcnhip_bce_predict_rows(gcnhip_ctx *ctx, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes,
                             uint32_t *bits, int words_per_row, float *prob, int ld_prob);
+/* ---- class-weighted losses (wloss.hip; beyond the reference, whose loss weighs every row equally) -------------------
+ * Weighted softmax cross-entropy over a row list: the arguments of gcnhip_xent_fwd_rows_scaled plus d_class_weight [C]
+ * (finite, >= 0) and weight_sum.  For each listed row r with truth t in [0, C) and w = d_class_weight[t]: the term
+ * w * (log sum exp(z - max) - (z_t - max)); when training, grad[r, j] = w * (p_j - [j == t]) / weight_sum, times
+ * d_grad_row_scale[r] when given, where weight_sum = sum of w[truth] over the scored split's rows of ALL ranks (the caller
+ * knows it: labels and splits never change) and must be > 0.  Accuracy is not weighted.  d_result[4] = {sum of w * term,
+ * sum of w over this call's rows, correct, total} — every entry additive across ranks; loss = [0] / [1], the weighted mean of
+ * torch's cross_entropy(weight=, reduction="mean").  d_result_i (may be NULL) [2] = {correct, total}.  A listed row whose
+ * truth is outside [0, C) has no weight: zero gradient row, in no count.  Same grids, lane -> row assignment and order of
+ * additions as gcnhip_xent_fwd_rows_scaled: with every weight 1.0f the gradient and all of d_result / d_result_i have that
+ * entry point's bits.  Deterministic (block partials added in block order by a finalize launch, which also writes an armed
+ * gcnhip_metrics_record_with_next_loss row).  1 <= num_classes <= 256, else -1 with a message.  Graph-capturable. */
+int gcnhip_wxent_fwd_rows(gcnhip_ctx *ctx, float *logits, int ld, float *grad, int ld_grad,
+                          const int32_t *truth, const int32_t *d_rows, int n_listed, int num_classes, int training,
+                          int count, int shift_in_place, float *d_result, int32_t *d_result_i, const float *d_grad_row_scale,
+                          const float *d_class_weight, float weight_sum);
+/* gcnhip_bce_fwd_rows with a weight on the positive term of every class, d_pos_weight [C] (finite, >= 0): the term
+ * pw_c * y * softplus(-z) + (1 - y) * softplus(z), softplus(x) = max(x, 0) + log1p(exp(-|x|)); when training, grad[r, c] =
+ * (y ? -pw_c * sigmoid(-z) : sigmoid(z)) / (count * C) [* d_grad_row_scale[r]].  Normaliser, TP / FP / FN, d_result,
+ * d_result_i, limits, determinism and the armed metrics row exactly as gcnhip_bce_fwd_rows: torch's
+ * binary_cross_entropy_with_logits(pos_weight=, reduction="mean"). */
+int gcnhip_wbce_fwd_rows(gcnhip_ctx *ctx, const float *logits, int ld, float *grad, int ld_grad,
+                         const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
+                         int num_classes, int training, int count, const float *d_grad_row_scale,
+                         float *d_result, int32_t *d_result_i, const float *d_pos_weight);
 /* ---- per-class evaluation counts (report.hip; beyond the reference, which reports one accuracy per split) -----------
  * Both entry points ZERO their outputs on ctx's stream and then count, so a call with n == 0 leaves zeros.  All counts are
  * integers and integer addition commutes and associates: the result depends neither on the order of the blocks nor on the

@@ -89,6 +89,30 @@ int gcnhost_model_create_multilabel(gcnhost_model **m, const gcnhost_params *p,
                                     long seed, int device, int flags,
                                     int rank, int world, const char *nccl_id,
                                     gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user);
+/* Either of the two with per-class loss weights (beyond the reference; host/class_weights.h): class_weights [output_dim], finite
+ * and not negative, at most 256 classes.  multihot == NULL: a single-label model whose loss is the weighted mean
+ * sum(w[t] . term) / sum(w[t]) over the scored split (gcnhip_wxent_fwd_rows; torch's cross_entropy(weight=)); accuracy is not
+ * weighted.  multihot != NULL: class_weights is the weight of every class's positive term (gcnhip_wbce_fwd_rows; torch's
+ * BCEWithLogitsLoss(pos_weight=)).  class_weights == NULL: exactly gcnhost_model_create / gcnhost_model_create_multilabel.
+ * Refused with a message: a negative / NaN / infinite weight, a non-empty split whose weights sum to 0 (single-label).
+ * predict, evaluate, save / load of weights work on such a model as on any other. */
+int gcnhost_model_create_weighted(gcnhost_model **m, const gcnhost_params *p,
+                                  const int *g_indptr, const int *g_indices,
+                                  const int *f_indptr, const int *f_indices, const float *f_val,
+                                  const int *split, const int *label, const uint32_t *multihot, const float *class_weights,
+                                  long seed, int device, int flags,
+                                  int rank, int world, const char *nccl_id,
+                                  gcnhost_allgather_fn host_ag, gcnhost_allreduce_fn host_ar, void *host_user);
+/* "Balanced" class weights from the rows of split which_split (1 = train), host only.  multihot == NULL: w_c = n / (C . n_c)
+ * over the rows whose label is in [0, C) (n their number, n_c those of class c; 0 when n_c = 0) — scikit-learn's rule.
+ * multihot != NULL (label may be NULL): pw_c = (n - pos_c) / pos_c over the split's rows (1 when pos_c = 0) — the rule PyTorch
+ * documents for pos_weight.  weights [num_classes]. */
+int gcnhost_balanced_class_weights(int num_nodes, int num_classes, const int *split, const int *label, const uint32_t *multihot,
+                                   int which_split, float *weights);
+/* A class weights text file, host only: one float per line, one line per class.  *num_classes > 0: the file must have that many
+ * lines; it receives the number read.  weights may be NULL (check and count only).  A wrong line count, a token that is not a
+ * number, a negative, NaN or infinite value is an error whose message names the line. */
+int gcnhost_class_weights_read(const char *path, int *num_classes, float *weights);
 int gcnhost_model_destroy(gcnhost_model *m);
 
 int gcnhost_model_train_epoch(gcnhost_model *m, float *loss, float *acc);      /* gcn.cpp:107-118; synchronises */
