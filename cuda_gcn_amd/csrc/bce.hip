@@ -7,6 +7,9 @@
 // row's logits and truth word are loaded while this row's terms are computed (each row is a dependent chain rows[q] ->
 // logits).  Reductions are deterministic: per-lane in row order, a fixed shuffle tree, block partials added in block
 // order by a one-block finalize launch — the grid depends on n_rows alone, so two launches give the same bits.
+//
+// bce_fwd_kernel<true> (gcnhip_wbce_fwd_rows) is the same walk with a weight per class on the positive term and its gradient
+// (pos_weight), which a lane holds in four registers for the whole launch: no LDS.
 #include "common.h"
 #include <stdlib.h>
 #pragma clang fp contract(off)
@@ -24,6 +27,7 @@ struct BceArgs {
     float denom;                // count * C (the gradient's divisor)
     float *part_f;              // [blocks]
     int32_t *part_i;            // [blocks * 3] {TP, FP, FN}
+    const float *pos_weight;    // W = true only: [C] (kept at the end: the offsets the unweighted kernel reads stay where they were)
 };
 
 __device__ inline float bce_sigmoid(float z) {
@@ -32,6 +36,7 @@ __device__ inline float bce_sigmoid(float z) {
     return e / (1.f + e);
 }
 
+template <bool W>
 __global__ __launch_bounds__(256) void bce_fwd_kernel(BceArgs a) {
     __shared__ float sh_f[4];
     __shared__ int sh_i[12];
@@ -39,6 +44,14 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(BceArgs a) {
     const int waves_total = gridDim.x * 4;
     float loss = 0.f;
     int tp = 0, fp = 0, fn = 0;
+    float pw[BCE_MAXC_REG];
+    if constexpr (W) {
+#pragma unroll
+        for (int k = 0; k < BCE_MAXC_REG; k++) {
+            const int j = lane + k * WAVE;
+            pw[k] = j < a.C ? a.pos_weight[j] : 0.f;
+        }
+    }
     float nv[BCE_MAXC_REG];
     uint32_t nw[BCE_MAXC_REG];
     auto prefetch = [&](int q) {
@@ -69,15 +82,21 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(BceArgs a) {
             if (j >= a.C) continue;
             const float z = v[k];
             const bool y = (w[k] >> (j & 31)) & 1u;
-            // max(z, 0) - z y + log(1 + exp(-|z|)): finite for every finite z
-            loss += (fmaxf(z, 0.f) - (y ? z : 0.f)) + log1pf(expf(-fabsf(z)));
+            if constexpr (W) {
+                // pw . y . softplus(-z) + (1 - y) . softplus(z), softplus(x) = max(x, 0) + log1p(exp(-|x|)): finite for every finite z
+                const float l1p = log1pf(expf(-fabsf(z)));
+                loss += y ? pw[k] * (fmaxf(-z, 0.f) + l1p) : fmaxf(z, 0.f) + l1p;
+            } else {
+                // max(z, 0) - z y + log(1 + exp(-|z|)): finite for every finite z
+                loss += (fmaxf(z, 0.f) - (y ? z : 0.f)) + log1pf(expf(-fabsf(z)));
+            }
             const bool pos = z > 0.f;
             tp += pos && y;
             fp += pos && !y;
             fn += !pos && y;
             if (gr) {
                 // sigmoid(z) - 1 = -sigmoid(-z): no cancellation when y = 1 and z is large (float 1 - 4e-8 keeps one digit)
-                const float g = (y ? -bce_sigmoid(-z) : bce_sigmoid(z)) / a.denom;
+                const float g = (y ? -(W ? pw[k] * bce_sigmoid(-z) : bce_sigmoid(-z)) : bce_sigmoid(z)) / a.denom;
                 gr[j] = a.grad_row_scale ? g * gs : g;
             }
         }
@@ -111,13 +130,7 @@ __global__ __launch_bounds__(256) void bce_finalize_kernel(const float *part_f, 
     const float r[4] = {(shf[0] + shf[1]) + (shf[2] + shf[3]), (float)((double)n_rows * C), (float)(2.0 * TP), (float)(2.0 * TP + FP + FN)};
     if (res) { res[0] = r[0]; res[1] = r[1]; res[2] = r[2]; res[3] = r[3]; }
     if (res_i) { res_i[0] = TP; res_i[1] = FP; res_i[2] = FN; res_i[3] = n_rows; }
-    if (ring) {                                           // metrics_record_kernel's row (elementwise.hip)
-        const uint32_t e = ring_epoch ? *ring_epoch : 0u;
-        float *row = ring + ((size_t)(e % (uint32_t)ring_capacity) * 4 + ring_slot) * 8;
-        row[0] = r[0]; row[1] = r[1]; row[2] = r[2]; row[3] = r[3];
-        row[4] = ring_sumsq ? *ring_sumsq : 0.f;
-        row[5] = (float)e; row[6] = 0.f; row[7] = 0.f;
-    }
+    ring_row_write({ring, ring_capacity, ring_slot, ring_epoch, ring_sumsq}, r[0], r[1], r[2], r[3]);
 }
 
 // one wave per listed row: bit c of the row's words = (z_c > 0), the rule the TP / FP / FN counts use; optional sigmoid row
@@ -140,18 +153,16 @@ __global__ __launch_bounds__(256) void bce_predict_kernel(const float *logits, i
     }
 }
 
-extern "C" {
-
-int gcnhip_bce_fwd_rows(gcnhip_ctx *c, const float *logits, int ld, float *grad, int ld_grad,
-                        const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
-                        int num_classes, int training, int count, const float *d_grad_row_scale,
-                        float *d_result, int32_t *d_result_i) {
-    if (!c || !logits || !truth_bits || !d_result || num_classes < 1 || num_classes > BCE_MAXC_REG * WAVE || ld < num_classes) return -1;
+// both entry points, after the checks that differ between them; d_pos_weight chooses the weighted kernel
+static int bce_launch(gcnhip_ctx *c, const float *logits, int ld, float *grad, int ld_grad,
+                      const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
+                      int num_classes, int training, int count, const float *d_grad_row_scale,
+                      float *d_result, int32_t *d_result_i, const float *d_pos_weight) {
     if (words_per_row < (num_classes + 31) / 32 || n_listed < 0 || (n_listed > 0 && !d_rows)) return -1;
     if (training && (!grad || ld_grad < num_classes || count <= 0)) return -1;
     BceArgs a;
     a.logits = logits; a.grad = training ? grad : nullptr; a.truth = truth_bits; a.rows = d_rows;
-    a.grad_row_scale = d_grad_row_scale;
+    a.grad_row_scale = d_grad_row_scale; a.pos_weight = d_pos_weight;
     a.ld = ld; a.ld_grad = ld_grad; a.wpr = words_per_row; a.n_rows = n_listed; a.C = num_classes;
     a.denom = (float)((double)(count > 0 ? count : 1) * num_classes);
     int blocks = ceil_div(n_listed, 4 * 4);               // ~4 rows per wave on small inputs; the cap decides on large ones
@@ -159,17 +170,35 @@ int gcnhip_bce_fwd_rows(gcnhip_ctx *c, const float *logits, int ld, float *grad,
     if (blocks < 1) blocks = 1;                           // a rank that owns no rows still reports zeros
     a.part_f = c->red_f + 2048;
     a.part_i = c->red_i;
-    bce_fwd_kernel<<<blocks, 256, 0, c->stream>>>(a);
+    if (d_pos_weight) bce_fwd_kernel<true><<<blocks, 256, 0, c->stream>>>(a);
+    else bce_fwd_kernel<false><<<blocks, 256, 0, c->stream>>>(a);
     GCNHIP_LAUNCH_CHECK();
-    float *ring = nullptr; int cap = 1, slot = 0; const uint32_t *ep = nullptr; const float *sumsq = nullptr;
-    if (c->rec_armed) {                                   // gcnhip_metrics_record_with_next_loss: this launch writes the row
-        ring = c->rec_ring; cap = c->rec_capacity; slot = c->rec_slot; ep = c->rec_epoch; sumsq = c->rec_sumsq;
-        c->rec_armed = false;
-    }
+    const RingRow g = ring_row_take(c);                   // gcnhip_metrics_record_with_next_loss: this launch writes the row
     bce_finalize_kernel<<<1, 256, 0, c->stream>>>(a.part_f, a.part_i, blocks, n_listed, num_classes, d_result, d_result_i,
-                                                  ring, cap, slot, ep, sumsq);
+                                                  g.ring, g.capacity, g.slot, g.epoch, g.sumsq);
     GCNHIP_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" {
+
+int gcnhip_bce_fwd_rows(gcnhip_ctx *c, const float *logits, int ld, float *grad, int ld_grad,
+                        const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
+                        int num_classes, int training, int count, const float *d_grad_row_scale,
+                        float *d_result, int32_t *d_result_i) {
+    if (!c || !logits || !truth_bits || !d_result || num_classes < 1 || num_classes > BCE_MAXC_REG * WAVE || ld < num_classes) return -1;
+    return bce_launch(c, logits, ld, grad, ld_grad, truth_bits, words_per_row, d_rows, n_listed, num_classes, training, count,
+                      d_grad_row_scale, d_result, d_result_i, nullptr);
+}
+
+int gcnhip_wbce_fwd_rows(gcnhip_ctx *c, const float *logits, int ld, float *grad, int ld_grad,
+                         const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows, int n_listed,
+                         int num_classes, int training, int count, const float *d_grad_row_scale,
+                         float *d_result, int32_t *d_result_i, const float *d_pos_weight) {
+    if (!c || !logits || !truth_bits || !d_result || !d_pos_weight || num_classes < 1 || ld < num_classes) return -1;
+    if (num_classes > BCE_MAXC_REG * WAVE) return gcnhip_fail("gcnhip_wbce_fwd_rows: more than 256 classes");
+    return bce_launch(c, logits, ld, grad, ld_grad, truth_bits, words_per_row, d_rows, n_listed, num_classes, training, count,
+                      d_grad_row_scale, d_result, d_result_i, d_pos_weight);
 }
 
 int gcnhip_bce_predict_rows(gcnhip_ctx *c, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes,
@@ -184,4 +213,4 @@ int gcnhip_bce_predict_rows(gcnhip_ctx *c, const float *logits, int ld, const in
 
 }  // extern "C"
 
-GCNHIP_DEFINE_PRELOAD(bce, bce_fwd_kernel)
+GCNHIP_DEFINE_PRELOAD(bce, bce_fwd_kernel<false>)

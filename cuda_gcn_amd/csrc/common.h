@@ -204,6 +204,29 @@ __device__ inline int wave_sum_i(int v) {
     return v;
 }
 
+// An armed row of the metrics ring (gcnhip_metrics_record_with_next_loss): the loss launch that takes it writes the row
+// metrics_record_kernel (elementwise.hip) would have copied afterwards.  ring == NULL: none.
+struct RingRow {
+    float *ring; int capacity, slot; const uint32_t *epoch; const float *sumsq;
+};
+__device__ inline void ring_row_write(const RingRow &g, float r0, float r1, float r2, float r3) {
+    if (!g.ring) return;
+    const uint32_t e = g.epoch ? *g.epoch : 0u;
+    float *row = g.ring + ((size_t)(e % (uint32_t)g.capacity) * 4 + g.slot) * 8;
+    row[0] = r0; row[1] = r1; row[2] = r2; row[3] = r3;
+    row[4] = g.sumsq ? *g.sumsq : 0.f;
+    row[5] = (float)e; row[6] = 0.f; row[7] = 0.f;
+}
+// the context's armed row, disarmed by taking it
+static inline RingRow ring_row_take(gcnhip_ctx *c) {
+    RingRow g = {nullptr, 1, 0, nullptr, nullptr};
+    if (c->rec_armed) {
+        g = {c->rec_ring, c->rec_capacity, c->rec_slot, c->rec_epoch, c->rec_sumsq};
+        c->rec_armed = false;
+    }
+    return g;
+}
+
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // Each .hip file is its own code object inside the library, and the runtime loads a code object when the first kernel from it

@@ -609,6 +609,31 @@ void HipGCN::wire_overlap(HipGraphSum *gs, bool output_layer) {
     if (!(flags & HIPGCN_ALL_ROWS)) { gs->fwd_out_rows_loc = &cur_out_rows_loc; gs->fwd_out_rows_rem = &cur_out_rows_rem; }
 }
 
+// The loss module of one site (the modular list, the fused list, the evaluation lane).  Multi-label models take the sigmoid
+// loss, the others the softmax loss; class weights, when the model has them, go to either.  Both are loss kernels on the stored
+// logits, except the unweighted softmax loss, which rides in the epilogue of the launch that produces the logits (f32 tables, at
+// most 64 classes; the paths that cut that launch in two — exchange overlap — or gather bf16 tables keep the loss kernel:
+// HipGraphSum::forward decides).
+Module *HipGCN::make_loss(const LossSite &s) {
+    const int C = params.output_dim;
+    if (opt_.multilabel) {
+        auto *bce = new HipBCELoss(s.env, s.Z, d_ml_truth, ml_wpr, s.count, s.d_result, s.d_result_i, C);
+        bce->rows_list = s.rows; bce->rows_n = s.rows_n; bce->grad_row_scale = s.grad_row_scale;
+        bce->d_pos_weight = d_class_w;
+        return bce;
+    }
+    auto *ce = new HipCrossEntropyLoss(s.env, s.Z, s.truth, s.count, s.d_result, s.d_result_i, C, s.shift_in_place);
+    if (s.list_rows) { ce->rows_list = s.rows; ce->rows_n = s.rows_n; }
+    ce->grad_row_scale = s.grad_row_scale;
+    ce->d_weight = d_class_w; ce->weight_sum = s.wsum;
+    if (s.epilogue && !d_class_w && opt_.loss_epilogue && C <= 64 && !s.env->bf16_tables) {
+        const size_t n = (size_t)2 * std::max(n_local, 1);
+        ce->row_terms = dev_upload(s.env->ctx, std::vector<float>(n, 0.f).data(), n);
+        s.epilogue->loss = ce;
+    }
+    return ce;
+}
+
 void HipGCN::build_modules() {
     const int N = n_local, F = params.input_dim, H = params.hidden_dim, C = params.output_dim;
     const int rank = env.comm->rank();
@@ -627,20 +652,9 @@ void HipGCN::build_modules() {
         modules.push_back(new HipDropout(&env, H1, p, KEY_HIDDEN_DROPOUT, hid_off, (flags & HIPGCN_HOST_MASKS) ? &env.keep_hidden : &no_mask));
         modules.push_back(new HipMatmul(&env, H1, W2, Z0, N, H, C));
         { auto *gs = new HipGraphSum(&env, Z0, Z, graph, C); gs->bwd_row_bits = &bwd_bits; gs->bwd_graph = graph_bwd_out; gs->fwd_out_rows = &cur_out_rows; wire_overlap(gs, true); modules.push_back(gs); logits_gs = gs; }
-        if (opt_.multilabel && d_class_w) {
-            auto *bce = new HipWeightedBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_class_w, d_result, d_result_i, C);
-            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
-            modules.push_back(bce);
-        } else if (opt_.multilabel) {
-            auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
-            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
-            modules.push_back(bce);
-        } else if (d_class_w) {
-            auto *wce = new HipWeightedCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, &cur_wsum, d_class_w, d_result, d_result_i, C, true);
-            wce->rows_list = &cur_rows; wce->rows_n = &cur_rows_n;
-            modules.push_back(wce);
-        } else
-        modules.push_back(new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, true));
+        // the reference's loss visits every row; the losses beyond it (multi-label, class weights) take the split's row list
+        modules.push_back(make_loss({&env, Z, &cur_truth, &cur_count, &cur_wsum, &cur_rows, &cur_rows_n, d_result, d_result_i, true, nullptr,
+                                     opt_.multilabel || d_class_w != nullptr, nullptr}));
     } else {
         const float scale = 1 / (1 - p);
         auto *sm = new HipSparseMatmul(&env, &input_vals, W1, H0, feat, N, F, H, p, nnz_off);
@@ -683,37 +697,10 @@ void HipGCN::build_modules() {
             gs_logits = gs;
             logits_gs = gs;
         }
-        if (d_class_w) {                               // class-weighted: the loss kernels of wloss.hip on the stored logits (no loss epilogue)
-            const float *dinv = nullptr;
-            if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &dinv, nullptr, nullptr, nullptr));
-            if (opt_.multilabel) {
-                auto *bce = new HipWeightedBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_class_w, d_result, d_result_i, C);
-                bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n; bce->grad_row_scale = dinv;
-                modules.push_back(bce);
-            } else {
-                auto *wce = new HipWeightedCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, &cur_wsum, d_class_w, d_result, d_result_i, C, false);
-                wce->rows_list = &cur_rows; wce->rows_n = &cur_rows_n; wce->grad_row_scale = dinv;
-                modules.push_back(wce);
-            }
-            return;
-        }
-        if (opt_.multilabel) {                         // the loss kernel on the stored logits (no loss epilogue)
-            auto *bce = new HipBCELoss(&env, Z, d_ml_truth, ml_wpr, &cur_count, d_result, d_result_i, C);
-            bce->rows_list = &cur_rows; bce->rows_n = &cur_rows_n;
-            if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &bce->grad_row_scale, nullptr, nullptr, nullptr));
-            modules.push_back(bce);
-            return;
-        }
-        auto *ce = new HipCrossEntropyLoss(&env, Z, &cur_truth, &cur_count, d_result, d_result_i, C, false);
-        ce->rows_list = &cur_rows; ce->rows_n = &cur_rows_n;
-        if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &ce->grad_row_scale, nullptr, nullptr, nullptr));   // dZ' = dinv . dZ
-        // the loss rides in the epilogue of the launch that produces the logits (f32 tables, at most 64 classes; the paths that
-        // cut that launch in two — exchange overlap — or gather bf16 tables keep the loss kernel: HipGraphSum::forward decides)
-        if (opt_.loss_epilogue && C <= 64 && !env.bf16_tables) {
-            ce->row_terms = dev_upload(env.ctx, std::vector<float>((size_t)2 * std::max(N, 1), 0.f).data(), (size_t)2 * std::max(N, 1));
-            gs_logits->loss = ce;
-        }
-        modules.push_back(ce);
+        const float *dinv = nullptr;
+        if (factored_) GCNHIP_CHECK(gcnhip_graph_scales(graph, &dinv, nullptr, nullptr, nullptr));   // dZ' = dinv . dZ
+        modules.push_back(make_loss({&env, Z, &cur_truth, &cur_count, &cur_wsum, &cur_rows, &cur_rows_n, d_result, d_result_i, false, dinv, true,
+                                     gs_logits}));
     }
 }
 
@@ -832,27 +819,8 @@ void HipGCN::build_eval_lane() {
     gs_logits->fwd_out_rows = &L.out_rows;
     if (factored_) gs_logits->fwd_scaling = 1;
     L.modules.push_back(gs_logits);
-    if (d_class_w && opt_.multilabel) {
-        auto *bce = new HipWeightedBCELoss(&L.env, L.Z.get(), d_ml_truth, ml_wpr, &L.count, d_class_w, L.d_result, L.d_result_i, C);
-        bce->rows_list = &L.rows; bce->rows_n = &L.rows_n;
-        L.modules.push_back(bce);
-    } else if (d_class_w) {
-        auto *wce = new HipWeightedCrossEntropyLoss(&L.env, L.Z.get(), &L.truth, &L.count, &L.wsum, d_class_w, L.d_result, L.d_result_i, C, false);
-        wce->rows_list = &L.rows; wce->rows_n = &L.rows_n;
-        L.modules.push_back(wce);
-    } else if (opt_.multilabel) {
-        auto *bce = new HipBCELoss(&L.env, L.Z.get(), d_ml_truth, ml_wpr, &L.count, L.d_result, L.d_result_i, C);
-        bce->rows_list = &L.rows; bce->rows_n = &L.rows_n;
-        L.modules.push_back(bce);
-    } else {
-        auto *ce = new HipCrossEntropyLoss(&L.env, L.Z.get(), &L.truth, &L.count, L.d_result, L.d_result_i, C, false);
-        ce->rows_list = &L.rows; ce->rows_n = &L.rows_n;
-        if (opt_.loss_epilogue && C <= 64 && !L.env.bf16_tables) {     // as on the training context
-            ce->row_terms = dev_upload(L.env.ctx, std::vector<float>((size_t)2 * std::max(N, 1), 0.f).data(), (size_t)2 * std::max(N, 1));
-            gs_logits->loss = ce;
-        }
-        L.modules.push_back(ce);
-    }
+    L.modules.push_back(make_loss({&L.env, L.Z.get(), &L.truth, &L.count, &L.wsum, &L.rows, &L.rows_n, L.d_result, L.d_result_i, false, nullptr,
+                                   true, gs_logits}));       // the loss epilogue as on the training context
     GCNHIP_CHECK(gcnhip_event_create_sync(&L.ev_weights));
     GCNHIP_CHECK(gcnhip_event_create_sync(&L.ev_done));
     GCNHIP_CHECK(gcnhip_event_create_sync(&L.ev_fork));

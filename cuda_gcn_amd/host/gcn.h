@@ -385,6 +385,23 @@ private:
     void apply_schedule(gcnhip_ctx *ctx, gcnhip_graph *g);
     void add_split_rowsets(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *out[4]);
     void build_modules();
+    // what differs between the sites that build a loss module (make_loss)
+    struct LossSite {
+        HipEnv *env;
+        HipVariable *Z;                         // the logits
+        int32_t *const *truth;
+        const int *count;
+        const float *wsum;
+        int32_t *const *rows;
+        const int *rows_n;
+        float *d_result;
+        int32_t *d_result_i;
+        bool shift_in_place;
+        const float *grad_row_scale;
+        bool list_rows;                         // false: the single-label loss visits every row, as the reference does
+        HipGraphSum *epilogue;                  // the aggregation that may carry the loss epilogue, or NULL
+    };
+    Module *make_loss(const LossSite &s);
     void set_truth(int current_split);
     void host_masks_for_epoch();
     void train_epoch_async();

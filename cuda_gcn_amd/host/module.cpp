@@ -318,7 +318,7 @@ HipCrossEntropyLoss::HipCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32
 HipCrossEntropyLoss::~HipCrossEntropyLoss() { if (row_terms) gcnhip_free(env->ctx, row_terms); }
 
 bool HipCrossEntropyLoss::epilogue_opts(bool training, gcnhip_gs_loss *o) const {
-    if (!row_terms || !rows_list || !*rows_list || *count <= 0 || num_classes > 64 || shift_in_place) return false;
+    if (!row_terms || !rows_list || !*rows_list || *count <= 0 || num_classes > 64 || shift_in_place || d_weight) return false;
     o->truth = *truth; o->grad = logits->grad; o->ld_grad = logits->ld; o->training = training ? 1 : 0; o->count = *count;
     o->grad_row_scale = grad_row_scale; o->row_terms = row_terms;
     return true;
@@ -326,7 +326,11 @@ bool HipCrossEntropyLoss::epilogue_opts(bool training, gcnhip_gs_loss *o) const 
 
 void HipCrossEntropyLoss::forward(bool training) {
     env->timers->start(TMR_LOSS_FW);
-    if (terms_fresh) {
+    if (d_weight)
+        GCNHIP_CHECK(gcnhip_wxent_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, *truth, *rows_list, rows_n ? *rows_n : 0,
+                                           num_classes, training && *count > 0 ? 1 : 0, *count > 0 ? *count : 1, shift_in_place ? 1 : 0,
+                                           d_result, d_result_i, grad_row_scale, d_weight, *weight_sum));
+    else if (terms_fresh) {
         terms_fresh = false;
         GCNHIP_CHECK(gcnhip_xent_from_row_terms(env->ctx, row_terms, *truth, *rows_list, *rows_n, d_result, d_result_i));
     } else if (rows_list && *rows_list && *count > 0)
@@ -348,37 +352,12 @@ HipBCELoss::HipBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, 
 void HipBCELoss::forward(bool training) {
     env->timers->start(TMR_LOSS_FW);
     const int n = rows_n ? *rows_n : 0;
+    if (d_pos_weight)
+        GCNHIP_CHECK(gcnhip_wbce_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, truth, wpr, *rows_list, n, num_classes,
+                                          training && *count > 0 ? 1 : 0, *count, grad_row_scale, d_result, d_result_i, d_pos_weight));
+    else
     GCNHIP_CHECK(gcnhip_bce_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, truth, wpr, *rows_list, n, num_classes,
                                      training && *count > 0 ? 1 : 0, *count, grad_row_scale, d_result, d_result_i));
-    env->timers->stop(TMR_LOSS_FW);
-}
-
-// ---------------------------------------------------------- class-weighted
-HipWeightedCrossEntropyLoss::HipWeightedCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count,
-                                                         const float *weight_sum, const float *d_weight, float *d_result,
-                                                         int32_t *d_result_i, int num_classes, bool shift)
-    : env(env), logits(logits), truth(truth), count(count), weight_sum(weight_sum), d_weight(d_weight), d_result(d_result),
-      d_result_i(d_result_i), num_classes(num_classes), shift_in_place(shift) {}
-
-void HipWeightedCrossEntropyLoss::forward(bool training) {
-    env->timers->start(TMR_LOSS_FW);
-    const int n = rows_n ? *rows_n : 0;
-    GCNHIP_CHECK(gcnhip_wxent_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, *truth, *rows_list, n, num_classes,
-                                       training && *count > 0 ? 1 : 0, *count > 0 ? *count : 1, shift_in_place ? 1 : 0, d_result, d_result_i,
-                                       grad_row_scale, d_weight, *weight_sum));
-    env->timers->stop(TMR_LOSS_FW);
-}
-
-HipWeightedBCELoss::HipWeightedBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count,
-                                       const float *d_pos_weight, float *d_result, int32_t *d_result_i, int num_classes)
-    : env(env), logits(logits), truth(truth), wpr(wpr), count(count), d_pos_weight(d_pos_weight), d_result(d_result),
-      d_result_i(d_result_i), num_classes(num_classes) {}
-
-void HipWeightedBCELoss::forward(bool training) {
-    env->timers->start(TMR_LOSS_FW);
-    const int n = rows_n ? *rows_n : 0;
-    GCNHIP_CHECK(gcnhip_wbce_fwd_rows(env->ctx, logits->data, logits->ld, logits->grad, logits->ld, truth, wpr, *rows_list, n, num_classes,
-                                      training && *count > 0 ? 1 : 0, *count, grad_row_scale, d_result, d_result_i, d_pos_weight));
     env->timers->stop(TMR_LOSS_FW);
 }
 

@@ -189,7 +189,12 @@ public:
     // row_terms: [2 x rows] floats owned by this module (NULL: the loss kernel reads the logits, as before).
     float *row_terms = nullptr;
     bool terms_fresh = false;                   // the producing launch of this forward wrote row_terms
-    bool epilogue_opts(bool training, gcnhip_gs_loss *o) const;   // false: not applicable (no row list, empty split)
+    bool epilogue_opts(bool training, gcnhip_gs_loss *o) const;   // false: not applicable (no row list, empty split, class weights)
+    // Class weights (beyond the reference; HipGCNOptions::class_weights): d_weight [C] set, forward() is gcnhip_wxent_fwd_rows on
+    // the stored logits of the listed rows (a row list is required, no loss epilogue); d_result = {sum of w . term, sum of w,
+    // correct, total}; weight_sum points at the current split's sum of w[truth] over ALL ranks (the gradient's divisor).
+    const float *d_weight = nullptr;
+    const float *weight_sum = nullptr;
     ~HipCrossEntropyLoss() override;
     HipCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count,
                         float *d_result, int32_t *d_result_i, int num_classes, bool shift_in_place);
@@ -213,54 +218,9 @@ public:
     int32_t *const *rows_list = nullptr;        // rows of the current split on this rank (ascending) and their number
     const int *rows_n = nullptr;
     const float *grad_row_scale = nullptr;      // factored aggregation: dZ' = dinv . dZ
+    const float *d_pos_weight = nullptr;        // [C] set: a weight per class on the positive term (gcnhip_wbce_fwd_rows)
     HipBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count,
                float *d_result, int32_t *d_result_i, int num_classes);
-    void forward(bool) override;
-    void backward() override {}
-};
-
-// Class-weighted losses (beyond the reference; HipGCNOptions::class_weights): the loss kernels of wloss.hip on the stored logits
-// of the scored split's rows, wired as HipBCELoss is — row lists always, grad_row_scale in the factored form, no loss
-// epilogue.  Single-label: d_result = {sum of w . term, sum of w, correct, total}; weight_sum points at the current split's
-// sum of w[truth] over ALL ranks (the gradient's divisor).
-class HipWeightedCrossEntropyLoss : public Module {
-    HipEnv *env;
-    HipVariable *logits;
-    int32_t *const *truth;
-    const int *count;
-    const float *weight_sum;
-    const float *d_weight;          // [C]
-    float *d_result;
-    int32_t *d_result_i;
-    int num_classes;
-    bool shift_in_place;
-public:
-    int32_t *const *rows_list = nullptr;
-    const int *rows_n = nullptr;
-    const float *grad_row_scale = nullptr;
-    HipWeightedCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count, const float *weight_sum,
-                                const float *d_weight, float *d_result, int32_t *d_result_i, int num_classes, bool shift_in_place);
-    void forward(bool) override;
-    void backward() override {}
-};
-
-// multi-label: HipBCELoss with a weight per class on the positive term (gcnhip_wbce_fwd_rows)
-class HipWeightedBCELoss : public Module {
-    HipEnv *env;
-    HipVariable *logits;
-    const uint32_t *truth;
-    int wpr;
-    const int *count;
-    const float *d_pos_weight;      // [C]
-    float *d_result;
-    int32_t *d_result_i;
-    int num_classes;
-public:
-    int32_t *const *rows_list = nullptr;
-    const int *rows_n = nullptr;
-    const float *grad_row_scale = nullptr;
-    HipWeightedBCELoss(HipEnv *env, HipVariable *logits, const uint32_t *truth, int wpr, const int *count, const float *d_pos_weight,
-                       float *d_result, int32_t *d_result_i, int num_classes);
     void forward(bool) override;
     void backward() override {}
 };

@@ -318,7 +318,7 @@ int gcnhip_bce_fwd_rows(gcnhip_ctx *ctx, const float *logits, int ld, float *gra
  * [i * ld_prob + c] = sigmoid(z_c).  1 <= num_classes <= 256. */
 int gcnhip_bce_predict_rows(gcnhip_ctx *ctx, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes,
                             uint32_t *bits, int words_per_row, float *prob, int ld_prob);
-/* ---- class-weighted losses (wloss.hip; beyond the reference, whose loss weighs every row equally) -------------------
+/* ---- class-weighted losses (xent.hip, bce.hip: the W = true kernels; beyond the reference, whose loss weighs every row equally) -------------------
  * Weighted softmax cross-entropy over a row list: the arguments of gcnhip_xent_fwd_rows_scaled plus d_class_weight [C]
  * (finite, >= 0) and weight_sum.  For each listed row r with truth t in [0, C) and w = d_class_weight[t]: the term
  * w * (log sum exp(z - max) - (z_t - max)); when training, grad[r, j] = w * (p_j - [j == t]) / weight_sum, times
