@@ -1,0 +1,742 @@
+"""The HIP kernels and the host driver on graphs and sparse features as data files really give them (tests/irregular_inputs.py):
+unsorted rows, repeated neighbours and feature ids, the self loop stored twice, one-directional edges, a hub row that is
+long only through repeats, a full-length permuted feature row.  The reference's semantics: degree = stored
+row length, a repeated entry contributes twice, forward and backward are the same row gather.
+
+Expected values: the CPU oracle first, the float64 products of irregular_inputs.dense_reference beside it
+(test_irregular_cpu.py proves the two agree before a GPU sees them).  Sums: test_ops_gpu.close_mag with k = 8, mag from the
+float64 product on absolute values.  The one exception is stated in test_irregular_cpu.test_oracle_graphsum_vs_float64: on the
+row that lists one neighbour 300 times the reference's own sequential f32 sum is 25-36 eps.mag from float64, so that row is
+held to float64 within max(8, the reference's own distance, measured here on the same input and printed) and not to the oracle.
+Measured on an MI355X: on that row the kernels are at most 13.9 eps.mag from float64 (plain, factored, masked, bf16, either
+split length) where the oracle is 35.6; every other row is inside k = 8 against both.  The file: 134 cases in 9 s.
+Bit-exact results are compared on .view(np.uint32).  Traces: test_model_gpu.check_trace.
+"""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from cuda_gcn_amd import datagen
+from tests import irregular_inputs as irr
+from tests.irregular_inputs import dense_reference
+from tests.test_ops_gpu import EPS, bf16_round, close_mag, philox_keep, thr_of
+from tests.test_model_gpu import check_trace, oracle_trace
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WIDTHS = [(1, 1), (7, 7), (41, 41), (41, 44), (128, 128), (260, 260)]
+DIMS = [1, 7, 41, 128, 260]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from cuda_gcn_amd.ops import Device
+    d = Device(0)
+    yield d
+    d.close()
+
+
+class Agg:
+    """the adjacency of the aggregation tests with its float64 operator; want(x) -> the expected values of A^ . x"""
+
+    def __init__(self, oracle):
+        self.gp, self.gi = irr.gpu_graph()
+        self.n = self.gp.size - 1
+        self.deg = np.diff(self.gp).astype(np.int64)
+        self.hub = int(np.argmax(self.deg))
+        self.a64 = irr.dense_adjacency(self.gp, self.gi)
+        self.heavy = irr.rows_repeating_one_entry(self.gp, self.gi)
+        self.rest = np.setdiff1d(np.arange(self.n), self.heavy)
+        self.oracle = oracle
+        self._memo = {}
+
+    def want(self, x, key=None):
+        """(oracle, float64, mag) of A^ . x; memoised under `key` so that tests share one reference"""
+        if key is not None and key in self._memo:
+            return self._memo[key]
+        x = np.ascontiguousarray(x, np.float32)
+        out = (self.oracle.graphsum(self.gp, self.gi, x, x.shape[1]), self.a64 @ x.astype(np.float64), self.a64 @ np.abs(x).astype(np.float64))
+        if key is not None:
+            self._memo[key] = out
+        return out
+
+    def x(self, dim):
+        return np.random.default_rng(1000 + dim).standard_normal((self.n, dim)).astype(np.float32)
+
+    def close(self, got, ref, rows=None, scale=1.0, what=""):
+        """got against ref = want(...): every row but the repeated-term row against the oracle AND float64 with k = 8; the
+        repeated-term row against float64 with max(8, the oracle's own distance from float64 on that row)"""
+        wo, w64, mag = ref
+        got = np.asarray(got, np.float64)
+        sel = np.arange(self.n) if rows is None else np.flatnonzero(rows)
+        rest = np.intersect1d(sel, self.rest)
+        close_mag(got[rest], wo[rest] * scale, mag[rest] * scale)
+        close_mag(got[rest], w64[rest] * scale, mag[rest] * scale)
+        assert self.hub in self.rest
+        for r in np.intersect1d(sel, self.heavy):
+            unit = EPS * mag[r] * scale + 1e-300
+            own = float((np.abs(wo[r] * scale - w64[r] * scale) / unit).max())
+            k_got = float((np.abs(got[r] - w64[r] * scale) / unit).max())
+            print(f"{what} row {r} ({self.deg[r]} entries, one repeated 300 times): oracle {own:.1f}, GPU {k_got:.1f} eps.mag from float64")
+            close_mag(got[r], w64[r] * scale, mag[r] * scale, k=max(8.0, own))
+
+
+@pytest.fixture(scope="module")
+def agg(oracle):
+    return Agg(oracle)
+
+
+@pytest.fixture(scope="module")
+def graph(dev, agg):
+    g = dev.graph(agg.gp, agg.gi)
+    yield g
+    g.free()
+
+
+# ---------------------------------------------------------------------------------------------------- aggregation family
+@pytest.mark.parametrize("dim,ld", WIDTHS)
+def test_graphsum(dev, agg, graph, dim, ld):
+    x = agg.x(dim)
+    got = dev.graphsum(graph, x, ld_in=ld, ld_out=ld)
+    agg.close(got, agg.want(x, dim), what=f"graphsum d{dim}")
+
+
+def test_coefficients_and_scales(dev, agg, graph):
+    """Graph.coef() bit-exact against the reference's per-edge coefficients (module.cpp:91-93: degree = STORED row length of
+    the row and of the column's own row), both sides with every row's (column, coefficient) pairs sorted — the library stores
+    the columns of the same rows in another order, so the device's columns are read back too.  Graph.scales() = 1 / sqrt and
+    1 / (stored row length), row and column arrays alike."""
+    gp, gi, deg = agg.gp, agg.gi, agg.deg
+    src = np.repeat(np.arange(agg.n), deg)
+    want = (1.0 / np.sqrt((deg[src] * deg[gi]).astype(np.float32)).astype(np.float64)).astype(np.float32)
+    got = graph.coef()
+    pi = C.c_void_p()
+    from cuda_gcn_amd.ops import _ck
+    _ck(dev.lib, dev.lib.gcnhip_graph_arrays(graph.h, None, C.byref(pi), None, None, None), "graph_arrays")
+    cols = np.empty(gi.size, np.int32)
+    _ck(dev.lib, dev.lib.gcnhip_d2h(dev.ctx, cols.ctypes.data, pi, cols.nbytes), "d2h")
+    assert got.size == gi.size                                                  # no entry dropped: repeats are stored
+    o_got, o_want = np.lexsort((bits(got), cols, src)), np.lexsort((bits(want), gi, src))
+    assert np.array_equal(cols[o_got], gi[o_want])                              # the same multiset of columns in every row
+    assert np.array_equal(bits(got)[o_got], bits(want)[o_want])
+    dr, dr2, dc, dc2 = graph.scales()
+    assert np.array_equal(bits(dr), bits((1.0 / np.sqrt(deg.astype(np.float64))).astype(np.float32)))
+    assert np.array_equal(bits(dr2), bits((1.0 / deg.astype(np.float64)).astype(np.float32)))
+    assert np.array_equal(bits(dr), bits(dc)) and np.array_equal(bits(dr2), bits(dc2))
+    in_deg = np.bincount(gi, minlength=agg.n)
+    assert (in_deg != deg).sum() > agg.n // 2                                   # (an in-degree would have been another array)
+
+
+@pytest.mark.parametrize("dim", DIMS)
+def test_graphsum_ex_every_scaling(dev, agg, graph, dim):
+    """the factored operator dinv (.) sum(dinv (.) x) in every form test_factored_operator_vs_oracle uses: it equals the
+    per-edge coefficients only if "degree of column j" is the stored length of row j"""
+    n, g = agg.n, graph
+    dr = g.scales()[0]
+    x = agg.x(dim)
+    ref = agg.want(x, dim)
+    xs = (x * dr[:, None]).astype(np.float32)
+    d64 = dr[:, None].astype(np.float64)
+    agg.close(dev.graphsum_ex(g, xs, 1), ref, what=f"ex1 d{dim}")
+    agg.close(dev.graphsum_ex(g, xs, 2) / d64, ref, what=f"ex2 d{dim}")
+    agg.close(dev.graphsum_ex(g, xs, 3) * d64, ref, what=f"ex3 d{dim}")
+    ld4 = (dim + 3) // 4 * 4
+    assert np.array_equal(bits(dev.graphsum_ex(g, x, 0)), bits(dev.graphsum(g, x, ld_in=ld4, ld_out=ld4)))
+    rng = np.random.default_rng(dim)
+    rows = rng.random(n) < 0.3
+    rows[[agg.hub, 1, 2]] = True
+    rs = g.add_rowset(rows)
+    got = dev.graphsum_ex(g, xs, 1, rows=rs, fill=5.0)
+    agg.close(got, ref, rows=rows, what=f"ex1 rowset d{dim}")
+    assert np.all(got[~rows] == 5.0)
+    g.remove_rowset(rs)
+    nz = rng.random(n) < 0.5
+    xm = x * nz[:, None]
+    agg.close(dev.graphsum_ex(g, (xm * dr[:, None]).astype(np.float32), 1, row_nonzero=nz), agg.want(xm), what=f"ex1 rowmask d{dim}")
+    own = np.arange(n) < n // 2                        # two operators with complementary columns, the second accumulates
+    ga, gb = g.restricted(own), g.restricted(~own)
+    part = dev.graphsum_ex(ga, xs, 3)
+    agg.close(dev.graphsum_ex(gb, xs, 1, prev=part), ref, what=f"ex parts d{dim}")
+    ga.free(); gb.free()
+
+
+@pytest.mark.parametrize("dim,ld", WIDTHS)
+def test_masked_rowset_rowmask_and_schedules(dev, agg, dim, ld):
+    """output-row mask, registered row subsets under every schedule, input-row mask (NaN in the rows promised zero), random
+    row groups at creation and through set_schedule: the computed rows carry the bits of the plain launch, the others the fill"""
+    n = agg.n
+    rng = np.random.default_rng(dim + ld)
+    x = agg.x(dim)
+    groups = rng.integers(0, 7, n).astype(np.int32)
+    g, g1 = dev.graph(agg.gp, agg.gi), dev.graph(agg.gp, agg.gi, row_group=groups)
+    full = dev.graphsum(g, x, ld_in=ld, ld_out=ld)
+    agg.close(full, agg.want(x, dim), what=f"plain d{dim}")
+    assert np.array_equal(bits(full), bits(dev.graphsum(g1, x, ld_in=ld, ld_out=ld)))
+    assert np.array_equal(bits(g.coef()), bits(g1.coef()))
+    nz = rng.random(n) < 0.6
+    nz[[agg.hub, 1]] = True
+    xz = np.where(nz[:, None], x, 0).astype(np.float32)
+    xn = np.where(nz[:, None], x, np.nan).astype(np.float32)
+    masked = dev.graphsum(g, xn, ld_in=ld, ld_out=ld, row_nonzero=nz)
+    agg.close(masked, agg.want(xz), what=f"rowmask d{dim}")
+    assert np.array_equal(bits(masked), bits(dev.graphsum(g1, xn, ld_in=ld, ld_out=ld, row_nonzero=nz)))
+    for trial in range(2):
+        rows = rng.random(n) < (0.66 if trial == 0 else 0.1)
+        rows[agg.hub] = trial == 0
+        rows[1] = trial == 1
+        got = dev.graphsum_masked(g, x, ld_in=ld, ld_out=ld, out_rows=rows, fill=123.0)
+        assert np.array_equal(bits(got[rows]), bits(full[rows])) and np.all(got[~rows] == 123.0)
+        both = dev.graphsum_masked(g, xn, ld_in=ld, ld_out=ld, row_nonzero=nz, out_rows=rows, fill=-7.0)
+        assert np.array_equal(bits(both[rows]), bits(masked[rows])) and np.all(both[~rows] == -7.0)
+        rs = g.add_rowset(rows)
+        for sched in range(4):
+            if sched == 1:
+                g.set_schedule(1, groups)
+            elif sched == 2:
+                g.set_schedule(2, None, 16)
+            elif sched == 3:
+                g.set_schedule(0)
+            got = dev.graphsum_rowset(g, rs, x, ld_in=ld, ld_out=ld, fill=55.0)
+            assert np.array_equal(bits(got[rows]), bits(full[rows])) and np.all(got[~rows] == 55.0), sched
+            both = dev.graphsum_rowset(g, rs, xn, ld_in=ld, ld_out=ld, row_nonzero=nz, fill=-7.0)
+            assert np.array_equal(bits(both[rows]), bits(masked[rows])) and np.all(both[~rows] == -7.0), sched
+            assert np.array_equal(bits(full), bits(dev.graphsum(g, x, ld_in=ld, ld_out=ld))), sched
+    g.free(); g1.free()
+
+
+@pytest.mark.parametrize("dim,ld", WIDTHS)
+def test_graphsum_relu_dropout(dev, agg, graph, dim, ld):
+    n, g = agg.n, graph
+    x = agg.x(dim)
+    wo, w64, mag = agg.want(x, dim)
+    relu = (np.maximum(wo, 0), np.maximum(w64, 0), mag)                     # |relu(a) - relu(b)| <= |a - b|
+    agg.close(dev.graphsum_relu_dropout(g, x, training=False, p=0.5, ld=ld), relu, what=f"relu d{dim}")
+    rng = np.random.default_rng(dim)
+    keep = rng.integers(0, 2, n * dim).astype(np.uint8)
+    k2 = keep.reshape(n, dim) != 0
+    got = dev.graphsum_relu_dropout(g, x, training=True, p=0.5, keep_mask=keep, ld=ld)
+    assert np.all(got[~k2] == 0)
+    agg.close(got, tuple(t * k2 for t in relu), scale=2.0, what=f"relu+keep d{dim}")
+    seed, epoch, off = 0x1234abcd5678, 7, 4 * 1000
+    k = philox_keep(seed, epoch, np.arange(n * dim, dtype=np.uint64) + np.uint64(off), thr_of(0.5)).reshape(n, dim)
+    got = dev.graphsum_relu_dropout(g, x, training=True, p=0.5, seed=seed, epoch=epoch, elem_offset=off, ld=ld)
+    assert np.all(got[~k] == 0)
+    agg.close(got, tuple(t * k for t in relu), scale=2.0, what=f"relu+philox d{dim}")
+
+
+@pytest.mark.parametrize("dim", [64, 128])
+def test_graphsum_relu_dropout_bits(dev, agg, graph, dim):
+    """the _bits form with injected keep decisions and with the device stream: out == the form without bits, bits == (out > 0)"""
+    n, g = agg.n, graph
+    x = agg.x(dim)
+    keep = np.random.default_rng(dim).integers(0, 2, n * dim).astype(np.uint8)
+    for training, kw in ((True, dict(keep_mask=keep)), (True, dict(seed=0xabcdef12345, epoch=3, elem_offset=128 * 7)), (False, {})):
+        want = dev.graphsum_relu_dropout(g, x, training=training, p=0.5, **kw)
+        got, words = dev.graphsum_relu_dropout_bits(g, x, training=training, p=0.5, **kw)
+        assert np.array_equal(bits(got), bits(want))
+        pos = got > 0
+        packed = np.packbits(pos.reshape(n, dim // 32, 32), axis=2, bitorder="little").view(np.uint32).reshape(n, dim // 32)
+        assert np.array_equal(words, packed)
+        assert 0.1 < pos.mean() < 0.6 and pos[agg.hub].any() and pos[1].any()
+    wo, w64, mag = agg.want(x, dim)
+    agg.close(got, (np.maximum(wo, 0), np.maximum(w64, 0), mag), what=f"bits d{dim}")
+
+
+@pytest.mark.parametrize("dim,ld", [(7, 8), (41, 48), (128, 128), (200, 256)])
+def test_graphsum_bf16_table(dev, agg, graph, dim, ld):
+    x = agg.x(dim)
+    codes, xr = bf16_round(x)
+    tab = dev.to_bf16(x, ld_dst=ld)
+    assert np.array_equal(tab[:, :dim], codes)
+    got = dev.graphsum_bf16(graph, tab, dim)
+    agg.close(got, agg.want(xr), what=f"bf16 d{dim}")                       # the oracle on the bf16-rounded table
+    if dim == 128:
+        assert np.array_equal(bits(got), bits(dev.graphsum(graph, xr)))
+
+
+@pytest.mark.parametrize("dim", [3, 7, 41, 64])
+def test_graphsum_loss_and_predict(dev, agg, graph, oracle, dim):
+    """the loss and prediction epilogues of the logit aggregation: logits against the oracle's aggregation, loss / correct
+    count / gradient rows against oracle.xent_fwd of it, epilogue and separate loss kernel bit-identical, predict = argmax"""
+    n, g = agg.n, graph
+    rng = np.random.default_rng(dim)
+    dr = g.scales()[0]
+    x = (rng.standard_normal((n, dim)) * 3).astype(np.float32)
+    xs = (x * dr[:, None]).astype(np.float32)
+    truth = rng.integers(0, dim, n).astype(np.int32)
+    truth[rng.random(n) < 0.4] = -1
+    truth[[agg.hub, 1, 2]] = 1 % dim
+    scored = truth >= 0
+    rs = g.add_rowset(scored)
+    ref = agg.want(x)
+    a = dev.graphsum_loss(g, xs, 1, truth, rows=rs, training=True, epilogue=True, grad_fill=7.0)
+    b = dev.graphsum_loss(g, xs, 1, truth, rows=rs, training=True, epilogue=False, grad_fill=7.0)
+    agg.close(a["logits"], ref, rows=scored, what=f"loss logits d{dim}")
+    assert np.array_equal(bits(a["logits"][scored]), bits(b["logits"][scored])) and np.array_equal(bits(a["res"]), bits(b["res"]))
+    assert (a["correct"], a["total"]) == (b["correct"], b["total"]) and a["total"] == int(scored.sum())
+    w4 = (dim + 3) // 4 * 4
+    assert np.array_equal(bits(a["grad"][scored][:, :w4]), bits(b["grad"][scored][:, :w4])) and np.all(a["grad"][~scored] == 7.0)
+    # oracle.xent_fwd on the oracle's own aggregation (rows not scored: truth -1)
+    loss, shifted, grad = oracle.xent_fwd(ref[0], truth, dim, training=True)
+    n_sc = int(scored.sum())
+    assert abs(a["loss_sum"] - loss * n_sc) <= 4e-5 * max(1.0, abs(loss * n_sc))            # test_loss_epilogue_of_the_logit_aggregation's bound
+    assert np.allclose(a["grad"][scored][:, :dim], grad[scored], rtol=2e-4, atol=1e-7)      # test_first_epoch_tensors_vs_oracle's, for gradients
+    z = ref[1][scored]                                                        # float64 logits: rows whose winner is clear
+    top = np.sort(z, axis=1)
+    clear = (top[:, -1] - top[:, -2] > 1e-4 * max(1.0, np.abs(z).max())) if dim > 1 else np.ones(n_sc, bool)
+    hit = (z.argmax(1) == truth[scored])
+    assert abs(a["correct"] - int(hit.sum())) <= int((~clear).sum())
+    p = dev.graphsum_predict(g, x=xs, scaling=1, rows=rs)
+    assert np.array_equal(bits(p["logits"][scored]), bits(a["logits"][scored]))
+    assert np.array_equal(p["pred"][scored][clear], z.argmax(1)[clear]) and np.all(p["pred"][~scored] == -1)
+    assert np.array_equal(p["pred"][scored], np.argmax(p["logits"][scored], axis=1))
+    lz = z - z.max(1, keepdims=True)
+    lz = lz - np.log(np.exp(lz).sum(1, keepdims=True))
+    assert np.allclose(p["logp"][scored], lz, rtol=0, atol=1e-4 * max(1.0, np.abs(z).max()))
+    g.remove_rowset(rs)
+
+
+@pytest.mark.parametrize("dim,ld", [(7, 7), (41, 44), (128, 128)])
+@pytest.mark.parametrize("share", [0.0, 0.6, 1.0])
+def test_restricted_operator(dev, agg, dim, ld, share):
+    """Graph.restricted(keep_cols): the operator without the entries that point at rows promised zero, against the masked
+    launch of the parent and the oracle on the zeroed input (NaN in the dropped rows: never read)"""
+    n = agg.n
+    rng = np.random.default_rng(dim + int(share * 10))
+    x = agg.x(dim)
+    nz = rng.random(n) < share
+    if share == 0.6:
+        nz[[agg.hub, 1]] = True
+    xz = np.where(nz[:, None], x, 0).astype(np.float32)
+    xn = np.where(nz[:, None], x, np.nan).astype(np.float32)
+    g = dev.graph(agg.gp, agg.gi, row_group=(np.arange(n) % 7).astype(np.int32))
+    gr = g.restricted(nz)
+    got = dev.graphsum(gr, xn, ld_in=ld, ld_out=ld)
+    ref = agg.want(xz)
+    agg.close(got, ref, what=f"restricted d{dim} share {share}")
+    agg.close(dev.graphsum(g, xn, ld_in=ld, ld_out=ld, row_nonzero=nz), ref, what=f"masked d{dim} share {share}")
+    if share == 1.0:
+        assert np.array_equal(bits(got), bits(dev.graphsum(g, x, ld_in=ld, ld_out=ld)))
+    if share == 0.0:
+        assert np.all(got == 0)
+    assert gr.coef().size == int(nz[agg.gi].sum())                            # every stored copy of a kept column is kept
+    if share > 0:
+        full = np.sort(g.coef()); sub = gr.coef()
+        pos = np.searchsorted(full, sub)
+        assert np.array_equal(full[np.minimum(pos, full.size - 1)], sub)
+    gr.free(); g.free()
+
+
+@pytest.mark.parametrize("dim", [7, 128])
+def test_split_edges_option(agg, dim):
+    """split_edges is read at graph creation: 0 (by size: 128-entry segments on a graph this small) and 1024 (the length
+    full-size graphs get; the hub row of 2 500 stored entries is still cut, the 307-entry row no longer) — each right, hub
+    row included, and equal within the bound"""
+    from cuda_gcn_amd.ops import Device
+    x = agg.x(dim)
+    ref = agg.want(x, dim)
+    outs = []
+    for value in (0, 1024):
+        d = Device(0)
+        d.set_option("split_edges", value)
+        g = d.graph(agg.gp, agg.gi)
+        got = d.graphsum(g, x)
+        agg.close(got, ref, what=f"split_edges {value} d{dim}")
+        close_mag(got[agg.hub], ref[0][agg.hub], ref[2][agg.hub])
+        outs.append(got)
+        g.free(); d.close()
+    close_mag(outs[0][agg.rest], outs[1][agg.rest], ref[2][agg.rest])
+
+
+# ------------------------------------------------------------------------------------------------ sparse transform family
+def spmm_refs(oracle, fp, fi, fv, F, w, dout):
+    p = w.shape[1]
+    f64, mag = dense_reference.spmm_fwd(fp, fi, fv, F, w)
+    b64, magb = dense_reference.spmm_bwd(fp, fi, fv, F, dout)
+    return (oracle.spmm_fwd(fp, fi, fv, w, p), f64, mag), (oracle.spmm_bwd(fp, fi, fv, dout, F, p), b64, magb)
+
+
+def close2(got, ref):
+    close_mag(got, ref[0], ref[2])
+    close_mag(got, ref[1], ref[2])
+
+
+@pytest.mark.parametrize("case", ["last", "first", "full"])
+@pytest.mark.parametrize("p", [3, 16, 41, 64, 128, 256])
+def test_spmm_products(dev, oracle, case, p):
+    fp, fi, fv, F = irr.gpu_features(case)
+    n = fp.size - 1
+    rng = np.random.default_rng(p)
+    w = rng.standard_normal((F, p)).astype(np.float32)
+    dout = rng.standard_normal((n, p)).astype(np.float32)
+    f = dev.feat(fp, fi, fv, F)
+    assert not f.dense
+    fwd, bwd = spmm_refs(oracle, fp, fi, fv, F, w, dout)
+    got = dev.spmm_fwd(f, w)
+    close2(got, fwd)
+    assert np.all(got[0] == 0) and np.all(got[-1] == 0)                        # the empty first and last rows
+    close2(dev.spmm_fwd_relu(f, w), tuple(np.maximum(t, 0) for t in fwd[:2]) + (fwd[2],))
+    dw = dev.spmm_bwd(f, dout)
+    close2(dw, bwd)
+    empty = irr.feature_properties(fp, fi, fv, F)["empty_columns"]
+    assert np.all(dw[empty] == 0) and (case == "full") == (empty.size == 0)   # columns that never occur are written as zeros
+    assert np.array_equal(bits(dw), bits(dev.spmm_bwd(f, dout)))               # no atomics: run to run the same bits
+    # input dropout, decisions per STORED element: an injected mask, the device stream at a non-zero offset, and p = 0
+    keep = rng.integers(0, 2, fi.size).astype(np.uint8)
+    off = 4 * 1001
+    k = philox_keep(99, 3, np.arange(fi.size, dtype=np.uint64) + np.uint64(off), thr_of(0.5))
+    for kept, kw in ((keep != 0, dict(p_drop=0.5, keep_mask=keep)), (k, dict(p_drop=0.5, seed=99, epoch=3, nnz_offset=off))):
+        vd = (fv * np.where(kept, np.float32(2), np.float32(0))).astype(np.float32)
+        fd, bd = spmm_refs(oracle, fp, fi, vd, F, w, dout)
+        close2(dev.spmm_fwd(f, w, **kw), fd)
+        close2(dev.spmm_bwd(f, dout, **kw), bd)
+        # two copies of one id in one row with different decisions exist, so a per-(row, id) decision would show
+        row_of = np.repeat(np.arange(n), np.diff(fp))
+        key = row_of.astype(np.int64) * F + fi
+        o = np.argsort(key, kind="stable")
+        same = key[o][1:] == key[o][:-1]
+        assert (kept[o][1:][same] != kept[o][:-1][same]).sum() >= 10
+    assert np.array_equal(bits(dev.spmm_fwd(f, w, p_drop=0.0, seed=99, epoch=3)), bits(got))
+    assert np.array_equal(bits(dev.spmm_bwd(f, dout, p_drop=0.0, seed=99, epoch=3)), bits(dw))
+    f.free()
+
+
+@pytest.mark.parametrize("p", [16, 41, 128])
+@pytest.mark.parametrize("nw,general", [(1, -1), (4, -1), (16, -1), (1, 1), (4, 1), (16, 1)])
+def test_spmm_options_and_a_column_long_through_one_row(oracle, p, nw, general):
+    """options spmm_nw (read at feature creation) and spmm_general on the matrix whose longest column (4 571 entries) holds
+    4 500 copies from ONE row: longer than every segment length of the weight gradient (1 024 at 1 and 4 waves, 4 096 at 16),
+    so the column is cut and folded; and on an ordinary irregular matrix"""
+    from cuda_gcn_amd.ops import Device
+    d = Device(0)
+    d.set_option("spmm_nw", nw)
+    d.set_option("spmm_general", general)
+    for case in ("long", "last"):
+        fp, fi, fv, F = irr.gpu_features(case)
+        n = fp.size - 1
+        rng = np.random.default_rng(100 + p)
+        w = rng.standard_normal((F, p)).astype(np.float32)
+        dout = rng.standard_normal((n, p)).astype(np.float32)
+        f = d.feat(fp, fi, fv, F)
+        assert not f.dense
+        k = philox_keep(5, 2, np.arange(fi.size, dtype=np.uint64), thr_of(0.5))
+        vd = (fv * np.where(k, np.float32(2), np.float32(0))).astype(np.float32)
+        for v, kw in ((fv, {}), (vd, dict(p_drop=0.5, seed=5, epoch=2))):
+            fwd, bwd = spmm_refs(oracle, fp, fi, v, F, w, dout)
+            dw = d.spmm_bwd(f, dout, **kw)
+            close2(dw, bwd)
+            assert np.all(dw[-3:] == 0)                                        # the columns that never occur
+            assert np.array_equal(bits(dw), bits(d.spmm_bwd(f, dout, **kw)))
+            close2(d.spmm_fwd(f, w, **kw), fwd)
+        assert d.spmm_bwd_plan(f, p) == (0, 0)                                 # a sparse object never takes the dense split plan
+        f.free()
+    d.close()
+
+
+@pytest.mark.parametrize("p", [128, 41])
+def test_spmm_bwd_parts_only_on_the_dense_layout(dev, p):
+    """gcnhip_spmm_bwd_plan/_part/_finish belong to the dense split plan: a matrix with nnz == N.F and one permuted row must
+    report no plan (0, 0) — it is a sparse object — while the same matrix with every row sorted gets one at p = 128, and its
+    parts with two and three cuts, dropout included, give the bits of the one-call gradient"""
+    rng = np.random.default_rng(p)
+    n, F = 2100, 96
+    fp, fi, fv, row = irr.permuted_full_features(rng, n, F)
+    dout = rng.standard_normal((n, p)).astype(np.float32)
+    f = dev.feat(fp, fi, fv, F)
+    assert not f.dense and dev.spmm_bwd_plan(f, p) == (0, 0)
+    sp, si, sv = irr.sorted_rows(fp, fi, fv)
+    c = dev.feat(sp, si, sv, F)
+    assert c.dense
+    rps, ns = dev.spmm_bwd_plan(c, p)
+    assert (ns >= 3 and (ns - 1) * rps < n <= ns * rps) if p == 128 else (rps, ns) == (0, 0)
+    for pd in (0.0, 0.5):
+        want = dev.spmm_bwd(c, dout, p_drop=pd, seed=11, epoch=3)
+        if pd == 0.0:                                                          # (keep decisions follow storage positions: only p = 0 is comparable)
+            close_mag(want, dev.spmm_bwd(f, dout), dense_reference.spmm_bwd(fp, fi, fv, F, dout)[1])
+        if ns >= 3:
+            for cuts in ([0, ns // 2, ns], [0, ns // 3, (2 * ns) // 3, ns]):
+                assert np.array_equal(bits(dev.spmm_bwd_parts(c, dout, cuts, p_drop=pd, seed=11, epoch=3)), bits(want)), (cuts, pd)
+    f.free(); c.free()
+
+
+@pytest.mark.parametrize("p", [3, 41, 128])
+@pytest.mark.parametrize("n,F", [(300, 48), (257, 130)])
+def test_full_length_permuted_row_is_not_dense(dev, oracle, n, F, p):
+    """nnz == N.F with exactly one row a non-identity permutation: NOT the dense layout (the MFMA path would read that row's
+    values in storage order = under the wrong columns).  Control: the same matrix with every row sorted IS dense, and its
+    products equal the sparse path's within the bound."""
+    rng = np.random.default_rng(n + p)
+    fp, fi, fv, row = irr.permuted_full_features(rng, n, F)
+    w = rng.standard_normal((F, p)).astype(np.float32)
+    dout = rng.standard_normal((n, p)).astype(np.float32)
+    f = dev.feat(fp, fi, fv, F)
+    assert not f.dense
+    fwd, bwd = spmm_refs(oracle, fp, fi, fv, F, w, dout)
+    a, da = dev.spmm_fwd(f, w), dev.spmm_bwd(f, dout)
+    close2(a, fwd); close2(da, bwd)
+    close2(dev.spmm_fwd_relu(f, w), tuple(np.maximum(t, 0) for t in fwd[:2]) + (fwd[2],))
+    k = philox_keep(7, 11, np.arange(fi.size, dtype=np.uint64), thr_of(0.5))
+    vd = (fv * np.where(k, np.float32(2), np.float32(0))).astype(np.float32)
+    fd, bd = spmm_refs(oracle, fp, fi, vd, F, w, dout)
+    kw = dict(p_drop=0.5, seed=7, epoch=11)
+    close2(dev.spmm_fwd(f, w, **kw), fd); close2(dev.spmm_bwd(f, dout, **kw), bd)
+    sp, si, sv = irr.sorted_rows(fp, fi, fv)
+    c = dev.feat(sp, si, sv, F)
+    assert c.dense
+    close2(dev.spmm_fwd(c, w), fwd); close2(dev.spmm_bwd(c, dout), bwd)
+    close_mag(dev.spmm_fwd(c, w), a, fwd[2]); close_mag(dev.spmm_bwd(c, dout), da, bwd[2])
+    # a row of F copies of one id in a full matrix, too
+    fi2 = fi.copy().reshape(n, F); fi2[row] = F // 2
+    g = dev.feat(fp, fi2.reshape(-1), fv, F)
+    assert not g.dense
+    fwd2, bwd2 = spmm_refs(oracle, fp, fi2.reshape(-1), fv, F, w, dout)
+    close2(dev.spmm_fwd(g, w), fwd2); close2(dev.spmm_bwd(g, dout), bwd2)
+    f.free(); c.free(); g.free()
+
+
+def test_spmm_sliced_forward(dev, oracle):
+    """the XCD-sliced forward (W past an XCD's L2) at the width test_spmm_sparse_sliced_forward_vs_oracle uses, on rows with
+    unsorted and repeated ids; N stays small, so the float64 products are formed row by row instead of through a dense X"""
+    p = 128
+    rng = np.random.default_rng(p)
+    N, F = 1031, (4 << 20) // (p * 4) + 700
+    lens = rng.integers(0, 40, N); lens[0] = 0; lens[-1] = 0; lens[11] = 300
+    rows = []
+    for k in lens:
+        ids = rng.integers(0, F, int(k))                                       # drawn with replacement, left in drawn order
+        if k > 2:
+            ids[1] = ids[0]
+        rows.append(ids)
+    rows[11][:] = rows[11][0]                                                  # 300 copies of one id, each with its own value
+    fp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    fi = np.concatenate(rows).astype(np.int32)
+    vals = rng.standard_normal(fi.size).astype(np.float32)
+    w = rng.standard_normal((F, p)).astype(np.float32)
+    row_of = np.repeat(np.arange(N), lens)
+    # (F ~ 8 900 is what takes this path, so the matrix is drawn here and not by irregular_features; its properties, by count)
+    q = irr.feature_properties(fp, fi, vals, F)
+    assert q["unsorted_rows"] >= N // 2 and q["rows_with_repeats"] >= N // 2 and q["first_row_empty"] and q["last_row_empty"]
+    assert q["empty_columns"].size > 0 and np.unique(fi[fp[11]:fp[12]]).size == 1 and fp[12] - fp[11] == 300
+    f64, mag = np.zeros((N, p)), np.zeros((N, p))
+    np.add.at(f64, row_of, vals[:, None].astype(np.float64) * w[fi].astype(np.float64))
+    np.add.at(mag, row_of, np.abs(vals[:, None].astype(np.float64) * w[fi].astype(np.float64)))
+    ref = (oracle.spmm_fwd(fp, fi, vals, w, p), f64, mag)
+    close_mag(ref[0], f64, mag)
+    f = dev.feat(fp, fi, vals, F)
+    assert not f.dense
+    old = dev.get_option("spmm_slices")
+    try:
+        outs = {}
+        for mode in (1, 0):
+            dev.set_option("spmm_slices", mode)
+            outs[mode] = dev.spmm_fwd(f, w)
+            close2(outs[mode], ref)
+            close2(dev.spmm_fwd_relu(f, w), (np.maximum(ref[0], 0), np.maximum(f64, 0), mag))
+            k = philox_keep(5, 2, np.arange(fi.size, dtype=np.uint64), thr_of(0.5))
+            vd = (vals * np.where(k, np.float32(2), np.float32(0))).astype(np.float32)
+            d64, dmag = np.zeros((N, p)), np.zeros((N, p))
+            np.add.at(d64, row_of, vd[:, None].astype(np.float64) * w[fi].astype(np.float64))
+            np.add.at(dmag, row_of, np.abs(vd[:, None].astype(np.float64) * w[fi].astype(np.float64)))
+            close2(dev.spmm_fwd(f, w, p_drop=0.5, seed=5, epoch=2), (oracle.spmm_fwd(fp, fi, vd, w, p), d64, dmag))
+        assert not np.array_equal(outs[0], outs[1])                            # two summation orders: the sliced kernel really ran
+    finally:
+        dev.set_option("spmm_slices", old)
+    f.free()
+
+
+@pytest.mark.parametrize("p", [3, 128])
+def test_spmm_edge_objects(dev, oracle, p):
+    """nnz = 0, a single row (unsorted, with a repeat), F = 1 (every stored id is a repeat of column 0)"""
+    rng = np.random.default_rng(p)
+    cases = [(np.zeros(6, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), 9),
+             (np.array([0, 5], np.int32), np.array([4, 1, 4, 0, 2], np.int32), rng.standard_normal(5).astype(np.float32), 7),
+             (np.array([0, 0, 3, 4, 4, 9], np.int32), np.zeros(9, np.int32), rng.standard_normal(9).astype(np.float32), 1)]
+    for fp, fi, fv, F in cases:
+        n = fp.size - 1
+        w = rng.standard_normal((F, p)).astype(np.float32)
+        dout = rng.standard_normal((n, p)).astype(np.float32)
+        f = dev.feat(fp, fi, fv, F)
+        assert not f.dense
+        fwd, bwd = spmm_refs(oracle, fp, fi, fv, F, w, dout)
+        close2(dev.spmm_fwd(f, w), fwd)
+        close2(dev.spmm_bwd(f, dout), bwd)
+        if fi.size:
+            keep = (np.arange(fi.size) % 2).astype(np.uint8)
+            vd = (fv * np.where(keep != 0, np.float32(2), np.float32(0))).astype(np.float32)
+            fd, bd = spmm_refs(oracle, fp, fi, vd, F, w, dout)
+            close2(dev.spmm_fwd(f, w, p_drop=0.5, keep_mask=keep), fd)
+            close2(dev.spmm_bwd(f, dout, p_drop=0.5, keep_mask=keep), bd)
+        f.free()
+
+
+# ------------------------------------------------------------------------------------------------------------ whole model
+@pytest.fixture(scope="module")
+def ds():
+    return irr.irregular_dataset()
+
+
+_TRACES = {}
+
+
+def shared_oracle_trace(oracle, ds, seed, epochs, hidden, dropout):
+    key = (seed, epochs, hidden, dropout)
+    if key not in _TRACES:
+        want, test, om = oracle_trace(oracle, ds, seed, epochs, hidden_dim=hidden, dropout=dropout)
+        om.close()
+        _TRACES[key] = (want, test)
+    return _TRACES[key]
+
+
+def model_flags(names):
+    from cuda_gcn_amd import model as M
+    f = 0
+    for k in names.split("|"):
+        f |= getattr(M, k) if k != "0" else 0
+    return f
+
+
+@pytest.mark.parametrize("hidden", [16, 128])
+@pytest.mark.parametrize("dropout", [0.0, 0.5])
+@pytest.mark.parametrize("names", ["0", "MODULAR", "ALL_ROWS", "EDGE_COEF", "MASKED_BWD", "EVAL_LANE", "NO_AGG_FIRST_EVAL|ALL_ROWS"])
+def test_trace_vs_oracle(oracle, ds, hidden, dropout, names):
+    """fused and MODULAR, dropout 0 and HOST_MASKS dropout 0.5 (the reference's decisions replayed), hidden 16 and 128, and
+    the flag sets test_model_gpu names: scored rows only (default) / ALL_ROWS, the factored aggregation (default) / EDGE_COEF,
+    the restricted backward operator (default) / MASKED_BWD, EVAL_LANE — each against the oracle's trace"""
+    from cuda_gcn_amd.model import HipGCNModel, HOST_MASKS
+    epochs = 20 if hidden == 16 else 12
+    want, want_test = shared_oracle_trace(oracle, ds, 5, epochs, hidden, dropout)
+    assert want[-1, 0] < want[0, 0] - 0.1                                      # training moves on this dataset
+    m = HipGCNModel(ds, seed=5, flags=model_flags(names) | (HOST_MASKS if dropout else 0), hidden_dim=hidden, dropout=dropout, epochs=epochs)
+    got = np.array([m.train_epoch() + m.eval(2) for _ in range(epochs)], np.float32)
+    print(names, hidden, dropout, "max |d loss|", np.abs(got[:, [0, 2]] - want[:, [0, 2]]).max())
+    check_trace(got, want, ds)
+    tl, ta = m.eval(3)
+    assert abs(tl - want_test[0]) <= 2e-3 and abs(ta - want_test[1]) <= 2.0 / int((ds["split"] == 3).sum()) + 1e-6
+    m.close()
+
+
+@pytest.mark.parametrize("hidden", [16, 128])
+def test_bf16_tables_track_the_oracle(oracle, ds, hidden):
+    """BF16_TABLES under test_bf16_tables_track_the_f32_trace's envelope: |d loss| <= 5e-3, |d acc| <= 0.03"""
+    from cuda_gcn_amd.model import HipGCNModel, HOST_MASKS, BF16_TABLES
+    epochs = 20 if hidden == 16 else 12
+    want, want_test = shared_oracle_trace(oracle, ds, 5, epochs, hidden, 0.5)
+    m = HipGCNModel(ds, seed=5, flags=HOST_MASKS | BF16_TABLES, hidden_dim=hidden, dropout=0.5, epochs=epochs)
+    got = np.array([m.train_epoch() + m.eval(2) for _ in range(epochs)], np.float64)
+    assert np.abs(got[:, [0, 2]] - want[:, [0, 2]]).max() <= 5e-3
+    assert np.abs(got[:, [1, 3]] - want[:, [1, 3]]).max() <= 0.03
+    t = m.eval(3)
+    assert abs(t[0] - want_test[0]) <= 5e-3 and abs(t[1] - want_test[1]) <= 0.03
+    assert np.abs(got - want).max() > 0
+    m.close()
+
+
+@pytest.mark.parametrize("edge_coef", [False, True])
+@pytest.mark.parametrize("all_rows", [True, False])
+def test_first_epoch_tensors_vs_oracle(oracle, ds, all_rows, edge_coef):
+    """every intermediate of one training epoch, with test_model_gpu.test_first_epoch_tensors_vs_oracle's tolerances"""
+    from cuda_gcn_amd.model import HipGCNModel, HOST_MASKS, ALL_ROWS, EDGE_COEF
+    N, H, Cn = ds["num_nodes"], 16, ds["output_dim"]
+    om = oracle.model(ds, seed_time=9, hidden_dim=H, dropout=0.5)
+    m = HipGCNModel(ds, seed=9, flags=HOST_MASKS | (ALL_ROWS if all_rows else 0) | (EDGE_COEF if edge_coef else 0), hidden_dim=H, dropout=0.5)
+    dinv, factored = m.row_scale()
+    assert factored == (not edge_coef)
+    assert np.allclose(dinv, 1.0 / np.sqrt(np.diff(ds["g_indptr"])), rtol=1e-7)        # stored row lengths
+    assert np.array_equal(m.var(2).reshape(-1), om.var(2)) and np.array_equal(m.var(5).reshape(-1), om.var(5))
+    a, b = m.train_epoch(), om.train_epoch()
+    assert abs(a[0] - b[0]) <= 2e-5 and abs(a[1] - b[1]) <= 1e-6
+    train = ds["split"] == 1
+    for k, shp in {1: (N, H), 3: (N, H), 4: (N, Cn), 6: (N, Cn)}.items():
+        want = om.var(k).reshape(shp)
+        got = m.var_reference(k)
+        if k == 6:
+            got = got - got.max(axis=1, keepdims=True) * train[:, None]
+            if not all_rows:
+                assert np.all(got[~train] == 0)
+                got, want = got[train], want[train]
+        assert np.allclose(got, want, rtol=2e-5, atol=2e-6), k
+        assert np.allclose(m.var_reference(k, True), om.var(k, True).reshape(shp), rtol=2e-4, atol=1e-7), ("grad", k)
+    for k in (2, 5):
+        assert np.allclose(m.var(k).reshape(-1), om.var(k), rtol=1e-5, atol=1e-6)
+    m.close(); om.close()
+
+
+def test_predict_and_evaluate_on_the_trained_model(oracle, ds):
+    from cuda_gcn_amd.model import HipGCNModel
+    from tests.test_predict_gpu import clear_rows, cpu_eval_logits, log_softmax
+    m = HipGCNModel(ds, seed=3, hidden_dim=16, dropout=0.5)
+    for _ in range(15):
+        m.train_epoch()
+    z = cpu_eval_logits(oracle, ds, m.var(2), m.var(5)).reshape(ds["num_nodes"], -1)
+    tol = 1e-4 * max(1.0, float(np.abs(z).max()))
+    ok = clear_rows(z, tol)
+    assert ok.mean() > 0.9
+    pred, prob, logp = m.predict(logp=True)
+    assert np.array_equal(pred[ok], np.argmax(z, axis=1)[ok])
+    lz = log_softmax(z)
+    assert np.allclose(logp, lz, rtol=0, atol=tol) and np.allclose(prob[ok], np.exp(lz.max(axis=1))[ok], rtol=0, atol=1e-5)
+    for s in (1, 2, 3):
+        rows = ds["split"] == s
+        rep = m.evaluate(split=s)
+        conf = np.zeros((ds["output_dim"],) * 2, np.int64)
+        np.add.at(conf, (ds["label"][rows], pred[rows]), 1)
+        assert rep["rows"] == int(rows.sum()) and rep["unlabelled"] == 0 and np.array_equal(rep["confusion"], conf)
+        unclear = int((~ok[rows]).sum())
+        assert abs(int(np.trace(conf)) - int((np.argmax(z, axis=1)[rows] == ds["label"][rows]).sum())) <= unclear
+        assert abs(rep["accuracy"] - m.eval(s)[1]) <= 1e-6
+    m.close()
+
+
+@pytest.mark.parametrize("world,dropout,flags", [(2, 0.0, "OVERLAP_EXCHANGE"), (3, 0.0, "OVERLAP_EXCHANGE|EXCHANGE_HALO"), (3, 0.0, "0"),
+                                                 (2, 0.0, "STRUCTURE_PARTITION"), (3, 0.5, "HOST_MASKS|OVERLAP_EXCHANGE"),
+                                                 (2, 0.5, "HOST_MASKS|EXCHANGE_ALLGATHER")])
+def test_logical_ranks_match_the_single_rank_trace(oracle, ds, world, dropout, flags):
+    """two and three logical ranks as threads (tests/mr_threads.py): row blocks of a NON-symmetric adjacency, all-gather and
+    halo plans, the cut operators of the overlapped exchange, node renumbering — under test_logical_ranks_as_threads_match_
+    single_gpu's bounds against the single-rank model, and check_trace against the oracle (dropout 0: the model is invariant
+    under renumbering; 0.5: HOST_MASKS keeps the dataset order)"""
+    from cuda_gcn_amd.model import HipGCNModel
+    from tests.mr_threads import run_ranks
+    epochs, hidden = 10, 16
+    f = model_flags(flags)
+    got = run_ranks(ds, world, f, epochs, hidden, dropout, seed=5)
+    for tr in got["traces"][1:]:
+        assert np.array_equal(tr, got["traces"][0])
+    m = HipGCNModel(ds, seed=5, flags=f & (1 | 2), hidden_dim=hidden, dropout=dropout, epochs=epochs)
+    want = np.array([m.train_epoch() + m.eval(2) for _ in range(epochs)], np.float32)
+    wtest = m.eval(3)
+    assert np.abs(got["trace"][:, [0, 2]] - want[:, [0, 2]]).max() <= 2e-4, np.abs(got["trace"] - want).max(axis=0)
+    n_scored = max(1, int((ds["split"] == 2).sum()))
+    assert np.abs(got["trace"][:, [1, 3]] - want[:, [1, 3]]).max() <= max(0.005, 2.0 / n_scored)
+    assert np.abs(got["test"] - np.array(wtest, np.float32)).max() <= 2e-4
+    dh = np.abs(got["h1"] - m.var(3))
+    assert np.median(dh) <= 1e-5 and np.quantile(dh, 0.999) <= 1e-3 * max(1.0, float(np.abs(m.var(3)).max())), (np.median(dh), dh.max())
+    m.close()
+    owant, _ = shared_oracle_trace(oracle, ds, 5, 20, hidden, dropout)
+    check_trace(got["trace"], owant, ds)
+
+
+def test_cli_on_text_files_beside_gcn_seq(ds):
+    """`gcn-hip irr` beside `gcn-seq irr` on the text files datagen.write_text makes of the irregular dataset (the files
+    test_irregular_cpu round-trips): the reference's decisions replayed, test_cli_gpu's comparison"""
+    from tests.test_cli_gpu import HIP, SEQ, compare, run_cli, total_and_test
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "gcn-seq"], check=True)
+    args = ["irr", "-", "-", "16", "-", "0.5", "-", "-", "20"]
+    with tempfile.TemporaryDirectory() as td:
+        datagen.write_text(ds, os.path.join(td, "data"), "irr")
+        la, ea, _ = run_cli(HIP, td, args, GCN_SEED="3", GCN_HOST_MASKS="1")
+        lb, eb, _ = run_cli(SEQ, td, args, GCN_SEED="3")
+    assert "Parse Split Succeeded." in la and "RUNNING ON GPU" in la and "RUNNING ON CPU" in lb
+    assert len(ea) == 20
+    compare(ea, eb, ds)
+    _, xa = total_and_test(la)
+    _, xb = total_and_test(lb)
+    assert abs(xa["test_loss"] - xb["test_loss"]) <= 2e-3 + 1e-5 and abs(xa["test_acc"] - xb["test_acc"]) <= 2.0 / int((ds["split"] == 3).sum()) + 1e-5
