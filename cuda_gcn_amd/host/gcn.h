@@ -8,6 +8,7 @@
 #include <utility>
 #include <vector>
 #include "comm.h"
+#include "device_arena.h"
 #include "module.h"
 #include "optim.h"
 #include "partition.h"
@@ -118,6 +119,17 @@ struct HipGCNOptions {
     static HipGCNOptions from_environment(HipGCNOptions base);
 };
 
+// Which split a pass scores: what set_truth (gcn.cpp:78-81) switches, as one value.  The loss module and the class-width
+// aggregation hold pointers to the fields; the training context has one, the validation lane its own.
+struct ScoredSplit {
+    int32_t *truth = nullptr;                                  // d_truth of the split
+    int count = 0;                                             // its labelled rows, all ranks
+    float wsum = 0.f;                                          // single-label class weights: sum of w[label] over it, all ranks
+    gcnhip_rowset *out_rows = nullptr;                         // its rows of the adjacency (all the loss reads); NULL with HIPGCN_ALL_ROWS
+    gcnhip_rowset *out_rows_loc = nullptr, *out_rows_rem = nullptr;   // HIPGCN_OVERLAP_EXCHANGE: the same on the two halves of the cut
+    int32_t *rows = nullptr; int rows_n = 0;                   // its local row ids, ascending (the loss walks only these)
+};
+
 class HipGCN {
 public:
     GCNParams params;
@@ -222,6 +234,7 @@ private:
     const char *node_order_name_ = "ids";
     void renumber_nodes(int world);
     HipEnv env;
+    DeviceArena arena;                                         // every device buffer of the training context that no other object owns
     std::unique_ptr<Comm> owned_comm;
     std::unique_ptr<DeviceTimers> timers;
     RowPartition part;
@@ -271,7 +284,8 @@ private:
     float *d_result = nullptr;
     int32_t *d_result_i = nullptr;
     int32_t *d_truth[4] = {};                                  // per split code 1..3
-    int32_t *cur_truth = nullptr;
+    ScoredSplit scored;                                        // follows set_truth
+    void fill_scored(ScoredSplit &d, int s, gcnhip_rowset *const *rows) const;
     uint32_t *d_ml_truth = nullptr;                            // multi-label: this rank's rows of GCNData::multihot
     int ml_wpr = 0;
     float *d_ml_logits = nullptr;                              // predict_multilabel: scratch logits [local rows x ld of Z]
@@ -284,6 +298,7 @@ private:
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
     void forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect);
     float *ml_logits_scratch();
+    void pred_scratch();                                       // d_pred / d_prob, on first use
     // evaluate(): the counts on the device (also the float limbs of their all-reduce), an uploaded row list, every local label
     int32_t *d_eval_counts = nullptr, *d_eval_rows = nullptr, *d_label_all = nullptr;
     size_t eval_rows_cap = 0;
@@ -292,7 +307,6 @@ private:
     // subsets of the last aggregation on both halves, and the exchange stream
     gcnhip_graph *graph_loc = nullptr, *graph_rem = nullptr, *graph_bwd_loc = nullptr, *graph_bwd_rem = nullptr;
     gcnhip_rowset *split_rows_loc[4] = {}, *split_rows_rem[4] = {};
-    gcnhip_rowset *cur_out_rows_loc = nullptr, *cur_out_rows_rem = nullptr;
     std::unique_ptr<ExchangeLane> xlane;
     void build_overlap();
     void wire_overlap(HipGraphSum *gs, bool output_layer);
@@ -300,16 +314,11 @@ private:
     uint32_t *d_train_bits = nullptr;                          // bit per (padded) node: in the training split
     const uint32_t *bwd_bits = nullptr;
     gcnhip_rowset *split_rows[4] = {};                         // rows of `graph` whose node is in split s (all the loss reads); owned by graph
-    gcnhip_rowset *cur_out_rows = nullptr;                     // follows set_truth; NULL with HIPGCN_ALL_ROWS
     int32_t *d_split_list[4] = {};                             // local row ids of split s, ascending (the loss walks only these)
     int split_local_n[4] = {};
-    int32_t *cur_rows = nullptr;
-    int cur_rows_n = 0;
     int split_count[4] = {};
-    int cur_count = 0;
     float *d_class_w = nullptr;                                // class weights [C] (HipGCNOptions::class_weights), else NULL
     float split_wsum[4] = {};                                  // single-label: sum of w[label] over split s, all ranks (the weighted gradient's divisor)
-    float cur_wsum = 0.f;                                      // follows set_truth
     float *d_ring = nullptr;
     static constexpr int RING = 1024;
     uint8_t *d_keep0 = nullptr, *d_keep1 = nullptr;
@@ -318,6 +327,9 @@ private:
     long epochs_done = 0;                                      // training passes enqueued = *env.d_epoch once their Adam launches have run
     void *epoch_graph = nullptr;                               // captured train_epoch + eval(2)
     bool enqueue_epoch_replay();                               // one epoch from the captured hipGraph (captures it on first use); false: not replayable
+    bool zipped() const { return lane && !(timers->enabled && env.comm->size() == 1); }   // validation on the lane, beside the next training pass
+    void enqueue_epoch(bool first, bool last);
+    void print_line(long epoch, std::pair<float, float> train, std::pair<float, float> scored_now, float dt) const;
     // run(): read-back of an epoch's metrics row without stalling the producer streams
     static constexpr int PIPELINE_DEPTH = 4;                   // read-back groups in flight
     static constexpr int READBACK_GROUP_MAX = 64;              // epochs per read-back group, at most (RING is a multiple)
@@ -342,6 +354,7 @@ private:
     // communicator / activation buffers lets one lane compute while the other communicates.
     struct EvalLane {
         HipEnv env;
+        DeviceArena arena;                                     // on the lane's context
         ExchangeBuffers xbuf;
         std::unique_ptr<Comm> comm;
         std::unique_ptr<DeviceTimers> timers;
@@ -351,13 +364,8 @@ private:
         std::vector<Module *> modules;
         float *d_result = nullptr;
         int32_t *d_result_i = nullptr;
-        int32_t *truth = nullptr;
         gcnhip_rowset *split_rows[4] = {};                     // the lane has its own adjacency object
-        gcnhip_rowset *out_rows = nullptr;
-        int32_t *rows = nullptr;
-        int rows_n = 0;
-        int count = 0;
-        float wsum = 0.f;                                      // split_wsum of the lane's split
+        ScoredSplit scored;
         void *ev_weights = nullptr, *ev_done = nullptr;        // Adam(e) -> eval(e);  eval(e) -> Adam(e+1)
         void *ev_fork = nullptr;                               // one GPU: training GEMM done -> the validation pass may start
         bool pending = false;
@@ -374,6 +382,10 @@ private:
     void eval_then_train_zipped(int current_split);
     void train_begin();
     void train_end();
+    void refresh_input();
+    void metrics_before(HipEnv &e, int slot, const uint32_t *epoch_word);
+    void metrics_after(HipEnv &e, DeviceTimers &t, int slot, const uint32_t *epoch_word, float *result, size_t n);
+    gcnhip_graph *create_rows_graph(gcnhip_ctx *ctx);          // this rank's rows of the adjacency, GLOBAL column ids, width reserved
 
     // row schedule of the aggregation (gcnhip_graph_set_schedule): candidates timed once, fastest kept
     int sched_mode = 0, sched_groups = 0, slice_floats = 64;
@@ -389,11 +401,7 @@ private:
     struct LossSite {
         HipEnv *env;
         HipVariable *Z;                         // the logits
-        int32_t *const *truth;
-        const int *count;
-        const float *wsum;
-        int32_t *const *rows;
-        const int *rows_n;
+        const ScoredSplit *split;               // what the loss scores: the fields are read at every forward
         float *d_result;
         int32_t *d_result_i;
         bool shift_in_place;

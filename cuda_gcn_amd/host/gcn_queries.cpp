@@ -1,0 +1,276 @@
+// gcn_queries.cpp — what a caller asks of a built HipGCN between passes: variables and weights, prediction, per-class
+// evaluation, the weights file.
+#include "gcn.h"
+#include "weights.h"
+#include "hip_check.h"
+
+void HipGCN::row_scale(std::vector<float> &dinv) {
+    dinv.assign((size_t)n_local, 1.f);
+    const float *d = nullptr;
+    GCNHIP_CHECK(gcnhip_graph_scales(graph, &d, nullptr, nullptr, nullptr));
+    if (n_local) GCNHIP_CHECK(gcnhip_d2h(env.ctx, dinv.data(), d, dinv.size() * sizeof(float)));
+}
+
+void HipGCN::get_var(int k, bool grad, std::vector<float> &out, int *rows, int *cols) {
+    if (k < 1 || k > 6) throw GcnHipFailure(-1, "get_var: k must be 1..6");
+    HipVariable *v = variables[k].get();
+    if (k == 3 && !grad && h1_from_fused_eval && !eval_modules.empty()) {
+        // the last forward on this stream was an evaluation whose hidden matrix stayed in registers: run it as its own launch
+        static_cast<HipSparseMatmul *>(eval_modules[0])->forward_stored();
+        h1_from_fused_eval = false;
+        sync();
+    }
+    out.resize((size_t)v->rows * v->cols);
+    v->download(out.data(), grad);
+    if (rows) *rows = v->rows;
+    if (cols) *cols = v->cols;
+}
+
+void HipGCN::set_weights(const float *w1, const float *w2) {
+    variables[2]->upload(w1);
+    variables[5]->upload(w2);
+    GCNHIP_CHECK(gcnhip_sumsq(env.ctx, variables[2]->data, (int64_t)variables[2]->elems(), optimizer->d_sumsq));
+    sync();
+}
+
+// ---- prediction and the weights file (beyond the reference) ------------------------------------------------------------
+
+// dataset node ids -> local rows of this rank (node_order() undone); NULL: every local row
+void HipGCN::query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows) {
+    const int N = params.num_nodes;
+    rows.resize(n);
+    if (!nodes) {
+        for (int i = 0; i < n; i++) rows[i] = i;
+        return;
+    }
+    std::vector<int> pos;
+    if (!node_order_.empty()) {
+        pos.assign(N, -1);
+        for (int p = 0; p < N; p++) pos[node_order_[p]] = p;
+    }
+    const int r0 = row_start();
+    for (int i = 0; i < n; i++) {
+        const int id = nodes[i];
+        if (id < 0 || id >= N) throw GcnHipFailure(-1, std::string(what) + ": node " + std::to_string(id) + " is not a node of the dataset (0.." + std::to_string(N - 1) + ")");
+        const int r = (pos.empty() ? id : pos[id]) - r0;
+        if (r < 0 || r >= n_local)
+            throw GcnHipFailure(-1, std::string(what) + ": node " + std::to_string(id) + " is not a row of rank " + std::to_string(env.comm->rank()) + " (each rank predicts its own rows)");
+        rows[i] = r;
+    }
+}
+
+// a registered subset of `graph` holding these rows: the same query reuses it
+const gcnhip_rowset *HipGCN::query_subset(const std::vector<int> &rows) {
+    std::vector<uint32_t> bits(((size_t)n_local + 31) / 32 + 1, 0u);
+    for (int r : rows) bits[r >> 5] |= 1u << (r & 31);
+    if (!pred_rows || bits != pred_bits) {
+        if (pred_rows) { GCNHIP_CHECK(gcnhip_graph_remove_rowset(env.ctx, graph, pred_rows)); pred_rows = nullptr; }
+        GCNHIP_CHECK(gcnhip_graph_add_rowset(env.ctx, graph, bits.data(), &pred_rows));
+        pred_bits.swap(bits);
+    }
+    return pred_rows;
+}
+
+// An evaluation forward (eval_async's module list without the loss) on the main stream with one hook set on the logit
+// aggregation: the prediction epilogue, or the logits redirected to a scratch table.  Training state stays as it was.
+void HipGCN::forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect) {
+    refresh_input();
+    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
+    struct Unhook {                                            // also when a forward throws
+        HipGraphSum *gs;
+        ~Unhook() { gs->predict = nullptr; gs->redirect = nullptr; }
+    } unhook{logits_gs};
+    logits_gs->predict = prediction;
+    logits_gs->redirect = redirect;
+    for (size_t i = 0; i + 1 < list.size(); i++) list[i]->forward(false);           // the last module is the loss
+    // variable 3: a fused evaluation keeps H1 in registers (what it held stays); otherwise the forward stored it
+    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+}
+
+// scratch logits of the multi-label prediction and evaluation [local rows x ld of Z], zeroed once
+float *HipGCN::ml_logits_scratch() {
+    if (!d_ml_logits) d_ml_logits = arena.alloc_zeroed<float>((size_t)std::max(n_local, 1) * variables[6]->ld);
+    return d_ml_logits;
+}
+
+// predicted class and its probability per local row (predict, evaluate), on first use
+void HipGCN::pred_scratch() {
+    if (d_pred) return;
+    const size_t nl = (size_t)std::max(n_local, 1);
+    d_pred = arena.alloc<int32_t>(nl);
+    d_prob = arena.alloc<float>(nl);
+}
+
+void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
+    const int C = params.output_dim;
+    if (opt_.multilabel) throw GcnHipFailure(-1, "predict: this is a multi-label model: use predict_multilabel");
+    if (!logits_gs) throw GcnHipFailure(-1, "predict: this model has no class-width aggregation");
+    if (C > 64) throw GcnHipFailure(-1, "predict: at most 64 classes (the logit row of a node sits in one wave)");
+    if ((n > 0 && (!pred || !prob)) || n < 0) throw GcnHipFailure(-1, "predict: invalid argument");
+    if (!nodes) n = n_local;
+    std::vector<int> rows;
+    query_rows("predict", nodes, n, rows);
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
+    const size_t nl = (size_t)std::max(n_local, 1);
+    pred_scratch();
+    if (logp && !d_logp) d_logp = arena.alloc<float>(nl * C);
+    // the logit aggregation runs the prediction epilogue instead of its usual launch and stores no logits
+    HipGraphSum::Prediction req;
+    req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = logp ? d_logp : nullptr; req.ld_logp = C;
+    forward_hooked(&req, nullptr);
+    if (n == 0) { sync(); return; }
+    std::vector<int32_t> hp(nl);
+    std::vector<float> hq(nl), hl;
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, hp.data(), d_pred, nl * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, hq.data(), d_prob, nl * sizeof(float)));
+    if (logp) {
+        hl.resize(nl * C);
+        GCNHIP_CHECK(gcnhip_d2h(env.ctx, hl.data(), d_logp, nl * C * sizeof(float)));
+    }
+    for (int i = 0; i < n; i++) {
+        pred[i] = hp[rows[i]];
+        prob[i] = hq[rows[i]];
+        if (logp) std::copy(hl.begin() + (size_t)rows[i] * C, hl.begin() + (size_t)(rows[i] + 1) * C, logp + (size_t)i * C);
+    }
+}
+
+void HipGCN::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob) {
+    const int C = params.output_dim;
+    if (!opt_.multilabel) throw GcnHipFailure(-1, "predict_multilabel: this is a single-label model: use predict");
+    if (!logits_gs) throw GcnHipFailure(-1, "predict_multilabel: this model has no class-width aggregation");
+    if ((n > 0 && !bits) || n < 0) throw GcnHipFailure(-1, "predict_multilabel: invalid argument");
+    if (!nodes) n = n_local;
+    std::vector<int> rows;
+    query_rows("predict_multilabel", nodes, n, rows);
+    sync();
+    const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
+    HipVariable *Z = variables[6].get();
+    const size_t nq = (size_t)std::max(n, 1);
+    ml_logits_scratch();
+    if (nq > ml_query_cap) {
+        ml_query_cap = 0;                                      // (a regrow that throws leaves NULL behind: nothing is sized until all three exist)
+        arena.regrow(d_ml_bits, nq * ml_wpr);
+        arena.regrow(d_ml_prob, nq * C);
+        arena.regrow(d_ml_rows, nq);
+        ml_query_cap = nq;
+    }
+    // the logit aggregation stores the requested rows into the scratch table instead of variable 6
+    HipGraphSum::Redirect req;
+    req.data = d_ml_logits; req.ld = Z->ld; req.rows = subset;
+    forward_hooked(nullptr, &req);
+    if (n == 0) { sync(); return; }
+    GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_ml_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_bce_predict_rows(env.ctx, d_ml_logits, Z->ld, d_ml_rows, n, C, d_ml_bits, ml_wpr, prob ? d_ml_prob : nullptr, C));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, bits, d_ml_bits, (size_t)n * ml_wpr * sizeof(uint32_t)));
+    if (prob) GCNHIP_CHECK(gcnhip_d2h(env.ctx, prob, d_ml_prob, (size_t)n * C * sizeof(float)));
+}
+
+void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
+    const int C = params.output_dim;
+    const bool ml = opt_.multilabel;
+    if (!logits_gs) throw GcnHipFailure(-1, "evaluate: this model has no class-width aggregation");
+    if (!ml && C > 64) throw GcnHipFailure(-1, "evaluate: at most 64 classes on a single-label model (the logit row of a node sits in one wave)");
+    if (ml && C > 256) throw GcnHipFailure(-1, "evaluate: at most 256 classes on a multi-label model");
+    if (split < 0 || split > 3 || !counts || n < 0) throw GcnHipFailure(-1, "evaluate: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
+    // the rows to score: the split's list (already on the device on the fused path), or the query
+    std::vector<int> rows;
+    const int32_t *d_list = nullptr;
+    bool upload = false;
+    if (split) {
+        if (d_split_list[split]) {
+            d_list = d_split_list[split];
+            n = split_local_n[split];
+        } else {
+            const int r0 = row_start();
+            for (int r = 0; r < n_local; r++)
+                if (data->split[r0 + r] == split) rows.push_back(r);
+            n = (int)rows.size();
+            upload = true;
+        }
+    } else {
+        if (!nodes) n = n_local;
+        query_rows("evaluate", nodes, n, rows);
+        upload = nodes != nullptr;                             // NULL: rows 0 .. n_local - 1, no list
+    }
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    const gcnhip_rowset *subset = split ? split_rows[split] : (nodes ? query_subset(rows) : nullptr);
+    const int m = ml ? 3 * C : C * C + 1;                      // all that crosses to the host
+    if (!d_eval_counts)                                        // ... or its two float limbs each, plus the listed rows' (below)
+        d_eval_counts = arena.alloc<int32_t>(((size_t)std::max(3 * C, C * C + 1) + 1) * 2);
+    if (upload && (size_t)std::max(n, 1) > eval_rows_cap) {
+        eval_rows_cap = 0;
+        arena.regrow(d_eval_rows, (size_t)std::max(n, 1));
+        eval_rows_cap = (size_t)std::max(n, 1);
+    }
+    if (upload) {
+        if (n) GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_eval_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+        d_list = d_eval_rows;
+    }
+    if (ml) {
+        HipVariable *Z = variables[6].get();
+        HipGraphSum::Redirect req;
+        req.data = ml_logits_scratch(); req.ld = Z->ld; req.rows = subset;
+        forward_hooked(nullptr, &req);
+        GCNHIP_CHECK(gcnhip_bce_class_counts_rows(env.ctx, d_ml_logits, Z->ld, d_ml_truth, ml_wpr, d_list, n, C, d_eval_counts));
+    } else {
+        pred_scratch();
+        const int32_t *truth = d_truth[split];
+        if (!split) {                                          // a query is scored against the labels themselves
+            if (!d_label_all) {
+                std::vector<int32_t> lab(data->label.begin() + row_start(), data->label.begin() + row_start() + n_local);
+                if (lab.empty()) lab.assign(1, -1);
+                d_label_all = arena.upload(lab.data(), lab.size());
+            }
+            truth = d_label_all;
+        }
+        HipGraphSum::Prediction req;
+        req.rows = subset; req.pred = d_pred; req.prob = d_prob;
+        forward_hooked(&req, nullptr);
+        GCNHIP_CHECK(gcnhip_confusion_rows(env.ctx, d_pred, truth, n_local, d_list, n, C, d_eval_counts, d_eval_counts + C * C));
+    }
+    std::vector<int32_t> h(m);
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, h.data(), d_eval_counts, (size_t)m * sizeof(int32_t)));
+    std::vector<int64_t> total(h.begin(), h.end());
+    int64_t listed = n;
+    if (world() > 1) {
+        // The counts are additive across ranks, like the four metric floats of an epoch, and go through the same float
+        // all-reduce — as two limbs each, so that the sum is exact: a rank's count is below 2^31, so its high limb (count >> 12)
+        // is below 2^19 and its low limb below 2^12; up to 32 ranks every partial sum of either stays below 2^24, where f32
+        // holds every integer.  (One float per count would round silently from 2^24 rows in a cell.)
+        if (world() > 32) throw GcnHipFailure(-1, "evaluate: the exact sum of the counts is laid out for at most 32 ranks");
+        std::vector<float> limbs(2 * (size_t)(m + 1));
+        for (int i = 0; i <= m; i++) {
+            const int64_t v = i < m ? (int64_t)h[i] : listed;
+            limbs[2 * i] = (float)(v & 4095);
+            limbs[2 * i + 1] = (float)(v >> 12);
+        }
+        float *d_limbs = (float *)d_eval_counts;               // sized for it above; the counts are on the host already
+        GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_limbs, limbs.data(), limbs.size() * sizeof(float)));
+        env.comm->allreduce_sum(d_limbs, limbs.size());
+        GCNHIP_CHECK(gcnhip_d2h(env.ctx, limbs.data(), d_limbs, limbs.size() * sizeof(float)));
+        for (int i = 0; i < m; i++) total[i] = (int64_t)limbs[2 * i + 1] * 4096 + (int64_t)limbs[2 * i];
+        listed = (int64_t)limbs[2 * m + 1] * 4096 + (int64_t)limbs[2 * m];
+    }
+    sync();
+    std::copy(total.begin(), total.begin() + (ml ? 3 * C : C * C), counts);
+    const int64_t no_truth = ml ? 0 : total[C * C];            // single-label: listed rows that are in no cell of the matrix
+    if (rows_counted) *rows_counted = listed - no_truth;
+    if (unlabelled) *unlabelled = no_truth;
+}
+
+void HipGCN::save_weights(const char *path) {
+    std::vector<float> w1, w2;
+    get_var(2, false, w1, nullptr, nullptr);
+    get_var(5, false, w2, nullptr, nullptr);
+    std::string err;
+    if (gcn_weights_write(path, params.input_dim, params.hidden_dim, params.output_dim, w1.data(), w2.data(), &err) != 0) throw GcnHipFailure(-1, err);
+}
+
+void HipGCN::load_weights(const char *path) {
+    int F = params.input_dim, h = params.hidden_dim, C = params.output_dim;
+    std::vector<float> w1((size_t)F * h), w2((size_t)h * C);
+    std::string err;
+    if (gcn_weights_read(path, &F, &h, &C, w1.data(), w2.data(), &err) != 0) throw GcnHipFailure(-1, err);
+    set_weights(w1.data(), w2.data());
+}

@@ -315,7 +315,6 @@ HipCrossEntropyLoss::HipCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32
     : env(env), logits(logits), truth(truth), count(count), d_result(d_result), d_result_i(d_result_i),
       num_classes(num_classes), shift_in_place(shift) {}
 
-HipCrossEntropyLoss::~HipCrossEntropyLoss() { if (row_terms) gcnhip_free(env->ctx, row_terms); }
 
 bool HipCrossEntropyLoss::epilogue_opts(bool training, gcnhip_gs_loss *o) const {
     if (!row_terms || !rows_list || !*rows_list || *count <= 0 || num_classes > 64 || shift_in_place || d_weight) return false;

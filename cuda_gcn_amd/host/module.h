@@ -186,7 +186,7 @@ public:
     // Loss epilogue (round 5, gcnhip_gs_loss): the aggregation that produces `logits` computes each scored row's loss term,
     // accuracy flag and gradient row while the row is still in its wave's registers (HipGraphSum::loss points here and
     // fills epilogue_opts()); forward() then only adds the terms — same bits as the loss kernel on the stored logits.
-    // row_terms: [2 x rows] floats owned by this module (NULL: the loss kernel reads the logits, as before).
+    // row_terms: [2 x rows] floats, borrowed from the model (NULL: the loss kernel reads the logits, as before).
     float *row_terms = nullptr;
     bool terms_fresh = false;                   // the producing launch of this forward wrote row_terms
     bool epilogue_opts(bool training, gcnhip_gs_loss *o) const;   // false: not applicable (no row list, empty split, class weights)
@@ -195,7 +195,6 @@ public:
     // correct, total}; weight_sum points at the current split's sum of w[truth] over ALL ranks (the gradient's divisor).
     const float *d_weight = nullptr;
     const float *weight_sum = nullptr;
-    ~HipCrossEntropyLoss() override;
     HipCrossEntropyLoss(HipEnv *env, HipVariable *logits, int32_t *const *truth, const int *count,
                         float *d_result, int32_t *d_result_i, int num_classes, bool shift_in_place);
     void forward(bool) override;

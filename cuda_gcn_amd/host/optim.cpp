@@ -10,38 +10,25 @@ float HipAdam::step_size(const AdamParams &p, int t) {
 
 void HipAdam::init(HipEnv *e, std::vector<std::pair<HipVariable *, bool>> vs, AdamParams p, int max_steps) {
     env = e; params = p; step_count = 0;
+    arena.bind(env->ctx);
     for (auto &pr : vs) {
         HipVariable *v = pr.first;
         gcnhip_adam_var av;
         av.w = v->data; av.g = v->grad; av.n = (int64_t)v->elems(); av.decay = pr.second ? 1 : 0;
-        void *m, *vv;
-        GCNHIP_CHECK(gcnhip_malloc(env->ctx, &m, v->elems() * sizeof(float)));
-        GCNHIP_CHECK(gcnhip_malloc(env->ctx, &vv, v->elems() * sizeof(float)));
-        GCNHIP_CHECK(gcnhip_memset_async(env->ctx, m, 0, v->elems() * sizeof(float)));
-        GCNHIP_CHECK(gcnhip_memset_async(env->ctx, vv, 0, v->elems() * sizeof(float)));
-        av.m = (float *)m; av.v = (float *)vv;
-        state.push_back(av.m); state.push_back(av.v);
+        av.m = arena.alloc_zeroed<float>(v->elems());
+        av.v = arena.alloc_zeroed<float>(v->elems());
         vars.push_back(av);
     }
-    void *q;
-    GCNHIP_CHECK(gcnhip_malloc(env->ctx, &q, sizeof(float)));
-    d_sumsq = (float *)q;
+    d_sumsq = arena.alloc<float>(1);
     // sum(w0^2) of the initial weights, for the loss reported before the first update
     GCNHIP_CHECK(gcnhip_sumsq(env->ctx, vars[0].w, vars[0].n, d_sumsq));
     table_len = max_steps > 0 ? max_steps : 1;
     std::vector<float> tab(table_len);
     for (int t = 1; t <= table_len; t++) tab[t - 1] = step_size(params, t);   // host libm, as the CPU path
-    GCNHIP_CHECK(gcnhip_malloc(env->ctx, &q, table_len * sizeof(float)));
-    d_step_sizes = (float *)q;
-    GCNHIP_CHECK(gcnhip_h2d(env->ctx, d_step_sizes, tab.data(), table_len * sizeof(float)));
+    d_step_sizes = arena.upload(tab.data(), tab.size());
 }
 
-HipAdam::~HipAdam() {
-    if (!env) return;
-    for (float *p : state) gcnhip_free(env->ctx, p);
-    gcnhip_free(env->ctx, d_sumsq);
-    gcnhip_free(env->ctx, d_step_sizes);
-}
+HipAdam::~HipAdam() { arena.free_all(); }
 
 void HipAdam::step() {
     step_count++;

@@ -3,6 +3,7 @@
 #pragma once
 #include <utility>
 #include <vector>
+#include "device_arena.h"
 #include "module.h"
 
 struct AdamParams {
@@ -15,7 +16,7 @@ class HipAdam {
     AdamParams params;
     int step_count = 0;
     std::vector<gcnhip_adam_var> vars;
-    std::vector<float *> state;             // m, v buffers (owned)
+    DeviceArena arena;                      // m, v buffers, the step-size table, d_sumsq
     float *d_step_sizes = nullptr;          // step size of step t at [t-1] (device table for graph replay)
     int table_len = 0;
 public:
