@@ -104,6 +104,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_graphsum_relu_dropout_bits": (I, [P, P, P, I, P, I, I, I, F, U64, P, U64, P, P, I]),
     "gcnhip_graphsum_ex": (I, [P, P, P, P, I, P, I, I]),
     "gcnhip_graphsum_predict": (I, [P, P, P, P, P, I, P, I, I, I, P, P, P, I]),
+    "gcnhip_graphsum_blend": (I, [P, P, P, I, P, I, P, I, I, F, F, F, F, P]),
+    "gcnhip_cs_error_rows": (I, [P, P, I, P, I, P, I, I, P, I, P]),
+    "gcnhip_cs_correct_rows": (I, [P, P, I, P, I, P, I, I, P, P, I]),
     "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
@@ -217,6 +220,9 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_predict": (I, [P, P, I, P, P, P]),
     "gcnhost_model_predict_multilabel": (I, [P, P, I, P, P]),
     "gcnhost_model_evaluate": (I, [P, I, P, I, P, C.POINTER(I64), C.POINTER(I64)]),
+    "gcnhost_model_propagate": (I, [P, P, I, F, I, F, F, P, P]),
+    "gcnhost_model_label_propagation": (I, [P, F, I, I, P, P]),
+    "gcnhost_model_correct_and_smooth": (I, [P, F, I, F, I, I, P, P]),
     "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),
     "gcnhost_model_save_weights": (I, [P, C.c_char_p]),

@@ -843,6 +843,122 @@ __global__ __launch_bounds__(256) void graphsum_finalize_predict_kernel(GsArgs a
     predict_row_epilogue1(a, p, row, v, col);
 }
 
+// ---- blend epilogue (gcnhip_graphsum_blend) -------------------------------------------------------------------------
+// One step of label propagation / Correct & Smooth:  out[r, :] = clamp(alpha * (A^ . in)[r, :] + beta * base[r, :], lo, hi),
+// optionally pred[r] = argmax of that row (the lowest column on a tie).  The gather is graphsum_predict_vec_kernel's — same
+// task list, lane groups, edge order, reduction tree and split-row scratch — with another epilogue; kept apart so that no
+// existing kernel changes.  The operator is taken UNFACTORED (per-edge coefficients, g->coef): at class width the 4-byte
+// coefficient rides beside a 192-byte gathered row, and staying unscaled keeps the iterate in one form — the table a launch
+// writes is the table the next one gathers, with no dinv-scaled copy to maintain between iterations.
+struct BlendArgs {
+    const float *base;      // [n_rows x ld_base]; may be the gathered table itself
+    int ld_base;
+    float alpha, beta, lo, hi;
+    int32_t *pred;          // NULL, or [n_rows]
+};
+
+__device__ __forceinline__ float blend1(const BlendArgs &b, float sum, float base) {
+#pragma clang fp contract(off)
+    return fminf(fmaxf(b.alpha * sum + b.beta * base, b.lo), b.hi);
+}
+
+template <int L, int U>
+__global__ __launch_bounds__(256) void graphsum_blend_vec_kernel(GsArgs a, BlendArgs b) {
+    const int lane = threadIdx.x & 63;
+    int t;
+    {
+        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if (t >= a.bounds[xcd + 1]) return;                // wave-uniform
+    }
+    int row, e0, e1, slot;
+    if (a.n_tasks) {
+        const int4 tk = a.tasks[t];
+        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
+    } else {
+        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
+    }
+    const int g = lane / L, l = lane % L;
+    const int col0 = l * 4;
+    const bool active = col0 < a.dim;
+    const float *in = a.in + (active ? col0 : 0);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = e0; base < e1; base += WAVE) {
+        const int cnt = min(WAVE, e1 - base);
+        int my_idx = 0;
+        float my_c = 0.f;
+        if (lane < cnt) {
+            my_idx = a.indices[base + lane];
+            my_c = a.coef[base + lane];
+        }
+        acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
+    }
+#pragma unroll
+    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
+    if (slot >= 0) {                                        // the finalize launch adds the segments and blends
+        if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+        return;
+    }
+    float x[4] = {acc.x, acc.y, acc.z, acc.w};
+    float bv = -INFINITY;
+    int bi = 0x7FFFFFFF;
+    if (g == 0 && active) {
+        const float *bp = b.base + (size_t)row * b.ld_base + col0;
+        float *o = a.out + (size_t)row * a.ld_out + col0;
+        if (col0 + 4 <= a.dim) {
+            const float4 bb = *reinterpret_cast<const float4 *>(bp);
+            x[0] = blend1(b, x[0], bb.x); x[1] = blend1(b, x[1], bb.y); x[2] = blend1(b, x[2], bb.z); x[3] = blend1(b, x[3], bb.w);
+            *reinterpret_cast<float4 *>(o) = make_float4(x[0], x[1], x[2], x[3]);
+        } else {                                           // ragged tail: the padding of base is not read, that of out not written
+            for (int i = 0; col0 + i < a.dim; i++) { x[i] = blend1(b, x[i], bp[i]); o[i] = x[i]; }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (col0 + i < a.dim && (bi == 0x7FFFFFFF || x[i] > bv)) { bv = x[i]; bi = col0 + i; }
+    }
+    if (b.pred) {                                           // wave-uniform; lanes 0 .. L-1 are group 0
+#pragma unroll
+        for (int m = 1; m < L; m <<= 1) argmax_merge(bv, bi, __shfl_xor(bv, m, WAVE), __shfl_xor(bi, m, WAVE));
+        if (lane == 0) b.pred[row] = bi;
+    }
+}
+
+// graphsum_finalize_predict_kernel's segment sum (one wave per split row, lane c on column c) with the blend epilogue
+__global__ __launch_bounds__(64) void graphsum_finalize_blend_kernel(GsArgs a, BlendArgs b, const int4 *split_rows, int n_split_rows) {
+    const int s = blockIdx.x;
+    if (s >= n_split_rows || threadIdx.x >= WAVE) return;
+    const int4 sr = split_rows[s];
+    const int row = sr.x, first = sr.y, ns = sr.z;
+    const int col = threadIdx.x;
+    const bool in_row = col < a.dim;
+    float v = 0.f;
+    if (in_row) {
+        const float *pp = a.partials + (size_t)first * a.part_ld + col;
+        int k = 0;
+        for (; k + 4 <= ns; k += 4) {
+            const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
+            const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
+            v += p0; v += p1; v += p2; v += p3;
+        }
+        for (; k < ns; k++) v += pp[(size_t)k * a.part_ld];
+        v = blend1(b, v, b.base[(size_t)row * b.ld_base + col]);
+        a.out[(size_t)row * a.ld_out + col] = v;
+    }
+    if (b.pred) {
+        float bv = in_row ? v : -INFINITY;
+        int bi = in_row ? col : 0x7FFFFFFF;
+#pragma unroll
+        for (int m = 1; m < WAVE; m <<= 1) argmax_merge(bv, bi, __shfl_xor(bv, m, WAVE), __shfl_xor(bi, m, WAVE));
+        if (col == 0) b.pred[row] = bi;
+    }
+}
+
+template <int L>
+static void launch_blend(const GsArgs &a, const BlendArgs &b, int blocks, int u, hipStream_t s) {
+    if (u >= 4) graphsum_blend_vec_kernel<L, 4><<<blocks, 256, 0, s>>>(a, b);
+    else graphsum_blend_vec_kernel<L, 2><<<blocks, 256, 0, s>>>(a, b);
+}
+
 template <int L>
 static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c, const PredArgs *pred = nullptr) {
     hipStream_t s = c->stream;
@@ -1057,6 +1173,42 @@ int gcnhip_graphsum_predict(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_r
     // (no logits stored: a stride that passes the 16-byte row test; nothing is written through it)
     return graphsum_impl(c, g, in, ld_in, out, out ? ld_out : (dim + 3) / 4 * 4, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, in_bf16, nullptr, rows, 0,
                          nullptr, 0, scaling, nullptr, &pa);
+}
+
+int gcnhip_graphsum_blend(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in, const float *base, int ld_base,
+                          float *out, int ld_out, int dim, float alpha, float beta, float lo, float hi, int32_t *pred) {
+    if (!c || !g || !in || !base || !out) return gcnhip_fail("gcnhip_graphsum_blend: null argument");
+    if (dim < 1 || dim > 64) return gcnhip_fail("gcnhip_graphsum_blend: 1 <= dim <= 64 (the row of a node sits in one lane group)");
+    if (ld_in < dim || ld_base < dim || ld_out < dim || ld_in % 4 || ld_base % 4 || ld_out % 4 || !aligned16(in) || !aligned16(base) || !aligned16(out))
+        return gcnhip_fail("gcnhip_graphsum_blend: needs f32 rows that are 16-byte aligned (ld % 4 == 0, ld >= dim)");
+    if (out == in) return gcnhip_fail("gcnhip_graphsum_blend: out must not be in (other rows are still gathering it); base may be");
+    if (g->n_rows == 0) return 0;
+    if (g->n_slots && g->part_ld < (dim + 7) / 8 * 8)
+        return gcnhip_fail("gcnhip_graphsum_blend: dim is wider than the split-row scratch of this adjacency object; call gcnhip_graph_reserve_width");
+    GsArgs a = {};
+    a.indptr = g->indptr; a.indices = g->indices; a.coef = g->coef;
+    a.tasks = g->tasks; a.n_tasks = g->n_tasks; a.n_rows = g->n_rows; a.nnz = g->nnz;
+    a.table_bytes = (size_t)g->n_cols * ld_in * 4;
+    a.in = in; a.out = out; a.partials = g->partials;
+    a.ld_in = ld_in; a.ld_out = ld_out; a.part_ld = g->part_ld; a.dim = dim;
+    a.n_slices = 1;
+    int max_blocks = 1;
+    for (int k = 0; k <= 8; k++) a.bounds[k] = g->bounds[3][k];
+    for (int k = 0; k < 8; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
+    const BlendArgs b = {base, ld_base, alpha, beta, lo, hi, pred};
+    const int u = c->opt.gs_u ? c->opt.gs_u : (a.table_bytes > ((size_t)256 << 20) ? 2 : 4);   // launch_vec's rule
+    const int d4 = (dim + 3) / 4, blocks = max_blocks * 8;
+    if (d4 <= 1) launch_blend<1>(a, b, blocks, u, c->stream);
+    else if (d4 <= 2) launch_blend<2>(a, b, blocks, u, c->stream);
+    else if (d4 <= 4) launch_blend<4>(a, b, blocks, u, c->stream);
+    else if (d4 <= 8) launch_blend<8>(a, b, blocks, u, c->stream);
+    else launch_blend<16>(a, b, blocks, u, c->stream);
+    GCNHIP_LAUNCH_CHECK();
+    if (g->n_split_rows) {
+        graphsum_finalize_blend_kernel<<<g->n_split_rows, WAVE, 0, c->stream>>>(a, b, g->split_rows, g->n_split_rows);
+        GCNHIP_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 int gcnhip_f32_to_bf16(gcnhip_ctx *c, const float *src, int ld_src, uint16_t *dst, int ld_dst, int64_t rows, int dim) {

@@ -224,6 +224,19 @@ int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n,
     if (!m || !counts) { g_err = "gcnhost_model_evaluate: invalid argument"; return -1; }
     API_TRY({ m->gcn->evaluate(split, nodes, n, counts, rows_counted, unlabelled); })
 }
+int gcnhost_model_propagate(gcnhost_model *m, const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred) {
+    if (!m || !y0 || !out) { g_err = "gcnhost_model_propagate: invalid argument"; return -1; }
+    API_TRY({ m->gcn->propagate(y0, dim, alpha, iters, lo, hi, out, pred); })
+}
+int gcnhost_model_label_propagation(gcnhost_model *m, float alpha, int iters, int splits_mask, int32_t *pred, float *y) {
+    if (!m || !pred) { g_err = "gcnhost_model_label_propagation: invalid argument"; return -1; }
+    API_TRY({ m->gcn->label_propagation(alpha, iters, splits_mask, pred, y); })
+}
+int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth,
+                                     int splits_mask, int32_t *pred, float *g) {
+    if (!m || !pred) { g_err = "gcnhost_model_correct_and_smooth: invalid argument"; return -1; }
+    API_TRY({ m->gcn->correct_and_smooth(alpha_correct, iters_correct, alpha_smooth, iters_smooth, splits_mask, pred, g); })
+}
 int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
                          int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {
     ClassReport r;

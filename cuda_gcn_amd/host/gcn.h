@@ -213,6 +213,23 @@ public:
     // graph are left as they were; a train_epoch() after it has the same bits as one without it.  Synchronises.  More than
     // 64 (single-label) or 256 (multi-label) classes: an error.  host/report.h derives precision / recall / F1 from the counts.
     void evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+    // Label propagation and Correct & Smooth (beyond the reference; Huang et al., 2020): the graph and the known labels used
+    // at inference time.  Every iteration is one gcnhip_graphsum_blend launch through `graph` with its per-edge coefficients,
+    // ping-ponging two of four [local rows x ld] f32 tables from the arena (allocated on first use; ld by the row rule of
+    // variable 6).  Arrays are in DATASET node order.  predict()'s contract: the call starts with sync(); the metrics ring, the
+    // current split, variable 6 and the captured epoch graph are untouched.  Refused with a message before any launch: more
+    // than one rank (every iteration would need a table exchange), alpha outside [0, 1], iters < 0, a width outside 1..64, and
+    // for the two label schemes a multi-label model or more than 64 classes.  splits_mask: bit s = the labelled nodes of split
+    // s are known (2 = the training split).
+    //   propagate: Y_{k+1} = clamp(alpha . A^ . Y_k + (1 - alpha) . y0, lo, hi), Y_0 = y0 [num_nodes x dim]; out = Y_iters, pred
+    //   (may be NULL) its row argmax (lowest column on a tie).  Needs neither labels nor trained weights.
+    //   label_propagation: propagate from the one-hot rows of the known nodes (zero rows elsewhere), clamp [0, 1].
+    //   correct_and_smooth: one hooked evaluation forward leaves the log-softmax rows on the device; gcnhip_cs_error_rows,
+    //   iters_correct blends clamped to [-1, 1], gcnhip_cs_correct_rows, iters_smooth blends clamped to [0, 1], the last of which
+    //   writes pred — the only array that must cross to the host; g (may be NULL) is copied when asked for.
+    void propagate(const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred);
+    void label_propagation(float alpha, int iters, int splits_mask, int32_t *pred, float *y);
+    void correct_and_smooth(float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth, int splits_mask, int32_t *pred, float *g);
     // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
     // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
     // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
@@ -302,6 +319,19 @@ private:
     // evaluate(): the counts on the device (also the float limbs of their all-reduce), an uploaded row list, every local label
     int32_t *d_eval_counts = nullptr, *d_eval_rows = nullptr, *d_label_all = nullptr;
     size_t eval_rows_cap = 0;
+    // propagate / label_propagation / correct_and_smooth: four tables [local rows x smooth_ld], the merged truth of the known
+    // splits, sigma = {sum |E_0|, rows}
+    float *d_smooth[4] = {};
+    int smooth_ld = 0;
+    int32_t *d_smooth_truth = nullptr;
+    float *d_sigma = nullptr;
+    static int smooth_row_ld(int dim) { return dim <= 32 ? (dim + 3) / 4 * 4 : (dim + 15) / 16 * 16; }   // HipVariable's rule
+    void smooth_check(const char *what, float alpha, int iters) const;
+    void smooth_tables(int ld);
+    const int32_t *smooth_truth(const char *what, int splits_mask, std::vector<int32_t> *host);
+    float *smooth_iterate(const float *base, float *a, float *b, int ld, int dim, float alpha, int iters, float lo, float hi, int32_t *pred);
+    void smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows);
+    void smooth_pred_download(int32_t *pred);
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

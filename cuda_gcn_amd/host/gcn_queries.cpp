@@ -259,6 +259,150 @@ void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64
     if (unlabelled) *unlabelled = no_truth;
 }
 
+// ---- label propagation and Correct & Smooth (beyond the reference) ------------------------------------------------------
+
+void HipGCN::smooth_check(const char *what, float alpha, int iters) const {
+    if (world() > 1)
+        throw GcnHipFailure(-1, std::string(what) + ": one rank only (with several, every iteration would need a table exchange)");
+    if (!(alpha >= 0.f && alpha <= 1.f)) throw GcnHipFailure(-1, std::string(what) + ": alpha must be in [0, 1]");
+    if (iters < 0) throw GcnHipFailure(-1, std::string(what) + ": iters must be >= 0");
+}
+
+// the four tables, wide enough for rows of ld floats (zeroed: no launch reads their padding, a download may)
+void HipGCN::smooth_tables(int ld) {
+    if (ld <= smooth_ld) return;
+    smooth_ld = 0;
+    for (float *&t : d_smooth) {
+        arena.release(t);
+        t = nullptr;
+        t = arena.alloc_zeroed<float>((size_t)std::max(n_local, 1) * ld);
+    }
+    smooth_ld = ld;
+}
+
+// label of every local row whose node is in a split of the mask, else -1; on the device too when `host` is NULL
+const int32_t *HipGCN::smooth_truth(const char *what, int splits_mask, std::vector<int32_t> *host) {
+    if (splits_mask == 0 || (splits_mask & ~14))
+        throw GcnHipFailure(-1, std::string(what) + ": splits are 1 (train), 2 (validation), 3 (test), at least one");
+    if (!host)
+        for (int s = 1; s <= 3; s++)
+            if (splits_mask == (1 << s)) return d_truth[s];
+    std::vector<int32_t> t((size_t)std::max(n_local, 1), -1);
+    const int r0 = row_start();
+    for (int r = 0; r < n_local; r++) {
+        const int s = data->split[r0 + r];
+        if (s >= 1 && s <= 3 && ((splits_mask >> s) & 1)) t[r] = data->label[r0 + r];
+    }
+    if (host) { host->swap(t); return nullptr; }
+    if (!d_smooth_truth) d_smooth_truth = arena.alloc<int32_t>(t.size());
+    GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_smooth_truth, t.data(), t.size() * sizeof(int32_t)));
+    return d_smooth_truth;
+}
+
+// `iters` blend launches from `base` (= Y_0, never written), alternating between tables a and b; the last one writes pred
+// when asked.  Returns the table that holds Y_iters (base itself when iters == 0).
+float *HipGCN::smooth_iterate(const float *base, float *a, float *b, int ld, int dim, float alpha, int iters, float lo, float hi, int32_t *pred) {
+    const float *in = base;
+    for (int k = 0; k < iters; k++) {
+        float *out = (k & 1) ? b : a;
+        GCNHIP_CHECK(gcnhip_graphsum_blend(env.ctx, graph, in, ld, base, ld, out, ld, dim, alpha, 1.f - alpha, lo, hi, k + 1 == iters ? pred : nullptr));
+        in = out;
+    }
+    return const_cast<float *>(in);
+}
+
+// a table's rows to dataset node order; pred_from_rows: also the row argmax (lowest column on a tie), formed on the host
+void HipGCN::smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows) {
+    if (!n_local) return;
+    std::vector<float> h((size_t)n_local * ld);
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, h.data(), table, h.size() * sizeof(float)));
+    const int r0 = row_start();
+    for (int r = 0; r < n_local; r++) {
+        const int id = node_order_.empty() ? r0 + r : node_order_[r0 + r];
+        const float *row = h.data() + (size_t)r * ld;
+        if (out) std::copy(row, row + dim, out + (size_t)id * dim);
+        if (pred_from_rows) pred_from_rows[id] = (int32_t)(std::max_element(row, row + dim) - row);
+    }
+}
+
+void HipGCN::smooth_pred_download(int32_t *pred) {
+    if (!n_local) return;
+    std::vector<int32_t> h((size_t)n_local);
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, h.data(), d_pred, h.size() * sizeof(int32_t)));
+    const int r0 = row_start();
+    for (int r = 0; r < n_local; r++) pred[node_order_.empty() ? r0 + r : node_order_[r0 + r]] = h[r];
+}
+
+void HipGCN::propagate(const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred) {
+    smooth_check("propagate", alpha, iters);
+    if (dim < 1 || dim > 64) throw GcnHipFailure(-1, "propagate: y0 has 1 to 64 columns (the row of a node sits in one wave)");
+    if (!y0 || !out) throw GcnHipFailure(-1, "propagate: invalid argument");
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    const int ld = smooth_row_ld(dim);
+    smooth_tables(ld);
+    pred_scratch();
+    {
+        std::vector<float> h((size_t)std::max(n_local, 1) * ld, 0.f);
+        const int r0 = row_start();
+        for (int r = 0; r < n_local; r++) {
+            const int id = node_order_.empty() ? r0 + r : node_order_[r0 + r];
+            std::copy(y0 + (size_t)id * dim, y0 + (size_t)(id + 1) * dim, h.begin() + (size_t)r * ld);
+        }
+        GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_smooth[0], h.data(), h.size() * sizeof(float)));
+    }
+    const float *y = smooth_iterate(d_smooth[0], d_smooth[1], d_smooth[2], ld, dim, alpha, iters, lo, hi, pred ? d_pred : nullptr);
+    smooth_download(y, ld, dim, out, pred && iters == 0 ? pred : nullptr);
+    if (pred && iters > 0) smooth_pred_download(pred);
+    sync();
+}
+
+void HipGCN::label_propagation(float alpha, int iters, int splits_mask, int32_t *pred, float *y) {
+    const int C = params.output_dim;
+    smooth_check("label_propagation", alpha, iters);
+    if (opt_.multilabel) throw GcnHipFailure(-1, "label_propagation: this is a multi-label model (the scheme spreads one label per node)");
+    if (C > 64) throw GcnHipFailure(-1, "label_propagation: at most 64 classes (the row of a node sits in one wave)");
+    if (!pred) throw GcnHipFailure(-1, "label_propagation: invalid argument");
+    std::vector<int32_t> t;
+    smooth_truth("label_propagation", splits_mask, &t);
+    // Y_0 in dataset order: the one-hot rows of the known nodes
+    std::vector<float> y0((size_t)params.num_nodes * C, 0.f), out(y ? 0 : y0.size());
+    const int r0 = row_start();
+    for (int r = 0; r < n_local; r++)
+        if (t[r] >= 0 && t[r] < C) y0[(size_t)(node_order_.empty() ? r0 + r : node_order_[r0 + r]) * C + t[r]] = 1.f;
+    propagate(y0.data(), C, alpha, iters, 0.f, 1.f, y ? y : out.data(), pred);
+}
+
+void HipGCN::correct_and_smooth(float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth, int splits_mask, int32_t *pred, float *g) {
+    const int C = params.output_dim;
+    smooth_check("correct_and_smooth", alpha_correct, iters_correct);
+    smooth_check("correct_and_smooth", alpha_smooth, iters_smooth);
+    if (opt_.multilabel) throw GcnHipFailure(-1, "correct_and_smooth: this is a multi-label model (the scheme corrects a softmax)");
+    if (!logits_gs) throw GcnHipFailure(-1, "correct_and_smooth: this model has no class-width aggregation");
+    if (C > 64) throw GcnHipFailure(-1, "correct_and_smooth: at most 64 classes (the row of a node sits in one wave)");
+    if (!pred) throw GcnHipFailure(-1, "correct_and_smooth: invalid argument");
+    sync();
+    const int32_t *truth = smooth_truth("correct_and_smooth", splits_mask, nullptr);
+    const int ld = smooth_row_ld(C);
+    const size_t nl = (size_t)std::max(n_local, 1);
+    smooth_tables(ld);
+    pred_scratch();
+    if (!d_logp) d_logp = arena.alloc<float>(nl * C);
+    if (!d_sigma) d_sigma = arena.alloc<float>(2);
+    // P: predict()'s forward, the log-softmax rows kept on the device
+    HipGraphSum::Prediction req;
+    req.rows = nullptr; req.pred = d_pred; req.prob = d_prob; req.logp = d_logp; req.ld_logp = C;
+    forward_hooked(&req, nullptr);
+    // correct: spread the residual of the known rows
+    GCNHIP_CHECK(gcnhip_cs_error_rows(env.ctx, d_logp, C, truth, n_local, nullptr, n_local, C, d_smooth[0], ld, d_sigma));
+    const float *eh = smooth_iterate(d_smooth[0], d_smooth[1], d_smooth[2], ld, C, alpha_correct, iters_correct, -1.f, 1.f, nullptr);
+    // scale it, add it to P, reset the known rows to their labels; then smooth (E_0, E^ are done with: their tables are free)
+    GCNHIP_CHECK(gcnhip_cs_correct_rows(env.ctx, d_logp, C, eh, ld, truth, n_local, C, d_sigma, d_smooth[3], ld));
+    const float *G = smooth_iterate(d_smooth[3], d_smooth[0], d_smooth[1], ld, C, alpha_smooth, iters_smooth, 0.f, 1.f, d_pred);
+    if (iters_smooth > 0) smooth_pred_download(pred);
+    if (g || iters_smooth == 0) smooth_download(G, ld, C, g, iters_smooth == 0 ? pred : nullptr);
+    sync();
+}
+
 void HipGCN::save_weights(const char *path) {
     std::vector<float> w1, w2;
     get_var(2, false, w1, nullptr, nullptr);

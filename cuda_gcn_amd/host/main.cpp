@@ -44,6 +44,11 @@
 //                            `macro_f1 <x> micro_f1 <y>`, and for a single-label model a line `confusion` followed by the matrix
 //                            (row = truth, column = prediction) as C lines of C integers.  With several GPUs every worker takes
 //                            part, all receive the same totals, and the file is written once after the join.
+//   GCN_SMOOTH=cs|lp        after the test line, the predictions are post-processed with the graph and the training labels on the GPU
+//                            (HipGCN::correct_and_smooth / label_propagation at their default settings: alpha 0.8 / 50 iterations
+//                            each for cs, alpha 0.9 / 50 iterations for lp) and one more line is printed:
+//                            `smoothed_test_acc=<share of the test split whose smoothed class is its label>`.  GCN_PREDICT then
+//                            writes the smoothed classes, one line `node class` per node.  One GPU, single-label.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -147,6 +152,20 @@ int main(int argc, char **argv) {
         }
     }
 
+    const char *smooth = getenv("GCN_SMOOTH");
+    if (smooth && !*smooth) smooth = nullptr;
+    if (smooth) {
+        const char *why = strcmp(smooth, "cs") != 0 && strcmp(smooth, "lp") != 0 ? "is cs (Correct & Smooth) or lp (label propagation)"
+                          : multilabel_path                                       ? "post-processes a single-label model (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                            ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > 64                                ? "takes at most 64 classes"
+                                                                                  : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_SMOOTH " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     int n_dev = 0;
     if (gcnhip_device_count(&n_dev) != 0 || n_dev < 1) {
         std::cerr << "gcn-hip: no GPU available (this backend has no CPU path; use gcn-seq)" << std::endl;
@@ -215,6 +234,15 @@ int main(int argc, char **argv) {
                     const int id = order.empty() ? r0 + r : order[r0 + r];
                     std::copy(b.begin() + (size_t)r * ml_wpr, b.begin() + (size_t)(r + 1) * ml_wpr, all_bits.begin() + (size_t)id * ml_wpr);
                 }
+            } else if (smooth) {                               // one rank (checked above): arrays by node id
+                std::vector<int32_t> p(std::max(params.num_nodes, 1));
+                if (strcmp(smooth, "cs") == 0) gcn.correct_and_smooth(0.8f, 50, 0.8f, 50, 1 << 1, p.data(), nullptr);
+                else gcn.label_propagation(0.9f, 50, 1 << 1, p.data(), nullptr);
+                long hit = 0, total = 0;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) { total++; hit += p[i] == data.label[i]; }
+                printf("smoothed_test_acc=%.5f\n", total ? (double)hit / (double)total : 0.0);
+                if (predict_path) std::copy(p.begin(), p.begin() + params.num_nodes, all_pred.begin());
             } else if (predict_path) {                         // every rank: the logit aggregation exchanges rows
                 const int n = gcn.local_rows(), r0 = gcn.row_start();
                 std::vector<int32_t> p(std::max(n, 1));
@@ -269,6 +297,10 @@ int main(int argc, char **argv) {
         FILE *f = fopen(predict_path, "w");
         bool ok = f != nullptr;
         for (int i = 0; ok && i < params.num_nodes; i++) {
+            if (smooth) {                                  // smoothed classes carry no softmax probability
+                ok = fprintf(f, "%d %d\n", i, all_pred[i]) > 0;
+                continue;
+            }
             if (!multilabel_path) {
                 ok = fprintf(f, "%d %d %.6g\n", i, all_pred[i], all_prob[i]) > 0;
                 continue;

@@ -263,6 +263,71 @@ class HipGCNModel:
         out["rows"] = rows.value
         return out
 
+    # ---- label propagation and Correct & Smooth: the graph and the known labels used at inference time
+    def _smooth_args(self, what, pairs, splits=None):
+        """argument checks that need no GPU; returns the split mask (bit s = the labelled nodes of split s are known)"""
+        for name, alpha, iters in pairs:
+            if not 0.0 <= float(alpha) <= 1.0:
+                raise ValueError(f"{what}: {name} must be in [0, 1], got {alpha!r}")
+            if int(iters) != iters or iters < 0:
+                raise ValueError(f"{what}: iters must be an integer >= 0, got {iters!r}")
+        if splits is None:
+            return 0
+        if self.multilabel:
+            raise ValueError(f"{what}: this is a multi-label model")
+        if self.params.output_dim > 64:
+            raise ValueError(f"{what}: at most 64 classes, this model has {self.params.output_dim}")
+        s = sorted(set(int(x) for x in np.atleast_1d(splits)))
+        if not s or any(x not in (1, 2, 3) for x in s):
+            raise ValueError(f"{what}: splits are 1 (train), 2 (validation), 3 (test), at least one; got {splits!r}")
+        return sum(1 << x for x in s)
+
+    def propagate(self, y0, alpha, iters, clamp=(-np.inf, np.inf), argmax=False):
+        """Y_{k+1} = clip(alpha . A^ . Y_k + (1 - alpha) . Y_0, lo, hi) with Y_0 = y0, `iters` times on the GPU (one blend
+        aggregation per iteration, ping-ponging two device tables).  y0: float32 [num_nodes, C'] in dataset node order, 1 <= C' <=
+        64 (it need not be the model's class count).  Returns Y_iters (y0 itself for iters=0), and with argmax=True also its row
+        argmax (int32, the lowest column on a tie).  One rank only.  Training state is not touched."""
+        lo, hi = clamp
+        self._smooth_args("propagate", [("alpha", alpha, iters)])
+        y = np.ascontiguousarray(y0, np.float32)
+        n = self.params.num_nodes
+        if y.ndim != 2 or y.shape[0] != n or not 1 <= y.shape[1] <= 64:
+            raise ValueError(f"propagate: y0 must be [num_nodes={n}, C'] with 1 <= C' <= 64, got {y.shape}")
+        if not float(lo) <= float(hi):
+            raise ValueError(f"propagate: clamp=(lo, hi) needs lo <= hi, got {clamp!r}")
+        out = np.zeros_like(y)
+        pred = np.zeros(max(n, 1), np.int32) if argmax else None
+        _ck(self.lib, self.lib.gcnhost_model_propagate(self.h, y.ctypes.data, y.shape[1], float(alpha), int(iters), float(lo), float(hi),
+                                                       out.ctypes.data, pred.ctypes.data if argmax else None), "propagate")
+        return (out, pred[:n]) if argmax else out
+
+    def label_propagation(self, alpha=0.9, iters=50, splits=(1,)):
+        """(pred int32 [num_nodes], Y f32 [num_nodes, C]) — label propagation from the labelled nodes of `splits`: propagate() with
+        Y_0 = their one-hot rows (zero rows elsewhere) and clamp [0, 1].  Needs no trained weights.  Single-label models, at most
+        64 classes, one rank."""
+        mask = self._smooth_args("label_propagation", [("alpha", alpha, iters)], splits)
+        n, c = self.params.num_nodes, self.params.output_dim
+        pred, y = np.zeros(max(n, 1), np.int32), np.zeros((n, c), np.float32)
+        _ck(self.lib, self.lib.gcnhost_model_label_propagation(self.h, float(alpha), int(iters), mask, pred.ctypes.data, y.ctypes.data),
+            "label_propagation")
+        return pred[:n], y
+
+    def correct_and_smooth(self, alpha_correct=0.8, iters_correct=50, alpha_smooth=0.8, iters_smooth=50, splits=(1,), scores=True):
+        """(pred int32 [num_nodes], G f32 [num_nodes, C]) — Correct & Smooth (Huang et al., 2020) on the softmax of one evaluation
+        forward with the current weights: the residual of the labelled nodes of `splits` is propagated (clamp [-1, 1]), scaled per
+        row and added to the softmax, the labelled rows are reset to their one-hot labels, and the result is propagated again
+        (clamp [0, 1]); pred is the row argmax of G, written by the last launch.  scores=False: G is not copied back (None).
+        Single-label models, at most 64 classes, one rank.  Training state is not touched."""
+        mask = self._smooth_args("correct_and_smooth", [("alpha_correct", alpha_correct, iters_correct),
+                                                        ("alpha_smooth", alpha_smooth, iters_smooth)], splits)
+        n, c = self.params.num_nodes, self.params.output_dim
+        pred = np.zeros(max(n, 1), np.int32)
+        g = np.zeros((n, c), np.float32) if scores else None
+        _ck(self.lib, self.lib.gcnhost_model_correct_and_smooth(self.h, float(alpha_correct), int(iters_correct), float(alpha_smooth),
+                                                                int(iters_smooth), mask, pred.ctypes.data, g.ctypes.data if scores else None),
+            "correct_and_smooth")
+        return pred[:n], g
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")

@@ -242,6 +242,59 @@ class Device:
         return dict(pred=pb.download()[:n], prob=qb.download()[:n], logp=lb.download()[:n] if lb else None,
                     logits=out.download()[:, :dim] if out else None)
 
+    def graphsum_blend(self, g: "Graph", x, base=None, alpha=1.0, beta=0.0, lo=-np.inf, hi=np.inf, ld=None, argmax=False, fill=np.nan,
+                       alias_out=False):
+        """gcnhip_graphsum_blend: clip(alpha . (A^ . x) + beta . base, lo, hi) with the object's per-edge coefficients.  base=None:
+        the gathered table itself is the base (the same device buffer); alias_out=True passes out = in (refused).  Returns the
+        WHOLE out table [n_rows, ld] (its padding columns keep `fill`), and with argmax=True also pred int32 [n_rows]."""
+        x = np.asarray(x, np.float32)
+        dim = x.shape[1]
+        ld = ld or (dim + 3) // 4 * 4
+        xin = self.padded(x, ld)
+        bb = xin if base is None else self.padded(np.asarray(base, np.float32), ld)
+        out = xin if alias_out else self.buf(np.full((g.n_rows, ld), fill, np.float32))
+        pb = self.buf(np.full(max(g.n_rows, 1), -1, np.int32)) if argmax else None
+        g.reserve(dim)
+        rc = self.lib.gcnhip_graphsum_blend(self.ctx, g.h, xin.ptr, ld, bb.ptr, ld, out.ptr, ld, dim, float(alpha), float(beta), float(lo),
+                                            float(hi), pb.ptr if pb else None)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_graphsum_blend: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        o = out.download()
+        return (o, pb.download()[:g.n_rows]) if argmax else o
+
+    def cs_error_rows(self, logp, truth, rows=None, ld_e=None, fill=np.nan):
+        """gcnhip_cs_error_rows: (E [n, ld_e] — uploaded as `fill`, the launch zeroes it —, sigma f32 [2] = {sum |E|, rows}).  logp
+        f32 [n, C] (unpadded rows), truth int32 [n]; rows: the listed rows (None: every row)"""
+        logp = np.ascontiguousarray(logp, np.float32)
+        truth = np.ascontiguousarray(truth, np.int32)
+        n, c = logp.shape
+        ld_e = ld_e or (c + 3) // 4 * 4
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        lb, tb = self.buf(logp), self.buf(truth)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        eb = self.buf(np.full((n, ld_e), fill, np.float32))
+        sb = self.buf(np.full(2, np.nan, np.float32))
+        rc = self.lib.gcnhip_cs_error_rows(self.ctx, lb.ptr, c, tb.ptr, n, rb.ptr if rb else None, int(n if rows is None else rows.size), c,
+                                           eb.ptr, ld_e, sb.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_cs_error_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return eb.download(), sb.download()
+
+    def cs_correct_rows(self, logp, e_hat, truth, sigma, ld_g=None, fill=np.nan):
+        """gcnhip_cs_correct_rows: G0 [n, ld_g] (padding columns keep `fill`).  logp f32 [n, C], e_hat f32 [n, ld_e >= C], truth
+        int32 [n], sigma f32 [2] as cs_error_rows leaves it"""
+        logp = np.ascontiguousarray(logp, np.float32)
+        e_hat = np.ascontiguousarray(e_hat, np.float32)
+        n, c = logp.shape
+        ld_g = ld_g or (c + 3) // 4 * 4
+        lb, eb, tb = self.buf(logp), self.buf(e_hat), self.buf(np.ascontiguousarray(truth, np.int32))
+        sb = self.buf(np.ascontiguousarray(sigma, np.float32))
+        gb = self.buf(np.full((n, ld_g), fill, np.float32))
+        rc = self.lib.gcnhip_cs_correct_rows(self.ctx, lb.ptr, c, eb.ptr, e_hat.shape[1], tb.ptr, n, c, sb.ptr, gb.ptr, ld_g)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_cs_correct_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return gb.download()
+
     def graphsum(self, g: "Graph", x, ld_in=None, ld_out=None, row_nonzero=None):
         x = np.asarray(x, np.float32)
         dim = x.shape[1]
@@ -802,6 +855,18 @@ class Graph:
         out = np.empty(nnz.value, np.float32)
         _ck(self.dev.lib, self.dev.lib.gcnhip_d2h(self.dev.ctx, out.ctypes.data, pc, out.nbytes), "d2h")
         return out
+
+    def csr(self):
+        """(indptr int32 [n_rows + 1], indices int32 [nnz], coef f32 [nnz]) as the device object stores them: every row's
+        neighbours in the order the kernels add them, with the f32 coefficients they multiply by"""
+        pp, pi, pc = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nr, nnz = C.c_int(), C.c_int()
+        _ck(self.dev.lib, self.dev.lib.gcnhip_graph_arrays(self.h, C.byref(pp), C.byref(pi), C.byref(pc), C.byref(nr), C.byref(nnz)), "graph_arrays")
+        out = [np.empty(nr.value + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value, np.float32)]
+        for a, q in zip(out, (pp, pi, pc)):
+            if a.nbytes:
+                _ck(self.dev.lib, self.dev.lib.gcnhip_d2h(self.dev.ctx, a.ctypes.data, q, a.nbytes), "d2h")
+        return tuple(out)
 
     def free(self):
         if self.h and self.dev.ctx:

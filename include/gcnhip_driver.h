@@ -184,6 +184,34 @@ int gcnhip_graphsum_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const gcnhip_gs_o
  * dim <= 64 (the row then sits in one wave).  Separate kernels: no existing launch changes. */
 int gcnhip_graphsum_predict(gcnhip_ctx *ctx, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, const uint16_t *in_bf16,
                             int ld_in, float *out, int ld_out, int dim, int scaling, int32_t *pred, float *prob, float *logp, int ld_logp);
+/* ---- label propagation and Correct & Smooth (beyond the reference: the graph and the known labels used at inference time) ----
+ * Blend epilogue of the class-width aggregation, one step of either scheme:
+ *   out[r, j] = min(max(alpha * sum_e coef(e) * in[col(e), j] + beta * base[r, j], lo), hi)      for every row r, j < dim
+ *   pred[r]   = argmax_j out[r, j], the LOWEST j on a tie (numpy.argmax's rule); only when pred != NULL ([n_rows] int32)
+ * The gather is gcnhip_graphsum_predict's (same task list, lane groups, edge order, reduction tree, split-row scratch; rows
+ * longer than the split length are summed in segment order by a finalize launch that applies the same epilogue) with the
+ * per-edge coefficients of the object, never the factored form: the iterate stays in one form from launch to launch.
+ * f32 rows only: 1 <= dim <= 64, every ld % 4 == 0 and >= dim, 16-byte aligned tables; anything else returns -1 with a message
+ * (gcnhip_last_error), never a wrong answer.  `in` has n_cols rows, base and out n_rows.  out must not be `in` (other waves
+ * are still gathering it: refused); base may be `in` or any other table.  Columns [dim, ld_out) of out are not written, those
+ * of base not read.  lo = -INFINITY / hi = +INFINITY: no clamp.  Deterministic (no float atomics: two launches give the same
+ * bits); neither allocates nor synchronises. */
+int gcnhip_graphsum_blend(gcnhip_ctx *ctx, const gcnhip_graph *g, const float *in, int ld_in, const float *base, int ld_base,
+                          float *out, int ld_out, int dim, float alpha, float beta, float lo, float hi, int32_t *pred);
+/* The row-local steps of Correct & Smooth (smooth.hip; a wave per row, lane j on class j: 1 <= num_classes <= 64, rows of any
+ * stride).  logp: log-softmax rows as gcnhip_graphsum_predict writes them; truth: an array as gcnhip_set_truth makes (-1 outside
+ * the split); all tables have n_table rows.
+ * gcnhip_cs_error_rows zeroes e (n_table x ld_e floats, on ctx's stream), then for each of the n_listed rows r = d_rows[i]
+ * (distinct; d_rows == NULL: rows 0 .. n_listed - 1) whose truth[r] is in [0, C) writes e[r, j] = [j == truth[r]] - expf(logp[r, j])
+ * and leaves d_sigma[2] = {sum of |e| over those rows, their number}; rows with another truth, or an id outside the table,
+ * contribute nothing.  The sum is deterministic (block partials added in block order by a one-block finalize launch).
+ * gcnhip_cs_correct_rows: for every row r, s = (d_sigma[0] / d_sigma[1]) / sum_j |e_hat[r, j]|, replaced by 1 unless s <= 1000
+ * (a zero row, inf and NaN included); g0[r, :] = the one-hot row of truth[r] where that is in [0, C), else
+ * expf(logp[r, :]) + s * e_hat[r, :].  g0 must not be e_hat.  Columns past num_classes are not written. */
+int gcnhip_cs_error_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, const int32_t *truth, int n_table, const int32_t *d_rows,
+                         int n_listed, int num_classes, float *e, int ld_e, float *d_sigma);
+int gcnhip_cs_correct_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, const float *e_hat, int ld_e, const int32_t *truth, int n_table,
+                           int num_classes, const float *d_sigma, float *g0, int ld_g);
 /* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
  * subsets made at call time, such as the node queries of a prediction. */
 int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);

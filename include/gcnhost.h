@@ -174,6 +174,28 @@ int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, 
  * the same totals.  Only the counts cross to the host.  Training state is not touched, as for gcnhost_model_predict.
  * More than 64 (single-label) or 256 (multi-label) classes is an error.  Synchronises. */
 int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+/* Label propagation and Correct & Smooth (beyond the reference): the graph and the known labels used at inference time.  Every
+ * iteration is one gcnhip_graphsum_blend launch over this model's adjacency, ping-ponging two device tables; arrays are in
+ * DATASET node order, [num_nodes x width] row-major.  gcnhost_model_predict's contract holds: the call synchronises first, and
+ * the training state (metrics ring, current split, variable 6, the captured epoch graph) is untouched.  One rank only: with
+ * several, every iteration would need a table exchange — refused with a message.  Refused before any launch, too: alpha outside
+ * [0, 1], iters < 0, a width outside 1..64 and, for the two label schemes, a multi-label model or more than 64 classes.
+ * splits_mask: bit s set = the labelled nodes of split s (1 train, 2 validation, 3 test) are known; e.g. 2 = train only.
+ *
+ * gcnhost_model_propagate: Y_0 = y0 [num_nodes x dim]; Y_{k+1} = min(max(alpha . A^ . Y_k + (1 - alpha) . Y_0, lo), hi); out
+ * [num_nodes x dim] = Y_iters (iters == 0: y0), pred (may be NULL) [num_nodes] = its argmax per row, lowest column on a tie.
+ * dim need not be the model's class count and no trained weights are needed.
+ * gcnhost_model_label_propagation: propagate with Y_0 = the one-hot rows of the known nodes whose label is in [0, C), zero rows
+ * elsewhere, clamp [0, 1]; pred [num_nodes], y (may be NULL) [num_nodes x output_dim].
+ * gcnhost_model_correct_and_smooth (Huang et al., 2020): P = softmax of one evaluation forward (log-softmax kept on the device);
+ * E_0 = onehot - P on the known rows, zero elsewhere (gcnhip_cs_error_rows); E_{k+1} = clamp(a1 . A^ . E_k + (1 - a1) . E_0, -1, 1);
+ * G_0 = the one-hot row on known rows, P + s . E^ elsewhere with the autoscale s of gcnhip_cs_correct_rows;
+ * G_{k+1} = clamp(a2 . A^ . G_k + (1 - a2) . G_0, 0, 1), whose last launch writes pred.  Only pred [num_nodes] must cross to the
+ * host; g (may be NULL) [num_nodes x output_dim] is copied when asked for. */
+int gcnhost_model_propagate(gcnhost_model *m, const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred);
+int gcnhost_model_label_propagation(gcnhost_model *m, float alpha, int iters, int splits_mask, int32_t *pred, float *y);
+int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth,
+                                     int splits_mask, int32_t *pred, float *g);
 /* Per-class metrics from integer counts, host only (host/report.h): either confusion [C x C] (row = truth, column =
  * prediction) or tp / fp / fn [C] (the other form NULL).  Every output may be NULL: tp_fp_fn [3 x C] the counts used; support
  * (TP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), f1 = 2 TP / (2 TP + FP + FN) [C], float64, each 0 when
