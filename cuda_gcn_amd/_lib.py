@@ -107,6 +107,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_graphsum_blend": (I, [P, P, P, I, P, I, P, I, I, F, F, F, F, P]),
     "gcnhip_cs_error_rows": (I, [P, P, I, P, I, P, I, I, P, I, P]),
     "gcnhip_cs_correct_rows": (I, [P, P, I, P, I, P, I, I, P, P, I]),
+    "gcnhip_calib_nll_rows": (I, [P, P, I, P, I, P, I, I, F, P]),
+    "gcnhip_calib_bins_rows": (I, [P, P, I, P, I, P, I, I, F, I, P, P, P]),
+    "gcnhip_calib_scale_rows": (I, [P, P, I, I, P, I, I, F, P, I, P]),
     "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
@@ -223,6 +226,11 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_propagate": (I, [P, P, I, F, I, F, F, P, P]),
     "gcnhost_model_label_propagation": (I, [P, F, I, I, P, P]),
     "gcnhost_model_correct_and_smooth": (I, [P, F, I, F, I, I, P, P]),
+    "gcnhost_model_calibration": (I, [P, I, P, I, F, I, P, P, P, P]),
+    "gcnhost_model_calibrate": (I, [P, I, I, P, P, P, P]),
+    "gcnhost_model_set_temperature": (I, [P, F]),
+    "gcnhost_model_temperature": (I, [P, C.POINTER(F)]),
+    "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),
     "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),
     "gcnhost_model_save_weights": (I, [P, C.c_char_p]),

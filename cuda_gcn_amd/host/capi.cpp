@@ -12,6 +12,7 @@
 #include "class_weights.h"
 #include "labels.h"
 #include "report.h"
+#include "calibration.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -236,6 +237,36 @@ int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int 
                                      int splits_mask, int32_t *pred, float *g) {
     if (!m || !pred) { g_err = "gcnhost_model_correct_and_smooth: invalid argument"; return -1; }
     API_TRY({ m->gcn->correct_and_smooth(alpha_correct, iters_correct, alpha_smooth, iters_smooth, splits_mask, pred, g); })
+}
+int gcnhost_model_calibration(gcnhost_model *m, int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count,
+                              int64_t *correct, double *conf_sum) {
+    if (!m || !sums || !count || !correct || !conf_sum) { g_err = "gcnhost_model_calibration: invalid argument"; return -1; }
+    API_TRY({ m->gcn->calibration(split, nodes, n, temperature, bins, sums, count, correct, conf_sum); })
+}
+int gcnhost_model_calibrate(gcnhost_model *m, int split, int bins, double *out, int64_t *count, int64_t *correct, double *conf_sum) {
+    if (!m || !out) { g_err = "gcnhost_model_calibrate: invalid argument"; return -1; }
+    API_TRY({
+        const HipGCN::Calibrated c = m->gcn->calibrate(split, bins, count, correct, conf_sum);
+        out[0] = c.temperature; out[1] = c.nll_before; out[2] = c.nll_after; out[3] = c.steps; out[4] = c.at_bound ? 1.0 : 0.0;
+        out[5] = (double)c.rows;
+    })
+}
+int gcnhost_model_set_temperature(gcnhost_model *m, float temperature) {
+    if (!m) { g_err = "gcnhost_model_set_temperature: invalid argument"; return -1; }
+    API_TRY({ m->gcn->set_temperature(temperature); })
+}
+int gcnhost_model_temperature(gcnhost_model *m, float *temperature) {
+    if (!m || !temperature) { g_err = "gcnhost_model_temperature: invalid argument"; return -1; }
+    API_TRY({ *temperature = m->gcn->temperature(); })
+}
+int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
+                               double *confidence, double *summary) {
+    CalibrationReport r;
+    if (gcn_calibration_report(bins, count, correct, conf_sum, &r, &g_err) != 0) return -1;
+    if (accuracy) std::copy(r.accuracy.begin(), r.accuracy.end(), accuracy);
+    if (confidence) std::copy(r.confidence.begin(), r.confidence.end(), confidence);
+    if (summary) { summary[0] = r.ece; summary[1] = r.mce; summary[2] = (double)r.rows; }
+    return 0;
 }
 int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
                          int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {

@@ -230,6 +230,41 @@ public:
     void propagate(const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred);
     void label_propagation(float alpha, int iters, int splits_mask, int32_t *pred, float *y);
     void correct_and_smooth(float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth, int splits_mask, int32_t *pred, float *g);
+    // Temperature scaling and calibration error (beyond the reference; Guo et al., 2017): are predict()'s probabilities to be
+    // trusted, and one scalar T that repairs them — softmax(z / T) with T fitted on a held-out split.  All three work on the
+    // log-softmax rows predict()'s hooked forward leaves on the device (log_softmax(z / T) = log_softmax(log_softmax(z) / T)) with
+    // the row-local kernels of csrc/calib.hip, and hold predict()'s contract: the call starts with sync(); the metrics ring, the
+    // current split, variable 6 and the captured epoch graph are untouched.  Rows: the labelled nodes of `split` (1 train,
+    // 2 validation, 3 test), or with split == 0 the `nodes` query scored against the dataset's labels, as evaluate() takes them.
+    // Refused with a message before any launch: a multi-label model, more than 64 classes, more than one rank (the double sums
+    // would need an exact all-reduce that the float transport does not give), bins outside 1..64, a temperature that is not
+    // finite and > 0, and for calibrate a split without labelled rows.
+    //   calibration: one forward, one gcnhip_calib_nll_rows and one gcnhip_calib_bins_rows launch at beta = 1 / temperature;
+    //   sums[4] = {sum nll, sum d nll / d beta, sum d2 nll / d beta2, rows}, count / correct [bins], conf_sum [bins]: the 4 + 3 . bins
+    //   numbers that cross to the host (host/calibration.h turns them into the report).
+    //   calibrate: one forward, then a safeguarded Newton iteration on the convex NLL(beta) run by the host — a step is one nll
+    //   launch and one 32-byte copy.  From beta = 1 inside the bracket [0.01, 100], which moves with the sign of the gradient; the
+    //   Newton step beta - g / h when h > 0 and it stays strictly inside the bracket, else the geometric midpoint (while the end
+    //   the step goes to is still the outer limit, the step is at least a factor 2, so a minimum that is not there is left behind
+    //   within the 40 steps); stops when
+    //   |delta beta| <= 1e-6 beta or after 40 steps.  at_bound: the result sits on an end of [0.01, 100] (a split the model
+    //   classifies perfectly: the NLL falls in beta without end).  With bins > 0 the reliability counts of the same rows at T = 1
+    //   and at the fitted T are formed by two more launches on the rows already there: count / correct / conf_sum [2 x bins].
+    //   calibrate does not set the temperature.
+    //   set_temperature(T != 1): predict() keeps the log-softmax rows, runs gcnhip_calib_scale_rows on the queried rows and returns
+    //   the scaled prob (and logp); pred does not depend on T.  correct_and_smooth() scales its rows in place before the residual.
+    //   At T == 1 (the default) neither launches anything new.  Training, eval, evaluate and the weights file ignore it.
+    struct Calibrated {
+        float temperature = 1.f;
+        double nll_before = 0, nll_after = 0;                  // mean NLL of the split at beta = 1 and at the result
+        int steps = 0;
+        bool at_bound = false;
+        int64_t rows = 0;
+    };
+    void calibration(int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count, int64_t *correct, double *conf_sum);
+    Calibrated calibrate(int split, int bins, int64_t *count, int64_t *correct, double *conf_sum);
+    void set_temperature(float t);
+    float temperature() const { return temperature_; }
     // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
     // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
     // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
@@ -332,6 +367,17 @@ private:
     float *smooth_iterate(const float *base, float *a, float *b, int ld, int dim, float alpha, int iters, float lo, float hi, int32_t *pred);
     void smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows);
     void smooth_pred_download(int32_t *pred);
+    // calibration / calibrate: {nll sums [4] | conf_sum [2 x 64]} doubles and {count, correct} [2 x 2 x 64] ints on the device
+    float temperature_ = 1.f;
+    double *d_calib_sums = nullptr;
+    int32_t *d_calib_counts = nullptr;
+    void calib_check(const char *what, float temperature, int bins) const;
+    // the rows a split or a query names, as evaluate() lists them, and the truth they are scored against
+    struct ScoredRows { const int32_t *d_list; int n; const int32_t *truth; const gcnhip_rowset *subset; };
+    ScoredRows scored_rows(const char *what, int split, const int *nodes, int n);
+    const int32_t *upload_rows(const std::vector<int> &rows);
+    void forward_logp(const gcnhip_rowset *subset);            // predict()'s hooked forward, d_logp kept
+    void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

@@ -3,6 +3,8 @@
 #include "gcn.h"
 #include "weights.h"
 #include "hip_check.h"
+#include <algorithm>
+#include <cmath>
 
 void HipGCN::row_scale(std::vector<float> &dinv) {
     dinv.assign((size_t)n_local, 1.f);
@@ -114,12 +116,26 @@ void HipGCN::predict(const int *nodes, int n, int32_t *pred, float *prob, float 
     const gcnhip_rowset *subset = nodes ? query_subset(rows) : nullptr;
     const size_t nl = (size_t)std::max(n_local, 1);
     pred_scratch();
-    if (logp && !d_logp) d_logp = arena.alloc<float>(nl * C);
+    const bool scaled = temperature_ != 1.f;                   // a set temperature: the rows are kept and rescaled behind the forward
+    if ((logp || scaled) && !d_logp) d_logp = arena.alloc<float>(nl * C);
     // the logit aggregation runs the prediction epilogue instead of its usual launch and stores no logits
     HipGraphSum::Prediction req;
-    req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = logp ? d_logp : nullptr; req.ld_logp = C;
+    req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = logp || scaled ? d_logp : nullptr; req.ld_logp = C;
     forward_hooked(&req, nullptr);
     if (n == 0) { sync(); return; }
+    if (scaled) {
+        // in place, so every queried row once: a query may repeat a node
+        const int32_t *d_list = nullptr;
+        int listed = n_local;
+        if (nodes) {
+            std::vector<int> once(rows);
+            std::sort(once.begin(), once.end());
+            once.erase(std::unique(once.begin(), once.end()), once.end());
+            listed = (int)once.size();
+            d_list = upload_rows(once);
+        }
+        GCNHIP_CHECK(gcnhip_calib_scale_rows(env.ctx, d_logp, C, n_local, d_list, listed, C, 1.f / temperature_, d_logp, C, d_prob));
+    }
     std::vector<int32_t> hp(nl);
     std::vector<float> hq(nl), hl;
     GCNHIP_CHECK(gcnhip_d2h(env.ctx, hp.data(), d_pred, nl * sizeof(int32_t)));
@@ -166,6 +182,57 @@ void HipGCN::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *
     if (prob) GCNHIP_CHECK(gcnhip_d2h(env.ctx, prob, d_ml_prob, (size_t)n * C * sizeof(float)));
 }
 
+// a list of local rows on the device (evaluate's scratch, grown when needed)
+const int32_t *HipGCN::upload_rows(const std::vector<int> &rows) {
+    const size_t n = std::max(rows.size(), (size_t)1);
+    if (n > eval_rows_cap) {
+        eval_rows_cap = 0;
+        arena.regrow(d_eval_rows, n);
+        eval_rows_cap = n;
+    }
+    if (!rows.empty()) GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_eval_rows, rows.data(), rows.size() * sizeof(int32_t)));
+    return d_eval_rows;
+}
+
+// The rows to score: the split's list (already on the device on the fused path), or the query; their subset of `graph`; and on
+// a single-label model the truth they are scored against (a query: the labels themselves).  Synchronises before it touches the device.
+HipGCN::ScoredRows HipGCN::scored_rows(const char *what, int split, const int *nodes, int n) {
+    ScoredRows q{nullptr, n, nullptr, nullptr};
+    std::vector<int> rows;
+    bool upload = false;
+    if (split) {
+        if (d_split_list[split]) {
+            q.d_list = d_split_list[split];
+            q.n = split_local_n[split];
+        } else {
+            const int r0 = row_start();
+            for (int r = 0; r < n_local; r++)
+                if (data->split[r0 + r] == split) rows.push_back(r);
+            q.n = (int)rows.size();
+            upload = true;
+        }
+    } else {
+        if (!nodes) q.n = n_local;
+        query_rows(what, nodes, q.n, rows);
+        upload = nodes != nullptr;                             // NULL: rows 0 .. n_local - 1, no list
+    }
+    sync();                                                    // run()'s epochs in flight, the validation lane's pass
+    q.subset = split ? split_rows[split] : (nodes ? query_subset(rows) : nullptr);
+    if (upload) q.d_list = upload_rows(rows);
+    if (!opt_.multilabel) {
+        q.truth = d_truth[split];
+        if (!split) {                                          // a query is scored against the labels themselves
+            if (!d_label_all) {
+                std::vector<int32_t> lab(data->label.begin() + row_start(), data->label.begin() + row_start() + n_local);
+                if (lab.empty()) lab.assign(1, -1);
+                d_label_all = arena.upload(lab.data(), lab.size());
+            }
+            q.truth = d_label_all;
+        }
+    }
+    return q;
+}
+
 void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
     const int C = params.output_dim;
     const bool ml = opt_.multilabel;
@@ -173,40 +240,13 @@ void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64
     if (!ml && C > 64) throw GcnHipFailure(-1, "evaluate: at most 64 classes on a single-label model (the logit row of a node sits in one wave)");
     if (ml && C > 256) throw GcnHipFailure(-1, "evaluate: at most 256 classes on a multi-label model");
     if (split < 0 || split > 3 || !counts || n < 0) throw GcnHipFailure(-1, "evaluate: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
-    // the rows to score: the split's list (already on the device on the fused path), or the query
-    std::vector<int> rows;
-    const int32_t *d_list = nullptr;
-    bool upload = false;
-    if (split) {
-        if (d_split_list[split]) {
-            d_list = d_split_list[split];
-            n = split_local_n[split];
-        } else {
-            const int r0 = row_start();
-            for (int r = 0; r < n_local; r++)
-                if (data->split[r0 + r] == split) rows.push_back(r);
-            n = (int)rows.size();
-            upload = true;
-        }
-    } else {
-        if (!nodes) n = n_local;
-        query_rows("evaluate", nodes, n, rows);
-        upload = nodes != nullptr;                             // NULL: rows 0 .. n_local - 1, no list
-    }
-    sync();                                                    // run()'s epochs in flight, the validation lane's pass
-    const gcnhip_rowset *subset = split ? split_rows[split] : (nodes ? query_subset(rows) : nullptr);
+    const ScoredRows q = scored_rows("evaluate", split, nodes, n);
+    const int32_t *d_list = q.d_list;
+    const gcnhip_rowset *subset = q.subset;
+    n = q.n;
     const int m = ml ? 3 * C : C * C + 1;                      // all that crosses to the host
     if (!d_eval_counts)                                        // ... or its two float limbs each, plus the listed rows' (below)
         d_eval_counts = arena.alloc<int32_t>(((size_t)std::max(3 * C, C * C + 1) + 1) * 2);
-    if (upload && (size_t)std::max(n, 1) > eval_rows_cap) {
-        eval_rows_cap = 0;
-        arena.regrow(d_eval_rows, (size_t)std::max(n, 1));
-        eval_rows_cap = (size_t)std::max(n, 1);
-    }
-    if (upload) {
-        if (n) GCNHIP_CHECK(gcnhip_h2d(env.ctx, d_eval_rows, rows.data(), (size_t)n * sizeof(int32_t)));
-        d_list = d_eval_rows;
-    }
     if (ml) {
         HipVariable *Z = variables[6].get();
         HipGraphSum::Redirect req;
@@ -215,15 +255,7 @@ void HipGCN::evaluate(int split, const int *nodes, int n, int64_t *counts, int64
         GCNHIP_CHECK(gcnhip_bce_class_counts_rows(env.ctx, d_ml_logits, Z->ld, d_ml_truth, ml_wpr, d_list, n, C, d_eval_counts));
     } else {
         pred_scratch();
-        const int32_t *truth = d_truth[split];
-        if (!split) {                                          // a query is scored against the labels themselves
-            if (!d_label_all) {
-                std::vector<int32_t> lab(data->label.begin() + row_start(), data->label.begin() + row_start() + n_local);
-                if (lab.empty()) lab.assign(1, -1);
-                d_label_all = arena.upload(lab.data(), lab.size());
-            }
-            truth = d_label_all;
-        }
+        const int32_t *truth = q.truth;
         HipGraphSum::Prediction req;
         req.rows = subset; req.pred = d_pred; req.prob = d_prob;
         forward_hooked(&req, nullptr);
@@ -392,6 +424,8 @@ void HipGCN::correct_and_smooth(float alpha_correct, int iters_correct, float al
     HipGraphSum::Prediction req;
     req.rows = nullptr; req.pred = d_pred; req.prob = d_prob; req.logp = d_logp; req.ld_logp = C;
     forward_hooked(&req, nullptr);
+    if (temperature_ != 1.f)                                   // the calibrated softmax is what gets corrected and smoothed
+        GCNHIP_CHECK(gcnhip_calib_scale_rows(env.ctx, d_logp, C, n_local, nullptr, n_local, C, 1.f / temperature_, d_logp, C, nullptr));
     // correct: spread the residual of the known rows
     GCNHIP_CHECK(gcnhip_cs_error_rows(env.ctx, d_logp, C, truth, n_local, nullptr, n_local, C, d_smooth[0], ld, d_sigma));
     const float *eh = smooth_iterate(d_smooth[0], d_smooth[1], d_smooth[2], ld, C, alpha_correct, iters_correct, -1.f, 1.f, nullptr);
@@ -401,6 +435,115 @@ void HipGCN::correct_and_smooth(float alpha_correct, int iters_correct, float al
     if (iters_smooth > 0) smooth_pred_download(pred);
     if (g || iters_smooth == 0) smooth_download(G, ld, C, g, iters_smooth == 0 ? pred : nullptr);
     sync();
+}
+
+// ---- temperature scaling and calibration error (beyond the reference) ---------------------------------------------------
+
+void HipGCN::calib_check(const char *what, float temperature, int bins) const {
+    const std::string w(what);
+    if (opt_.multilabel) throw GcnHipFailure(-1, w + ": this is a multi-label model (a temperature scales one softmax per node)");
+    if (!logits_gs) throw GcnHipFailure(-1, w + ": this model has no class-width aggregation");
+    if (params.output_dim > 64) throw GcnHipFailure(-1, w + ": at most 64 classes (the row of a node sits in one wave)");
+    if (world() > 1) throw GcnHipFailure(-1, w + ": one rank only (the double sums would need an exact all-reduce that the float transport does not give)");
+    if (bins < 1 || bins > 64) throw GcnHipFailure(-1, w + ": bins must be in 1..64");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) throw GcnHipFailure(-1, w + ": the temperature must be finite and > 0");
+}
+
+void HipGCN::set_temperature(float t) {
+    if (!(t > 0.f) || !std::isfinite(t)) throw GcnHipFailure(-1, "set_temperature: the temperature must be finite and > 0");
+    if (t != 1.f && opt_.multilabel) throw GcnHipFailure(-1, "set_temperature: this is a multi-label model (a temperature scales one softmax per node)");
+    if (t != 1.f && params.output_dim > 64) throw GcnHipFailure(-1, "set_temperature: at most 64 classes (the row of a node sits in one wave)");
+    temperature_ = t;
+}
+
+void HipGCN::forward_logp(const gcnhip_rowset *subset) {
+    const int C = params.output_dim;
+    pred_scratch();
+    if (!d_logp) d_logp = arena.alloc<float>((size_t)std::max(n_local, 1) * C);
+    if (!d_calib_sums) {
+        d_calib_sums = arena.alloc<double>(4 + 2 * 64);
+        d_calib_counts = arena.alloc<int32_t>(2 * 2 * 64);
+    }
+    HipGraphSum::Prediction req;
+    req.rows = subset; req.pred = d_pred; req.prob = d_prob; req.logp = d_logp; req.ld_logp = C;
+    forward_hooked(&req, nullptr);
+}
+
+// one bins launch on the rows d_logp holds, and its 3 . bins numbers to the host (slot 0 or 1 of the device scratch)
+void HipGCN::calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum) {
+    const int C = params.output_dim;
+    int32_t *d_cnt = d_calib_counts + slot * 128, *d_cor = d_cnt + bins;
+    double *d_conf = d_calib_sums + 4 + slot * 64;
+    GCNHIP_CHECK(gcnhip_calib_bins_rows(env.ctx, d_logp, C, q.truth, n_local, q.d_list, q.n, C, beta, bins, d_cnt, d_cor, d_conf));
+    std::vector<int32_t> h(2 * (size_t)bins);
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, h.data(), d_cnt, h.size() * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, conf_sum, d_conf, (size_t)bins * sizeof(double)));
+    std::copy(h.begin(), h.begin() + bins, count);
+    std::copy(h.begin() + bins, h.end(), correct);
+}
+
+void HipGCN::calibration(int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count, int64_t *correct, double *conf_sum) {
+    calib_check("calibration", temperature, bins);
+    if (split < 0 || split > 3 || n < 0 || !sums || !count || !correct || !conf_sum)
+        throw GcnHipFailure(-1, "calibration: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
+    const int C = params.output_dim;
+    const ScoredRows q = scored_rows("calibration", split, nodes, n);
+    forward_logp(q.subset);
+    const float beta = 1.f / temperature;
+    GCNHIP_CHECK(gcnhip_calib_nll_rows(env.ctx, d_logp, C, q.truth, n_local, q.d_list, q.n, C, beta, d_calib_sums));
+    GCNHIP_CHECK(gcnhip_d2h(env.ctx, sums, d_calib_sums, 4 * sizeof(double)));
+    calib_bins_download(q, beta, bins, 0, count, correct, conf_sum);
+    sync();
+}
+
+HipGCN::Calibrated HipGCN::calibrate(int split, int bins, int64_t *count, int64_t *correct, double *conf_sum) {
+    calib_check("calibrate", 1.f, bins ? bins : 1);            // bins == 0: no reliability counts
+    if (split < 1 || split > 3) throw GcnHipFailure(-1, "calibrate: split is 1 (train), 2 (validation) or 3 (test)");
+    if (bins && (!count || !correct || !conf_sum)) throw GcnHipFailure(-1, "calibrate: invalid argument");
+    if (split_count[split] < 1) throw GcnHipFailure(-1, "calibrate: split " + std::to_string(split) + " has no labelled rows to fit on");
+    const int C = params.output_dim;
+    const ScoredRows q = scored_rows("calibrate", split, nullptr, 0);
+    forward_logp(q.subset);
+    double s[4];
+    auto nll_at = [&](double beta) {                           // one launch, 32 bytes back
+        GCNHIP_CHECK(gcnhip_calib_nll_rows(env.ctx, d_logp, C, q.truth, n_local, q.d_list, q.n, C, (float)beta, d_calib_sums));
+        GCNHIP_CHECK(gcnhip_d2h(env.ctx, s, d_calib_sums, sizeof s));
+    };
+    constexpr double LO = 0.01, HI = 100.0;
+    double lo = LO, hi = HI, beta = 1.0;
+    nll_at(beta);
+    if (!(s[3] >= 1.0)) throw GcnHipFailure(-1, "calibrate: split " + std::to_string(split) + " has no labelled rows to fit on");
+    Calibrated out;
+    out.rows = (int64_t)s[3];
+    out.nll_before = s[0] / s[3];
+    while (out.steps < 40) {
+        const double g = s[1], h = s[2];
+        if (g > 0) hi = beta;                                  // convex: the minimum lies where the gradient points away from
+        else if (g < 0) lo = beta;
+        else break;
+        double next = h > 0 ? beta - g / h : 0.0;
+        // no minimum seen yet on the side the step goes to (that end is still the outer limit): at least a factor 2, so that a
+        // minimum that is not there — the tail of a perfectly classified split, where a Newton step is a constant — is left behind
+        if (h > 0 && g < 0 && hi == HI) next = std::max(next, 2 * beta);
+        if (h > 0 && g > 0 && lo == LO) next = std::min(next, beta / 2);
+        if (!(h > 0) || !(next > lo && next < hi)) next = std::sqrt(lo * hi);
+        next = (double)(float)next;                            // the kernels take an f32 beta: iterate on the values they see
+        const double delta = std::fabs(next - beta);
+        beta = next;
+        out.steps++;
+        nll_at(beta);
+        if (delta <= 1e-6 * beta) break;
+    }
+    out.temperature = (float)(1.0 / beta);
+    out.nll_after = s[0] / s[3];
+    // on an end of the bracket — or the gradient vanished in f32 before any minimum was bracketed on that side
+    out.at_bound = (hi == HI && (beta >= HI * (1 - 1e-4) || (s[1] == 0 && beta > 1))) || (lo == LO && (beta <= LO * (1 + 1e-4) || (s[1] == 0 && beta < 1)));
+    if (bins) {
+        calib_bins_download(q, 1.f, bins, 0, count, correct, conf_sum);
+        calib_bins_download(q, 1.f / out.temperature, bins, 1, count + bins, correct + bins, conf_sum + bins);
+    }
+    sync();
+    return out;
 }
 
 void HipGCN::save_weights(const char *path) {

@@ -49,6 +49,13 @@
 //                            each for cs, alpha 0.9 / 50 iterations for lp) and one more line is printed:
 //                            `smoothed_test_acc=<share of the test split whose smoothed class is its label>`.  GCN_PREDICT then
 //                            writes the smoothed classes, one line `node class` per node.  One GPU, single-label.
+//   GCN_CALIBRATE=<file>     directly after the test line (before GCN_REPORT / GCN_SMOOTH / GCN_PREDICT, which then see the temperature):
+//                            one scalar temperature T is fitted on the VALIDATION split by minimising the negative log-likelihood of
+//                            softmax(z / T) (HipGCN::calibrate), set on the model, and one line is printed:
+//                            `temperature=<T> val_nll_before=<x> val_nll_after=<y> test_ece_before=<a> test_ece_after=<b>` (ECE: expected
+//                            calibration error of the TEST split, 15 bins).  The file gets the test split's reliability table at
+//                            T = 1 and at the fitted T (host/calibration.h: a summary line, then one line per bin).  Works with
+//                            GCN_LOAD_WEIGHTS and 0 epochs.  One GPU, single-label, at most 64 classes.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -70,6 +77,7 @@
 #include <thread>
 #include <unistd.h>
 #include <vector>
+#include "calibration.h"
 #include "class_weights.h"
 #include "gcn.h"
 #include "hip_check.h"
@@ -166,6 +174,19 @@ int main(int argc, char **argv) {
         }
     }
 
+    const char *calibrate_path = getenv("GCN_CALIBRATE");
+    if (calibrate_path && !*calibrate_path) calibrate_path = nullptr;
+    if (calibrate_path) {
+        const char *why = multilabel_path              ? "fits the temperature of a single-label model (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1 ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > 64     ? "takes at most 64 classes"
+                                                       : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_CALIBRATE " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     int n_dev = 0;
     if (gcnhip_device_count(&n_dev) != 0 || n_dev < 1) {
         std::cerr << "gcn-hip: no GPU available (this backend has no CPU path; use gcn-seq)" << std::endl;
@@ -224,6 +245,30 @@ int main(int argc, char **argv) {
             if (save_path && rank == 0) {
                 gcn.save_weights(save_path);
                 fprintf(stderr, "gcn-hip: weights written to %s\n", save_path);
+            }
+            if (calibrate_path) {                              // one rank (checked above)
+                constexpr int BINS = 15;
+                const HipGCN::Calibrated fit = gcn.calibrate(2, 0, nullptr, nullptr, nullptr);
+                double sums[2][4], conf[2][BINS];
+                int64_t count[2][BINS], correct[2][BINS];
+                CalibrationReport rep[2];
+                const float T[2] = {1.f, fit.temperature};
+                std::string err;
+                for (int k = 0; k < 2; k++) {
+                    gcn.calibration(3, nullptr, 0, T[k], BINS, sums[k], count[k], correct[k], conf[k]);
+                    if (gcn_calibration_report(BINS, count[k], correct[k], conf[k], &rep[k], &err) != 0) throw GcnHipFailure(-1, err);
+                }
+                gcn.set_temperature(fit.temperature);
+                printf("temperature=%.5f val_nll_before=%.5f val_nll_after=%.5f test_ece_before=%.5f test_ece_after=%.5f\n", fit.temperature,
+                       fit.nll_before, fit.nll_after, rep[0].ece, rep[1].ece);
+                FILE *f = fopen(calibrate_path, "w");
+                bool ok = f != nullptr;
+                for (int k = 0; ok && k < 2; k++)
+                    ok = gcn_calibration_table_write(f, T[k], sums[k][3] > 0 ? sums[k][0] / sums[k][3] : 0.0, BINS, count[k], rep[k]);
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the reliability tables to ") + calibrate_path);
+                fprintf(stderr, "gcn-hip: reliability tables of the test split written to %s%s\n", calibrate_path,
+                        fit.at_bound ? " (the fit stopped on an end of its bracket: the validation split is classified perfectly)" : "");
             }
             if (predict_path && multilabel_path) {             // the same, as class sets
                 const int n = gcn.local_rows(), r0 = gcn.row_start();

@@ -328,6 +328,81 @@ class HipGCNModel:
             "correct_and_smooth")
         return pred[:n], g
 
+    # ---- temperature scaling and calibration error: can predict()'s probabilities be trusted, and one scalar that repairs them
+    def _calib_args(self, what, bins=None, temperature=None):
+        """argument checks that need no GPU"""
+        if self.multilabel:
+            raise GcnHostError(f"{what}: this is a multi-label model (a temperature scales one softmax per node)")
+        if self.params.output_dim > 64:
+            raise GcnHostError(f"{what}: at most 64 classes, this model has {self.params.output_dim}")
+        if bins is not None and (int(bins) != bins or not 1 <= bins <= 64):
+            raise GcnHostError(f"{what}: bins must be an integer in 1..64, got {bins!r}")
+        if temperature is not None and not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
+            raise GcnHostError(f"{what}: the temperature must be finite and > 0, got {temperature!r}")
+
+    @property
+    def temperature(self):
+        """the temperature T of predict()'s softmax(z / T) and of correct_and_smooth's starting point (1 unless set)"""
+        t = C.c_float()
+        _ck(self.lib, self.lib.gcnhost_model_temperature(self.h, C.byref(t)), "temperature")
+        return t.value
+
+    def set_temperature(self, temperature):
+        """From now on predict() returns prob (and logp) of softmax(z / T) — pred does not depend on T — and correct_and_smooth()
+        starts from that softmax.  At T = 1 both run exactly what they ran before.  Training, eval, evaluate and the weights file
+        ignore the temperature."""
+        if float(temperature) != 1.0:
+            self._calib_args("set_temperature", temperature=temperature)
+        _ck(self.lib, self.lib.gcnhost_model_set_temperature(self.h, float(temperature)), "set_temperature")
+
+    def calibrate(self, split=2, bins=15, apply=True):
+        """Temperature scaling (Guo et al., 2017): fits T on the labelled rows of `split` (the validation split) by minimising the
+        negative log-likelihood of softmax(z / T) — one evaluation forward, then a safeguarded Newton iteration in beta = 1 / T on
+        [0.01, 100] whose every step is one small launch.  Returns a dict: temperature, nll_before / nll_after (mean NLL of the
+        split at T = 1 and at the fit), steps, at_bound (the fit stopped on an end of the bracket: a split classified perfectly
+        has no minimum), rows, and ece_before / ece_after of the same split over `bins` bins.  apply=True then sets the
+        temperature.  Single-label models, at most 64 classes, one rank.  Training state is not touched."""
+        self._calib_args("calibrate", bins=bins)
+        if split not in (1, 2, 3):
+            raise GcnHostError(f"calibrate: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        out = np.zeros(6, np.float64)
+        count, correct, conf = np.zeros((2, bins), np.int64), np.zeros((2, bins), np.int64), np.zeros((2, bins), np.float64)
+        _ck(self.lib, self.lib.gcnhost_model_calibrate(self.h, int(split), int(bins), out.ctypes.data, count.ctypes.data, correct.ctypes.data,
+                                                       conf.ctypes.data), "calibrate")
+        res = dict(temperature=float(out[0]), nll_before=float(out[1]), nll_after=float(out[2]), steps=int(out[3]), at_bound=bool(out[4]),
+                   rows=int(out[5]), ece_before=calibration_report(count[0], correct[0], conf[0])["ece"],
+                   ece_after=calibration_report(count[1], correct[1], conf[1])["ece"])
+        if apply:
+            self.set_temperature(res["temperature"])
+        return res
+
+    def calibration(self, split=None, nodes=None, temperature=None, bins=15):
+        """Reliability of softmax(z / T): one evaluation forward over the labelled rows of `split` (1 train, 2 validation, 3 test) or,
+        with split=None, of the `nodes` query with predict()'s conventions (None: every row), then the negative log-likelihood
+        and the reliability diagram formed on the GPU.  temperature=None: the model's own.  Returns a dict: nll (mean), ece, mce,
+        rows, and per bin (b / bins, (b + 1) / bins] count (int64), accuracy and confidence (float64, 0 for an empty bin).
+        Single-label models, at most 64 classes, one rank.  Training state is not touched."""
+        self._calib_args("calibration", bins=bins, temperature=temperature)
+        if split is not None and nodes is not None:
+            raise GcnHostError("calibration: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"calibration: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if nodes is None:
+            n, qp = 0, None
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = q.size
+            q = q if n else np.zeros(1, np.int32)              # an empty query is still a query (not "every row")
+            qp = q.ctypes.data
+        t = self.temperature if temperature is None else float(temperature)
+        sums = np.zeros(4, np.float64)
+        count, correct, conf = np.zeros(bins, np.int64), np.zeros(bins, np.int64), np.zeros(bins, np.float64)
+        _ck(self.lib, self.lib.gcnhost_model_calibration(self.h, int(split or 0), qp, n, t, int(bins), sums.ctypes.data, count.ctypes.data,
+                                                         correct.ctypes.data, conf.ctypes.data), "calibration")
+        out = calibration_report(count, correct, conf)
+        out.update(nll=float(sums[0] / sums[3]) if sums[3] else 0.0, temperature=t, sums=sums)
+        return out
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")
@@ -409,6 +484,23 @@ def class_report(confusion=None, tp=None, fp=None, fn=None):
                                       summ.ctypes.data), "class_report")
     return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
                 macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
+
+
+def calibration_report(count, correct, conf_sum):
+    """The reliability diagram from per-bin counts — host only, no GPU; the one place it is derived (host/calibration.h).  count,
+    correct (integers) and conf_sum (float64) [bins]: rows, rows predicted right and the sum of confidences in bin (b / bins,
+    (b + 1) / bins].  Returns a dict: count (int64), accuracy = correct / count and confidence = conf_sum / count (float64, 0 for
+    an empty bin), ece = sum_b (count_b / rows) |accuracy_b - confidence_b|, mce = the largest gap of a non-empty bin, rows.  Arrays
+    of different lengths, correct above count or a negative entry raise GcnHostError."""
+    c, k, s = (np.ascontiguousarray(count, np.int64).ravel(), np.ascontiguousarray(correct, np.int64).ravel(),
+               np.ascontiguousarray(conf_sum, np.float64).ravel())
+    if not (c.size == k.size == s.size) or c.size < 1:
+        raise GcnHostError(f"calibration_report: count, correct and conf_sum must have one length >= 1, got {[c.size, k.size, s.size]}")
+    lib = _lib.gcnhost()
+    acc, conf, summ = np.zeros(c.size, np.float64), np.zeros(c.size, np.float64), np.zeros(3, np.float64)
+    _ck(lib, lib.gcnhost_calibration_report(c.size, c.ctypes.data, k.ctypes.data, s.ctypes.data, acc.ctypes.data, conf.ctypes.data,
+                                            summ.ctypes.data), "calibration_report")
+    return dict(count=c.copy(), accuracy=acc, confidence=conf, ece=float(summ[0]), mce=float(summ[1]), rows=int(summ[2]))
 
 
 def balanced_class_weights(labels_or_y, split, num_classes, which_split=1):

@@ -295,6 +295,51 @@ class Device:
             raise GcnHipError(f"gcnhip_cs_correct_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return gb.download()
 
+    def _calib_inputs(self, logp, ld, truth, rows):
+        logp = np.ascontiguousarray(logp, np.float32)
+        n_table, c = logp.shape
+        lb = self.padded(logp, ld or c)
+        tb = self.buf(np.ascontiguousarray(truth, np.int32) if n_table else np.zeros(1, np.int32)) if truth is not None else None
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        return lb, tb, rb, n_table, c, int(n_table if rows is None else rows.size)
+
+    def calib_nll_rows(self, logp, truth, beta, rows=None, ld=None, n=None):
+        """gcnhip_calib_nll_rows: float64 [4] = {sum nll, sum g, sum h, rows counted}.  logp f32 [n_table, C] (uploaded with row
+        stride ld, NaN padding), truth int32 [n_table]; rows: the listed rows (None: rows 0 .. n - 1, n = n_table unless given)"""
+        lb, tb, rb, n_table, c, listed = self._calib_inputs(logp, ld, truth, rows)
+        ob = self.buf(np.full(4, np.nan, np.float64))
+        rc = self.lib.gcnhip_calib_nll_rows(self.ctx, lb.ptr, ld or c, tb.ptr, n_table, rb.ptr if rb else None, listed if n is None else int(n), c,
+                                            float(beta), ob.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_calib_nll_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return ob.download()
+
+    def calib_bins_rows(self, logp, truth, beta, bins, rows=None, ld=None):
+        """gcnhip_calib_bins_rows: (count int32 [bins], correct int32 [bins], conf_sum float64 [bins]); the outputs are uploaded as
+        garbage — the launch zeroes or overwrites them"""
+        lb, tb, rb, n_table, c, listed = self._calib_inputs(logp, ld, truth, rows)
+        k = max(int(bins), 1)
+        cb, kb = self.buf(np.full(k, 12345, np.int32)), self.buf(np.full(k, -777, np.int32))
+        sb = self.buf(np.full(k, np.nan, np.float64))
+        rc = self.lib.gcnhip_calib_bins_rows(self.ctx, lb.ptr, ld or c, tb.ptr, n_table, rb.ptr if rb else None, listed, c, float(beta), int(bins),
+                                             cb.ptr, kb.ptr, sb.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_calib_bins_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return cb.download(), kb.download(), sb.download()
+
+    def calib_scale_rows(self, logp, beta, rows=None, ld=None, ld_out=None, in_place=False, fill=np.nan):
+        """gcnhip_calib_scale_rows: (out [n_table, ld_out] — rows not listed and padding columns keep `fill` —, prob f32 [n_table],
+        `fill` where no row was scaled).  in_place=True: out is the uploaded logp table itself (its own stride and contents)"""
+        lb, _, rb, n_table, c, listed = self._calib_inputs(logp, ld, None, rows)
+        ld_out = (ld or c) if in_place else (ld_out or c)
+        ob = lb if in_place else self.buf(np.full((n_table, ld_out), fill, np.float32))
+        pb = self.buf(np.full(max(n_table, 1), fill, np.float32))
+        rc = self.lib.gcnhip_calib_scale_rows(self.ctx, lb.ptr, ld or c, n_table, rb.ptr if rb else None, listed, c, float(beta), ob.ptr, ld_out, pb.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_calib_scale_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return ob.download(), pb.download()[:n_table]
+
     def graphsum(self, g: "Graph", x, ld_in=None, ld_out=None, row_nonzero=None):
         x = np.asarray(x, np.float32)
         dim = x.shape[1]

@@ -212,6 +212,29 @@ int gcnhip_cs_error_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, const 
                          int n_listed, int num_classes, float *e, int ld_e, float *d_sigma);
 int gcnhip_cs_correct_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, const float *e_hat, int ld_e, const int32_t *truth, int n_table,
                            int num_classes, const float *d_sigma, float *g0, int ld_g);
+/* ---- temperature scaling and calibration error (calib.hip; beyond the reference: are the softmax probabilities to be trusted?) ----
+ * Row-local passes over log-softmax rows as gcnhip_graphsum_predict writes them: a wave per row, lane j on class j
+ * (1 <= num_classes <= 64, rows of any stride >= num_classes).  With l_j = logp[r, j], beta = 1 / T (finite, > 0) and
+ * p = softmax(beta . l), formed with the row maximum subtracted; entries with p_j == 0 contribute nothing (a column at -1e4
+ * gives no NaN).  The listed rows are d_rows[i], i < n, or 0 .. n - 1 when d_rows == NULL (then n <= n_table); ids outside
+ * [0, n_table) and, where truth is an argument, rows whose truth[r] is outside [0, C) are skipped.  Per-row values are f32;
+ * sums over rows are doubles formed in a fixed order (rows in row order per wave, block partials in block order by a one-block
+ * finalize launch; no float or double atomics), so two launches give the same bits.  No launch allocates or synchronises.
+ * Anything else returns -1 with a message (gcnhip_last_error).
+ * gcnhip_calib_nll_rows: d_out[4] = {sum nll_r, sum g_r, sum h_r, rows counted}: nll_r = lse(beta . l) - beta . l_t,
+ *   g_r = mu - l_t with mu = sum_j p_j l_j (d nll / d beta), h_r = sum_j p_j (l_j - mu)^2 >= 0 (d2 nll / d beta2, the centred sum).
+ * gcnhip_calib_bins_rows (1 <= bins <= 64): per counted row conf = max_j p_j, pred = the largest l_j (lowest column on a tie),
+ *   bin b = clamp(ceil(conf . bins) - 1, 0, bins - 1) — the (b / B, (b + 1) / B] rule of Guo et al.; d_count[b] rows, d_correct[b]
+ *   those with pred == truth (int32, zeroed on the stream first, integer adds), d_conf_sum[b] the sum of conf (double).
+ * gcnhip_calib_scale_rows: out_logp[r, :] = beta . l - lse(beta . l) for every listed row inside the table (no truth), and
+ *   d_prob[r] = expf(max_j out_logp[r, j]) when d_prob != NULL.  out_logp may be logp (a wave holds its row before it stores);
+ *   the listed rows must then be distinct. */
+int gcnhip_calib_nll_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
+                          int num_classes, float beta, double *d_out);
+int gcnhip_calib_bins_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
+                           int num_classes, float beta, int bins, int32_t *d_count, int32_t *d_correct, double *d_conf_sum);
+int gcnhip_calib_scale_rows(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, float beta,
+                            float *out_logp, int ld_out, float *d_prob);
 /* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
  * subsets made at call time, such as the node queries of a prediction. */
 int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);

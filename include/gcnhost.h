@@ -196,6 +196,33 @@ int gcnhost_model_propagate(gcnhost_model *m, const float *y0, int dim, float al
 int gcnhost_model_label_propagation(gcnhost_model *m, float alpha, int iters, int splits_mask, int32_t *pred, float *y);
 int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth,
                                      int splits_mask, int32_t *pred, float *g);
+/* Temperature scaling and calibration error (beyond the reference; Guo et al., 2017).  predict's probabilities are softmax(z / T)
+ * with one scalar T, 1 by default; these fit it, measure what it does, and set it.  All work on the log-softmax rows of one
+ * evaluation forward kept on the device, with the row-local kernels gcnhip_calib_nll_rows / _bins_rows / _scale_rows, and hold
+ * gcnhost_model_predict's contract: the call synchronises first and the training state is untouched.  Single-label models, at most
+ * 64 classes, one rank; 1 <= bins <= 64; a temperature is finite and > 0: anything else is refused with a message before any launch.
+ *
+ * gcnhost_model_calibration: the rows of `split` (1 train, 2 validation, 3 test), or with split == 0 the `nodes` query (n dataset
+ * ids; NULL: every row) scored against the dataset's labels, at `temperature`.  sums[4] = {sum of the rows' negative
+ * log-likelihood, its first and second derivative in beta = 1 / T, rows counted}; count / correct / conf_sum [bins]: rows, rows
+ * predicted right and the sum of confidences (largest probability) per bin (b / bins, (b + 1) / bins].
+ * gcnhost_model_calibrate: fits T on `split` by a safeguarded Newton iteration on the convex NLL(beta), beta in [0.01, 100], one
+ * launch and a 32-byte copy per step.  out[6] = {T, mean NLL at T = 1, mean NLL at the result, steps, 1 when the result sits on
+ * an end of the bracket (a split classified perfectly), rows}.  bins > 0: count / correct / conf_sum [2 x bins] = the reliability
+ * counts of the same rows at T = 1 and at the fitted T; bins == 0: the three may be NULL.  It does not set the temperature.
+ * gcnhost_model_set_temperature: from now on predict returns prob (and logp) at this T (pred does not depend on it) and
+ * correct_and_smooth starts from the calibrated softmax; at T = 1 both launch exactly what they did.  Training, eval, evaluate and
+ * the weights file ignore it.
+ * gcnhost_calibration_report, host only (host/calibration.h): accuracy / confidence [bins] per bin (0 for an empty bin),
+ * summary[3] = {ECE = sum_b (count_b / rows) |accuracy_b - confidence_b|, MCE = the largest gap of a non-empty bin, rows};
+ * every output may be NULL. */
+int gcnhost_model_calibration(gcnhost_model *m, int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count,
+                              int64_t *correct, double *conf_sum);
+int gcnhost_model_calibrate(gcnhost_model *m, int split, int bins, double *out, int64_t *count, int64_t *correct, double *conf_sum);
+int gcnhost_model_set_temperature(gcnhost_model *m, float temperature);
+int gcnhost_model_temperature(gcnhost_model *m, float *temperature);
+int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
+                               double *confidence, double *summary);
 /* Per-class metrics from integer counts, host only (host/report.h): either confusion [C x C] (row = truth, column =
  * prediction) or tp / fp / fn [C] (the other form NULL).  Every output may be NULL: tp_fp_fn [3 x C] the counts used; support
  * (TP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), f1 = 2 TP / (2 TP + FP + FN) [C], float64, each 0 when
