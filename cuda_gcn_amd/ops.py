@@ -608,11 +608,57 @@ class Device:
         _ck(self.lib, self.lib.gcnhip_dropout_bwd(self.ctx, g.ptr, mb.ptr, g.shape[0], p), "gcnhip_dropout_bwd")
         return g.download()
 
-    def relu_dropout_bwd(self, grad, h, scale):
+    def relu_dropout_bwd(self, grad, h, scale, ld_grad=None, ld_h=None, dim=None):
+        """gcnhip_relu_dropout_bwd.  Packed by default (grad and h are [rows, dim]).  With ld_grad / ld_h given, grad is the WHOLE
+        buffer [rows, ld_grad] and h the whole buffer [rows, ld_h], padding included, `dim` (required then) the logical width;
+        the whole grad buffer comes back, so the padding can be inspected."""
         grad, h = np.asarray(grad, np.float32), np.asarray(h, np.float32)
+        if ld_grad is None and ld_h is None and dim is None:
+            ld_grad, ld_h, dim = grad.shape[1], h.shape[1], grad.shape[1]
+        else:
+            ld_grad, ld_h = ld_grad or grad.shape[1], ld_h or h.shape[1]
+            if dim is None or grad.shape[1] != ld_grad or h.shape[1] != ld_h or grad.shape[0] != h.shape[0]:
+                raise ValueError("relu_dropout_bwd: the strided form takes whole buffers [rows, ld_grad], [rows, ld_h] and dim")
         g, hb = self.buf(np.ascontiguousarray(grad)), self.buf(np.ascontiguousarray(h))
-        _ck(self.lib, self.lib.gcnhip_relu_dropout_bwd(self.ctx, g.ptr, grad.shape[1], hb.ptr, h.shape[1], grad.shape[0], grad.shape[1], scale), "relu_dropout_bwd")
+        _ck(self.lib, self.lib.gcnhip_relu_dropout_bwd(self.ctx, g.ptr, ld_grad, hb.ptr, ld_h, grad.shape[0], dim, scale), "relu_dropout_bwd")
         return g.download()
+
+    # ---- the strided forms (module.cpp's calls: ld > cols).  x / grad are WHOLE buffers [rows, ld], padding included, and come
+    # back whole; masks and keep decisions are flat [rows . cols], keyed by r . cols + c
+    def relu_fwd_2d(self, x, cols, training=True, mask_fill=0):
+        """gcnhip_relu_fwd_2d -> (buffer [rows, ld], mask uint8 [rows . cols], uploaded as mask_fill)"""
+        x = np.ascontiguousarray(x, np.float32)
+        rows, ld = x.shape
+        xb = self.buf(x)
+        mb = self.buf(np.full(max(rows * cols, 1), mask_fill, np.uint8))
+        _ck(self.lib, self.lib.gcnhip_relu_fwd_2d(self.ctx, xb.ptr, ld, rows, int(cols), mb.ptr, int(training)), "gcnhip_relu_fwd_2d")
+        return xb.download(), mb.download()[:rows * cols]
+
+    def relu_bwd_2d(self, grad, cols, mask):
+        grad = np.ascontiguousarray(grad, np.float32)
+        rows, ld = grad.shape
+        gb, mb = self.buf(grad), self.buf(np.ascontiguousarray(mask, np.uint8))
+        _ck(self.lib, self.lib.gcnhip_relu_bwd_2d(self.ctx, gb.ptr, ld, rows, int(cols), mb.ptr), "gcnhip_relu_bwd_2d")
+        return gb.download()
+
+    def dropout_fwd_2d(self, x, cols, p, seed=0, epoch=0, elem_offset=0, keep_in=None, want_mask=True):
+        """gcnhip_dropout_fwd_2d -> (buffer [rows, ld], mask int32 [rows . cols] or None)"""
+        x = np.ascontiguousarray(x, np.float32)
+        rows, ld = x.shape
+        xb = self.buf(x)
+        mb = self.buf(np.full(max(rows * cols, 1), -1, np.int32)) if want_mask else None
+        ep = self.buf(np.array([epoch], np.uint32))
+        kb = self.buf(np.ascontiguousarray(keep_in, np.uint8)) if keep_in is not None else None
+        _ck(self.lib, self.lib.gcnhip_dropout_fwd_2d(self.ctx, xb.ptr, ld, rows, int(cols), mb.ptr if mb else None, p, seed, ep.ptr, elem_offset,
+                                                      kb.ptr if kb else None), "gcnhip_dropout_fwd_2d")
+        return xb.download(), (mb.download()[:rows * cols] if mb else None)
+
+    def dropout_bwd_2d(self, grad, cols, mask, p):
+        grad = np.ascontiguousarray(grad, np.float32)
+        rows, ld = grad.shape
+        gb, mb = self.buf(grad), self.buf(np.ascontiguousarray(mask, np.int32))
+        _ck(self.lib, self.lib.gcnhip_dropout_bwd_2d(self.ctx, gb.ptr, ld, rows, int(cols), mb.ptr, p), "gcnhip_dropout_bwd_2d")
+        return gb.download()
 
     def xent_fwd(self, logits, truth, training=True, count=0, shift_in_place=True, ld=None):
         """returns dict(loss_sum, count, correct, total, logits, grad)"""
@@ -815,6 +861,43 @@ class Device:
             else:
                 _ck(self.lib, self.lib.gcnhip_adam_step(self.ctx, arr, len(ws), float(step), None, None, beta1, beta2, eps, weight_decay, sq.ptr), "gcnhip_adam_step")
         return [b["w"].download() for b in bufs], float(sq.download()[0])
+
+    def adam_step_state(self, ws=None, gs=None, ms=None, vs=None, decays=None, step_size=0.0, weight_decay=0.0, beta1=0.9, beta2=0.999,
+                        eps=1e-8, step_table=None, epoch_words=None, advance=False, want_sumsq=True, state=None):
+        """ONE launch of gcnhip_adam_step (advance=False) or gcnhip_adam_step_advance (advance=True) from GIVEN state: ws, gs, ms,
+        vs are lists of arrays, one per variable, uploaded as they are.  step_table: a device Buf of f32 step sizes (then
+        epoch_words is required: the launch reads step_table[*d_epoch], d_epoch = the first word of epoch_words, and the scalar
+        step_size is ignored); epoch_words: a device Buf of two uint32 [counter, done] — with advance=True the launch moves
+        them, and d_epoch is that same counter word, as HipAdam::step passes it.  want_sumsq=False passes d_sumsq = NULL.
+        Returns dict(w, m, v: lists of arrays, sumsq: f32 value or None, state).  Passing the returned `state` back in keeps the
+        device buffers (w, m, v carry on; ws / ms / vs are then ignored, gs — if given — is uploaded as the new gradients)."""
+        if state is None:
+            bufs = []
+            for w, g, m, v in zip(ws, gs, ms, vs):
+                w, g, m, v = (np.ascontiguousarray(t, np.float32).reshape(-1) for t in (w, g, m, v))
+                assert w.size == g.size == m.size == v.size
+                bufs.append(dict(w=self.buf(w), g=self.buf(g), m=self.buf(m), v=self.buf(v), n=w.size))
+            arr = (_lib.AdamVar * len(bufs))()
+            for k, b in enumerate(bufs):
+                arr[k] = _lib.AdamVar(b["w"].ptr, b["g"].ptr, b["m"].ptr, b["v"].ptr, b["n"], int(decays[k]))
+            state = dict(bufs=bufs, arr=arr, sq=self.buf(np.full(1, np.nan, np.float32)))
+        elif gs is not None:
+            for b, g in zip(state["bufs"], gs):
+                b["g"].upload(np.ascontiguousarray(g, np.float32).reshape(-1))
+        bufs, arr, sq = state["bufs"], state["arr"], state["sq"]
+        if (step_table is not None or advance) and epoch_words is None:
+            raise ValueError("adam_step_state: step_table and advance need epoch_words")
+        tab = step_table.ptr if step_table is not None else None
+        d_epoch = epoch_words.ptr if step_table is not None else None
+        d_sq = sq.ptr if want_sumsq else None
+        if advance:
+            _ck(self.lib, self.lib.gcnhip_adam_step_advance(self.ctx, arr, len(bufs), float(step_size), tab, d_epoch, beta1, beta2, eps, weight_decay,
+                                                            d_sq, epoch_words.ptr, epoch_words.ptr + 4), "gcnhip_adam_step_advance")
+        else:
+            _ck(self.lib, self.lib.gcnhip_adam_step(self.ctx, arr, len(bufs), float(step_size), tab, d_epoch, beta1, beta2, eps, weight_decay, d_sq),
+                "gcnhip_adam_step")
+        return dict(w=[b["w"].download() for b in bufs], m=[b["m"].download() for b in bufs], v=[b["v"].download() for b in bufs],
+                    sumsq=sq.download()[0] if want_sumsq else None, state=state)
 
 
 def pack_multihot(y):
