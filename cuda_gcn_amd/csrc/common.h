@@ -2,10 +2,12 @@
 // Wave = 64 lanes everywhere in this directory (CDNA4); nothing here is
 // written for 32-wide warps.
 #pragma once
+#include <memory>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "devbuf.h"
 #include "../../include/gcnhip_driver.h"
 
 #define GCNHIP_TRY(expr)                                   \
@@ -43,26 +45,26 @@ extern const GcnOptionEntry GCN_OPTION_TABLE[];
 extern const int GCN_OPTION_COUNT;
 
 struct gcnhip_ctx {
-    int device;
-    GcnOptions opt;
-    hipStream_t stream;
-    bool own_stream;
-    int n_cu;
+    int device = 0;
+    GcnOptions opt = {};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int n_cu = 0;
     // scratch for block-level partial reductions (xent, sumsq, adam sumsq)
-    float *red_f;       // [RED_SLOTS * 4]
-    int32_t *red_i;     // [RED_SLOTS * 4]
-    uint32_t *ticket;   // arrival counters for last-block reductions: [0] the loss kernels, [1] Adam's sum of squares; zero between launches
+    DevBuf<float> red_f;       // [RED_SLOTS * 4]
+    DevBuf<int32_t> red_i;     // [RED_SLOTS * 4]
+    DevBuf<uint32_t> ticket;   // arrival counters for last-block reductions: [0] the loss kernels, [1] Adam's sum of squares; zero between launches
     // gcnhip_metrics_record_with_next_loss: the next loss launch on this context writes the ring row itself
     bool rec_armed = false;
     float *rec_ring = nullptr; int rec_capacity = 0, rec_slot = 0; const uint32_t *rec_epoch = nullptr; const float *rec_sumsq = nullptr;
     // split-K slabs for the dense weight-gradient GEMMs
-    float *slab;
-    size_t slab_bytes;
-    int slab_n;         // partial slabs the last dense weight-gradient product left there (split ranges, or workgroups of the persistent form)
+    DevBuf<float> slab;
+    size_t slab_bytes = 0;
+    int slab_n = 0;     // partial slabs the last dense weight-gradient product left there (split ranges, or workgroups of the persistent form)
     // packed weight image of the persistent forward GEMM (dense_persist.h), sized once at creation
-    float *wpack;
-    size_t wpack_bytes;
-    int corun;          // gcnhip_ctx_set_corun: this stream's kernels are meant to share the chip with another stream's
+    DevBuf<float> wpack;
+    size_t wpack_bytes = 0;
+    int corun = 0;      // gcnhip_ctx_set_corun: this stream's kernels are meant to share the chip with another stream's
 };
 constexpr size_t WPACK_BYTES = (size_t)2 << 20;    // K <= 4096 at p = 128
 constexpr int RED_SLOTS = 4096;
@@ -71,66 +73,74 @@ constexpr int RED_SLOTS = 4096;
 // object's current row schedule (rebuilt whenever that changes).  Segment slots are the full schedule's.
 struct gcnhip_graph;
 struct gcnhip_rowset {
-    const gcnhip_graph *owner;    // the adjacency object the subset was registered on (its task lists and segment slots)
+    const gcnhip_graph *owner = nullptr;   // the adjacency object the subset was registered on (its task lists and segment slots)
     std::vector<uint32_t> bits;   // host copy: bit r = row r is in the subset
-    int n_tasks;
-    int4 *tasks;
-    int n_split_rows;
-    int4 *split_rows;
-    int bounds[4][9];
+    int n_tasks = 0;
+    DevBuf<int4> tasks;
+    int n_split_rows = 0;
+    DevBuf<int4> split_rows;
+    int bounds[4][9] = {};
 };
 
 struct gcnhip_graph {
-    int n_rows, n_cols, nnz;
-    int *indptr;        // [n_rows+1]
-    int *indices;       // [nnz]
-    float *coef;        // [nnz]
+    int n_rows = 0, n_cols = 0, nnz = 0;
+    DevBuf<int> indptr;        // [n_rows+1]
+    DevBuf<int> indices;       // [nnz]
+    DevBuf<float> coef;        // [nnz]
     // Â = D^-1/2 (A+I) D^-1/2 factored instead of stored per edge (gcnhip_graphsum_ex, scaling != 0):
     // dinv = (float)(1/sqrt(deg)), dinv2 = (float)(1/deg), deg = the FULL graph's degrees (a restricted object copies its parent's)
-    float *dinv_row, *dinv2_row;   // [n_rows]
-    float *dinv_col, *dinv2_col;   // [n_cols]
+    DevBuf<float> dinv_row, dinv2_row;   // [n_rows]
+    DevBuf<float> dinv_col, dinv2_col;   // [n_cols]
     // long-row splitting (rows above SPLIT_EDGES are cut into segments)
-    int split_edges_opt; // the creating context's split_edges option (0: by size)
-    int n_tasks;        // number of (row, e0, e1) tasks; 0 => one task per row
-    int4 *tasks;        // {row, e_begin, e_end, partial_slot or -1}
-    int n_split_rows;   // rows that own partial slots
-    int4 *split_rows;   // {row, first_slot, n_slots, 0}
-    float *partials;    // [n_slots * part_ld]
-    int part_ld;
-    int n_slots;
+    int split_edges_opt = 0; // the creating context's split_edges option (0: by size)
+    int n_tasks = 0;        // number of (row, e0, e1) tasks; 0 => one task per row
+    DevBuf<int4> tasks;        // {row, e_begin, e_end, partial_slot or -1}
+    int n_split_rows = 0;   // rows that own partial slots
+    DevBuf<int4> split_rows;   // {row, first_slot, n_slots, 0}
+    DevBuf<float> partials;    // [n_slots * part_ld]
+    int part_ld = 0;
+    int n_slots = 0;
     // task ranges of equal edge count for 1, 2, 4 or 8 XCD groups: bounds[log2 G][g] .. bounds[log2 G][g+1]
-    int bounds[4][9];
-    int *tmp_col_deg;   // only during construction
-    std::vector<int> *h_indptr;   // host copy of the row pointers (the schedule can be rebuilt)
-    std::vector<int4> *h_tasks, *h_srows;   // host copies of the full schedule (row subsets are cut from them)
-    std::vector<gcnhip_rowset *> *rowsets;   // owned
+    int bounds[4][9] = {};
+    std::vector<int> h_indptr;    // host copy of the row pointers (the schedule can be rebuilt)
+    std::vector<int4> h_tasks, h_srows;     // host copies of the full schedule (row subsets are cut from them)
+    std::vector<std::unique_ptr<gcnhip_rowset>> rowsets;
 };
 
 struct gcnhip_feat {
-    int n_rows, n_cols;
-    int64_t nnz;
-    bool dense;
-    int *indptr;        // [n_rows+1] (kept for dense too: row r starts at r*n_cols)
-    int *indices;       // [nnz]; NULL when dense
-    float *values;      // [nnz] pristine X
-    float *values_pad;  // dense X whose rows are not 16-byte aligned: a copy with row stride ld_pad (multiple of 4)
-    int ld_pad;
+    int n_rows = 0, n_cols = 0;
+    int64_t nnz = 0;
+    bool dense = false;
+    DevBuf<int> indptr;        // [n_rows+1] (kept for dense too: row r starts at r*n_cols)
+    DevBuf<int> indices;       // [nnz]; NULL when dense
+    DevBuf<float> values;      // [nnz] pristine X
+    DevBuf<float> values_pad;  // dense X whose rows are not 16-byte aligned: a copy with row stride ld_pad (multiple of 4)
+    int ld_pad = 0;
     // CSC view for the weight gradient (sparse X only)
-    int *csc_ptr;       // [n_cols+1]
-    int *csc_row;       // [nnz] source row of each entry
-    int *csc_pos;       // [nnz] position jj in CSR order (selects value + dropout decision)
-    float *csc_val;     // [nnz] values[csc_pos[q]]: the pristine values in CSC order (one dependent load less per entry)
-    uint32_t *keep_bits; // [ceil(nnz/32)+1] input-dropout decisions of the current call (dense path)
-    int keep_layout;     // how the last producer laid keep_bits out: 0 = flat (bit e & 31 of word e >> 5), 1 = chunk-major (dense_bf16x3.h)
+    DevBuf<int> csc_ptr;       // [n_cols+1]
+    DevBuf<int> csc_row;       // [nnz] source row of each entry
+    DevBuf<int> csc_pos;       // [nnz] position jj in CSR order (selects value + dropout decision)
+    DevBuf<float> csc_val;     // [nnz] values[csc_pos[q]]: the pristine values in CSC order (one dependent load less per entry)
+    DevBuf<uint32_t> keep_bits; // [ceil(nnz/32)+1] input-dropout decisions of the current call (dense path)
+    int keep_layout = 0; // how the last producer laid keep_bits out: 0 = flat (bit e & 31 of word e >> 5), 1 = chunk-major (dense_bf16x3.h)
     // the weight gradient's task list over the CSC view (sparse X, spmm_sparse.h): a column is one task of bwd_nw waves, a
     // column longer than the segment length several tasks whose partial rows a fold launch adds in order
-    int4 *bwd_tasks;    // {column, q_begin, q_end, partial slot or -1}
-    int n_bwd_tasks, bwd_nw;
-    int4 *bwd_split;    // {column, first slot, segments, 0} for the columns that were cut
-    int n_bwd_split, n_bwd_slots;
-    float *bwd_partials; // [n_bwd_slots * bwd_part_ld], sized by the first backward call that needs it (and on a wider call)
-    int bwd_part_ld;
+    DevBuf<int4> bwd_tasks;    // {column, q_begin, q_end, partial slot or -1}
+    int n_bwd_tasks = 0, bwd_nw = 0;
+    DevBuf<int4> bwd_split;    // {column, first slot, segments, 0} for the columns that were cut
+    int n_bwd_split = 0, n_bwd_slots = 0;
+    DevBuf<float> bwd_partials; // [n_bwd_slots * bwd_part_ld], sized by the first backward call that needs it (and on a wider call)
+    int bwd_part_ld = 0;
 };
+
+// a task list and its split list on the device (the adjacency's rows, a row subset, the feature object's columns); an empty list: no block
+static inline int upload_lists(const std::vector<int4> &tasks, const std::vector<int4> &split, DevBuf<int4> &d_tasks, DevBuf<int4> &d_split) {
+    d_tasks.reset();
+    d_split.reset();
+    if (!tasks.empty()) GCNHIP_TRY(d_tasks.upload(tasks.data(), tasks.size()));
+    if (!split.empty()) GCNHIP_TRY(d_split.upload(split.data(), split.size()));
+    return 0;
+}
 
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter-based, so the dropout
 // decision of an element depends only on (seed, epoch, global element index).

@@ -506,9 +506,8 @@ static inline void launch_slab_reduce(const float *slab, int n_workers, int n, i
 static inline int ensure_slab(gcnhip_ctx *c, size_t bytes) {
     if (c->slab_bytes >= bytes) return 0;
     GCNHIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->slab) GCNHIP_TRY(hipFree(c->slab));
-    c->slab = nullptr; c->slab_bytes = 0;
-    GCNHIP_TRY(hipMalloc((void **)&c->slab, bytes));
+    c->slab_bytes = 0;
+    GCNHIP_TRY(c->slab.alloc(bytes / sizeof(float)));
     c->slab_bytes = bytes;
     return 0;
 }

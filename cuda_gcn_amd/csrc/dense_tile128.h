@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void dropbits_kernel(uint32_t *__restrict__ bi
 // The same words when the stream offset is a multiple of 128 (one GPU: 0): a thread owns a whole Philox block = four words,
 // so every Philox call is used in full (dropbits_kernel draws one block per WORD and keeps a quarter of it: 13.8 us per
 // epoch at Reddit size, this form 5) and the words leave as one 16-byte store.  `bits` is 16-byte aligned (hipMalloc) and
-// has slack past the last word (ctx.hip).
+// has slack past the last word (feat.hip).
 __device__ inline void dropbits_block_body(int64_t q, uint32_t *__restrict__ bits, int64_t n_elems, int thr,
                                            uint64_t seed, const uint32_t *d_epoch, uint64_t block0) {
     if (q * 128 >= n_elems) return;                                           // Philox block q = elements 128q .. 128q+127

@@ -236,7 +236,7 @@ static int dense_fwd_bf16x3(gcnhip_ctx *c, const gcnhip_feat *f, const Tile128Ar
     if (zf && !dense_fwd_bf16x3_z0_fits(c, t, d, fast, *zf)) return GCNHIP_NOT_AVAILABLE;   // the caller runs the two products one after the other
     if (!dense_fwd_bf16x3_fits(c, f, t, d, fast, zf != nullptr)) return NOT_MINE;
     const int n_chunks = (t.K + PG_BK - 1) / PG_BK, n_hs = 2 * n_chunks;
-    uint4 *wp3 = reinterpret_cast<uint4 *>(c->wpack);
+    uint4 *wp3 = reinterpret_cast<uint4 *>((float *)c->wpack);
     uint4 *w2img = wp3 + (size_t)n_hs * (BX_BH_BYTES / 16);
     if (d.on) {                                  // keep words (chunk-major) and the packed planes of W from one launch
         const BxBitsArgs kb = keep_bits_cm_args(f, d);
@@ -542,8 +542,8 @@ int gcnhip_spmm_bwd(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, cons
         // the partial rows of cut columns: sized by the first call that needs them (synchronises once, like the split-K slabs)
         gcnhip_feat *fm = const_cast<gcnhip_feat *>(f);
         GCNHIP_TRY(hipStreamSynchronize(c->stream));
-        if (fm->bwd_partials) { GCNHIP_TRY(hipFree(fm->bwd_partials)); fm->bwd_partials = nullptr; fm->bwd_part_ld = 0; }
-        GCNHIP_TRY(hipMalloc((void **)&fm->bwd_partials, (size_t)f->n_bwd_slots * p_ld * sizeof(float)));
+        fm->bwd_part_ld = 0;
+        GCNHIP_TRY(fm->bwd_partials.alloc((size_t)f->n_bwd_slots * p_ld));
         fm->bwd_part_ld = p_ld;
     }
     SpBwdArgs a;

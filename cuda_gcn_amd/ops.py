@@ -960,6 +960,15 @@ class Graph:
         g.dev, g.n_rows, g.n_cols, g.h = self.dev, self.n_rows, self.n_cols, h
         return g
 
+    def clone(self):
+        """a second, independent object with the same edges, coefficients and current row order (gcnhip_graph_clone); row
+        subsets are not copied"""
+        h = C.c_void_p()
+        _ck(self.dev.lib, self.dev.lib.gcnhip_graph_clone(self.dev.ctx, C.byref(h), self.h), "gcnhip_graph_clone")
+        g = Graph.__new__(Graph)
+        g.dev, g.n_rows, g.n_cols, g.h = self.dev, self.n_rows, self.n_cols, h
+        return g
+
     def reserve(self, dim):
         """segment scratch for aggregations up to `dim` columns (256 are reserved when the object is built)"""
         if dim > 256:

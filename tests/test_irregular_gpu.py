@@ -335,6 +335,39 @@ def test_restricted_operator(dev, agg, dim, ld, share):
     gr.free(); g.free()
 
 
+@pytest.mark.parametrize("dim,ld", [(41, 44), (128, 128)])
+def test_clone_and_restricted_are_one_path_from_the_parent(dev, dim, ld):
+    """Graph.clone() and Graph.restricted(every column kept) on the 300-node graph (hub row split), after the parent was
+    dealt into 7 groups: both carry the parent's edges in its order, its coefficients, its nnz (so its segment length) and
+    its row order, and the row schedule never changes a bit — so all three aggregate to the same bits.  The clone is an
+    object of its own: it outlives the parent, takes row subsets, and refuses the parent's."""
+    n = 300
+    gp, gi = irr.irregular_graph(np.random.default_rng(irr.SEED_GRAPH), n)
+    rng = np.random.default_rng(dim)
+    x = rng.standard_normal((n, dim)).astype(np.float32)
+    rows = rng.random(n) < 0.5
+    rows[int(np.argmax(np.diff(gp)))] = True                                   # the split row is in the subset
+    g = dev.graph(gp, gi)
+    g.set_schedule(2, None, 7)
+    full = dev.graphsum(g, x, ld_in=ld, ld_out=ld)
+    gc, gr = g.clone(), g.restricted(np.ones(n, bool))
+    assert np.array_equal(full, dev.graphsum(gc, x, ld_in=ld, ld_out=ld))
+    assert np.array_equal(full, dev.graphsum(gr, x, ld_in=ld, ld_out=ld))
+    for child in (gc, gr):
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(g.csr() + tuple(g.scales()), child.csr() + tuple(child.scales())))
+    # the parent's subset with the clone: refused
+    rs_parent = g.add_rowset(rows)
+    xin, out = dev.padded(x, ld), dev.buf(np.zeros((n, ld), np.float32))
+    rc = dev.lib.gcnhip_graphsum_rowset(dev.ctx, gc.h, rs_parent, xin.ptr, ld, out.ptr, ld, dim, None)
+    assert rc == -1 and b"another adjacency object" in dev.lib.gcnhip_last_error()
+    g.free(); gr.free()
+    # the clone after the parent has gone, and a subset registered on it
+    assert np.array_equal(full, dev.graphsum(gc, x, ld_in=ld, ld_out=ld))
+    got = dev.graphsum_rowset(gc, gc.add_rowset(rows), x, ld_in=ld, ld_out=ld, fill=55.0)
+    assert np.array_equal(bits(got[rows]), bits(full[rows])) and np.all(got[~rows] == 55.0)
+    gc.free()
+
+
 @pytest.mark.parametrize("dim", [7, 128])
 def test_split_edges_option(agg, dim):
     """split_edges is read at graph creation: 0 (by size: 128-entry segments on a graph this small) and 1024 (the length

@@ -18,6 +18,7 @@
 #include <stdio.h>
 #include <algorithm>
 #include <vector>
+#include "../cuda_gcn_amd/csrc/plan.h"
 
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "gather_peak: %s at %d\n", hipGetErrorString(_e), __LINE__); return -1; } } while (0)
 
@@ -332,16 +333,10 @@ int gp_run2(void *p, int ld, int dim, int U, int waves_per_simd, int store, int 
     a.n_slices = (ychunks > 1 && 8 % ychunks == 0) ? ychunks : 1;
     if (ychunks > 1 && a.n_slices == 1) return -1;      // only the shapes the product slices (d = 128, 256) or single-slice rows
     const int groups = 8 / a.n_slices;
-    // equal-work contiguous task ranges per XCD group, each starting on a multiple of 4 tasks (csrc/ctx.hip, xcd_bounds)
+    // equal-work contiguous task ranges per XCD group, each starting on a multiple of 4 tasks: the product's own rule (csrc/plan.h)
     std::vector<int64_t> prefix((size_t)h->n_tasks + 1, 0);
     for (int t = 0; t < h->n_tasks; t++) prefix[t + 1] = prefix[t] + (h->h_tasks[t].y - h->h_tasks[t].x) + 8;
-    a.bounds[0] = 0;
-    for (int k = 1; k < groups; k++) {
-        int t = (int)(std::lower_bound(prefix.begin(), prefix.end(), prefix[h->n_tasks] * k / groups) - prefix.begin());
-        t = std::min(h->n_tasks, (t + 3) / 4 * 4);
-        a.bounds[k] = std::max(t, a.bounds[k - 1]);
-    }
-    for (int k = groups; k <= 8; k++) a.bounds[k] = h->n_tasks;
+    plan::xcd_group_bounds(prefix, groups, a.bounds);
     int max_blocks = 1;
     for (int k = 0; k < groups; k++) max_blocks = std::max(max_blocks, (a.bounds[k + 1] - a.bounds[k] + 3) / 4);
     const dim3 grid(max_blocks * 8);

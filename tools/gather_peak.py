@@ -2,7 +2,7 @@
 """Measured ceiling of the aggregation's row gather on this chip (driver of tools/gather_peak.hip; run on the GPU box).
 
 For the dataset's own adjacency in the product's order (rows label-major / descending degree, neighbours of a row by
-descending degree, rows above 1024 edges cut into segments, 256-byte column slices bound to XCD groups) and for a uniformly
+descending degree, rows above the split length cut into segments, 256-byte column slices bound to XCD groups) and for a uniformly
 random index stream with the same row lengths, a gather-and-sum kernel with no coefficient stream, no multiply and no
 epilogue is swept over row loads in flight (U), resident waves per SIMD and with / without storing the result row.
 Reports gathered GB/s (4 bytes x gathered floats per edge x edges / time) per configuration and the best per table;
@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from cuda_gcn_amd import datagen  # noqa: E402
 from cuda_gcn_amd.provenance import source_sha  # noqa: E402
+from tests.plan_ref import product_order, schedule_key  # noqa: E402  (the schedule rules, checked against csrc/plan.h by tests/test_plan_cpu.py)
 
 LIB = os.path.join(ROOT, "build", "libgatherpeak.so")
 
@@ -40,46 +41,6 @@ def load_lib():
     lib.gp_run2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.gp_destroy.argtypes = [C.c_void_p]
     return lib
-
-
-def schedule_key(ds, schedule):
-    """the row-group key csrc/ctx.hip sorts the task list by (gcnhip_graph_set_schedule): labels, nothing, or degree rank dealt
-    into G groups"""
-    n = ds["num_nodes"]
-    deg = np.diff(ds["g_indptr"].astype(np.int64))
-    if schedule == "label-major":
-        return ds["label"].astype(np.int64)
-    if schedule.startswith("dealt-"):
-        G = int(schedule.split("-")[1])
-        order = np.argsort(-deg, kind="stable")
-        key = np.empty(n, np.int64)
-        key[order] = np.arange(n) % G
-        return key
-    return np.zeros(n, np.int64)
-
-
-def product_order(ds, group_major=True, key=None):
-    """the task list and index array as csrc/ctx.hip builds them: neighbours of a row by descending degree (stable),
-    rows by (group key, descending degree) — key = label when group_major, else none; rows above 1024 edges in 1024-edge segments"""
-    gp, gi = ds["g_indptr"].astype(np.int64), ds["g_indices"]
-    n = gp.size - 1
-    deg = np.diff(gp)
-    row_of = np.repeat(np.arange(n), deg)
-    # per row: neighbours sorted by (-degree, id) — std::sort of pairs (-deg, id) in graph_create_impl
-    order = np.lexsort((gi, -deg[gi], row_of))
-    idx = gi[order].astype(np.int32)
-    if key is None:
-        key = ds["label"].astype(np.int64) if group_major else np.zeros(n, np.int64)
-    rows = np.lexsort((np.arange(n), -deg, key))                 # stable: (key asc, degree desc)
-    e0, e1, tr = [], [], []
-    for r in rows.tolist():
-        a, b = int(gp[r]), int(gp[r + 1])
-        if b - a <= 1024:
-            e0.append(a); e1.append(b); tr.append(r)
-        else:
-            for s in range(a, b, 1024):
-                e0.append(s); e1.append(min(b, s + 1024)); tr.append(r)
-    return np.array(e0, np.int32), np.array(e1, np.int32), np.array(tr, np.int32), idx
 
 
 def main():
