@@ -1,5 +1,5 @@
 // calibration.h — the reliability diagram and its summary from per-bin integer counts and confidence sums (beyond the
-// reference).  Host only: no GPU.  The ONE place where (count, correct, conf_sum) become a report: HipGCN::calibration's
+// reference).  Host only: no GPU.  The ONE place where (count, correct, conf_sum) become a report: ModelQueries::calibration's
 // callers (the Python binding, gcn-hip's GCN_CALIBRATE) hand it what gcnhip_calib_bins_rows formed.
 //
 // Bin b holds the rows whose confidence (largest softmax probability) lies in (b / B, (b + 1) / B] (Guo et al., 2017).

@@ -3,9 +3,11 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <vector>
 #include "gcn.h"
+#include "queries.h"
 #include "cluster.h"
 #include "hip_check.h"
 #include "parser.h"
@@ -172,11 +174,9 @@ int gcnhost_model_info(gcnhost_model *m, int *rank, int *world, int *row_start, 
 }
 int gcnhost_model_row_ids(gcnhost_model *m, int *ids, int *renumbered) {
     API_TRY({
-        const std::vector<int> &order = m->gcn->node_order();
-        const int r0 = m->gcn->row_start(), n = m->gcn->local_rows();
-        if (renumbered) *renumbered = order.empty() ? 0 : 1;
+        if (renumbered) *renumbered = !m->gcn->node_order().empty();
         if (ids)
-            for (int r = 0; r < n; r++) ids[r] = order.empty() ? r0 + r : order[(size_t)r0 + r];
+            for (int r = 0; r < m->gcn->local_rows(); r++) ids[r] = m->gcn->node_id(r);
     })
 }
 int gcnhost_model_row_scale(gcnhost_model *m, float *dinv, int *factored) {
@@ -216,48 +216,48 @@ int gcnhost_model_get_var(gcnhost_model *m, int k, int grad, float *out, int *ro
 }
 int gcnhost_model_set_weights(gcnhost_model *m, const float *w1, const float *w2) { API_TRY({ m->gcn->set_weights(w1, w2); }) }
 int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pred, float *prob, float *logp) {
-    API_TRY({ m->gcn->predict(nodes, n, pred, prob, logp); })
+    API_TRY({ m->gcn->queries().predict(nodes, n, pred, prob, logp); })
 }
 int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob) {
-    API_TRY({ m->gcn->predict_multilabel(nodes, n, bits, prob); })
+    API_TRY({ m->gcn->queries().predict_multilabel(nodes, n, bits, prob); })
 }
 int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
     if (!m || !counts) { g_err = "gcnhost_model_evaluate: invalid argument"; return -1; }
-    API_TRY({ m->gcn->evaluate(split, nodes, n, counts, rows_counted, unlabelled); })
+    API_TRY({ m->gcn->queries().evaluate(split, nodes, n, counts, rows_counted, unlabelled); })
 }
 int gcnhost_model_propagate(gcnhost_model *m, const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred) {
     if (!m || !y0 || !out) { g_err = "gcnhost_model_propagate: invalid argument"; return -1; }
-    API_TRY({ m->gcn->propagate(y0, dim, alpha, iters, lo, hi, out, pred); })
+    API_TRY({ m->gcn->queries().propagate(y0, dim, alpha, iters, lo, hi, out, pred); })
 }
 int gcnhost_model_label_propagation(gcnhost_model *m, float alpha, int iters, int splits_mask, int32_t *pred, float *y) {
     if (!m || !pred) { g_err = "gcnhost_model_label_propagation: invalid argument"; return -1; }
-    API_TRY({ m->gcn->label_propagation(alpha, iters, splits_mask, pred, y); })
+    API_TRY({ m->gcn->queries().label_propagation(alpha, iters, splits_mask, pred, y); })
 }
 int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth,
                                      int splits_mask, int32_t *pred, float *g) {
     if (!m || !pred) { g_err = "gcnhost_model_correct_and_smooth: invalid argument"; return -1; }
-    API_TRY({ m->gcn->correct_and_smooth(alpha_correct, iters_correct, alpha_smooth, iters_smooth, splits_mask, pred, g); })
+    API_TRY({ m->gcn->queries().correct_and_smooth(alpha_correct, iters_correct, alpha_smooth, iters_smooth, splits_mask, pred, g); })
 }
 int gcnhost_model_calibration(gcnhost_model *m, int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count,
                               int64_t *correct, double *conf_sum) {
     if (!m || !sums || !count || !correct || !conf_sum) { g_err = "gcnhost_model_calibration: invalid argument"; return -1; }
-    API_TRY({ m->gcn->calibration(split, nodes, n, temperature, bins, sums, count, correct, conf_sum); })
+    API_TRY({ m->gcn->queries().calibration(split, nodes, n, temperature, bins, sums, count, correct, conf_sum); })
 }
 int gcnhost_model_calibrate(gcnhost_model *m, int split, int bins, double *out, int64_t *count, int64_t *correct, double *conf_sum) {
     if (!m || !out) { g_err = "gcnhost_model_calibrate: invalid argument"; return -1; }
     API_TRY({
-        const HipGCN::Calibrated c = m->gcn->calibrate(split, bins, count, correct, conf_sum);
+        const ModelQueries::Calibrated c = m->gcn->queries().calibrate(split, bins, count, correct, conf_sum);
         out[0] = c.temperature; out[1] = c.nll_before; out[2] = c.nll_after; out[3] = c.steps; out[4] = c.at_bound ? 1.0 : 0.0;
         out[5] = (double)c.rows;
     })
 }
 int gcnhost_model_set_temperature(gcnhost_model *m, float temperature) {
     if (!m) { g_err = "gcnhost_model_set_temperature: invalid argument"; return -1; }
-    API_TRY({ m->gcn->set_temperature(temperature); })
+    API_TRY({ m->gcn->queries().set_temperature(temperature); })
 }
 int gcnhost_model_temperature(gcnhost_model *m, float *temperature) {
     if (!m || !temperature) { g_err = "gcnhost_model_temperature: invalid argument"; return -1; }
-    API_TRY({ *temperature = m->gcn->temperature(); })
+    API_TRY({ *temperature = m->gcn->queries().temperature(); })
 }
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary) {
@@ -584,9 +584,11 @@ int gcnhost_choose_node_order(const int *g_indptr, const int *g_indices, int n_r
         const OrderCost ids = exchange_cost(g_indptr, g_indices, n_rows, world);
         if ((force || ids.halo_share > 0.75) && n_rows >= 4096) sg = structure_groups(g_indptr, g_indices, n_rows);
         const NodeOrderChoice ch = choose_node_order(g_indptr, g_indices, n_rows, world, sg.useful ? sg.group.data() : nullptr, force != 0);
-        if (renumbered) *renumbered = ch.order.empty() ? 0 : 1;
-        if (order)
-            for (int k = 0; k < n_rows; k++) order[k] = ch.order.empty() ? k : ch.order[k];
+        if (renumbered) *renumbered = !ch.order.empty();
+        if (order) {                                            // the identity, under the chosen order when there is one
+            std::iota(order, order + n_rows, 0);
+            std::copy(ch.order.begin(), ch.order.end(), order);
+        }
         if (ids_share) *ids_share = ch.ids.halo_share;
         if (ids_recv_rows) *ids_recv_rows = ch.ids.recv_rows_max;
         if (new_share) *new_share = ch.chosen.halo_share;

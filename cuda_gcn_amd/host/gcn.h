@@ -121,6 +121,8 @@ struct HipGCNOptions {
 
 // Which split a pass scores: what set_truth (gcn.cpp:78-81) switches, as one value.  The loss module and the class-width
 // aggregation hold pointers to the fields; the training context has one, the validation lane its own.
+class ModelQueries;
+
 struct ScoredSplit {
     int32_t *truth = nullptr;                                  // d_truth of the split
     int count = 0;                                             // its labelled rows, all ranks
@@ -164,7 +166,9 @@ public:
     const RowPartition &partition() const { return part; }
     // multi-GPU: the model may renumber the nodes before it partitions them (partition.h, choose_node_order): row r of
     // this rank is then node node_order()[row_start() + r] of the dataset it was given.  Empty: the ids were kept.
+    // node_id(r) is that node either way.
     const std::vector<int> &node_order() const { return node_order_; }
+    int node_id(int local_row) const { const int p = row_start() + local_row; return node_order_.empty() ? p : node_order_[p]; }
     const char *node_order_name() const { return node_order_name_; }
     const ExchangePlan &exchange_plan() const { return xplan; }
     // variable k as in gcn.cpp:21-54 (1 H0, 2 W1, 3 H1, 4 Z0, 5 W2, 6 Z); rows x cols floats, this rank's rows.
@@ -181,90 +185,10 @@ public:
     bool factored() const { return factored_; }
     void row_scale(std::vector<float> &dinv);                 // 1/sqrt(deg) of this rank's rows (deg of the full graph, self loop included)
     void set_weights(const float *w1, const float *w2);       // [F x h], [h x C] row-major
-
-    // Prediction (beyond the reference, which only prints accuracy): an evaluation forward with the current weights — no
-    // dropout, the model's usual evaluation order (aggregate-first when that is on) — whose logit aggregation carries the
-    // prediction epilogue (gcnhip_graphsum_predict) on the requested rows.  nodes: n DATASET node ids, each a row of this
-    // rank (repeats allowed); NULL: every row of this rank, in the order of local rows (node_order()/row_start() name
-    // them).  pred[i] = argmax of node i's logits (lowest class on a tie), prob[i] = its softmax probability, logp
-    // (may be NULL) [n x C] = the log-softmax rows.  Several GPUs: a collective (the logit aggregation's exchange) —
-    // every rank calls it, each with its own nodes.  Training state is not touched: the metrics ring, the current split,
-    // the logits (variable 6) and the captured epoch graph are left as they were; a train_epoch() after it has the
-    // same bits as one without it.  Synchronises.
-    void predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp);
-    // Multi-label prediction, the same contract as predict() (dataset ids, NULL = every row of this rank, a collective, training
-    // state untouched, synchronises): one evaluation forward whose logits go to scratch (not variable 6), then
-    // gcnhip_bce_predict_rows.  bits [n x ceil(C / 32)]: bit (c & 31) of word c >> 5 = (z_c > 0); prob (may be NULL) [n x C] =
-    // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
-    void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
+    // what a caller asks of the trained model (host/queries.h): prediction, per-class evaluation, smoothing, temperature scaling
+    ModelQueries &queries() { return *queries_; }
     bool multilabel() const { return opt_.multilabel; }
     bool weighted() const { return !opt_.class_weights.empty(); }
-    // Per-class evaluation (beyond the reference): one evaluation forward with the current weights (no dropout) over a set of
-    // rows, and integer counts per class formed on the GPU behind it.  Rows: the nodes of `split` (1 train, 2 validation,
-    // 3 test — eval's codes) on this rank, `nodes` then ignored; or, with split == 0, the `nodes` query with predict()'s
-    // conventions (n dataset ids, each a row of this rank, repeats counted as often as listed; NULL: every row of this rank).
-    // Single-label model: the logit aggregation runs gcnhip_graphsum_predict on those rows only, then gcnhip_confusion_rows;
-    // counts [C x C], counts[t * C + p] = rows with truth t predicted as p; *unlabelled = rows whose truth is outside [0, C)
-    // (not in the matrix), *rows_counted = rows in the matrix.  Multi-label model: predict_multilabel's forward (logits to
-    // scratch), then gcnhip_bce_class_counts_rows; counts [3 x C] = TP, FP, FN per class (z > 0 predicts the class),
-    // *rows_counted = the rows, *unlabelled = 0.  Several GPUs: a collective like predict(); each rank counts its own rows, the
-    // counts are summed exactly over the ranks and every rank returns the same totals.  Only the counts cross to the host.
-    // Training state is not touched: the metrics ring, the current split, the logits (variable 6) and the captured epoch
-    // graph are left as they were; a train_epoch() after it has the same bits as one without it.  Synchronises.  More than
-    // 64 (single-label) or 256 (multi-label) classes: an error.  host/report.h derives precision / recall / F1 from the counts.
-    void evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
-    // Label propagation and Correct & Smooth (beyond the reference; Huang et al., 2020): the graph and the known labels used
-    // at inference time.  Every iteration is one gcnhip_graphsum_blend launch through `graph` with its per-edge coefficients,
-    // ping-ponging two of four [local rows x ld] f32 tables from the arena (allocated on first use; ld by the row rule of
-    // variable 6).  Arrays are in DATASET node order.  predict()'s contract: the call starts with sync(); the metrics ring, the
-    // current split, variable 6 and the captured epoch graph are untouched.  Refused with a message before any launch: more
-    // than one rank (every iteration would need a table exchange), alpha outside [0, 1], iters < 0, a width outside 1..64, and
-    // for the two label schemes a multi-label model or more than 64 classes.  splits_mask: bit s = the labelled nodes of split
-    // s are known (2 = the training split).
-    //   propagate: Y_{k+1} = clamp(alpha . A^ . Y_k + (1 - alpha) . y0, lo, hi), Y_0 = y0 [num_nodes x dim]; out = Y_iters, pred
-    //   (may be NULL) its row argmax (lowest column on a tie).  Needs neither labels nor trained weights.
-    //   label_propagation: propagate from the one-hot rows of the known nodes (zero rows elsewhere), clamp [0, 1].
-    //   correct_and_smooth: one hooked evaluation forward leaves the log-softmax rows on the device; gcnhip_cs_error_rows,
-    //   iters_correct blends clamped to [-1, 1], gcnhip_cs_correct_rows, iters_smooth blends clamped to [0, 1], the last of which
-    //   writes pred — the only array that must cross to the host; g (may be NULL) is copied when asked for.
-    void propagate(const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred);
-    void label_propagation(float alpha, int iters, int splits_mask, int32_t *pred, float *y);
-    void correct_and_smooth(float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth, int splits_mask, int32_t *pred, float *g);
-    // Temperature scaling and calibration error (beyond the reference; Guo et al., 2017): are predict()'s probabilities to be
-    // trusted, and one scalar T that repairs them — softmax(z / T) with T fitted on a held-out split.  All three work on the
-    // log-softmax rows predict()'s hooked forward leaves on the device (log_softmax(z / T) = log_softmax(log_softmax(z) / T)) with
-    // the row-local kernels of csrc/calib.hip, and hold predict()'s contract: the call starts with sync(); the metrics ring, the
-    // current split, variable 6 and the captured epoch graph are untouched.  Rows: the labelled nodes of `split` (1 train,
-    // 2 validation, 3 test), or with split == 0 the `nodes` query scored against the dataset's labels, as evaluate() takes them.
-    // Refused with a message before any launch: a multi-label model, more than 64 classes, more than one rank (the double sums
-    // would need an exact all-reduce that the float transport does not give), bins outside 1..64, a temperature that is not
-    // finite and > 0, and for calibrate a split without labelled rows.
-    //   calibration: one forward, one gcnhip_calib_nll_rows and one gcnhip_calib_bins_rows launch at beta = 1 / temperature;
-    //   sums[4] = {sum nll, sum d nll / d beta, sum d2 nll / d beta2, rows}, count / correct [bins], conf_sum [bins]: the 4 + 3 . bins
-    //   numbers that cross to the host (host/calibration.h turns them into the report).
-    //   calibrate: one forward, then a safeguarded Newton iteration on the convex NLL(beta) run by the host — a step is one nll
-    //   launch and one 32-byte copy.  From beta = 1 inside the bracket [0.01, 100], which moves with the sign of the gradient; the
-    //   Newton step beta - g / h when h > 0 and it stays strictly inside the bracket, else the geometric midpoint (while the end
-    //   the step goes to is still the outer limit, the step is at least a factor 2, so a minimum that is not there is left behind
-    //   within the 40 steps); stops when
-    //   |delta beta| <= 1e-6 beta or after 40 steps.  at_bound: the result sits on an end of [0.01, 100] (a split the model
-    //   classifies perfectly: the NLL falls in beta without end).  With bins > 0 the reliability counts of the same rows at T = 1
-    //   and at the fitted T are formed by two more launches on the rows already there: count / correct / conf_sum [2 x bins].
-    //   calibrate does not set the temperature.
-    //   set_temperature(T != 1): predict() keeps the log-softmax rows, runs gcnhip_calib_scale_rows on the queried rows and returns
-    //   the scaled prob (and logp); pred does not depend on T.  correct_and_smooth() scales its rows in place before the residual.
-    //   At T == 1 (the default) neither launches anything new.  Training, eval, evaluate and the weights file ignore it.
-    struct Calibrated {
-        float temperature = 1.f;
-        double nll_before = 0, nll_after = 0;                  // mean NLL of the split at beta = 1 and at the result
-        int steps = 0;
-        bool at_bound = false;
-        int64_t rows = 0;
-    };
-    void calibration(int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count, int64_t *correct, double *conf_sum);
-    Calibrated calibrate(int split, int bins, int64_t *count, int64_t *correct, double *conf_sum);
-    void set_temperature(float t);
-    float temperature() const { return temperature_; }
     // Weights file (host/weights.h): save_weights writes W1, W2 of this model (rank 0 of several writes the same weights every
     // rank holds); load_weights checks the file's widths against the model (mismatch: an error, never a reshape) and hands the
     // weights to set_weights.  Adam's moments and step count are NOT in the file: a loaded model that trains further starts
@@ -315,12 +239,7 @@ private:
     std::vector<Module *> eval_modules;                        // [0] owned (the GEMM on A^.X); the rest are modules[2..]
     bool h1_from_fused_eval = false;                           // the last forward on the main stream kept its hidden matrix in registers (get_var(3) rebuilds it)
     void build_agg_first_eval();
-    HipGraphSum *logits_gs = nullptr;                          // the class-width aggregation (producer of Z): predict() hooks it
-    // predict(): the last node query's row subset (registered on `graph`, removed when the next query differs) and scratch
-    std::vector<uint32_t> pred_bits;
-    gcnhip_rowset *pred_rows = nullptr;
-    int32_t *d_pred = nullptr;
-    float *d_prob = nullptr, *d_logp = nullptr;
+    HipGraphSum *logits_gs = nullptr;                          // the class-width aggregation (producer of Z): forward_hooked() hooks it
     const float *full_vals = nullptr;
     bool replicate_l1 = false;
     bool rebuild_dh1 = false;                                  // multi-GPU backward: gather dZ0 + mask bits, rebuild dH1 everywhere
@@ -340,44 +259,11 @@ private:
     void fill_scored(ScoredSplit &d, int s, gcnhip_rowset *const *rows) const;
     uint32_t *d_ml_truth = nullptr;                            // multi-label: this rank's rows of GCNData::multihot
     int ml_wpr = 0;
-    float *d_ml_logits = nullptr;                              // predict_multilabel: scratch logits [local rows x ld of Z]
-    uint32_t *d_ml_bits = nullptr;
-    float *d_ml_prob = nullptr;
-    int32_t *d_ml_rows = nullptr;
-    size_t ml_query_cap = 0;
     std::pair<float, float> ring_metrics(const float *row) const;   // (loss + L2, accuracy or micro-F1) of a metrics-ring row
-    void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows (predict*)
-    const gcnhip_rowset *query_subset(const std::vector<int> &rows);
+    // the queries: their state and device scratch live in this object (host/queries.h lists what it reads here), freed with it
+    friend class ModelQueries;
+    std::unique_ptr<ModelQueries> queries_;
     void forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect);
-    float *ml_logits_scratch();
-    void pred_scratch();                                       // d_pred / d_prob, on first use
-    // evaluate(): the counts on the device (also the float limbs of their all-reduce), an uploaded row list, every local label
-    int32_t *d_eval_counts = nullptr, *d_eval_rows = nullptr, *d_label_all = nullptr;
-    size_t eval_rows_cap = 0;
-    // propagate / label_propagation / correct_and_smooth: four tables [local rows x smooth_ld], the merged truth of the known
-    // splits, sigma = {sum |E_0|, rows}
-    float *d_smooth[4] = {};
-    int smooth_ld = 0;
-    int32_t *d_smooth_truth = nullptr;
-    float *d_sigma = nullptr;
-    static int smooth_row_ld(int dim) { return dim <= 32 ? (dim + 3) / 4 * 4 : (dim + 15) / 16 * 16; }   // HipVariable's rule
-    void smooth_check(const char *what, float alpha, int iters) const;
-    void smooth_tables(int ld);
-    const int32_t *smooth_truth(const char *what, int splits_mask, std::vector<int32_t> *host);
-    float *smooth_iterate(const float *base, float *a, float *b, int ld, int dim, float alpha, int iters, float lo, float hi, int32_t *pred);
-    void smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows);
-    void smooth_pred_download(int32_t *pred);
-    // calibration / calibrate: {nll sums [4] | conf_sum [2 x 64]} doubles and {count, correct} [2 x 2 x 64] ints on the device
-    float temperature_ = 1.f;
-    double *d_calib_sums = nullptr;
-    int32_t *d_calib_counts = nullptr;
-    void calib_check(const char *what, float temperature, int bins) const;
-    // the rows a split or a query names, as evaluate() lists them, and the truth they are scored against
-    struct ScoredRows { const int32_t *d_list; int n; const int32_t *truth; const gcnhip_rowset *subset; };
-    ScoredRows scored_rows(const char *what, int split, const int *nodes, int n);
-    const int32_t *upload_rows(const std::vector<int> &rows);
-    void forward_logp(const gcnhip_rowset *subset);            // predict()'s hooked forward, d_logp kept
-    void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

@@ -1,6 +1,7 @@
 // gcn_build.cpp — HipGCN's construction and teardown: argument checks, device objects and buffers, module wiring, the
 // validation lane, release.  (What init() decides about the graph on the way is in gcn_schedule.cpp.)
 #include "gcn.h"
+#include "queries.h"
 #include "class_weights.h"
 #include "cluster.h"
 #include <chrono>
@@ -87,6 +88,7 @@ void HipGCN::init(const HipGCNOptions &opt) {
     }
     GCNHIP_CHECK(gcnhip_ctx_create(&env.ctx, opt.device, nullptr));
     arena.bind(env.ctx);
+    queries_.reset(new ModelQueries(*this));                    // allocates nothing until the first query
     if (opt.gemm >= 0) GCNHIP_CHECK(gcnhip_ctx_set_option(env.ctx, "gemm_bf16x3", opt.gemm ? 2 : 0));   // HIPGCN_GEMM; else the library's default
     timers.reset(new DeviceTimers(env.ctx));
     timers->enabled = (flags & HIPGCN_TIMERS) != 0;
@@ -647,6 +649,7 @@ void HipGCN::release() {
     if (!env.ctx) return;
     gcnhip_ctx_sync(env.ctx);
     destroy_lane();
+    queries_.reset();                                         // the queries' scratch, before the adjacency object and the context
     if (!eval_modules.empty()) delete eval_modules[0];       // the rest are borrowed from `modules`
     eval_modules.clear();
     for (auto m : modules) delete m;

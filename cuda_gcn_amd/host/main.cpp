@@ -39,19 +39,19 @@
 //                            (class = argmax of the node's logits, lowest on a tie; its softmax probability).  With several
 //                            GPUs each worker predicts its own rows into an array indexed by node id; the file is written
 //                            after the join.
-//   GCN_REPORT=<file>        after the test line, the TEST split is evaluated per class (HipGCN::evaluate: counts formed on the GPU) and
+//   GCN_REPORT=<file>        after the test line, the TEST split is evaluated per class (ModelQueries::evaluate: counts formed on the GPU) and
 //                            a text report written: `class <c> support <n> precision <p> recall <r> f1 <f>` per class, a line
 //                            `macro_f1 <x> micro_f1 <y>`, and for a single-label model a line `confusion` followed by the matrix
 //                            (row = truth, column = prediction) as C lines of C integers.  With several GPUs every worker takes
 //                            part, all receive the same totals, and the file is written once after the join.
 //   GCN_SMOOTH=cs|lp        after the test line, the predictions are post-processed with the graph and the training labels on the GPU
-//                            (HipGCN::correct_and_smooth / label_propagation at their default settings: alpha 0.8 / 50 iterations
+//                            (ModelQueries::correct_and_smooth / label_propagation at their default settings: alpha 0.8 / 50 iterations
 //                            each for cs, alpha 0.9 / 50 iterations for lp) and one more line is printed:
 //                            `smoothed_test_acc=<share of the test split whose smoothed class is its label>`.  GCN_PREDICT then
 //                            writes the smoothed classes, one line `node class` per node.  One GPU, single-label.
 //   GCN_CALIBRATE=<file>     directly after the test line (before GCN_REPORT / GCN_SMOOTH / GCN_PREDICT, which then see the temperature):
 //                            one scalar temperature T is fitted on the VALIDATION split by minimising the negative log-likelihood of
-//                            softmax(z / T) (HipGCN::calibrate), set on the model, and one line is printed:
+//                            softmax(z / T) (ModelQueries::calibrate), set on the model, and one line is printed:
 //                            `temperature=<T> val_nll_before=<x> val_nll_after=<y> test_ece_before=<a> test_ece_after=<b>` (ECE: expected
 //                            calibration error of the TEST split, 15 bins).  The file gets the test split's reliability table at
 //                            T = 1 and at the fitted T (host/calibration.h: a summary line, then one line per bin).  Works with
@@ -78,6 +78,7 @@
 #include <unistd.h>
 #include <vector>
 #include "calibration.h"
+#include "queries.h"
 #include "class_weights.h"
 #include "gcn.h"
 #include "hip_check.h"
@@ -248,17 +249,17 @@ int main(int argc, char **argv) {
             }
             if (calibrate_path) {                              // one rank (checked above)
                 constexpr int BINS = 15;
-                const HipGCN::Calibrated fit = gcn.calibrate(2, 0, nullptr, nullptr, nullptr);
+                const ModelQueries::Calibrated fit = gcn.queries().calibrate(2, 0, nullptr, nullptr, nullptr);
                 double sums[2][4], conf[2][BINS];
                 int64_t count[2][BINS], correct[2][BINS];
                 CalibrationReport rep[2];
                 const float T[2] = {1.f, fit.temperature};
                 std::string err;
                 for (int k = 0; k < 2; k++) {
-                    gcn.calibration(3, nullptr, 0, T[k], BINS, sums[k], count[k], correct[k], conf[k]);
+                    gcn.queries().calibration(3, nullptr, 0, T[k], BINS, sums[k], count[k], correct[k], conf[k]);
                     if (gcn_calibration_report(BINS, count[k], correct[k], conf[k], &rep[k], &err) != 0) throw GcnHipFailure(-1, err);
                 }
-                gcn.set_temperature(fit.temperature);
+                gcn.queries().set_temperature(fit.temperature);
                 printf("temperature=%.5f val_nll_before=%.5f val_nll_after=%.5f test_ece_before=%.5f test_ece_after=%.5f\n", fit.temperature,
                        fit.nll_before, fit.nll_after, rep[0].ece, rep[1].ece);
                 FILE *f = fopen(calibrate_path, "w");
@@ -271,38 +272,36 @@ int main(int argc, char **argv) {
                         fit.at_bound ? " (the fit stopped on an end of its bracket: the validation split is classified perfectly)" : "");
             }
             if (predict_path && multilabel_path) {             // the same, as class sets
-                const int n = gcn.local_rows(), r0 = gcn.row_start();
+                const int n = gcn.local_rows();
                 std::vector<uint32_t> b((size_t)std::max(n, 1) * ml_wpr);
-                gcn.predict_multilabel(nullptr, n, b.data(), nullptr);
-                const std::vector<int> &order = gcn.node_order();
+                gcn.queries().predict_multilabel(nullptr, n, b.data(), nullptr);
                 for (int r = 0; r < n; r++) {
-                    const int id = order.empty() ? r0 + r : order[r0 + r];
+                    const int id = gcn.node_id(r);
                     std::copy(b.begin() + (size_t)r * ml_wpr, b.begin() + (size_t)(r + 1) * ml_wpr, all_bits.begin() + (size_t)id * ml_wpr);
                 }
             } else if (smooth) {                               // one rank (checked above): arrays by node id
                 std::vector<int32_t> p(std::max(params.num_nodes, 1));
-                if (strcmp(smooth, "cs") == 0) gcn.correct_and_smooth(0.8f, 50, 0.8f, 50, 1 << 1, p.data(), nullptr);
-                else gcn.label_propagation(0.9f, 50, 1 << 1, p.data(), nullptr);
+                if (strcmp(smooth, "cs") == 0) gcn.queries().correct_and_smooth(0.8f, 50, 0.8f, 50, 1 << 1, p.data(), nullptr);
+                else gcn.queries().label_propagation(0.9f, 50, 1 << 1, p.data(), nullptr);
                 long hit = 0, total = 0;
                 for (int i = 0; i < params.num_nodes; i++)
                     if (data.split[i] == 3) { total++; hit += p[i] == data.label[i]; }
                 printf("smoothed_test_acc=%.5f\n", total ? (double)hit / (double)total : 0.0);
                 if (predict_path) std::copy(p.begin(), p.begin() + params.num_nodes, all_pred.begin());
             } else if (predict_path) {                         // every rank: the logit aggregation exchanges rows
-                const int n = gcn.local_rows(), r0 = gcn.row_start();
+                const int n = gcn.local_rows();
                 std::vector<int32_t> p(std::max(n, 1));
                 std::vector<float> q(std::max(n, 1));
-                gcn.predict(nullptr, n, p.data(), q.data(), nullptr);
-                const std::vector<int> &order = gcn.node_order();
+                gcn.queries().predict(nullptr, n, p.data(), q.data(), nullptr);
                 for (int r = 0; r < n; r++) {
-                    const int id = order.empty() ? r0 + r : order[r0 + r];
+                    const int id = gcn.node_id(r);
                     all_pred[id] = p[r];
                     all_prob[id] = q[r];
                 }
             }
             if (report_path) {                                 // every rank: a collective; the totals are the same everywhere
                 std::vector<int64_t> cnt(report_counts.size());
-                gcn.evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
+                gcn.queries().evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
                 if (rank == 0) report_counts = cnt;
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {

@@ -1,0 +1,171 @@
+// queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
+// evaluation, label propagation and Correct & Smooth, temperature scaling.  ModelQueries owns every device buffer and every
+// piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// first query, and HipGCN::release() frees all of it by destroying this one object.
+//
+// It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
+//   reads   params, opt_.multilabel, env (context, comm), n_local, row_start(), node_order_ (query_rows' inverse map; node_id()
+//           elsewhere), data->split, data->label, graph, logits_gs (null test only), variables[6]->ld, d_truth[], split_rows[],
+//           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr
+//   calls   sync(), forward_hooked()
+// It writes no member of HipGCN.
+#pragma once
+#include <cstdint>
+#include <vector>
+#include "device_arena.h"
+
+class HipGCN;
+
+class ModelQueries {
+public:
+    explicit ModelQueries(HipGCN &model);
+    ~ModelQueries() { arena.free_all(); }
+
+    // Prediction: an evaluation forward with the current weights — no dropout, the model's usual evaluation order
+    // (aggregate-first when that is on) — whose logit aggregation carries the prediction epilogue (gcnhip_graphsum_predict) on
+    // the requested rows.  nodes: n DATASET node ids, each a row of this rank (repeats allowed); NULL: every row of this rank, in
+    // the order of local rows (HipGCN::node_id() names them).  pred[i] = argmax of node i's logits (lowest class on a tie),
+    // prob[i] = its softmax probability, logp (may be NULL) [n x C] = the log-softmax rows.  Several GPUs: a collective (the
+    // logit aggregation's exchange) — every rank calls it, each with its own nodes.  Training state is not touched: the metrics
+    // ring, the current split, the logits (variable 6) and the captured epoch graph are left as they were; a train_epoch()
+    // after it has the same bits as one without it.  Synchronises.
+    void predict(const int *nodes, int n, int32_t *pred, float *prob, float *logp);
+    // Multi-label prediction, the same contract as predict() (dataset ids, NULL = every row of this rank, a collective, training
+    // state untouched, synchronises): one evaluation forward whose logits go to scratch (not variable 6), then
+    // gcnhip_bce_predict_rows.  bits [n x ceil(C / 32)]: bit (c & 31) of word c >> 5 = (z_c > 0); prob (may be NULL) [n x C] =
+    // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
+    void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
+    // Per-class evaluation: one evaluation forward with the current weights (no dropout) over a set of rows, and integer counts
+    // per class formed on the GPU behind it.  Rows: the nodes of `split` (1 train, 2 validation, 3 test — eval's codes) on this
+    // rank, `nodes` then ignored; or, with split == 0, the `nodes` query with predict()'s conventions (n dataset ids, each a row
+    // of this rank, repeats counted as often as listed; NULL: every row of this rank).
+    // Single-label model: the logit aggregation runs gcnhip_graphsum_predict on those rows only, then gcnhip_confusion_rows;
+    // counts [C x C], counts[t * C + p] = rows with truth t predicted as p; *unlabelled = rows whose truth is outside [0, C)
+    // (not in the matrix), *rows_counted = rows in the matrix.  Multi-label model: predict_multilabel's forward (logits to
+    // scratch), then gcnhip_bce_class_counts_rows; counts [3 x C] = TP, FP, FN per class (z > 0 predicts the class),
+    // *rows_counted = the rows, *unlabelled = 0.  Several GPUs: a collective like predict(); each rank counts its own rows, the
+    // counts are summed exactly over the ranks and every rank returns the same totals.  Only the counts cross to the host.
+    // Training state is not touched, as with predict().  Synchronises.  More than 64 (single-label) or 256 (multi-label)
+    // classes: an error.  host/report.h derives precision / recall / F1 from the counts.
+    void evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+    // Label propagation and Correct & Smooth (Huang et al., 2020): the graph and the known labels used at inference time.  Every
+    // iteration is one gcnhip_graphsum_blend launch through the model's adjacency with its per-edge coefficients, ping-ponging
+    // two of four [local rows x ld] f32 tables (allocated on first use; ld by the row rule of variable 6).  Arrays are in
+    // DATASET node order.  predict()'s contract: the call starts with sync(); the metrics ring, the current split, variable 6
+    // and the captured epoch graph are untouched.  Refused with a message before any launch: more than one rank (every
+    // iteration would need a table exchange), alpha outside [0, 1], iters < 0, a width outside 1..64, and for the two label
+    // schemes a multi-label model or more than 64 classes.  splits_mask: bit s = the labelled nodes of split s are known
+    // (2 = the training split).
+    //   propagate: Y_{k+1} = clamp(alpha . A^ . Y_k + (1 - alpha) . y0, lo, hi), Y_0 = y0 [num_nodes x dim]; out = Y_iters, pred
+    //   (may be NULL) its row argmax (lowest column on a tie).  Needs neither labels nor trained weights.
+    //   label_propagation: propagate from the one-hot rows of the known nodes (zero rows elsewhere), clamp [0, 1].
+    //   correct_and_smooth: one hooked evaluation forward leaves the log-softmax rows on the device; gcnhip_cs_error_rows,
+    //   iters_correct blends clamped to [-1, 1], gcnhip_cs_correct_rows, iters_smooth blends clamped to [0, 1], the last of which
+    //   writes pred — the only array that must cross to the host; g (may be NULL) is copied when asked for.
+    void propagate(const float *y0, int dim, float alpha, int iters, float lo, float hi, float *out, int32_t *pred);
+    void label_propagation(float alpha, int iters, int splits_mask, int32_t *pred, float *y);
+    void correct_and_smooth(float alpha_correct, int iters_correct, float alpha_smooth, int iters_smooth, int splits_mask, int32_t *pred, float *g);
+    // Temperature scaling and calibration error (Guo et al., 2017): are predict()'s probabilities to be trusted, and one scalar T
+    // that repairs them — softmax(z / T) with T fitted on a held-out split.  All three work on the log-softmax rows predict()'s
+    // hooked forward leaves on the device (log_softmax(z / T) = log_softmax(log_softmax(z) / T)) with the row-local kernels of
+    // csrc/calib.hip, and hold predict()'s contract: the call starts with sync(); the metrics ring, the current split,
+    // variable 6 and the captured epoch graph are untouched.  Rows: the labelled nodes of `split` (1 train, 2 validation,
+    // 3 test), or with split == 0 the `nodes` query scored against the dataset's labels, as evaluate() takes them.
+    // Refused with a message before any launch: a multi-label model, more than 64 classes, more than one rank (the double sums
+    // would need an exact all-reduce that the float transport does not give), bins outside 1..64, a temperature that is not
+    // finite and > 0, and for calibrate a split without labelled rows.
+    //   calibration: one forward, one gcnhip_calib_nll_rows and one gcnhip_calib_bins_rows launch at beta = 1 / temperature;
+    //   sums[4] = {sum nll, sum d nll / d beta, sum d2 nll / d beta2, rows}, count / correct [bins], conf_sum [bins]: the 4 + 3 . bins
+    //   numbers that cross to the host (host/calibration.h turns them into the report).
+    //   calibrate: one forward, then a safeguarded Newton iteration on the convex NLL(beta) run by the host — a step is one nll
+    //   launch and one 32-byte copy.  From beta = 1 inside the bracket [0.01, 100], which moves with the sign of the gradient; the
+    //   Newton step beta - g / h when h > 0 and it stays strictly inside the bracket, else the geometric midpoint (while the end
+    //   the step goes to is still the outer limit, the step is at least a factor 2, so a minimum that is not there is left behind
+    //   within the 40 steps); stops when |delta beta| <= 1e-6 beta or after 40 steps.  at_bound: the result sits on an end of
+    //   [0.01, 100] (a split the model classifies perfectly: the NLL falls in beta without end).  With bins > 0 the reliability
+    //   counts of the same rows at T = 1 and at the fitted T are formed by two more launches on the rows already there:
+    //   count / correct / conf_sum [2 x bins].  calibrate does not set the temperature.
+    //   set_temperature(T != 1): predict() keeps the log-softmax rows, runs gcnhip_calib_scale_rows on the queried rows and returns
+    //   the scaled prob (and logp); pred does not depend on T.  correct_and_smooth() scales its rows in place before the residual.
+    //   At T == 1 (the default) neither launches anything new.  Training, eval, evaluate and the weights file ignore it.
+    struct Calibrated {
+        float temperature = 1.f;
+        double nll_before = 0, nll_after = 0;                  // mean NLL of the split at beta = 1 and at the result
+        int steps = 0;
+        bool at_bound = false;
+        int64_t rows = 0;
+    };
+    void calibration(int split, const int *nodes, int n, float temperature, int bins, double *sums, int64_t *count, int64_t *correct, double *conf_sum);
+    Calibrated calibrate(int split, int bins, int64_t *count, int64_t *correct, double *conf_sum);
+    void set_temperature(float t);
+    float temperature() const { return temperature_; }
+
+private:
+    HipGCN &m;
+    DeviceArena arena;                                         // every device buffer of a query
+    // Device scratch that grows and never shrinks: need(n) returns room for n elements (for one when n == 0: a rank without
+    // rows), allocated on first use and again, contents not kept, when n exceeds the capacity.  An allocation that throws leaves
+    // capacity 0 and NULL behind.  Zeroed: a new block is cleared (tables whose padding no launch writes but a download may read).
+    template <class T, bool Zeroed = false>
+    struct Scratch {
+        DeviceArena *arena;
+        T *p = nullptr;
+        size_t cap = 0;
+        T *need(size_t n) {
+            if (n < 1) n = 1;
+            if (n <= cap) return p;
+            cap = 0;
+            arena->release(p);
+            p = nullptr;
+            p = Zeroed ? arena->alloc_zeroed<T>(n) : arena->alloc<T>(n);
+            cap = n;
+            return p;
+        }
+    };
+    // what a call needs of the model (require): the refusals every query shares, worded once
+    enum Need { SINGLE_LABEL = 1, MULTI_LABEL = 2, CLASS_AGGREGATION = 4, AT_MOST_64 = 8, AT_MOST_256 = 16, ONE_RANK = 32 };
+    void require(const char *what, int needs) const;
+
+    // predict, evaluate, calibration, Correct & Smooth: predicted class and its probability per local row, the log-softmax rows
+    // [local rows x C]; the last node query's row subset (registered on the adjacency, removed when the next query differs)
+    Scratch<int32_t> d_pred{&arena};
+    Scratch<float> d_prob{&arena}, d_logp{&arena};
+    std::vector<uint32_t> pred_bits;
+    gcnhip_rowset *pred_rows = nullptr;
+    // predict_multilabel, evaluate: scratch logits [local rows x ld of Z]; the query's bits, probabilities and rows
+    Scratch<float, true> d_ml_logits{&arena};
+    Scratch<uint32_t> d_ml_bits{&arena};
+    Scratch<float> d_ml_prob{&arena};
+    Scratch<int32_t> d_ml_rows{&arena};
+    // evaluate: the counts on the device (also the float limbs of their all-reduce), an uploaded row list; every local label,
+    // uploaded once
+    Scratch<int32_t> d_eval_counts{&arena}, d_eval_rows{&arena};
+    int32_t *d_label_all = nullptr;
+    // propagate / label_propagation / correct_and_smooth: four tables [local rows x ld] that grow together, the merged truth of
+    // the known splits, sigma = {sum |E_0|, rows}
+    Scratch<float, true> d_smooth[4] = {{&arena}, {&arena}, {&arena}, {&arena}};
+    Scratch<int32_t> d_smooth_truth{&arena};
+    Scratch<float> d_sigma{&arena};
+    // calibration / calibrate: {nll sums [4] | conf_sum [2 x 64]} doubles and {count, correct} [2 x 2 x 64] ints on the device
+    float temperature_ = 1.f;
+    Scratch<double> d_calib_sums{&arena};
+    Scratch<int32_t> d_calib_counts{&arena};
+
+    void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
+    const gcnhip_rowset *query_subset(const std::vector<int> &rows);
+    const int32_t *upload_rows(const std::vector<int> &rows);
+    // the rows a split or a query names, as evaluate() lists them, and the truth they are scored against
+    struct ScoredRows { const int32_t *d_list; int n; const int32_t *truth; const gcnhip_rowset *subset; };
+    ScoredRows scored_rows(const char *what, int split, const int *nodes, int n);
+    // the two hooked forwards: d_pred / d_prob (and d_logp when kept) of the subset's rows; their logits into d_ml_logits
+    void forward_predict(const gcnhip_rowset *subset, bool keep_logp);
+    void forward_redirect(const gcnhip_rowset *subset);
+    static int smooth_row_ld(int dim) { return dim <= 32 ? (dim + 3) / 4 * 4 : (dim + 15) / 16 * 16; }   // HipVariable's rule
+    void smooth_check(const char *what, int needs, float alpha, int iters) const;
+    const int32_t *smooth_truth(const char *what, int splits_mask, std::vector<int32_t> *host);
+    float *smooth_iterate(const float *base, float *a, float *b, int ld, int dim, float alpha, int iters, float lo, float hi, int32_t *pred);
+    void smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows);
+    void smooth_pred_download(int32_t *pred);
+    void calib_check(const char *what, float temperature, int bins) const;
+    void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
+};

@@ -1,5 +1,5 @@
 // report.h — per-class metrics from integer counts (beyond the reference, which reports one accuracy per split).  Host only:
-// no GPU.  The ONE place where precision / recall / F1 are derived: HipGCN::evaluate's callers (the Python binding, gcn-hip's
+// no GPU.  The ONE place where precision / recall / F1 are derived: ModelQueries::evaluate's callers (the Python binding, gcn-hip's
 // GCN_REPORT) hand it the counts the GPU formed.
 //
 // Everything is float64 arithmetic on integers: each per-class metric is one division of two exactly represented integers

@@ -211,6 +211,84 @@ def test_predict_between_epochs_changes_nothing(flags):
     b.close()
 
 
+def same_result(x, y):
+    """results of one query on two models: integer and bool arrays equal, float arrays equal bit for bit, the rest =="""
+    if isinstance(x, dict):
+        return x.keys() == y.keys() and all(same_result(x[k], y[k]) for k in x)
+    if isinstance(x, tuple):
+        return len(x) == len(y) and all(same_result(p, q) for p, q in zip(x, y))
+    if isinstance(x, np.ndarray):
+        return x.dtype == y.dtype and x.shape == y.shape and np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes()
+    return x == y or (x != x and y != y)                 # (a metric of an empty class may be NaN)
+
+
+def check_any_order(a, b, steps):
+    """model a runs the queries top to bottom, model b (the same weights) bottom to top: scratch that an earlier, larger or
+    smaller query sized must not show in any result"""
+    ra = [call(a) for _, call in steps]
+    rb = [call(b) for _, call in reversed(steps)][::-1]
+    for (name, _), x, y in zip(steps, ra, rb):
+        assert same_result(x, y), name
+    return ra, rb
+
+
+def test_queries_in_any_order_single_label():
+    """the twelve single-label queries — node queries of 3, 5, 1000 and 1500 ids, splits, 64- and 3-wide propagation, Correct &
+    Smooth, a fit — give the same bits whichever way round they run; the first and the last (the same 3 ids) agree too"""
+    from cuda_gcn_amd.model import HipGCNModel
+    ds = datagen.make_dataset("cora-syn")
+    N = ds["num_nodes"]
+    a = HipGCNModel(ds, seed=6, hidden_dim=16, dropout=0.5)
+    b = HipGCNModel(ds, seed=6, hidden_dim=16, dropout=0.5)
+    for _ in range(3):
+        a.train_epoch()
+    b.set_weights(a.var(2), a.var(5))
+    rng = np.random.default_rng(0)
+    q3, q5 = rng.permutation(N)[:3].astype(np.int32), rng.permutation(N)[:5].astype(np.int32)
+    q1000, q1500 = rng.integers(0, N, 1000).astype(np.int32), rng.integers(0, N, 1500).astype(np.int32)
+    y64, y3 = rng.random((N, 64), np.float32), rng.random((N, 3), np.float32)
+    steps = [("predict 3", lambda m: m.predict(nodes=q3)),
+             ("evaluate split 3", lambda m: m.evaluate(split=3)),
+             ("calibration 1000", lambda m: m.calibration(nodes=q1000, temperature=1.5, bins=7)),
+             ("predict logp", lambda m: m.predict(logp=True)),
+             ("propagate 64", lambda m: m.propagate(y64, 0.8, 2)),
+             ("propagate 3 argmax", lambda m: m.propagate(y3, 0.8, 2, argmax=True)),
+             ("correct_and_smooth", lambda m: m.correct_and_smooth(iters_correct=2, iters_smooth=2)),
+             ("evaluate 5", lambda m: m.evaluate(nodes=q5)),
+             ("predict 1500 logp", lambda m: m.predict(nodes=q1500, logp=True)),
+             ("calibrate", lambda m: m.calibrate(apply=False)),
+             ("label_propagation", lambda m: m.label_propagation(iters=2)),
+             ("predict 3 again", lambda m: m.predict(nodes=q3))]
+    ra, rb = check_any_order(a, b, steps)
+    assert ra[9] == rb[9]                                                                # calibrate's dict: plain numbers
+    assert same_result(ra[0], ra[11]) and same_result(rb[0], rb[11])
+    a.close()
+    b.close()
+
+
+def test_queries_in_any_order_multilabel():
+    """the same for a multi-label model: queries of 2 and 700 ids, the test split and every row"""
+    from cuda_gcn_amd.model import HipGCNModel
+    ds = datagen.planted_multilabel(classes=41)
+    N = ds["num_nodes"]
+    kw = dict(seed=6, hidden_dim=16, dropout=0.5, multilabel=ds["multilabel"])
+    a, b = HipGCNModel(ds, **kw), HipGCNModel(ds, **kw)
+    for _ in range(3):
+        a.train_epoch()
+    b.set_weights(a.var(2), a.var(5))
+    rng = np.random.default_rng(1)
+    q2, q700 = rng.permutation(N)[:2].astype(np.int32), rng.integers(0, N, 700).astype(np.int32)
+    steps = [("predict_multilabel 2", lambda m: m.predict_multilabel(nodes=q2)),
+             ("predict_multilabel 700 prob", lambda m: m.predict_multilabel(nodes=q700, prob=True)),
+             ("evaluate split 3", lambda m: m.evaluate(split=3)),
+             ("predict_multilabel", lambda m: m.predict_multilabel()),
+             ("predict_multilabel 2 again", lambda m: m.predict_multilabel(nodes=q2))]
+    ra, rb = check_any_order(a, b, steps)
+    assert same_result(ra[0], ra[4]) and same_result(rb[0], rb[4])
+    a.close()
+    b.close()
+
+
 def test_save_and_load_weights(tmp_path):
     """a model saves its weights; a model with a different seed loads them: eval(2), eval(3) and predict() are bit-identical;
     a file with other widths is refused"""
