@@ -110,6 +110,11 @@ GCNHIP_SYMBOLS = {
     "gcnhip_calib_nll_rows": (I, [P, P, I, P, I, P, I, I, F, P]),
     "gcnhip_calib_bins_rows": (I, [P, P, I, P, I, P, I, I, F, I, P, P, P]),
     "gcnhip_calib_scale_rows": (I, [P, P, I, I, P, I, I, F, P, I, P]),
+    "gcnhip_embed_inv_norms": (I, [P, P, I, I, I, P]),
+    "gcnhip_topk_plan": (I, [I, I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_topk_rows": (I, [P, P, I, I, I, P, P, P, I, I, I, I, P, C.c_size_t, I, P, P]),
+    "gcnhip_pair_scores": (I, [P, P, I, I, I, P, P, P, I, P]),
+    "gcnhip_embed_rows": (I, [P, P, I, I, I, P, P, I, P, I]),
     "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
@@ -230,6 +235,9 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_calibrate": (I, [P, I, I, P, P, P, P]),
     "gcnhost_model_set_temperature": (I, [P, F]),
     "gcnhost_model_temperature": (I, [P, C.POINTER(F)]),
+    "gcnhost_model_embed": (I, [P, P, I, P, I]),
+    "gcnhost_model_similar": (I, [P, P, I, I, I, I, P, P]),
+    "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),
     "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),

@@ -259,6 +259,18 @@ int gcnhost_model_temperature(gcnhost_model *m, float *temperature) {
     if (!m || !temperature) { g_err = "gcnhost_model_temperature: invalid argument"; return -1; }
     API_TRY({ *temperature = m->gcn->queries().temperature(); })
 }
+int gcnhost_model_embed(gcnhost_model *m, const int *nodes, int n, float *out, int normalize) {
+    if (!m) { g_err = "gcnhost_model_embed: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().embed(nodes, n, out, normalize != 0); })
+}
+int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int metric, int exclude_self, int32_t *out_id, float *out_score) {
+    if (!m) { g_err = "gcnhost_model_similar: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().similar(nodes, n, k, metric, exclude_self != 0, out_id, out_score); })
+}
+int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out) {
+    if (!m) { g_err = "gcnhost_model_score_pairs: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().score_pairs(src, dst, n_pairs, metric, out); })
+}
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary) {
     CalibrationReport r;

@@ -264,6 +264,7 @@ private:
     friend class ModelQueries;
     std::unique_ptr<ModelQueries> queries_;
     void forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect);
+    bool forward_hidden_only();                                // aggregate-first models: the hidden layer alone, stored; false: no such form
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

@@ -49,6 +49,17 @@ void HipGCN::forward_hooked(const HipGraphSum::Prediction *prediction, const Hip
     if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
 }
 
+// The hidden matrix of an evaluation forward in variable 3 at the price of its own product: an aggregate-first model computes
+// ReLU((A^.X).W1) in one launch (what get_var(3) runs after a fused evaluation, so the bits are get_var's).  Other models have
+// no such form: the caller runs a whole hooked forward, whose hidden-width aggregation stores the matrix.
+bool HipGCN::forward_hidden_only() {
+    if (eval_modules.empty()) return false;
+    refresh_input();
+    static_cast<HipSparseMatmul *>(eval_modules[0])->forward_stored();
+    h1_from_fused_eval = false;
+    return true;
+}
+
 void HipGCN::save_weights(const char *path) {
     std::vector<float> w1, w2;
     get_var(2, false, w1, nullptr, nullptr);

@@ -56,6 +56,12 @@
 //                            calibration error of the TEST split, 15 bins).  The file gets the test split's reliability table at
 //                            T = 1 and at the fitted T (host/calibration.h: a summary line, then one line per bin).  Works with
 //                            GCN_LOAD_WEIGHTS and 0 epochs.  One GPU, single-label, at most 64 classes.
+// Node embeddings (beyond the reference; ModelQueries::embed / similar, kernels in csrc/embed.hip), after the test line and every
+// post-processing step above; stdout is unchanged.  One GPU, hidden_dim at most 256; single- and multi-label models alike:
+//   GCN_EMBED=<file>         one line per node of the dataset in id order: `node v1 ... vh`, the node's row of the hidden layer
+//                            H1 = ReLU(A^.X.W1) of an evaluation forward with the final (or loaded) weights, %.9g (exact f32).
+//   GCN_SIMILAR=<file>       one line per node: `node id:score ...`, its 10 nearest nodes by the cosine of those rows (best
+//                            first, equal scores by ascending id, the node itself left out), found on the GPU.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -188,6 +194,19 @@ int main(int argc, char **argv) {
         }
     }
 
+    const char *embed_path = getenv("GCN_EMBED"), *similar_path = getenv("GCN_SIMILAR");
+    if (embed_path && !*embed_path) embed_path = nullptr;
+    if (similar_path && !*similar_path) similar_path = nullptr;
+    if (embed_path || similar_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1 ? "run on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256  ? "take a hidden width of at most 256"
+                                                     : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_EMBED / GCN_SIMILAR " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     int n_dev = 0;
     if (gcnhip_device_count(&n_dev) != 0 || n_dev < 1) {
         std::cerr << "gcn-hip: no GPU available (this backend has no CPU path; use gcn-seq)" << std::endl;
@@ -303,6 +322,39 @@ int main(int argc, char **argv) {
                 std::vector<int64_t> cnt(report_counts.size());
                 gcn.queries().evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
                 if (rank == 0) report_counts = cnt;
+            }
+            if (embed_path) {                                  // one rank (checked above): rows by node id
+                const int N = params.num_nodes, h = params.hidden_dim;
+                std::vector<float> e((size_t)std::max(N, 1) * h);
+                gcn.queries().embed(nullptr, N, e.data(), false);
+                FILE *f = fopen(embed_path, "w");
+                bool ok = f != nullptr;
+                for (int i = 0; ok && i < N; i++) {
+                    ok = fprintf(f, "%d", i) > 0;
+                    for (int j = 0; ok && j < h; j++) ok = fprintf(f, " %.9g", e[(size_t)i * h + j]) > 0;
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the embeddings to ") + embed_path);
+                fprintf(stderr, "gcn-hip: embeddings of %d nodes (%d wide) written to %s\n", N, h, embed_path);
+            }
+            if (similar_path) {
+                constexpr int K = 10;
+                const int N = params.num_nodes;
+                std::vector<int32_t> ids((size_t)std::max(N, 1) * K);
+                std::vector<float> sc((size_t)std::max(N, 1) * K);
+                gcn.queries().similar(nullptr, N, K, ModelQueries::METRIC_COSINE, true, ids.data(), sc.data());
+                FILE *f = fopen(similar_path, "w");
+                bool ok = f != nullptr;
+                for (int i = 0; ok && i < N; i++) {
+                    ok = fprintf(f, "%d", i) > 0;
+                    for (int j = 0; ok && j < K && ids[(size_t)i * K + j] >= 0; j++)
+                        ok = fprintf(f, " %d:%.9g", ids[(size_t)i * K + j], sc[(size_t)i * K + j]) > 0;
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the neighbours to ") + similar_path);
+                fprintf(stderr, "gcn-hip: %d cosine neighbours of %d nodes written to %s\n", K, N, similar_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

@@ -1,10 +1,11 @@
-// queries.cpp — ModelQueries: prediction, per-class evaluation, label propagation and Correct & Smooth, temperature scaling
-// on a built HipGCN, between passes.  Off the epoch path.
+// queries.cpp — ModelQueries: prediction, per-class evaluation, label propagation and Correct & Smooth, temperature scaling,
+// node embeddings on a built HipGCN, between passes.  Off the epoch path.
 #include "queries.h"
 #include "gcn.h"
 #include "hip_check.h"
 #include <algorithm>
 #include <cmath>
+#include <numeric>
 
 ModelQueries::ModelQueries(HipGCN &model) : m(model) { arena.bind(m.env.ctx); }
 
@@ -430,4 +431,100 @@ ModelQueries::Calibrated ModelQueries::calibrate(int split, int bins, int64_t *c
     }
     m.sync();
     return out;
+}
+
+// ---- node embeddings ------------------------------------------------------------------------------------------------------
+
+void ModelQueries::embed_check(const char *what, int metric) const {
+    require(what, ONE_RANK);
+    if (m.params.hidden_dim < 1 || m.params.hidden_dim > 256)
+        throw GcnHipFailure(-1, std::string(what) + ": a hidden width of at most 256 (the embedding kernels keep a query tile in LDS)");
+    if (metric != METRIC_DOT && metric != METRIC_COSINE) throw GcnHipFailure(-1, std::string(what) + ": the metric is 0 (dot) or 1 (cosine)");
+}
+
+std::vector<int> ModelQueries::embed_query(const char *what, const int *nodes, int &n) {
+    std::vector<int> all, rows;
+    if (!nodes) {                                              // every node, in dataset id order
+        all.resize((size_t)m.params.num_nodes);
+        std::iota(all.begin(), all.end(), 0);
+        nodes = all.data();
+        n = (int)all.size();
+    }
+    query_rows(what, nodes, n, rows);
+    return rows;
+}
+
+ModelQueries::EmbedTable ModelQueries::embed_forward(bool norms) {
+    if (!m.forward_hidden_only()) forward_redirect(nullptr);
+    const HipVariable &h1 = *m.variables[3];
+    EmbedTable t{h1.data, h1.ld, m.n_local, m.params.hidden_dim, nullptr};
+    if (norms) {
+        GCNHIP_CHECK(gcnhip_embed_inv_norms(m.env.ctx, t.data, t.ld, t.rows, t.dim, d_emb_inv.need((size_t)t.rows)));
+        t.inv_norm = d_emb_inv.p;
+    }
+    return t;
+}
+
+void ModelQueries::embed(const int *nodes, int n, float *out, bool normalize) {
+    embed_check("embed", METRIC_DOT);
+    if (n < 0 || (!out && (n > 0 || !nodes))) throw GcnHipFailure(-1, "embed: invalid argument");
+    const std::vector<int> rows = embed_query("embed", nodes, n);
+    m.sync();                                                  // run()'s epochs in flight, the validation lane's pass
+    const EmbedTable t = embed_forward(normalize);
+    if (n == 0) { m.sync(); return; }
+    int32_t *d_rows = d_emb_rows.need((size_t)n);
+    float *d_out = d_emb_out.need((size_t)n * t.dim);
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_embed_rows(m.env.ctx, t.data, t.ld, t.rows, t.dim, t.inv_norm, d_rows, n, d_out, t.dim));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, out, d_out, (size_t)n * t.dim * sizeof(float)));
+}
+
+void ModelQueries::similar(const int *nodes, int n, int k, int metric, bool exclude_self, int32_t *out_id, float *out_score) {
+    embed_check("similar", metric);
+    if (k < 1 || k > 64) throw GcnHipFailure(-1, "similar: k must be in 1..64 (a list is one entry per lane)");
+    if (n < 0 || ((!out_id || !out_score) && (n > 0 || !nodes))) throw GcnHipFailure(-1, "similar: invalid argument");
+    const std::vector<int> rows = embed_query("similar", nodes, n);
+    m.sync();
+    if (m.n_local < 1) {                                       // no candidate at all: every slot is the empty one
+        std::fill(out_id, out_id + (size_t)n * k, -1);
+        std::fill(out_score, out_score + (size_t)n * k, -INFINITY);
+        return;
+    }
+    if (!d_node_ids) {                                         // the dataset id of every local row: the order never changes
+        std::vector<int32_t> ids((size_t)m.n_local);
+        for (int r = 0; r < m.n_local; r++) ids[r] = m.node_id(r);
+        d_node_ids = arena.upload(ids.data(), ids.size());
+    }
+    const EmbedTable t = embed_forward(metric == METRIC_COSINE);
+    if (n == 0) { m.sync(); return; }
+    size_t full = 0, least = 0;
+    if (gcnhip_topk_plan(t.rows, n, k, 0, nullptr, nullptr, &full, &least) != 0) throw GcnHipFailure(-1, std::string("similar: ") + gcnhip_last_error());
+    const size_t bytes = std::max(std::min(full, EMBED_SCRATCH_CAP), least);
+    int32_t *d_rows = d_emb_rows.need((size_t)n);
+    int32_t *d_ids = d_emb_ids.need((size_t)n * k);
+    float *d_scores = d_emb_out.need((size_t)n * k);
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_topk_rows(m.env.ctx, t.data, t.ld, t.rows, t.dim, t.inv_norm, d_node_ids, d_rows, n, k, exclude_self ? 1 : 0, 0,
+                                  d_emb_scratch.need(bytes), bytes, 3, d_ids, d_scores));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, out_id, d_ids, (size_t)n * k * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, out_score, d_scores, (size_t)n * k * sizeof(float)));
+}
+
+void ModelQueries::score_pairs(const int *src, const int *dst, int n_pairs, int metric, float *out) {
+    embed_check("score_pairs", metric);
+    if (n_pairs < 0 || (n_pairs > 0 && (!src || !dst || !out))) throw GcnHipFailure(-1, "score_pairs: invalid argument");
+    std::vector<int> rows, rows_dst;
+    if (n_pairs) {
+        query_rows("score_pairs", src, n_pairs, rows);
+        query_rows("score_pairs", dst, n_pairs, rows_dst);
+        rows.insert(rows.end(), rows_dst.begin(), rows_dst.end());
+    }
+    m.sync();
+    const EmbedTable t = embed_forward(metric == METRIC_COSINE);
+    if (n_pairs == 0) { m.sync(); return; }
+    int32_t *d_rows = d_emb_rows.need(2 * (size_t)n_pairs);    // src, then dst
+    float *d_out = d_emb_out.need((size_t)n_pairs);
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_rows, rows.data(), rows.size() * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_pair_scores(m.env.ctx, t.data, t.ld, t.rows, t.dim, t.inv_norm, d_rows, d_rows + n_pairs, n_pairs, d_out));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, out, d_out, (size_t)n_pairs * sizeof(float)));
 }

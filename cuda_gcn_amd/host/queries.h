@@ -1,13 +1,13 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
-// evaluation, label propagation and Correct & Smooth, temperature scaling.  ModelQueries owns every device buffer and every
+// evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings.  ModelQueries owns every device buffer and every
 // piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
 //   reads   params, opt_.multilabel, env (context, comm), n_local, row_start(), node_order_ (query_rows' inverse map; node_id()
 //           elsewhere), data->split, data->label, graph, logits_gs (null test only), variables[6]->ld, d_truth[], split_rows[],
-//           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr
-//   calls   sync(), forward_hooked()
+//           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr, variables[3] (data, ld), node_id()
+//   calls   sync(), forward_hooked(), forward_hidden_only()
 // It writes no member of HipGCN.
 #pragma once
 #include <cstdint>
@@ -99,6 +99,27 @@ public:
     Calibrated calibrate(int split, int bins, int64_t *count, int64_t *correct, double *conf_sum);
     void set_temperature(float t);
     float temperature() const { return temperature_; }
+    // Node embeddings: the hidden matrix H1 = ReLU(A^.X.W1) of an evaluation forward with the current weights (no dropout), as
+    // variable 3 stores it — on a factored model (HipGCN::factored()) row r carries the factor dinv[r], which cosine scores and
+    // normalised rows do not see — queried where it lies.  The csrc/embed.hip kernels do the work; ids are DATASET node ids
+    // everywhere, and ties of similar() are broken by dataset id (row_id = node_id()).  predict()'s contract: the call starts
+    // with sync(); the metrics ring, the current split, variable 6 and the captured epoch graph are untouched; variable 3 is
+    // rewritten, as by every forward, and h1_from_fused_eval stays truthful.  Single- and multi-label models alike.  Every call
+    // recomputes the hidden layer (an aggregate-first model: its one product, HipGCN::forward_hidden_only; else a whole hooked
+    // forward with the logits redirected to scratch) and the norms: nothing is cached, so nothing can go stale when weights
+    // change.  Refused with a message before any launch: more than one rank (the table would need an exchange), a hidden width
+    // above 256, k outside 1..64, a metric other than METRIC_DOT / METRIC_COSINE, a node id outside the graph.
+    //   embed: out [n x hidden] = the rows of `nodes` (n dataset ids, repeats allowed; NULL: every node in id order, n ignored),
+    //   gathered on the device so that only n x hidden floats cross; normalize: each row times 1 / its norm (a zero row stays zero).
+    //   similar: per queried node (NULL: every node) the k best nodes of the graph by METRIC_DOT (the f32 dot product) or
+    //   METRIC_COSINE, best first, equal scores by ascending id, without the node itself when exclude_self: out_id / out_score
+    //   [n x k]; slots past the candidates hold -1 / -inf.  The per-chunk lists go through a scratch block of at most 64 MiB:
+    //   more queries than it holds are answered in batches.
+    //   score_pairs: out[i] = the score of nodes (src[i], dst[i]); src[i] == dst[i] is allowed.
+    enum Metric { METRIC_DOT = 0, METRIC_COSINE = 1 };
+    void embed(const int *nodes, int n, float *out, bool normalize);
+    void similar(const int *nodes, int n, int k, int metric, bool exclude_self, int32_t *out_id, float *out_score);
+    void score_pairs(const int *src, const int *dst, int n_pairs, int metric, float *out);
 
 private:
     HipGCN &m;
@@ -150,6 +171,13 @@ private:
     float temperature_ = 1.f;
     Scratch<double> d_calib_sums{&arena};
     Scratch<int32_t> d_calib_counts{&arena};
+    // embed / similar / score_pairs: inverse norms [local rows]; the dataset id of every local row, uploaded once; the query's
+    // rows (two lists for pairs), its float and int results, and the partial lists of the top-k product
+    Scratch<float> d_emb_inv{&arena}, d_emb_out{&arena};
+    Scratch<int32_t> d_emb_rows{&arena}, d_emb_ids{&arena};
+    Scratch<unsigned char> d_emb_scratch{&arena};
+    int32_t *d_node_ids = nullptr;
+    static constexpr size_t EMBED_SCRATCH_CAP = (size_t)64 << 20;
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
@@ -167,5 +195,9 @@ private:
     void smooth_download(const float *table, int ld, int dim, float *out, int32_t *pred_from_rows);
     void smooth_pred_download(int32_t *pred);
     void calib_check(const char *what, float temperature, int bins) const;
+    void embed_check(const char *what, int metric) const;
+    std::vector<int> embed_query(const char *what, const int *nodes, int &n);            // dataset ids (NULL: all) -> local rows
+    struct EmbedTable { const float *data; int ld, rows, dim; const float *inv_norm; };
+    EmbedTable embed_forward(bool norms);                      // the hidden matrix where variable 3 keeps it (and its inverse norms)
     void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
 };

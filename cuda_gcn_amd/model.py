@@ -403,6 +403,70 @@ class HipGCNModel:
         out.update(nll=float(sums[0] / sums[3]) if sums[3] else 0.0, temperature=t, sums=sums)
         return out
 
+    # ---- node embeddings: the hidden layer H1 = ReLU(A^.X.W1), queried on the GPU
+    METRICS = {"dot": 0, "cosine": 1}
+
+    def _embed_args(self, what, metric="dot", k=1, **node_lists):
+        """argument checks that need no GPU; returns the metric's code and the node lists as int32 arrays"""
+        if metric not in self.METRICS:
+            raise GcnHostError(f"{what}: the metric is 'dot' or 'cosine', got {metric!r}")
+        if not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= 64):
+            raise GcnHostError(f"{what}: k must be an integer in 1..64, got {k!r}")
+        if self.params.hidden_dim > 256:
+            raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+        out = []
+        for name, nodes in node_lists.items():
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            if q.size and (q.min() < 0 or q.max() >= self.params.num_nodes):
+                raise GcnHostError(f"{what}: {name} holds an id that is not a node of the dataset (0..{self.params.num_nodes - 1})")
+            out.append(q)
+        return [self.METRICS[metric]] + out
+
+    def embed(self, nodes=None, normalize=False):
+        """float32 [n, hidden_dim] — the rows of the hidden layer H1 = ReLU(A^.X.W1) of an evaluation forward with the current
+        weights (no dropout) for the listed dataset node ids (repeats allowed; None: every node, in id order), gathered on the
+        GPU so that only these rows cross.  The values are var(3)'s: a factored model (row_scale()) keeps 1/sqrt(deg) of the
+        node on its row.  normalize=True: each row divided by its Euclidean norm (an all-zero row stays zero).  One rank, hidden
+        width at most 256.  Training state is not touched."""
+        if nodes is None:
+            n, qp = self.params.num_nodes, None
+        else:
+            _, q = self._embed_args("embed", nodes=nodes)
+            n, q = q.size, (q if q.size else np.zeros(1, np.int32))         # an empty query is still a query (not "every node")
+            qp = q.ctypes.data
+        out = np.zeros((max(n, 1), self.params.hidden_dim), np.float32)
+        _ck(self.lib, self.lib.gcnhost_model_embed(self.h, qp, n, out.ctypes.data, int(bool(normalize))), "embed")
+        return out[:n]
+
+    def similar(self, nodes, k=10, metric="cosine", exclude_self=True):
+        """(ids int32 [n, k], scores float32 [n, k]) — for each listed node (None: every node) the k nodes of the graph whose
+        embed() rows score highest against its own: metric "dot" (the f32 dot product) or "cosine"; best first, equal scores by
+        ascending node id; without the node itself unless exclude_self=False.  Slots past the last candidate hold -1 / -inf.  The
+        n x N x hidden product and the selection run on the GPU; only the answer crosses.  1 <= k <= 64."""
+        if nodes is None:
+            code, = self._embed_args("similar", metric, k)
+            n, qp = self.params.num_nodes, None
+        else:
+            code, q = self._embed_args("similar", metric, k, nodes=nodes)
+            n, q = q.size, (q if q.size else np.zeros(1, np.int32))
+            qp = q.ctypes.data
+        ids = np.zeros((max(n, 1), k), np.int32)
+        scores = np.zeros((max(n, 1), k), np.float32)
+        _ck(self.lib, self.lib.gcnhost_model_similar(self.h, qp, n, int(k), code, int(bool(exclude_self)), ids.ctypes.data, scores.ctypes.data), "similar")
+        return ids[:n], scores[:n]
+
+    def score_edges(self, src, dst, metric="dot"):
+        """float32 [m] — the score of every listed node pair (src[i], dst[i]) under the metric: candidate edges ranked by the
+        embeddings of their ends.  src[i] == dst[i] is allowed (cosine: about 1, or 0 for a zero row)."""
+        code, s, d = self._embed_args("score_edges", metric, src=src, dst=dst)
+        if s.size != d.size:
+            raise GcnHostError(f"score_edges: {s.size} sources for {d.size} destinations")
+        out = np.zeros(max(s.size, 1), np.float32)
+        z = np.zeros(1, np.int32)
+        _ck(self.lib, self.lib.gcnhost_model_score_pairs(self.h, (s if s.size else z).ctypes.data, (d if d.size else z).ctypes.data, int(s.size), code,
+                                                         out.ctypes.data), "score_edges")
+        return out[:s.size]
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")

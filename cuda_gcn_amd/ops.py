@@ -340,6 +340,84 @@ class Device:
             raise GcnHipError(f"gcnhip_calib_scale_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return ob.download(), pb.download()[:n_table]
 
+    # ---- node embeddings (csrc/embed.hip): the table is uploaded with row stride ld and NaN padding
+    def _embed_inputs(self, table, ld, inv_norm):
+        table = np.ascontiguousarray(table, np.float32)
+        n_table, dim = table.shape
+        tb = self.padded(table, ld or dim) if n_table else self.buf(np.full((1, ld or dim), np.nan, np.float32))
+        nb = None if inv_norm is None else self.buf(np.ascontiguousarray(inv_norm, np.float32) if n_table else np.zeros(1, np.float32))
+        return tb, nb, n_table, dim, int(ld or dim)
+
+    def _embed_fail(self, what, rc):
+        raise GcnHipError(f"{what}: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+
+    def embed_inv_norms(self, table, ld=None):
+        """gcnhip_embed_inv_norms: f32 [n_table] = 1 / sqrt(sum of squares) of every row, exactly 0 for an all-zero row"""
+        tb, _, n_table, dim, ld = self._embed_inputs(table, ld, None)
+        ob = self.buf(np.full(max(n_table, 1), np.nan, np.float32))
+        rc = self.lib.gcnhip_embed_inv_norms(self.ctx, tb.ptr, ld, n_table, dim, ob.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_embed_inv_norms", rc)
+        return ob.download()[:n_table]
+
+    def topk_plan(self, n_table, nq, k, chunk_rows=0):
+        """gcnhip_topk_plan: dict(chunk_rows, n_chunks, scratch_bytes, scratch_bytes_min) of a gcnhip_topk_rows call"""
+        rows, chunks = C.c_int(), C.c_int()
+        full, least = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_topk_plan(int(n_table), int(nq), int(k), int(chunk_rows), C.byref(rows), C.byref(chunks), C.byref(full), C.byref(least))
+        if rc != 0:
+            self._embed_fail("gcnhip_topk_plan", rc)
+        return dict(chunk_rows=rows.value, n_chunks=chunks.value, scratch_bytes=full.value, scratch_bytes_min=least.value)
+
+    def topk_rows(self, table, q_rows, k, inv_norm=None, row_id=None, exclude_self=True, chunk_rows=0, ld=None, scratch_bytes=None, launches=3,
+                  plan=False):
+        """gcnhip_topk_rows: (ids int32 [nq, k], scores f32 [nq, k]) — the k best rows of `table` per listed query row, by dot
+        product (inv_norm None) or cosine (inv_norm: embed_inv_norms of the table), best first, equal scores by ascending id
+        (row_id[c], or c).  The outputs are uploaded as garbage.  scratch_bytes: the caller's scratch (None: room for every query
+        at once); plan=True: a third value, topk_plan's dict for this call."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        q = np.ascontiguousarray(q_rows, np.int32).ravel()
+        nq, k = int(q.size), int(k)
+        qb = self.buf(q if nq else np.zeros(1, np.int32))
+        rb = None if row_id is None else self.buf(np.ascontiguousarray(row_id, np.int32))
+        info = self.topk_plan(n_table, nq, k, chunk_rows)
+        sbytes = info["scratch_bytes"] if scratch_bytes is None else int(scratch_bytes)
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        ib = self.buf(np.full(max(nq * k, 1), 12345, np.int32))
+        ob = self.buf(np.full(max(nq * k, 1), np.nan, np.float32))
+        rc = self.lib.gcnhip_topk_rows(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, qb.ptr, nq, k,
+                                       int(bool(exclude_self)), int(chunk_rows), sb.ptr, sbytes, int(launches), ib.ptr, ob.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_topk_rows", rc)
+        out = ib.download()[:nq * k].reshape(nq, k), ob.download()[:nq * k].reshape(nq, k)
+        return out + (info,) if plan else out
+
+    def pair_scores(self, table, src, dst, inv_norm=None, ld=None):
+        """gcnhip_pair_scores: f32 [m] = the score (dot, or cosine with inv_norm) of the listed row pairs"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        s, d = np.ascontiguousarray(src, np.int32).ravel(), np.ascontiguousarray(dst, np.int32).ravel()
+        assert s.size == d.size
+        m = int(s.size)
+        sb, db = self.buf(s if m else np.zeros(1, np.int32)), self.buf(d if m else np.zeros(1, np.int32))
+        ob = self.buf(np.full(max(m, 1), np.nan, np.float32))
+        rc = self.lib.gcnhip_pair_scores(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, sb.ptr, db.ptr, m, ob.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_pair_scores", rc)
+        return ob.download()[:m]
+
+    def embed_rows(self, table, rows=None, inv_norm=None, ld=None, ld_out=None, fill=np.nan):
+        """gcnhip_embed_rows: f32 [n, dim] = the listed rows of the table (None: every row), times inv_norm of the row when given"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        n = n_table if r is None else int(r.size)
+        rb = None if r is None else self.buf(r if n else np.zeros(1, np.int32))
+        ld_out = int(ld_out or dim)
+        ob = self.buf(np.full((max(n, 1), ld_out), fill, np.float32))
+        rc = self.lib.gcnhip_embed_rows(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, ob.ptr, ld_out)
+        if rc != 0:
+            self._embed_fail("gcnhip_embed_rows", rc)
+        return ob.download()[:n, :dim]
+
     def graphsum(self, g: "Graph", x, ld_in=None, ld_out=None, row_nonzero=None):
         x = np.asarray(x, np.float32)
         dim = x.shape[1]

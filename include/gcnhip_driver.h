@@ -235,6 +235,35 @@ int gcnhip_calib_bins_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int
                            int num_classes, float beta, int bins, int32_t *d_count, int32_t *d_correct, double *d_conf_sum);
 int gcnhip_calib_scale_rows(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, float beta,
                             float *out_logp, int ld_out, float *d_prob);
+/* ---- node embeddings (embed.hip; beyond the reference: what a GCN learns, taken out without leaving the device) ----
+ * All entry points read an f32 table [n_table x ld] with 1 <= dim <= 256 and dim <= ld, rows of any stride and alignment;
+ * columns [dim, ld) are never read as values.  Score of rows (q, c): their f32 dot product (inv_norm == NULL, metric "dot"),
+ * else (dot . inv_norm[q]) . inv_norm[c] (metric "cosine").  No launch allocates or synchronises; two launches give the same
+ * bits; anything else returns -1 with a message (gcnhip_last_error).
+ * gcnhip_embed_inv_norms: inv_norm[r] = 1 / sqrt(sum_j x_rj^2) in f32; an all-zero row (ReLU makes them) gives exactly 0.
+ * gcnhip_topk_rows: for each of the nq listed query rows (q_rows: device int32, repeats allowed; a row outside the table gets
+ *   the empty answer) the k best of all n_table candidate rows, without the query's own row when exclude_self != 0.  Order:
+ *   score descending, on equal scores the smaller id first, id = row_id[c] (row_id == NULL: c itself) — a total order, so the
+ *   answer does not depend on how the candidates are cut into chunks.  out_id [nq x k] int32 holds ids, out_score [nq x k] f32;
+ *   1 <= k <= 64; with fewer than k candidates the remaining slots are -1 / -inf.  chunk_rows: candidate rows per workgroup,
+ *   0 = the library's choice (gcnhip_topk_plan reports it).  The per-chunk lists go through `scratch`, device memory of the
+ *   caller: gcnhip_topk_plan's *scratch_bytes holds every query at once; with less, down to *scratch_bytes_min (one tile of 64
+ *   queries), the queries are answered in batches of as many tiles as fit — more launches, the same bits.  launches: 3 = the
+ *   product launch and the merge launch (the answer); 1 or 2 = only the one or the other, for timing them apart.
+ * gcnhip_pair_scores: out[i] = score(src[i], dst[i]) for n_pairs listed row pairs (device int32; src[i] == dst[i] allowed); a
+ *   row outside the table gives NaN.
+ * gcnhip_embed_rows: out[i, :dim] = table[d_rows[i], :dim], times inv_norm[d_rows[i]] when inv_norm != NULL (d_rows == NULL:
+ *   row i, n <= n_table); the export gather, so that only the asked rows cross to the host. */
+int gcnhip_embed_inv_norms(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, float *inv_norm);
+int gcnhip_topk_plan(int n_table, int nq, int k, int chunk_rows, int *chunk_rows_used, int *n_chunks, size_t *scratch_bytes,
+                     size_t *scratch_bytes_min);
+int gcnhip_topk_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *row_id,
+                     const int32_t *q_rows, int nq, int k, int exclude_self, int chunk_rows, void *scratch, size_t scratch_bytes,
+                     int launches, int32_t *out_id, float *out_score);
+int gcnhip_pair_scores(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *src,
+                       const int32_t *dst, int n_pairs, float *out);
+int gcnhip_embed_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                      int n, float *out, int ld_out);
 /* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
  * subsets made at call time, such as the node queries of a prediction. */
 int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);

@@ -223,6 +223,20 @@ int gcnhost_model_set_temperature(gcnhost_model *m, float temperature);
 int gcnhost_model_temperature(gcnhost_model *m, float *temperature);
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary);
+/* Node embeddings (ModelQueries, host/queries.h; kernels in csrc/embed.hip): the hidden matrix H1 = ReLU(A^.X.W1) of one evaluation
+ * forward with the current weights (no dropout), as variable 3 stores it (a factored model keeps dinv[r] on row r; cosine scores
+ * and normalised rows do not depend on it), queried on the device.  Ids are DATASET node ids.  predict's contract: training state
+ * is not touched.  One rank, a hidden width of at most 256, single- or multi-label; metric: 0 = dot product, 1 = cosine.  Refused
+ * with a message before any launch: several ranks, a wider hidden layer, k outside 1..64, another metric, a node id outside the graph.
+ * gcnhost_model_embed: out [n x hidden] = the rows of the n listed nodes (repeats allowed; nodes == NULL: every node in id
+ *   order, out [num_nodes x hidden]), gathered on the device; normalize != 0: each row divided by its norm (a zero row stays zero).
+ * gcnhost_model_similar: for each listed node (NULL: every node) the k best nodes by the metric, best first, equal scores by
+ *   ascending id, without the node itself when exclude_self != 0: out_id [n x k] int32, out_score [n x k] f32; -1 / -inf where the
+ *   graph has fewer candidates.
+ * gcnhost_model_score_pairs: out[i] = the score of nodes (src[i], dst[i]). */
+int gcnhost_model_embed(gcnhost_model *m, const int *nodes, int n, float *out, int normalize);
+int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int metric, int exclude_self, int32_t *out_id, float *out_score);
+int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out);
 /* Per-class metrics from integer counts, host only (host/report.h): either confusion [C x C] (row = truth, column =
  * prediction) or tp / fp / fn [C] (the other form NULL).  Every output may be NULL: tp_fp_fn [3 x C] the counts used; support
  * (TP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), f1 = 2 TP / (2 TP + FP + FN) [C], float64, each 0 when
