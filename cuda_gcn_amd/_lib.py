@@ -115,6 +115,10 @@ GCNHIP_SYMBOLS = {
     "gcnhip_topk_rows": (I, [P, P, I, I, I, P, P, P, I, I, I, I, P, C.c_size_t, I, P, P]),
     "gcnhip_pair_scores": (I, [P, P, I, I, I, P, P, P, I, P]),
     "gcnhip_embed_rows": (I, [P, P, I, I, I, P, P, I, P, I]),
+    "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
+    "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
+    "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
+    "gcnhip_explain_abs_colsum": (I, [P, P, I, P, I, I, I, P, P]),
     "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
@@ -238,6 +242,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_embed": (I, [P, P, I, P, I]),
     "gcnhost_model_similar": (I, [P, P, I, I, I, I, P, P]),
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
+    "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),
+    "gcnhost_model_feature_importance": (I, [P, I, P, I, C.c_size_t, P, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),
     "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),

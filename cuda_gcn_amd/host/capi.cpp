@@ -271,6 +271,23 @@ int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, 
     if (!m) { g_err = "gcnhost_model_score_pairs: invalid argument"; return -1; }
     API_TRY({ m->gcn->queries().score_pairs(src, dst, n_pairs, metric, out); })
 }
+int gcnhost_model_explain(gcnhost_model *m, const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class, float *logit,
+                          float *hidden, float *feat, int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values, int64_t *nbr_total) {
+    if (!m) { g_err = "gcnhost_model_explain: invalid argument"; return -1; }
+    API_TRY({
+        if (!nbr_ids) {                                        // the first call: the length of the neighbour lists
+            if (!nbr_total) throw GcnHipFailure(-1, "explain: invalid argument");
+            *nbr_total = m->gcn->queries().explain_size(nodes, n);
+        } else {
+            m->gcn->queries().explain(nodes, classes, n, feat_scratch_bytes, out_class, logit, hidden, feat, nbr_ptr, nbr_ids, nbr_values);
+            if (nbr_total && nbr_ptr) *nbr_total = nbr_ptr[nodes ? n : m->gcn->params.num_nodes];
+        }
+    })
+}
+int gcnhost_model_feature_importance(gcnhost_model *m, int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs, int64_t *count) {
+    if (!m) { g_err = "gcnhost_model_feature_importance: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().feature_importance(split, nodes, n, feat_scratch_bytes, mean_abs, count); })
+}
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary) {
     CalibrationReport r;

@@ -62,6 +62,13 @@
 //                            H1 = ReLU(A^.X.W1) of an evaluation forward with the final (or loaded) weights, %.9g (exact f32).
 //   GCN_SIMILAR=<file>       one line per node: `node id:score ...`, its 10 nearest nodes by the cosine of those rows (best
 //                            first, equal scores by ascending id, the node itself left out), found on the GPU.
+// Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
+// and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
+//   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
+//                            class with the node's highest logit, that logit, and the five largest shares of it by neighbour (node
+//                            ids, the self loop among them) and by input feature column, largest first, ties by ascending id or
+//                            column (%.9g); then one line per class, `class c nodes=<n> | f:mean x10`: the ten columns with the
+//                            largest mean |share| over the test nodes explained for that class.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -73,6 +80,7 @@
 //                            from the training split (single-label n / (C n_c); with GCN_MULTILABEL the positive-term weight
 //                            (n - pos_c) / pos_c).  <file>: one float per line, one line per class.  The lines keep their
 //                            format; the loss columns are the weighted loss.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -203,6 +211,19 @@ int main(int argc, char **argv) {
                                                      : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_EMBED / GCN_SIMILAR " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *explain_path = getenv("GCN_EXPLAIN");
+    if (explain_path && !*explain_path) explain_path = nullptr;
+    if (explain_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1      ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256        ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0) ? "does not go with GCN_BF16_TABLES"
+                                                           : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_EXPLAIN " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -355,6 +376,50 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the neighbours to ") + similar_path);
                 fprintf(stderr, "gcn-hip: %d cosine neighbours of %d nodes written to %s\n", K, N, similar_path);
+            }
+            if (explain_path) {                                // one rank (checked above)
+                const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;
+                std::vector<int> nodes;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) nodes.push_back(i);
+                const int n = (int)nodes.size();
+                const size_t total = (size_t)gcn.queries().explain_size(nodes.data(), n);
+                std::vector<int32_t> cls(std::max(n, 1)), ids(std::max<size_t>(total, 1));
+                std::vector<float> logit(std::max(n, 1)), hid((size_t)std::max(n, 1) * h), feat((size_t)std::max(n, 1) * F), vals(std::max<size_t>(total, 1));
+                std::vector<int64_t> ptr((size_t)n + 1);
+                gcn.queries().explain(nodes.data(), nullptr, n, 0, cls.data(), logit.data(), hid.data(), feat.data(), ptr.data(), ids.data(), vals.data());
+                std::vector<double> mean((size_t)C * F);
+                std::vector<int64_t> cnt((size_t)C);
+                if (n) gcn.queries().feature_importance(3, nullptr, 0, 0, mean.data(), cnt.data());
+                FILE *f = fopen(explain_path, "w");
+                bool ok = f != nullptr;
+                // the `top` largest of key[0 .. m), largest first, ties by ascending label
+                auto top_of = [](int m, int top, auto value, auto label) {
+                    std::vector<int> order(m);
+                    for (int j = 0; j < m; j++) order[j] = j;
+                    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return value(a) > value(b) || (value(a) == value(b) && label(a) < label(b)); });
+                    order.resize(std::min(m, top));
+                    return order;
+                };
+                for (int i = 0; ok && i < n; i++) {
+                    ok = fprintf(f, "%d %d %.9g |", nodes[i], cls[i], logit[i]) > 0;
+                    const int64_t e0 = ptr[i];
+                    for (int j : top_of((int)(ptr[i + 1] - e0), 5, [&](int a) { return vals[e0 + a]; }, [&](int a) { return ids[e0 + a]; }))
+                        ok = ok && fprintf(f, " %d:%.9g", ids[e0 + j], vals[e0 + j]) > 0;
+                    ok = ok && fputs(" |", f) != EOF;
+                    for (int j : top_of(F, 5, [&](int a) { return feat[(size_t)i * F + a]; }, [](int a) { return a; }))
+                        ok = ok && fprintf(f, " %d:%.9g", j, feat[(size_t)i * F + j]) > 0;
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                for (int c = 0; ok && c < C; c++) {
+                    ok = fprintf(f, "class %d nodes=%lld |", c, (long long)cnt[c]) > 0;
+                    for (int j : top_of(F, 10, [&](int a) { return mean[(size_t)c * F + a]; }, [](int a) { return a; }))
+                        ok = ok && fprintf(f, " %d:%.9g", j, mean[(size_t)c * F + j]) > 0;
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the explanations to ") + explain_path);
+                fprintf(stderr, "gcn-hip: explanations of %d test nodes written to %s\n", n, explain_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

@@ -528,3 +528,190 @@ void ModelQueries::score_pairs(const int *src, const int *dst, int n_pairs, int 
     GCNHIP_CHECK(gcnhip_pair_scores(m.env.ctx, t.data, t.ld, t.rows, t.dim, t.inv_norm, d_rows, d_rows + n_pairs, n_pairs, d_out));
     GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, out, d_out, (size_t)n_pairs * sizeof(float)));
 }
+
+// ---- explaining a logit ---------------------------------------------------------------------------------------------------
+
+void ModelQueries::explain_check(const char *what, bool default_classes) const {
+    require(what, ONE_RANK);
+    const std::string w = std::string(what) + ": ";
+    if (m.params.hidden_dim < 1 || m.params.hidden_dim > 256)
+        throw GcnHipFailure(-1, w + "a hidden width of at most 256 (thread k of a workgroup owns hidden unit k)");
+    if (m.flags & HIPGCN_BF16_TABLES) throw GcnHipFailure(-1, w + "not with bf16 tables (the gates are read from the f32 hidden matrix a forward stores)");
+    // the logits of the default classes, and the hidden layer of a model without the aggregate-first form, come from a hooked forward
+    if (default_classes || m.eval_modules.empty()) require(what, CLASS_AGGREGATION);
+}
+
+const std::vector<int> &ModelQueries::explain_indptr() {
+    if (xp_indptr.empty()) {
+        const int *d_indptr = nullptr;
+        int n_rows = 0;
+        GCNHIP_CHECK(gcnhip_graph_arrays(m.graph, &d_indptr, nullptr, nullptr, &n_rows, nullptr));
+        xp_indptr.assign((size_t)n_rows + 1, 0);
+        GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, xp_indptr.data(), d_indptr, xp_indptr.size() * sizeof(int)));
+    }
+    return xp_indptr;
+}
+
+int64_t ModelQueries::explain_size(const int *nodes, int n) {
+    explain_check("explain", false);
+    if (n < 0) throw GcnHipFailure(-1, "explain: invalid argument");
+    const std::vector<int> rows = embed_query("explain", nodes, n);
+    m.sync();
+    const std::vector<int> &ip = explain_indptr();
+    int64_t total = 0;
+    for (int r : rows) total += ip[r + 1] - ip[r];
+    return total;
+}
+
+ModelQueries::EmbedTable ModelQueries::explain_forward(const char *what, const std::vector<int> &rows, const int32_t *d_rows, const int *classes,
+                                                       std::vector<int32_t> &cls) {
+    const int C = m.params.output_dim, n = (int)rows.size();
+    cls.resize(rows.size());
+    if (classes) {
+        for (int i = 0; i < n; i++) {
+            if (classes[i] < 0 || classes[i] >= C)
+                throw GcnHipFailure(-1, std::string(what) + ": class " + std::to_string(classes[i]) + " is not a class of the model (0.." + std::to_string(C - 1) + ")");
+            cls[i] = classes[i];
+        }
+        return embed_forward(false);
+    }
+    // one evaluation forward with its logits in scratch; where its fused launch kept the hidden layer in registers, the layer's
+    // own product stores it (same weights, same input: the forward's hidden layer)
+    forward_redirect(nullptr);
+    if (!m.eval_modules.empty() && static_cast<HipSparseMatmul *>(m.eval_modules[0])->hidden_not_stored) m.forward_hidden_only();
+    const HipVariable &h1 = *m.variables[3];
+    const EmbedTable t{h1.data, h1.ld, m.n_local, m.params.hidden_dim, nullptr};
+    if (n == 0) return t;
+    // the queried rows of the logits (d_rows: the caller's upload of `rows`), gathered on the device; the argmax (lowest class
+    // on a tie) on the host
+    const size_t batch = std::max<size_t>(1, ((size_t)16 << 20) / ((size_t)C * sizeof(float)));
+    std::vector<float> z;
+    for (size_t q0 = 0; q0 < (size_t)n; q0 += batch) {
+        const size_t nb = std::min(batch, (size_t)n - q0);
+        z.resize(nb * C);
+        float *d_z = d_xp_z.need(nb * C);
+        const int ld_z = m.variables[6]->ld;
+        for (int c0 = 0; c0 < C; c0 += 256) {                   // the row gather takes at most 256 columns at a time
+            const int cw = std::min(256, C - c0);
+            GCNHIP_CHECK(gcnhip_embed_rows(m.env.ctx, d_ml_logits.p + c0, ld_z, m.n_local, cw, nullptr, d_rows + q0, (int)nb, d_z + c0, C));
+        }
+        GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, z.data(), d_z, z.size() * sizeof(float)));
+        for (size_t i = 0; i < nb; i++) {
+            const float *row = z.data() + i * C;
+            cls[q0 + i] = (int32_t)(std::max_element(row, row + C) - row);
+        }
+    }
+    return t;
+}
+
+void ModelQueries::explain_features(const EmbedTable &t, const int32_t *d_rows, const int32_t *d_cls, int n, size_t cap_bytes, float *host_out, double *d_acc,
+                                    int32_t *d_count) {
+    const int F = m.params.input_dim, C = m.params.output_dim;
+    const HipVariable &w1 = *m.variables[2], &w2 = *m.variables[5];
+    const int scaling = m.factored_ ? 1 : 0;
+    if (!cap_bytes) cap_bytes = EMBED_SCRATCH_CAP;
+    const size_t batch = std::max<size_t>(1, std::min(cap_bytes, EMBED_SCRATCH_CAP) / ((size_t)F * sizeof(float)));
+    for (size_t q0 = 0; q0 < (size_t)n; q0 += batch) {
+        const int nb = (int)std::min(batch, (size_t)n - q0);
+        float *d_feat = d_xp_feat.need((size_t)nb * F);
+        if (m.feat_agg)
+            GCNHIP_CHECK(gcnhip_explain_features_agg(m.env.ctx, m.graph, d_rows + q0, d_cls + q0, nb, t.data, t.ld, t.dim, w2.data, w2.ld, C, w1.data, w1.ld, F,
+                                                     gcnhip_feat_values(m.feat_agg), F, scaling, d_feat, F));
+        else
+            GCNHIP_CHECK(gcnhip_explain_features_walk(m.env.ctx, m.graph, m.feat, d_rows + q0, d_cls + q0, nb, t.data, t.ld, t.dim, w2.data, w2.ld, C, w1.data,
+                                                      w1.ld, scaling, d_feat, F));
+        if (d_acc) GCNHIP_CHECK(gcnhip_explain_abs_colsum(m.env.ctx, d_feat, F, d_cls + q0, nb, F, C, d_acc, d_count));
+        if (host_out) GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, host_out + q0 * F, d_feat, (size_t)nb * F * sizeof(float)));
+    }
+}
+
+void ModelQueries::explain(const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class, float *logit, float *hidden, float *feat,
+                           int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values) {
+    explain_check("explain", classes == nullptr);
+    if (n < 0 || ((n > 0 || !nodes) && (!out_class || !logit || !hidden || !nbr_ptr || !nbr_ids || !nbr_values))) throw GcnHipFailure(-1, "explain: invalid argument");
+    const std::vector<int> rows = embed_query("explain", nodes, n);
+    const int h = m.params.hidden_dim, C = m.params.output_dim;
+    if (classes)                                               // before any launch
+        for (int i = 0; i < n; i++)
+            if (classes[i] < 0 || classes[i] >= C)
+                throw GcnHipFailure(-1, "explain: class " + std::to_string(classes[i]) + " is not a class of the model (0.." + std::to_string(C - 1) + ")");
+    m.sync();                                                  // run()'s epochs in flight, the validation lane's pass
+    const std::vector<int> &ip = explain_indptr();
+    std::vector<int32_t> ptr((size_t)n + 1, 0), cls;
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (nbr_ptr) nbr_ptr[i] = total;
+        ptr[i] = (int32_t)total;
+        total += ip[rows[i] + 1] - ip[rows[i]];
+        if (total > INT32_MAX) throw GcnHipFailure(-1, "explain: more than 2^31 - 1 neighbour entries in one query: ask for fewer nodes at a time");
+    }
+    if (nbr_ptr) nbr_ptr[n] = total;
+    int32_t *d_rows = d_xp_rows.need((size_t)n), *d_cls = d_xp_cls.need((size_t)n), *d_ptr = d_xp_ptr.need((size_t)n);
+    if (n) GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    const EmbedTable t = explain_forward("explain", rows, d_rows, classes, cls);
+    if (n == 0) { m.sync(); return; }
+    const HipVariable &w2 = *m.variables[5];
+    int32_t *d_nrow = d_xp_nbr_row.need((size_t)total);
+    float *d_nval = d_xp_nbr_val.need((size_t)total), *d_logit = d_xp_logit.need((size_t)n), *d_hidden = d_xp_hidden.need((size_t)n * h);
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_cls, cls.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_ptr, ptr.data(), (size_t)n * sizeof(int32_t)));
+    GCNHIP_CHECK(gcnhip_explain_hops(m.env.ctx, m.graph, d_rows, d_cls, n, t.data, t.ld, t.dim, w2.data, w2.ld, C, m.factored_ ? 1 : 0, d_logit, d_hidden, h, d_ptr,
+                                     d_nrow, d_nval, total));
+    std::copy(cls.begin(), cls.end(), out_class);
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, logit, d_logit, (size_t)n * sizeof(float)));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, hidden, d_hidden, (size_t)n * h * sizeof(float)));
+    if (total) {
+        GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, nbr_ids, d_nrow, (size_t)total * sizeof(int32_t)));
+        GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, nbr_values, d_nval, (size_t)total * sizeof(float)));
+        for (int64_t e = 0; e < total; e++) nbr_ids[e] = m.node_id(nbr_ids[e]);
+    }
+    if (feat) explain_features(t, d_rows, d_cls, n, feat_scratch_bytes, feat, nullptr, nullptr);
+    m.sync();
+}
+
+void ModelQueries::feature_importance(int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs, int64_t *count) {
+    explain_check("feature_importance", true);
+    if (m.params.output_dim > 256)
+        throw GcnHipFailure(-1, "feature_importance: at most 256 classes (a thread keeps its column's sum of every class in LDS), this model has " +
+                                    std::to_string(m.params.output_dim));
+    if (split < 0 || split > 3 || n < 0 || !mean_abs || !count)
+        throw GcnHipFailure(-1, "feature_importance: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
+    const int F = m.params.input_dim, C = m.params.output_dim;
+    std::vector<int> rows;
+    if (split) {                                               // the split's nodes in id order
+        std::vector<int> ids;
+        for (int id = 0; id < m.params.num_nodes; id++) ids.push_back(id);
+        std::vector<int> all;
+        query_rows("feature_importance", ids.data(), (int)ids.size(), all);
+        const int r0 = m.row_start();
+        for (int r : all)
+            if (m.data->split[r0 + r] == split) rows.push_back(r);
+        if (rows.empty()) throw GcnHipFailure(-1, "feature_importance: split " + std::to_string(split) + " has no rows");
+    } else {
+        rows = embed_query("feature_importance", nodes, n);
+    }
+    n = (int)rows.size();
+    m.sync();
+    std::vector<int32_t> cls;
+    int32_t *d_rows = d_xp_rows.need((size_t)n);
+    if (n) GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_rows, rows.data(), (size_t)n * sizeof(int32_t)));
+    const EmbedTable t = explain_forward("feature_importance", rows, d_rows, nullptr, cls);
+    double *d_acc = d_xp_acc.need((size_t)C * F);
+    int32_t *d_cnt = d_xp_count.need((size_t)C);
+    GCNHIP_CHECK(gcnhip_memset_async(m.env.ctx, d_acc, 0, (size_t)C * F * sizeof(double)));
+    GCNHIP_CHECK(gcnhip_memset_async(m.env.ctx, d_cnt, 0, (size_t)C * sizeof(int32_t)));
+    if (n) {
+        int32_t *d_cls = d_xp_cls.need((size_t)n);
+        GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_cls, cls.data(), (size_t)n * sizeof(int32_t)));
+        explain_features(t, d_rows, d_cls, n, feat_scratch_bytes, nullptr, d_acc, d_cnt);
+    }
+    std::vector<int32_t> hc((size_t)C);
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, mean_abs, d_acc, (size_t)C * F * sizeof(double)));
+    GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, hc.data(), d_cnt, (size_t)C * sizeof(int32_t)));
+    for (int c = 0; c < C; c++) {
+        count[c] = hc[c];
+        if (hc[c])
+            for (int f = 0; f < F; f++) mean_abs[(size_t)c * F + f] /= (double)hc[c];
+    }
+    m.sync();
+}

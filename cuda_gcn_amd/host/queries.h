@@ -1,12 +1,13 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
-// evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings.  ModelQueries owns every device buffer and every
+// evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations.  ModelQueries owns every device buffer and every
 // piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
 //   reads   params, opt_.multilabel, env (context, comm), n_local, row_start(), node_order_ (query_rows' inverse map; node_id()
 //           elsewhere), data->split, data->label, graph, logits_gs (null test only), variables[6]->ld, d_truth[], split_rows[],
-//           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr, variables[3] (data, ld), node_id()
+//           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr, variables[3] (data, ld), node_id(), and for
+//           explanations variables[2] / [5] (data, ld), factored_, flags, feat, feat_agg, eval_modules[0]->hidden_not_stored
 //   calls   sync(), forward_hooked(), forward_hidden_only()
 // It writes no member of HipGCN.
 #pragma once
@@ -120,6 +121,31 @@ public:
     void embed(const int *nodes, int n, float *out, bool normalize);
     void similar(const int *nodes, int n, int k, int metric, bool exclude_self, int32_t *out_id, float *out_score);
     void score_pairs(const int *src, const int *dst, int n_pairs, int metric, float *out);
+    // Explaining a logit: the network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed
+    // the logit of (node v, class c) is a plain sum, split here without approximation by the neighbour a term came through, by
+    // hidden unit and by input feature column (csrc/explain.hip; include/gcnhip_driver.h has the formulas).  embed()'s contract:
+    // the call starts with sync(); the hidden layer is recomputed through embed_forward with nothing cached; the metrics ring, the
+    // current split, variable 6 and the captured epoch graph are untouched; variable 3 is rewritten, as by every forward.  The
+    // gates are variable 3's own (H1 > 0), the results the reference's quantities on factored and HIPGCN_EDGE_COEF models alike.
+    // Ids are DATASET node ids, also those of the neighbours.  classes == NULL: the explained class of a node is its highest
+    // logit, lowest class on a tie (single- and multi-label), taken from the logits of the query's own forward (the evaluation
+    // forward with its logits redirected to scratch; an aggregate-first model whose fused launch keeps the hidden layer in
+    // registers then stores it by its one product).  The features path is gcnhip_explain_features_agg when the model has A^.X
+    // (feat_agg), else gcnhip_explain_features_walk on its feature object; its scratch is feat_scratch_bytes (0: 64 MiB) at most,
+    // larger queries run in batches and give the same bits.  Refused with a message before any launch: more than one rank, a
+    // hidden width above 256, bf16 tables, a node id or class out of range; for feature_importance more than 256 classes or a
+    // split without rows.
+    //   explain: n queries (nodes NULL: every node in id order).  explain_size tells the length of the neighbour lists (the sum
+    //   of the queried rows' stored lengths, self loops and repeated edges included) without touching the device beyond one
+    //   copy of the row pointers.  out_class [n], logit [n], hidden [n x h], feat [n x F] (NULL: not computed), nbr_ptr [n + 1],
+    //   nbr_ids / nbr_values [nbr_ptr[n]]: the stored edges of the node's row in stored order.
+    //   feature_importance: over the nodes of `split` (1..3), or with split == 0 the `nodes` query, each explained for its
+    //   default class: mean_abs [C x F] = the mean of |feat| per explained class (float64, accumulated on the device in query
+    //   order; a class without nodes: zeros), count [C].
+    int64_t explain_size(const int *nodes, int n);
+    void explain(const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class, float *logit, float *hidden, float *feat,
+                 int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values);
+    void feature_importance(int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs, int64_t *count);
 
 private:
     HipGCN &m;
@@ -178,6 +204,12 @@ private:
     Scratch<unsigned char> d_emb_scratch{&arena};
     int32_t *d_node_ids = nullptr;
     static constexpr size_t EMBED_SCRATCH_CAP = (size_t)64 << 20;
+    // explain / feature_importance: the row pointers of the adjacency (host, downloaded once: the graph never changes); the
+    // query's rows, classes and scan; its outputs; the features batch; the importance sums
+    std::vector<int> xp_indptr;
+    Scratch<int32_t> d_xp_rows{&arena}, d_xp_cls{&arena}, d_xp_ptr{&arena}, d_xp_nbr_row{&arena}, d_xp_count{&arena};
+    Scratch<float> d_xp_logit{&arena}, d_xp_hidden{&arena}, d_xp_nbr_val{&arena}, d_xp_feat{&arena}, d_xp_z{&arena};
+    Scratch<double> d_xp_acc{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
@@ -199,5 +231,14 @@ private:
     std::vector<int> embed_query(const char *what, const int *nodes, int &n);            // dataset ids (NULL: all) -> local rows
     struct EmbedTable { const float *data; int ld, rows, dim; const float *inv_norm; };
     EmbedTable embed_forward(bool norms);                      // the hidden matrix where variable 3 keeps it (and its inverse norms)
+    void explain_check(const char *what, bool default_classes) const;
+    const std::vector<int> &explain_indptr();
+    // the forward of an explanation: variable 3 rewritten; cls = the given classes (checked) or each row's highest logit
+    // (d_rows: `rows` on the device)
+    EmbedTable explain_forward(const char *what, const std::vector<int> &rows, const int32_t *d_rows, const int *classes, std::vector<int32_t> &cls);
+    // the feature shares of n uploaded queries in batches of at most cap_bytes: copied to host_out [n x F] and / or added to the
+    // importance sums
+    void explain_features(const EmbedTable &t, const int32_t *d_rows, const int32_t *d_cls, int n, size_t cap_bytes, float *host_out, double *d_acc,
+                          int32_t *d_count);
     void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
 };

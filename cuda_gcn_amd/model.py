@@ -467,6 +467,73 @@ class HipGCNModel:
                                                          out.ctypes.data), "score_edges")
         return out[:s.size]
 
+    # ---- explaining a logit: neighbour, hidden-unit and feature shares, on the GPU
+    def _explain_args(self, what, nodes, classes=None):
+        """argument checks that need no GPU; returns (node ids int32 or None, classes int32 or None)"""
+        if self.params.hidden_dim > 256:
+            raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+        q = None
+        if nodes is not None:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            if q.size and (q.min() < 0 or q.max() >= self.params.num_nodes):
+                raise GcnHostError(f"{what}: nodes holds an id that is not a node of the dataset (0..{self.params.num_nodes - 1})")
+        c = None
+        if classes is not None:
+            c = np.ascontiguousarray(classes, np.int32).ravel()
+            n = self.params.num_nodes if q is None else q.size
+            if c.size != n:
+                raise GcnHostError(f"{what}: {c.size} classes for {n} nodes")
+            if c.size and (c.min() < 0 or c.max() >= self.params.output_dim):
+                raise GcnHostError(f"{what}: classes holds a class the model does not have (0..{self.params.output_dim - 1})")
+        return q, c
+
+    def explain(self, nodes, classes=None, features=True, scratch_bytes=0):
+        """Why the model gives a node its logit.  The network is Z = A^.(ReLU(A^.X.W1).W2) without bias, so with the ReLU gates
+        of an evaluation forward fixed the logit of (node, class) is a plain sum, split here exactly three ways; every split adds
+        up to the logit (the feature shares up to the first layer's own rounding).  nodes: dataset ids (repeats allowed; None:
+        every node); classes: one per node, or None for each node's highest logit (lowest class on a tie; predict()'s class on a
+        single-label model).  Returns a dict: logit f32 [n]; classes int32 [n]; hidden f32 [n, hidden_dim], the share of every
+        hidden unit; features f32 [n, input_dim], the share of every input column (None when features=False); nbr_ptr int64
+        [n + 1], nbr_ids int32, nbr_values f32: entries nbr_ptr[i] .. nbr_ptr[i + 1] - 1 are the shares of the stored edges of
+        node i's row (dataset ids; the self loop included, a repeated edge twice).  scratch_bytes: device scratch of the feature
+        shares (0: 64 MiB, the most); larger queries run in batches, same bits.  One rank, hidden width at most 256, f32 tables.
+        Training state is not touched."""
+        q, c = self._explain_args("explain", nodes, classes)
+        n = self.params.num_nodes if q is None else int(q.size)
+        z = np.zeros(1, np.int32)
+        qp = None if q is None else (q if n else z).ctypes.data
+        cp = None if c is None else (c if n else z).ctypes.data
+        total = C.c_int64(0)
+        _ck(self.lib, self.lib.gcnhost_model_explain(self.h, qp, cp, n, 0, None, None, None, None, None, None, None, C.byref(total)), "explain")
+        h, nf = self.params.hidden_dim, self.params.input_dim
+        out_c, logit = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        hidden = np.zeros((max(n, 1), h), np.float32)
+        feat = np.zeros((max(n, 1), nf), np.float32) if features else None
+        ptr = np.zeros(n + 1, np.int64)
+        ids, vals = np.zeros(max(total.value, 1), np.int32), np.zeros(max(total.value, 1), np.float32)
+        _ck(self.lib, self.lib.gcnhost_model_explain(self.h, qp, cp, n, int(scratch_bytes), out_c.ctypes.data, logit.ctypes.data, hidden.ctypes.data,
+                                                     feat.ctypes.data if features else None, ptr.ctypes.data, ids.ctypes.data, vals.ctypes.data,
+                                                     C.byref(total)), "explain")
+        return dict(logit=logit[:n], classes=out_c[:n], hidden=hidden[:n], features=feat[:n] if features else None, nbr_ptr=ptr,
+                    nbr_ids=ids[:total.value], nbr_values=vals[:total.value])
+
+    def feature_importance(self, split=3, nodes=None, scratch_bytes=0):
+        """(mean_abs float64 [C, input_dim], count int64 [C]) — the mean of |explain().features| over the nodes of `split` (1 train,
+        2 validation, 3 test), or over `nodes` when given, each explained for its default class, grouped by that class: which
+        input columns the model leans on for each class.  Formed on the GPU; only C x F numbers cross.  At most 256 classes."""
+        q, _ = self._explain_args("feature_importance", nodes)
+        if self.params.output_dim > 256:
+            raise GcnHostError(f"feature_importance: at most 256 classes, this model has {self.params.output_dim}")
+        if q is None and split not in (1, 2, 3):
+            raise GcnHostError(f"feature_importance: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        n = 0 if q is None else int(q.size)
+        qp = None if q is None else (q if n else np.zeros(1, np.int32)).ctypes.data
+        nc, nf = self.params.output_dim, self.params.input_dim
+        mean_abs, count = np.zeros((nc, nf), np.float64), np.zeros(nc, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_feature_importance(self.h, 0 if q is not None else int(split), qp, n, int(scratch_bytes), mean_abs.ctypes.data,
+                                                                count.ctypes.data), "feature_importance")
+        return mean_abs, count
+
     def save_weights(self, path):
         """W1, W2 to a weights file (read_weights; Adam's state is not saved)"""
         _ck(self.lib, self.lib.gcnhost_model_save_weights(self.h, os.fsencode(path)), "save_weights")

@@ -418,6 +418,88 @@ class Device:
             self._embed_fail("gcnhip_embed_rows", rc)
         return ob.download()[:n, :dim]
 
+    # ---- explaining a logit (csrc/explain.hip): tables are uploaded with their row stride and NaN padding
+    def _explain_inputs(self, q_row, q_class, h1, w2, ld_h1, ld_w2):
+        qr, qc = np.ascontiguousarray(q_row, np.int32).ravel(), np.ascontiguousarray(q_class, np.int32).ravel()
+        assert qr.size == qc.size
+        nq = int(qr.size)
+        h1, w2 = np.ascontiguousarray(h1, np.float32), np.ascontiguousarray(w2, np.float32)
+        h, c = w2.shape
+        assert h1.shape[1] == h
+        ld_h1, ld_w2 = int(ld_h1 or h), int(ld_w2 or c)
+        z = np.zeros(1, np.int32)
+        return (self.buf(qr if nq else z), self.buf(qc if nq else z), nq, self.padded(h1, ld_h1), ld_h1, h, self.padded(w2, ld_w2), ld_w2, c)
+
+    def explain_hops(self, g: "Graph", q_row, q_class, h1, w2, scaling=0, ld_h1=None, ld_w2=None, ld_out=None, nbr_ptr=None):
+        """gcnhip_explain_hops: dict(logit f32 [nq], hidden f32 [nq, h], nbr_ptr int64 [nq + 1], nbr_row int32, nbr_val f32) of the
+        listed (row, class) queries.  nbr_ptr: the exclusive scan handed to the library (None: made from the object's rows)."""
+        qr, qc, nq, hb, ld_h1, h, wb, ld_w2, c = self._explain_inputs(q_row, q_class, h1, w2, ld_h1, ld_w2)
+        indptr = g.csr()[0].astype(np.int64)
+        rows = np.ascontiguousarray(q_row, np.int64).ravel()
+        ok = (rows >= 0) & (rows < g.n_rows)
+        length = np.where(ok, indptr[np.clip(rows, 0, g.n_rows - 1) + 1] - indptr[np.clip(rows, 0, g.n_rows - 1)], 0)
+        ptr = np.concatenate([[0], np.cumsum(length)]) if nbr_ptr is None else np.asarray(nbr_ptr, np.int64)
+        total = int(ptr[-1])
+        ld_out = int(ld_out or h)
+        pb = self.buf(ptr[:max(nq, 1)].astype(np.int32))
+        lb = self.buf(np.full(max(nq, 1), np.nan, np.float32))
+        ob = self.buf(np.full((max(nq, 1), ld_out), np.nan, np.float32))
+        rb = self.buf(np.full(max(total, 1), -12345, np.int32))
+        vb = self.buf(np.full(max(total, 1), np.nan, np.float32))
+        rc = self.lib.gcnhip_explain_hops(self.ctx, g.h, qr.ptr, qc.ptr, nq, hb.ptr, ld_h1, h, wb.ptr, ld_w2, c, int(scaling), lb.ptr, ob.ptr, ld_out,
+                                          pb.ptr, rb.ptr, vb.ptr, total)
+        if rc != 0:
+            self._embed_fail("gcnhip_explain_hops", rc)
+        return dict(logit=lb.download()[:nq], hidden=ob.download()[:nq, :h], nbr_ptr=ptr, nbr_row=rb.download()[:total], nbr_val=vb.download()[:total])
+
+    def explain_features_agg(self, g: "Graph", q_row, q_class, h1, w2, w1, s, scaling=0, ld_h1=None, ld_w2=None, ld_w1=None, ld_s=None, ld_f=None):
+        """gcnhip_explain_features_agg: f32 [nq, F], the feature shares from dense rows of S = A^.X"""
+        qr, qc, nq, hb, ld_h1, h, wb, ld_w2, c = self._explain_inputs(q_row, q_class, h1, w2, ld_h1, ld_w2)
+        w1, s = np.ascontiguousarray(w1, np.float32), np.ascontiguousarray(s, np.float32)
+        nf = w1.shape[0]
+        assert w1.shape[1] == h and s.shape[1] == nf
+        ld_w1, ld_s, ld_f = int(ld_w1 or h), int(ld_s or nf), int(ld_f or nf)
+        w1b, sb = self.padded(w1, ld_w1), self.padded(s, ld_s)
+        fb = self.buf(np.full((max(nq, 1), ld_f), np.nan, np.float32))
+        rc = self.lib.gcnhip_explain_features_agg(self.ctx, g.h, qr.ptr, qc.ptr, nq, hb.ptr, ld_h1, h, wb.ptr, ld_w2, c, w1b.ptr, ld_w1, nf, sb.ptr, ld_s,
+                                                  int(scaling), fb.ptr, ld_f)
+        if rc != 0:
+            self._embed_fail("gcnhip_explain_features_agg", rc)
+        return fb.download()[:nq, :nf]
+
+    def explain_features_walk(self, g: "Graph", x: "Feat", q_row, q_class, h1, w2, w1, scaling=0, ld_h1=None, ld_w2=None, ld_w1=None, ld_f=None):
+        """gcnhip_explain_features_walk: f32 [nq, F], the feature shares by the two-hop walk over a feature object"""
+        qr, qc, nq, hb, ld_h1, h, wb, ld_w2, c = self._explain_inputs(q_row, q_class, h1, w2, ld_h1, ld_w2)
+        w1 = np.ascontiguousarray(w1, np.float32)
+        nf = x.n_cols
+        assert w1.shape == (nf, h)
+        ld_w1, ld_f = int(ld_w1 or h), int(ld_f or nf)
+        w1b = self.padded(w1, ld_w1)
+        fb = self.buf(np.full((max(nq, 1), ld_f), np.nan, np.float32))
+        rc = self.lib.gcnhip_explain_features_walk(self.ctx, g.h, x.h, qr.ptr, qc.ptr, nq, hb.ptr, ld_h1, h, wb.ptr, ld_w2, c, w1b.ptr, ld_w1, int(scaling),
+                                                   fb.ptr, ld_f)
+        if rc != 0:
+            self._embed_fail("gcnhip_explain_features_walk", rc)
+        return fb.download()[:nq, :nf]
+
+    def explain_abs_colsum(self, batches, num_classes, ld_f=None):
+        """gcnhip_explain_abs_colsum over `batches` = [(feat f32 [nq, F], q_class [nq]), ...] accumulated in order into zeroed sums:
+        (acc float64 [C, F], count int32 [C])"""
+        nf = int(np.asarray(batches[0][0]).shape[1])
+        ld_f = int(ld_f or nf)
+        ab = self.buf(np.zeros((num_classes, nf), np.float64))
+        cb = self.buf(np.zeros(max(num_classes, 1), np.int32))
+        for feat, cls in batches:
+            feat = np.ascontiguousarray(feat, np.float32)
+            cls = np.ascontiguousarray(cls, np.int32).ravel()
+            nq = int(cls.size)
+            fb = self.padded(feat, ld_f) if nq else self.buf(np.zeros((1, ld_f), np.float32))
+            qb = self.buf(cls if nq else np.zeros(1, np.int32))
+            rc = self.lib.gcnhip_explain_abs_colsum(self.ctx, fb.ptr, ld_f, qb.ptr, nq, nf, int(num_classes), ab.ptr, cb.ptr)
+            if rc != 0:
+                self._embed_fail("gcnhip_explain_abs_colsum", rc)
+        return ab.download(), cb.download()[:num_classes]
+
     def graphsum(self, g: "Graph", x, ld_in=None, ld_out=None, row_nonzero=None):
         x = np.asarray(x, np.float32)
         dim = x.shape[1]

@@ -264,6 +264,44 @@ int gcnhip_pair_scores(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        const int32_t *dst, int n_pairs, float *out);
 int gcnhip_embed_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
                       int n, float *out, int ld_out);
+/* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
+ * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
+ * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and
+ * a class c; e_1 .. e_d are the stored edges of row v in stored order (gcnhip_graph_arrays), u_i = col(e_i), a_i = A^[v, u_i],
+ * g_i[k] = (H1[u_i, k] > 0) read from the table passed in, S = A^ . X:
+ *   logit   z      = sum_i a_i sum_k H1[u_i, k] W2[k, c]
+ *   nbr_i          = a_i sum_k H1[u_i, k] W2[k, c]                      one per stored edge (a repeated edge: two entries)
+ *   hid_k          = W2[k, c] sum_i a_i H1[u_i, k]                      [h]
+ *   feat_f         = sum_i a_i sum_k g_i[k] W2[k, c] W1[f, k] S[u_i, f] [F]
+ * All take device lists q_row / q_class [nq] (repeats allowed), an f32 H1 table [g->n_cols x ld_h1] with 1 <= h <= 256 (any stride
+ * and alignment; columns [h, ld) are never read as values), W2 [h x C] with its own stride, W1 [F x h], and `scaling` with
+ * gcnhip_graphsum_ex's meaning: 0 = plain tables, a_i = coef[e_i]; 1 = the factored form, where row r of H1 / S / the feature
+ * object carries dinv[r] and a_i . H1[u_i] = dinv_row[v] . H1'[u_i], a_i . S[u_i] = dinv_row[v] . S'[u_i], a_i . A^[u_i, w] . x(w) =
+ * dinv_row[v] . dinv2_row[u_i] . X'[w].  The query lists are copied to the host and checked first (this synchronises the stream):
+ * a row outside the object or a class outside [0, C) is an argument error (-1, gcnhip_last_error) before any launch.  No float
+ * atomics, no allocation inside a launch; two launches give the same bits, and the result of a query does not depend on which
+ * other queries are in the launch.
+ * gcnhip_explain_hops: one launch writes logit [nq], hidden [nq x ld_out] (columns < h) and the neighbour shares: nbr_val[nbr_ptr[q]
+ *   + i] = nbr_i, nbr_row[nbr_ptr[q] + i] = u_i.  nbr_ptr [nq] is the exclusive scan of the queried rows' lengths, made by the caller
+ *   and checked against the object (nbr_capacity = entries of nbr_row / nbr_val).  Any degree.
+ * gcnhip_explain_features_agg: feat [nq x ld_f] from dense rows of S [g->n_cols x ld_s]: per query the product [F x d] . [d x h] of
+ *   gathered S rows with the gated rows r_i[k] = a_i g_i[k] W2[k, c], folded row-wise with W1 — 2 d F h flops, d F 4 gathered bytes.
+ * gcnhip_explain_features_walk: the same numbers from a feature object in CSR (sparse, or dense) by the two-hop walk i -> w in
+ *   row(u_i) -> non-zeros (f, x), adding a_i A^[u_i, w] x . (W1[f, :] . r_i) in that order, one lane adding; needs a square adjacency
+ *   object and at most 40 896 feature columns (a neighbour's inner sum sits in LDS: the sum is d + D additions deep, as _agg's).
+ * gcnhip_explain_abs_colsum: acc[q_class[q] * F + f] += |feat[q, f]| in float64 with the rows taken in order, count[class] += 1
+ *   (int32); batches accumulate in call order; the caller zeroes acc and count.  1 <= C <= 256. */
+int gcnhip_explain_hops(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *q_row, const int32_t *q_class, int nq, const float *h1,
+                        int ld_h1, int h, const float *w2, int ld_w2, int num_classes, int scaling, float *logit, float *hidden,
+                        int ld_out, const int32_t *nbr_ptr, int32_t *nbr_row, float *nbr_val, int64_t nbr_capacity);
+int gcnhip_explain_features_agg(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *q_row, const int32_t *q_class, int nq,
+                                const float *h1, int ld_h1, int h, const float *w2, int ld_w2, int num_classes, const float *w1,
+                                int ld_w1, int n_features, const float *s, int ld_s, int scaling, float *feat, int ld_f);
+int gcnhip_explain_features_walk(gcnhip_ctx *ctx, const gcnhip_graph *g, const gcnhip_feat *x, const int32_t *q_row,
+                                 const int32_t *q_class, int nq, const float *h1, int ld_h1, int h, const float *w2, int ld_w2,
+                                 int num_classes, const float *w1, int ld_w1, int scaling, float *feat, int ld_f);
+int gcnhip_explain_abs_colsum(gcnhip_ctx *ctx, const float *feat, int ld_f, const int32_t *q_class, int nq, int n_features,
+                              int num_classes, double *acc, int32_t *count);
 /* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
  * subsets made at call time, such as the node queries of a prediction. */
 int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);

@@ -237,6 +237,25 @@ int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *co
 int gcnhost_model_embed(gcnhost_model *m, const int *nodes, int n, float *out, int normalize);
 int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int metric, int exclude_self, int32_t *out_id, float *out_score);
 int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out);
+/* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
+ * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
+ * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
+ * repeated edge twice), by hidden unit [hidden] and by input feature column [F]; each split adds up to the logit (the feature
+ * shares up to the first layer's own rounding).  Ids are DATASET node ids.  embed's contract: training state is not touched.
+ * classes == NULL: each node's highest logit, lowest class on a tie.  feat_scratch_bytes: device scratch of the feature shares
+ * (0: 64 MiB, the most it may be); larger queries run in batches with the same bits.  Refused with a message before any launch:
+ * several ranks, a hidden width above 256, bf16 tables, a node id or class out of range; for the importance more than 256 classes
+ * or a split without rows.
+ * gcnhost_model_explain: a first call with nbr_ids == NULL writes only *nbr_total, the length of the neighbour lists of the query
+ *   (as gcnhost_local_graph reports its sizes).  The second call fills out_class [n], logit [n], hidden [n x hidden], feat [n x F]
+ *   (NULL: not computed), nbr_ptr [n + 1], nbr_ids / nbr_values [nbr_total]: the shares of query i are entries nbr_ptr[i] ..
+ *   nbr_ptr[i + 1] - 1, in the stored order of the row.  nodes == NULL: every node in id order (n = num_nodes).
+ * gcnhost_model_feature_importance: mean_abs [C x F] float64 = the mean of |feature share| over the nodes of `split` (1 train,
+ *   2 validation, 3 test; 0: the `nodes` query) explained for their default class, per explained class; count [C] the nodes. */
+int gcnhost_model_explain(gcnhost_model *m, const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class,
+                          float *logit, float *hidden, float *feat, int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values, int64_t *nbr_total);
+int gcnhost_model_feature_importance(gcnhost_model *m, int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs,
+                                     int64_t *count);
 /* Per-class metrics from integer counts, host only (host/report.h): either confusion [C x C] (row = truth, column =
  * prediction) or tp / fp / fn [C] (the other form NULL).  Every output may be NULL: tp_fp_fn [3 x C] the counts used; support
  * (TP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), f1 = 2 TP / (2 TP + FP + FN) [C], float64, each 0 when
