@@ -242,33 +242,107 @@ __device__ __forceinline__ float4 gather_chunk(const GsArgs &a, const float *in,
     return acc;
 }
 
+// ---- the pieces every gather kernel is made of -----------------------------------------------------------------------
+// Each kernel below stays a kernel of its own: it calls these and then runs its own epilogue.
+
+// A row task: the edges [e0, e1) of `row`.  slot >= 0: a segment of a split row, whose sum goes to partials[slot].
+struct GsTask { int row, e0, e1, slot; };
+__device__ __forceinline__ GsTask gs_task(const GsArgs &a, int t) {
+    if (a.n_tasks) {
+        const int4 tk = a.tasks[t];
+        return {tk.x, tk.y, tk.z, tk.w};
+    }
+    return {t, a.indptr[t], a.indptr[t + 1], -1};
+}
+
+// XCD-aware mapping of a block's waves to (task t, column slice) — speed only, never correctness: workgroups are dealt
+// round-robin over the 8 XCDs, so blockIdx % 8 names the group of blocks that share an L2.  Each group gets
+//  (a) one column slice (wide rows, SLICED): its 4 MiB L2 then sees 1/n_slices of the gathered table;
+//  (b) a CONTIGUOUS range of the task list, so rows that are neighbours in the node order —
+//      the same community after reordering — are gathered through the same L2.
+// false: the group has no task left for this wave (wave-uniform).
+template <bool SLICED>
+__device__ __forceinline__ bool gs_block_task(const GsArgs &a, int &t, int &cslice) {
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    cslice = SLICED ? xcd % a.n_slices : blockIdx.y;
+    const int g_id = SLICED ? xcd / a.n_slices : xcd;      // which share of the tasks
+    t = a.bounds[g_id] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    return t < a.bounds[g_id + 1];
+}
+
+// One chunk of cnt <= 64 (index, coef) pairs, one pair per lane with one coalesced load each; lanes past cnt hold (0, 0).
+__device__ __forceinline__ void gs_load_edges(const GsArgs &a, int base, int cnt, int lane, int &my_idx, float &my_c) {
+    my_idx = 0;
+    my_c = 0.f;
+    if (lane < cnt) {
+        my_idx = a.indices[base + lane];
+        // > 0 for every real edge.  Factored operator (a.coef == NULL, wave-uniform): every edge counts 1 and no coefficient
+        // stream is read — the saving is the stream (measured 0.756 -> 0.720 ms at Reddit scale); instantiations that also
+        // drop the hand-out shuffle and the multiply measured the same 0.720 ms and were not kept
+        my_c = a.coef ? a.coef[base + lane] : 1.f;
+        if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;   // wave-uniform test
+    }
+}
+
+// The lane groups' partial sums combined by wave shuffles: every lane ends with the sum over all groups.
+template <int L>
+__device__ __forceinline__ float4 gs_group_sum(float4 acc) {
+#pragma unroll
+    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
+    return acc;
+}
+
+// A segment's sum to its slot of the split-row scratch: a finalize launch adds the segments.
+__device__ __forceinline__ void gs_store_partial(const GsArgs &a, int slot, int col0, float4 acc) {
+    *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+}
+__device__ __forceinline__ void gs_store_partial(const GsArgs &a, int slot, int col0, float4 lo, float4 hi) {
+    gs_store_partial(a, slot, col0, lo);
+    gs_store_partial(a, slot, col0 + 4, hi);
+}
+
+// v + the segments [first, first + ns) of a split row at column col, left to right (ns >= 1).  Four partials in flight per
+// batch, the tail by unconditional loads from clamped slots.
+__device__ __forceinline__ float gs_segment_sum(const GsArgs &a, int first, int ns, int col, float v) {
+    const float *pp = a.partials + (size_t)first * a.part_ld + col;
+    int k = 0;
+    for (; k + 4 <= ns; k += 4) {
+        const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
+        const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
+        v += p0; v += p1; v += p2; v += p3;
+    }
+    const float p0 = pp[(size_t)min(k, ns - 1) * a.part_ld], p1 = pp[(size_t)min(k + 1, ns - 1) * a.part_ld];
+    const float p2 = pp[(size_t)min(k + 2, ns - 1) * a.part_ld];
+    if (k < ns) v += p0;
+    if (k + 1 < ns) v += p1;
+    if (k + 2 < ns) v += p2;
+    return v;
+}
+
+// The factored operator's row factor (a.post == NULL: none), and the store of a lane's quad at o = &out[row, col0]: whole,
+// or the ragged tail of a row with dim % 4 != 0.
+__device__ __forceinline__ float4 gs_post4(const GsArgs &a, int row, float4 acc) {
+    if (a.post) { const float ps = a.post[row]; acc.x *= ps; acc.y *= ps; acc.z *= ps; acc.w *= ps; }
+    return acc;
+}
+__device__ __forceinline__ void gs_store_row4(const GsArgs &a, float *o, int col0, float4 acc) {
+    if (col0 + 4 <= a.dim) {
+        *reinterpret_cast<float4 *>(o) = acc;
+    } else {
+        const float x[4] = {acc.x, acc.y, acc.z, acc.w};
+        for (int i = 0; col0 + i < a.dim; i++) o[i] = x[i];
+    }
+}
+
 // L lanes per feature row (float4 each), G = 64/L rows per wave instruction.
 // SLICED: the launch binds one column slice to each XCD group (it only changes the block -> (tasks, columns) mapping; the
 // flag is a template argument so that profiles name the hidden-width launches apart from the class-width ones).
 template <int L, int U = GS_U, bool SLICED = false>
 __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
-    constexpr int G = WAVE / L;
     const int lane = threadIdx.x & 63;
-    // XCD-aware mapping (speed only, never correctness): workgroups are dealt round-robin over the
-    // 8 XCDs, so blockIdx % 8 names the group of blocks that share an L2.  Each group gets
-    //  (a) one column slice (wide rows): its 4 MiB L2 then sees 1/n_slices of the gathered table;
-    //  (b) a CONTIGUOUS range of the task list, so rows that are neighbours in the node order —
-    //      the same community after reordering — are gathered through the same L2.
     int t, cslice;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        cslice = SLICED ? xcd % a.n_slices : blockIdx.y;
-        const int g_id = SLICED ? xcd / a.n_slices : xcd;  // which share of the tasks
-        t = a.bounds[g_id] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (t >= a.bounds[g_id + 1]) return;               // wave-uniform
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    if (!gs_block_task<SLICED>(a, t, cslice)) return;
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     if (!row_wanted(a, row)) return;                       // wave-uniform
     const int g = lane / L, l = lane % L;
     const int col0 = (cslice * L + l) * 4;                  // first column of this lane's float4
@@ -277,22 +351,14 @@ __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int base = e0; base < e1; base += WAVE) {
         const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            // > 0 for every real edge.  Factored operator (a.coef == NULL, wave-uniform): every edge counts 1 and no coefficient
-            // stream is read — the saving is the stream (measured 0.756 -> 0.720 ms at Reddit scale); instantiations that also
-            // drop the hand-out shuffle and the multiply measured the same 0.720 ms and were not kept
-            my_c = a.coef ? a.coef[base + lane] : 1.f;
-            if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;
-        }
+        int my_idx;
+        float my_c;
+        gs_load_edges(a, base, cnt, lane, my_idx, my_c);
         acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
     }
-#pragma unroll
-    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
-    if (slot >= 0) {                                        // a finalize launch will add the segments
-        if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+    if constexpr (L < WAVE) acc = gs_group_sum<L>(acc);    // L == 64: one lane group, nothing to combine (an empty call still moves registers)
+    if (slot >= 0) {
+        if (g == 0 && active) gs_store_partial(a, slot, col0, acc);
         return;
     }
     uint32_t nib = 0;                                       // this lane's four (out > 0) bits, at their place in the row's word
@@ -307,14 +373,9 @@ __global__ __launch_bounds__(256) void graphsum_vec_kernel(GsArgs a) {
                 acc = make_float4(x[0], x[1], x[2], x[3]);
             }
         }
-        if (a.post) { const float ps = a.post[row]; acc.x *= ps; acc.y *= ps; acc.z *= ps; acc.w *= ps; }
+        acc = gs_post4(a, row, acc);
         if (a.fuse) acc = relu_dropout4(acc, a, row, col0);
-        if (col0 + 4 <= a.dim) {
-            *reinterpret_cast<float4 *>(o) = acc;
-        } else {                                           // ragged tail: dim % 4 != 0
-            const float x[4] = {acc.x, acc.y, acc.z, acc.w};
-            for (int i = 0; col0 + i < a.dim; i++) o[i] = x[i];
-        }
+        gs_store_row4(a, o, col0, acc);
         nib = ((acc.x > 0.f ? 1u : 0u) | (acc.y > 0.f ? 2u : 0u) | (acc.z > 0.f ? 4u : 0u) | (acc.w > 0.f ? 8u : 0u)) << (4 * (l & 7));
     }
     if constexpr (!SLICED && L <= 16)
@@ -339,25 +400,56 @@ __device__ inline void bf8_fma(float c, const uint4 v, float4 &lo, float4 &hi) {
     hi.z += c * __uint_as_float(v.w << 16); hi.w += c * __uint_as_float(v.w & 0xFFFF0000u);
 }
 
+// gather_chunk for the bf16 table: the same batches of GS_U row loads in flight, the same j_safe tail, the same order of the sum
+template <int L>
+__device__ __forceinline__ void gather_chunk_bf16(const GsArgs &a, const uint16_t *in, int my_idx, float my_c, int cnt, int g, float4 &lo, float4 &hi) {
+    constexpr int G = WAVE / L;
+    const int iters = (cnt + G - 1) / G;
+    int k = 0;
+    if (!a.row_bits) {
+        for (; (k + GS_U) * G <= cnt; k += GS_U) {
+            uint4 v[GS_U];
+            float cc[GS_U];
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) {
+                const int src = (k + u) * G + g;
+                const int j = __shfl(my_idx, src, WAVE);
+                cc[u] = __shfl(my_c, src, WAVE);
+                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)j * a.ld_in);
+            }
+#pragma unroll
+            for (int u = 0; u < GS_U; u++) bf8_fma(cc[u], v[u], lo, hi);
+        }
+    }
+    const int j_safe = __shfl(my_idx, 0, WAVE);
+    for (; k < iters; k += GS_U) {
+        uint4 v[GS_U];
+        float cc[GS_U];
+        bool on[GS_U];
+#pragma unroll
+        for (int u = 0; u < GS_U; u++) {
+            const int src = (k + u) * G + g;
+            const int j = __shfl(my_idx, src & 63, WAVE);
+            cc[u] = __shfl(my_c, src & 63, WAVE);
+            on[u] = src < cnt && cc[u] != 0.f;
+            v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
+        }
+#pragma unroll
+        for (int u = 0; u < GS_U; u++) {
+            float4 nlo = lo, nhi = hi;
+            bf8_fma(cc[u], v[u], nlo, nhi);
+            lo.x = on[u] ? nlo.x : lo.x; lo.y = on[u] ? nlo.y : lo.y; lo.z = on[u] ? nlo.z : lo.z; lo.w = on[u] ? nlo.w : lo.w;
+            hi.x = on[u] ? nhi.x : hi.x; hi.y = on[u] ? nhi.y : hi.y; hi.z = on[u] ? nhi.z : hi.z; hi.w = on[u] ? nhi.w : hi.w;
+        }
+    }
+}
+
 template <int L>
 __global__ __launch_bounds__(256) void graphsum_bf16_kernel(GsArgs a) {
-    constexpr int G = WAVE / L;
     const int lane = threadIdx.x & 63;
-    int t, cslice;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        cslice = a.n_slices > 1 ? xcd % a.n_slices : blockIdx.y;
-        const int g_id = xcd / a.n_slices;
-        t = a.bounds[g_id] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (t >= a.bounds[g_id + 1]) return;
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    int t, cslice;                                          // sliced or not is the launch's choice (a.n_slices), wave-uniform
+    if (!(a.n_slices > 1 ? gs_block_task<true>(a, t, cslice) : gs_block_task<false>(a, t, cslice))) return;
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     if (!row_wanted(a, row)) return;                       // wave-uniform
     const int g = lane / L, l = lane % L;
     const int col0 = (cslice * L + l) * 8;
@@ -366,60 +458,16 @@ __global__ __launch_bounds__(256) void graphsum_bf16_kernel(GsArgs a) {
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
     for (int base = e0; base < e1; base += WAVE) {
         const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            my_c = a.coef[base + lane];
-            if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;
-        }
-        const int iters = (cnt + G - 1) / G;
-        // batches of GS_U row loads in flight, as gather_chunk does for the f32 table
-        int k = 0;
-        if (!a.row_bits) {
-            for (; (k + GS_U) * G <= cnt; k += GS_U) {
-                uint4 v[GS_U];
-                float cc[GS_U];
-#pragma unroll
-                for (int u = 0; u < GS_U; u++) {
-                    const int src = (k + u) * G + g;
-                    const int j = __shfl(my_idx, src, WAVE);
-                    cc[u] = __shfl(my_c, src, WAVE);
-                    v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)j * a.ld_in);
-                }
-#pragma unroll
-                for (int u = 0; u < GS_U; u++) bf8_fma(cc[u], v[u], lo, hi);
-            }
-        }
-        const int j_safe = __shfl(my_idx, 0, WAVE);
-        for (; k < iters; k += GS_U) {
-            uint4 v[GS_U];
-            float cc[GS_U];
-            bool on[GS_U];
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) {
-                const int src = (k + u) * G + g;
-                const int j = __shfl(my_idx, src & 63, WAVE);
-                cc[u] = __shfl(my_c, src & 63, WAVE);
-                on[u] = src < cnt && cc[u] != 0.f;
-                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
-            }
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) {
-                float4 nlo = lo, nhi = hi;
-                bf8_fma(cc[u], v[u], nlo, nhi);
-                lo.x = on[u] ? nlo.x : lo.x; lo.y = on[u] ? nlo.y : lo.y; lo.z = on[u] ? nlo.z : lo.z; lo.w = on[u] ? nlo.w : lo.w;
-                hi.x = on[u] ? nhi.x : hi.x; hi.y = on[u] ? nhi.y : hi.y; hi.z = on[u] ? nhi.z : hi.z; hi.w = on[u] ? nhi.w : hi.w;
-            }
-        }
+        int my_idx;
+        float my_c;
+        gs_load_edges(a, base, cnt, lane, my_idx, my_c);
+        gather_chunk_bf16<L>(a, in, my_idx, my_c, cnt, g, lo, hi);
     }
-#pragma unroll
-    for (int m = L; m < WAVE; m <<= 1) { lo = f4_add(lo, f4_shfl_xor(lo, m)); hi = f4_add(hi, f4_shfl_xor(hi, m)); }
+    lo = gs_group_sum<L>(lo);
+    hi = gs_group_sum<L>(hi);
     if (g == 0 && active) {
         if (slot >= 0) {
-            float *pp = a.partials + (size_t)slot * a.part_ld + col0;
-            *reinterpret_cast<float4 *>(pp) = lo;
-            *reinterpret_cast<float4 *>(pp + 4) = hi;
+            gs_store_partial(a, slot, col0, lo, hi);
         } else {
             if (a.fuse) { lo = relu_dropout4(lo, a, row, col0); hi = relu_dropout4(hi, a, row, col0 + 4); }
             float *o = a.out + (size_t)row * a.ld_out + col0;
@@ -438,7 +486,7 @@ __global__ __launch_bounds__(256) void graphsum_bf16_kernel(GsArgs a) {
 // The row reduction of the loss epilogue with a different output: pred[r] = argmax of the logit row (the LOWEST column on a
 // tie, numpy.argmax's rule), prob[r] = 1 / sum_j exp(z_j - max) — max and the left-to-right sum are the loss epilogue's, so
 // the bits of the sum are those of xent_row_epilogue*'s `se` — and optionally logp[r, :] = (z - max) - log(sum), the whole
-// log-softmax row.  Never part of an existing kernel: separate instantiations (graphsum_predict_*) carry it.
+// log-softmax row.  Kernels of their own (graphsum_predict_*) carry it.
 struct PredArgs {
     int32_t *pred;          // [rows of out]
     float *prob;            // [rows of out]
@@ -517,26 +565,16 @@ __device__ __forceinline__ void predict_row_epilogue1(const GsArgs &a, const Pre
     if (p.logp && in_row) p.logp[(size_t)row * p.ld_logp + lane] = x - logf(se);
 }
 
-// Prediction kernels: the gathers of graphsum_vec_kernel (one column chunk, not sliced), graphsum_bf16_kernel and
+// Prediction kernels: the pieces of graphsum_vec_kernel (one column chunk, not sliced), graphsum_bf16_kernel and
 // graphsum_finalize_kernel — same lane groups, same edge order, same reduction tree and post factor, so the logits have the
 // bits of those kernels — with the prediction epilogue in place of the ReLU / dropout / mask / loss options (which a
-// prediction never takes).  Kept apart so that no existing kernel changes.  `out` may be NULL: the logits are not stored.
+// prediction never takes, so those kernels do not carry it).  `out` may be NULL: the logits are not stored.
 template <int L, int U>
 __global__ __launch_bounds__(256) void graphsum_predict_vec_kernel(GsArgs a, PredArgs p) {
     const int lane = threadIdx.x & 63;
-    int t;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (t >= a.bounds[xcd + 1]) return;                // wave-uniform
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    int t, cslice;
+    if (!gs_block_task<false>(a, t, cslice)) return;
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     const int g = lane / L, l = lane % L;
     const int col0 = l * 4;
     const bool active = col0 < a.dim;
@@ -544,31 +582,19 @@ __global__ __launch_bounds__(256) void graphsum_predict_vec_kernel(GsArgs a, Pre
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int base = e0; base < e1; base += WAVE) {
         const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            my_c = a.coef ? a.coef[base + lane] : 1.f;
-        }
+        int my_idx;
+        float my_c;
+        gs_load_edges(a, base, cnt, lane, my_idx, my_c);
         acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
     }
-#pragma unroll
-    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
-    if (slot >= 0) {                                        // the finalize launch adds the segments and predicts
-        if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+    acc = gs_group_sum<L>(acc);
+    if (slot >= 0) {                                        // the finalize launch predicts
+        if (g == 0 && active) gs_store_partial(a, slot, col0, acc);
         return;
     }
     if (g == 0 && active) {
-        if (a.post) { const float ps = a.post[row]; acc.x *= ps; acc.y *= ps; acc.z *= ps; acc.w *= ps; }
-        if (a.out) {
-            float *o = a.out + (size_t)row * a.ld_out + col0;
-            if (col0 + 4 <= a.dim) {
-                *reinterpret_cast<float4 *>(o) = acc;
-            } else {
-                const float x[4] = {acc.x, acc.y, acc.z, acc.w};
-                for (int i = 0; col0 + i < a.dim; i++) o[i] = x[i];
-            }
-        }
+        acc = gs_post4(a, row, acc);
+        if (a.out) gs_store_row4(a, a.out + (size_t)row * a.ld_out + col0, col0, acc);
     }
     const float z[4] = {acc.x, acc.y, acc.z, acc.w};
     predict_row_epilogue<L, 4>(a, p, row, z, lane, l, g, col0);
@@ -576,79 +602,26 @@ __global__ __launch_bounds__(256) void graphsum_predict_vec_kernel(GsArgs a, Pre
 
 template <int L>
 __global__ __launch_bounds__(256) void graphsum_predict_bf16_kernel(GsArgs a, PredArgs p) {
-    constexpr int G = WAVE / L;
     const int lane = threadIdx.x & 63;
-    int t;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (t >= a.bounds[xcd + 1]) return;
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    int t, cslice;
+    if (!gs_block_task<false>(a, t, cslice)) return;
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     const int g = lane / L, l = lane % L;
     const int col0 = l * 8;
     const bool active = col0 < a.dim;
     const uint16_t *in = a.in_bf + (active ? col0 : 0);
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-    for (int base = e0; base < e1; base += WAVE) {          // graphsum_bf16_kernel's batches, without an input row mask
+    for (int base = e0; base < e1; base += WAVE) {
         const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            my_c = a.coef[base + lane];
-        }
-        const int iters = (cnt + G - 1) / G;
-        int k = 0;
-        for (; (k + GS_U) * G <= cnt; k += GS_U) {
-            uint4 v[GS_U];
-            float cc[GS_U];
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) {
-                const int src = (k + u) * G + g;
-                const int j = __shfl(my_idx, src, WAVE);
-                cc[u] = __shfl(my_c, src, WAVE);
-                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)j * a.ld_in);
-            }
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) bf8_fma(cc[u], v[u], lo, hi);
-        }
-        const int j_safe = __shfl(my_idx, 0, WAVE);
-        for (; k < iters; k += GS_U) {
-            uint4 v[GS_U];
-            float cc[GS_U];
-            bool on[GS_U];
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) {
-                const int src = (k + u) * G + g;
-                const int j = __shfl(my_idx, src & 63, WAVE);
-                cc[u] = __shfl(my_c, src & 63, WAVE);
-                on[u] = src < cnt && cc[u] != 0.f;
-                v[u] = *reinterpret_cast<const uint4 *>(in + (size_t)(on[u] ? j : j_safe) * a.ld_in);
-            }
-#pragma unroll
-            for (int u = 0; u < GS_U; u++) {
-                float4 nlo = lo, nhi = hi;
-                bf8_fma(cc[u], v[u], nlo, nhi);
-                lo.x = on[u] ? nlo.x : lo.x; lo.y = on[u] ? nlo.y : lo.y; lo.z = on[u] ? nlo.z : lo.z; lo.w = on[u] ? nlo.w : lo.w;
-                hi.x = on[u] ? nhi.x : hi.x; hi.y = on[u] ? nhi.y : hi.y; hi.z = on[u] ? nhi.z : hi.z; hi.w = on[u] ? nhi.w : hi.w;
-            }
-        }
+        int my_idx;
+        float my_c;
+        gs_load_edges(a, base, cnt, lane, my_idx, my_c);
+        gather_chunk_bf16<L>(a, in, my_idx, my_c, cnt, g, lo, hi);
     }
-#pragma unroll
-    for (int m = L; m < WAVE; m <<= 1) { lo = f4_add(lo, f4_shfl_xor(lo, m)); hi = f4_add(hi, f4_shfl_xor(hi, m)); }
+    lo = gs_group_sum<L>(lo);
+    hi = gs_group_sum<L>(hi);
     if (slot >= 0) {
-        if (g == 0 && active) {
-            float *pp = a.partials + (size_t)slot * a.part_ld + col0;
-            *reinterpret_cast<float4 *>(pp) = lo;
-            *reinterpret_cast<float4 *>(pp + 4) = hi;
-        }
+        if (g == 0 && active) gs_store_partial(a, slot, col0, lo, hi);
         return;
     }
     const float z[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -681,16 +654,62 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restric
     }
 }
 
-template <int L>
-static void launch_bf16(GsArgs a, const int (*xb)[9], hipStream_t s, const PredArgs *pred = nullptr) {
-    const int ychunks = ceil_div(a.dim, L * 8);
-    const bool sliced = ychunks > 1 && 8 % ychunks == 0;
-    a.n_slices = sliced ? ychunks : 1;
-    const int G = 8 / a.n_slices;
+// ---- the pieces every launch is made of ------------------------------------------------------------------------------
+// The rows a launch computes: every row of the adjacency object, or a registered subset of them.
+struct GsRows {
+    const int (*bounds)[9];
+    const int4 *split_rows;
+    int n_split_rows;
+};
+
+// The operator's part of GsArgs.  A registered row subset brings its own compacted task list (same order, same segment slots).
+static GsRows gs_fill(GsArgs &a, const gcnhip_graph *g, const gcnhip_rowset *rs, int ld_in, int elem_bytes) {
+    a.indptr = g->indptr; a.indices = g->indices; a.coef = g->coef;
+    a.tasks = rs ? rs->tasks : g->tasks; a.n_tasks = rs ? rs->n_tasks : g->n_tasks; a.n_rows = g->n_rows; a.nnz = g->nnz;
+    a.table_bytes = (size_t)g->n_cols * ld_in * elem_bytes;
+    a.partials = g->partials; a.part_ld = g->part_ld;
+    if (rs) return {rs->bounds, rs->split_rows, rs->n_split_rows};
+    return {g->bounds, g->split_rows, g->n_split_rows};
+}
+
+// The segment scratch of split rows is sized when the object is built (256 columns) or by gcnhip_graph_reserve_width;
+// a launch never allocates, synchronises or touches the object.
+static bool gs_scratch_too_narrow(const gcnhip_graph *g, int dim) { return g->n_slots && g->part_ld < (dim + 7) / 8 * 8; }
+
+// The task ranges of the 8 / n_slices XCD groups that share the task list; returns the blocks (of 4 waves) per XCD.
+static int gs_bounds(GsArgs &a, const int (*xb)[9], int n_slices) {
+    a.n_slices = n_slices;
+    const int G = 8 / n_slices;
     const int lg = G == 8 ? 3 : (G == 4 ? 2 : (G == 2 ? 1 : 0));
     int max_blocks = 1;
     for (int k = 0; k <= 8; k++) a.bounds[k] = xb[lg][k];
     for (int k = 0; k < G; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
+    return max_blocks;
+}
+
+// Batch depth by regime.  A table that fits the 256 MiB Infinity Cache is gathered with 4 row loads in flight per lane
+// group (latency-bound otherwise: 1.08 -> 0.85 ms at Reddit scale).  Past it the kernel is HBM-bound and 2 is the
+// optimum (R-MAT scale 21, 1 GiB table, d = 128: 5.33 / 5.16 / 5.51 ms with 1 / 2 / 4 in flight).
+static int gs_batch_depth(const gcnhip_ctx *c, const GsArgs &a) {
+    return c->opt.gs_u ? c->opt.gs_u : (a.table_bytes > ((size_t)256 << 20) ? 2 : 4);
+}
+
+// After the gather launch: the finalize launch, when there are split rows.
+template <class F>
+static int gs_finish(int n_split_rows, F finalize) {
+    GCNHIP_LAUNCH_CHECK();
+    if (n_split_rows) {
+        finalize();
+        GCNHIP_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+template <int L>
+static void launch_bf16(GsArgs a, const int (*xb)[9], hipStream_t s, const PredArgs *pred = nullptr) {
+    const int ychunks = ceil_div(a.dim, L * 8);
+    const bool sliced = ychunks > 1 && 8 % ychunks == 0;
+    const int max_blocks = gs_bounds(a, xb, sliced ? ychunks : 1);
     if constexpr (L <= 8) {
         if (pred) { graphsum_predict_bf16_kernel<L><<<max_blocks * 8, 256, 0, s>>>(a, *pred); return; }   // dim <= 64: one chunk
     }
@@ -706,26 +725,16 @@ __global__ __launch_bounds__(256) void graphsum_scalar_kernel(GsArgs a) {
     const int t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int nt = a.n_tasks ? a.n_tasks : a.n_rows;
     if (t >= nt) return;
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     if (!row_wanted(a, row)) return;                       // wave-uniform
     const int g = lane / L, l = lane % L;
     for (int cbase = 0; cbase < a.dim; cbase += L * MAXC) {
         float acc[MAXC] = {0.f, 0.f, 0.f, 0.f};
         for (int base = e0; base < e1; base += WAVE) {
             const int cnt = min(WAVE, e1 - base);
-            int my_idx = 0;
-            float my_c = 0.f;
-            if (lane < cnt) {
-                my_idx = a.indices[base + lane];
-                my_c = a.coef[base + lane];
-                if (a.row_bits && !((a.row_bits[my_idx >> 5] >> (my_idx & 31)) & 1u)) my_c = 0.f;
-            }
+            int my_idx;
+            float my_c;
+            gs_load_edges(a, base, cnt, lane, my_idx, my_c);
             const int iters = (cnt + G - 1) / G;
 #pragma unroll 4
             for (int k = 0; k < iters; k++) {
@@ -782,22 +791,7 @@ __global__ __launch_bounds__(256) void graphsum_finalize_kernel(GsArgs a, const 
         const int col = c0 + threadIdx.x;
         float v = 0.f;
         if (col < a.dim) {
-            v = a.accumulate ? a.out[(size_t)row * a.ld_out + col] : 0.f;
-            // four partials in flight per batch (unconditional loads from clamped slots; the same left-to-right sum)
-            const float *pp = a.partials + (size_t)first * a.part_ld + col;
-            int k = 0;
-            for (; k + 4 <= ns; k += 4) {
-                const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
-                const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
-                v += p0; v += p1; v += p2; v += p3;
-            }
-            {
-                const float p0 = pp[(size_t)min(k, ns - 1) * a.part_ld], p1 = pp[(size_t)min(k + 1, ns - 1) * a.part_ld];
-                const float p2 = pp[(size_t)min(k + 2, ns - 1) * a.part_ld];
-                if (k < ns) v += p0;
-                if (k + 1 < ns) v += p1;
-                if (k + 2 < ns) v += p2;
-            }
+            v = gs_segment_sum(a, first, ns, col, a.accumulate ? a.out[(size_t)row * a.ld_out + col] : 0.f);
             if (a.post) v *= a.post[row];
             if (a.fuse) {
                 v = v > 0.f ? v : 0.f;
@@ -820,7 +814,7 @@ __global__ __launch_bounds__(256) void graphsum_finalize_kernel(GsArgs a, const 
     }
 }
 
-// graphsum_finalize_kernel's segment sum (dim <= 64: one pass, the first wave holds the row) with the prediction epilogue
+// the segment sum (dim <= 64: one pass, the first wave holds the row) with the prediction epilogue
 __global__ __launch_bounds__(256) void graphsum_finalize_predict_kernel(GsArgs a, PredArgs p, const int4 *split_rows, int n_split_rows) {
     const int s = blockIdx.x;
     if (s >= n_split_rows || threadIdx.x >= WAVE) return;  // whole wave 0 stays
@@ -829,14 +823,7 @@ __global__ __launch_bounds__(256) void graphsum_finalize_predict_kernel(GsArgs a
     const int col = threadIdx.x;
     float v = 0.f;
     if (col < a.dim) {
-        const float *pp = a.partials + (size_t)first * a.part_ld + col;
-        int k = 0;
-        for (; k + 4 <= ns; k += 4) {
-            const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
-            const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
-            v += p0; v += p1; v += p2; v += p3;
-        }
-        for (; k < ns; k++) v += pp[(size_t)k * a.part_ld];
+        v = gs_segment_sum(a, first, ns, col, 0.f);
         if (a.post) v *= a.post[row];
         if (a.out) a.out[(size_t)row * a.ld_out + col] = v;
     }
@@ -845,9 +832,9 @@ __global__ __launch_bounds__(256) void graphsum_finalize_predict_kernel(GsArgs a
 
 // ---- blend epilogue (gcnhip_graphsum_blend) -------------------------------------------------------------------------
 // One step of label propagation / Correct & Smooth:  out[r, :] = clamp(alpha * (A^ . in)[r, :] + beta * base[r, :], lo, hi),
-// optionally pred[r] = argmax of that row (the lowest column on a tie).  The gather is graphsum_predict_vec_kernel's — same
-// task list, lane groups, edge order, reduction tree and split-row scratch — with another epilogue; kept apart so that no
-// existing kernel changes.  The operator is taken UNFACTORED (per-edge coefficients, g->coef): at class width the 4-byte
+// optionally pred[r] = argmax of that row (the lowest column on a tie).  The gather is graphsum_predict_vec_kernel's — the same
+// pieces: task list, lane groups, edge order, reduction tree and split-row scratch — with another epilogue in a kernel of its
+// own.  The operator is taken UNFACTORED (per-edge coefficients, g->coef): at class width the 4-byte
 // coefficient rides beside a 192-byte gathered row, and staying unscaled keeps the iterate in one form — the table a launch
 // writes is the table the next one gathers, with no dinv-scaled copy to maintain between iterations.
 struct BlendArgs {
@@ -865,19 +852,9 @@ __device__ __forceinline__ float blend1(const BlendArgs &b, float sum, float bas
 template <int L, int U>
 __global__ __launch_bounds__(256) void graphsum_blend_vec_kernel(GsArgs a, BlendArgs b) {
     const int lane = threadIdx.x & 63;
-    int t;
-    {
-        const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-        t = a.bounds[xcd] + q * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (t >= a.bounds[xcd + 1]) return;                // wave-uniform
-    }
-    int row, e0, e1, slot;
-    if (a.n_tasks) {
-        const int4 tk = a.tasks[t];
-        row = tk.x; e0 = tk.y; e1 = tk.z; slot = tk.w;
-    } else {
-        row = t; e0 = a.indptr[t]; e1 = a.indptr[t + 1]; slot = -1;
-    }
+    int t, cslice;
+    if (!gs_block_task<false>(a, t, cslice)) return;
+    const auto [row, e0, e1, slot] = gs_task(a, t);
     const int g = lane / L, l = lane % L;
     const int col0 = l * 4;
     const bool active = col0 < a.dim;
@@ -885,18 +862,14 @@ __global__ __launch_bounds__(256) void graphsum_blend_vec_kernel(GsArgs a, Blend
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int base = e0; base < e1; base += WAVE) {
         const int cnt = min(WAVE, e1 - base);
-        int my_idx = 0;
-        float my_c = 0.f;
-        if (lane < cnt) {
-            my_idx = a.indices[base + lane];
-            my_c = a.coef[base + lane];
-        }
+        int my_idx;
+        float my_c;
+        gs_load_edges(a, base, cnt, lane, my_idx, my_c);
         acc = gather_chunk<L, U>(a, in, my_idx, my_c, cnt, g, acc);
     }
-#pragma unroll
-    for (int m = L; m < WAVE; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
-    if (slot >= 0) {                                        // the finalize launch adds the segments and blends
-        if (g == 0 && active) *reinterpret_cast<float4 *>(a.partials + (size_t)slot * a.part_ld + col0) = acc;
+    acc = gs_group_sum<L>(acc);
+    if (slot >= 0) {                                        // the finalize launch blends
+        if (g == 0 && active) gs_store_partial(a, slot, col0, acc);
         return;
     }
     float x[4] = {acc.x, acc.y, acc.z, acc.w};
@@ -904,14 +877,16 @@ __global__ __launch_bounds__(256) void graphsum_blend_vec_kernel(GsArgs a, Blend
     int bi = 0x7FFFFFFF;
     if (g == 0 && active) {
         const float *bp = b.base + (size_t)row * b.ld_base + col0;
-        float *o = a.out + (size_t)row * a.ld_out + col0;
+        float bb[4] = {0.f, 0.f, 0.f, 0.f};                 // ragged tail: the padding of base is not read, that of out not written
         if (col0 + 4 <= a.dim) {
-            const float4 bb = *reinterpret_cast<const float4 *>(bp);
-            x[0] = blend1(b, x[0], bb.x); x[1] = blend1(b, x[1], bb.y); x[2] = blend1(b, x[2], bb.z); x[3] = blend1(b, x[3], bb.w);
-            *reinterpret_cast<float4 *>(o) = make_float4(x[0], x[1], x[2], x[3]);
-        } else {                                           // ragged tail: the padding of base is not read, that of out not written
-            for (int i = 0; col0 + i < a.dim; i++) { x[i] = blend1(b, x[i], bp[i]); o[i] = x[i]; }
+            const float4 q = *reinterpret_cast<const float4 *>(bp);
+            bb[0] = q.x; bb[1] = q.y; bb[2] = q.z; bb[3] = q.w;
+        } else {
+            for (int i = 0; col0 + i < a.dim; i++) bb[i] = bp[i];
         }
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[i] = blend1(b, x[i], bb[i]);
+        gs_store_row4(a, a.out + (size_t)row * a.ld_out + col0, col0, make_float4(x[0], x[1], x[2], x[3]));
 #pragma unroll
         for (int i = 0; i < 4; i++)
             if (col0 + i < a.dim && (bi == 0x7FFFFFFF || x[i] > bv)) { bv = x[i]; bi = col0 + i; }
@@ -923,7 +898,7 @@ __global__ __launch_bounds__(256) void graphsum_blend_vec_kernel(GsArgs a, Blend
     }
 }
 
-// graphsum_finalize_predict_kernel's segment sum (one wave per split row, lane c on column c) with the blend epilogue
+// the segment sum (one wave per split row, lane c on column c) with the blend epilogue
 __global__ __launch_bounds__(64) void graphsum_finalize_blend_kernel(GsArgs a, BlendArgs b, const int4 *split_rows, int n_split_rows) {
     const int s = blockIdx.x;
     if (s >= n_split_rows || threadIdx.x >= WAVE) return;
@@ -933,14 +908,7 @@ __global__ __launch_bounds__(64) void graphsum_finalize_blend_kernel(GsArgs a, B
     const bool in_row = col < a.dim;
     float v = 0.f;
     if (in_row) {
-        const float *pp = a.partials + (size_t)first * a.part_ld + col;
-        int k = 0;
-        for (; k + 4 <= ns; k += 4) {
-            const float p0 = pp[(size_t)k * a.part_ld], p1 = pp[(size_t)(k + 1) * a.part_ld];
-            const float p2 = pp[(size_t)(k + 2) * a.part_ld], p3 = pp[(size_t)(k + 3) * a.part_ld];
-            v += p0; v += p1; v += p2; v += p3;
-        }
-        for (; k < ns; k++) v += pp[(size_t)k * a.part_ld];
+        v = gs_segment_sum(a, first, ns, col, 0.f);
         v = blend1(b, v, b.base[(size_t)row * b.ld_base + col]);
         a.out[(size_t)row * a.ld_out + col] = v;
     }
@@ -964,17 +932,8 @@ static void launch_vec(GsArgs &a, const int (*xb)[9], const gcnhip_ctx *c, const
     hipStream_t s = c->stream;
     const int ychunks = ceil_div(a.dim, L * 4);
     const bool sliced = ychunks > 1 && 8 % ychunks == 0;   // XCD-sliced columns (1-D grid)
-    a.n_slices = sliced ? ychunks : 1;
-    const int G = 8 / a.n_slices;                          // XCD groups that share the task list
-    const int lg = G == 8 ? 3 : (G == 4 ? 2 : (G == 2 ? 1 : 0));
-    int max_blocks = 1;
-    for (int k = 0; k <= 8; k++) a.bounds[k] = xb[lg][k];
-    for (int k = 0; k < G; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
-    // Batch depth by regime.  A table that fits the 256 MiB Infinity Cache is gathered with 4 row loads in flight per lane
-    // group (latency-bound otherwise: 1.08 -> 0.85 ms at Reddit scale).  Past it the kernel is HBM-bound and 2 is the
-    // optimum (R-MAT scale 21, 1 GiB table, d = 128: 5.33 / 5.16 / 5.51 ms with 1 / 2 / 4 in flight).
-    const int force_u = c->opt.gs_u;
-    const int u = force_u ? force_u : (a.table_bytes > ((size_t)256 << 20) ? 2 : 4);
+    const int max_blocks = gs_bounds(a, xb, sliced ? ychunks : 1);
+    const int u = gs_batch_depth(c, a);
     const dim3 grid(max_blocks * 8, sliced ? 1 : ychunks);
     if constexpr (L <= 16) {
         if (pred) {                                         // dim <= 64: one column chunk, never sliced; 1 or 2 loads in flight: same bits
@@ -998,45 +957,67 @@ static void launch_scalar(const GsArgs &a, int nt, hipStream_t s) {
     graphsum_scalar_kernel<L><<<ceil_div(nt, 4), 256, 0, s>>>(a);
 }
 
-static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in, float *out, int ld_out,
-                         int dim, int fuse, int training, float p, uint64_t seed, const uint32_t *d_epoch,
-                         uint64_t elem_offset, const uint8_t *keep_mask, const uint32_t *row_bits = nullptr,
-                         const uint16_t *in_bf = nullptr, const uint32_t *out_bits = nullptr,
-                         const gcnhip_rowset *rs = nullptr, int accumulate = 0, uint32_t *pos_bits = nullptr, int wpr = 0, int scaling = 0,
-                         const gcnhip_gs_loss *loss = nullptr, const PredArgs *pred = nullptr) {
+// One aggregation launch as the entry points describe it: each names what it sets, the rest keeps its default.
+struct GsCall {
+    const float *in = nullptr;
+    const uint16_t *in_bf = nullptr;                        // the bf16 table, in place of `in`
+    float *out = nullptr;                                   // may be NULL with pred: the logits are not stored
+    int ld_in = 0, ld_out = 0, dim = 0;
+    const gcnhip_rowset *rs = nullptr;
+    const uint32_t *row_bits = nullptr, *out_bits = nullptr;
+    int accumulate = 0, scaling = 0;
+    // the ReLU + dropout store epilogue (fuse), and the mask words its backward reads
+    int fuse = 0, training = 0;
+    float p = 0.f;
+    uint64_t seed = 0, elem_offset = 0;
+    const uint32_t *d_epoch = nullptr;
+    const uint8_t *keep_mask = nullptr;
+    uint32_t *pos_bits = nullptr;
+    int wpr = 0;
+    const gcnhip_gs_loss *loss = nullptr;
+    const PredArgs *pred = nullptr;
+};
+
+static GsCall gs_call(const float *in, int ld_in, float *out, int ld_out, int dim) {
+    GsCall k;
+    k.in = in; k.ld_in = ld_in; k.out = out; k.ld_out = ld_out; k.dim = dim;
+    return k;
+}
+
+static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const GsCall &k) {
+    const float *in = k.in;
+    const uint16_t *in_bf = k.in_bf;
+    float *out = k.out;
+    const int ld_in = k.ld_in, ld_out = k.ld_out, dim = k.dim, fuse = k.fuse;
+    const gcnhip_rowset *rs = k.rs;
+    const gcnhip_gs_loss *loss = k.loss;
+    const PredArgs *pred = k.pred;
+    uint32_t *pos_bits = k.pos_bits;
     if (!c || !g || (!in && !in_bf) || (!out && !pred) || dim <= 0 || ld_in < dim || ld_out < dim) return -1;
-    if (scaling < 0 || scaling > 3) return -1;
-    if (accumulate && in_bf) return -1;                     // the bf16 kernel has no accumulating store
+    if (k.scaling < 0 || k.scaling > 3) return -1;
+    if (k.accumulate && in_bf) return -1;                   // the bf16 kernel has no accumulating store
     if (rs && rs->owner != g)                                // a subset brings task lists and segment slots of ITS adjacency object
         return gcnhip_fail("gcnhip_graphsum*: the row subset was registered on another adjacency object");
     if (in_bf && (ld_in % 8 != 0 || !aligned16(in_bf))) return -1;
     if (g->n_rows == 0 || (rs && rs->n_tasks == 0)) return 0;
-    // the segment scratch of split rows is sized when the object is built (256 columns) or by
-    // gcnhip_graph_reserve_width; a launch never allocates, synchronises or touches the object
-    if (g->n_slots && g->part_ld < (dim + 7) / 8 * 8)
+    if (gs_scratch_too_narrow(g, dim))
         return gcnhip_fail("gcnhip_graphsum*: dim is wider than the split-row scratch of this adjacency object; call "
                            "gcnhip_graph_reserve_width(ctx, g, dim) once before the first launch (restricted objects: on them too)");
-    GsArgs a;
-    a.indptr = g->indptr; a.indices = g->indices; a.coef = g->coef;
-    // a registered row subset brings its own compacted task list (same order, same segment slots)
-    a.tasks = rs ? rs->tasks : g->tasks; a.n_tasks = rs ? rs->n_tasks : g->n_tasks; a.n_rows = g->n_rows; a.nnz = g->nnz;
-    a.table_bytes = (size_t)g->n_cols * ld_in * (in_bf ? 2 : 4);
-    const int (*xb)[9] = rs ? rs->bounds : g->bounds;
-    const int4 *split_rows = rs ? rs->split_rows : g->split_rows;
-    const int n_split_rows = rs ? rs->n_split_rows : g->n_split_rows;
-    a.in = in; a.in_bf = in_bf; a.out = out; a.partials = g->partials;
-    a.ld_in = ld_in; a.ld_out = ld_out; a.part_ld = g->part_ld; a.dim = dim;
-    a.fuse = fuse; a.training = training; a.thr = dropout_threshold(p);
-    a.scale = 1 / (1 - p);                                  // module.cpp:212
-    a.seed = seed; a.elem_offset = elem_offset; a.d_epoch = d_epoch; a.keep_mask = keep_mask;
-    a.row_bits = row_bits;
-    a.out_bits = out_bits;
-    a.accumulate = accumulate;
-    a.pos_bits = pos_bits; a.wpr = wpr;
-    a.post = nullptr;
+    GsArgs a = {};
+    const GsRows rows = gs_fill(a, g, rs, ld_in, in_bf ? 2 : 4);
+    const int (*xb)[9] = rows.bounds;
+    a.in = in; a.in_bf = in_bf; a.out = out;
+    a.ld_in = ld_in; a.ld_out = ld_out; a.dim = dim;
+    a.fuse = fuse; a.training = k.training; a.thr = dropout_threshold(k.p);
+    a.scale = 1 / (1 - k.p);                                // module.cpp:212
+    a.seed = k.seed; a.elem_offset = k.elem_offset; a.d_epoch = k.d_epoch; a.keep_mask = k.keep_mask;
+    a.row_bits = k.row_bits;
+    a.out_bits = k.out_bits;
+    a.accumulate = k.accumulate;
+    a.pos_bits = pos_bits; a.wpr = k.wpr;
     const int nt = a.n_tasks ? a.n_tasks : g->n_rows;
     const bool vec = (ld_in % 4 == 0) && (ld_out % 4 == 0) && aligned16(in) && aligned16(out);
-    a.xe_truth = nullptr; a.xe_grad = nullptr; a.xe_ld_grad = 0; a.xe_training = 0; a.xe_count = 1.f; a.xe_grad_scale = nullptr; a.xe_terms = nullptr;
+    a.xe_count = 1.f;
     if (loss) {
         const int w4 = (dim + 3) / 4 * 4;
         if (in_bf || !vec || dim > 64 || fuse || pos_bits || !loss->truth || !loss->row_terms || loss->count <= 0 || ((uintptr_t)loss->row_terms & 7))
@@ -1046,15 +1027,15 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         a.xe_truth = loss->truth; a.xe_grad = loss->training ? loss->grad : nullptr; a.xe_ld_grad = loss->ld_grad; a.xe_training = loss->training ? 1 : 0;
         a.xe_count = (float)loss->count; a.xe_grad_scale = loss->grad_row_scale; a.xe_terms = loss->row_terms;
     }
-    if (pred && (dim > 64 || fuse || pos_bits || loss || accumulate || row_bits || out_bits || (!in_bf && !vec)))
+    if (pred && (dim > 64 || fuse || pos_bits || loss || k.accumulate || k.row_bits || k.out_bits || (!in_bf && !vec)))
         return gcnhip_fail("gcnhip_graphsum_predict: needs dim <= 64 and f32 rows that are 16-byte aligned (ld % 4 == 0) or a bf16 table");
-    if (scaling) {
+    if (k.scaling) {
         // the factored operator runs in the 16-byte-row f32 kernel only (what the model's layouts always are)
         if (in_bf || !vec) return gcnhip_fail("gcnhip_graphsum_ex: scaling != 0 needs f32 rows that are 16-byte aligned (ld % 4 == 0)");
         a.coef = nullptr;
-        a.post = scaling == 1 ? g->dinv_row : (scaling == 2 ? g->dinv2_row : nullptr);
+        a.post = k.scaling == 1 ? g->dinv_row : (k.scaling == 2 ? g->dinv2_row : nullptr);
     }
-    if (pos_bits && !(fuse && !in_bf && vec && dim % 32 == 0 && wpr * 32 >= dim))
+    if (pos_bits && !(fuse && !in_bf && vec && dim % 32 == 0 && k.wpr * 32 >= dim))
         return gcnhip_fail("gcnhip_graphsum_relu_dropout_bits: needs the fused epilogue, 16-byte aligned rows, dim % 32 == 0 and words_per_row * 32 >= dim");
     const int d4 = (dim + 3) / 4;
     a.n_slices = 1;
@@ -1096,36 +1077,39 @@ static int graphsum_impl(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, 
         else if (dim <= 32) launch_scalar<32>(a, nt, c->stream);
         else launch_scalar<64>(a, nt, c->stream);
     }
-    GCNHIP_LAUNCH_CHECK();
-    if (n_split_rows) {
-        if (pred) graphsum_finalize_predict_kernel<<<n_split_rows, WAVE, 0, c->stream>>>(a, *pred, split_rows, n_split_rows);
-        else graphsum_finalize_kernel<<<n_split_rows, 256, 0, c->stream>>>(a, split_rows, n_split_rows);
-        GCNHIP_LAUNCH_CHECK();
-    }
-    return 0;
+    return gs_finish(rows.n_split_rows, [&] {
+        if (pred) graphsum_finalize_predict_kernel<<<rows.n_split_rows, WAVE, 0, c->stream>>>(a, *pred, rows.split_rows, rows.n_split_rows);
+        else graphsum_finalize_kernel<<<rows.n_split_rows, 256, 0, c->stream>>>(a, rows.split_rows, rows.n_split_rows);
+    });
 }
 
 extern "C" {
 
 int gcnhip_graphsum(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in,
                     float *out, int ld_out, int dim) {
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr);
+    return graphsum_impl(c, g, gs_call(in, ld_in, out, ld_out, dim));
 }
 
 int gcnhip_graphsum_rowmask(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in,
                             float *out, int ld_out, int dim, const uint32_t *in_row_bits) {
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, in_row_bits);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.row_bits = in_row_bits;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_masked(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in,
                            float *out, int ld_out, int dim, const uint32_t *in_row_bits, const uint32_t *out_row_bits) {
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, in_row_bits, nullptr, out_row_bits);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.row_bits = in_row_bits; k.out_bits = out_row_bits;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_rowset(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, int ld_in,
                            float *out, int ld_out, int dim, const uint32_t *in_row_bits) {
     if (!rows) return -1;
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, in_row_bits, nullptr, nullptr, rows);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.row_bits = in_row_bits; k.rs = rows;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_relu_dropout(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in,
@@ -1133,7 +1117,10 @@ int gcnhip_graphsum_relu_dropout(gcnhip_ctx *c, const gcnhip_graph *g, const flo
                                  uint64_t seed, const uint32_t *d_epoch, uint64_t elem_offset,
                                  const uint8_t *keep_mask) {
     if (training && !(p >= 0.f && p < 1.f)) return -1;
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 1, training, p, seed, d_epoch, elem_offset, keep_mask);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.fuse = 1; k.training = training; k.p = p;
+    k.seed = seed; k.d_epoch = d_epoch; k.elem_offset = elem_offset; k.keep_mask = keep_mask;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_relu_dropout_bits(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in,
@@ -1142,8 +1129,11 @@ int gcnhip_graphsum_relu_dropout_bits(gcnhip_ctx *c, const gcnhip_graph *g, cons
                                       const uint8_t *keep_mask, uint32_t *pos_bits, int words_per_row) {
     if (training && !(p >= 0.f && p < 1.f)) return -1;
     if (!pos_bits) return -1;
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, 1, training, p, seed, d_epoch, elem_offset, keep_mask, nullptr, nullptr, nullptr,
-                         nullptr, 0, pos_bits, words_per_row);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.fuse = 1; k.training = training; k.p = p;
+    k.seed = seed; k.d_epoch = d_epoch; k.elem_offset = elem_offset; k.keep_mask = keep_mask;
+    k.pos_bits = pos_bits; k.wpr = words_per_row;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_part(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, int ld_in,
@@ -1151,17 +1141,24 @@ int gcnhip_graphsum_part(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rows
                          int relu_dropout, int training, float p, uint64_t seed, const uint32_t *d_epoch,
                          uint64_t elem_offset, const uint8_t *keep_mask) {
     if (relu_dropout && training && !(p >= 0.f && p < 1.f)) return -1;
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, relu_dropout ? 1 : 0, relu_dropout ? training : 0, relu_dropout ? p : 0.f,
-                         seed, d_epoch, elem_offset, keep_mask, in_row_bits, nullptr, nullptr, rows, accumulate ? 1 : 0);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.fuse = relu_dropout ? 1 : 0; k.training = relu_dropout ? training : 0; k.p = relu_dropout ? p : 0.f;
+    k.seed = seed; k.d_epoch = d_epoch; k.elem_offset = elem_offset; k.keep_mask = keep_mask;
+    k.row_bits = in_row_bits; k.rs = rows; k.accumulate = accumulate ? 1 : 0;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_ex(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_gs_opts *o, const float *in, int ld_in, float *out, int ld_out, int dim) {
     if (!o) return -1;
     if (o->relu_dropout && o->training && !(o->p >= 0.f && o->p < 1.f)) return -1;
     if (o->pos_bits && !o->relu_dropout) return -1;
-    return graphsum_impl(c, g, in, ld_in, out, ld_out, dim, o->relu_dropout ? 1 : 0, o->relu_dropout ? o->training : 0, o->relu_dropout ? o->p : 0.f,
-                         o->seed, o->d_epoch, o->elem_offset, o->keep_mask, o->in_row_bits, nullptr, nullptr, o->rows, o->accumulate ? 1 : 0,
-                         o->pos_bits, o->words_per_row, o->scaling, o->loss);
+    GsCall k = gs_call(in, ld_in, out, ld_out, dim);
+    k.fuse = o->relu_dropout ? 1 : 0; k.training = o->relu_dropout ? o->training : 0; k.p = o->relu_dropout ? o->p : 0.f;
+    k.seed = o->seed; k.d_epoch = o->d_epoch; k.elem_offset = o->elem_offset; k.keep_mask = o->keep_mask;
+    k.row_bits = o->in_row_bits; k.rs = o->rows; k.accumulate = o->accumulate ? 1 : 0;
+    k.pos_bits = o->pos_bits; k.wpr = o->words_per_row;
+    k.scaling = o->scaling; k.loss = o->loss;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_predict(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_rowset *rows, const float *in, const uint16_t *in_bf16,
@@ -1171,8 +1168,9 @@ int gcnhip_graphsum_predict(gcnhip_ctx *c, const gcnhip_graph *g, const gcnhip_r
     if (in_bf16 && scaling) return gcnhip_fail("gcnhip_graphsum_predict: the factored operator (scaling != 0) gathers f32 rows only");
     const PredArgs pa = {pred, prob, logp, ld_logp};
     // (no logits stored: a stride that passes the 16-byte row test; nothing is written through it)
-    return graphsum_impl(c, g, in, ld_in, out, out ? ld_out : (dim + 3) / 4 * 4, dim, 0, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, in_bf16, nullptr, rows, 0,
-                         nullptr, 0, scaling, nullptr, &pa);
+    GsCall k = gs_call(in, ld_in, out, out ? ld_out : (dim + 3) / 4 * 4, dim);
+    k.in_bf = in_bf16; k.rs = rows; k.scaling = scaling; k.pred = &pa;
+    return graphsum_impl(c, g, k);
 }
 
 int gcnhip_graphsum_blend(gcnhip_ctx *c, const gcnhip_graph *g, const float *in, int ld_in, const float *base, int ld_base,
@@ -1183,32 +1181,24 @@ int gcnhip_graphsum_blend(gcnhip_ctx *c, const gcnhip_graph *g, const float *in,
         return gcnhip_fail("gcnhip_graphsum_blend: needs f32 rows that are 16-byte aligned (ld % 4 == 0, ld >= dim)");
     if (out == in) return gcnhip_fail("gcnhip_graphsum_blend: out must not be in (other rows are still gathering it); base may be");
     if (g->n_rows == 0) return 0;
-    if (g->n_slots && g->part_ld < (dim + 7) / 8 * 8)
+    if (gs_scratch_too_narrow(g, dim))
         return gcnhip_fail("gcnhip_graphsum_blend: dim is wider than the split-row scratch of this adjacency object; call gcnhip_graph_reserve_width");
     GsArgs a = {};
-    a.indptr = g->indptr; a.indices = g->indices; a.coef = g->coef;
-    a.tasks = g->tasks; a.n_tasks = g->n_tasks; a.n_rows = g->n_rows; a.nnz = g->nnz;
-    a.table_bytes = (size_t)g->n_cols * ld_in * 4;
-    a.in = in; a.out = out; a.partials = g->partials;
-    a.ld_in = ld_in; a.ld_out = ld_out; a.part_ld = g->part_ld; a.dim = dim;
-    a.n_slices = 1;
-    int max_blocks = 1;
-    for (int k = 0; k <= 8; k++) a.bounds[k] = g->bounds[3][k];
-    for (int k = 0; k < 8; k++) max_blocks = std::max(max_blocks, ceil_div(a.bounds[k + 1] - a.bounds[k], 4));
+    const GsRows rows = gs_fill(a, g, nullptr, ld_in, 4);
+    a.in = in; a.out = out;
+    a.ld_in = ld_in; a.ld_out = ld_out; a.dim = dim;
+    const int blocks = gs_bounds(a, rows.bounds, 1) * 8;
     const BlendArgs b = {base, ld_base, alpha, beta, lo, hi, pred};
-    const int u = c->opt.gs_u ? c->opt.gs_u : (a.table_bytes > ((size_t)256 << 20) ? 2 : 4);   // launch_vec's rule
-    const int d4 = (dim + 3) / 4, blocks = max_blocks * 8;
+    const int u = gs_batch_depth(c, a);
+    const int d4 = (dim + 3) / 4;
     if (d4 <= 1) launch_blend<1>(a, b, blocks, u, c->stream);
     else if (d4 <= 2) launch_blend<2>(a, b, blocks, u, c->stream);
     else if (d4 <= 4) launch_blend<4>(a, b, blocks, u, c->stream);
     else if (d4 <= 8) launch_blend<8>(a, b, blocks, u, c->stream);
     else launch_blend<16>(a, b, blocks, u, c->stream);
-    GCNHIP_LAUNCH_CHECK();
-    if (g->n_split_rows) {
-        graphsum_finalize_blend_kernel<<<g->n_split_rows, WAVE, 0, c->stream>>>(a, b, g->split_rows, g->n_split_rows);
-        GCNHIP_LAUNCH_CHECK();
-    }
-    return 0;
+    return gs_finish(rows.n_split_rows, [&] {
+        graphsum_finalize_blend_kernel<<<rows.n_split_rows, WAVE, 0, c->stream>>>(a, b, rows.split_rows, rows.n_split_rows);
+    });
 }
 
 int gcnhip_f32_to_bf16(gcnhip_ctx *c, const float *src, int ld_src, uint16_t *dst, int ld_dst, int64_t rows, int dim) {
@@ -1226,8 +1216,11 @@ int gcnhip_graphsum_bf16(gcnhip_ctx *c, const gcnhip_graph *g, const uint16_t *i
                          int relu_dropout, int training, float p, uint64_t seed, const uint32_t *d_epoch,
                          uint64_t elem_offset, const uint8_t *keep_mask) {
     if (relu_dropout && training && !(p >= 0.f && p < 1.f)) return -1;
-    return graphsum_impl(c, g, nullptr, ld_in, out, ld_out, dim, relu_dropout ? 1 : 0, training, relu_dropout ? p : 0.f, seed, d_epoch,
-                         elem_offset, keep_mask, in_row_bits, in_bf16, nullptr, out_rows);
+    GsCall k = gs_call(nullptr, ld_in, out, ld_out, dim);
+    k.fuse = relu_dropout ? 1 : 0; k.training = training; k.p = relu_dropout ? p : 0.f;
+    k.seed = seed; k.d_epoch = d_epoch; k.elem_offset = elem_offset; k.keep_mask = keep_mask;
+    k.in_bf = in_bf16; k.row_bits = in_row_bits; k.rs = out_rows;
+    return graphsum_impl(c, g, k);
 }
 
 }  // extern "C"

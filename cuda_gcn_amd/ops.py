@@ -511,9 +511,7 @@ class Device:
         if row_nonzero is None:
             _ck(self.lib, self.lib.gcnhip_graphsum(self.ctx, g.h, xin.ptr, ld_in, out.ptr, ld_out, dim), "gcnhip_graphsum")
         else:
-            bits = np.packbits(np.asarray(row_nonzero, bool), bitorder="little")
-            bits = np.concatenate([bits, np.zeros((-bits.size) % 4 + 4, np.uint8)]).view(np.uint32)
-            bb = self.buf(bits)
+            bb = self._bits(row_nonzero)
             _ck(self.lib, self.lib.gcnhip_graphsum_rowmask(self.ctx, g.h, xin.ptr, ld_in, out.ptr, ld_out, dim, bb.ptr), "gcnhip_graphsum_rowmask")
         return out.download()[:, :dim]
 
@@ -544,11 +542,7 @@ class Device:
         ld_out = ld_out or dim
         tb = self.buf(t)
         out = self.buf(np.full((g.n_rows, ld_out), fill, np.float32))
-        bb = None
-        if row_nonzero is not None:
-            bits = np.packbits(np.asarray(row_nonzero, bool), bitorder="little")
-            bits = np.concatenate([bits, np.zeros((-bits.size) % 4 + 4, np.uint8)]).view(np.uint32)
-            bb = self.buf(bits)
+        bb = self._bits(row_nonzero) if row_nonzero is not None else None
         rd = relu_dropout or {}
         g.reserve(dim)
         ep = self.buf(np.array([rd.get("epoch", 0)], np.uint32))

@@ -100,6 +100,32 @@ def test_blend_refusals(blend_setup):
         dev.graphsum_blend(g, np.zeros((g.n_rows, 7), np.float32), None, 0.5, 0.5, ld=7)
 
 
+@pytest.mark.parametrize("split_edges", [0, 16, 32])
+def test_blend_and_predict_gathers_are_the_aggregation_bit_for_bit(split_edges):
+    """The blend and prediction kernels gather as the plain aggregation does, so with an epilogue that changes nothing they
+    give its bits.  split_edges 0: the hub is 3 segments of 128; 16: the 64-, 65- and 300-edge rows are 4, 5 and 19 segments;
+    32: they are 2, 3 and 10 — the segment sum's four-wide batch runs 0 to 4 times and is followed by tails of 0, 1, 2 and 3.
+    The blend with base = 0, alpha = 1, beta = 0 and no clamp is exact: 1 . s is s, 0 . 0 is +0, and s is never -0 because the
+    running sum starts at +0."""
+    from cuda_gcn_amd.ops import Device
+    dev = Device(0)
+    dev.set_option("split_edges", split_edges)
+    g = dev.graph(*irregular_graph())
+    n = g.n_rows
+    for dim in (1, 3, 7, 16, 29, 41, 64):
+        x = (np.random.default_rng(100 + dim).standard_normal((n, dim)) * 2).astype(np.float32)
+        agg = {s: dev.graphsum_ex(g, x, scaling=s) for s in (0, 1)}
+        blend = dev.graphsum_blend(g, x, base=np.zeros_like(x), alpha=1.0, beta=0.0, lo=-np.inf, hi=np.inf)
+        assert same_bits(blend[:, :dim], agg[0]), ("blend", dim)
+        for s in (0, 1):
+            assert same_bits(dev.graphsum_predict(g, x=x, scaling=s)["logits"], agg[s]), ("predict", dim, s)
+        t = dev.to_bf16(x)
+        want = dev.graphsum_bf16(g, t, dim, ld_out=(dim + 3) // 4 * 4)
+        assert same_bits(dev.graphsum_predict(g, table_bf16=t, dim=dim)["logits"], want), ("predict bf16", dim)
+    g.free()
+    dev.close()
+
+
 # ---- smooth.hip ---------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("c", [3, 41, 64])

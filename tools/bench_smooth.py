@@ -1,6 +1,7 @@
 """Label propagation / Correct & Smooth on reddit-syn (hidden 128, 41 classes), HIP events — the figures of DESIGN §4.8:
-  * one blend launch (gcnhip_graphsum_blend) against one all-row class-width gcnhip_graphsum_ex launch (per-edge
-    coefficients) on the same table: the blend reads one more row per output row;
+  * one blend launch (gcnhip_graphsum_blend) and one prediction launch (gcnhip_graphsum_predict, no logits stored) against
+    one all-row class-width gcnhip_graphsum_ex launch (per-edge coefficients) on the same table: the blend reads one more
+    row per output row;
   * HipGCNModel.correct_and_smooth at the default iteration counts against predict(), wall time with a synchronisation;
   * test-split accuracy before and after.
 Prints one JSON line.  None of the values is a pass/fail threshold.  usage: bench_smooth.py [dataset] [epochs]"""
@@ -59,14 +60,15 @@ def main():
     g = dev.graph(ds["g_indptr"], ds["g_indices"], row_group=ds["label"])             # as HipGCN builds it
     rng = np.random.default_rng(0)
     x, base, out = dev.buf(rng.random((N, ld), dtype=np.float32)), dev.buf(rng.random((N, ld), dtype=np.float32)), dev.buf((N, ld))
-    pred = dev.buf((N,), np.int32)
+    pred, prob = dev.buf((N,), np.int32), dev.buf((N,), np.float32)
     o = GsOpts()
     res["graphsum_ex_ms"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_ex(dev.ctx, g.h, C.byref(o), x.ptr, ld, out.ptr, ld, c), "graphsum_ex"))
     res["blend_ms"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_blend(dev.ctx, g.h, x.ptr, ld, base.ptr, ld, out.ptr, ld, c, 0.8, 0.2, 0.0, 1.0, None), "blend"))
     res["blend_own_base_ms"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_blend(dev.ctx, g.h, x.ptr, ld, x.ptr, ld, out.ptr, ld, c, 0.8, 0.2, 0.0, 1.0, None), "blend"))
     res["blend_pred_ms"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_blend(dev.ctx, g.h, x.ptr, ld, base.ptr, ld, out.ptr, ld, c, 0.8, 0.2, 0.0, 1.0, pred.ptr), "blend"))
+    res["predict_ms"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_predict(dev.ctx, g.h, None, x.ptr, None, ld, None, ld, c, 0, pred.ptr, prob.ptr, None, 0), "predict"))
     res["graphsum_ex_ms_again"] = timeit(dev, lambda: _ck(lib, lib.gcnhip_graphsum_ex(dev.ctx, g.h, C.byref(o), x.ptr, ld, out.ptr, ld, c), "graphsum_ex"))
-    for b in (x, base, out, pred):
+    for b in (x, base, out, pred, prob):
         b.free()
     g.free()
     dev.close()
