@@ -159,22 +159,77 @@ class Device:
                                                        ib.ptr if ib else None), "gcnhip_graphsum_rowset")
         return out.download()[:, :dim]
 
-    def graphsum_ex(self, g: "Graph", x, scaling, ld=None, rows=None, row_nonzero=None, prev=None, fill=np.nan):
-        """gcnhip_graphsum_ex: the factored operator.  `x` must already hold dinv[col] * (the reference's input) when scaling != 0;
-        prev: the rows of `out` before the call (accumulate = 1)"""
-        x = np.asarray(x, np.float32)
-        dim = x.shape[1]
-        ld = ld or (dim + 3) // 4 * 4
-        xin = self.padded(x, ld)
-        out = self.padded(prev, ld) if prev is not None else self.buf(np.full((g.n_rows, ld), fill, np.float32))
+    def _gs_operands(self, g, x, dim, ld, ld_in, ld_out, prev, fill, out, row_nonzero, keep_mask, epoch, want_bits, bits):
+        """the device operands of one aggregation call.  x, row_nonzero (packed bits), keep_mask, out and bits may be Bufs that
+        already sit on the device (a table of cases keeps them there between calls); arrays are uploaded.  `out` given as a
+        Buf is used as the caller left it."""
+        if isinstance(x, Buf):
+            xin, ld_in = x, x.shape[1]
+            dim = dim or ld_in
+        else:
+            x = np.asarray(x, np.float32)
+            dim = x.shape[1]
+            ld_in = ld_in or ld or (dim + 3) // 4 * 4
+            xin = self.padded(x, ld_in)
+        ld_out = out.shape[1] if out is not None else (ld_out or ld or (dim + 3) // 4 * 4)
+        if out is None:
+            out = self.padded(prev, ld_out) if prev is not None else self.buf(np.full((g.n_rows, ld_out), fill, np.float32))
         g.reserve(dim)
-        ib = self._bits(row_nonzero) if row_nonzero is not None else None
+        ib = row_nonzero if isinstance(row_nonzero, Buf) or row_nonzero is None else self._bits(row_nonzero)
+        km = keep_mask if isinstance(keep_mask, Buf) or keep_mask is None else self.buf(np.ascontiguousarray(keep_mask, np.uint8))
+        ep = self.buf(np.array([epoch], np.uint32))
+        wpr = (dim + 31) // 32
+        if want_bits and bits is None:
+            bits = self.buf(np.full((g.n_rows, wpr), 0xDEADBEEF, np.uint32))
+        return xin, ld_in, out, ld_out, dim, ib, km, ep, bits, wpr
+
+    def graphsum_ex(self, g: "Graph", x, scaling=0, ld=None, rows=None, row_nonzero=None, prev=None, fill=np.nan, ld_in=None, ld_out=None,
+                    out_rows=None, relu_dropout=False, training=False, p=0.0, seed=0, epoch=0, elem_offset=0, keep_mask=None,
+                    want_bits=False, dim=None, out=None, bits=None, accumulate=None):
+        """gcnhip_graphsum_ex: one aggregation with every option of the launch record.  scaling != 0 is the factored operator:
+        `x` must already hold dinv[col] * (the reference's input).  prev: the rows of `out` before the call (accumulate = 1).
+        ld_in / ld_out: any value >= dim (ld: both); rows: a handle from Graph.add_rowset.  relu_dropout, training, p, seed,
+        epoch, elem_offset, keep_mask: the store epilogue; want_bits: also return the (out > 0) words, uint32 [n_rows, dim / 32].
+        out_rows (bool per row, or a Buf of packed bits): output-row bits.  The entry point that carries them is
+        gcnhip_graphsum_masked, which takes input-row bits beside them and nothing else, so the call goes there.
+        x, row_nonzero, keep_mask, out and bits may be device Bufs (see _gs_operands); `accumulate` then says what prev would."""
+        xin, ld_in, out, ld_out, dim, ib, km, ep, bits, wpr = self._gs_operands(g, x, dim, ld, ld_in, ld_out, prev, fill, out, row_nonzero,
+                                                                                 keep_mask, epoch, want_bits, bits)
+        acc = int(accumulate if accumulate is not None else prev is not None)
+        if out_rows is not None:
+            if rows is not None or acc or scaling or relu_dropout or bits is not None:
+                raise ValueError("graphsum_ex: output-row bits travel through gcnhip_graphsum_masked, which takes only input-row bits beside them")
+            ob = out_rows if isinstance(out_rows, Buf) else self._bits(out_rows)
+            _ck(self.lib, self.lib.gcnhip_graphsum_masked(self.ctx, g.h, xin.ptr, ld_in, out.ptr, ld_out, dim, ib.ptr if ib else None, ob.ptr),
+                "gcnhip_graphsum_masked")
+            return out.download()[:, :dim]
         o = GsOpts()
         o.rows = rows
         o.in_row_bits = ib.ptr if ib else None
-        o.accumulate = 1 if prev is not None else 0
+        o.accumulate = acc
+        o.relu_dropout, o.training, o.p = int(bool(relu_dropout)), int(bool(training)), float(p)
+        o.seed, o.d_epoch, o.elem_offset = int(seed), ep.ptr, int(elem_offset)
+        o.keep_mask = km.ptr if km else None
+        o.pos_bits, o.words_per_row = (bits.ptr, wpr) if bits is not None else (None, 0)
         o.scaling = int(scaling)
-        _ck(self.lib, self.lib.gcnhip_graphsum_ex(self.ctx, g.h, C.byref(o), xin.ptr, ld, out.ptr, ld, dim), "gcnhip_graphsum_ex")
+        rc = self.lib.gcnhip_graphsum_ex(self.ctx, g.h, C.byref(o), xin.ptr, ld_in, out.ptr, ld_out, dim)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_graphsum_ex: error {rc} ({self.lib.gcnhip_error_string(rc).decode()}): {self.lib.gcnhip_last_error().decode()}")
+        res = out.download()[:, :dim]
+        return (res, bits.download()) if bits is not None else res
+
+    def graphsum_part(self, g: "Graph", x, rows=None, row_nonzero=None, prev=None, fill=np.nan, ld=None, ld_in=None, ld_out=None,
+                      relu_dropout=False, training=False, p=0.0, seed=0, epoch=0, elem_offset=0, keep_mask=None, dim=None, out=None,
+                      accumulate=None):
+        """gcnhip_graphsum_part: one operator's share of a row-partitioned aggregation (arguments as graphsum_ex)"""
+        xin, ld_in, out, ld_out, dim, ib, km, ep, _, _ = self._gs_operands(g, x, dim, ld, ld_in, ld_out, prev, fill, out, row_nonzero,
+                                                                            keep_mask, epoch, False, None)
+        acc = int(accumulate if accumulate is not None else prev is not None)
+        rc = self.lib.gcnhip_graphsum_part(self.ctx, g.h, rows, xin.ptr, ld_in, out.ptr, ld_out, dim, ib.ptr if ib else None, acc,
+                                           int(bool(relu_dropout)), int(bool(training)), float(p), int(seed), ep.ptr, int(elem_offset),
+                                           km.ptr if km else None)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_graphsum_part: error {rc} ({self.lib.gcnhip_error_string(rc).decode()}): {self.lib.gcnhip_last_error().decode()}")
         return out.download()[:, :dim]
 
     def graphsum_loss(self, g: "Graph", x, scaling, truth, rows=None, training=True, grad_row_scale=None, ld=None, epilogue=True, grad_fill=0.0):

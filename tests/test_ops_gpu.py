@@ -533,9 +533,11 @@ def test_graphsum_relu_dropout_bits_and_fused_bits_backward(dev, dim):
 @pytest.mark.parametrize("dim", [64, 128, 256])
 def test_narrow_column_slices_keep_every_epilogue(dev, oracle, gl, dim):
     """context option gs_l (8: 32-float, 4: 16-float column slices per XCD group) with the ReLU/dropout
-    epilogue that also writes the mask bits, with accumulate and with a row subset.  16-float slices hold half a mask word
-    per lane group, so with pos_bits the launch must fall back to the 64-float slices (same bits as gs_l = 0) instead of
-    leaving the words unwritten; everything else is held to the oracle and to bits == (out > 0)."""
+    epilogue that also writes the mask bits, on every row of the hub graph, and the plain aggregation under the same option.
+    16-float slices hold half a mask word per lane group, so with pos_bits the launch must fall back to the 64-float slices
+    (same bits as gs_l = 0) instead of leaving the words unwritten; everything else is held to the oracle and to
+    bits == (out > 0).  The slices with accumulate, with a row subset and with every other option of the launch record:
+    test_graphsum_options_gpu.py (paths gl8-* and gl4-*)."""
     gp, gi = hub_graph(3000, 2600, 3)             # rows above the 1024-edge split length
     n = gp.size - 1
     rng = np.random.default_rng(dim + gl)
