@@ -15,6 +15,7 @@
 #include "labels.h"
 #include "report.h"
 #include "calibration.h"
+#include "conformal.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -296,6 +297,38 @@ int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *co
     if (confidence) std::copy(r.confidence.begin(), r.confidence.end(), confidence);
     if (summary) { summary[0] = r.ece; summary[1] = r.mce; summary[2] = (double)r.rows; }
     return 0;
+}
+int gcnhost_model_conformal_fit(gcnhost_model *m, int split, const int *nodes, int n, double alpha, int method, float lam, int k_reg,
+                                float diffusion, int per_class, gcnhost_conformal *fit, float *scores, int64_t scores_cap, int64_t *n_scores) {
+    if (!m || !fit) { g_err = "gcnhost_model_conformal_fit: invalid argument"; return -1; }
+    API_TRY({
+        std::vector<float> s;
+        const ModelQueries::Conformal f = m->gcn->queries().conformal_fit(split, nodes, n, alpha, method, lam, k_reg, diffusion, per_class != 0,
+                                                                           scores || n_scores ? &s : nullptr);
+        if (scores && (int64_t)s.size() > scores_cap) throw GcnHipFailure(-1, "conformal_fit: the scores need room for " + std::to_string(s.size()) + " floats");
+        fit->method = f.method; fit->lam = f.lam; fit->k_reg = f.k_reg; fit->diffusion = f.diffusion; fit->temperature = f.temperature;
+        fit->alpha = f.alpha; fit->per_class = f.per_class ? 1 : 0;
+        std::copy(f.thresh, f.thresh + 64, fit->thresh);
+        std::copy(f.n_cal, f.n_cal + 64, fit->n_cal);
+        if (scores) std::copy(s.begin(), s.end(), scores);
+        if (n_scores) *n_scores = (int64_t)s.size();
+    })
+}
+int gcnhost_model_conformal_sets(gcnhost_model *m, const gcnhost_conformal *fit, int split, const int *nodes, int n, uint32_t *bits,
+                                 int32_t *size, int64_t *counts) {
+    if (!m || !fit) { g_err = "gcnhost_model_conformal_sets: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries::Conformal f;
+        f.method = fit->method; f.lam = fit->lam; f.k_reg = fit->k_reg; f.diffusion = fit->diffusion; f.temperature = fit->temperature;
+        f.alpha = fit->alpha; f.per_class = fit->per_class != 0;
+        std::copy(fit->thresh, fit->thresh + 64, f.thresh);
+        std::copy(fit->n_cal, fit->n_cal + 64, f.n_cal);
+        m->gcn->queries().conformal_sets(f, split, nodes, n, bits, size, counts);
+    })
+}
+int gcnhost_conformal_quantile(const float *scores, int64_t n, double alpha, const int32_t *labels, int num_classes, float *thresh,
+                               int64_t *n_cal, int64_t *k) {
+    return gcn_conformal_quantile(scores, n, alpha, labels, num_classes, thresh, n_cal, k, &g_err);
 }
 int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
                          int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {

@@ -56,6 +56,13 @@
 //                            calibration error of the TEST split, 15 bins).  The file gets the test split's reliability table at
 //                            T = 1 and at the fitted T (host/calibration.h: a summary line, then one line per bin).  Works with
 //                            GCN_LOAD_WEIGHTS and 0 epochs.  One GPU, single-label, at most 64 classes.
+//   GCN_CONFORMAL=<file>     after the test line (and after GCN_CALIBRATE's fit when both are set, at its temperature): split conformal
+//                            prediction sets (ModelQueries::conformal_fit / conformal_sets).  The threshold is fitted on the
+//                            VALIDATION split at GCN_CONFORMAL_ALPHA (default 0.1) with GCN_CONFORMAL_METHOD=aps|lac (default aps) and
+//                            GCN_CONFORMAL_DIFFUSION=<d in [0, 1]> (default 0: the scores are not blended with their neighbours'), and
+//                            one line is printed: `conformal_alpha=<a> threshold=<q> cal_rows=<n> test_coverage=<share of the labelled
+//                            test nodes whose set holds their label> test_mean_set_size=<s> test_empty=<n>`.  The file gets one line
+//                            per node of the TEST split in id order: `node size c1,c2,...`.  One GPU, single-label, at most 64 classes.
 // Node embeddings (beyond the reference; ModelQueries::embed / similar, kernels in csrc/embed.hip), after the test line and every
 // post-processing step above; stdout is unchanged.  One GPU, hidden_dim at most 256; single- and multi-label models alike:
 //   GCN_EMBED=<file>         one line per node of the dataset in id order: `node v1 ... vh`, the node's row of the hidden layer
@@ -202,6 +209,30 @@ int main(int argc, char **argv) {
         }
     }
 
+    const char *conformal_path = getenv("GCN_CONFORMAL");
+    if (conformal_path && !*conformal_path) conformal_path = nullptr;
+    double conformal_alpha = 0.1;
+    int conformal_method = ModelQueries::CONFORMAL_APS;
+    float conformal_diffusion = 0.f;
+    if (conformal_path) {
+        const char *a = getenv("GCN_CONFORMAL_ALPHA"), *meth = getenv("GCN_CONFORMAL_METHOD"), *d = getenv("GCN_CONFORMAL_DIFFUSION");
+        if (a && *a) conformal_alpha = atof(a);
+        if (d && *d) conformal_diffusion = (float)atof(d);
+        const bool lac = meth && strcmp(meth, "lac") == 0;
+        if (lac) conformal_method = ModelQueries::CONFORMAL_LAC;
+        const char *why = multilabel_path                                          ? "builds the sets of a single-label model (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                             ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > 64                                 ? "takes at most 64 classes"
+                          : !(conformal_alpha > 0.0 && conformal_alpha < 1.0)      ? "needs GCN_CONFORMAL_ALPHA in (0, 1)"
+                          : meth && *meth && !lac && strcmp(meth, "aps") != 0      ? "needs GCN_CONFORMAL_METHOD=aps or lac"
+                          : !(conformal_diffusion >= 0.f && conformal_diffusion <= 1.f) ? "needs GCN_CONFORMAL_DIFFUSION in [0, 1]"
+                                                                                   : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_CONFORMAL " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
     const char *embed_path = getenv("GCN_EMBED"), *similar_path = getenv("GCN_SIMILAR");
     if (embed_path && !*embed_path) embed_path = nullptr;
     if (similar_path && !*similar_path) similar_path = nullptr;
@@ -310,6 +341,40 @@ int main(int argc, char **argv) {
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the reliability tables to ") + calibrate_path);
                 fprintf(stderr, "gcn-hip: reliability tables of the test split written to %s%s\n", calibrate_path,
                         fit.at_bound ? " (the fit stopped on an end of its bracket: the validation split is classified perfectly)" : "");
+            }
+            if (conformal_path) {                              // one rank (checked above); after the calibration: at its temperature
+                const int C = params.output_dim, wpr = (C + 31) / 32;
+                const ModelQueries::Conformal fit =
+                    gcn.queries().conformal_fit(2, nullptr, 0, conformal_alpha, conformal_method, 0.f, 0, conformal_diffusion, false, nullptr);
+                std::vector<int> test;
+                test.reserve(1);                               // an empty split is still a query (not "every row")
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) test.push_back(i);
+                const size_t nt = test.size();
+                std::vector<uint32_t> bits(std::max<size_t>(nt, 1) * wpr);
+                std::vector<int32_t> size(std::max<size_t>(nt, 1));
+                std::vector<int64_t> counts((size_t)(4 + 3 * C + 1));
+                gcn.queries().conformal_sets(fit, 0, test.data(), (int)nt, bits.data(), size.data(), counts.data());
+                int64_t total = 0;
+                for (size_t i = 0; i < nt; i++) total += size[i];
+                printf("conformal_alpha=%g threshold=%.6f cal_rows=%lld test_coverage=%.5f test_mean_set_size=%.4f test_empty=%lld\n", conformal_alpha,
+                       fit.thresh[0], (long long)fit.n_cal[0], counts[1] ? (double)counts[2] / (double)counts[1] : 0.0,
+                       nt ? (double)total / (double)nt : 0.0, (long long)counts[3]);
+                FILE *f = fopen(conformal_path, "w");
+                bool ok = f != nullptr;
+                for (size_t i = 0; ok && i < nt; i++) {
+                    ok = fprintf(f, "%d %d", test[i], size[i]) > 0;
+                    bool first = true;
+                    for (int c = 0; ok && c < C; c++)
+                        if ((bits[i * wpr + (c >> 5)] >> (c & 31)) & 1u) {
+                            ok = fprintf(f, "%s%d", first ? " " : ",", c) > 0;
+                            first = false;
+                        }
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the prediction sets to ") + conformal_path);
+                fprintf(stderr, "gcn-hip: conformal prediction sets of the test split written to %s\n", conformal_path);
             }
             if (predict_path && multilabel_path) {             // the same, as class sets
                 const int n = gcn.local_rows();

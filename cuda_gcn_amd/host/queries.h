@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
-// evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations.  ModelQueries owns every device buffer and every
-// piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
+// sets.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -146,6 +146,41 @@ public:
     void explain(const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class, float *logit, float *hidden, float *feat,
                  int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values);
     void feature_importance(int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs, int64_t *count);
+    // Split conformal prediction (LAC: Sadinle et al., 2019; APS / RAPS: Romano et al., 2020, Angelopoulos et al., 2021; the
+    // neighbourhood diffusion of the scores: Zargarbashi et al., 2023): calibration says whether the probabilities can be trusted
+    // on average, this gives a guarantee per node — a SET of classes that holds the true one with probability >= 1 - alpha,
+    // whatever the model, from one threshold (or one per class) fitted on a held-out split.  Both calls work on the log-softmax
+    // rows predict()'s hooked forward leaves on the device with the row-local kernels of csrc/conformal.hip (formulas there),
+    // at beta = 1 / temperature(), and hold predict()'s contract: the call starts with sync(); the metrics ring, the current
+    // split, variable 6 and the captured epoch graph are untouched.  Rows: as calibration() takes them (the nodes of `split`, or
+    // with split == 0 the `nodes` query scored against the dataset's labels).  The score table [local rows x smooth_row_ld(C)]
+    // is indexed by local row; with diffusion d in (0, 1] the forward and the scores cover every row and one
+    // gcnhip_graphsum_blend launch forms S' = d . A^ . S + (1 - d) . S (no clamp) into a second table; d == 0 launches no blend.
+    // Refused with a message before any launch: a multi-label model, more than 64 classes, more than one rank, alpha outside
+    // (0, 1), a method other than CONFORMAL_LAC / CONFORMAL_APS, lam < 0, k_reg < 0, diffusion outside [0, 1]; for the fit a
+    // split without labelled rows; for the sets a NaN threshold, or a fit made at another temperature than the model's
+    // current one (the guarantee is for the scores the threshold was fitted on).
+    //   conformal_fit: gcnhip_conformal_true_scores on the listed rows, n floats to the host (the quantile is NOT selected on
+    //   the device: 93 KB for Reddit's validation split), host/conformal.h's rule.  Not per_class: thresh[c] is the one
+    //   threshold and n_cal[c] the number of scored rows, for every c < C; per_class: per label.  scores (may be NULL): the
+    //   downloaded scores in list order, -1 for a row without a label in [0, C).
+    //   conformal_sets: one gcnhip_conformal_sets_rows launch.  bits [n x ceil(C / 32)] and size [n] (by list position; either may
+    //   be NULL) and counts [4 + 3 C + 1] = {rows, labelled rows, covered, empty sets | size_hist [C + 1] | class_support [C] |
+    //   class_covered [C]}.  With bits == size == NULL only the counts cross to the host: the coverage report.
+    enum ConformalMethod { CONFORMAL_LAC = 0, CONFORMAL_APS = 1 };
+    struct Conformal {
+        int method = CONFORMAL_APS;
+        float lam = 0.f;
+        int k_reg = 0;
+        float diffusion = 0.f, temperature = 1.f;
+        double alpha = 0.1;
+        bool per_class = false;
+        float thresh[64] = {};
+        int64_t n_cal[64] = {};
+    };
+    Conformal conformal_fit(int split, const int *nodes, int n, double alpha, int method, float lam, int k_reg, float diffusion, bool per_class,
+                            std::vector<float> *scores);
+    void conformal_sets(const Conformal &fit, int split, const int *nodes, int n, uint32_t *bits, int32_t *size, int64_t *counts);
 
 private:
     HipGCN &m;
@@ -210,6 +245,12 @@ private:
     Scratch<int32_t> d_xp_rows{&arena}, d_xp_cls{&arena}, d_xp_ptr{&arena}, d_xp_nbr_row{&arena}, d_xp_count{&arena};
     Scratch<float> d_xp_logit{&arena}, d_xp_hidden{&arena}, d_xp_nbr_val{&arena}, d_xp_feat{&arena}, d_xp_z{&arena};
     Scratch<double> d_xp_acc{&arena};
+    // conformal_fit / conformal_sets: the score table and its diffused copy [local rows x ld]; the listed rows' true scores; the
+    // thresholds [64]; the sets' bits, sizes and counts
+    Scratch<float, true> d_cf_table[2] = {{&arena}, {&arena}};
+    Scratch<float> d_cf_score{&arena}, d_cf_thresh{&arena};
+    Scratch<uint32_t> d_cf_bits{&arena};
+    Scratch<int32_t> d_cf_size{&arena}, d_cf_counts{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
@@ -241,4 +282,7 @@ private:
     void explain_features(const EmbedTable &t, const int32_t *d_rows, const int32_t *d_cls, int n, size_t cap_bytes, float *host_out, double *d_acc,
                           int32_t *d_count);
     void calib_bins_download(const ScoredRows &q, float beta, int bins, int slot, int64_t *count, int64_t *correct, double *conf_sum);
+    void conformal_check(const char *what, int split, int n, double alpha, int method, float lam, int k_reg, float diffusion) const;
+    // the forward, the scores launch and the blend of both calls; returns the table the rows are read from (row stride *ld)
+    const float *conformal_table(const ScoredRows &q, int method, float lam, int k_reg, float diffusion, int *ld);
 };

@@ -403,6 +403,100 @@ class HipGCNModel:
         out.update(nll=float(sums[0] / sums[3]) if sums[3] else 0.0, temperature=t, sums=sums)
         return out
 
+    # ---- split conformal prediction: a set of classes per node that holds the true one with probability >= 1 - alpha
+    CONFORMAL_METHODS = {"lac": 0, "aps": 1}
+
+    def _conformal_query(self, what, split, nodes):
+        if split is not None and nodes is not None:
+            raise GcnHostError(f"{what}: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"{what}: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if nodes is None:
+            return None, 0, self.info()["local_rows"]          # (a split lists at most that many rows)
+        q = np.ascontiguousarray(nodes, np.int32).ravel()
+        n = q.size
+        return (q if n else np.zeros(1, np.int32)), n, n       # an empty query is still a query (not "every row")
+
+    def _conformal_struct(self, fit):
+        """the dict conformal_fit returned -> the C struct"""
+        c = self.params.output_dim
+        if c > 64:
+            raise GcnHostError(f"conformal_sets: at most 64 classes, this model has {c}")
+        s = _ConformalFit()
+        try:
+            s.method = self.CONFORMAL_METHODS[fit["method"]]
+            s.lam, s.k_reg, s.diffusion, s.temperature = float(fit["lam"]), int(fit["k_reg"]), float(fit["diffusion"]), float(fit["temperature"])
+            s.alpha, s.per_class = float(fit["alpha"]), int(bool(fit["per_class"]))
+            th = np.ascontiguousarray(fit["thresh"], np.float32).ravel()
+            nc = np.ascontiguousarray(fit["n_cal"], np.int64).ravel()
+        except (KeyError, TypeError) as e:
+            raise GcnHostError(f"conformal_sets: not a fit as conformal_fit returns it ({e!r})") from None
+        if th.size != c or nc.size != c:
+            raise GcnHostError(f"conformal_sets: the fit holds {th.size} thresholds, the model has {c} classes")
+        for j in range(c):
+            s.thresh[j], s.n_cal[j] = float(th[j]), int(nc[j])
+        return s
+
+    def conformal_fit(self, alpha=0.1, split=2, nodes=None, method="aps", lam=0.0, k_reg=0, diffusion=0.0, per_class=False, return_scores=False):
+        """Split conformal prediction: fits the threshold of the prediction sets on the labelled rows of `split` (the validation
+        split; or, with split=None, of the `nodes` query) so that a set holds the true class with probability >= 1 - alpha.
+        method "lac": the score of class j is 1 - p_j; "aps": the probability cumulated from the most likely class down to j,
+        plus the RAPS penalty lam . max(0, rank_j + 1 - k_reg).  diffusion d in (0, 1]: the scores are blended with their
+        neighbourhood mean, d . A^ . S + (1 - d) . S.  per_class: one threshold per label (class-conditional coverage).  One
+        evaluation forward, the scores formed on the GPU at the model's temperature, one float per row to the host and the
+        quantile rule of conformal_quantile() there.  Returns a dict: method, lam, k_reg, diffusion, temperature, alpha,
+        per_class, thresh (f32 [C]; +inf: too few rows for this alpha), n_cal (int64 [C]), threshold (thresh[0] unless per_class),
+        and with return_scores=True scores (f32 per listed row, -1 for a row without a label).  Single-label models, at most 64
+        classes, one rank.  Training state is not touched."""
+        if method not in self.CONFORMAL_METHODS:
+            raise GcnHostError(f"conformal_fit: the method is 'aps' or 'lac', got {method!r}")
+        q, n, listed = self._conformal_query("conformal_fit", split, nodes)
+        s = _ConformalFit()
+        sc = np.zeros(max(listed, 1), np.float32)
+        ns = C.c_int64()
+        _ck(self.lib, self.lib.gcnhost_model_conformal_fit(self.h, int(split or 0), q.ctypes.data if q is not None else None, n, float(alpha),
+                                                           self.CONFORMAL_METHODS[method], float(lam), int(k_reg), float(diffusion), int(bool(per_class)),
+                                                           C.addressof(s), sc.ctypes.data, sc.size, C.byref(ns)), "conformal_fit")
+        c = self.params.output_dim
+        out = dict(method=method, lam=float(s.lam), k_reg=int(s.k_reg), diffusion=float(s.diffusion), temperature=float(s.temperature),
+                   alpha=float(s.alpha), per_class=bool(s.per_class), thresh=np.array(s.thresh[:c], np.float32), n_cal=np.array(s.n_cal[:c], np.int64))
+        if not out["per_class"]:
+            out["threshold"] = float(out["thresh"][0])
+        if return_scores:
+            out["scores"] = sc[:ns.value].copy()
+        return out
+
+    def predict_sets(self, fit, nodes=None):
+        """(sets bool [n, C], size int32 [n]) — the conformal prediction set of every queried node under `fit` (conformal_fit's
+        dict): class j is in the set iff its score is <= the threshold.  nodes as in predict().  Refused when the model's
+        temperature is not the one the fit was made at.  Training state is not touched."""
+        from .ops import unpack_multihot
+        q, n, listed = self._conformal_query("predict_sets", None, nodes)
+        c = self.params.output_dim
+        words = np.zeros((max(listed, 1), (c + 31) // 32), np.uint32)
+        size = np.zeros(max(listed, 1), np.int32)
+        s = self._conformal_struct(fit)
+        _ck(self.lib, self.lib.gcnhost_model_conformal_sets(self.h, C.addressof(s), 0, q.ctypes.data if q is not None else None, n, words.ctypes.data,
+                                                            size.ctypes.data, None), "predict_sets")
+        return unpack_multihot(words[:listed], c), size[:listed]
+
+    def coverage(self, fit, split=3, nodes=None):
+        """How the sets of `fit` do on the labelled rows of `split` (the test split; or, with split=None, of the `nodes` query):
+        counted on the GPU, only 4 + 3 C + 1 integers cross.  Returns a dict: rows, labelled, covered (labelled rows whose set holds
+        their label), coverage = covered / labelled, mean_size (over all rows), empty, size_hist (int64 [C + 1]), class_support and
+        class_covered (int64 [C])."""
+        q, n, _ = self._conformal_query("coverage", split, nodes)
+        c = self.params.output_dim
+        cnt = np.zeros(4 + 3 * c + 1, np.int64)
+        s = self._conformal_struct(fit)
+        _ck(self.lib, self.lib.gcnhost_model_conformal_sets(self.h, C.addressof(s), int(split or 0), q.ctypes.data if q is not None else None, n, None,
+                                                            None, cnt.ctypes.data), "coverage")
+        hist = cnt[4:4 + c + 1].copy()
+        rows, labelled, covered = int(cnt[0]), int(cnt[1]), int(cnt[2])
+        return dict(rows=rows, labelled=labelled, covered=covered, coverage=covered / labelled if labelled else 0.0,
+                    mean_size=float((hist * np.arange(c + 1)).sum() / rows) if rows else 0.0, empty=int(cnt[3]), size_hist=hist,
+                    class_support=cnt[4 + c + 1:4 + 2 * c + 1].copy(), class_covered=cnt[4 + 2 * c + 1:].copy())
+
     # ---- node embeddings: the hidden layer H1 = ReLU(A^.X.W1), queried on the GPU
     METRICS = {"dot": 0, "cosine": 1}
 
@@ -615,6 +709,35 @@ def class_report(confusion=None, tp=None, fp=None, fn=None):
                                       summ.ctypes.data), "class_report")
     return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
                 macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
+
+
+class _ConformalFit(C.Structure):
+    """gcnhost_conformal of include/gcnhost.h"""
+    _fields_ = [("method", C.c_int), ("lam", C.c_float), ("k_reg", C.c_int), ("diffusion", C.c_float), ("temperature", C.c_float),
+                ("alpha", C.c_double), ("per_class", C.c_int), ("thresh", C.c_float * 64), ("n_cal", C.c_int64 * 64)]
+
+
+def conformal_quantile(scores, alpha, labels=None, num_classes=None):
+    """The threshold of split conformal prediction — host only, no GPU; the one place it is derived (host/conformal.h).  Negative
+    scores are dropped (a row without a label); with n' left, k = ceil((n' + 1)(1 - alpha)) in float64 and the threshold is the
+    k-th smallest score, +inf when k > n'.  Returns a dict: threshold (float), n_cal, k.  With labels (int [n]) and num_classes
+    the scores are grouped by label and threshold (f32 [C]), n_cal and k (int64 [C]) hold one entry per class.  alpha outside
+    (0, 1) or a NaN score raise GcnHostError."""
+    s = np.ascontiguousarray(scores, np.float32).ravel()
+    lib = _lib.gcnhost()
+    if labels is None:
+        c, lp = 1, None
+    else:
+        lab = _i32(labels).ravel()
+        if lab.size != s.size or num_classes is None:
+            raise GcnHostError(f"conformal_quantile: {lab.size} labels for {s.size} scores (and num_classes must be given)")
+        c, lp = int(num_classes), (lab if lab.size else np.zeros(1, np.int32)).ctypes.data
+    th, nc, k = np.zeros(max(c, 1), np.float32), np.zeros(max(c, 1), np.int64), np.zeros(max(c, 1), np.int64)
+    sp = (s if s.size else np.zeros(1, np.float32)).ctypes.data
+    _ck(lib, lib.gcnhost_conformal_quantile(sp, s.size, float(alpha), lp, c, th.ctypes.data, nc.ctypes.data, k.ctypes.data), "conformal_quantile")
+    if labels is None:
+        return dict(threshold=float(th[0]), n_cal=int(nc[0]), k=int(k[0]))
+    return dict(threshold=th, n_cal=nc, k=k)
 
 
 def calibration_report(count, correct, conf_sum):

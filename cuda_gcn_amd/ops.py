@@ -395,6 +395,45 @@ class Device:
             raise GcnHipError(f"gcnhip_calib_scale_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return ob.download(), pb.download()[:n_table]
 
+    # ---- split conformal prediction sets (csrc/conformal.hip)
+    def conformal_scores(self, logp, beta, method, lam=0.0, k_reg=0, rows=None, ld=None, ld_out=None, fill=np.nan, n=None):
+        """gcnhip_conformal_scores: out [n_table, ld_out] — rows not listed and padding columns keep `fill`.  logp f32 [n_table, C]
+        (uploaded with row stride ld, NaN padding); method 0 lac, 1 aps; rows: the listed rows (None: rows 0 .. n - 1)"""
+        lb, _, rb, n_table, c, listed = self._calib_inputs(logp, ld, None, rows)
+        ld_out = ld_out or c
+        ob = self.buf(np.full((max(n_table, 1), ld_out), fill, np.float32))
+        rc = self.lib.gcnhip_conformal_scores(self.ctx, lb.ptr, ld or c, n_table, rb.ptr if rb else None, listed if n is None else int(n), c, float(beta),
+                                              int(method), float(lam), int(k_reg), ob.ptr, ld_out)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_conformal_scores: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return ob.download()[:n_table]
+
+    def conformal_true_scores(self, table, truth, rows=None, ld=None, fill=np.nan):
+        """gcnhip_conformal_true_scores: f32 [n listed] = table[r, truth[r]], -1 for an id outside the table or a truth outside
+        [0, C).  table f32 [n_table, C] (uploaded with row stride ld, NaN padding)"""
+        tb, hb, rb, n_table, c, listed = self._calib_inputs(table, ld, truth, rows)
+        sb = self.buf(np.full(max(listed, 1), fill, np.float32))
+        rc = self.lib.gcnhip_conformal_true_scores(self.ctx, tb.ptr, ld or c, hb.ptr, n_table, rb.ptr if rb else None, listed, c, sb.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_conformal_true_scores: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return sb.download()[:listed]
+
+    def conformal_sets_rows(self, table, thresh, truth=None, rows=None, ld=None, bits=True, size=True, counts=True):
+        """gcnhip_conformal_sets_rows: (sets bool [n listed, C], size int32 [n listed], counts int32 [4 + 3 C + 1]), None for an
+        output that was not asked for; the outputs are uploaded as garbage — the launch zeroes or overwrites them.  thresh f32 [C]"""
+        tb, hb, rb, n_table, c, listed = self._calib_inputs(table, ld, truth, rows)
+        wpr = (c + 31) // 32
+        th = self.buf(np.ascontiguousarray(thresh, np.float32))
+        bb = self.buf(np.full((max(listed, 1), wpr), 0xdeadbeef, np.uint32)) if bits else None
+        zb = self.buf(np.full(max(listed, 1), -777, np.int32)) if size else None
+        cb = self.buf(np.full(4 + 3 * c + 1, 12345, np.int32)) if counts else None
+        rc = self.lib.gcnhip_conformal_sets_rows(self.ctx, tb.ptr, ld or c, n_table, rb.ptr if rb else None, listed, c, th.ptr, hb.ptr if hb else None,
+                                                 bb.ptr if bb else None, zb.ptr if zb else None, cb.ptr if cb else None)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_conformal_sets_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return (unpack_multihot(bb.download()[:listed], c) if bits else None, zb.download()[:listed] if size else None,
+                cb.download() if counts else None)
+
     # ---- node embeddings (csrc/embed.hip): the table is uploaded with row stride ld and NaN padding
     def _embed_inputs(self, table, ld, inv_norm):
         table = np.ascontiguousarray(table, np.float32)
@@ -1124,7 +1163,7 @@ def unpack_multihot(words, c):
     """uint32 [n, ceil(C / 32)] -> bool [n, C]"""
     w = np.ascontiguousarray(words, np.uint32)
     bits = (w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
-    return bits.reshape(w.shape[0], -1)[:, :c].astype(bool)
+    return bits.reshape(w.shape[0], w.shape[1] * 32)[:, :c].astype(bool)      # (-1 cannot be inferred for zero rows)
 
 
 class Graph:

@@ -235,6 +235,30 @@ int gcnhip_calib_bins_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int
                            int num_classes, float beta, int bins, int32_t *d_count, int32_t *d_correct, double *d_conf_sum);
 int gcnhip_calib_scale_rows(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, float beta,
                             float *out_logp, int ld_out, float *d_prob);
+/* ---- split conformal prediction sets (conformal.hip; beyond the reference: a set of classes per node with a coverage guarantee) ----
+ * The conventions of the calibration kernels above: a wave per row, lane j on class j (1 <= num_classes <= 64, rows of any stride
+ * >= num_classes), fp contract(off), rows listed as d_rows[i], i < n, or 0 .. n - 1 when d_rows == NULL (then n <= n_table), ids
+ * outside [0, n_table) skipped; no float atomics, so two launches give the same bits; no launch allocates or synchronises; anything
+ * refused returns -1 with a message naming the entry point (gcnhip_last_error).  p = softmax(beta . l) of l = logp[r, :] as above.
+ * rank_j = #{k : l_k > l_j, or l_k == l_j and k < j}, on the f32 inputs: exact, ties to the lower class as in predict.
+ * gcnhip_conformal_scores: out[r, j] for every listed row r, j < num_classes (columns past it and unlisted rows are not written;
+ *   out is indexed by table row so that gcnhip_graphsum_blend can gather it).  method 0 (LAC): 1 - p_j.  method 1 (APS,
+ *   non-randomised, inclusive): cum_j + lam . max(0, rank_j + 1 - k_reg), cum_j = the sum of p_k over rank_k <= rank_j in one fixed
+ *   tree of at most six additions per result, clamped to 1, and exactly 1.0f for the last-ranked class (a threshold >= 1 gives the
+ *   full set whatever the last ulp of sum p); lam >= 0 and k_reg >= 0 are the RAPS penalty, lam = 0 plain APS.
+ * gcnhip_conformal_true_scores: d_score[i] = table[r, truth[r]] for list position i, or -1.f when r is outside the table or
+ *   truth[r] outside [0, num_classes) (scores are never negative); repeats are scored as often as listed.
+ * gcnhip_conformal_sets_rows: class j is in the set of row r iff table[r, j] <= d_thresh[j] (d_thresh [num_classes]; +inf allowed,
+ *   NaN is the caller's to refuse).  By list position: d_bits [n x ceil(num_classes / 32)] (bit (j & 31) of word j >> 5; zero for a
+ *   skipped id) and d_size [n] (-1 for a skipped id); either may be NULL.  d_counts (may be NULL; int32 [4 + 3 C + 1], zeroed on the
+ *   stream first, integer adds only) = {rows in the table, labelled rows, covered, empty sets | size_hist [C + 1] | class_support
+ *   [C] | class_covered [C]}; truth may be NULL (then no row is labelled). */
+int gcnhip_conformal_scores(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, float beta,
+                            int method, float lam, int k_reg, float *out, int ld_out);
+int gcnhip_conformal_true_scores(gcnhip_ctx *ctx, const float *table, int ld, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
+                                 int num_classes, float *d_score);
+int gcnhip_conformal_sets_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, const int32_t *d_rows, int n, int num_classes,
+                               const float *d_thresh, const int32_t *truth, uint32_t *d_bits, int32_t *d_size, int32_t *d_counts);
 /* ---- node embeddings (embed.hip; beyond the reference: what a GCN learns, taken out without leaving the device) ----
  * All entry points read an f32 table [n_table x ld] with 1 <= dim <= 256 and dim <= ld, rows of any stride and alignment;
  * columns [dim, ld) are never read as values.  Score of rows (q, c): their f32 dot product (inv_norm == NULL, metric "dot"),

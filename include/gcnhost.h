@@ -223,6 +223,40 @@ int gcnhost_model_set_temperature(gcnhost_model *m, float temperature);
 int gcnhost_model_temperature(gcnhost_model *m, float *temperature);
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary);
+/* Split conformal prediction sets (beyond the reference; ModelQueries::conformal_fit / conformal_sets, kernels in csrc/conformal.hip):
+ * a set of classes per node that holds the true class with probability >= 1 - alpha, from a threshold fitted on a held-out split.
+ * Both model calls hold gcnhost_model_predict's contract (the call synchronises first, the training state is untouched) and work at
+ * the model's current temperature.  Single-label models, at most 64 classes, one rank, alpha in (0, 1), method 0 (LAC: 1 - p) or
+ * 1 (APS: the cumulated probability down to the class, plus lam . max(0, rank + 1 - k_reg)), lam >= 0, k_reg >= 0, diffusion in [0, 1]
+ * (the scores blended with their neighbourhood mean, d . A^ . S + (1 - d) . S): anything else is refused with a message before any launch.
+ *
+ * gcnhost_model_conformal_fit: the rows of `split` (1 train, 2 validation, 3 test) or, with split == 0, the `nodes` query (n dataset ids;
+ * NULL: every row) scored against the dataset's labels.  Fills *fit: thresh / n_cal [64] — without per_class the one threshold and the
+ * number of scored rows in every entry below the class count, with it one per label.  scores (may be NULL; room for scores_cap floats):
+ * the true-class score of every listed row, -1 for a row without a label; *n_scores (may be NULL) their number.  A split without
+ * labelled rows is refused.
+ * gcnhost_model_conformal_sets: the sets of the listed rows under *fit.  bits [n x ceil(C / 32)] and size [n] by list position (either may
+ * be NULL), counts (may be NULL) [4 + 3 C + 1] = {rows, labelled rows, covered, empty sets | size_hist [C + 1] | class_support [C] |
+ * class_covered [C]}.  Refused: a NaN threshold, and a fit made at another temperature than the model's current one.
+ * gcnhost_conformal_quantile, host only (host/conformal.h): negative scores are dropped; with n' left, k = ceil((n' + 1)(1 - alpha)) in
+ * double and the threshold is the k-th smallest score, +inf when k > n'.  labels == NULL: thresh / n_cal / k hold one entry;
+ * else scores are grouped by labels[i] in [0, num_classes) and each holds num_classes entries.  n_cal and k may be NULL. */
+typedef struct gcnhost_conformal {
+    int method;
+    float lam;
+    int k_reg;
+    float diffusion, temperature;
+    double alpha;
+    int per_class;
+    float thresh[64];
+    int64_t n_cal[64];
+} gcnhost_conformal;
+int gcnhost_model_conformal_fit(gcnhost_model *m, int split, const int *nodes, int n, double alpha, int method, float lam, int k_reg,
+                                float diffusion, int per_class, gcnhost_conformal *fit, float *scores, int64_t scores_cap, int64_t *n_scores);
+int gcnhost_model_conformal_sets(gcnhost_model *m, const gcnhost_conformal *fit, int split, const int *nodes, int n, uint32_t *bits,
+                                 int32_t *size, int64_t *counts);
+int gcnhost_conformal_quantile(const float *scores, int64_t n, double alpha, const int32_t *labels, int num_classes, float *thresh,
+                               int64_t *n_cal, int64_t *k);
 /* Node embeddings (ModelQueries, host/queries.h; kernels in csrc/embed.hip): the hidden matrix H1 = ReLU(A^.X.W1) of one evaluation
  * forward with the current weights (no dropout), as variable 3 stores it (a factored model keeps dinv[r] on row r; cosine scores
  * and normalised rows do not depend on it), queried on the device.  Ids are DATASET node ids.  predict's contract: training state
