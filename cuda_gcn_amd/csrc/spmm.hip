@@ -380,7 +380,7 @@ static int spmm_fwd_impl(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals,
     // narrow 16-byte aligned rows (hidden <= 64; the reference's default is 16): the shuffle-free kernel (spmm_sparse.h)
     // (small inputs keep the general kernel: at a few microseconds per launch the shorter program wins — cora-syn / citeseer-syn
     //  3.3 / 3.5 us against 3.3 / 4.4; pubmed-syn and up: 7.7 against 8.9 us, 2 M rows: 0.81 against 0.95 ms)
-    const bool narrow = vec && units <= 16 && f->nnz * 4 < 0x7FFFFFFF && !c->opt.spmm_general && (f->nnz >= SPMM_NARROW_MIN_NNZ || c->opt.spmm_general < 0);
+    const bool narrow = vec && units <= 16 && f->nnz * 4 < 0x7FFFFFFF && c->opt.spmm_general <= 0 && (f->nnz >= SPMM_NARROW_MIN_NNZ || c->opt.spmm_general < 0);
     if (narrow) {
         if (units <= 1) spmm_csr_fwd_q_kernel<1><<<grid, 256, 0, c->stream>>>(a);
         else if (units <= 2) spmm_csr_fwd_q_kernel<2><<<grid, 256, 0, c->stream>>>(a);
@@ -556,7 +556,7 @@ int gcnhip_spmm_bwd(gcnhip_ctx *c, const gcnhip_feat *f, const float *vals, cons
     const bool vec = ld_dout % 4 == 0 && aligned16(dout);
     const int units = vec ? (p + 3) / 4 : p;
     a.nnz_bytes = (int)std::min<int64_t>(f->nnz * 4, 0x7FFFFFFF);
-    if (vec && units <= 16 && a.csc_val && f->nnz * 4 < 0x7FFFFFFF && !c->opt.spmm_general &&
+    if (vec && units <= 16 && a.csc_val && f->nnz * 4 < 0x7FFFFFFF && c->opt.spmm_general <= 0 &&
         (f->nnz >= SPMM_NARROW_MIN_NNZ || c->opt.spmm_general < 0)) {                            // narrow rows: the shuffle-free kernel
 #define SPQ(L_)                                                                                             \
     do {                                                                                                    \

@@ -706,78 +706,122 @@ class Device:
                                                      bt.ptr, bits.shape[1], rs.ptr if rs else None), "gcnhip_matmul_bwd_ex")
         return da.download(), db.download()[:, :p]
 
-    def spmm_fwd(self, f: "Feat", w, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, keep_mask=None, vals=None, ld_w=None, ld_out=None):
+    # ---- the first-layer products.  Beside the operands: vals (a value array of the caller's instead of the object's own), a
+    # row stride per table, shift = {operand name: floats} (that operand starts so many floats into its allocation: an
+    # address that is not a multiple of 16 bytes), whole / fill (return the WHOLE written table, uploaded as `fill`, padding
+    # columns included, as graphsum_blend does; with it `.base` of the result is the flat allocation: `shift` floats in
+    # front of the table and SLACK_ROWS rows behind it, which no launch may touch)
+    SLACK_ROWS = 2
+
+    def _operand(self, arr, ld, shift=0, fill=np.nan):
+        """a 2-D float table with row stride ld (padding = fill), `shift` floats into an allocation with SLACK_ROWS rows of slack
+        behind it -> (Buf, device address of element [0, 0], floats of the table)"""
+        arr = np.asarray(arr, np.float32)
+        rows, cols = arr.shape
+        flat = np.full(shift + (rows + self.SLACK_ROWS) * ld + 4, fill, np.float32)
+        table = flat[shift:shift + rows * ld].reshape(rows, ld)
+        table[:, :cols] = arr
+        b = self.buf(flat)
+        return b, b.ptr + 4 * shift, rows * ld
+
+    @staticmethod
+    def _table(buf, shift, rows, ld, cols, whole):
+        flat = buf.download()
+        table = flat[shift:shift + rows * ld].reshape(rows, ld)
+        return table if whole else table[:, :cols].copy()
+
+    def _vals(self, f, vals, shift):
+        if vals is None:
+            return None, f.values_ptr
+        b, ptr, _ = self._operand(np.ascontiguousarray(vals, np.float32).reshape(1, -1), max(int(np.size(vals)), 1), shift)
+        return b, ptr
+
+    def spmm_fwd(self, f: "Feat", w, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, keep_mask=None, vals=None, ld_w=None, ld_out=None,
+                 whole=False, fill=np.nan, shift=None):
         w = np.asarray(w, np.float32)
         p = w.shape[1]
         ld_w = ld_w or p
         ld_out = ld_out or p
-        wb = self.padded(w, ld_w)
-        out = self.buf(np.full((f.n_rows, ld_out), np.nan, np.float32))
+        sh = shift or {}
+        wb, wptr, _ = self._operand(w, ld_w, sh.get("w", 0))
+        out, optr, _ = self._operand(np.zeros((f.n_rows, 0), np.float32), ld_out, sh.get("out", 0), fill)
         ep = self.buf(np.array([epoch], np.uint32))
         km = self.buf(np.ascontiguousarray(keep_mask, np.uint8)) if keep_mask is not None else None
-        vb = self.buf(np.ascontiguousarray(vals, np.float32)) if vals is not None else None
-        vptr = vb.ptr if vb else f.values_ptr
-        _ck(self.lib, self.lib.gcnhip_spmm_fwd(self.ctx, f.h, vptr, wb.ptr, ld_w, out.ptr, ld_out, p, p_drop, seed, ep.ptr,
+        vb, vptr = self._vals(f, vals, sh.get("vals", 0))
+        _ck(self.lib, self.lib.gcnhip_spmm_fwd(self.ctx, f.h, vptr, wptr, ld_w, optr, ld_out, p, p_drop, seed, ep.ptr,
                                                 nnz_offset, km.ptr if km else None), "gcnhip_spmm_fwd")
-        return out.download()[:, :p]
+        return self._table(out, sh.get("out", 0), f.n_rows, ld_out, p, whole)
 
-    def spmm_fwd_relu(self, f: "Feat", w, ld_w=None, ld_out=None):
+    def spmm_fwd_relu(self, f: "Feat", w, ld_w=None, ld_out=None, vals=None, whole=False, fill=np.nan, shift=None):
         """ReLU(X . w) through gcnhip_spmm_fwd_relu (the evaluation form on an aggregated feature object)"""
         w = np.asarray(w, np.float32)
         p = w.shape[1]
         ld_w, ld_out = ld_w or p, ld_out or p
-        wb = self.padded(w, ld_w)
-        out = self.buf(np.full((f.n_rows, ld_out), np.nan, np.float32))
-        _ck(self.lib, self.lib.gcnhip_spmm_fwd_relu(self.ctx, f.h, f.values_ptr, wb.ptr, ld_w, out.ptr, ld_out, p), "gcnhip_spmm_fwd_relu")
-        return out.download()[:, :p]
+        sh = shift or {}
+        wb, wptr, _ = self._operand(w, ld_w, sh.get("w", 0))
+        out, optr, _ = self._operand(np.zeros((f.n_rows, 0), np.float32), ld_out, sh.get("out", 0), fill)
+        vb, vptr = self._vals(f, vals, sh.get("vals", 0))
+        _ck(self.lib, self.lib.gcnhip_spmm_fwd_relu(self.ctx, f.h, vptr, wptr, ld_w, optr, ld_out, p), "gcnhip_spmm_fwd_relu")
+        return self._table(out, sh.get("out", 0), f.n_rows, ld_out, p, whole)
 
-    def spmm_fwd_relu_matmul(self, f: "Feat", w, w2, ld_z=None):
+    def spmm_fwd_relu_matmul(self, f: "Feat", w, w2, ld_z=None, vals=None, ld_w=None, ld_w2=None, whole=False, fill=np.nan, shift=None):
         """gcnhip_spmm_fwd_relu_matmul: ReLU(X . w) . w2 in one launch; returns None when the fused form is not available"""
         w, w2 = np.asarray(w, np.float32), np.asarray(w2, np.float32)
         p, p2 = w.shape[1], w2.shape[1]
         ld_z = ld_z or (p2 + 3) // 4 * 4
-        wb, w2b = self.buf(w), self.padded(w2, ld_z)
-        z = self.buf(np.full((f.n_rows, ld_z), np.nan, np.float32))
-        rc = self.lib.gcnhip_spmm_fwd_relu_matmul(self.ctx, f.h, f.values_ptr, wb.ptr, p, p, w2b.ptr, ld_z, p2, z.ptr, ld_z)
+        ld_w, ld_w2 = ld_w or p, ld_w2 or ld_z
+        sh = shift or {}
+        wb, wptr, _ = self._operand(w, ld_w, sh.get("w", 0))
+        w2b, w2ptr, _ = self._operand(w2, ld_w2, sh.get("w2", 0))
+        z, zptr, _ = self._operand(np.zeros((f.n_rows, 0), np.float32), ld_z, sh.get("out", 0), fill)
+        vb, vptr = self._vals(f, vals, sh.get("vals", 0))
+        rc = self.lib.gcnhip_spmm_fwd_relu_matmul(self.ctx, f.h, vptr, wptr, ld_w, p, w2ptr, ld_w2, p2, zptr, ld_z)
         if rc == -2:
             return None
         _ck(self.lib, rc, "gcnhip_spmm_fwd_relu_matmul")
-        return z.download()[:, :p2]
+        return self._table(z, sh.get("out", 0), f.n_rows, ld_z, p2, whole)
 
-    def spmm_bwd(self, f: "Feat", dout, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, keep_mask=None, vals=None, ld_dout=None, ld_dw=None):
+    def spmm_bwd(self, f: "Feat", dout, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, keep_mask=None, vals=None, ld_dout=None, ld_dw=None,
+                 whole=False, fill=np.nan, shift=None):
         dout = np.asarray(dout, np.float32)
         p = dout.shape[1]
         ld_dout = ld_dout or p
         ld_dw = ld_dw or p
-        db = self.padded(dout, ld_dout)
-        dw = self.buf(np.full((f.n_cols, ld_dw), np.nan, np.float32))
+        sh = shift or {}
+        db, dptr, _ = self._operand(dout, ld_dout, sh.get("dout", 0))
+        dw, wptr, _ = self._operand(np.zeros((f.n_cols, 0), np.float32), ld_dw, sh.get("out", 0), fill)
         ep = self.buf(np.array([epoch], np.uint32))
         km = self.buf(np.ascontiguousarray(keep_mask, np.uint8)) if keep_mask is not None else None
-        vb = self.buf(np.ascontiguousarray(vals, np.float32)) if vals is not None else None
-        vptr = vb.ptr if vb else f.values_ptr
-        _ck(self.lib, self.lib.gcnhip_spmm_bwd(self.ctx, f.h, vptr, db.ptr, ld_dout, dw.ptr, ld_dw, p, p_drop, seed, ep.ptr,
+        vb, vptr = self._vals(f, vals, sh.get("vals", 0))
+        _ck(self.lib, self.lib.gcnhip_spmm_bwd(self.ctx, f.h, vptr, dptr, ld_dout, wptr, ld_dw, p, p_drop, seed, ep.ptr,
                                                 nnz_offset, km.ptr if km else None), "gcnhip_spmm_bwd")
-        return dw.download()[:, :p]
+        return self._table(dw, sh.get("out", 0), f.n_cols, ld_dw, p, whole)
 
     def spmm_bwd_plan(self, f: "Feat", p):
         rps, ns = C.c_int(), C.c_int()
         _ck(self.lib, self.lib.gcnhip_spmm_bwd_plan(self.ctx, f.h, p, C.byref(rps), C.byref(ns)), "gcnhip_spmm_bwd_plan")
         return rps.value, ns.value
 
-    def spmm_bwd_parts(self, f: "Feat", dout, cuts, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, order=None, make_first=True):
+    def spmm_bwd_parts(self, f: "Feat", dout, cuts, p_drop=0.0, seed=0, epoch=0, nnz_offset=0, order=None, make_first=True, keep_mask=None,
+                       vals=None, ld_dout=None, ld_dw=None, whole=False, fill=np.nan, shift=None):
         """the weight gradient as gcnhip_spmm_bwd_part calls on the split ranges between `cuts` (in `order`), then _finish;
         make_first=False: no part makes the keep decisions (a forward with the same arguments left them in the feature object)"""
         dout = np.asarray(dout, np.float32)
         p = dout.shape[1]
-        db = self.padded(dout, p)
-        dw = self.buf(np.full((f.n_cols, p), np.nan, np.float32))
+        ld_dout, ld_dw = ld_dout or p, ld_dw or p
+        sh = shift or {}
+        db, dptr, _ = self._operand(dout, ld_dout, sh.get("dout", 0))
+        dw, wptr, _ = self._operand(np.zeros((f.n_cols, 0), np.float32), ld_dw, sh.get("out", 0), fill)
         ep = self.buf(np.array([epoch], np.uint32))
+        km = self.buf(np.ascontiguousarray(keep_mask, np.uint8)) if keep_mask is not None else None
+        vb, vptr = self._vals(f, vals, sh.get("vals", 0))
         ranges = list(zip(cuts[:-1], cuts[1:]))
         for k, i in enumerate(order if order is not None else range(len(ranges))):
-            _ck(self.lib, self.lib.gcnhip_spmm_bwd_part(self.ctx, f.h, f.values_ptr, db.ptr, p, p, p_drop, seed, ep.ptr, nnz_offset, None,
-                                                         ranges[i][0], ranges[i][1], 1 if (k == 0 and make_first) else 0), "gcnhip_spmm_bwd_part")
-        _ck(self.lib, self.lib.gcnhip_spmm_bwd_finish(self.ctx, f.h, dw.ptr, p, p), "gcnhip_spmm_bwd_finish")
-        return dw.download()
+            _ck(self.lib, self.lib.gcnhip_spmm_bwd_part(self.ctx, f.h, vptr, dptr, ld_dout, p, p_drop, seed, ep.ptr, nnz_offset,
+                                                         km.ptr if km else None, ranges[i][0], ranges[i][1],
+                                                         1 if (k == 0 and make_first) else 0), "gcnhip_spmm_bwd_part")
+        _ck(self.lib, self.lib.gcnhip_spmm_bwd_finish(self.ctx, f.h, wptr, ld_dw, p), "gcnhip_spmm_bwd_finish")
+        return self._table(dw, sh.get("out", 0), f.n_cols, ld_dw, p, whole)
 
     def matmul_fwd(self, a, b, lda=None, ldb=None, ldc=None):
         a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
@@ -1291,6 +1335,13 @@ class Feat:
         self.h = h
         self.values_ptr = dev.lib.gcnhip_feat_values(h)
         self.dense = bool(dev.lib.gcnhip_feat_is_dense(h))
+
+    def scale_rows(self, scale):
+        """gcnhip_feat_scale_rows: X[r, :] *= scale[r] in every copy the object keeps (values, the padded copy, the CSC copy)"""
+        scale = np.ascontiguousarray(scale, np.float32).ravel()
+        assert scale.size == self.n_rows
+        sb = self.dev.buf(scale if scale.size else np.zeros(1, np.float32))
+        _ck(self.dev.lib, self.dev.lib.gcnhip_feat_scale_rows(self.dev.ctx, self.h, sb.ptr), "gcnhip_feat_scale_rows")
 
     def free(self):
         if self.h and self.dev.ctx:
