@@ -16,6 +16,7 @@
 #include "report.h"
 #include "calibration.h"
 #include "conformal.h"
+#include "ranking.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -329,6 +330,28 @@ int gcnhost_model_conformal_sets(gcnhost_model *m, const gcnhost_conformal *fit,
 int gcnhost_conformal_quantile(const float *scores, int64_t n, double alpha, const int32_t *labels, int num_classes, float *thresh,
                                int64_t *n_cal, int64_t *k) {
     return gcn_conformal_quantile(scores, n, alpha, labels, num_classes, thresh, n_cal, k, &g_err);
+}
+int gcnhost_model_ranking(gcnhost_model *m, int split, const int *nodes, int n, size_t scratch_bytes, int64_t *u2, double *ap_sum, int64_t *pos,
+                          int64_t *neg, int64_t *invalid, int64_t *unlabelled, int64_t *rows, float *scores, int64_t scores_cap) {
+    if (!m || !u2 || !ap_sum || !pos || !neg || !invalid) { g_err = "gcnhost_model_ranking: invalid argument"; return -1; }
+    API_TRY({
+        std::vector<float> s;
+        const int64_t listed = m->gcn->queries().ranking(split, nodes, n, scratch_bytes, u2, ap_sum, pos, neg, invalid, unlabelled, scores ? &s : nullptr);
+        if (scores && (int64_t)s.size() > scores_cap) throw GcnHipFailure(-1, "ranking: the scores need room for " + std::to_string(s.size()) + " floats");
+        if (scores) std::copy(s.begin(), s.end(), scores);
+        if (rows) *rows = listed;
+    })
+}
+int gcnhost_ranking_report(int num_classes, const int64_t *u2, const double *ap_sum, const int64_t *pos, const int64_t *neg, double *auc, double *ap,
+                           int32_t *auc_defined, int32_t *ap_defined, double *summary) {
+    RankingReport r;
+    if (gcn_ranking_report(num_classes, u2, ap_sum, pos, neg, &r, &g_err) != 0) return -1;
+    if (auc) std::copy(r.auc.begin(), r.auc.end(), auc);
+    if (ap) std::copy(r.ap.begin(), r.ap.end(), ap);
+    if (auc_defined) std::copy(r.auc_defined.begin(), r.auc_defined.end(), auc_defined);
+    if (ap_defined) std::copy(r.ap_defined.begin(), r.ap_defined.end(), ap_defined);
+    if (summary) { summary[0] = r.macro_auc; summary[1] = r.macro_ap; summary[2] = r.weighted_auc; summary[3] = r.weighted_ap; summary[4] = (double)r.classes_defined; }
+    return 0;
 }
 int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
                          int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {

@@ -63,6 +63,13 @@
 //                            one line is printed: `conformal_alpha=<a> threshold=<q> cal_rows=<n> test_coverage=<share of the labelled
 //                            test nodes whose set holds their label> test_mean_set_size=<s> test_empty=<n>`.  The file gets one line
 //                            per node of the TEST split in id order: `node size c1,c2,...`.  One GPU, single-label, at most 64 classes.
+//   GCN_RANKING=<file>       after the test line (and after GCN_CALIBRATE's fit when both are set, at its temperature): per-class ROC-AUC
+//                            and average precision of the TEST split without a decision threshold (ModelQueries::ranking: keys, a
+//                            segmented sort and binary searches on the GPU; host/ranking.h derives the metrics).  The file gets one line
+//                            per class, `class <c> pos <P> neg <N> auc <a> ap <p>` with `undefined` in place of a value the class does
+//                            not have (no positive, or no negative), then `macro_auc <x> macro_ap <y> weighted_auc <u> weighted_ap <v>
+//                            classes <k>` (the means over the defined classes).  stdout and the GCN_REPORT file are unchanged.  One GPU;
+//                            at most 64 classes, or 256 on a multi-label model (scored on its logits).
 // Node embeddings (beyond the reference; ModelQueries::embed / similar, kernels in csrc/embed.hip), after the test line and every
 // post-processing step above; stdout is unchanged.  One GPU, hidden_dim at most 256; single- and multi-label models alike:
 //   GCN_EMBED=<file>         one line per node of the dataset in id order: `node v1 ... vh`, the node's row of the hidden layer
@@ -105,6 +112,7 @@
 #include "hip_check.h"
 #include "labels.h"
 #include "parser.h"
+#include "ranking.h"
 #include "report.h"
 
 static int env_int(const char *name, int dflt) {
@@ -229,6 +237,18 @@ int main(int argc, char **argv) {
                                                                                    : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_CONFORMAL " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *ranking_path = getenv("GCN_RANKING");
+    if (ranking_path && !*ranking_path) ranking_path = nullptr;
+    if (ranking_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1                              ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > (multilabel_path ? 256 : 64)      ? "takes at most 64 classes (256 on a multi-label model)"
+                                                                                  : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_RANKING " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -375,6 +395,20 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the prediction sets to ") + conformal_path);
                 fprintf(stderr, "gcn-hip: conformal prediction sets of the test split written to %s\n", conformal_path);
+            }
+            if (ranking_path) {                                // one rank (checked above); after the calibration: at its temperature
+                const int C = params.output_dim;
+                std::vector<int64_t> u2(C), pos(C), neg(C), invalid(C);
+                std::vector<double> ap_sum(C);
+                int64_t unlabelled = 0;
+                gcn.queries().ranking(3, nullptr, 0, 0, u2.data(), ap_sum.data(), pos.data(), neg.data(), invalid.data(), &unlabelled, nullptr);
+                RankingReport rep;
+                std::string err;
+                if (gcn_ranking_report(C, u2.data(), ap_sum.data(), pos.data(), neg.data(), &rep, &err) != 0 ||
+                    gcn_ranking_report_write(ranking_path, C, rep, pos.data(), neg.data(), &err) != 0)
+                    throw GcnHipFailure(-1, "gcn-hip: GCN_RANKING: " + err);
+                fprintf(stderr, "gcn-hip: ranking metrics of the test split (macro AUC %.5f, macro AP %.5f over %d classes) written to %s\n", rep.macro_auc,
+                        rep.macro_ap, rep.classes_defined, ranking_path);
             }
             if (predict_path && multilabel_path) {             // the same, as class sets
                 const int n = gcn.local_rows();

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -181,6 +181,23 @@ public:
     Conformal conformal_fit(int split, const int *nodes, int n, double alpha, int method, float lam, int k_reg, float diffusion, bool per_class,
                             std::vector<float> *scores);
     void conformal_sets(const Conformal &fit, int split, const int *nodes, int n, uint32_t *bits, int32_t *size, int64_t *counts);
+    // Ranking metrics: per-class ROC-AUC and average precision, the threshold-free scores of multi-label and imbalanced tasks
+    // (csrc/ranking.hip: keys, a segmented sort, binary searches; formulas there and in host/ranking.h).  Rows as evaluate()
+    // takes them (the nodes of `split`, or with split == 0 the `nodes` query scored against the dataset's labels, repeats
+    // counted as often as listed).  predict()'s contract: the call starts with sync(); the metrics ring, the current split,
+    // variable 6 and the captured epoch graph are untouched.  One forward: a multi-label model's logits go to scratch and are
+    // scored as they are (monotone in the sigmoid, which would saturate into ties); a single-label model is scored one-vs-rest
+    // on the log-softmax rows at the current temperature — exactly predict()'s logp: at T != 1 gcnhip_calib_scale_rows runs
+    // on every queried row once.  A row whose label is outside [0, C) is in no class's counts (*unlabelled); a NaN score is in
+    // neither P nor N of its class (invalid[c]).  The classes run in batches whose two key tables and sort scratch (4 x 4
+    // bytes per listed row and class) fit scratch_bytes (0: 256 MiB), at least one class per batch; every batching gives the
+    // same bits.  u2 [C] (int64, exact), ap_sum [C] (float64), pos / neg / invalid [C] and *unlabelled are all that crosses
+    // to the host — 5 C + 1 numbers — unless scores != NULL: then also the [n x C] f32 score rows in list order, gathered on
+    // the device (ROC / PR curves, tests).  Returns the number of listed rows.  Refused with a message before any launch:
+    // more than one rank (the sort would need a gather), more than 64 (single-label) or 256 (multi-label) classes, a split
+    // outside 0..3, more than 2^24 listed rows.
+    int64_t ranking(int split, const int *nodes, int n, size_t scratch_bytes, int64_t *u2, double *ap_sum, int64_t *pos, int64_t *neg, int64_t *invalid,
+                    int64_t *unlabelled, std::vector<float> *scores);
 
 private:
     HipGCN &m;
@@ -251,6 +268,14 @@ private:
     Scratch<float> d_cf_score{&arena}, d_cf_thresh{&arena};
     Scratch<uint32_t> d_cf_bits{&arena};
     Scratch<int32_t> d_cf_size{&arena}, d_cf_counts{&arena};
+    // ranking: a batch's key tables and sort scratch; the counts {pos | neg | invalid [C] | unlabelled}; {ap_sum | u2} [2 C]; the
+    // block partials of gcnhip_rank_stats; the gathered score rows; a query's rows listed once (the temperature rescale)
+    static constexpr size_t RANKING_SCRATCH_DEFAULT = (size_t)256 << 20;
+    static constexpr int RANKING_ROWS_MAX = 1 << 24;
+    Scratch<uint32_t> d_rk_keys{&arena};
+    Scratch<int32_t> d_rk_counts{&arena}, d_rk_once{&arena};
+    Scratch<double> d_rk_sums{&arena}, d_rk_work{&arena};
+    Scratch<float> d_rk_scores{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

@@ -263,6 +263,44 @@ class HipGCNModel:
         out["rows"] = rows.value
         return out
 
+    def ranking(self, split=3, nodes=None, return_scores=False, scratch_bytes=0):
+        """Per-class ROC-AUC and average precision without a decision threshold: one evaluation forward with the current weights
+        (no dropout), then keys, a segmented sort and binary searches on the GPU; 5 C + 1 numbers cross to the host.  Rows as in
+        evaluate(): the nodes of `split` (3, the test split, by default), or with split=None the `nodes` query (repeats counted
+        as often as listed; None: every row).  A multi-label model is scored on its logits; a single-label model one-vs-rest on
+        the log-softmax rows at the model's temperature (predict's logp).  Returns a dict: rows, unlabelled (rows with a label
+        outside [0, C): in no class), invalid (int64 [C]: labelled rows whose score is NaN), pos, neg, u2 (int64 [C]), ap_sum
+        (float64 [C]) and what ranking_report() derives from them: auc, ap, auc_defined, ap_defined, macro_auc, macro_ap,
+        weighted_auc, weighted_ap, classes_defined.  return_scores=True adds scores (f32 [rows, C], in list order).
+        scratch_bytes caps the key tables and the sort scratch (0: 256 MiB): the classes run in batches, with the same result
+        in every batching.  One rank, at most 64 (single-label) or 256 (multi-label) classes.  Training state is not touched."""
+        if split is not None and nodes is not None:
+            raise ValueError("ranking: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise ValueError(f"ranking: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if int(scratch_bytes) < 0:
+            raise ValueError(f"ranking: scratch_bytes must be >= 0, got {scratch_bytes!r}")
+        if nodes is None:
+            n, qp, listed = 0, None, self.info()["local_rows"]     # (a split lists at most that many rows)
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = listed = q.size
+            q = q if n else np.zeros(1, np.int32)              # an empty query is still a query (not "every row")
+            qp = q.ctypes.data
+        c = self.params.output_dim
+        u2, pos, neg, inv = (np.zeros(c, np.int64) for _ in range(4))
+        aps = np.zeros(c, np.float64)
+        unl, rows = C.c_int64(), C.c_int64()
+        sc = np.zeros((max(listed, 1), c), np.float32) if return_scores else None
+        _ck(self.lib, self.lib.gcnhost_model_ranking(self.h, int(split or 0), qp, n, int(scratch_bytes), u2.ctypes.data, aps.ctypes.data, pos.ctypes.data,
+                                                     neg.ctypes.data, inv.ctypes.data, C.byref(unl), C.byref(rows),
+                                                     sc.ctypes.data if return_scores else None, sc.size if return_scores else 0), "ranking")
+        out = ranking_report(u2=u2, ap_sum=aps, pos=pos, neg=neg)
+        out.update(rows=rows.value, unlabelled=unl.value, invalid=inv, pos=pos, neg=neg, u2=u2, ap_sum=aps)
+        if return_scores:
+            out["scores"] = sc[:rows.value].copy()
+        return out
+
     # ---- label propagation and Correct & Smooth: the graph and the known labels used at inference time
     def _smooth_args(self, what, pairs, splits=None):
         """argument checks that need no GPU; returns the split mask (bit s = the labelled nodes of split s are known)"""
@@ -709,6 +747,28 @@ def class_report(confusion=None, tp=None, fp=None, fn=None):
                                       summ.ctypes.data), "class_report")
     return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
                 macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
+
+
+def ranking_report(u2, ap_sum, pos, neg):
+    """Per-class ROC-AUC and average precision from the numbers ranking() forms on the GPU — host only, no GPU; the one place they
+    are derived (host/ranking.h).  u2, pos, neg (integers) and ap_sum (float64) [C].  auc = u2 / (2 pos neg), defined when the
+    class has a positive and a negative; ap = ap_sum / pos, defined when it has a positive; an undefined value is 0, never NaN.
+    Returns a dict: auc, ap (float64 [C]), auc_defined, ap_defined (bool [C]), macro_auc, macro_ap (means over the defined
+    classes only), weighted_auc, weighted_ap (weighted by pos over the defined classes), classes_defined.  A negative count, u2
+    outside [0, 2 pos neg] or ap_sum outside [0, pos] raise GcnHostError."""
+    u2, pos, neg = (np.ascontiguousarray(a, np.int64).ravel() for a in (u2, pos, neg))
+    aps = np.ascontiguousarray(ap_sum, np.float64).ravel()
+    c = u2.size
+    if not (pos.size == c and neg.size == c and aps.size == c):
+        raise GcnHostError(f"ranking_report: u2, ap_sum, pos and neg must have one entry per class, got {u2.size}, {aps.size}, {pos.size}, {neg.size}")
+    lib = _lib.gcnhost()
+    auc, ap = np.zeros(max(c, 1), np.float64), np.zeros(max(c, 1), np.float64)
+    ad, pd = np.zeros(max(c, 1), np.int32), np.zeros(max(c, 1), np.int32)
+    summ = np.zeros(5, np.float64)
+    _ck(lib, lib.gcnhost_ranking_report(c, u2.ctypes.data, aps.ctypes.data, pos.ctypes.data, neg.ctypes.data, auc.ctypes.data, ap.ctypes.data,
+                                        ad.ctypes.data, pd.ctypes.data, summ.ctypes.data), "ranking_report")
+    return dict(auc=auc[:c], ap=ap[:c], auc_defined=ad[:c].astype(bool), ap_defined=pd[:c].astype(bool), macro_auc=float(summ[0]),
+                macro_ap=float(summ[1]), weighted_auc=float(summ[2]), weighted_ap=float(summ[3]), classes_defined=int(summ[4]))
 
 
 class _ConformalFit(C.Structure):

@@ -434,6 +434,56 @@ class Device:
         return (unpack_multihot(bb.download()[:listed], c) if bits else None, zb.download()[:listed] if size else None,
                 cb.download() if counts else None)
 
+    # ---- ranking metrics (csrc/ranking.hip)
+    def rank_keys(self, table, c0=0, c1=None, truth=None, truth_bits=None, rows=None, ld=None, stride=None, fill=0x5A5A5A5A, n=None):
+        """gcnhip_rank_keys: (pos_keys, neg_keys uint32 [c1 - c0, stride], pos, neg, invalid int32 [c1 - c0], unlabelled int).
+        table f32 [n_table, C] (uploaded with row stride ld, NaN padding); truth int32 [n_table] OR truth_bits bool [n_table, C];
+        rows: the listed rows (None: rows 0 .. n_table - 1).  The key tables are uploaded holding `fill`, the counts as garbage."""
+        lb, tb, rb, n_table, c, listed = self._calib_inputs(table, ld, truth, rows)
+        listed = listed if n is None else int(n)
+        c1 = c if c1 is None else int(c1)
+        s, stride = max(c1 - c0, 1), int(stride or max(listed, 1))
+        words = pack_multihot(truth_bits) if truth_bits is not None else None
+        wb = self.buf(words if words.size else np.zeros(1, np.uint32)) if words is not None else None
+        pk, nk = self.buf(np.full((s, stride), fill, np.uint32)), self.buf(np.full((s, stride), fill, np.uint32))
+        cnt = [self.buf(np.full(s, 12345, np.int32)) for _ in range(3)]
+        ub = self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_rank_keys(self.ctx, lb.ptr, ld or c, n_table, rb.ptr if rb else None, listed, int(c0), c1, c, tb.ptr if tb else None,
+                                       wb.ptr if wb else None, words.shape[1] if words is not None else 0, pk.ptr, nk.ptr, stride, cnt[0].ptr,
+                                       cnt[1].ptr, cnt[2].ptr, ub.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_rank_keys: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return pk.download(), nk.download(), cnt[0].download(), cnt[1].download(), cnt[2].download(), int(ub.download()[0])
+
+    def sort_segments(self, keys, n=None, segments=None, scratch_fill=0xC3C3C3C3, scratch=True, return_scratch=False):
+        """gcnhip_sort_segments_u32: keys uint32 [S, stride] with the first n (default: stride) keys of every row sorted ascending;
+        the scratch table is uploaded holding `scratch_fill` and returned too when asked for."""
+        keys = np.ascontiguousarray(keys, np.uint32)
+        s, stride = keys.shape
+        kb = self.buf(keys if keys.size else np.zeros(1, np.uint32))
+        sb = self.buf(np.full(max(keys.size, 1), scratch_fill, np.uint32)) if scratch else None
+        rc = self.lib.gcnhip_sort_segments_u32(self.ctx, kb.ptr, sb.ptr if sb else None, stride if n is None else int(n),
+                                               s if segments is None else int(segments), stride)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_sort_segments_u32: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        out = kb.download()[:keys.size].reshape(s, stride)
+        return (out, sb.download()[:keys.size].reshape(s, stride)) if return_scratch else out
+
+    def rank_stats(self, pos_keys, neg_keys, pos, neg, n=None):
+        """gcnhip_rank_stats: (u2 int64 [S], ap_sum float64 [S]) from two sorted key tables uint32 [S, stride] and their valid
+        lengths pos / neg int32 [S]; n: the keys per class (default: stride).  The outputs are uploaded as garbage."""
+        pos_keys, neg_keys = np.ascontiguousarray(pos_keys, np.uint32), np.ascontiguousarray(neg_keys, np.uint32)
+        s, stride = pos_keys.shape
+        assert neg_keys.shape == pos_keys.shape
+        pk, nk = self.buf(pos_keys), self.buf(neg_keys)
+        pb, nb = self.buf(np.ascontiguousarray(pos, np.int32)), self.buf(np.ascontiguousarray(neg, np.int32))
+        work = self.buf(np.full(s * RANK_STATS_BLOCKS * 2, np.nan, np.float64))
+        ub, ab = self.buf(np.full(s, -777, np.int64)), self.buf(np.full(s, np.nan, np.float64))
+        rc = self.lib.gcnhip_rank_stats(self.ctx, pk.ptr, nk.ptr, stride, stride if n is None else int(n), s, pb.ptr, nb.ptr, work.ptr, ub.ptr, ab.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_rank_stats: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return ub.download(), ab.download()
+
     # ---- node embeddings (csrc/embed.hip): the table is uploaded with row stride ld and NaN padding
     def _embed_inputs(self, table, ld, inv_norm):
         table = np.ascontiguousarray(table, np.float32)
@@ -1190,6 +1240,28 @@ class Device:
                 "gcnhip_adam_step")
         return dict(w=[b["w"].download() for b in bufs], m=[b["m"].download() for b in bufs], v=[b["v"].download() for b in bufs],
                     sumsq=sq.download()[0] if want_sumsq else None, state=state)
+
+
+RANK_SENTINEL = 0xFFFFFFFF          # the padding of the key tables of csrc/ranking.hip: no score's key
+RANK_STATS_BLOCKS = 32              # GCNHIP_RANK_STATS_BLOCKS of include/gcnhip_driver.h
+
+
+def __getattr__(name):
+    if name == "SORT_TILE":         # the keys a workgroup of gcnhip_sort_segments_u32 sorts at a time, asked of the library
+        return int(_lib.gcnhip().gcnhip_sort_tile())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def rank_key_host(x):
+    """The order-preserving uint32 image of float32 scores, as gcnhip_rank_keys forms it: -0.0 is +0.0; with b the bits, ~b when
+    the sign bit is set, else b | 0x80000000.  Non-NaN scores compare as their keys; a NaN gets RANK_SENTINEL here (the kernel
+    gives it no key)."""
+    x = np.ascontiguousarray(x, np.float32)
+    b = x.view(np.uint32).copy()
+    b[b == 0x80000000] = 0
+    k = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    k[np.isnan(x)] = RANK_SENTINEL
+    return k
 
 
 def pack_multihot(y):

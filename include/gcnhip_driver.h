@@ -259,6 +259,40 @@ int gcnhip_conformal_true_scores(gcnhip_ctx *ctx, const float *table, int ld, co
                                  int num_classes, float *d_score);
 int gcnhip_conformal_sets_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, const int32_t *d_rows, int n, int num_classes,
                                const float *d_thresh, const int32_t *truth, uint32_t *d_bits, int32_t *d_size, int32_t *d_counts);
+/* ---- ranking metrics (ranking.hip; beyond the reference: per-class ROC-AUC and average precision without a threshold) ----
+ * Key: the order-preserving u32 image of an f32 score — -0.0 is +0.0 first; with b its bits, ~b when the sign bit is set, else
+ * b | 0x80000000.  Non-NaN scores compare as their keys do; 0xFFFFFFFF is no score's key and is the padding sentinel; a NaN score
+ * gets no key.  None of the entry points is part of a captured epoch; no float atomics, so two launches give the same bits; no
+ * launch allocates or synchronises; anything refused returns -1 with a message naming the entry point (gcnhip_last_error).
+ * gcnhip_rank_keys: table f32 [n_table x ld], the listed rows d_rows[i], i < n (NULL: rows 0 .. n - 1, then n <= n_table; repeats
+ *   count as often as listed), the classes [c0, c1) of num_classes <= ld.  Truth is EITHER int32 per table row as gcnhip_set_truth
+ *   makes it (class c's positives are the rows with truth == c, its negatives the other rows with a truth in [0, num_classes); a
+ *   row with any other truth is in no class and counted in *d_unlabelled) OR multi-hot bit rows (bit (c & 31) of word
+ *   truth_bits[r * words_per_row + (c >> 5)]; every row is labelled).  pos_keys / neg_keys u32 [(c1 - c0) x stride], stride >=
+ *   max(n, 1): entry i of column c - c0 = the key of listed row i when it is a positive (resp. negative) of class c, else the
+ *   sentinel; entries [n, stride) are not written.  d_pos / d_neg / d_invalid int32 [c1 - c0] (zeroed on the stream first, integer
+ *   adds): positives, negatives, and labelled rows whose score is NaN (in neither).  d_unlabelled (may be NULL) int32 [1]: listed
+ *   rows without a usable truth, an id outside [0, n_table) among them.  Reads and writes both coalesce (an LDS tile transposes).
+ * gcnhip_sort_segments_u32: sorts `segments` runs of n keys ascending in place, run s at keys + s * stride; scratch: a table of the
+ *   same extent (may be NULL when n <= GCNHIP_SORT_TILE).  The result always lands in keys.  Entries [n, stride) of a run are
+ *   neither read nor written, in either table.  A bitonic network per tile of GCNHIP_SORT_TILE keys (256 threads, 16 keys each:
+ *   strides below 16 in registers, below 1024 by cross-lane moves, above through LDS), then ceil(log2(n / GCNHIP_SORT_TILE))
+ *   merge-path passes between the two tables.  0 <= n <= 2^24, segments >= 1, 64-bit offsets.  gcnhip_sort_tile() returns the tile.
+ * gcnhip_rank_stats: sorted tables as above with the valid lengths d_pos[c] / d_neg[c] (clamped to [0, n]; the sentinel is never
+ *   compared with).  For every class c < segments: d_u2[c] = sum over its positives of #{negatives with a smaller key} +
+ *   #{negatives with a key not larger} (int64, exact), d_ap_sum[c] = sum over its positives of TP_ge / (TP_ge + FP_ge) with TP_ge /
+ *   FP_ge the positives / negatives whose key is not smaller (float64; per thread in index order, then one fixed tree per block,
+ *   then the blocks in order).  A class without positives gives zeros.  d_work: segments * GCNHIP_RANK_STATS_BLOCKS * 16 bytes,
+ *   8-byte aligned. */
+#define GCNHIP_SORT_TILE 4096
+#define GCNHIP_RANK_STATS_BLOCKS 32
+int gcnhip_sort_tile(void);
+int gcnhip_rank_keys(gcnhip_ctx *ctx, const float *table, int ld, int n_table, const int32_t *d_rows, int n, int c0, int c1, int num_classes,
+                     const int32_t *truth, const uint32_t *truth_bits, int words_per_row, uint32_t *pos_keys, uint32_t *neg_keys, int64_t stride,
+                     int32_t *d_pos, int32_t *d_neg, int32_t *d_invalid, int32_t *d_unlabelled);
+int gcnhip_sort_segments_u32(gcnhip_ctx *ctx, uint32_t *keys, uint32_t *scratch, int n, int segments, int64_t stride);
+int gcnhip_rank_stats(gcnhip_ctx *ctx, const uint32_t *pos_keys, const uint32_t *neg_keys, int64_t stride, int n, int segments, const int32_t *d_pos,
+                      const int32_t *d_neg, void *d_work, int64_t *d_u2, double *d_ap_sum);
 /* ---- node embeddings (embed.hip; beyond the reference: what a GCN learns, taken out without leaving the device) ----
  * All entry points read an f32 table [n_table x ld] with 1 <= dim <= 256 and dim <= ld, rows of any stride and alignment;
  * columns [dim, ld) are never read as values.  Score of rows (q, c): their f32 dot product (inv_norm == NULL, metric "dot"),

@@ -257,6 +257,28 @@ int gcnhost_model_conformal_sets(gcnhost_model *m, const gcnhost_conformal *fit,
                                  int32_t *size, int64_t *counts);
 int gcnhost_conformal_quantile(const float *scores, int64_t n, double alpha, const int32_t *labels, int num_classes, float *thresh,
                                int64_t *n_cal, int64_t *k);
+/* Ranking metrics (beyond the reference; ModelQueries::ranking, kernels in csrc/ranking.hip): per-class ROC-AUC and average
+ * precision without a decision threshold.  Rows as gcnhost_model_evaluate takes them (split 1..3, or split == 0 with the `nodes`
+ * query; repeats count as often as listed), gcnhost_model_predict's contract (the call synchronises first, the training state is
+ * untouched).  A multi-label model is scored on its logits, a single-label one one-vs-rest on the log-softmax rows at the model's
+ * current temperature (what gcnhost_model_predict returns as logp).  One rank, at most 64 (single-label) or 256 (multi-label)
+ * classes, at most 2^24 listed rows: anything else is refused with a message before any launch.
+ *
+ * gcnhost_model_ranking: per class c of C = output_dim, over the listed rows with a label in [0, C) (every row of a multi-label
+ * model) and a score that is not NaN: pos[c] / neg[c] = its positives P / negatives N; u2[c] = sum over the positives of
+ * #{negatives scored lower} + #{negatives scored not higher} (exact); ap_sum[c] = sum over the positives of TP_ge / (TP_ge + FP_ge),
+ * the positives / negatives scored not lower (float64); invalid[c] = labelled rows with a NaN score; *unlabelled = rows with a
+ * label outside [0, C); *rows = the listed rows.  scratch_bytes: the cap of the key tables and the sort scratch (0: 256 MiB); the
+ * classes run in batches that fit it, at least one at a time, with the same bits in every batching.  scores (may be NULL; room for
+ * scores_cap floats, else refused): the [rows x C] f32 score rows in list order.
+ * gcnhost_ranking_report, host only (host/ranking.h): auc[c] = u2 / (2 P N), defined (auc_defined[c] = 1) when P > 0 and N > 0;
+ * ap[c] = ap_sum / P, defined when P > 0; an undefined value is 0, never NaN.  summary[5] = {macro_auc, macro_ap, weighted_auc,
+ * weighted_ap, classes with an AUC}: the macro means run over the defined classes only, the weighted ones weigh them by P.
+ * Refused: C < 1, a negative count, u2 outside [0, 2 P N], ap_sum outside [0, P]. */
+int gcnhost_model_ranking(gcnhost_model *m, int split, const int *nodes, int n, size_t scratch_bytes, int64_t *u2, double *ap_sum, int64_t *pos,
+                          int64_t *neg, int64_t *invalid, int64_t *unlabelled, int64_t *rows, float *scores, int64_t scores_cap);
+int gcnhost_ranking_report(int num_classes, const int64_t *u2, const double *ap_sum, const int64_t *pos, const int64_t *neg, double *auc, double *ap,
+                           int32_t *auc_defined, int32_t *ap_defined, double *summary);
 /* Node embeddings (ModelQueries, host/queries.h; kernels in csrc/embed.hip): the hidden matrix H1 = ReLU(A^.X.W1) of one evaluation
  * forward with the current weights (no dropout), as variable 3 stores it (a factored model keeps dinv[r] on row r; cosine scores
  * and normalised rows do not depend on it), queried on the device.  Ids are DATASET node ids.  predict's contract: training state
