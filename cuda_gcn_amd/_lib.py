@@ -117,6 +117,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_rank_keys": (I, [P, P, I, I, P, I, I, I, I, P, P, I, P, P, I64, P, P, P, P]),
     "gcnhip_sort_segments_u32": (I, [P, P, P, I, I, I64]),
     "gcnhip_rank_stats": (I, [P, P, P, I64, I, I, P, P, P, P, P]),
+    "gcnhip_threshold_scan": (I, [P, P, P, I64, I, I, P, P, C.c_double, P, P, P, P, P]),
+    "gcnhip_bce_predict_rows_thr": (I, [P, P, I, P, I, I, P, P, I, P, I]),
+    "gcnhip_bce_class_counts_rows_thr": (I, [P, P, I, P, I, P, I, I, P, P]),
     "gcnhip_embed_inv_norms": (I, [P, P, I, I, I, P]),
     "gcnhip_topk_plan": (I, [I, I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_topk_rows": (I, [P, P, I, I, I, P, P, P, I, I, I, I, P, C.c_size_t, I, P, P]),
@@ -257,6 +260,11 @@ GCNHOST_SYMBOLS = {
     "gcnhost_conformal_quantile": (I, [P, I64, C.c_double, P, I, P, P, P]),
     "gcnhost_model_ranking": (I, [P, I, P, I, C.c_size_t, P, P, P, P, P, P, P, P, I64]),
     "gcnhost_ranking_report": (I, [I, P, P, P, P, P, P, P, P, P]),
+    "gcnhost_model_tune_thresholds": (I, [P, I, P, I, C.c_double, C.c_size_t, P, P, P, P, P, P, P, P, P, P]),
+    "gcnhost_model_predict_multilabel_thr": (I, [P, P, I, P, I, P, P]),
+    "gcnhost_model_evaluate_thr": (I, [P, I, P, I, P, I, P, P]),
+    "gcnhost_thresholds_read": (I, [C.c_char_p, C.POINTER(I), P]),
+    "gcnhost_thresholds_write": (I, [C.c_char_p, I, P, P, P, P, P, P, P]),
     "gcnhost_class_report": (I, [I, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_labels_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P]),
     "gcnhost_model_save_weights": (I, [P, C.c_char_p]),

@@ -13,6 +13,7 @@
 #include "common.h"
 #include <stdlib.h>
 #pragma clang fp contract(off)
+#include "score_rules.h"                 // bce_sigmoid
 
 constexpr int BCE_MAXC_REG = 4;          // 4 x 64 = 256 classes
 constexpr int BCE_MAX_BLOCKS = 1024;     // part_i holds 3 ints per block: red_i[0, 3072)
@@ -29,12 +30,6 @@ struct BceArgs {
     int32_t *part_i;            // [blocks * 3] {TP, FP, FN}
     const float *pos_weight;    // W = true only: [C] (kept at the end: the offsets the unweighted kernel reads stay where they were)
 };
-
-__device__ inline float bce_sigmoid(float z) {
-    if (z >= 0.f) return 1.f / (1.f + expf(-z));
-    const float e = expf(z);
-    return e / (1.f + e);
-}
 
 template <bool W>
 __global__ __launch_bounds__(256) void bce_fwd_kernel(BceArgs a) {

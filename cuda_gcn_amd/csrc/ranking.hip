@@ -24,11 +24,11 @@
 #include <algorithm>
 #include <cstdio>
 #pragma clang fp contract(off)
+#include "score_rules.h"                                       // the key, the sentinel, the searches in a sorted column
 
 constexpr int SORT_TILE = GCNHIP_SORT_TILE;                    // keys a workgroup sorts or merges at a time
 constexpr int SORT_THREADS = 256, SORT_PER = SORT_TILE / SORT_THREADS;
 constexpr int SORT_N_MAX = 1 << 24;
-constexpr uint32_t RANK_SENTINEL = 0xFFFFFFFFu;
 // LDS image of a tile: key i sits at word i + (i >> 4) — a thread's 16 consecutive keys start 17 words apart, so the lanes of
 // a wave reading "their" keys, or the keys of a partner thread, touch 32 different banks; consecutive i stay (almost)
 // consecutive for the coalescing copies.  One word past the last key may be read (never used) by the serial merge.
@@ -38,11 +38,6 @@ static_assert(SORT_PER == 16, "the register network below is laid out for 16 key
 namespace {
 
 __device__ __forceinline__ int sort_phys(int i) { return i + (i >> 4); }
-
-__device__ __forceinline__ uint32_t rank_key(uint32_t b) {
-    if (b == 0x80000000u) b = 0u;                              // -0.0 == +0.0
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 // One compare-exchange step of the bitonic network over the 4096 keys of a tile, key i = 16 t + e in register e of thread t:
 // partner i ^ J, ascending where (i & K) == 0.  J < 16: both keys are this thread's.  16 <= J < 1024: the partner is lane ^
@@ -282,23 +277,6 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(const float *__restrict_
 }
 
 // ---- statistics ------------------------------------------------------------------------------------------------------------
-__device__ inline int rank_lower_bound(const uint32_t *a, int n, uint32_t k) {    // #{a < k}
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ inline int rank_upper_bound(const uint32_t *a, int n, uint32_t k) {    // #{a <= k}
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // grid (GCNHIP_RANK_STATS_BLOCKS, S): block bx of class c takes the positives bx . 256 + t, + blocks . 256, ...
 __global__ __launch_bounds__(256) void rank_stats_kernel(const uint32_t *__restrict__ pos_keys, const uint32_t *__restrict__ neg_keys, int64_t stride,
                                                          int n, const int32_t *__restrict__ pos, const int32_t *__restrict__ neg,

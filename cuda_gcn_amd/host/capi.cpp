@@ -17,6 +17,7 @@
 #include "calibration.h"
 #include "conformal.h"
 #include "ranking.h"
+#include "thresholds.h"
 #include "weights.h"
 
 static thread_local std::string g_err;
@@ -352,6 +353,38 @@ int gcnhost_ranking_report(int num_classes, const int64_t *u2, const double *ap_
     if (ap_defined) std::copy(r.ap_defined.begin(), r.ap_defined.end(), ap_defined);
     if (summary) { summary[0] = r.macro_auc; summary[1] = r.macro_ap; summary[2] = r.weighted_auc; summary[3] = r.weighted_ap; summary[4] = (double)r.classes_defined; }
     return 0;
+}
+int gcnhost_model_tune_thresholds(gcnhost_model *m, int split, const int *nodes, int n, double beta, size_t scratch_bytes, float *thr, int64_t *tp,
+                                  int64_t *fp, int64_t *fn, double *f, int64_t *pos, int64_t *neg, int64_t *invalid, int32_t *defined, int64_t *rows) {
+    if (!m || !thr || !tp || !fp || !fn || !f || !pos || !neg || !invalid || !defined) { g_err = "gcnhost_model_tune_thresholds: invalid argument"; return -1; }
+    API_TRY({
+        const int64_t listed = m->gcn->queries().tune_thresholds(split, nodes, n, beta, scratch_bytes, thr, tp, fp, fn, f, pos, neg, invalid, defined);
+        if (rows) *rows = listed;
+    })
+}
+int gcnhost_model_predict_multilabel_thr(gcnhost_model *m, const int *nodes, int n, const float *thr, int n_thr, uint32_t *bits, float *prob) {
+    if (!m || !thr) { g_err = "gcnhost_model_predict_multilabel_thr: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().predict_multilabel(nodes, n, thr, n_thr, bits, prob); })
+}
+int gcnhost_model_evaluate_thr(gcnhost_model *m, int split, const int *nodes, int n, const float *thr, int n_thr, int64_t *counts, int64_t *rows_counted) {
+    if (!m || !thr || !counts) { g_err = "gcnhost_model_evaluate_thr: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().evaluate(split, nodes, n, thr, n_thr, counts, rows_counted); })
+}
+int gcnhost_thresholds_read(const char *path, int *num_classes, float *thr) {
+    if (!path || !num_classes) { g_err = "gcnhost_thresholds_read: invalid argument"; return -1; }
+    std::vector<float> t;
+    if (gcn_thresholds_read(path, *num_classes, t, &g_err) != 0) return -1;
+    *num_classes = (int)t.size();
+    if (thr) memcpy(thr, t.data(), t.size() * sizeof(float));
+    return 0;
+}
+int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr, const int64_t *pos, const int64_t *neg, const int64_t *tp,
+                             const int64_t *fp, const int64_t *fn, const double *f) {
+    const bool any = pos || neg || tp || fp || fn || f, all = pos && neg && tp && fp && fn && f;
+    if (any != all) { g_err = "gcnhost_thresholds_write: pos, neg, tp, fp, fn and f go together"; return -1; }
+    ThresholdFit fit;
+    fit.pos = pos; fit.neg = neg; fit.tp = tp; fit.fp = fp; fit.fn = fn; fit.f = f;
+    return gcn_thresholds_write(path, num_classes, thr, all ? &fit : nullptr, &g_err);
 }
 int gcnhost_class_report(int num_classes, const int64_t *confusion, const int64_t *tp, const int64_t *fp, const int64_t *fn,
                          int64_t *tp_fp_fn, double *support, double *precision, double *recall, double *f1, double *summary) {

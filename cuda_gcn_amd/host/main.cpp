@@ -70,6 +70,17 @@
 //                            not have (no positive, or no negative), then `macro_auc <x> macro_ap <y> weighted_auc <u> weighted_ap <v>
 //                            classes <k>` (the means over the defined classes).  stdout and the GCN_REPORT file are unchanged.  One GPU;
 //                            at most 64 classes, or 256 on a multi-label model (scored on its logits).
+//   GCN_THRESHOLDS=<file>    after the test line (and GCN_RANKING): one decision threshold per class of a multi-label model, fitted on
+//                            the VALIDATION split for the largest F-beta, GCN_THRESHOLDS_BETA (default 1), on the GPU
+//                            (ModelQueries::tune_thresholds; csrc/thresholds.hip has the rule), and written to the file (host/thresholds.h:
+//                            one line per class, `<threshold> # class c pos P neg N tp .. fp .. fn .. f ..`).  One line is printed:
+//                            `thresholds_beta=<b> val_macro_f1_default=<x> val_macro_f1_tuned=<y> test_micro_f1_default=<a>
+//                            test_micro_f1_tuned=<b> test_macro_f1_default=<c> test_macro_f1_tuned=<d>` (default: the rule logit > 0).
+//                            GCN_PREDICT and GCN_REPORT then decide by the tuned cuts (logit >= threshold).
+//   GCN_APPLY_THRESHOLDS=<file>  the cuts are read from such a file (checked before the GPU is touched) instead of fitted — for
+//                            GCN_LOAD_WEIGHTS runs with 0 epochs; the line printed is `test_micro_f1_default=.. test_micro_f1_tuned=..
+//                            test_macro_f1_default=.. test_macro_f1_tuned=..`.  Both need GCN_MULTILABEL, one GPU and at most 256 classes,
+//                            and exclude each other.
 // Node embeddings (beyond the reference; ModelQueries::embed / similar, kernels in csrc/embed.hip), after the test line and every
 // post-processing step above; stdout is unchanged.  One GPU, hidden_dim at most 256; single- and multi-label models alike:
 //   GCN_EMBED=<file>         one line per node of the dataset in id order: `node v1 ... vh`, the node's row of the hidden layer
@@ -114,6 +125,7 @@
 #include "parser.h"
 #include "ranking.h"
 #include "report.h"
+#include "thresholds.h"
 
 static int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
@@ -249,6 +261,31 @@ int main(int argc, char **argv) {
                                                                                   : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_RANKING " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *thresholds_path = getenv("GCN_THRESHOLDS"), *apply_thresholds_path = getenv("GCN_APPLY_THRESHOLDS");
+    if (thresholds_path && !*thresholds_path) thresholds_path = nullptr;
+    if (apply_thresholds_path && !*apply_thresholds_path) apply_thresholds_path = nullptr;
+    double thresholds_beta = 1.0;
+    std::vector<float> cuts;                                   // one per class once read or fitted; empty: the rule logit > 0
+    if (thresholds_path || apply_thresholds_path) {
+        const char *b = getenv("GCN_THRESHOLDS_BETA");
+        if (b && *b) thresholds_beta = atof(b);
+        const char *why = !multilabel_path                                  ? "need GCN_MULTILABEL (a cut per class of a multi-label model)"
+                          : env_int("GCN_GPUS", 1) > 1                       ? "run on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > 256                          ? "take at most 256 classes"
+                          : thresholds_path && apply_thresholds_path         ? "exclude each other: fit the cuts or read them"
+                          : !(thresholds_beta > 0.0 && thresholds_beta < 1e300) ? "need GCN_THRESHOLDS_BETA finite and > 0"
+                                                                             : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_THRESHOLDS / GCN_APPLY_THRESHOLDS " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::string err;
+        if (apply_thresholds_path && gcn_thresholds_read(apply_thresholds_path, params.output_dim, cuts, &err) != 0) {
+            std::cerr << "gcn-hip: GCN_APPLY_THRESHOLDS: " << err << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -410,10 +447,43 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "gcn-hip: ranking metrics of the test split (macro AUC %.5f, macro AP %.5f over %d classes) written to %s\n", rep.macro_auc,
                         rep.macro_ap, rep.classes_defined, ranking_path);
             }
-            if (predict_path && multilabel_path) {             // the same, as class sets
+            if (thresholds_path || apply_thresholds_path) {    // one rank, multi-label (checked above)
+                const int C = params.output_dim;
+                std::string err;
+                // macro- and micro-F1 of a split by the rule logit > 0 (thr == NULL) or by the cuts, derived where every report is
+                auto f1 = [&](int split, const float *thr, double *micro) {
+                    std::vector<int64_t> cnt(3 * (size_t)C);
+                    if (thr) gcn.queries().evaluate(split, nullptr, 0, thr, C, cnt.data(), nullptr);
+                    else gcn.queries().evaluate(split, nullptr, 0, cnt.data(), nullptr, nullptr);
+                    ClassReport r;
+                    if (gcn_class_report(C, nullptr, cnt.data(), cnt.data() + C, cnt.data() + 2 * C, &r, &err) != 0) throw GcnHipFailure(-1, err);
+                    if (micro) *micro = r.micro_f1;
+                    return r.macro_f1;
+                };
+                if (thresholds_path) {
+                    std::vector<int64_t> tp(C), fp(C), fn(C), pos(C), neg(C), invalid(C);
+                    std::vector<double> f(C);
+                    std::vector<int32_t> defined(C);
+                    cuts.resize(C);
+                    gcn.queries().tune_thresholds(2, nullptr, 0, thresholds_beta, 0, cuts.data(), tp.data(), fp.data(), fn.data(), f.data(), pos.data(),
+                                                  neg.data(), invalid.data(), defined.data());
+                    ThresholdFit fit;
+                    fit.pos = pos.data(); fit.neg = neg.data(); fit.tp = tp.data(); fit.fp = fp.data(); fit.fn = fn.data(); fit.f = f.data();
+                    if (gcn_thresholds_write(thresholds_path, C, cuts.data(), &fit, &err) != 0) throw GcnHipFailure(-1, "gcn-hip: GCN_THRESHOLDS: " + err);
+                    const double val_default = f1(2, nullptr, nullptr), val_tuned = f1(2, cuts.data(), nullptr);
+                    printf("thresholds_beta=%g val_macro_f1_default=%.5f val_macro_f1_tuned=%.5f ", thresholds_beta, val_default, val_tuned);
+                    fprintf(stderr, "gcn-hip: decision thresholds of %d classes, fitted on the validation split, written to %s\n", C, thresholds_path);
+                }
+                double micro_default = 0, micro_tuned = 0;
+                const double macro_default = f1(3, nullptr, &micro_default), macro_tuned = f1(3, cuts.data(), &micro_tuned);
+                printf("test_micro_f1_default=%.5f test_micro_f1_tuned=%.5f test_macro_f1_default=%.5f test_macro_f1_tuned=%.5f\n", micro_default, micro_tuned,
+                       macro_default, macro_tuned);
+            }
+            if (predict_path && multilabel_path) {             // the same, as class sets (by the cuts when there are any)
                 const int n = gcn.local_rows();
                 std::vector<uint32_t> b((size_t)std::max(n, 1) * ml_wpr);
-                gcn.queries().predict_multilabel(nullptr, n, b.data(), nullptr);
+                if (cuts.empty()) gcn.queries().predict_multilabel(nullptr, n, b.data(), nullptr);
+                else gcn.queries().predict_multilabel(nullptr, n, cuts.data(), (int)cuts.size(), b.data(), nullptr);
                 for (int r = 0; r < n; r++) {
                     const int id = gcn.node_id(r);
                     std::copy(b.begin() + (size_t)r * ml_wpr, b.begin() + (size_t)(r + 1) * ml_wpr, all_bits.begin() + (size_t)id * ml_wpr);
@@ -440,7 +510,8 @@ int main(int argc, char **argv) {
             }
             if (report_path) {                                 // every rank: a collective; the totals are the same everywhere
                 std::vector<int64_t> cnt(report_counts.size());
-                gcn.queries().evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
+                if (cuts.empty()) gcn.queries().evaluate(3, nullptr, 0, cnt.data(), nullptr, nullptr);
+                else gcn.queries().evaluate(3, nullptr, 0, cuts.data(), (int)cuts.size(), cnt.data(), nullptr);
                 if (rank == 0) report_counts = cnt;
             }
             if (embed_path) {                                  // one rank (checked above): rows by node id

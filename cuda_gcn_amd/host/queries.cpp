@@ -118,8 +118,33 @@ void ModelQueries::predict(const int *nodes, int n, int32_t *pred, float *prob, 
 }
 
 void ModelQueries::predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob) {
-    const int C = m.params.output_dim, wpr = m.ml_wpr;
     require("predict_multilabel", MULTI_LABEL | CLASS_AGGREGATION);
+    predict_multilabel_rows(nodes, n, nullptr, bits, prob);
+}
+
+void ModelQueries::predict_multilabel(const int *nodes, int n, const float *thr, int n_thr, uint32_t *bits, float *prob) {
+    require("predict_multilabel", MULTI_LABEL | CLASS_AGGREGATION | ONE_RANK | AT_MOST_256);
+    thresholds_check("predict_multilabel", thr, n_thr);
+    predict_multilabel_rows(nodes, n, thr, bits, prob);
+}
+
+// what a query and an evaluation refuse of the cuts they are given
+void ModelQueries::thresholds_check(const char *what, const float *thr, int n_thr) const {
+    const int C = m.params.output_dim;
+    if (!thr || n_thr != C)
+        throw GcnHipFailure(-1, std::string(what) + ": " + std::to_string(thr ? n_thr : 0) + " thresholds for " + std::to_string(C) + " classes");
+    for (int c = 0; c < C; c++)
+        if (std::isnan(thr[c])) throw GcnHipFailure(-1, std::string(what) + ": the threshold of class " + std::to_string(c) + " is NaN");
+}
+
+const float *ModelQueries::upload_cuts(const float *thr) {
+    const size_t C = (size_t)m.params.output_dim;
+    GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_th_cuts.need(C), thr, C * sizeof(float)));
+    return d_th_cuts.p;
+}
+
+void ModelQueries::predict_multilabel_rows(const int *nodes, int n, const float *thr, uint32_t *bits, float *prob) {
+    const int C = m.params.output_dim, wpr = m.ml_wpr;
     if ((n > 0 && !bits) || n < 0) throw GcnHipFailure(-1, "predict_multilabel: invalid argument");
     if (!nodes) n = m.n_local;
     std::vector<int> rows;
@@ -132,7 +157,11 @@ void ModelQueries::predict_multilabel(const int *nodes, int n, uint32_t *bits, f
     forward_redirect(subset);
     if (n == 0) { m.sync(); return; }
     GCNHIP_CHECK(gcnhip_h2d(m.env.ctx, d_ml_rows.p, rows.data(), (size_t)n * sizeof(int32_t)));
-    GCNHIP_CHECK(gcnhip_bce_predict_rows(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, d_ml_rows.p, n, C, d_ml_bits.p, wpr, prob ? d_ml_prob.p : nullptr, C));
+    if (thr)
+        GCNHIP_CHECK(gcnhip_bce_predict_rows_thr(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, d_ml_rows.p, n, C, upload_cuts(thr), d_ml_bits.p, wpr,
+                                                 prob ? d_ml_prob.p : nullptr, C));
+    else
+        GCNHIP_CHECK(gcnhip_bce_predict_rows(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, d_ml_rows.p, n, C, d_ml_bits.p, wpr, prob ? d_ml_prob.p : nullptr, C));
     GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, bits, d_ml_bits.p, (size_t)n * wpr * sizeof(uint32_t)));
     if (prob) GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, prob, d_ml_prob.p, (size_t)n * C * sizeof(float)));
 }
@@ -180,9 +209,19 @@ ModelQueries::ScoredRows ModelQueries::scored_rows(const char *what, int split, 
 }
 
 void ModelQueries::evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
+    require("evaluate", CLASS_AGGREGATION | (m.opt_.multilabel ? AT_MOST_256 : AT_MOST_64));
+    evaluate_rows(split, nodes, n, nullptr, counts, rows_counted, unlabelled);
+}
+
+void ModelQueries::evaluate(int split, const int *nodes, int n, const float *thr, int n_thr, int64_t *counts, int64_t *rows_counted) {
+    require("evaluate", MULTI_LABEL | CLASS_AGGREGATION | ONE_RANK | AT_MOST_256);
+    thresholds_check("evaluate", thr, n_thr);
+    evaluate_rows(split, nodes, n, thr, counts, rows_counted, nullptr);
+}
+
+void ModelQueries::evaluate_rows(int split, const int *nodes, int n, const float *thr, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
     const int C = m.params.output_dim;
     const bool ml = m.opt_.multilabel;
-    require("evaluate", CLASS_AGGREGATION | (ml ? AT_MOST_256 : AT_MOST_64));
     if (split < 0 || split > 3 || !counts || n < 0) throw GcnHipFailure(-1, "evaluate: invalid argument (split is 0 with a node query, or 1 train, 2 validation, 3 test)");
     const ScoredRows q = scored_rows("evaluate", split, nodes, n);
     n = q.n;
@@ -190,7 +229,11 @@ void ModelQueries::evaluate(int split, const int *nodes, int n, int64_t *counts,
     int32_t *d_counts = d_eval_counts.need(((size_t)std::max(3 * C, C * C + 1) + 1) * 2);
     if (ml) {
         forward_redirect(q.subset);
-        GCNHIP_CHECK(gcnhip_bce_class_counts_rows(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, m.d_ml_truth, m.ml_wpr, q.d_list, n, C, d_counts));
+        if (thr)
+            GCNHIP_CHECK(gcnhip_bce_class_counts_rows_thr(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, m.d_ml_truth, m.ml_wpr, q.d_list, n, C, upload_cuts(thr),
+                                                          d_counts));
+        else
+            GCNHIP_CHECK(gcnhip_bce_class_counts_rows(m.env.ctx, d_ml_logits.p, m.variables[6]->ld, m.d_ml_truth, m.ml_wpr, q.d_list, n, C, d_counts));
     } else {
         forward_predict(q.subset, false);
         GCNHIP_CHECK(gcnhip_confusion_rows(m.env.ctx, d_pred.p, q.truth, m.n_local, q.d_list, n, C, d_counts, d_counts + C * C));

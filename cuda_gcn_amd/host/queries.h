@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -12,6 +12,7 @@
 // It writes no member of HipGCN.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <vector>
 #include "device_arena.h"
 
@@ -36,6 +37,10 @@ public:
     // gcnhip_bce_predict_rows.  bits [n x ceil(C / 32)]: bit (c & 31) of word c >> 5 = (z_c > 0); prob (may be NULL) [n x C] =
     // sigmoid(z).  Only on a multi-label model (predict() only on a single-label one).
     void predict_multilabel(const int *nodes, int n, uint32_t *bits, float *prob);
+    // The same call deciding by one cut per class (tune_thresholds below; csrc/thresholds.hip has the rule): thr [n_thr], bit c =
+    // (z_c is not NaN and z_c >= thr[c], compared on the integer keys), gcnhip_bce_predict_rows_thr; prob stays sigmoid(z).
+    // Refused with a message before any launch: n_thr != C, a NaN threshold, more than one rank, more than 256 classes.
+    void predict_multilabel(const int *nodes, int n, const float *thr, int n_thr, uint32_t *bits, float *prob);
     // Per-class evaluation: one evaluation forward with the current weights (no dropout) over a set of rows, and integer counts
     // per class formed on the GPU behind it.  Rows: the nodes of `split` (1 train, 2 validation, 3 test — eval's codes) on this
     // rank, `nodes` then ignored; or, with split == 0, the `nodes` query with predict()'s conventions (n dataset ids, each a row
@@ -49,6 +54,9 @@ public:
     // Training state is not touched, as with predict().  Synchronises.  More than 64 (single-label) or 256 (multi-label)
     // classes: an error.  host/report.h derives precision / recall / F1 from the counts.
     void evaluate(int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+    // evaluate() of a multi-label model with one cut per class in place of z > 0 (gcnhip_bce_class_counts_rows_thr): counts
+    // [3 x C] = TP, FP, FN.  Refused as predict_multilabel with thresholds is, and on a single-label model.
+    void evaluate(int split, const int *nodes, int n, const float *thr, int n_thr, int64_t *counts, int64_t *rows_counted);
     // Label propagation and Correct & Smooth (Huang et al., 2020): the graph and the known labels used at inference time.  Every
     // iteration is one gcnhip_graphsum_blend launch through the model's adjacency with its per-edge coefficients, ping-ponging
     // two of four [local rows x ld] f32 tables (allocated on first use; ld by the row rule of variable 6).  Arrays are in
@@ -199,6 +207,20 @@ public:
     int64_t ranking(int split, const int *nodes, int n, size_t scratch_bytes, int64_t *u2, double *ap_sum, int64_t *pos, int64_t *neg, int64_t *invalid,
                     int64_t *unlabelled, std::vector<float> *scores);
 
+    // Multi-label decision thresholds: per class the cut on the logit with the largest F-beta over the listed rows — the last
+    // step on data with rare classes, where the training rule z > 0 is seldom the best cut (csrc/thresholds.hip: the rule, the
+    // candidates, the float64 expression of F and why every reduction order gives the same bits).  ranking()'s path on a
+    // multi-label model up to the sorted key columns: rows as evaluate() takes them, one forward whose logits go to scratch,
+    // the classes in ranking()'s batches under the same scratch cap; per batch gcnhip_rank_keys, one sort of both tables and
+    // one gcnhip_threshold_scan.  thr [C] f32, tp / fp / fn [C] at the cut, f [C] (float64), pos / neg / invalid [C],
+    // defined [C] (0: a class without a positive among the rows — thr 0, F 0) are all that crosses to the host; every batching
+    // gives the same bits.  Returns the number of listed rows.  predict()'s contract: the call starts with sync(); the metrics
+    // ring, the current split, variable 6 and the captured epoch graph are untouched.  Refused with a message before any
+    // launch: a single-label model, more than 256 classes, more than one rank, a split outside 0..3, beta not finite or <= 0,
+    // more than 2^24 listed rows.  host/thresholds.h reads and writes the thresholds file.
+    int64_t tune_thresholds(int split, const int *nodes, int n, double beta, size_t scratch_bytes, float *thr, int64_t *tp, int64_t *fp, int64_t *fn,
+                            double *f, int64_t *pos, int64_t *neg, int64_t *invalid, int32_t *defined);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                         // every device buffer of a query
@@ -276,6 +298,9 @@ private:
     Scratch<int32_t> d_rk_counts{&arena}, d_rk_once{&arena};
     Scratch<double> d_rk_sums{&arena}, d_rk_work{&arena};
     Scratch<float> d_rk_scores{&arena};
+    // tune_thresholds: one block {f [C] | thr [C] | TP, FP, FN per batch | defined [C]}; the cuts a query or an evaluation decides by
+    Scratch<double> d_th_fit{&arena};
+    Scratch<float> d_th_cuts{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
@@ -286,6 +311,17 @@ private:
     // the two hooked forwards: d_pred / d_prob (and d_logp when kept) of the subset's rows; their logits into d_ml_logits
     void forward_predict(const gcnhip_rowset *subset, bool keep_logp);
     void forward_redirect(const gcnhip_rowset *subset);
+    // predict_multilabel and the multi-label evaluate, by z > 0 (thr == NULL) or by the cuts thr [C] (host)
+    void predict_multilabel_rows(const int *nodes, int n, const float *thr, uint32_t *bits, float *prob);
+    void evaluate_rows(int split, const int *nodes, int n, const float *thr, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled);
+    void thresholds_check(const char *what, const float *thr, int n_thr) const;
+    const float *upload_cuts(const float *thr);
+    // ranking and tune_thresholds: the classes in batches whose two key tables and sort scratch fit the cap; per batch
+    // gcnhip_rank_keys and one sort of both tables, then stats(c0, S, pos_keys, neg_keys, stride, d_pos, d_neg, d_work) with
+    // the batch's counts and a work block of S * 32 * 16 bytes.  Returns the counts {pos | neg | invalid [C] | unlabelled}.
+    using BatchStats = std::function<void(int c0, int S, const uint32_t *pos_keys, const uint32_t *neg_keys, int64_t stride, const int32_t *d_pos,
+                                          const int32_t *d_neg, void *d_work)>;
+    const int32_t *sorted_class_batches(const ScoredRows &q, const float *table, int ld, size_t scratch_bytes, const BatchStats &stats);
     static int smooth_row_ld(int dim) { return dim <= 32 ? (dim + 3) / 4 * 4 : (dim + 15) / 16 * 16; }   // HipVariable's rule
     void smooth_check(const char *what, int needs, float alpha, int iters) const;
     const int32_t *smooth_truth(const char *what, int splits_mask, std::vector<int32_t> *host);

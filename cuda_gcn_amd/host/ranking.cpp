@@ -70,6 +70,31 @@ int gcn_ranking_report_write(const char *path, int C, const RankingReport &rep, 
     return ok ? 0 : -1;
 }
 
+// Classes in batches: the two key tables and their sort scratch — four columns of `stride` keys per class — fit the cap.
+// A class's column is sorted and searched by itself, so no result depends on the batching.
+const int32_t *ModelQueries::sorted_class_batches(const ScoredRows &q, const float *table, int ld, size_t scratch_bytes, const BatchStats &stats) {
+    static_assert(GCNHIP_THRESHOLD_SCAN_BLOCKS <= GCNHIP_RANK_STATS_BLOCKS, "one work block serves both statistics");
+    const int C = m.params.output_dim, n = q.n;
+    const bool ml = m.opt_.multilabel;
+    const size_t stride = (size_t)std::max(n, 1);
+    const size_t cap = scratch_bytes ? scratch_bytes : RANKING_SCRATCH_DEFAULT;
+    const int batch = (int)std::min<size_t>((size_t)C, std::max<size_t>(1, cap / (4 * stride * sizeof(uint32_t))));
+    uint32_t *keys = d_rk_keys.need(4 * (size_t)batch * stride);
+    uint32_t *sort_scratch = keys + 2 * (size_t)batch * stride;
+    int32_t *d_counts = d_rk_counts.need(3 * (size_t)C + 1);   // pos | neg | invalid | unlabelled
+    double *d_work = d_rk_work.need(2 * (size_t)batch * GCNHIP_RANK_STATS_BLOCKS);
+    for (int c0 = 0; c0 < C; c0 += batch) {
+        const int c1 = std::min(C, c0 + batch), S = c1 - c0;
+        uint32_t *pos_keys = keys, *neg_keys = keys + (size_t)S * stride;     // back to back: 2 S segments for one sort call
+        GCNHIP_CHECK(gcnhip_rank_keys(m.env.ctx, table, ld, m.n_local, q.d_list, n, c0, c1, C, ml ? nullptr : q.truth, ml ? m.d_ml_truth : nullptr, m.ml_wpr,
+                                      pos_keys, neg_keys, (int64_t)stride, d_counts + c0, d_counts + C + c0, d_counts + 2 * C + c0,
+                                      c0 == 0 ? d_counts + 3 * C : nullptr));
+        GCNHIP_CHECK(gcnhip_sort_segments_u32(m.env.ctx, keys, sort_scratch, n, 2 * S, (int64_t)stride));
+        stats(c0, S, pos_keys, neg_keys, (int64_t)stride, d_counts + c0, d_counts + C + c0, d_work);
+    }
+    return d_counts;
+}
+
 int64_t ModelQueries::ranking(int split, const int *nodes, int n, size_t scratch_bytes, int64_t *u2, double *ap_sum, int64_t *pos, int64_t *neg,
                               int64_t *invalid, int64_t *unlabelled, std::vector<float> *scores) {
     const int C = m.params.output_dim, n_local = m.n_local;
@@ -108,32 +133,18 @@ int64_t ModelQueries::ranking(int split, const int *nodes, int n, size_t scratch
             GCNHIP_CHECK(gcnhip_calib_scale_rows(m.env.ctx, d_logp.p, C, n_local, d_once, listed, C, 1.f / temperature_, d_logp.p, C, d_prob.p));
         }
     }
-    // Classes in batches: the two key tables and their sort scratch — four columns of `stride` keys per class — fit the cap.
-    // A class's column is sorted and searched by itself, so no result depends on the batching.
-    const size_t stride = (size_t)std::max(n, 1);
-    const size_t cap = scratch_bytes ? scratch_bytes : RANKING_SCRATCH_DEFAULT;
-    const int batch = (int)std::min<size_t>((size_t)C, std::max<size_t>(1, cap / (4 * stride * sizeof(uint32_t))));
-    uint32_t *keys = d_rk_keys.need(4 * (size_t)batch * stride);
-    uint32_t *sort_scratch = keys + 2 * (size_t)batch * stride;
-    int32_t *d_counts = d_rk_counts.need(3 * (size_t)C + 1);   // pos | neg | invalid | unlabelled
     double *d_ap = d_rk_sums.need(2 * (size_t)C);              // ap_sum [C] | u2 [C] (int64)
     int64_t *d_u2 = (int64_t *)(d_ap + C);
-    double *d_work = d_rk_work.need(2 * (size_t)batch * GCNHIP_RANK_STATS_BLOCKS);
-    for (int c0 = 0; c0 < C; c0 += batch) {
-        const int c1 = std::min(C, c0 + batch), S = c1 - c0;
-        uint32_t *pos_keys = keys, *neg_keys = keys + (size_t)S * stride;     // back to back: 2 S segments for one sort call
-        GCNHIP_CHECK(gcnhip_rank_keys(m.env.ctx, table, ld, n_local, q.d_list, n, c0, c1, C, ml ? nullptr : q.truth, ml ? m.d_ml_truth : nullptr, m.ml_wpr,
-                                      pos_keys, neg_keys, (int64_t)stride, d_counts + c0, d_counts + C + c0, d_counts + 2 * C + c0,
-                                      c0 == 0 ? d_counts + 3 * C : nullptr));
-        GCNHIP_CHECK(gcnhip_sort_segments_u32(m.env.ctx, keys, sort_scratch, n, 2 * S, (int64_t)stride));
-        GCNHIP_CHECK(gcnhip_rank_stats(m.env.ctx, pos_keys, neg_keys, (int64_t)stride, n, S, d_counts + c0, d_counts + C + c0, d_work, d_u2 + c0, d_ap + c0));
-    }
+    const int32_t *d_counts = sorted_class_batches(q, table, ld, scratch_bytes, [&](int c0, int S, const uint32_t *pos_keys, const uint32_t *neg_keys,
+                                                                                    int64_t stride, const int32_t *d_pos, const int32_t *d_neg, void *d_work) {
+        GCNHIP_CHECK(gcnhip_rank_stats(m.env.ctx, pos_keys, neg_keys, stride, n, S, d_pos, d_neg, d_work, d_u2 + c0, d_ap + c0));
+    });
     std::vector<int32_t> hc(3 * (size_t)C + 1);
     std::vector<double> hs(2 * (size_t)C);
     GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, hc.data(), d_counts, hc.size() * sizeof(int32_t)));
     GCNHIP_CHECK(gcnhip_d2h(m.env.ctx, hs.data(), d_ap, hs.size() * sizeof(double)));
     if (scores) {
-        std::vector<float> h(stride * ld);
+        std::vector<float> h((size_t)std::max(n, 1) * ld);
         if (n > 0 && q.d_list) {
             float *d = d_rk_scores.need((size_t)n * ld);
             GCNHIP_CHECK(gcnhip_gather_rows(m.env.ctx, table, ld, q.d_list, n, d));

@@ -210,10 +210,12 @@ class HipGCNModel:
         _ck(self.lib, self.lib.gcnhost_model_predict(self.h, qp, n, pred.ctypes.data, prob.ctypes.data, lp.ctypes.data if logp else None), "predict")
         return (pred[:n], prob[:n], lp[:n]) if logp else (pred[:n], prob[:n])
 
-    def predict_multilabel(self, nodes=None, prob=False):
+    def predict_multilabel(self, nodes=None, prob=False, thresholds=None):
         """bool [n, C] — the classes whose logit is above 0 (the rule micro-F1 counts with), from an evaluation forward with the
         current weights whose logits go to scratch; prob=True: also the sigmoid of every logit, f32 [n, C].  nodes as in
-        predict(); only on a model built with multilabel=.  Several ranks: every rank calls it.  Training state is not touched."""
+        predict(); only on a model built with multilabel=.  Several ranks: every rank calls it.  Training state is not touched.
+        thresholds (f32 [C], tune_thresholds()["threshold"] or read_thresholds()): class c is predicted when its logit is >=
+        thresholds[c] instead (one rank; prob stays the sigmoid); a wrong length or a NaN raises ValueError."""
         from .ops import unpack_multihot
         if nodes is None:
             n, qp = self.info()["local_rows"], None
@@ -223,19 +225,26 @@ class HipGCNModel:
         c = self.params.output_dim
         words = np.zeros((max(n, 1), (c + 31) // 32), np.uint32)
         pr = np.zeros((max(n, 1), c), np.float32) if prob else None
-        _ck(self.lib, self.lib.gcnhost_model_predict_multilabel(self.h, qp, n, words.ctypes.data, pr.ctypes.data if prob else None),
-            "predict_multilabel")
+        if thresholds is None:
+            _ck(self.lib, self.lib.gcnhost_model_predict_multilabel(self.h, qp, n, words.ctypes.data, pr.ctypes.data if prob else None),
+                "predict_multilabel")
+        else:
+            thr = thresholds_array("predict_multilabel", thresholds, c)
+            _ck(self.lib, self.lib.gcnhost_model_predict_multilabel_thr(self.h, qp, n, thr.ctypes.data, thr.size, words.ctypes.data,
+                                                                       pr.ctypes.data if prob else None), "predict_multilabel")
         sets = unpack_multihot(words[:n], c)
         return (sets, pr[:n]) if prob else sets
 
-    def evaluate(self, split=None, nodes=None):
+    def evaluate(self, split=None, nodes=None, thresholds=None):
         """Per-class evaluation: one evaluation forward with the current weights (no dropout) over a set of rows, integer counts
         per class formed on the GPU behind it, and the metrics class_report() derives from them.  Rows: the nodes of `split`
         (1 train, 2 validation, 3 test) on this rank; or, with split=None, the `nodes` query with predict()'s conventions
         (repeats counted as often as listed; None: every row of this rank).  Returns a dict: rows, support, precision, recall, f1
         (float64 [C]), macro_f1, micro_f1; a single-label model adds confusion (int64 [C, C], row = truth, column = prediction),
         accuracy, unlabelled (rows whose label is outside [0, C): in no cell); a multi-label model adds tp, fp, fn (int64 [C]).
-        Several ranks: every rank calls it and every rank gets the totals over all ranks.  Training state is not touched."""
+        Several ranks: every rank calls it and every rank gets the totals over all ranks.  Training state is not touched.
+        thresholds (f32 [C]; a multi-label model on one rank): class c is predicted when its logit is >= thresholds[c] instead
+        of > 0; a wrong length or a NaN raises ValueError."""
         if split is not None and nodes is not None:
             raise ValueError("evaluate: give a split or a node query, not both")
         if split is not None and split not in (1, 2, 3):
@@ -250,7 +259,13 @@ class HipGCNModel:
         c = self.params.output_dim
         counts = np.zeros((3, c) if self.multilabel else (c, c), np.int64)
         rows, unl = C.c_int64(), C.c_int64()
-        _ck(self.lib, self.lib.gcnhost_model_evaluate(self.h, int(split or 0), qp, n, counts.ctypes.data, C.byref(rows), C.byref(unl)), "evaluate")
+        if thresholds is None:
+            _ck(self.lib, self.lib.gcnhost_model_evaluate(self.h, int(split or 0), qp, n, counts.ctypes.data, C.byref(rows), C.byref(unl)), "evaluate")
+        else:
+            thr = thresholds_array("evaluate", thresholds, c)
+            counts = np.zeros((3, c), np.int64)                # the call refuses a single-label model
+            _ck(self.lib, self.lib.gcnhost_model_evaluate_thr(self.h, int(split or 0), qp, n, thr.ctypes.data, thr.size, counts.ctypes.data,
+                                                              C.byref(rows)), "evaluate")
         if self.multilabel:
             out = class_report(tp=counts[0], fp=counts[1], fn=counts[2])
             out.pop("accuracy")
@@ -299,6 +314,42 @@ class HipGCNModel:
         out.update(rows=rows.value, unlabelled=unl.value, invalid=inv, pos=pos, neg=neg, u2=u2, ap_sum=aps)
         if return_scores:
             out["scores"] = sc[:rows.value].copy()
+        return out
+
+    def tune_thresholds(self, split=2, nodes=None, beta=1.0, scratch_bytes=0):
+        """One decision threshold per class of a multi-label model, fitted on the GPU: the cut on the logit with the largest
+        F-beta over the listed rows (the validation split by default), the highest such cut on a tie.  ranking()'s path — one
+        evaluation forward, keys, a segmented sort — then one scan per class batch; only O(C) numbers cross to the host.  Rows as
+        in evaluate(); scratch_bytes as in ranking() (the same bits in every batching).  Returns a dict: threshold (f32 [C]: class
+        c is predicted when its logit is >= threshold[c]), defined (bool [C]; False: no positive among the rows — threshold 0, f 0),
+        tp, fp, fn (int64 [C], at the cut), f (float64 [C], the F-beta at the cut), pos, neg (int64 [C]), invalid (int64 [C]: rows
+        with a NaN logit, in neither), rows, beta, and the class_report(tp=, fp=, fn=) metrics of the fit rows at the cuts
+        (support, precision, recall, f1, macro_f1, micro_f1).  Hand threshold to predict_multilabel / evaluate(thresholds=) or
+        write_thresholds().  A multi-label model, one rank, at most 256 classes.  Training state is not touched."""
+        if split is not None and nodes is not None:
+            raise ValueError("tune_thresholds: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise ValueError(f"tune_thresholds: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if int(scratch_bytes) < 0:
+            raise ValueError(f"tune_thresholds: scratch_bytes must be >= 0, got {scratch_bytes!r}")
+        beta = check_beta("tune_thresholds", beta)
+        if nodes is None:
+            n, qp = 0, None
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = q.size
+            q = q if n else np.zeros(1, np.int32)              # an empty query is still a query (not "every row")
+            qp = q.ctypes.data
+        c = self.params.output_dim
+        thr, f, defined = np.zeros(c, np.float32), np.zeros(c, np.float64), np.zeros(c, np.int32)
+        tp, fp, fn, pos, neg, inv = (np.zeros(c, np.int64) for _ in range(6))
+        rows = C.c_int64()
+        _ck(self.lib, self.lib.gcnhost_model_tune_thresholds(self.h, int(split or 0), qp, n, beta, int(scratch_bytes), thr.ctypes.data, tp.ctypes.data,
+                                                             fp.ctypes.data, fn.ctypes.data, f.ctypes.data, pos.ctypes.data, neg.ctypes.data,
+                                                             inv.ctypes.data, defined.ctypes.data, C.byref(rows)), "tune_thresholds")
+        out = class_report(tp=tp, fp=fp, fn=fn)
+        out.pop("accuracy")
+        out.update(threshold=thr, defined=defined.astype(bool), tp=tp, fp=fp, fn=fn, f=f, pos=pos, neg=neg, invalid=inv, rows=rows.value, beta=beta)
         return out
 
     # ---- label propagation and Correct & Smooth: the graph and the known labels used at inference time
@@ -747,6 +798,55 @@ def class_report(confusion=None, tp=None, fp=None, fn=None):
                                       summ.ctypes.data), "class_report")
     return dict(tp=cnt[0].copy(), fp=cnt[1].copy(), fn=cnt[2].copy(), support=sup, precision=pre, recall=rec, f1=f1,
                 macro_f1=float(summ[0]), micro_f1=float(summ[1]), accuracy=float(summ[2]), rows=rows)
+
+
+def thresholds_array(what, thresholds, num_classes):
+    """f32 [C] from what a caller hands in as thresholds (an array, or the dict tune_thresholds() returns); a wrong length or a NaN
+    raises ValueError"""
+    if isinstance(thresholds, dict):
+        thresholds = thresholds["threshold"]
+    thr = np.ascontiguousarray(thresholds, np.float32).ravel()
+    if thr.size != int(num_classes):
+        raise ValueError(f"{what}: {thr.size} thresholds for {int(num_classes)} classes")
+    if np.isnan(thr).any():
+        raise ValueError(f"{what}: the threshold of class {int(np.flatnonzero(np.isnan(thr))[0])} is NaN")
+    return thr
+
+
+def check_beta(what, beta):
+    beta = float(beta)
+    if not (np.isfinite(beta) and beta > 0):
+        raise ValueError(f"{what}: beta must be finite and > 0, got {beta!r}")
+    return beta
+
+
+def read_thresholds(path, num_classes=None):
+    """f32 [C] from a thresholds text file (write_thresholds, gcn-hip's GCN_THRESHOLDS=<file>; host/thresholds.h): one line per
+    class, the first token the threshold, everything from '#' on ignored — host only, no GPU.  num_classes: the count the file
+    must hold.  A wrong count, a bad token or a NaN raises GcnHostError naming the line."""
+    lib = _lib.gcnhost()
+    c = C.c_int(int(num_classes or 0))
+    _ck(lib, lib.gcnhost_thresholds_read(os.fsencode(path), C.byref(c), None), "thresholds_read")
+    thr = np.zeros(c.value, np.float32)
+    _ck(lib, lib.gcnhost_thresholds_read(os.fsencode(path), C.byref(c), thr.ctypes.data), "thresholds_read")
+    return thr
+
+
+def write_thresholds(path, fit_or_array):
+    """A thresholds file from the dict tune_thresholds() returns (each line then carries `# class c pos P neg N tp .. fp .. fn ..
+    f ..`) or from a plain array of C thresholds — host only, no GPU.  Every float32 is written as %.9g and read back exactly.
+    A NaN raises ValueError."""
+    fit = fit_or_array if isinstance(fit_or_array, dict) else None
+    thr = np.ascontiguousarray(fit["threshold"] if fit else fit_or_array, np.float32).ravel()
+    thr = thresholds_array("write_thresholds", thr, max(thr.size, 1))
+    notes = [None] * 6
+    if fit:
+        notes = [np.ascontiguousarray(fit[k], np.int64).ravel() for k in ("pos", "neg", "tp", "fp", "fn")] + [np.ascontiguousarray(fit["f"], np.float64).ravel()]
+        if any(a.size != thr.size for a in notes):
+            raise ValueError("write_thresholds: the fit's arrays must have one entry per threshold")
+    lib = _lib.gcnhost()
+    _ck(lib, lib.gcnhost_thresholds_write(os.fsencode(path), thr.size, thr.ctypes.data, *[a.ctypes.data if a is not None else None for a in notes]),
+        "thresholds_write")
 
 
 def ranking_report(u2, ap_sum, pos, neg):

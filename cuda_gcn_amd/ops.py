@@ -484,6 +484,25 @@ class Device:
             raise GcnHipError(f"gcnhip_rank_stats: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return ub.download(), ab.download()
 
+    # ---- multi-label decision thresholds (csrc/thresholds.hip)
+    def threshold_scan(self, pos_keys, neg_keys, pos, neg, beta=1.0, n=None):
+        """gcnhip_threshold_scan: (threshold f32 [S], counts int32 [3, S] = TP, FP, FN at it, f float64 [S], defined int32 [S])
+        from two sorted key tables uint32 [S, stride] and their valid lengths pos / neg int32 [S]; n: the keys per class
+        (default: stride).  The outputs are uploaded as garbage."""
+        pos_keys, neg_keys = np.ascontiguousarray(pos_keys, np.uint32), np.ascontiguousarray(neg_keys, np.uint32)
+        s, stride = pos_keys.shape
+        assert neg_keys.shape == pos_keys.shape
+        pk, nk = self.buf(pos_keys), self.buf(neg_keys)
+        pb, nb = self.buf(np.ascontiguousarray(pos, np.int32)), self.buf(np.ascontiguousarray(neg, np.int32))
+        work = self.buf(np.full(s * THRESHOLD_SCAN_BLOCKS * 2, np.nan, np.float64))
+        tb, cb = self.buf(np.full(s, np.nan, np.float32)), self.buf(np.full(3 * s, 0x5A5A5A5A, np.int32))
+        fb, db = self.buf(np.full(s, np.nan, np.float64)), self.buf(np.full(s, -777, np.int32))
+        rc = self.lib.gcnhip_threshold_scan(self.ctx, pk.ptr, nk.ptr, stride, stride if n is None else int(n), s, pb.ptr, nb.ptr, float(beta), work.ptr,
+                                            tb.ptr, cb.ptr, fb.ptr, db.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_threshold_scan: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return tb.download(), cb.download().reshape(3, s), fb.download(), db.download()
+
     # ---- node embeddings (csrc/embed.hip): the table is uploaded with row stride ld and NaN padding
     def _embed_inputs(self, table, ld, inv_norm):
         table = np.ascontiguousarray(table, np.float32)
@@ -1125,6 +1144,23 @@ class Device:
             "gcnhip_bce_predict_rows")
         return unpack_multihot(bb.download()[:m], c), (qb.download()[:m] if qb else None)
 
+    def bce_predict_rows_thr(self, logits, thr, rows=None, prob=True, ld=None):
+        """gcnhip_bce_predict_rows_thr: (bool [len(rows), C] = logit >= thr[c] by the integer keys, sigmoid [len(rows), C] or None)"""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
+        m, wpr = rows.size, (c + 31) // 32
+        lb = self.padded(logits, ld)
+        rb = self.buf(rows if m else np.zeros(1, np.int32))
+        tb = self.buf(np.ascontiguousarray(thr, np.float32))
+        bb = self.buf(np.full((max(m, 1), wpr), 0xFFFFFFFF, np.uint32))
+        qb = self.buf(np.full((max(m, 1), c), np.nan, np.float32)) if prob else None
+        rc = self.lib.gcnhip_bce_predict_rows_thr(self.ctx, lb.ptr, ld, rb.ptr, m, c, tb.ptr, bb.ptr, wpr, qb.ptr if qb else None, c)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_bce_predict_rows_thr: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return unpack_multihot(bb.download()[:m], c), (qb.download()[:m] if qb else None)
+
     def confusion_rows(self, pred, truth, c, rows=None):
         """gcnhip_confusion_rows: (int32 [C, C] with [t, p] = listed rows of truth t predicted as p, listed rows in no cell).  pred,
         truth: int32 [n_table]; rows: the listed rows (repeats allowed), None: every row.  The output buffers are uploaded as
@@ -1155,6 +1191,25 @@ class Device:
         cb = self.buf(np.full(3 * c, 0x5A5A5A5A, np.int32))
         _ck(self.lib, self.lib.gcnhip_bce_class_counts_rows(self.ctx, lb.ptr, ld, tb.ptr, words.shape[1], rb.ptr if rb else None, int(m), c,
                                                              cb.ptr), "gcnhip_bce_class_counts_rows")
+        return cb.download().reshape(3, c)
+
+    def bce_class_counts_rows_thr(self, logits, truth, thr, rows=None, ld=None):
+        """gcnhip_bce_class_counts_rows_thr: int32 [3, C] = TP, FP, FN per class over the listed rows (None: every row) of a logit
+        table; truth: bool [n, C] (packed here into multi-hot words); class c is predicted when its logit is >= thr[c] by the
+        integer keys."""
+        logits = np.asarray(logits, np.float32)
+        n, c = logits.shape
+        ld = ld or c
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        m = n if rows is None else rows.size
+        words = pack_multihot(truth)
+        lb, tb = self.padded(logits, ld), self.buf(words)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        hb = self.buf(np.ascontiguousarray(thr, np.float32))
+        cb = self.buf(np.full(3 * c, 0x5A5A5A5A, np.int32))
+        rc = self.lib.gcnhip_bce_class_counts_rows_thr(self.ctx, lb.ptr, ld, tb.ptr, words.shape[1], rb.ptr if rb else None, int(m), c, hb.ptr, cb.ptr)
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_bce_class_counts_rows_thr: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return cb.download().reshape(3, c)
 
     def accuracy(self, logits, truth, ld=None):
@@ -1244,6 +1299,7 @@ class Device:
 
 RANK_SENTINEL = 0xFFFFFFFF          # the padding of the key tables of csrc/ranking.hip: no score's key
 RANK_STATS_BLOCKS = 32              # GCNHIP_RANK_STATS_BLOCKS of include/gcnhip_driver.h
+THRESHOLD_SCAN_BLOCKS = 32          # GCNHIP_THRESHOLD_SCAN_BLOCKS of include/gcnhip_driver.h
 
 
 def __getattr__(name):

@@ -293,6 +293,30 @@ int gcnhip_rank_keys(gcnhip_ctx *ctx, const float *table, int ld, int n_table, c
 int gcnhip_sort_segments_u32(gcnhip_ctx *ctx, uint32_t *keys, uint32_t *scratch, int n, int segments, int64_t stride);
 int gcnhip_rank_stats(gcnhip_ctx *ctx, const uint32_t *pos_keys, const uint32_t *neg_keys, int64_t stride, int n, int segments, const int32_t *d_pos,
                       const int32_t *d_neg, void *d_work, int64_t *d_u2, double *d_ap_sum);
+/* ---- multi-label decision thresholds (thresholds.hip; beyond the reference: one cut per class instead of the training rule z > 0) ----
+ * Rule: with a threshold t[c], class c is predicted for a row exactly when its logit z is not NaN and key(z) >= key(t[c]), key()
+ * as above — z >= t[c] in exact real comparison (-0.0 == +0.0), made on the integer keys, so denormal logits and thresholds
+ * behave the same whatever the float denormal mode.  A NaN threshold has no key: its class is predicted for no row.
+ * gcnhip_threshold_scan: the sorted tables and valid lengths of gcnhip_rank_stats (d_pos[c] / d_neg[c] clamped to [0, n]).  For
+ *   every class c < segments with P positives and N negatives the candidates are the keys k of its positives; at a cut TP =
+ *   #{pos >= k}, FP = #{neg >= k}, FN = P - TP (exact integers), and in float64 without contraction w = beta * beta, num =
+ *   (1.0 + w) * TP, den = num + w * FN + FP, F = num / den.  The winner has the largest F, among equal F the largest key.
+ *   d_thr[c] = the float of the winning key, d_counts int32 [3 * segments] = {TP | FP | FN} at it, d_f[c] = its F, d_defined[c] =
+ *   1.  P == 0: d_defined[c] = 0, d_thr[c] = 0.0f, TP = FN = 0, FP = #{neg >= key(0)}, F = 0.  The max over (F, key) commutes and
+ *   associates: every reduction order gives the same bits, two launches give the same bits; no atomics.  Grid
+ *   (GCNHIP_THRESHOLD_SCAN_BLOCKS, segments) and a fold launch.  d_work: segments * GCNHIP_THRESHOLD_SCAN_BLOCKS * 16 bytes,
+ *   8-byte aligned (the work block of gcnhip_rank_stats serves).  Refused with a message: beta not finite or <= 0, n > 2^24,
+ *   stride < max(n, 1), segments outside 1..65535, a misaligned work block. */
+#define GCNHIP_THRESHOLD_SCAN_BLOCKS 32
+int gcnhip_threshold_scan(gcnhip_ctx *ctx, const uint32_t *pos_keys, const uint32_t *neg_keys, int64_t stride, int n, int segments, const int32_t *d_pos,
+                          const int32_t *d_neg, double beta, void *d_work, float *d_thr, int32_t *d_counts, double *d_f, int32_t *d_defined);
+/* gcnhip_bce_predict_rows and gcnhip_bce_class_counts_rows (below) with the rule above in place of z > 0: thr f32 [num_classes] on
+ * the device.  Arguments, layouts, limits (1 <= num_classes <= 256) and determinism are theirs; prob stays sigmoid(z_c).  Neither
+ * reads thr on the host: a caller that must refuse a NaN threshold checks its own copy. */
+int gcnhip_bce_predict_rows_thr(gcnhip_ctx *ctx, const float *logits, int ld, const int32_t *d_rows, int n_rows, int num_classes, const float *thr,
+                                uint32_t *bits, int words_per_row, float *prob, int ld_prob);
+int gcnhip_bce_class_counts_rows_thr(gcnhip_ctx *ctx, const float *logits, int ld, const uint32_t *truth_bits, int words_per_row, const int32_t *d_rows,
+                                     int n, int num_classes, const float *thr, int32_t *counts);
 /* ---- node embeddings (embed.hip; beyond the reference: what a GCN learns, taken out without leaving the device) ----
  * All entry points read an f32 table [n_table x ld] with 1 <= dim <= 256 and dim <= ld, rows of any stride and alignment;
  * columns [dim, ld) are never read as values.  Score of rows (q, c): their f32 dot product (inv_norm == NULL, metric "dot"),

@@ -279,6 +279,34 @@ int gcnhost_model_ranking(gcnhost_model *m, int split, const int *nodes, int n, 
                           int64_t *neg, int64_t *invalid, int64_t *unlabelled, int64_t *rows, float *scores, int64_t scores_cap);
 int gcnhost_ranking_report(int num_classes, const int64_t *u2, const double *ap_sum, const int64_t *pos, const int64_t *neg, double *auc, double *ap,
                            int32_t *auc_defined, int32_t *ap_defined, double *summary);
+/* Multi-label decision thresholds (beyond the reference; ModelQueries::tune_thresholds, kernels in csrc/thresholds.hip): one cut per
+ * class on the logit in place of the training rule logit > 0.  Rule: class c is predicted for a row exactly when its logit z is not
+ * NaN and z >= thr[c], compared on the order-preserving integer keys of gcnhip_rank_keys (-0.0 == +0.0; denormals as the numbers
+ * they are).  Multi-label models, one rank, at most 256 classes; all hold gcnhost_model_predict's contract (the call synchronises
+ * first, the training state is untouched).
+ *
+ * gcnhost_model_tune_thresholds: rows as gcnhost_model_evaluate takes them (split 1..3, or split == 0 with the `nodes` query).  Per
+ * class c over the listed rows whose logit is not NaN, P positives and N negatives (pos / neg; invalid[c] = the NaN rows): the
+ * candidates are the logits of the positives; at a cut TP / FP = the positives / negatives scored not lower, FN = P - TP, and in
+ * float64, in this order, w = beta * beta, num = (1 + w) TP, den = num + w FN + FP, F = num / den.  thr[c] = the candidate with the
+ * largest F, the highest one among equal F; tp / fp / fn [C] its counts, f[c] its F, defined[c] = 1.  P == 0: defined[c] = 0,
+ * thr[c] = 0, tp = fn = 0, fp = the negatives scored >= 0, f = 0.  beta finite and > 0; at most 2^24 listed rows; scratch_bytes as
+ * for gcnhost_model_ranking (the same batches, the same bits in every batching).  Only these O(C) numbers cross to the host.
+ * *rows (may be NULL) = the listed rows.
+ * gcnhost_model_predict_multilabel_thr / gcnhost_model_evaluate_thr: gcnhost_model_predict_multilabel and the multi-label
+ * gcnhost_model_evaluate (counts [3 x output_dim] = TP, FP, FN) deciding by thr [n_thr]; prob stays the sigmoid.  Refused with a
+ * message: n_thr != output_dim, a NaN threshold, more than one rank, a single-label model.
+ * gcnhost_thresholds_read / _write, host only (host/thresholds.h): a text file, one line per class, the first token the threshold
+ * as %.9g (exact for every float32), everything from '#' on ignored.  read: *num_classes > 0 on entry = the count the file must
+ * hold, 0 = take it from the file; thr may be NULL (for the count).  write: pos .. f (all six, or all NULL) are appended to each
+ * line as `# class c pos P neg N tp .. fp .. fn .. f ..`.  A NaN threshold is refused by both. */
+int gcnhost_model_tune_thresholds(gcnhost_model *m, int split, const int *nodes, int n, double beta, size_t scratch_bytes, float *thr, int64_t *tp,
+                                  int64_t *fp, int64_t *fn, double *f, int64_t *pos, int64_t *neg, int64_t *invalid, int32_t *defined, int64_t *rows);
+int gcnhost_model_predict_multilabel_thr(gcnhost_model *m, const int *nodes, int n, const float *thr, int n_thr, uint32_t *bits, float *prob);
+int gcnhost_model_evaluate_thr(gcnhost_model *m, int split, const int *nodes, int n, const float *thr, int n_thr, int64_t *counts, int64_t *rows_counted);
+int gcnhost_thresholds_read(const char *path, int *num_classes, float *thr);
+int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr, const int64_t *pos, const int64_t *neg, const int64_t *tp,
+                             const int64_t *fp, const int64_t *fn, const double *f);
 /* Node embeddings (ModelQueries, host/queries.h; kernels in csrc/embed.hip): the hidden matrix H1 = ReLU(A^.X.W1) of one evaluation
  * forward with the current weights (no dropout), as variable 3 stores it (a factored model keeps dinv[r] on row r; cosine scores
  * and normalised rows do not depend on it), queried on the device.  Ids are DATASET node ids.  predict's contract: training state
