@@ -123,6 +123,12 @@ int gcnhip_ctx_set_corun(gcnhip_ctx *c, int on) {
     return 0;
 }
 
+int gcnhip_ctx_compute_units(const gcnhip_ctx *c, int *count) {
+    if (!c || !count) return -1;
+    *count = c->n_cu;
+    return 0;
+}
+
 int gcnhip_ctx_sync(gcnhip_ctx *c) { GCNHIP_TRY(hipStreamSynchronize(c->stream)); return 0; }
 void *gcnhip_ctx_stream(gcnhip_ctx *c) { return (void *)c->stream; }
 

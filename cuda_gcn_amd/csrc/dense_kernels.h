@@ -561,6 +561,28 @@ static int launch_atb(gcnhip_ctx *c, const float *A, int lda, const float *Bm, i
     return 0;
 }
 
+// What launch_rowstream decides from the operands' strides and addresses alone.  fits == false: K is too long for an
+// LDS-resident operand (gfx950: 160 KiB per CU) and nothing is launched — a caller with another launch in front of this
+// one (the backward entry points: db, then da) asks BEFORE that launch, so that a refused call writes nothing.
+struct RowStreamPlan { bool vec, staged, fits; int vec_out, NT, gy, Kp; size_t lds; };
+static inline RowStreamPlan rowstream_plan(const float *A, int lda, const float *C, int ldc, int K, int Nc, const float *H, int ldh,
+                                           const uint32_t *hbits) {
+    RowStreamPlan q;
+    q.vec = lda % 4 == 0 && aligned16(A);
+    // 16-byte stores of whole column quads (the ragged tail of Nc % 4 != 0 goes out as single floats; padding columns are
+    // never written)
+    q.vec_out = (ldc % 4 == 0 && aligned16(C) && (!H || hbits || (ldh % 4 == 0 && aligned16(H)))) ? 1 : 0;
+    if (!q.vec) q.vec_out = q.vec_out && Nc >= 64;    // the unaligned-A kernels: staged epilogue as before
+    const int nt_total = ceil_div(Nc, 16);
+    q.NT = nt_total >= 8 ? 8 : (nt_total > 4 ? 8 : (nt_total > 3 ? 4 : nt_total));
+    q.gy = ceil_div(nt_total, q.NT);
+    q.Kp = (K + 15) / 16 * 16;
+    q.staged = q.vec_out && !q.vec;            // only the unaligned-A kernels' epilogue goes through LDS
+    q.lds = ((size_t)q.Kp * (q.NT * 16 + 4) + (q.staged ? 4 * 16 * (q.NT * 16 + 4) : 0)) * sizeof(float);   // Bs (+ 4 waves' C staging)
+    q.fits = q.lds <= 156 * 1024;
+    return q;
+}
+
 // C[m x Nc] = A[m x K] . Bs  (Bs from B, optionally transposed), optional epilogue
 static int launch_rowstream(gcnhip_ctx *c, const float *A, int lda, const float *B, int ldb, int transB,
                             float *C, int ldc, int m, int K, int Nc, const float *H, int ldh, float scale,
@@ -571,18 +593,12 @@ static int launch_rowstream(gcnhip_ctx *c, const float *A, int lda, const float 
     a.hbits = hbits; a.wpr = wpr;
     a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.transB = transB; a.C = C; a.ldc = ldc;
     a.m = m; a.K = K; a.Nc = Nc; a.H = H; a.ldh = ldh; a.scale = scale;
-    const bool vec = lda % 4 == 0 && aligned16(A);
-    // 16-byte stores of whole column quads (the ragged tail of Nc % 4 != 0 goes out as single floats; padding columns are
-    // never written)
-    a.vec_out = (ldc % 4 == 0 && aligned16(C) && (!H || hbits || (ldh % 4 == 0 && aligned16(H)))) ? 1 : 0;
-    if (!vec) a.vec_out = a.vec_out && Nc >= 64;    // the unaligned-A kernels: staged epilogue as before
-    const int nt_total = ceil_div(Nc, 16);
-    const int NT = nt_total >= 8 ? 8 : (nt_total > 4 ? 8 : (nt_total > 3 ? 4 : nt_total));
-    const int gy = ceil_div(nt_total, NT);
-    const int Kp = (K + 15) / 16 * 16;
-    const bool staged = a.vec_out && !vec;     // only the unaligned-A kernels' epilogue goes through LDS
-    const size_t lds = ((size_t)Kp * (NT * 16 + 4) + (staged ? 4 * 16 * (NT * 16 + 4) : 0)) * sizeof(float);   // Bs (+ 4 waves' C staging)
-    if (lds > 156 * 1024) return -1;          // K too long for an LDS-resident operand (gfx950: 160 KiB per CU)
+    const RowStreamPlan q = rowstream_plan(A, lda, C, ldc, K, Nc, H, ldh, hbits);
+    if (!q.fits) return -1;
+    const bool vec = q.vec;
+    a.vec_out = q.vec_out;
+    const int NT = q.NT, gy = q.gy, Kp = q.Kp;
+    const size_t lds = q.lds;
     int gx = ceil_div(ceil_div(m, 16), 4);
     int per_cu = lds > 76 * 1024 ? 1 : (lds > 32 * 1024 ? 2 : 4);
     const int cap = c->n_cu * per_cu;

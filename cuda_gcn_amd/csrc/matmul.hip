@@ -50,6 +50,15 @@ static int launch_class_bwd(gcnhip_ctx *c, const float *a, int lda, const float 
     return 0;
 }
 
+// da = mask . f_r . (dc . b^T) on the row-stream kernels (h / bits: the mask source, both NULL: none).  fits_only: launch
+// nothing and answer what the launch would — 0, or -1 when W2 is too long for LDS.  The backward entry points write their
+// arguments once, ask first and launch db in between, so that a refused call writes nothing.
+static int da_product(gcnhip_ctx *c, bool fits_only, const float *dc, int lddc, const float *b, int ldb, float *da, int ldda, int m, int n, int p,
+                      const float *h, int ldh, float scale, const uint32_t *bits, int wpr, const float *rowscale) {
+    if (fits_only) return rowstream_plan(dc, lddc, da, ldda, p, n, h, ldh, bits).fits ? 0 : -1;
+    return launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, h, ldh, scale, bits, wpr, rowscale);
+}
+
 static int matmul_bwd_impl(gcnhip_ctx *c, const float *a, int lda, const float *b, int ldb,
                            const float *dc, int lddc, float *da, int ldda, float *db, int lddb,
                            int m, int n, int p, int fused, float scale) {
@@ -59,15 +68,14 @@ static int matmul_bwd_impl(gcnhip_ctx *c, const float *a, int lda, const float *
         if (db) for (int j = 0; j < n; j++) GCNHIP_TRY(hipMemsetAsync(db + (size_t)j * lddb, 0, p * sizeof(float), c->stream));
         return 0;
     }
+    // da = dc . b^T, module.cpp:34,37
+    auto da_call = [&](bool fits_only) { return da_product(c, fits_only, dc, lddc, b, ldb, da, ldda, m, n, p, fused ? a : nullptr, lda, scale, nullptr, 0, nullptr); };
+    if (da && da_call(true)) return -1;
     if (db) {                                 // db = a^T . dc, module.cpp:35 (a is still the forward input here)
         const int rc = launch_atb(c, a, lda, dc, lddc, db, lddb, m, n, p, 0, 0.f, 0, nullptr, 0, nullptr);
         if (rc) return rc;
     }
-    if (da) {                                 // da = dc . b^T, module.cpp:34,37
-        const int rc = launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, fused ? a : nullptr, lda, scale);
-        if (rc) return rc;
-    }
-    return 0;
+    return da ? da_call(false) : 0;
 }
 
 int gcnhip_matmul_bwd(gcnhip_ctx *c, const float *a, int lda, const float *b, int ldb,
@@ -91,11 +99,15 @@ int gcnhip_matmul_bwd_fused_bits(gcnhip_ctx *c, const float *a, int lda, const f
     if (db && lddb < p) return -1;
     if (words_per_row * 32 < n) return -1;
     if (m == 0) return matmul_bwd_impl(c, a, lda, b, ldb, dc, lddc, nullptr, 0, db, lddb, m, n, p, 0, 1.f);
+    auto da_call = [&](bool fits_only) {
+        return da_product(c, fits_only, dc, lddc, b, ldb, da, ldda, m, n, p, nullptr, 0, relu_dropout_scale, pos_bits, words_per_row, nullptr);
+    };
+    if (da_call(true)) return -1;
     if (db) {
         const int rc = launch_atb(c, a, lda, dc, lddc, db, lddb, m, n, p, 0, 0.f, 0, nullptr, 0, nullptr);
         if (rc) return rc;
     }
-    return launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, nullptr, 0, relu_dropout_scale, pos_bits, words_per_row);
+    return da_call(false);
 }
 
 // Every form of the fused backward behind one call, with an optional factor per row of da (the factored aggregation,
@@ -116,12 +128,16 @@ int gcnhip_matmul_bwd_ex(gcnhip_ctx *c, const float *a, int lda, const float *b,
     }
     if (db && c->opt.gemm_bf16x3 >= 1 && cls_bwd_fits(a, lda, dc, lddc, da, ldda, pos_bits, words_per_row, m, n, p))
         return launch_class_bwd(c, a, lda, b, ldb, dc, lddc, da, ldda, db, lddb, m, p, relu_dropout_scale, pos_bits, d_da_row_scale);
+    auto da_call = [&](bool fits_only) {
+        return da_product(c, fits_only, dc, lddc, b, ldb, da, ldda, m, n, p, pos_bits ? nullptr : a, lda, relu_dropout_scale, pos_bits, words_per_row,
+                          d_da_row_scale);
+    };
+    if (da_call(true)) return -1;
     if (db) {
         const int rc = launch_atb(c, a, lda, dc, lddc, db, lddb, m, n, p, 0, 0.f, 0, nullptr, 0, nullptr);
         if (rc) return rc;
     }
-    return launch_rowstream(c, dc, lddc, b, ldb, 1, da, ldda, m, p, n, pos_bits ? nullptr : a, lda, relu_dropout_scale, pos_bits, words_per_row,
-                            d_da_row_scale);
+    return da_call(false);
 }
 
 // da for ALL m rows from a bit mask instead of the forward activations (multi-GPU: every rank rebuilds the

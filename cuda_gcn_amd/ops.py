@@ -746,35 +746,6 @@ class Device:
                                                                   elem_offset, km.ptr if km else None, bits.ptr, wpr), "graphsum_relu_dropout_bits")
         return out.download()[:, :dim], bits.download()
 
-    def matmul_bwd_fused_bits(self, a, b, dc, scale, bits):
-        a, b, dc = (np.asarray(t, np.float32) for t in (a, b, dc))
-        m, n = a.shape
-        p = b.shape[1]
-        ldp = (p + 3) // 4 * 4
-        ab, bb, dcb = self.buf(a), self.padded(b, ldp), self.padded(dc, ldp)
-        bt = self.buf(np.ascontiguousarray(bits, np.uint32))
-        da = self.buf(np.full((m, n), np.nan, np.float32))
-        db = self.buf(np.full((n, ldp), np.nan, np.float32))
-        _ck(self.lib, self.lib.gcnhip_matmul_bwd_fused_bits(self.ctx, ab.ptr, n, bb.ptr, ldp, dcb.ptr, ldp, da.ptr, n, db.ptr, ldp, m, n, p, scale,
-                                                             bt.ptr, bits.shape[1]), "gcnhip_matmul_bwd_fused_bits")
-        return da.download(), db.download()[:, :p]
-
-    def matmul_bwd_ex(self, a, b, dc, scale, bits, rowscale=None, ldp=None, p=None):
-        """gcnhip_matmul_bwd_ex: da = mask(bits) . (scale * rowscale[r]) . (dc . b^T), db = a^T . dc; dc may come with its
-        padding columns (p = the real width)"""
-        a, b, dc = (np.asarray(t, np.float32) for t in (a, b, dc))
-        m, n = a.shape
-        p = p or b.shape[1]
-        ldp = ldp or (p + 3) // 4 * 4
-        ab, bb, dcb = self.buf(a), self.padded(b, ldp), self.padded(dc, ldp)
-        bt = self.buf(np.ascontiguousarray(bits, np.uint32))
-        rs = self.buf(np.ascontiguousarray(rowscale, np.float32)) if rowscale is not None else None
-        da = self.buf(np.full((m, n), np.nan, np.float32))
-        db = self.buf(np.full((n, ldp), np.nan, np.float32))
-        _ck(self.lib, self.lib.gcnhip_matmul_bwd_ex(self.ctx, ab.ptr, n, bb.ptr, ldp, dcb.ptr, ldp, da.ptr, n, db.ptr, ldp, m, n, p, scale,
-                                                     bt.ptr, bits.shape[1], rs.ptr if rs else None), "gcnhip_matmul_bwd_ex")
-        return da.download(), db.download()[:, :p]
-
     # ---- the first-layer products.  Beside the operands: vals (a value array of the caller's instead of the object's own), a
     # row stride per table, shift = {operand name: floats} (that operand starts so many floats into its allocation: an
     # address that is not a multiple of 16 bytes), whole / fill (return the WHOLE written table, uploaded as `fill`, padding
@@ -892,30 +863,91 @@ class Device:
         _ck(self.lib, self.lib.gcnhip_spmm_bwd_finish(self.ctx, f.h, wptr, ld_dw, p), "gcnhip_spmm_bwd_finish")
         return self._table(dw, sh.get("out", 0), f.n_cols, ld_dw, p, whole)
 
-    def matmul_fwd(self, a, b, lda=None, ldb=None, ldc=None):
+    # ---- the Matmul products.  As above: a row stride per operand, shift = {operand name: floats} ("a", "b", "c", "dc", "da",
+    # "db", "rowscale"; "bits": words), whole / fill for every output; da=False / db=False / bits=None pass NULL where the
+    # entry point takes it.
+    def matmul_fwd(self, a, b, lda=None, ldb=None, ldc=None, shift=None, whole=False, fill=np.nan):
         a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
         m, n = a.shape
         p = b.shape[1]
         lda, ldb, ldc = lda or n, ldb or p, ldc or p
-        ab, bb = self.padded(a, lda), self.padded(b, ldb)
-        cb = self.buf(np.full((m, ldc), np.nan, np.float32))
-        _ck(self.lib, self.lib.gcnhip_matmul_fwd(self.ctx, ab.ptr, lda, bb.ptr, ldb, cb.ptr, ldc, m, n, p), "gcnhip_matmul_fwd")
-        return cb.download()[:, :p]
+        sh = shift or {}
+        ab, aptr, _ = self._operand(a, lda, sh.get("a", 0))
+        bb, bptr, _ = self._operand(b, ldb, sh.get("b", 0))
+        cb, cptr, _ = self._operand(np.zeros((m, 0), np.float32), ldc, sh.get("c", 0), fill)
+        _ck(self.lib, self.lib.gcnhip_matmul_fwd(self.ctx, aptr, lda, bptr, ldb, cptr, ldc, m, n, p), "gcnhip_matmul_fwd")
+        return self._table(cb, sh.get("c", 0), m, ldc, p, whole)
 
-    def matmul_bwd(self, a, b, dc, lda=None, ldb=None, lddc=None, fused_scale=None):
+    def _matmul_bwd_call(self, entry, a, b, dc, m, n, p, ld, scale=None, bits=None, rowscale=None, da=True, db=True, shift=None,
+                         whole=False, fill=np.nan):
+        """one call of gcnhip_matmul_<entry>; ld = dict(a, b, dc, da, db) -> (da, db) tables (None where not asked for)"""
+        sh = shift or {}
+        aptr = None
+        if a is not None:
+            ab, aptr, _ = self._operand(a, ld["a"], sh.get("a", 0))
+        bb, bptr, _ = self._operand(b, ld["b"], sh.get("b", 0))
+        dcb, dcptr, _ = self._operand(dc, ld["dc"], sh.get("dc", 0))
+        dab = dbb = daptr = dbptr = btptr = rsptr = None
+        if da:
+            dab, daptr, _ = self._operand(np.zeros((m, 0), np.float32), ld["da"], sh.get("da", 0), fill)
+        if db:
+            dbb, dbptr, _ = self._operand(np.zeros((n, 0), np.float32), ld["db"], sh.get("db", 0), fill)
+        wpr = 0
+        if bits is not None:
+            bits = np.ascontiguousarray(bits, np.uint32)
+            wpr = bits.shape[1]
+            s = sh.get("bits", 0)
+            flat = np.full(s + (bits.shape[0] + self.SLACK_ROWS) * wpr + 4, 0xDEADBEEF, np.uint32)
+            flat[s:s + bits.size] = bits.ravel()
+            bt = self.buf(flat)
+            btptr = bt.ptr + 4 * s
+        if rowscale is not None:
+            rs, rsptr, _ = self._operand(np.ascontiguousarray(rowscale, np.float32).reshape(1, -1), max(int(np.size(rowscale)), 1), sh.get("rowscale", 0))
+        lib, x = self.lib, self.ctx
+        head = (x, aptr, ld["a"], bptr, ld["b"], dcptr, ld["dc"], daptr, ld["da"], dbptr, ld["db"], m, n, p)
+        if entry == "bwd":
+            rc = lib.gcnhip_matmul_bwd(*head)
+        elif entry == "bwd_fused":
+            rc = lib.gcnhip_matmul_bwd_fused(*head, scale)
+        elif entry == "bwd_fused_bits":
+            rc = lib.gcnhip_matmul_bwd_fused_bits(*head, scale, btptr, wpr)
+        elif entry == "bwd_ex":
+            rc = lib.gcnhip_matmul_bwd_ex(*head, scale, btptr, wpr, rsptr)
+        else:
+            assert entry == "bwd_da_bits"
+            rc = lib.gcnhip_matmul_bwd_da_bits(x, bptr, ld["b"], dcptr, ld["dc"], daptr, ld["da"], m, n, p, btptr, wpr, scale)
+        _ck(lib, rc, "gcnhip_matmul_" + entry)
+        return (self._table(dab, sh.get("da", 0), m, ld["da"], n, whole) if da else None,
+                self._table(dbb, sh.get("db", 0), n, ld["db"], p, whole) if db else None)
+
+    def matmul_bwd(self, a, b, dc, lda=None, ldb=None, lddc=None, fused_scale=None, ldda=None, lddb=None, da=True, db=True, **kw):
+        """gcnhip_matmul_bwd, or gcnhip_matmul_bwd_fused when fused_scale is given (mask = a > 0)"""
         a, b, dc = (np.asarray(t, np.float32) for t in (a, b, dc))
         m, n = a.shape
         p = b.shape[1]
         lda, ldb, lddc = lda or n, ldb or p, lddc or p
-        ab, bb, dcb = self.padded(a, lda), self.padded(b, ldb), self.padded(dc, lddc)
-        da = self.buf(np.full((m, lda), np.nan, np.float32))
-        db = self.buf(np.full((n, ldb), np.nan, np.float32))
-        if fused_scale is None:
-            _ck(self.lib, self.lib.gcnhip_matmul_bwd(self.ctx, ab.ptr, lda, bb.ptr, ldb, dcb.ptr, lddc, da.ptr, lda, db.ptr, ldb, m, n, p), "gcnhip_matmul_bwd")
-        else:
-            _ck(self.lib, self.lib.gcnhip_matmul_bwd_fused(self.ctx, ab.ptr, lda, bb.ptr, ldb, dcb.ptr, lddc, da.ptr, lda, db.ptr, ldb,
-                                                            m, n, p, fused_scale), "gcnhip_matmul_bwd_fused")
-        return da.download()[:, :n], db.download()[:, :p]
+        ld = dict(a=lda, b=ldb, dc=lddc, da=ldda or lda, db=lddb or ldb)
+        return self._matmul_bwd_call("bwd" if fused_scale is None else "bwd_fused", a, b, dc, m, n, p, ld, scale=fused_scale, da=da, db=db, **kw)
+
+    def matmul_bwd_fused_bits(self, a, b, dc, scale, bits, lda=None, ldb=None, lddc=None, ldda=None, lddb=None, db=True, **kw):
+        a, b, dc = (np.asarray(t, np.float32) for t in (a, b, dc))
+        m, n = a.shape
+        p = b.shape[1]
+        ldp = (p + 3) // 4 * 4
+        ld = dict(a=lda or n, b=ldb or ldp, dc=lddc or ldp, da=ldda or n, db=lddb or ldp)
+        return self._matmul_bwd_call("bwd_fused_bits", a, b, dc, m, n, p, ld, scale=scale, bits=bits, db=db, **kw)
+
+    def matmul_bwd_ex(self, a, b, dc, scale, bits, rowscale=None, ldp=None, p=None, lda=None, ldb=None, lddc=None, ldda=None, lddb=None,
+                      db=True, **kw):
+        """gcnhip_matmul_bwd_ex: da = mask . (scale * rowscale[r]) . (dc . b^T), mask = bits (None: a > 0), db = a^T . dc; dc may
+        come with its padding columns (p = the real width); a = None with db=False and bits given"""
+        b, dc = np.asarray(b, np.float32), np.asarray(dc, np.float32)
+        a = np.asarray(a, np.float32) if a is not None else None
+        m, n = dc.shape[0], b.shape[0]
+        p = p or b.shape[1]
+        ldp = ldp or (p + 3) // 4 * 4
+        ld = dict(a=lda or n, b=ldb or ldp, dc=lddc or ldp, da=ldda or n, db=lddb or ldp)
+        return self._matmul_bwd_call("bwd_ex", a, b, dc, m, n, p, ld, scale=scale, bits=bits, rowscale=rowscale, db=db, **kw)
 
     def pack_positive(self, h, ld=None):
         """bit (r, c) = h[r, c] > 0, 32 columns per little-endian word -> uint32 [rows, ceil(dim/32)]"""
@@ -928,17 +960,12 @@ class Device:
         _ck(self.lib, self.lib.gcnhip_pack_positive(self.ctx, hb.ptr, ld, rows, dim, bits.ptr, wpr), "gcnhip_pack_positive")
         return bits.download()
 
-    def matmul_bwd_da_bits(self, b, dc, bits, scale, ldb=None, lddc=None, ldda=None):
+    def matmul_bwd_da_bits(self, b, dc, bits, scale, ldb=None, lddc=None, ldda=None, **kw):
         b, dc = np.asarray(b, np.float32), np.asarray(dc, np.float32)
-        bits = np.ascontiguousarray(bits, np.uint32)
         n, p = b.shape
         m = dc.shape[0]
-        ldb, lddc, ldda = ldb or p, lddc or p, ldda or n
-        bb, dcb, bt = self.padded(b, ldb), self.padded(dc, lddc), self.buf(bits)
-        da = self.buf(np.full((m, ldda), np.nan, np.float32))
-        _ck(self.lib, self.lib.gcnhip_matmul_bwd_da_bits(self.ctx, bb.ptr, ldb, dcb.ptr, lddc, da.ptr, ldda, m, n, p,
-                                                          bt.ptr, bits.shape[1], scale), "gcnhip_matmul_bwd_da_bits")
-        return da.download()[:, :n]
+        ld = dict(a=0, b=ldb or p, dc=lddc or p, da=ldda or n, db=0)
+        return self._matmul_bwd_call("bwd_da_bits", None, b, dc, m, n, p, ld, scale=scale, bits=bits, db=False, **kw)[0]
 
     def relu_fwd(self, x, training=True):
         x = np.ascontiguousarray(x, np.float32).reshape(-1)

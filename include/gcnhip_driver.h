@@ -26,6 +26,8 @@ typedef struct gcnhip_rowset gcnhip_rowset;   /* a registered subset of an adjac
  * neighbour: measured on the two-stream epoch, 294 epochs/s with the persistent form on the lane against 297 with tiles.
  * Results do not depend on the hint beyond the order of floating-point sums of the two forms (each within the tested bound). */
 int gcnhip_ctx_set_corun(gcnhip_ctx *ctx, int on);
+/* The compute units of the context's device: every launcher caps its grid by a multiple of this count. */
+int gcnhip_ctx_compute_units(const gcnhip_ctx *ctx, int *count);
 /* Read-back without stalling the producer: page-locked host memory and a device-to-host copy that is only ENQUEUED on
  * ctx's stream (wait for it with an event recorded behind it + gcnhip_event_sync).  HipGCN::run() uses them to
  * print epoch e's line while epochs e+1.. are already running: behind a group of epochs, the metrics rows of the group are
