@@ -130,6 +130,7 @@ GCNHIP_SYMBOLS = {
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_abs_colsum": (I, [P, P, I, P, I, I, I, P, P]),
+    "gcnhip_attach_gather": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, I, P, P, P, I, F]),
     "gcnhip_graph_remove_rowset": (I, [P, P, P]),
     "gcnhip_graph_scales": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "gcnhip_feat_scale_rows": (I, [P, P, P]),
@@ -242,6 +243,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_set_weights": (I, [P, P, P]),
     "gcnhost_model_predict": (I, [P, P, I, P, P, P]),
     "gcnhost_model_predict_multilabel": (I, [P, P, I, P, P]),
+    "gcnhost_attach_rows": (I, [I, P, I, P, P, I, P, P, P, P]),
+    "gcnhost_model_predict_new": (I, [P, P, P, P, I, P, P, P, I, P, P, P, P]),
     "gcnhost_model_evaluate": (I, [P, I, P, I, P, C.POINTER(I64), C.POINTER(I64)]),
     "gcnhost_model_propagate": (I, [P, P, I, F, I, F, F, P, P]),
     "gcnhost_model_label_propagation": (I, [P, F, I, I, P, P]),

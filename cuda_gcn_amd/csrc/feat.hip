@@ -58,6 +58,10 @@ int gcnhip_feat_create(gcnhip_ctx *c, gcnhip_feat **out, const int *h_indptr, co
         GCNHIP_TRY(hipMemset(f->values_pad, 0, (size_t)n_rows * f->ld_pad * sizeof(float)));
         GCNHIP_TRY(hipMemcpy2D(f->values_pad, (size_t)f->ld_pad * sizeof(float), f->values, (size_t)n_cols * sizeof(float),
                                (size_t)n_cols * sizeof(float), (size_t)n_rows, hipMemcpyDeviceToDevice));
+        // a device memset and a device-to-device copy return before they have run, on the null stream, which the context's
+        // non-blocking stream does not wait for: a product launched straight after the object is made (predict_new) must
+        // find the padded image complete
+        GCNHIP_TRY(hipStreamSynchronize(nullptr));
     }
     if (!dense) {
         if (!plan::indices_in_range(h_indices, nnz, n_cols)) return -1;

@@ -8,6 +8,7 @@
 #include <vector>
 #include "gcn.h"
 #include "queries.h"
+#include "attach.h"
 #include "cluster.h"
 #include "hip_check.h"
 #include "parser.h"
@@ -223,6 +224,24 @@ int gcnhost_model_predict(gcnhost_model *m, const int *nodes, int n, int32_t *pr
 }
 int gcnhost_model_predict_multilabel(gcnhost_model *m, const int *nodes, int n, uint32_t *bits, float *prob) {
     API_TRY({ m->gcn->queries().predict_multilabel(nodes, n, bits, prob); })
+}
+int gcnhost_attach_rows(int num_nodes, const int *g_indptr, int n_new, const int64_t *nbr_ptr, const int *nbr_ids, int mode, int32_t *out_ptr,
+                        int32_t *out_col, float *out_coef, int32_t *out_len) {
+    if (num_nodes < 0 || !g_indptr || !nbr_ptr || !out_ptr) { g_err = "new_node_rows: invalid argument"; return -1; }
+    std::vector<int> len((size_t)num_nodes);
+    for (int r = 0; r < num_nodes; r++) len[r] = g_indptr[r + 1] - g_indptr[r];
+    AttachRows rows;
+    if (gcn_attach_rows(num_nodes, len.data(), nullptr, n_new, nbr_ptr, nbr_ids, mode, &rows, &g_err) != 0) return -1;
+    std::copy(rows.ptr.begin(), rows.ptr.end(), out_ptr);
+    if (out_col) std::copy(rows.col.begin(), rows.col.end(), out_col);
+    if (out_coef) std::copy(rows.coef.begin(), rows.coef.end(), out_coef);
+    if (out_len) std::copy(rows.len.begin(), rows.len.end(), out_len);
+    return 0;
+}
+int gcnhost_model_predict_new(gcnhost_model *m, const int *x_indptr, const int *x_indices, const float *x_values, int n_new, const int64_t *nbr_ptr,
+                              const int *nbr_ids, const float *thr, int n_thr, int32_t *pred, float *prob, float *logp, uint32_t *bits) {
+    if (!m) { g_err = "gcnhost_model_predict_new: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().predict_new(x_indptr, x_indices, x_values, n_new, nbr_ptr, nbr_ids, thr, n_thr, pred, prob, logp, bits); })
 }
 int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
     if (!m || !counts) { g_err = "gcnhost_model_evaluate: invalid argument"; return -1; }

@@ -265,6 +265,7 @@ private:
     std::unique_ptr<ModelQueries> queries_;
     void forward_hooked(const HipGraphSum::Prediction *prediction, const HipGraphSum::Redirect *redirect);
     bool forward_hidden_only();                                // aggregate-first models: the hidden layer alone, stored; false: no such form
+    void forward_class_products();                             // an evaluation forward up to variable 4 = H1.W2, no logit aggregation
     gcnhip_graph *graph_bwd_out = nullptr;                     // `graph` without the edges whose source is outside the training split
     // HIPGCN_OVERLAP_EXCHANGE: `graph` and `graph_bwd_out` cut by column owner (own rows / other ranks' rows), the split
     // subsets of the last aggregation on both halves, and the exchange stream

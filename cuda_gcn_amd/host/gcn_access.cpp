@@ -49,6 +49,16 @@ void HipGCN::forward_hooked(const HipGraphSum::Prediction *prediction, const Hip
     if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
 }
 
+// The evaluation forward up to the class-layer product: variable 4 = H1.W2 of every row of this rank (dinv . H1.W2 on a factored
+// model), neither the logit aggregation nor the loss — what a query needs that aggregates those rows itself (predict_new).
+// Variable 1 = X.W1 is written on the way unless the model evaluates aggregate-first.  Training state stays as it was.
+void HipGCN::forward_class_products() {
+    refresh_input();
+    const std::vector<Module *> &list = eval_modules.empty() ? modules : eval_modules;
+    for (size_t i = 0; i + 2 < list.size(); i++) list[i]->forward(false);           // the last two: the logit aggregation, the loss
+    if (eval_modules.empty() || !static_cast<HipSparseMatmul *>(eval_modules[0])->hidden_not_stored) h1_from_fused_eval = false;
+}
+
 // The hidden matrix of an evaluation forward in variable 3 at the price of its own product: an aggregate-first model computes
 // ReLU((A^.X).W1) in one launch (what get_var(3) runs after a fused evaluation, so the bits are get_var's).  Other models have
 // no such form: the caller runs a whole hooked forward, whose hidden-width aggregation stores the matrix.

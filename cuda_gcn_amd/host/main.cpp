@@ -81,6 +81,14 @@
 //                            GCN_LOAD_WEIGHTS runs with 0 epochs; the line printed is `test_micro_f1_default=.. test_micro_f1_tuned=..
 //                            test_macro_f1_default=.. test_macro_f1_tuned=..`.  Both need GCN_MULTILABEL, one GPU and at most 256 classes,
 //                            and exclude each other.
+// Unseen nodes (beyond the reference; ModelQueries::predict_new, host/attach.h, csrc/attach.hip), after the test line and every
+// step above (at GCN_CALIBRATE's temperature, by GCN_THRESHOLDS' cuts); stdout is unchanged.  One GPU, f32 tables, hidden_dim at most 256:
+//   GCN_NEW_NODES=<stem>     <stem>.graph and <stem>.svmlight in the dataset's own text format, read with its parser and checked before
+//                            the GPU is touched: line i is new node N + i (N = the dataset's nodes), the ids it lists are in
+//                            [0, N + lines) — a dataset node, or another new node of the same files — its stored row is itself first,
+//                            then those ids, and no existing row changes.  The label column of the .svmlight file is read and ignored.
+//   GCN_NEW_PREDICT=<file>   the new nodes' predictions in GCN_PREDICT's line format, node ids N + i.  Works with GCN_LOAD_WEIGHTS
+//                            and 0 epochs: the dataset, its adjacency object and schedule are built once, not again per batch of nodes.
 // Node embeddings (beyond the reference; ModelQueries::embed / similar, kernels in csrc/embed.hip), after the test line and every
 // post-processing step above; stdout is unchanged.  One GPU, hidden_dim at most 256; single- and multi-label models alike:
 //   GCN_EMBED=<file>         one line per node of the dataset in id order: `node v1 ... vh`, the node's row of the hidden layer
@@ -313,6 +321,38 @@ int main(int argc, char **argv) {
         if (why) {
             std::cerr << "gcn-hip: GCN_EXPLAIN " << why << std::endl;
             return EXIT_FAILURE;
+        }
+    }
+
+    // new nodes: read with the dataset's own text parser and checked before the GPU is touched
+    const char *new_nodes_stem = getenv("GCN_NEW_NODES"), *new_predict_path = getenv("GCN_NEW_PREDICT");
+    if (new_nodes_stem && !*new_nodes_stem) new_nodes_stem = nullptr;
+    if (new_predict_path && !*new_predict_path) new_predict_path = nullptr;
+    GCNData new_nodes;
+    std::vector<int64_t> new_nbr_ptr;
+    std::vector<int> new_nbr_ids;
+    int n_new = 0;
+    if (new_nodes_stem || new_predict_path) {
+        GCNParams np = params;
+        std::string why;
+        if (!new_nodes_stem || !new_predict_path) why = "GCN_NEW_NODES=<stem> and GCN_NEW_PREDICT=<file> go together";
+        else if (env_int("GCN_GPUS", 1) > 1) why = "runs on one GPU (GCN_GPUS is above 1)";
+        else if (env_int("GCN_BF16_TABLES", 0)) why = "does not go with GCN_BF16_TABLES";
+        else if (params.hidden_dim > 256) why = "takes a hidden width of at most 256";
+        else if (!Parser::parse_rows(new_nodes_stem, &np, &new_nodes)) why = std::string("cannot read ") + new_nodes_stem + ".graph and " + new_nodes_stem + ".svmlight (one line per new node in both)";
+        else if (new_nodes.feature_index.indptr.back() > 0 && np.input_dim > params.input_dim)
+            why = "a feature column " + std::to_string(np.input_dim - 1) + " is outside the dataset's input width " + std::to_string(params.input_dim);
+        if (!why.empty()) {
+            std::cerr << "gcn-hip: GCN_NEW_NODES " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+        n_new = np.num_nodes;
+        // line i of the .graph file lists the ids of new node N + i; the parser's implicit first entry is not one of them
+        new_nbr_ptr.assign(1, 0);
+        for (int i = 0; i < n_new; i++) {
+            const std::vector<int> &gp = new_nodes.graph.indptr, &gi = new_nodes.graph.indices;
+            new_nbr_ids.insert(new_nbr_ids.end(), gi.begin() + gp[i] + 1, gi.begin() + gp[i + 1]);
+            new_nbr_ptr.push_back((int64_t)new_nbr_ids.size());
         }
     }
 
@@ -590,6 +630,35 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the explanations to ") + explain_path);
                 fprintf(stderr, "gcn-hip: explanations of %d test nodes written to %s\n", n, explain_path);
+            }
+            if (new_predict_path) {                            // one rank (checked above); at the temperature and by the cuts of the steps above
+                const int C = params.output_dim, N = params.num_nodes;
+                std::vector<int32_t> p(std::max(n_new, 1));
+                std::vector<float> q(std::max(n_new, 1));
+                std::vector<uint32_t> b((size_t)std::max(n_new, 1) * ml_wpr);
+                static const int no_column = 0;                // rows without a single feature: still a sparse X_new, not a dense one
+                const int *x_cols = new_nodes.feature_index.indices.empty() ? &no_column : new_nodes.feature_index.indices.data();
+                static const float no_value = 0.f;
+                const float *x_vals = new_nodes.feature_value.empty() ? &no_value : new_nodes.feature_value.data();
+                gcn.queries().predict_new(new_nodes.feature_index.indptr.data(), x_cols, x_vals, n_new,
+                                          new_nbr_ptr.data(), new_nbr_ids.data(), cuts.empty() ? nullptr : cuts.data(), (int)cuts.size(), p.data(),
+                                          multilabel_path ? nullptr : q.data(), nullptr, b.data());
+                FILE *f = fopen(new_predict_path, "w");
+                bool ok = f != nullptr;
+                for (int i = 0; ok && i < n_new; i++) {            // GCN_PREDICT's line format, node ids N + i
+                    if (!multilabel_path) {
+                        ok = fprintf(f, "%d %d %.6g\n", N + i, p[i], q[i]) > 0;
+                        continue;
+                    }
+                    std::string line = std::to_string(N + i);
+                    char sep = ' ';
+                    for (int c = 0; c < C; c++)
+                        if ((b[(size_t)i * ml_wpr + (c >> 5)] >> (c & 31)) & 1u) { line += sep; line += std::to_string(c); sep = ','; }
+                    ok = fprintf(f, "%s\n", line.c_str()) > 0;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the new nodes' predictions to ") + new_predict_path);
+                fprintf(stderr, "gcn-hip: predictions of %d new nodes (ids %d..%d) written to %s\n", n_new, N, N + n_new - 1, new_predict_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

@@ -144,6 +144,13 @@ bool Parser::parse() {
     return true;
 }
 
+bool Parser::parse_rows(const std::string &stem, GCNParams *p, GCNData *d) {
+    *d = GCNData();
+    Parser t(p, d, "", "-");
+    if (!t.parseGraph(stem + ".graph") || !t.parseNode(stem + ".svmlight")) return false;
+    return d->feature_index.indptr.size() == d->graph.indptr.size();
+}
+
 // ---- binary cache: header + raw arrays --------------------------------------
 namespace {
 const char MAGIC[8] = {'G', 'C', 'N', 'B', 'I', 'N', '0', '1'};

@@ -19,6 +19,11 @@ public:
     bool from_cache() const { return from_cache_; }          // the last parse() was served by <name>.gcnbin
     std::string cache_path() const { return root + name + ".gcnbin"; }
     static bool load_binary(const std::string &path, GCNParams *p, GCNData *d);
+    // <stem>.graph and <stem>.svmlight alone, by the parsers of parse() (no split file, no cache, nothing printed): rows that are
+    // not a dataset of their own — the new nodes of GCN_NEW_NODES.  d->graph rows carry the implicit first entry (the line's own
+    // index) as parse() stores them; p->num_nodes = the lines, p->input_dim = the largest column + 1.  false: a file is missing
+    // or the two do not have the same number of lines.
+    static bool parse_rows(const std::string &stem, GCNParams *p, GCNData *d);
 private:
     bool from_cache_ = false;
     std::string root, name;

@@ -1,14 +1,15 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
 //   reads   params, opt_.multilabel, env (context, comm), n_local, row_start(), node_order_ (query_rows' inverse map; node_id()
 //           elsewhere), data->split, data->label, graph, logits_gs (null test only), variables[6]->ld, d_truth[], split_rows[],
 //           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr, variables[3] (data, ld), node_id(), and for
-//           explanations variables[2] / [5] (data, ld), factored_, flags, feat, feat_agg, eval_modules[0]->hidden_not_stored
-//   calls   sync(), forward_hooked(), forward_hidden_only()
+//           explanations variables[2] / [5] (data, ld), factored_, flags, feat, feat_agg, eval_modules[0]->hidden_not_stored; for
+//           predict_new also variables[1] / [4] (data, ld), eval_modules.empty(), env.seed, env.d_epoch
+//   calls   sync(), forward_hooked(), forward_hidden_only(), forward_class_products()
 // It writes no member of HipGCN.
 #pragma once
 #include <cstdint>
@@ -221,6 +222,35 @@ public:
     int64_t tune_thresholds(int split, const int *nodes, int n, double beta, size_t scratch_bytes, float *thr, int64_t *tp, int64_t *fp, int64_t *fn,
                             double *f, int64_t *pos, int64_t *neg, int64_t *invalid, int32_t *defined);
 
+    // Unseen nodes: classify n_new nodes that were not in the dataset the model was built from — each arrives with its
+    // feature row and a list of nodes it links to — without rebuilding the dataset, the adjacency object, its schedule or A^.X.
+    // The definition is the loader's rule (host/attach.h): new node i has id N + i and the stored row [N + i, its listed ids...],
+    // the ids in [0, N + n_new) (N + k: new node k of the same call), repeats counted as often as listed; the row is appended,
+    // no existing row changes, existing nodes do not list it back.  With a(v, j) = 1 / sqrt(len(v) . len(j)), T = [X; X_new] . W1
+    // and the dataset nodes' rows exactly as an evaluation forward forms them:
+    //   h_v = ReLU(sum_{j in row(v)} a(v, j) T_j),  P_v = h_v . W2,  z_v = sum_{j in row(v)} a(v, j) P_j   for each new v,
+    //   P_j = H1_j . W2 of the evaluation forward for a dataset node j: the new rows influence no dataset node.
+    // So the logits are what the reference's evaluation forward gives those rows on the augmented dataset.
+    // X_new is CSR (x_indptr [n_new + 1], x_indices, x_values); x_indices == NULL: dense rows of input_dim values each.
+    // Steps: sync(); HipGCN::forward_class_products (variable 4 = H1.W2 of every dataset node, carrying dinv of its row on a
+    // factored model); T of the dataset nodes — variable 1 as that forward wrote it, or on an aggregate-first model one
+    // gcnhip_spmm_fwd on the feature object into scratch (its values carry dinv on a factored model, so X_new's are scaled by
+    // dinv of the new rows on the host); gcnhip_feat_create + gcnhip_spmm_fwd for X_new; gcnhip_attach_gather with ReLU;
+    // gcnhip_matmul_fwd; gcnhip_attach_gather with the predict epilogue at beta = 1 / temperature().  The coefficient stream is
+    // a(v, j) per edge on a HIPGCN_EDGE_COEF model; on a factored one dinv(v)^2 for the hidden gather (its result then carries
+    // dinv(v), as variable 3 does) and dinv(v) for the class gather.
+    // Single-label: pred [n_new], prob [n_new], logp (may be NULL) [n_new x C], as predict() returns them; thr must be NULL.
+    // Multi-label: the second gather stores the logits and gcnhip_bce_predict_rows (thr [n_thr = C]: _thr, refused as
+    // predict_multilabel refuses) decides: bits [n_new x ceil(C / 32)], prob (may be NULL) [n_new x C] = sigmoid(z).
+    // The device scratch is the arena's (the feature object of X_new is the library's own and is destroyed before the call
+    // returns); nothing is cached between calls, so nothing can go stale when weights change.  predict()'s contract: the metrics
+    // ring, the current split, variable 6 and the captured epoch graph are untouched; variables 1, 3, 4 are rewritten, as by
+    // every forward.  Refused with a message before any launch: more than one rank, bf16 tables, a hidden width above 256, more
+    // than 64 (single-label) or 256 (multi-label) classes, a malformed X_new (pointers, a column outside the model's input
+    // width, dense rows of another width), and everything gcn_attach_rows refuses (a bad id, nbr_ptr, n_new < 0).
+    void predict_new(const int *x_indptr, const int *x_indices, const float *x_values, int n_new, const int64_t *nbr_ptr, const int *nbr_ids,
+                     const float *thr, int n_thr, int32_t *pred, float *prob, float *logp, uint32_t *bits);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                         // every device buffer of a query
@@ -301,6 +331,12 @@ private:
     // tune_thresholds: one block {f [C] | thr [C] | TP, FP, FN per batch | defined [C]}; the cuts a query or an evaluation decides by
     Scratch<double> d_th_fit{&arena};
     Scratch<float> d_th_cuts{&arena};
+    // predict_new: T of the dataset nodes (aggregate-first models), T / H1 / H1.W2 / logits of the new rows; their stored rows
+    // and the two coefficient streams; the results
+    Scratch<float> d_nn_ta{&arena}, d_nn_tb{&arena}, d_nn_pb{&arena}, d_nn_z{&arena}, d_nn_coef{&arena}, d_nn_prob{&arena}, d_nn_logp{&arena};
+    Scratch<float, true> d_nn_hb{&arena};
+    Scratch<int32_t> d_nn_ptr{&arena}, d_nn_col{&arena}, d_nn_pred{&arena};
+    Scratch<uint32_t> d_nn_bits{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

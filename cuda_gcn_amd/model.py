@@ -235,6 +235,57 @@ class HipGCNModel:
         sets = unpack_multihot(words[:n], c)
         return (sets, pr[:n]) if prob else sets
 
+    def predict_new_nodes(self, features, nbr_ptr, nbr_ids, logp=False, prob=False, thresholds=None):
+        """Classify m nodes the dataset did not hold, attached to the trained graph: new node i has id num_nodes + i, the
+        feature row features[i] and the stored row [num_nodes + i, nbr_ids[nbr_ptr[i]:nbr_ptr[i + 1]]...] (new_node_rows has the
+        rule; an id num_nodes + k names new node k of the same call).  No existing row changes and the new rows influence no
+        dataset node, so the logits are what an evaluation forward gives those rows on the augmented dataset; the dataset, the
+        adjacency object and its schedule are not rebuilt.  features: a float [m, input_dim] array, or an (indptr, indices,
+        values) CSR triple.  Single-label model: (pred int32 [m], prob f32 [m]) at the model's temperature, with logp=True a
+        third array [m, C] of log-softmax rows, as predict() returns them.  Multi-label model: the bool [m, C] sets (z > 0, or
+        z >= thresholds[c]), with prob=True also the sigmoid of every logit.  m = 0 returns empty arrays.  One rank; training
+        state is not touched and nothing is cached between calls."""
+        c, f = self.params.output_dim, self.params.input_dim
+        if isinstance(features, tuple):
+            xp, xi, xv = (np.ascontiguousarray(features[0], np.int32).ravel(), np.ascontiguousarray(features[1], np.int32).ravel(),
+                          np.ascontiguousarray(features[2], np.float32).ravel())
+            m = xp.size - 1
+            if m < 0 or xi.size != xv.size or (m >= 0 and xp.size and xi.size != xp[-1]):
+                raise ValueError("predict_new_nodes: features is (indptr [m + 1], indices [nnz], values [nnz])")
+        else:
+            x = np.ascontiguousarray(features, np.float32)
+            if x.ndim != 2 or x.shape[1] != f:
+                raise ValueError(f"predict_new_nodes: features has shape {x.shape}, the model takes [m, {f}]")
+            m = x.shape[0]
+            xp, xi, xv = np.arange(m + 1, dtype=np.int32) * f, None, x.ravel()
+        p64 = np.ascontiguousarray(nbr_ptr, np.int64).ravel()
+        ids = np.ascontiguousarray(nbr_ids, np.int32).ravel()
+        if p64.size != m + 1:
+            raise ValueError(f"predict_new_nodes: nbr_ptr has {p64.size} entries for {m} new nodes (m + 1 expected)")
+        if p64[-1] != ids.size:
+            raise ValueError(f"predict_new_nodes: nbr_ptr ends at {p64[-1]}, nbr_ids has {ids.size} entries")
+        thr = None
+        if thresholds is not None and self.multilabel:
+            thr = thresholds_array("predict_new_nodes", thresholds, c)
+        elif thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, np.float32).ravel()      # refused by the library: a single-label model
+        n1 = max(m, 1)
+        pred, pr1 = np.zeros(n1, np.int32), np.zeros(n1, np.float32)
+        lp = np.zeros((n1, c), np.float32) if logp and not self.multilabel else None
+        words = np.zeros((n1, (c + 31) // 32), np.uint32) if self.multilabel else None
+        prc = np.zeros((n1, c), np.float32) if prob and self.multilabel else None
+        probs = prc if self.multilabel else pr1
+        _ck(self.lib, self.lib.gcnhost_model_predict_new(
+            self.h, xp.ctypes.data, xi.ctypes.data if xi is not None else None, xv.ctypes.data, m, p64.ctypes.data, ids.ctypes.data,
+            thr.ctypes.data if thr is not None else None, thr.size if thr is not None else 0, pred.ctypes.data,
+            probs.ctypes.data if probs is not None else None, lp.ctypes.data if lp is not None else None,
+            words.ctypes.data if words is not None else None), "predict_new_nodes")
+        if self.multilabel:
+            from .ops import unpack_multihot
+            sets = unpack_multihot(words[:m], c)
+            return (sets, prc[:m]) if prob else sets
+        return (pred[:m], pr1[:m], lp[:m]) if logp else (pred[:m], pr1[:m])
+
     def evaluate(self, split=None, nodes=None, thresholds=None):
         """Per-class evaluation: one evaluation forward with the current weights (no dropout) over a set of rows, integer counts
         per class formed on the GPU behind it, and the metrics class_report() derives from them.  Rows: the nodes of `split`
@@ -811,6 +862,33 @@ def thresholds_array(what, thresholds, num_classes):
     if np.isnan(thr).any():
         raise ValueError(f"{what}: the threshold of class {int(np.flatnonzero(np.isnan(thr))[0])} is NaN")
     return thr
+
+
+def new_node_rows(g_indptr, nbr_ptr, nbr_ids, m=None, factored=False):
+    """The stored rows of m new nodes attached to a dataset's graph, host only (host/attach.h): the dataset has N =
+    len(g_indptr) - 1 nodes, new node i has id N + i and the row [N + i, nbr_ids[nbr_ptr[i]:nbr_ptr[i + 1]]...] — the self loop
+    first, then its listed ids in listed order, each in [0, N + m); repeats and one-way entries count as the loader counts them
+    (degree = stored row length).  Returns dict(ptr int32 [m + 1], col int32, coef f32, len int32 [m]); coef[e] =
+    1 / sqrt(len(v) . len(j)) as the adjacency object stores it, or with factored=True 1 / sqrt(len(v)) on every entry of row v
+    (the factored model, whose tables carry the factor of their own row).  m: None = len(nbr_ptr) - 1.  Raises GcnHostError with
+    a message for m < 0, nbr_ptr[0] != 0, a decreasing nbr_ptr, an id outside [0, N + m), more than 2^31 - 1 stored entries."""
+    lib = _lib.gcnhost()
+    gp = _i32(g_indptr).ravel()
+    p64 = np.ascontiguousarray(nbr_ptr, np.int64).ravel()
+    ids = np.ascontiguousarray(nbr_ids, np.int32).ravel()
+    m = p64.size - 1 if m is None else int(m)
+    if p64.size < max(m, 0) + 1:
+        raise ValueError(f"new_node_rows: nbr_ptr has {p64.size} entries for {m} new nodes (m + 1 expected)")
+    listed = int(p64[m]) if m >= 0 else 0
+    total = max(listed, 0) + max(m, 0)
+    if m >= 0 and ids.size < listed and total <= 2**31 - 1 and np.all(np.diff(p64[:m + 1]) >= 0):
+        raise ValueError(f"new_node_rows: nbr_ptr ends at {listed}, nbr_ids has {ids.size} entries")
+    room = total if total <= 2**31 - 1 else 1                # refused by the library before anything is written
+    ptr, ln = np.zeros(max(m, 0) + 1, np.int32), np.zeros(max(m, 1), np.int32)
+    col, coef = np.zeros(max(room, 1), np.int32), np.zeros(max(room, 1), np.float32)
+    _ck(lib, lib.gcnhost_attach_rows(gp.size - 1, gp.ctypes.data, m, p64.ctypes.data, ids.ctypes.data, 1 if factored else 0, ptr.ctypes.data,
+                                     col.ctypes.data, coef.ctypes.data, ln.ctypes.data), "new_node_rows")
+    return dict(ptr=ptr, col=col[:total], coef=coef[:total], len=ln[:m])
 
 
 def check_beta(what, beta):

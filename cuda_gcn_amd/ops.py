@@ -581,6 +581,43 @@ class Device:
             self._embed_fail("gcnhip_embed_rows", rc)
         return ob.download()[:n, :dim]
 
+    # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
+    def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,
+                      store=True):
+        """gcnhip_attach_gather: out f32 [m, dim] = epilogue(sum of coef[e] * row(col[e]) over ptr[i] <= e < ptr[i + 1]), row(c) = table_a[c]
+        for c < n_a, else table_b[c - n_a].  epilogue "none" / "relu": returns out.  "predict": returns dict(pred int32 [m], prob f32 [m],
+        logp f32 [m, dim] with logp=True, z = the stored logits unless store=False), the softmax taken of beta * z.  The outputs are
+        uploaded as NaN / garbage.  m = len(ptr) - 1; table_b may hold more than m rows (some rows of a batch launched on their own)."""
+        ptr, col = np.ascontiguousarray(ptr, np.int32).ravel(), np.ascontiguousarray(col, np.int32).ravel()
+        coef = np.ascontiguousarray(coef, np.float32).ravel()
+        ta, tb = np.ascontiguousarray(table_a, np.float32), np.ascontiguousarray(table_b, np.float32)
+        m, n_a, dim = int(ptr.size) - 1, int(ta.shape[0]), int(tb.shape[1])
+        assert tb.shape[0] >= m and ta.shape[1] == dim and col.size == coef.size == int(ptr[-1])
+        ld_a, ld_b, ld_out = int(ld_a or dim), int(ld_b or dim), int(ld_out or dim)
+        code = {"none": 0, "relu": 1, "predict": 2}[epilogue]
+        pb = self.buf(ptr)
+        cb, fb = self.buf(col if col.size else np.zeros(1, np.int32)), self.buf(coef if coef.size else np.zeros(1, np.float32))
+        ab = self.padded(ta, ld_a) if n_a else None
+        bb = self.padded(tb, ld_b) if m else self.buf(np.zeros(4, np.float32))
+        ob = self.buf(np.full((max(m, 1), ld_out), np.nan, np.float32)) if (store or code != 2) else None
+        qb = self.buf(np.full(max(m, 1), 12345, np.int32)) if code == 2 else None
+        rb = self.buf(np.full(max(m, 1), np.nan, np.float32)) if code == 2 else None
+        lb = self.buf(np.full((max(m, 1), dim), np.nan, np.float32)) if code == 2 and logp else None
+        rc = self.lib.gcnhip_attach_gather(self.ctx, pb.ptr, cb.ptr, fb.ptr, m, ab.ptr if ab else None, ld_a, n_a, bb.ptr, ld_b, dim, code,
+                                           ob.ptr if ob else None, ld_out, qb.ptr if qb else None, rb.ptr if rb else None, lb.ptr if lb else None, dim,
+                                           float(beta))
+        if rc != 0:
+            self._embed_fail("gcnhip_attach_gather", rc)
+        self.sync()
+        if code != 2:
+            return ob.download()[:m, :dim]
+        res = dict(pred=qb.download()[:m], prob=rb.download()[:m])
+        if lb:
+            res["logp"] = lb.download()[:m]
+        if ob:
+            res["z"] = ob.download()[:m, :dim]
+        return res
+
     # ---- explaining a logit (csrc/explain.hip): tables are uploaded with their row stride and NaN padding
     def _explain_inputs(self, q_row, q_class, h1, w2, ld_h1, ld_w2):
         qr, qc = np.ascontiguousarray(q_row, np.int32).ravel(), np.ascontiguousarray(q_class, np.int32).ravel()

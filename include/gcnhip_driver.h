@@ -386,6 +386,24 @@ int gcnhip_explain_features_walk(gcnhip_ctx *ctx, const gcnhip_graph *g, const g
                                  int num_classes, const float *w1, int ld_w1, int scaling, float *feat, int ld_f);
 int gcnhip_explain_abs_colsum(gcnhip_ctx *ctx, const float *feat, int ld_f, const int32_t *q_class, int nq, int n_features,
                               int num_classes, double *acc, int32_t *count);
+/* ---- new nodes attached to a trained graph (attach.hip; beyond the reference, which scores only the nodes it was built with) ----
+ * A gather for m rows that are not rows of an adjacency object, from two f32 tables read where they lie:
+ *   out[i, 0:dim] = epilogue( sum_{e in [d_ptr[i], d_ptr[i+1])} d_coef[e] * row(d_col[e]) ),   i < m
+ *   row(c) = table_a[c, :] for c < n_a,   table_b[c - n_a, :] for n_a <= c < n_a + m
+ * d_ptr [m + 1], d_col / d_coef [d_ptr[m]] are device arrays; the tables have row strides of their own (ld_a, ld_b >= dim, any
+ * alignment: rows that are 16-byte aligned in both tables are read in 16-byte pieces, others 4 bytes at a time, with the same
+ * bits); 1 <= dim <= 256; out [m x ld_out] must be neither table.  A row without edges is a zero row.
+ * epilogue 0: none.  1: ReLU (v > 0 ? v : 0).  2: predict (dim <= 64 only, otherwise -1 and a message) — d_pred[i] = the column
+ * of the largest sum, the LOWEST on a tie; d_prob[i] = its softmax probability; d_logp (may be NULL) [i * ld_logp + c] = the
+ * log-softmax row of beta . z, all three by the statements of gcnhip_graphsum_predict, followed at beta != 1 by those of
+ * gcnhip_calib_scale_rows on that row (a model temperature T is beta = 1 / T, finite and > 0); out may then be NULL, else it
+ * receives the logits z themselves.
+ * The order of a row's sum depends on that row's own edge list and on dim alone (attach.hip has it): not on m, the row's
+ * position or the other rows, so a row has the same bits alone, in any batch and on every launch.  No atomics.  The launch
+ * allocates nothing, does not synchronise and TRUSTS d_col to be in [0, n_a + m): the host validates (gcnhost_attach_rows). */
+int gcnhip_attach_gather(gcnhip_ctx *ctx, const int32_t *d_ptr, const int32_t *d_col, const float *d_coef, int m, const float *table_a,
+                         int ld_a, int n_a, const float *table_b, int ld_b, int dim, int epilogue, float *out, int ld_out, int32_t *d_pred,
+                         float *d_prob, float *d_logp, int ld_logp, float beta);
 /* Unregister a row subset made by gcnhip_graph_add_rowset (synchronises the context's stream, frees its task lists): for
  * subsets made at call time, such as the node queries of a prediction. */
 int gcnhip_graph_remove_rowset(gcnhip_ctx *ctx, gcnhip_graph *g, gcnhip_rowset *rows);

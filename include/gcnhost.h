@@ -304,6 +304,27 @@ int gcnhost_model_tune_thresholds(gcnhost_model *m, int split, const int *nodes,
                                   int64_t *fp, int64_t *fn, double *f, int64_t *pos, int64_t *neg, int64_t *invalid, int32_t *defined, int64_t *rows);
 int gcnhost_model_predict_multilabel_thr(gcnhost_model *m, const int *nodes, int n, const float *thr, int n_thr, uint32_t *bits, float *prob);
 int gcnhost_model_evaluate_thr(gcnhost_model *m, int split, const int *nodes, int n, const float *thr, int n_thr, int64_t *counts, int64_t *rows_counted);
+/* ---- unseen nodes: new rows attached to a trained graph (host/attach.h, host/queries.h; beyond the reference) ----
+ * The dataset has num_nodes = N nodes; a call brings m new ones, new node i has id N + i and the stored row
+ * [N + i, nbr_ids[nbr_ptr[i] : nbr_ptr[i + 1]] ...] — the self loop first, then its listed ids in listed order, each in
+ * [0, N + m) (N + k: new node k of the same call); repeats, and N + i listed again, count as the loader counts them (degree =
+ * stored row length); no existing row changes.  a(v, j) = 1 / sqrt(len(v) . len(j)), the product formed in 64 bits.
+ * gcnhost_attach_rows, host only: g_indptr [N + 1] = the dataset's row pointers (its row lengths); out_ptr [m + 1], out_col /
+ * out_coef [nbr_ptr[m] + m], out_len [m] (callers allocate).  mode 0: out_coef[e] = a(v, j) as gcnhip_graph_create stores it;
+ * mode 1 (the factored model, whose tables carry 1 / sqrt(len) of their own row): out_coef[e] = (float)(1 / sqrt(len(v))).
+ * Refused with a message: m < 0, nbr_ptr[0] != 0 or a decreasing nbr_ptr, an id outside [0, N + m), more than 2^31 - 1 stored entries.
+ * gcnhost_model_predict_new: the logits of the new rows are what the reference's evaluation forward gives them on the augmented
+ * dataset (the dataset nodes' rows as an evaluation forward forms them; the new rows influence no dataset node).  X_new is CSR
+ * (x_indptr [m + 1], x_indices, x_values); x_indices == NULL: dense rows of input_dim values.  Single-label model: pred [m],
+ * prob [m], logp (may be NULL) [m x output_dim] as gcnhost_model_predict returns them, at the model's temperature; thr must be
+ * NULL.  Multi-label model: bits [m x ceil(output_dim / 32)], prob (may be NULL) [m x output_dim] = sigmoid(z), decided by
+ * z > 0 or, with thr [n_thr = output_dim], as gcnhost_model_predict_multilabel_thr decides.  Training state is untouched and
+ * nothing is cached between calls.  Refused with a message before any launch: what gcnhost_attach_rows refuses, a malformed
+ * X_new, more than one rank, bf16 tables, a hidden width above 256, more than 64 (single-label) / 256 (multi-label) classes. */
+int gcnhost_attach_rows(int num_nodes, const int *g_indptr, int m, const int64_t *nbr_ptr, const int *nbr_ids, int mode, int32_t *out_ptr,
+                        int32_t *out_col, float *out_coef, int32_t *out_len);
+int gcnhost_model_predict_new(gcnhost_model *m, const int *x_indptr, const int *x_indices, const float *x_values, int n_new, const int64_t *nbr_ptr,
+                              const int *nbr_ids, const float *thr, int n_thr, int32_t *pred, float *prob, float *logp, uint32_t *bits);
 int gcnhost_thresholds_read(const char *path, int *num_classes, float *thr);
 int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr, const int64_t *pos, const int64_t *neg, const int64_t *tp,
                              const int64_t *fp, const int64_t *fn, const double *f);
