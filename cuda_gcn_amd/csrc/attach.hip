@@ -27,7 +27,9 @@
 // Epilogues: none; ReLU (v > 0 ? v : 0); predict (dim <= 64) — argmax (lowest class on a tie), its probability and optionally
 // the log-softmax row, by the statements of graphsum.hip's predict_row_epilogue (max, exp of the shifted logits, their sum left
 // to right, prob = 1 / sum, logp = (z - max) - log(sum)), followed at beta != 1 by those of calib.hip's calib_scale_kernel on
-// that row (s = beta . logp, logp' = (s - max s) - log(sum exp(s - max s)) left to right, prob = exp(max logp')).
+// that row (s = beta . logp, logp' = (s - max s) - log(sum exp(s - max s)), prob = exp(max logp')) — with ONE difference: the
+// sum runs left to right here, where calib_scale_kernel adds in a shuffle tree, so the two agree within the rounding of a sum
+// (an ulp or two of logp'), not bit for bit; tests/test_softmax_gpu.py holds both to float64.
 // The launch allocates nothing, does not synchronise and trusts col to be in [0, n_a + m): the host validates (host/attach.h).
 #include "common.h"
 #include <cmath>
@@ -172,7 +174,7 @@ __device__ __forceinline__ void attach_finish(const AttachArgs &a, int row, floa
     const float ls = logf(se);
 #pragma unroll
     for (int i = 0; i < 4; i++) x[i] -= ls;                    // the log-softmax row of z
-    if (a.beta != 1.f) {                                       // ... and of beta . z, from that row as calib_scale_kernel forms it
+    if (a.beta != 1.f) {                                       // ... and of beta . z, from that row by calib_scale_kernel's statements (sum left to right)
         float sm = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 4; i++) {

@@ -1118,15 +1118,65 @@ class Device:
         return dict(loss_sum=float(r[0]), count=float(r[1]), correct=int(ri[0]), total=int(ri[1]),
                     logits=lb.download()[:, :c], grad=gb.download()[:, :c] if training else None)
 
-    def bce_fwd_rows(self, logits, truth, rows=None, training=True, count=None, grad_row_scale=None, ld=None, grad_fill=np.nan):
+    def xent_call(self, entry, table, truth, c, grad=None, rows=None, training=True, count=0, shift_in_place=False, grad_row_scale=None,
+                  weight=None, weight_sum=0.0, offset=0, grad_offset=0, result_fill=0x5A5A5A5A):
+        """One call of a softmax loss entry point on tables exactly as the caller laid them out.  entry: "fwd" (gcnhip_xent_fwd),
+        "rows" (gcnhip_xent_fwd_rows), "scaled" (gcnhip_xent_fwd_rows_scaled), "weighted" (gcnhip_wxent_fwd_rows), "accuracy"
+        (gcnhip_accuracy).  table f32 [n, ld] and grad f32 [n, ld_grad] are WHOLE tables, padding columns included (their strides
+        are the leading dimensions); offset / grad_offset: the table starts that many floats into its allocation.  rows: the
+        list for the list forms.  Nothing is raised: returns dict(rc, result f32 [4], result_i int32 [2] — `result_fill` bits
+        where the call wrote nothing —, table, grad: the whole tables after the call)."""
+        table = np.ascontiguousarray(table, np.float32)
+        n, ld = table.shape
+        truth = np.ascontiguousarray(truth, np.int32)
+
+        def place(arr, off):
+            flat = np.full(arr.size + off + 4, np.nan, np.float32)
+            flat[off:off + arr.size] = arr.ravel()
+            b = self.buf(flat)
+            return b, C.c_void_p(b.ptr + 4 * off)
+        lb, lp = place(table, offset)
+        gb, gp, ld_grad = None, None, 0
+        if grad is not None:
+            grad = np.ascontiguousarray(grad, np.float32)
+            ld_grad = grad.shape[1]
+            gb, gp = place(grad, grad_offset)
+        tb = self.buf(truth if truth.size else np.zeros(1, np.int32))
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        sb = self.buf(np.ascontiguousarray(grad_row_scale, np.float32)) if grad_row_scale is not None else None
+        wb = self.buf(np.ascontiguousarray(weight, np.float32)) if weight is not None else None
+        res, resi = self.buf(np.full(4, result_fill, np.uint32).view(np.float32)), self.buf(np.full(2, result_fill, np.uint32).view(np.int32))
+        lib, listed = self.lib, int(rows.size) if rows is not None else 0
+        head = (self.ctx, lp, ld, gp, ld_grad, tb.ptr)
+        tail = (int(c), int(training), int(count), int(shift_in_place), res.ptr, resi.ptr)
+        if entry == "fwd":
+            rc = lib.gcnhip_xent_fwd(*head, n, *tail)
+        elif entry == "rows":
+            rc = lib.gcnhip_xent_fwd_rows(*head, rb.ptr, listed, *tail)
+        elif entry == "scaled":
+            rc = lib.gcnhip_xent_fwd_rows_scaled(*head, rb.ptr, listed, *tail, sb.ptr if sb else None)
+        elif entry == "weighted":
+            rc = lib.gcnhip_wxent_fwd_rows(*head, rb.ptr, listed, *tail, sb.ptr if sb else None, wb.ptr, float(weight_sum))
+        elif entry == "accuracy":
+            rc = lib.gcnhip_accuracy(self.ctx, lp, ld, tb.ptr, n, int(c), resi.ptr)
+        else:
+            raise ValueError(entry)
+        self.sync()
+        return dict(rc=rc, result=res.download(), result_i=resi.download(),
+                    table=lb.download()[offset:offset + table.size].reshape(n, ld),
+                    grad=gb.download()[grad_offset:grad_offset + grad.size].reshape(n, ld_grad) if gb else None)
+
+    def bce_fwd_rows(self, logits, truth, rows=None, training=True, count=None, grad_row_scale=None, ld=None, grad_fill=np.nan, words=None):
         """gcnhip_bce_fwd_rows: per-class sigmoid cross-entropy over the listed rows (None: every row).  truth: bool [n, C] (packed
         here into multi-hot words).  Returns dict(loss_sum, denom (rows * C), f1_num (2 TP), f1_den (2 TP + FP + FN), tp, fp, fn,
-        rows, loss, f1, grad [n, C] or None); grad rows outside the list keep grad_fill."""
+        rows, loss, f1, grad [n, C] or None); grad rows outside the list keep grad_fill.  words: the multi-hot words themselves,
+        uint32 [n, words_per_row], in place of the ones packed from truth (more words than C needs, bits past C set)."""
         logits = np.asarray(logits, np.float32)
         n, c = logits.shape
         ld = ld or c
         rows = np.arange(n, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, np.int32)
-        words = pack_multihot(truth)
+        words = pack_multihot(truth) if words is None else np.ascontiguousarray(words, np.uint32)
         lb = self.padded(logits, ld)
         gb = self.buf(np.full((n, ld), grad_fill, np.float32))
         tb, rb = self.buf(words), self.buf(rows if rows.size else np.zeros(1, np.int32))

@@ -396,8 +396,9 @@ int gcnhip_explain_abs_colsum(gcnhip_ctx *ctx, const float *feat, int ld_f, cons
  * epilogue 0: none.  1: ReLU (v > 0 ? v : 0).  2: predict (dim <= 64 only, otherwise -1 and a message) — d_pred[i] = the column
  * of the largest sum, the LOWEST on a tie; d_prob[i] = its softmax probability; d_logp (may be NULL) [i * ld_logp + c] = the
  * log-softmax row of beta . z, all three by the statements of gcnhip_graphsum_predict, followed at beta != 1 by those of
- * gcnhip_calib_scale_rows on that row (a model temperature T is beta = 1 / T, finite and > 0); out may then be NULL, else it
- * receives the logits z themselves.
+ * gcnhip_calib_scale_rows on that row (a model temperature T is beta = 1 / T, finite and > 0; the sum of the rescaled row runs
+ * left to right here and in a shuffle tree there, so the two agree within the rounding of one sum, not bit for bit); out may
+ * then be NULL, else it receives the logits z themselves.
  * The order of a row's sum depends on that row's own edge list and on dim alone (attach.hip has it): not on m, the row's
  * position or the other rows, so a row has the same bits alone, in any batch and on every launch.  No atomics.  The launch
  * allocates nothing, does not synchronise and TRUSTS d_col to be in [0, n_a + m): the host validates (gcnhost_attach_rows). */
