@@ -111,6 +111,8 @@ GCNHIP_SYMBOLS = {
     "gcnhip_calib_nll_rows": (I, [P, P, I, P, I, P, I, I, F, P]),
     "gcnhip_calib_bins_rows": (I, [P, P, I, P, I, P, I, I, F, I, P, P, P]),
     "gcnhip_calib_scale_rows": (I, [P, P, I, I, P, I, I, F, P, I, P]),
+    "gcnhip_mc_accumulate_rows": (I, [P, P, I, I, P, I, I, I, P, P]),
+    "gcnhip_mc_finalize_rows": (I, [P, P, P, I, I, I, P, I, P, P, P, P, P, P]),
     "gcnhip_conformal_scores": (I, [P, P, I, I, P, I, I, F, I, F, I, P, I]),
     "gcnhip_conformal_true_scores": (I, [P, P, I, P, I, P, I, I, P]),
     "gcnhip_conformal_sets_rows": (I, [P, P, I, I, P, I, I, P, P, P, P, P]),
@@ -251,6 +253,7 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_correct_and_smooth": (I, [P, F, I, F, I, I, P, P]),
     "gcnhost_model_calibration": (I, [P, I, P, I, F, I, P, P, P, P]),
     "gcnhost_model_calibrate": (I, [P, I, I, P, P, P, P]),
+    "gcnhost_model_mc_dropout": (I, [P, I, P, I, I, P, P, U64, I64, P, P, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_model_set_temperature": (I, [P, F]),
     "gcnhost_model_temperature": (I, [P, C.POINTER(F)]),
     "gcnhost_model_embed": (I, [P, P, I, P, I]),

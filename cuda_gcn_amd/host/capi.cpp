@@ -243,6 +243,25 @@ int gcnhost_model_predict_new(gcnhost_model *m, const int *x_indptr, const int *
     if (!m) { g_err = "gcnhost_model_predict_new: invalid argument"; return -1; }
     API_TRY({ m->gcn->queries().predict_new(x_indptr, x_indices, x_values, n_new, nbr_ptr, nbr_ids, thr, n_thr, pred, prob, logp, bits); })
 }
+int gcnhost_model_mc_dropout(gcnhost_model *m, int split, const int *nodes, int n, int samples, const float *p, const uint64_t *seed, uint64_t first_sample,
+                             int64_t capacity, int32_t *pred, float *confidence, float *entropy, float *expected_entropy, float *mutual_information,
+                             float *variation_ratio, float *mean_prob, int32_t *votes, float *samples_logp, uint64_t *seed_used, float *p_used,
+                             int64_t *rows) {
+    if (!m) { g_err = "gcnhost_model_mc_dropout: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.mc_dropout_rows(split, nodes, n, samples, p, first_sample);
+        if (rows) *rows = listed;
+        const bool any = pred || confidence || entropy || expected_entropy || mutual_information || variation_ratio || mean_prob || votes || samples_logp;
+        if (!any) return 0;                                    // the arguments are fine and *rows is known: a caller sizes its arrays
+        if (listed != capacity && !(listed == 0 && capacity >= 0))
+            throw GcnHipFailure(-1, "mc_dropout: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::McDropout r = q.mc_dropout(split, nodes, n, samples, p, seed, first_sample, pred, confidence, entropy, expected_entropy,
+                                                       mutual_information, variation_ratio, mean_prob, votes, samples_logp);
+        if (seed_used) *seed_used = r.seed;
+        if (p_used) *p_used = r.p;
+    })
+}
 int gcnhost_model_evaluate(gcnhost_model *m, int split, const int *nodes, int n, int64_t *counts, int64_t *rows_counted, int64_t *unlabelled) {
     if (!m || !counts) { g_err = "gcnhost_model_evaluate: invalid argument"; return -1; }
     API_TRY({ m->gcn->queries().evaluate(split, nodes, n, counts, rows_counted, unlabelled); })

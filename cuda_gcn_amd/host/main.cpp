@@ -56,6 +56,14 @@
 //                            calibration error of the TEST split, 15 bins).  The file gets the test split's reliability table at
 //                            T = 1 and at the fitted T (host/calibration.h: a summary line, then one line per bin).  Works with
 //                            GCN_LOAD_WEIGHTS and 0 epochs.  One GPU, single-label, at most 64 classes.
+//   GCN_UNCERTAINTY=<file>   after the test line and after GCN_CALIBRATE's fit (at its temperature), before every other step: Monte Carlo
+//                            dropout on the TEST split (ModelQueries::mc_dropout; csrc/mcdropout.hip has the definition) — GCN_MC_SAMPLES
+//                            (default 20, 1..1024) forwards with the model's dropout on, seeded by GCN_MC_SEED (a 64-bit integer;
+//                            default: the model's seed ^ KEY_MC_DROPOUT).  One line is printed: `mc_samples=<S> mc_test_acc=<share of
+//                            the test nodes whose mean-softmax class is their label> mc_mean_entropy=<x> mc_mean_mutual_information=<y>`.
+//                            The file gets one line per test node in id order: `node pred confidence entropy mutual_information`
+//                            (%.9g).  stdout is otherwise unchanged.  Works with GCN_LOAD_WEIGHTS and 0 epochs.  One GPU, single-label,
+//                            at most 64 classes, f32 tables, hidden_dim at most 256.
 //   GCN_CONFORMAL=<file>     after the test line (and after GCN_CALIBRATE's fit when both are set, at its temperature): split conformal
 //                            prediction sets (ModelQueries::conformal_fit / conformal_sets).  The threshold is fitted on the
 //                            VALIDATION split at GCN_CONFORMAL_ALPHA (default 0.1) with GCN_CONFORMAL_METHOD=aps|lac (default aps) and
@@ -233,6 +241,29 @@ int main(int argc, char **argv) {
                                                        : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_CALIBRATE " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *uncertainty_path = getenv("GCN_UNCERTAINTY");
+    if (uncertainty_path && !*uncertainty_path) uncertainty_path = nullptr;
+    const int mc_samples = env_int("GCN_MC_SAMPLES", 20);
+    uint64_t mc_seed = 0;
+    const char *mc_seed_text = getenv("GCN_MC_SEED");
+    if (mc_seed_text && !*mc_seed_text) mc_seed_text = nullptr;
+    if (uncertainty_path) {
+        char *end = nullptr;
+        if (mc_seed_text) mc_seed = strtoull(mc_seed_text, &end, 0);
+        const char *why = multilabel_path                                  ? "samples the softmax of a single-label model (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                     ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > 64                         ? "takes at most 64 classes"
+                          : params.hidden_dim > 256                        ? "takes a hidden_dim of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                  ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : mc_samples < 1 || mc_samples > ModelQueries::MC_SAMPLES_MAX ? "needs GCN_MC_SAMPLES in 1..1024"
+                          : mc_seed_text && (end == mc_seed_text || *end)  ? "needs an integer GCN_MC_SEED"
+                                                                           : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_UNCERTAINTY " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -438,6 +469,33 @@ int main(int argc, char **argv) {
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the reliability tables to ") + calibrate_path);
                 fprintf(stderr, "gcn-hip: reliability tables of the test split written to %s%s\n", calibrate_path,
                         fit.at_bound ? " (the fit stopped on an end of its bracket: the validation split is classified perfectly)" : "");
+            }
+            if (uncertainty_path) {                            // one rank (checked above); after the calibration: at its temperature
+                std::vector<int> test;
+                test.reserve(1);                               // an empty split is still a query (not "every row")
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) test.push_back(i);
+                const size_t nt = test.size(), cap = std::max<size_t>(nt, 1);
+                std::vector<int32_t> pred(cap);
+                std::vector<float> conf(cap), ent(cap), mi(cap);
+                const ModelQueries::McDropout r = gcn.queries().mc_dropout(0, test.data(), (int)nt, mc_samples, nullptr, mc_seed_text ? &mc_seed : nullptr, 0,
+                                                                           pred.data(), conf.data(), ent.data(), nullptr, mi.data(), nullptr, nullptr, nullptr,
+                                                                           nullptr);
+                double right = 0, sum_ent = 0, sum_mi = 0;
+                for (size_t i = 0; i < nt; i++) {
+                    right += pred[i] == data.label[test[i]];
+                    sum_ent += ent[i];
+                    sum_mi += mi[i];
+                }
+                const double d = nt ? (double)nt : 1.0;
+                printf("mc_samples=%d mc_test_acc=%.5f mc_mean_entropy=%.5f mc_mean_mutual_information=%.5f\n", r.samples, right / d, sum_ent / d, sum_mi / d);
+                FILE *f = fopen(uncertainty_path, "w");
+                bool ok = f != nullptr;
+                for (size_t i = 0; ok && i < nt; i++) ok = fprintf(f, "%d %d %.9g %.9g %.9g\n", test[i], pred[i], conf[i], ent[i], mi[i]) > 0;
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the uncertainties to ") + uncertainty_path);
+                fprintf(stderr, "gcn-hip: Monte Carlo dropout (%d samples, p %g, seed %llu) of the test split written to %s\n", r.samples, r.p,
+                        (unsigned long long)r.seed, uncertainty_path);
             }
             if (conformal_path) {                              // one rank (checked above); after the calibration: at its temperature
                 const int C = params.output_dim, wpr = (C + 31) / 32;

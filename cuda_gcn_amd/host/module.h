@@ -252,3 +252,5 @@ public:
 // distinct Philox keys for the two dropout sites
 constexpr uint64_t KEY_INPUT_DROPOUT = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t KEY_HIDDEN_DROPOUT = 0xD1B54A32D192ED03ull;
+// not a site: the default seed of a Monte Carlo dropout query is the model's seed ^ this, so that its samples repeat no epoch's masks
+constexpr uint64_t KEY_MC_DROPOUT = 0xA0761D6478BD642Full;

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -8,9 +8,13 @@
 //           elsewhere), data->split, data->label, graph, logits_gs (null test only), variables[6]->ld, d_truth[], split_rows[],
 //           d_split_list[], split_local_n[], split_count[], d_ml_truth, ml_wpr, variables[3] (data, ld), node_id(), and for
 //           explanations variables[2] / [5] (data, ld), factored_, flags, feat, feat_agg, eval_modules[0]->hidden_not_stored; for
-//           predict_new also variables[1] / [4] (data, ld), eval_modules.empty(), env.seed, env.d_epoch
+//           predict_new also variables[1] / [4] (data, ld), eval_modules.empty(), env.seed, env.d_epoch; for mc_dropout
+//           params.dropout, env.seed, feat, graph, factored_, flags, variables[1] / [3] / [4] (ld only), variables[2] / [5]
 //   calls   sync(), forward_hooked(), forward_hidden_only(), forward_class_products()
-// It writes no member of HipGCN.
+// It writes no member of HipGCN.  One object it reads is changed by a query all the same: mc_dropout's stochastic gcnhip_spmm_fwd
+// redraws the dropout-bit array of the feature object (and its layout flag), which the training backward reads.  That is harmless
+// only because every training pass runs its own forward — which draws them again — before its backward; a query is made between
+// passes (sync() first), never between a forward and its backward (tests/test_mc_dropout_gpu.py, "between epochs").
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -251,6 +255,40 @@ public:
     void predict_new(const int *x_indptr, const int *x_indices, const float *x_values, int n_new, const int64_t *nbr_ptr, const int *nbr_ids,
                      const float *thr, int n_thr, int32_t *pred, float *prob, float *logp, uint32_t *bits);
 
+    // Monte Carlo dropout (Gal & Ghahramani, 2016): how sure the model itself is about one node.  S forwards with dropout on,
+    // the softmax rows averaged, the predictive entropy split into its expected part and the mutual information between
+    // prediction and weights (BALD).  csrc/mcdropout.hip has the definition: sample s in [first_sample, first_sample + samples)
+    // is the training forward with the epoch word s, rate p (NULL: params.dropout) and the keys seed ^ KEY_INPUT_DROPOUT /
+    // seed ^ KEY_HIDDEN_DROPOUT (seed NULL: env.seed ^ KEY_MC_DROPOUT, so that by default no sample repeats a training epoch's
+    // masks; seed = env.seed and first_sample = e draw the masks of training epoch e).  Rows as evaluate() takes them (the nodes of
+    // `split`, or with split == 0 the `nodes` query, repeats allowed, NULL: every row).  Per sample: gcnhip_spmm_fwd on the
+    // model's feature object with p_drop = p, gcnhip_graphsum_ex with the ReLU + dropout epilogue (training, no pos_bits, no
+    // keep_mask) over every row, gcnhip_matmul_fwd, gcnhip_graphsum_predict on the query's row subset, gcnhip_calib_scale_rows
+    // when temperature() != 1, gcnhip_mc_accumulate_rows; then one gcnhip_mc_finalize_rows.  The coefficient form is the training
+    // forward's own: scaling 2 / 1 on a factored model (the feature values carry dinv), 0 on an HIPGCN_EDGE_COEF one.
+    // SCRATCH: T / H / H.W2 are tables of the query's own arena (laid out as variables 1, 3, 4); no variable of the model is
+    // written.  The epoch words are a small device array of the arena.  predict()'s contract: the call starts with sync(); the
+    // metrics ring, the current split, variable 6, the captured epoch graph, Adam's state, env.d_epoch and the model's mask bits
+    // (d_pos_bits) are untouched (the feature object's dropout bits are redrawn: see the head of this file).
+    // Outputs by list position, each may be NULL: pred, confidence, entropy, expected_entropy, mutual_information,
+    // variation_ratio [n]; mean_prob, votes [n x C]; samples_logp [samples x n x C], the per-sample log-softmax rows gathered on
+    // the device in list order.  Returns the rows listed and what was used.  Refused with a message before any launch: a
+    // multi-label model, more than 64 classes, more than one rank, bf16 tables, a hidden width above 256, samples outside
+    // 1..1024, p outside [0, 1), first_sample + samples > 2^32, a split outside 0..3, a node id outside the graph.
+    static constexpr int MC_SAMPLES_MAX = 1024;
+    struct McDropout {
+        uint64_t seed = 0;
+        float p = 0.f;
+        int samples = 0;
+        uint64_t first_sample = 0;
+        int64_t rows = 0;
+    };
+    // the refusals alone, and the number of rows the query lists (a caller sizes its arrays by it); touches no device state
+    int64_t mc_dropout_rows(int split, const int *nodes, int n, int samples, const float *p, uint64_t first_sample);
+    McDropout mc_dropout(int split, const int *nodes, int n, int samples, const float *p, const uint64_t *seed, uint64_t first_sample, int32_t *pred,
+                         float *confidence, float *entropy, float *expected_entropy, float *mutual_information, float *variation_ratio,
+                         float *mean_prob, int32_t *votes, float *samples_logp);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                         // every device buffer of a query
@@ -337,6 +375,14 @@ private:
     Scratch<float, true> d_nn_hb{&arena};
     Scratch<int32_t> d_nn_ptr{&arena}, d_nn_col{&arena}, d_nn_pred{&arena};
     Scratch<uint32_t> d_nn_bits{&arena};
+    // mc_dropout: T / H / H.W2 of a sample [local rows x ld of variables 1 / 3 / 4]; the epoch words; the accumulators by list
+    // position; the f32 results {confidence | entropy | expected | mutual information | variation ratio | mean_prob}; pred; the
+    // gathered per-sample rows; a query's rows listed once (the temperature rescale)
+    Scratch<float, true> d_mc_t{&arena}, d_mc_h{&arena}, d_mc_p{&arena};
+    Scratch<uint32_t> d_mc_epoch{&arena};
+    Scratch<double> d_mc_acc{&arena};
+    Scratch<int32_t> d_mc_votes{&arena}, d_mc_pred{&arena}, d_mc_once{&arena};
+    Scratch<float> d_mc_out{&arena}, d_mc_samples{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

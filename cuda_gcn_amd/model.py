@@ -64,6 +64,7 @@ class HipGCNModel:
     def __init__(self, ds, seed=0, device=0, flags=0, rank=0, world=1, nccl_id: bytes | None = None,
                  host_allgather=None, host_allreduce=None, multilabel=None, class_weights=None, **hyper):
         self.lib = lib = _lib.gcnhost()
+        self.seed = int(seed)
         out_dim = ds["output_dim"]
         words = None
         if multilabel is not None:
@@ -541,6 +542,89 @@ class HipGCNModel:
                                                          correct.ctypes.data, conf.ctypes.data), "calibration")
         out = calibration_report(count, correct, conf)
         out.update(nll=float(sums[0] / sums[3]) if sums[3] else 0.0, temperature=t, sums=sums)
+        return out
+
+    # ---- Monte Carlo dropout: how sure the model itself is about one node
+    MC_SAMPLES_MAX = 1024
+
+    @property
+    def stream_seed(self):
+        """the 64-bit seed of the model's dropout streams (host/gcn_build.cpp derives it from the constructor's seed):
+        mc_dropout(seed=stream_seed, first_sample=e) draws the masks of training epoch e"""
+        return ((self.seed & ((1 << 64) - 1)) * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & ((1 << 64) - 1)
+
+    def _mc_args(self, split, nodes, samples, p, seed, first_sample):
+        """argument checks that need no GPU"""
+        what = "mc_dropout"
+        if self.multilabel:
+            raise GcnHostError(f"{what}: this is a multi-label model (the call works on one softmax per node)")
+        if self.params.output_dim > 64:
+            raise GcnHostError(f"{what}: at most 64 classes, this model has {self.params.output_dim}")
+        if self.params.hidden_dim > 256:
+            raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+        if split is not None and nodes is not None:
+            raise GcnHostError(f"{what}: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"{what}: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if isinstance(samples, bool) or int(samples) != samples or not 1 <= samples <= self.MC_SAMPLES_MAX:
+            raise GcnHostError(f"{what}: samples must be an integer in 1..{self.MC_SAMPLES_MAX}, got {samples!r}")
+        if p is not None and not 0.0 <= float(p) < 1.0:
+            raise GcnHostError(f"{what}: the dropout rate p must be in [0, 1), got {p!r}")
+        if seed is not None and (int(seed) != seed or not 0 <= seed < 1 << 64):
+            raise GcnHostError(f"{what}: the seed is an integer in [0, 2^64), got {seed!r}")
+        if int(first_sample) != first_sample or first_sample < 0 or first_sample + samples > 1 << 32:
+            raise GcnHostError(f"{what}: first_sample >= 0 and first_sample + samples <= 2^32, got {first_sample!r} + {samples!r}")
+
+    def mc_dropout(self, split=None, nodes=None, samples=20, p=None, seed=None, first_sample=0, mean_prob=False, votes=False, return_samples=False):
+        """Monte Carlo dropout (Gal & Ghahramani, 2016): `samples` forwards with dropout ON, their softmax rows averaged, and the
+        predictive entropy split into its expected part and the mutual information between prediction and weights (BALD) — the
+        part of a node's uncertainty that is the model's own.  Sample s in [first_sample, first_sample + samples) is the training
+        forward with the epoch word s, the rate p (None: the model's dropout) and the 64-bit `seed` (None: the model's seed ^
+        KEY_MC_DROPOUT, so that no sample repeats a training epoch's masks; the model's own seed with first_sample=e draws the
+        masks of training epoch e).  Rows as in evaluate(): the nodes of `split`, or the `nodes` query (dataset ids, repeats
+        allowed), or with both None every row.  Returns a dict by list position: pred (int32, the argmax of the mean softmax row,
+        lowest class on a tie), confidence (its mean probability), entropy, expected_entropy, mutual_information, variation_ratio
+        (f32, formed in float64 on the GPU), with mean_prob=True mean_prob f32 [n, C], with votes=True votes int32 [n, C], with
+        return_samples=True samples_logp f32 [samples, n, C] (the per-sample log-softmax rows at the model's temperature), and
+        seed, p, samples, first_sample as used.  Single-label models, at most 64 classes, hidden width at most 256, f32 tables,
+        one rank.  Training state is not touched."""
+        self._mc_args(split, nodes, samples, p, seed, first_sample)
+        if nodes is None:
+            q, n, listed = None, 0, self.info()["local_rows"]     # (a split lists at most that many rows)
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = listed = q.size
+            q = q if n else np.zeros(1, np.int32)              # an empty query is still a query (not "every row")
+        c, s_count = self.params.output_dim, int(samples)
+        rows = C.c_int64()
+        pp = C.c_float(float(p)) if p is not None else None
+        sp = C.c_uint64(int(seed)) if seed is not None else None
+        args = (self.h, int(split or 0), q.ctypes.data if q is not None else None, n, s_count, C.byref(pp) if pp is not None else None,
+                C.byref(sp) if sp is not None else None, int(first_sample))
+        if split is not None:
+            # the rows of a split are known to the model: a call without arrays checks the arguments and counts them, no more
+            _ck(self.lib, self.lib.gcnhost_model_mc_dropout(*args, 0, *([None] * 11), C.byref(rows)), "mc_dropout")
+            listed = rows.value
+        cap = max(listed, 1)
+        pred = np.zeros(cap, np.int32)
+        f32 = {k: np.zeros(cap, np.float32) for k in ("confidence", "entropy", "expected_entropy", "mutual_information", "variation_ratio")}
+        mp = np.zeros((cap, c), np.float32) if mean_prob else None
+        vt = np.zeros((cap, c), np.int32) if votes else None
+        sl = np.zeros((s_count, cap, c), np.float32) if return_samples else None
+        su, pu = C.c_uint64(), C.c_float()
+        _ck(self.lib, self.lib.gcnhost_model_mc_dropout(
+            *args, cap, pred.ctypes.data, f32["confidence"].ctypes.data, f32["entropy"].ctypes.data, f32["expected_entropy"].ctypes.data,
+            f32["mutual_information"].ctypes.data, f32["variation_ratio"].ctypes.data, mp.ctypes.data if mean_prob else None,
+            vt.ctypes.data if votes else None, sl.ctypes.data if return_samples else None, C.byref(su), C.byref(pu), C.byref(rows)), "mc_dropout")
+        k = rows.value
+        out = dict(pred=pred[:k].copy(), seed=su.value, p=pu.value, samples=s_count, first_sample=int(first_sample))
+        out.update({name: a[:k].copy() for name, a in f32.items()})
+        if mean_prob:
+            out["mean_prob"] = mp[:k].copy()
+        if votes:
+            out["votes"] = vt[:k].copy()
+        if return_samples:
+            out["samples_logp"] = sl[:, :k].copy()
         return out
 
     # ---- split conformal prediction: a set of classes per node that holds the true one with probability >= 1 - alpha

@@ -395,6 +395,57 @@ class Device:
             raise GcnHipError(f"gcnhip_calib_scale_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
         return ob.download(), pb.download()[:n_table]
 
+    # ---- Monte Carlo dropout (csrc/mcdropout.hip)
+    def mc_accumulate_rows(self, samples, rows=None, ld=None, n=None, fill=None):
+        """gcnhip_mc_accumulate_rows, one launch per sample in order, the first with first=1: (acc float64 [n, C + 1], votes int32
+        [n, C]) by list position.  samples: f32 [S, n_table, C] log-softmax rows (each uploaded with row stride ld, NaN padding);
+        rows: the listed rows (None: rows 0 .. n - 1, n = n_table unless given).  fill=(f64, i32): the accumulators start as these
+        sentinels (the first launch must store over them); None: NaN / -777"""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim == 2:
+            samples = samples[None]
+        s_count, n_table, c = samples.shape
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        rb = self.buf(rows if rows.size else np.zeros(1, np.int32)) if rows is not None else None
+        listed = int(n_table if rows is None else rows.size) if n is None else int(n)
+        f64, i32 = (np.nan, -777) if fill is None else fill
+        ab = self.buf(np.full((max(listed, 1), c + 1), f64, np.float64))
+        vb = self.buf(np.full((max(listed, 1), c), i32, np.int32))
+        for s in range(s_count):
+            lb = self.padded(samples[s], max(ld or c, c)) if n_table else self.buf(np.zeros(1, np.float32))   # (a stride below C is refused)
+            rc = self.lib.gcnhip_mc_accumulate_rows(self.ctx, lb.ptr, ld or c, n_table, rb.ptr if rb else None, listed, c, int(s == 0), ab.ptr, vb.ptr)
+            if rc != 0:
+                raise GcnHipError(f"gcnhip_mc_accumulate_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return ab.download()[:listed], vb.download()[:listed]
+
+    MC_OUTPUTS = ("mean_prob", "pred", "confidence", "entropy", "expected_entropy", "mutual_information", "variation_ratio")
+
+    def mc_finalize_rows(self, acc, votes, samples, ld_mp=None, outputs=MC_OUTPUTS, fill=np.nan, pred_fill=-777):
+        """gcnhip_mc_finalize_rows: a dict of the outputs named in `outputs` (the others are passed as NULL) — mean_prob f32
+        [n, ld_mp] whose padding columns keep `fill`, pred int32 [n], the rest f32 [n]; every array starts as `fill` / `pred_fill`"""
+        acc = np.ascontiguousarray(acc, np.float64)
+        votes = np.ascontiguousarray(votes, np.int32)
+        n, c = votes.shape
+        ld_mp = ld_mp or c
+        ab = self.buf(acc if n else np.zeros(1, np.float64))
+        vb = self.buf(votes if n else np.zeros(1, np.int32))
+        bufs = {}
+        for name in self.MC_OUTPUTS:
+            if name not in outputs:
+                continue
+            if name == "mean_prob":
+                bufs[name] = self.buf(np.full((max(n, 1), ld_mp), fill, np.float32))
+            elif name == "pred":
+                bufs[name] = self.buf(np.full(max(n, 1), pred_fill, np.int32))
+            else:
+                bufs[name] = self.buf(np.full(max(n, 1), fill, np.float32))
+        ptr = lambda name: bufs[name].ptr if name in bufs else None
+        rc = self.lib.gcnhip_mc_finalize_rows(self.ctx, ab.ptr, vb.ptr, n, c, int(samples), ptr("mean_prob"), ld_mp, ptr("pred"), ptr("confidence"),
+                                              ptr("entropy"), ptr("expected_entropy"), ptr("mutual_information"), ptr("variation_ratio"))
+        if rc != 0:
+            raise GcnHipError(f"gcnhip_mc_finalize_rows: error {rc}: {self.lib.gcnhip_last_error().decode()}")
+        return {name: b.download()[:n] for name, b in bufs.items()}
+
     # ---- split conformal prediction sets (csrc/conformal.hip)
     def conformal_scores(self, logp, beta, method, lam=0.0, k_reg=0, rows=None, ld=None, ld_out=None, fill=np.nan, n=None):
         """gcnhip_conformal_scores: out [n_table, ld_out] — rows not listed and padding columns keep `fill`.  logp f32 [n_table, C]

@@ -237,6 +237,27 @@ int gcnhip_calib_bins_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int
                            int num_classes, float beta, int bins, int32_t *d_count, int32_t *d_correct, double *d_conf_sum);
 int gcnhip_calib_scale_rows(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, float beta,
                             float *out_logp, int ld_out, float *d_prob);
+/* ---- Monte Carlo dropout (mcdropout.hip; beyond the reference: per-node uncertainty from S stochastic forwards) ----
+ * The conventions of the calibration kernels above: a wave per listed row, lane j on class j (1 <= num_classes <= 64, rows of any
+ * stride >= num_classes), fp contract(off), rows listed as d_rows[i], i < n, or 0 .. n - 1 when d_rows == NULL (then n <= n_table);
+ * no atomics, so the bits depend on the sample sequence alone; no launch allocates or synchronises; anything refused returns -1
+ * with a message naming the entry point (gcnhip_last_error).  The accumulators are indexed by LIST POSITION i (a row listed
+ * twice has two independent ones): acc_f64 [n x (C + 1)] doubles, acc_votes [n x C] int32.
+ * gcnhip_mc_accumulate_rows: one sample.  l = logp[d_rows[i], :] are log-softmax rows as gcnhip_graphsum_predict leaves them (after
+ *   gcnhip_calib_scale_rows: the rows at T != 1, hence no beta here).  In float64: acc_f64[i (C + 1) + c] += exp(l_c);
+ *   acc_f64[i (C + 1) + C] += - sum_c exp(l_c) . l_c (a class with exp(l_c) == 0 contributes 0, l_c = -inf included);
+ *   acc_votes[i C + argmax_c l_c] += 1, the lowest class on a tie.  first != 0 stores instead of adding (no memset launch is
+ *   needed).  An id outside [0, n_table) adds nothing (first != 0: zeros).
+ * gcnhip_mc_finalize_rows: after `samples` >= 1 accumulations.  In float64 until the store: mean_prob[i, c] = acc / samples
+ *   ([n x ld_mp], columns past C not written); pred[i] = its argmax, lowest class on a tie; confidence[i] = mean_prob[i, pred];
+ *   entropy[i] = - sum_c mean_prob ln mean_prob (a zero contributes 0); expected_entropy[i] = acc[.., C] / samples;
+ *   mutual_information[i] = max(0, entropy - expected_entropy); variation_ratio[i] = 1 - max_c votes[i, c] / samples.
+ *   Outputs are f32 (int32 for pred), indexed by list position; any output pointer may be NULL. */
+int gcnhip_mc_accumulate_rows(gcnhip_ctx *ctx, const float *logp, int ld, int n_table, const int32_t *d_rows, int n, int num_classes, int first,
+                              double *acc_f64, int32_t *acc_votes);
+int gcnhip_mc_finalize_rows(gcnhip_ctx *ctx, const double *acc_f64, const int32_t *acc_votes, int n, int num_classes, int samples, float *mean_prob,
+                            int ld_mp, int32_t *pred, float *confidence, float *entropy, float *expected_entropy, float *mutual_information,
+                            float *variation_ratio);
 /* ---- split conformal prediction sets (conformal.hip; beyond the reference: a set of classes per node with a coverage guarantee) ----
  * The conventions of the calibration kernels above: a wave per row, lane j on class j (1 <= num_classes <= 64, rows of any stride
  * >= num_classes), fp contract(off), rows listed as d_rows[i], i < n, or 0 .. n - 1 when d_rows == NULL (then n <= n_table), ids

@@ -325,6 +325,26 @@ int gcnhost_attach_rows(int num_nodes, const int *g_indptr, int m, const int64_t
                         int32_t *out_col, float *out_coef, int32_t *out_len);
 int gcnhost_model_predict_new(gcnhost_model *m, const int *x_indptr, const int *x_indices, const float *x_values, int n_new, const int64_t *nbr_ptr,
                               const int *nbr_ids, const float *thr, int n_thr, int32_t *pred, float *prob, float *logp, uint32_t *bits);
+/* ---- Monte Carlo dropout (ModelQueries::mc_dropout, host/queries.h; csrc/mcdropout.hip has the definition; beyond the reference) ----
+ * Per-node uncertainty from `samples` forwards with dropout on: sample s in [first_sample, first_sample + samples) is the model's
+ * training forward with the epoch word s, the rate *p (p == NULL: the model's dropout) and the seed *seed (seed == NULL: the model's
+ * seed ^ KEY_MC_DROPOUT; the model's own seed with first_sample = e draws the masks of training epoch e).  Rows as
+ * gcnhost_model_evaluate takes them: the nodes of `split` (1 train, 2 validation, 3 test), or with split == 0 the `nodes` query (n
+ * dataset ids, repeats allowed; NULL: every row).  *rows = the rows listed.  A call with every array NULL checks the arguments,
+ * writes *rows and launches nothing (a split's rows are the model's to count); otherwise capacity must be *rows (samples_logp is
+ * laid out by it; capacity >= 1 will do for an empty list).  By list position, each array may be NULL: pred
+ * int32 [rows] = argmax of the mean softmax row (lowest class on a tie), confidence = its mean probability, entropy (predictive),
+ * expected_entropy, mutual_information = max(0, entropy - expected_entropy), variation_ratio = 1 - (largest vote count) / samples,
+ * all f32 [rows] formed in float64 on the device; mean_prob f32 [rows x C]; votes int32 [rows x C]; samples_logp f32 [samples x
+ * rows x C] = the per-sample log-softmax rows at the model's temperature.  *seed_used / *p_used: what the samples were drawn with.
+ * Training state is untouched (the metrics ring, the current split, the logits, the captured epoch graph, Adam's state, the epoch
+ * word, the mask bits).  Refused with a message before any launch: a multi-label model, more than 64 classes, more than one rank,
+ * bf16 tables, a hidden width above 256, samples outside 1..1024, p outside [0, 1), first_sample + samples > 2^32, a split outside
+ * 0..3, a node id outside the graph. */
+int gcnhost_model_mc_dropout(gcnhost_model *m, int split, const int *nodes, int n, int samples, const float *p, const uint64_t *seed, uint64_t first_sample,
+                             int64_t capacity, int32_t *pred, float *confidence, float *entropy, float *expected_entropy, float *mutual_information,
+                             float *variation_ratio, float *mean_prob, int32_t *votes, float *samples_logp, uint64_t *seed_used, float *p_used,
+                             int64_t *rows);
 int gcnhost_thresholds_read(const char *path, int *num_classes, float *thr);
 int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr, const int64_t *pos, const int64_t *neg, const int64_t *tp,
                              const int64_t *fp, const int64_t *fn, const double *f);
