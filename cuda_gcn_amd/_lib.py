@@ -128,6 +128,11 @@ GCNHIP_SYMBOLS = {
     "gcnhip_topk_rows": (I, [P, P, I, I, I, P, P, P, I, I, I, I, P, C.c_size_t, I, P, P]),
     "gcnhip_pair_scores": (I, [P, P, I, I, I, P, P, P, I, P]),
     "gcnhip_embed_rows": (I, [P, P, I, I, I, P, P, I, P, I]),
+    "gcnhip_kmeans_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_kmeans_assign": (I, [P, P, I, I, I, P, P, I, P, I, P, I, P, P, P, P]),
+    "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
+    "gcnhip_kmeans_seed": (I, [P, P, I, I, I, P, P, I, I, U64, P, I, P, P, C.c_size_t]),
+    "gcnhip_contingency_rows": (I, [P, P, P, I, P, I, I, I, P, P]),
     "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
@@ -259,6 +264,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_embed": (I, [P, P, I, P, I]),
     "gcnhost_model_similar": (I, [P, P, I, I, I, I, P, P]),
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
+    "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
+    "gcnhost_cluster_report": (I, [I, I, P, P]),
     "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),
     "gcnhost_model_feature_importance": (I, [P, I, P, I, C.c_size_t, P, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),

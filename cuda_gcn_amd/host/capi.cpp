@@ -16,6 +16,7 @@
 #include "labels.h"
 #include "report.h"
 #include "calibration.h"
+#include "kmeans.h"
 #include "conformal.h"
 #include "ranking.h"
 #include "thresholds.h"
@@ -328,6 +329,32 @@ int gcnhost_model_explain(gcnhost_model *m, const int *nodes, const int *classes
 int gcnhost_model_feature_importance(gcnhost_model *m, int split, const int *nodes, int n, size_t feat_scratch_bytes, double *mean_abs, int64_t *count) {
     if (!m) { g_err = "gcnhost_model_feature_importance: invalid argument"; return -1; }
     API_TRY({ m->gcn->queries().feature_importance(split, nodes, n, feat_scratch_bytes, mean_abs, count); })
+}
+int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, int n, int iters, int normalize, int init, const int *init_pos,
+                         const float *init_centers, const uint64_t *seed, size_t scratch_bytes, int64_t capacity, int32_t *assign, float *dist2,
+                         float *centers, int32_t *sizes, int32_t *seed_pos, double *history, int64_t *contingency, int64_t *info, double *inertia,
+                         uint64_t *seed_used) {
+    if (!m) { g_err = "gcnhost_model_kmeans: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.kmeans_rows(k, split, nodes, n, iters, init, init_pos, init_centers);
+        if ((assign || dist2) && listed > capacity)
+            throw GcnHipFailure(-1, "kmeans: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::KMeans r = q.kmeans(k, split, nodes, n, iters, normalize != 0, init, init_pos, init_centers, seed, scratch_bytes, assign, dist2,
+                                                centers, sizes, seed_pos, history, contingency);
+        if (info) { info[0] = r.rows; info[1] = r.iters_run; info[2] = r.converged ? 1 : 0; info[3] = r.skipped; }
+        if (inertia) *inertia = r.inertia;
+        if (seed_used) *seed_used = r.seed;
+    })
+}
+int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary) {
+    ClusterReport r;
+    if (gcn_cluster_report(k, num_classes, counts, &r, &g_err) != 0) return -1;
+    if (summary) {
+        const double v[9] = {r.purity, r.homogeneity, r.completeness, r.v_measure, r.nmi, r.ari, r.entropy_classes, r.entropy_clusters, (double)r.rows};
+        std::copy(v, v + 9, summary);
+    }
+    return 0;
 }
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,
                                double *confidence, double *summary) {

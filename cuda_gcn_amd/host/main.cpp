@@ -103,6 +103,14 @@
 //                            H1 = ReLU(A^.X.W1) of an evaluation forward with the final (or loaded) weights, %.9g (exact f32).
 //   GCN_SIMILAR=<file>       one line per node: `node id:score ...`, its 10 nearest nodes by the cosine of those rows (best
 //                            first, equal scores by ascending id, the node itself left out), found on the GPU.
+// Clustering (beyond the reference; ModelQueries::kmeans, kernels in csrc/kmeans.hip), after the test line and the steps above.
+// One GPU, hidden_dim at most 256, f32 tables, a single-label model:
+//   GCN_CLUSTER=<file>       k-means on the unit rows of the hidden layer of EVERY node: GCN_CLUSTER_K clusters (default: the
+//                            number of classes, 1..256), at most GCN_CLUSTER_ITERS iterations (default 100), k-means++ seeding
+//                            on GCN_CLUSTER_SEED (a 64-bit integer; default: the model's seed).  One line is printed:
+//                            `clusters=<k> cluster_iters=<n> cluster_inertia=<x> cluster_nmi=<a> cluster_ari=<b> cluster_purity=<c>`,
+//                            the last three of the TEST split's nodes against their labels (host/kmeans.h).  The file gets one
+//                            line per node in id order: `node cluster dist2` (%.9g).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
 // Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
 // and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
 //   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
@@ -137,6 +145,7 @@
 #include "class_weights.h"
 #include "gcn.h"
 #include "hip_check.h"
+#include "kmeans.h"
 #include "labels.h"
 #include "parser.h"
 #include "ranking.h"
@@ -338,6 +347,29 @@ int main(int argc, char **argv) {
                                                      : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_EMBED / GCN_SIMILAR " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *cluster_path = getenv("GCN_CLUSTER");
+    if (cluster_path && !*cluster_path) cluster_path = nullptr;
+    const int cluster_k = env_int("GCN_CLUSTER_K", params.output_dim), cluster_iters = env_int("GCN_CLUSTER_ITERS", 100);
+    uint64_t cluster_seed = 0;
+    const char *cluster_seed_text = getenv("GCN_CLUSTER_SEED");
+    if (cluster_seed_text && !*cluster_seed_text) cluster_seed_text = nullptr;
+    if (cluster_path) {
+        char *end = nullptr;
+        if (cluster_seed_text) cluster_seed = strtoull(cluster_seed_text, &end, 0);
+        const char *why = multilabel_path                                          ? "scores the clusters against single labels (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                             ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                                ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                          ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : cluster_k < 1 || cluster_k > 256 || cluster_k > params.num_nodes ? "needs GCN_CLUSTER_K in 1..256 and at most the number of nodes"
+                          : cluster_iters < 1                                      ? "needs GCN_CLUSTER_ITERS of at least 1"
+                          : cluster_seed_text && (end == cluster_seed_text || *end) ? "needs an integer GCN_CLUSTER_SEED"
+                                                                                   : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_CLUSTER " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -644,6 +676,29 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the neighbours to ") + similar_path);
                 fprintf(stderr, "gcn-hip: %d cosine neighbours of %d nodes written to %s\n", K, N, similar_path);
+            }
+            if (cluster_path) {                                // one rank (checked above): every node, rows by node id
+                const int N = params.num_nodes, C = params.output_dim, K = cluster_k;
+                std::vector<int32_t> assign((size_t)std::max(N, 1));
+                std::vector<float> dist2((size_t)std::max(N, 1));
+                const ModelQueries::KMeans r =
+                    gcn.queries().kmeans(K, 0, nullptr, N, cluster_iters, true, ModelQueries::KMEANS_INIT_PLUSPLUS, nullptr, nullptr,
+                                         cluster_seed_text ? &cluster_seed : nullptr, 0, assign.data(), dist2.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+                std::vector<int64_t> table((size_t)K * C, 0);      // the test split's nodes against their labels
+                for (int i = 0; i < N; i++)
+                    if (data.split[i] == 3 && data.label[i] >= 0 && data.label[i] < C && assign[i] >= 0) table[(size_t)assign[i] * C + data.label[i]]++;
+                ClusterReport rep;
+                std::string err;
+                if (gcn_cluster_report(K, C, table.data(), &rep, &err) != 0) throw GcnHipFailure(-1, err);
+                printf("clusters=%d cluster_iters=%d cluster_inertia=%.9g cluster_nmi=%.6f cluster_ari=%.6f cluster_purity=%.6f\n", K, r.iters_run, r.inertia,
+                       rep.nmi, rep.ari, rep.purity);
+                FILE *f = fopen(cluster_path, "w");
+                bool ok = f != nullptr;
+                for (int i = 0; ok && i < N; i++) ok = fprintf(f, "%d %d %.9g\n", i, assign[i], dist2[i]) > 0;
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the clusters to ") + cluster_path);
+                fprintf(stderr, "gcn-hip: %d clusters of %d nodes (%d iterations%s, seed %llu) written to %s\n", K, N, r.iters_run,
+                        r.converged ? ", converged" : "", (unsigned long long)r.seed, cluster_path);
             }
             if (explain_path) {                                // one rank (checked above)
                 const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;

@@ -254,3 +254,5 @@ constexpr uint64_t KEY_INPUT_DROPOUT = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t KEY_HIDDEN_DROPOUT = 0xD1B54A32D192ED03ull;
 // not a site: the default seed of a Monte Carlo dropout query is the model's seed ^ this, so that its samples repeat no epoch's masks
 constexpr uint64_t KEY_MC_DROPOUT = 0xA0761D6478BD642Full;
+// not a site either: the stream of the k-means++ seeding draws (ModelQueries::kmeans) is the query's seed ^ this
+constexpr uint64_t KEY_KMEANS = 0xE7037ED1A0B428DBull;

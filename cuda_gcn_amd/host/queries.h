@@ -289,6 +289,38 @@ public:
                          float *confidence, float *entropy, float *expected_entropy, float *mutual_information, float *variation_ratio,
                          float *mean_prob, int32_t *votes, float *samples_logp);
 
+    // k-means on the hidden layer (Lloyd, 1982; seeding: Arthur & Vassilvitskii, 2007): the rows embed() exports, grouped where
+    // they lie (csrc/kmeans.hip has the definitions; host/kmeans.cpp the loop).  Rows: the nodes of `split` (1..3) in ascending
+    // dataset id, or with split == 0 the `nodes` query (dataset ids in the order given, repeats allowed; NULL: every node in id
+    // order) — list order is part of the definition of the update's sums.  Steps: sync(); embed_forward (variable 3 rewritten, as
+    // by every forward; with `normalize` its inverse norms, so that the rows clustered are unit rows: a factored model's stored
+    // row carries 1 / sqrt(deg), see row_scale(); without it the clustering is of the stored rows); the initial centres —
+    // KMEANS_INIT_PLUSPLUS: gcnhip_kmeans_seed on the stream seed ^ KEY_KMEANS (seed NULL: env.seed); KMEANS_INIT_POSITIONS:
+    // the rows at k list positions; KMEANS_INIT_CENTERS: k x hidden floats — and their norms (gcnhip_kmeans_update on no rows);
+    // then gcnhip_kmeans_assign / gcnhip_kmeans_update until nothing moved or `iters` assignments were made: the four bytes of
+    // `moved` are all that is read back per iteration.  Every assignment is followed by its update, so the centres returned are
+    // the means of the returned assignment (at a fixed point also the centres it was made to: the same members in the same
+    // order give the same bits), and dist2 is measured to the centres the assignment was made to.  Outputs (each may be NULL):
+    // assign / dist2 [rows] by list position, centers [k x hidden], sizes [k], seed_pos [k] (list positions; KMEANS_INIT_PLUSPLUS only), history [iters x 2] =
+    // (moved, inertia of that assignment) per iteration run, contingency [k x C] (single-label models, at most 64 classes:
+    // gcnhip_contingency_rows against the dataset's labels) with *skipped.  predict()'s contract: the metrics ring, the current
+    // split, variable 6 and the captured epoch graph are untouched.  Refused with a message before any launch: more than one
+    // rank, a hidden width above 256, bf16 tables, k outside 1..256 or above the listed rows, iters < 1, a split outside 0..3,
+    // an init position outside the list, a node id outside the graph.
+    enum KMeansInit { KMEANS_INIT_PLUSPLUS = 0, KMEANS_INIT_POSITIONS = 1, KMEANS_INIT_CENTERS = 2 };
+    struct KMeans {
+        int k = 0, iters_run = 0;
+        bool converged = false;
+        int64_t rows = 0, skipped = 0;
+        double inertia = 0;
+        uint64_t seed = 0;
+    };
+    // the refusals alone, and the number of rows the query lists (a caller sizes its arrays by it); touches no device state
+    int64_t kmeans_rows(int k, int split, const int *nodes, int n, int iters, int init, const int *init_pos, const float *init_centers);
+    KMeans kmeans(int k, int split, const int *nodes, int n, int iters, bool normalize, int init, const int *init_pos, const float *init_centers,
+                  const uint64_t *seed, size_t scratch_bytes, int32_t *assign, float *dist2, float *centers, int32_t *sizes, int32_t *seed_pos,
+                  double *history, int64_t *contingency);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                         // every device buffer of a query
@@ -383,6 +415,13 @@ private:
     Scratch<double> d_mc_acc{&arena};
     Scratch<int32_t> d_mc_votes{&arena}, d_mc_pred{&arena}, d_mc_once{&arena};
     Scratch<float> d_mc_out{&arena}, d_mc_samples{&arena};
+    // kmeans: the listed rows, centres and their norms, both assignments, distances, sizes, seed positions, {moved | skipped},
+    // the inertia, the update's and the seeding's scratch, the cluster x class counts
+    Scratch<int32_t> d_km_rows{&arena}, d_km_assign{&arena}, d_km_sizes{&arena}, d_km_pos{&arena}, d_km_flag{&arena}, d_km_counts{&arena};
+    Scratch<float> d_km_centers{&arena}, d_km_cn{&arena}, d_km_dist{&arena};
+    Scratch<double> d_km_inertia{&arena};
+    Scratch<unsigned char> d_km_scratch{&arena};
+    std::vector<int> kmeans_list(const char *what, int split, const int *nodes, int &n);
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

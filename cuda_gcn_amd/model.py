@@ -785,6 +785,81 @@ class HipGCNModel:
                                                          out.ctypes.data), "score_edges")
         return out[:s.size]
 
+    # ---- k-means on the hidden layer: groups of nodes, on the GPU
+    def _cluster_args(self, k, split, nodes, iters, init, seed):
+        """argument checks that need no GPU; returns (k, init code, init positions or None, init centres or None)"""
+        what = "cluster"
+        if self.params.hidden_dim > 256:
+            raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+        if split is not None and nodes is not None:
+            raise GcnHostError(f"{what}: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"{what}: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        k = self.params.output_dim if k is None else k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 256:
+            raise GcnHostError(f"{what}: k must be an integer in 1..256, got {k!r}")
+        if isinstance(iters, bool) or int(iters) != iters or iters < 1:
+            raise GcnHostError(f"{what}: iters must be an integer >= 1, got {iters!r}")
+        if seed is not None and (int(seed) != seed or not 0 <= seed < 1 << 64):
+            raise GcnHostError(f"{what}: the seed is an integer in [0, 2^64), got {seed!r}")
+        if isinstance(init, str):
+            if init != "kmeans++":
+                raise GcnHostError(f"{what}: init is 'kmeans++', an int array of k row positions or a float [k, hidden] array, got {init!r}")
+            return int(k), 0, None, None
+        arr = np.asarray(init)
+        if arr.dtype.kind in "iu":
+            if arr.shape != (k,):
+                raise GcnHostError(f"{what}: init positions must have shape ({k},), got {arr.shape}")
+            return int(k), 1, np.ascontiguousarray(arr, np.int32), None
+        if arr.dtype.kind != "f" or arr.shape != (k, self.params.hidden_dim):
+            raise GcnHostError(f"{what}: init centres must be a float array of shape ({k}, {self.params.hidden_dim}), got {arr.dtype} {arr.shape}")
+        return int(k), 2, None, np.ascontiguousarray(arr, np.float32)
+
+    def cluster(self, k=None, split=None, nodes=None, iters=100, normalize=True, init="kmeans++", seed=None, report=True, scratch_bytes=0):
+        """k-means (Lloyd) on the rows embed() exports, run where they lie: one evaluation forward, k-means++ seeding by an
+        exponential race on a Philox stream, then assignment (an n x k x hidden product on the exact-f32 MFMA with the row-wise
+        argmin behind it) and update (float64 means in a summation order fixed by the data) until an assignment moves nothing or
+        `iters` are made — the same answer, bit for bit, on every run.  Rows: the nodes of `split` in ascending id, or the `nodes`
+        query (dataset ids in the order given, repeats allowed), or with both None every node in id order.  k: None = output_dim.
+        normalize=True clusters unit rows (cosine geometry); it is the default because a factored model (row_scale()) keeps
+        1/sqrt(deg) of the node on its stored row — with normalize=False the clustering is of the STORED rows, as similar()'s
+        "dot" is.  init: "kmeans++", an int array of k list positions whose rows start as centres, or a float [k, hidden] array.
+        seed: the 64-bit seed of the seeding draws (None: the model's stream_seed).  Returns a dict: assign int32 [n] and dist2
+        f32 [n] by list position (squared distance to the centre the row was assigned to), centers f32 [k, hidden] (the means of
+        the returned assignment; an empty cluster keeps its centre), sizes int32 [k], seed_pos (list positions, None unless
+        seeded), iters_run, converged, history float64 [iters_run, 2] = (moved, inertia) per iteration, inertia, seed.  With
+        report=True on a single-label model with at most 64 classes also contingency int64 [k, C] against the dataset's labels,
+        counted on the GPU, skipped (rows without a label in [0, C)) and cluster_report()'s scores.  One rank, hidden width at
+        most 256, f32 tables, k at most the rows listed.  Training state is not touched."""
+        k, code, ipos, icen = self._cluster_args(k, split, nodes, iters, init, seed)
+        if nodes is None:
+            q, n, cap = None, 0, self.params.num_nodes
+        else:
+            q = np.ascontiguousarray(nodes, np.int32).ravel()
+            n = cap = q.size
+            q = q if n else np.zeros(1, np.int32)
+        h, c = self.params.hidden_dim, self.params.output_dim
+        want_report = bool(report) and not self.multilabel and c <= 64
+        assign, dist2 = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        centers, sizes, pos = np.zeros((k, h), np.float32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        hist = np.zeros((int(iters), 2), np.float64)
+        cont = np.zeros((k, c), np.int64) if want_report else None
+        info, inertia, su = np.zeros(4, np.int64), C.c_double(), C.c_uint64()
+        sp = C.c_uint64(int(seed)) if seed is not None else None
+        _ck(self.lib, self.lib.gcnhost_model_kmeans(
+            self.h, k, int(split or 0), q.ctypes.data if q is not None else None, n, int(iters), int(bool(normalize)), code,
+            ipos.ctypes.data if ipos is not None else None, icen.ctypes.data if icen is not None else None,
+            C.byref(sp) if sp is not None else None, int(scratch_bytes), cap, assign.ctypes.data, dist2.ctypes.data, centers.ctypes.data,
+            sizes.ctypes.data, pos.ctypes.data if code == 0 else None, hist.ctypes.data, cont.ctypes.data if want_report else None,
+            info.ctypes.data, C.byref(inertia), C.byref(su)), "cluster")
+        rows, run = int(info[0]), int(info[1])
+        out = dict(assign=assign[:rows].copy(), dist2=dist2[:rows].copy(), centers=centers, sizes=sizes, seed_pos=pos if code == 0 else None,
+                   iters_run=run, converged=bool(info[2]), history=hist[:run].copy(), inertia=inertia.value, seed=su.value)
+        if want_report:
+            out.update(contingency=cont, skipped=int(info[3]))
+            out.update(cluster_report(cont))
+        return out
+
     # ---- explaining a logit: neighbour, hidden-unit and feature shares, on the GPU
     def _explain_args(self, what, nodes, classes=None):
         """argument checks that need no GPU; returns (node ids int32 or None, classes int32 or None)"""
@@ -1060,6 +1135,27 @@ def conformal_quantile(scores, alpha, labels=None, num_classes=None):
     if labels is None:
         return dict(threshold=float(th[0]), n_cal=int(nc[0]), k=int(k[0]))
     return dict(threshold=th, n_cal=nc, k=k)
+
+
+KEY_KMEANS = 0xE7037ED1A0B428DB           # host/module.h: the stream of cluster()'s seeding draws is its seed ^ this
+
+
+def cluster_report(contingency):
+    """The scores of a clustering against class labels from the integer table contingency [k, C] (rows: clusters) — host only,
+    no GPU; the one place they are derived (host/kmeans.h has the formulas).  Returns a dict of float64: purity, homogeneity,
+    completeness, v_measure (Rosenberg & Hirschberg), nmi (arithmetic-mean normalisation), ari (Hubert & Arabie),
+    entropy_classes, entropy_clusters (natural logarithm), and rows.  Empty rows and columns are allowed; one cluster or one class
+    gives the conventional values (both: a perfect match), never NaN.  A negative entry raises GcnHostError."""
+    t = np.ascontiguousarray(contingency, np.int64)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise GcnHostError(f"cluster_report: a [k, C] table with k, C >= 1, got shape {t.shape}")
+    lib = _lib.gcnhost()
+    s = np.zeros(9, np.float64)
+    _ck(lib, lib.gcnhost_cluster_report(t.shape[0], t.shape[1], t.ctypes.data, s.ctypes.data), "cluster_report")
+    names = ("purity", "homogeneity", "completeness", "v_measure", "nmi", "ari", "entropy_classes", "entropy_clusters")
+    out = {name: float(v) for name, v in zip(names, s)}
+    out["rows"] = int(s[8])
+    return out
 
 
 def calibration_report(count, correct, conf_sum):

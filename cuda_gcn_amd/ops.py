@@ -632,6 +632,92 @@ class Device:
             self._embed_fail("gcnhip_embed_rows", rc)
         return ob.download()[:n, :dim]
 
+    # ---- k-means on the rows of a table (csrc/kmeans.hip): table and centres are uploaded with their row strides and NaN padding
+    def _kmeans_rows(self, rows, n_table):
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        n = n_table if r is None else int(r.size)
+        return (None if r is None else self.buf(r if n else np.zeros(1, np.int32))), n
+
+    def kmeans_plan(self, n, k, dim):
+        """gcnhip_kmeans_plan: dict(update_bytes, update_bytes_min, seed_bytes) of device scratch"""
+        a, b, s = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_kmeans_plan(int(n), int(k), int(dim), C.byref(a), C.byref(b), C.byref(s))
+        if rc != 0:
+            self._embed_fail("gcnhip_kmeans_plan", rc)
+        return dict(update_bytes=a.value, update_bytes_min=b.value, seed_bytes=s.value)
+
+    def kmeans_assign(self, table, centers, cn, rows=None, inv_norm=None, prev=None, ld=None, ldm=None):
+        """gcnhip_kmeans_assign: (assign int32 [n], dist2 f32 [n], moved) — per list position (rows None: every row) the centre
+        with the smallest cn[c] - 2 (dot . inv_norm), the lowest c on equal values; -1 / NaN for a row outside the table.  The
+        outputs are uploaded as garbage."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        centers = np.ascontiguousarray(centers, np.float32)
+        k, ldm = centers.shape[0], int(ldm or dim)
+        mb = self.padded(centers, ldm)
+        cb = self.buf(np.ascontiguousarray(cn, np.float32).ravel())
+        rb, n = self._kmeans_rows(rows, n_table)
+        pb = None if prev is None else self.buf(np.ascontiguousarray(prev, np.int32).ravel() if n else np.zeros(1, np.int32))
+        ab = self.buf(np.full(max(n, 1), 12345, np.int32))
+        db = self.buf(np.full(max(n, 1), 7.5, np.float32))
+        fb = self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_kmeans_assign(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, mb.ptr, ldm, cb.ptr, k,
+                                           pb.ptr if pb else None, ab.ptr, db.ptr, fb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_kmeans_assign", rc)
+        return ab.download()[:n], db.download()[:n], int(fb.download()[0])
+
+    def kmeans_update(self, table, assign, centers, dist2=None, rows=None, inv_norm=None, ld=None, ldm=None, scratch_bytes=None):
+        """gcnhip_kmeans_update: dict(centers f32 [k, dim], sizes int32 [k], cn f32 [k], inertia float) — the float64 mean of every
+        centre's members in ascending list position (an empty centre keeps its row of `centers`).  scratch_bytes: the caller's
+        scratch (None: gcnhip_kmeans_plan's update_bytes)."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        centers = np.ascontiguousarray(centers, np.float32)
+        k, ldm = centers.shape[0], int(ldm or dim)
+        mb = self.padded(centers, ldm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        a = np.ascontiguousarray(assign, np.int32).ravel()
+        assert a.size == n, (a.size, n)
+        ab = self.buf(a if n else np.zeros(1, np.int32))
+        db = None if dist2 is None else self.buf(np.ascontiguousarray(dist2, np.float32).ravel() if n else np.zeros(1, np.float32))
+        sbytes = self.kmeans_plan(n, k, dim)["update_bytes"] if scratch_bytes is None else int(scratch_bytes)
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        zb, cb, ib = self.buf(np.full(k, -777, np.int32)), self.buf(np.full(k, np.nan, np.float32)), self.buf(np.full(1, np.nan, np.float64))
+        rc = self.lib.gcnhip_kmeans_update(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, ab.ptr,
+                                           db.ptr if db else None, k, mb.ptr, ldm, zb.ptr, cb.ptr, ib.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_kmeans_update", rc)
+        return dict(centers=mb.download()[:, :dim].copy(), sizes=zb.download(), cn=cb.download(), inertia=float(ib.download()[0]))
+
+    def kmeans_seed(self, table, k, stream_seed, rows=None, inv_norm=None, ld=None, ldm=None):
+        """gcnhip_kmeans_seed: (seed_pos int32 [k], centers f32 [k, dim]) — k-means++ by an exponential race on the Philox stream
+        `stream_seed` (the caller's seed ^ KEY_KMEANS)"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        k, ldm = int(k), int(ldm or dim)
+        mb = self.buf(np.full((max(k, 1), ldm), np.nan, np.float32))
+        rb, n = self._kmeans_rows(rows, n_table)
+        pb = self.buf(np.full(max(k, 1), -777, np.int32))
+        sbytes = self.kmeans_plan(n, k, dim)["seed_bytes"] if 1 <= k <= 256 else 1024
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        rc = self.lib.gcnhip_kmeans_seed(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, k,
+                                         int(stream_seed) & ((1 << 64) - 1), mb.ptr, ldm, pb.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_kmeans_seed", rc)
+        return pb.download()[:k], mb.download()[:k, :dim].copy()
+
+    def contingency_rows(self, assign, truth, k, num_classes, rows=None):
+        """gcnhip_contingency_rows: (counts int32 [k, C], skipped) — counts[a, y] = list positions with assign a whose row's truth is y"""
+        t = np.ascontiguousarray(truth, np.int32).ravel()
+        rb, n = self._kmeans_rows(rows, int(t.size))
+        a = np.ascontiguousarray(assign, np.int32).ravel()
+        assert a.size == n, (a.size, n)
+        ab, tb = self.buf(a if n else np.zeros(1, np.int32)), self.buf(t if t.size else np.zeros(1, np.int32))
+        cb = self.buf(np.full(max(int(k) * int(num_classes), 1), 0x5A5A5A5A, np.int32))
+        kb = self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_contingency_rows(self.ctx, ab.ptr, tb.ptr, int(t.size), rb.ptr if rb else None, n, int(k), int(num_classes), cb.ptr, kb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_contingency_rows", rc)
+        return cb.download()[:int(k) * int(num_classes)].reshape(int(k), int(num_classes)), int(kb.download()[0])
+
     # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
     def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,
                       store=True):

@@ -369,6 +369,43 @@ int gcnhip_pair_scores(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        const int32_t *dst, int n_pairs, float *out);
 int gcnhip_embed_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
                       int n, float *out, int ld_out);
+/* ---- k-means on the rows of a table (kmeans.hip; beyond the reference: grouping what a GCN learns, where it lies) ----
+ * The table contract of the embedding calls.  d_rows: a device int32 list of n rows, repeats allowed, NULL: rows 0 .. n - 1
+ * (then n <= n_table); a list position whose row is outside the table takes no part.  The row used is x^ = x . inv_norm[r]
+ * (inv_norm == NULL: x).  centers: f32 [k x ldm], 1 <= k <= 256, dim <= ldm; cn[c]: f32 squared norm of centre c.  No launch
+ * allocates or synchronises, none uses a float atomic; every output's bits are a function of the arguments' contents alone
+ * (not of launch geometry, scratch size or batching); anything else returns -1 with a message (gcnhip_last_error).
+ * gcnhip_kmeans_plan: the bytes of device scratch gcnhip_kmeans_update takes (*update_bytes: one batch; down to
+ *   *update_bytes_min: more launches, the same bits) and gcnhip_kmeans_seed needs (*seed_bytes); each may be NULL.
+ * gcnhip_kmeans_assign: d(i, c) = cn[c] - 2 . (dot_f32(T[r], M[c]) . inv_norm[r]) on the exact-f32 MFMA; assign[i] = argmin_c d,
+ *   the lowest c on equal d; dist2[i] = max(0, |x^|^2 + d(i, assign[i])) with |x^|^2 = (sumsq_f32(T[r]) . inv_norm[r]) . inv_norm[r];
+ *   *moved (device int32) = positions with assign[i] != prev[i] (prev == NULL: n).  A row outside the table: assign -1, dist2 NaN.
+ *   cn is an INPUT (gcnhip_kmeans_update writes it).  The table is read once whatever k is.
+ * gcnhip_kmeans_update: members of centre c = the positions with assign == c whose row is in the table, in ascending position.
+ *   sum[c, j] = float64 sum over them of (double)(x[r, j] . inv_norm[r]) (the product rounded to f32 first), added member by
+ *   member inside segments of 128 members and segment by segment; centers[c, j] = (float)(sum / count); an empty centre keeps
+ *   its row.  sizes[c] int32; cn[c] = (float)(the float64 sum over j, in order, of centers[c, j]^2), of kept rows too (n == 0:
+ *   the norms of the given centres); *inertia (device double, may be NULL) = the sum of dist2 over the members (dist2 NULL: 0),
+ *   per 1024 positions by a fixed tree, then over those partials by a fixed tree.
+ * gcnhip_kmeans_seed: k-means++ by an exponential race.  w(i, t) = word 0 of Philox4x32-10(counter {i, 0, t, 0x6B6D2B2B}, key
+ *   {lo32, hi32 of stream_seed}).  seed_pos[0] = (uint64(w(0, 0)) . n) >> 32; step t = 1 .. k - 1: d2min[i] = min(d2min[i],
+ *   sum_j (x^_ij - M[t - 1, j])^2) in f32 by differences; key_i = -log((w(i, t) + 0.5) . 2^-32) / d2min[i] in float64, +inf where
+ *   d2min == 0; seed_pos[t] = the position of the smallest key, the lowest position on a tie; every key +inf: the lowest
+ *   position whose row is in the table.  centers[t] = the chosen row, scaled.  All k steps are enqueued back to back.
+ * gcnhip_contingency_rows: counts [k x num_classes] int32, counts[a * C + y] = positions with assign[i] = a and truth[r] = y
+ *   (truth: [n_truth] by row, r = d_rows[i] or i); *skipped = positions with a negative assignment, a row outside [0, n_truth)
+ *   or a truth outside [0, C).  num_classes <= 64. */
+int gcnhip_kmeans_plan(int n, int k, int dim, size_t *update_bytes, size_t *update_bytes_min, size_t *seed_bytes);
+int gcnhip_kmeans_assign(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                         int n, const float *centers, int ldm, const float *cn, int k, const int32_t *prev, int32_t *assign, float *dist2,
+                         int32_t *moved);
+int gcnhip_kmeans_update(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                         int n, const int32_t *assign, const float *dist2, int k, float *centers, int ldm, int32_t *sizes, float *cn,
+                         double *inertia, void *scratch, size_t scratch_bytes);
+int gcnhip_kmeans_seed(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                       int n, int k, uint64_t stream_seed, float *centers, int ldm, int32_t *seed_pos, void *scratch, size_t scratch_bytes);
+int gcnhip_contingency_rows(gcnhip_ctx *ctx, const int32_t *assign, const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int k,
+                            int num_classes, int32_t *counts, int32_t *skipped);
 /* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
  * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
  * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and

@@ -362,6 +362,26 @@ int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr
 int gcnhost_model_embed(gcnhost_model *m, const int *nodes, int n, float *out, int normalize);
 int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int metric, int exclude_self, int32_t *out_id, float *out_score);
 int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out);
+/* k-means on the hidden layer (ModelQueries::kmeans, host/queries.h; kernels in csrc/kmeans.hip): the rows gcnhost_model_embed
+ * exports, grouped on the device.  Rows: the nodes of `split` (1 train, 2 validation, 3 test) in ascending id, or with split == 0
+ * the `nodes` query (n dataset ids in the order given, repeats allowed; NULL: every node in id order).  normalize != 0: unit
+ * rows (a factored model's stored row carries 1 / sqrt(deg)); 0: the stored rows.  init: 0 = k-means++ seeding on the stream
+ * (*seed, NULL: the model's seed) ^ KEY_KMEANS; 1 = init_pos [k] list positions; 2 = init_centers [k x hidden].  Each of
+ * at most `iters` iterations is one assignment and one update; it stops when an assignment moved nothing.  scratch_bytes: the
+ * update's device scratch (0: one batch; less: more launches, the same bits).  Outputs, each may be NULL: assign / dist2 (laid out
+ * for `capacity` rows, at least the rows listed), centers [k x hidden], sizes [k], seed_pos [k] (init 0), history [iters x 2] =
+ * (moved, inertia) per iteration run, contingency [k x num_classes] against the dataset's labels (single-label models, at most
+ * 64 classes), info [4] = {rows listed, iterations run, converged, rows the table skipped}, *inertia (the last), *seed_used.
+ * embed's contract: training state is not touched.  Refused with a message before any launch: several ranks, a hidden width
+ * above 256, bf16 tables, k outside 1..256 or above the rows listed, iters < 1, a bad split, init, position or node id.
+ * gcnhost_cluster_report (host/kmeans.h; no GPU): summary [9] = {purity, homogeneity, completeness, V-measure, NMI (arithmetic
+ * mean), ARI, H(classes), H(clusters), rows} of a table counts [k x num_classes] in float64; empty rows and columns are
+ * allowed, one cluster or one class gives the conventional values, never NaN. */
+int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, int n, int iters, int normalize, int init, const int *init_pos,
+                         const float *init_centers, const uint64_t *seed, size_t scratch_bytes, int64_t capacity, int32_t *assign, float *dist2,
+                         float *centers, int32_t *sizes, int32_t *seed_pos, double *history, int64_t *contingency, int64_t *info, double *inertia,
+                         uint64_t *seed_used);
+int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary);
 /* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
  * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
  * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
