@@ -273,7 +273,7 @@ extern "C" int gcnhip_attach_gather(gcnhip_ctx *c, const int32_t *d_ptr, const i
     if (epilogue == ATTACH_PREDICT) {
         if (dim > 64) return attach_refuse("the predict epilogue takes at most 64 columns (the row of a node sits in one wave)");
         if (!d_pred || !d_prob || (d_logp && ld_logp < dim)) return attach_refuse("the predict epilogue needs pred and prob (and ld_logp >= dim)");
-        if (!(beta > 0.f) || !(beta <= 3.402823466e38f)) return attach_refuse("beta must be finite and > 0");
+        if (!(beta > 0.f) || !(beta <= GCNHIP_BETA_MAX)) return attach_refuse(GCNHIP_BETA_REFUSAL);
     } else if (!out) {
         return attach_refuse("out is NULL and there is no predict epilogue");
     }

@@ -156,7 +156,7 @@ static const char *calib_refusal(int n_table, int n, const int32_t *d_rows, int 
     if (n_table < 0 || n < 0) return "invalid argument";
     if (C < 1 || C > WAVE) return "1 <= num_classes <= 64 (lane j holds class j)";
     if (ld < C) return "a row stride is below num_classes";
-    if (!(beta > 0.f) || !(beta <= 3.402823466e38f)) return "beta must be finite and > 0";
+    if (!(beta > 0.f) || !(beta <= GCNHIP_BETA_MAX)) return GCNHIP_BETA_REFUSAL;
     if (!d_rows && n > n_table) return "without a row list n is at most n_table";
     return nullptr;
 }

@@ -22,6 +22,9 @@ constexpr int WAVE = 64;
 // detail text for a -1 return (gcnhip_last_error); returns -1 so that a check can `return gcnhip_fail("...")`
 int gcnhip_fail(const char *detail);
 
+// what calib.hip, conformal.hip and attach.hip answer to a beta outside (0, GCNHIP_BETA_MAX] (the header derives the limit)
+#define GCNHIP_BETA_REFUSAL "beta must be finite and > 0, and at most 8e37 (beta . l must stay finite on the largest entry of a row: FLT_MAX / ln 64)"
+
 // Options of a context (gcnhip_ctx_set_option / _get_option).  Each starts from the environment variable
 // GCNHIP_<NAME IN CAPITALS>, read ONCE when the context is created — never at launch time — so a call's behaviour does not
 // depend on what the process environment holds at that moment.  gemm_bf16x3 and gs_l are the host driver's; spmm_slices,

@@ -200,7 +200,7 @@ int gcnhip_conformal_scores(gcnhip_ctx *c, const float *logp, int ld, int n_tabl
                             int method, float lam, int k_reg, float *out, int ld_out) {
     if (!c || !logp || !out) return gcnhip_fail("gcnhip_conformal_scores: invalid argument");
     if (const char *why = conformal_refusal(n_table, n, d_rows, num_classes, std::min(ld, ld_out))) CONFORMAL_REFUSE("gcnhip_conformal_scores", why);
-    if (!(beta > 0.f) || !(beta <= 3.402823466e38f)) return gcnhip_fail("gcnhip_conformal_scores: beta must be finite and > 0");
+    if (!(beta > 0.f) || !(beta <= GCNHIP_BETA_MAX)) CONFORMAL_REFUSE("gcnhip_conformal_scores", GCNHIP_BETA_REFUSAL);
     if (method != 0 && method != 1) return gcnhip_fail("gcnhip_conformal_scores: method is 0 (lac) or 1 (aps)");
     if (!(lam >= 0.f) || !(lam <= 3.402823466e38f)) return gcnhip_fail("gcnhip_conformal_scores: lam must be finite and >= 0");
     if (k_reg < 0) return gcnhip_fail("gcnhip_conformal_scores: k_reg must be >= 0");

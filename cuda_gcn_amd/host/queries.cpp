@@ -386,14 +386,21 @@ void ModelQueries::correct_and_smooth(float alpha_correct, int iters_correct, fl
 
 // ---- temperature scaling and calibration error ---------------------------------------------------------------------------
 
+// the kernels take beta = 1.f / T, which they accept up to GCNHIP_BETA_MAX (gcnhip_driver.h derives it): the same limit here,
+// on the same f32 quotient, so that no temperature that is accepted is refused later by a launch
+static void temperature_check(const char *what, float t) {
+    if (!(t > 0.f) || !std::isfinite(t) || !(1.f / t <= GCNHIP_BETA_MAX))
+        throw GcnHipFailure(-1, std::string(what) + ": the temperature must be finite and > 0, with 1 / T at most 8e37 (T >= 1.25e-38)");
+}
+
 void ModelQueries::calib_check(const char *what, float temperature, int bins) const {
     require(what, SINGLE_LABEL | CLASS_AGGREGATION | AT_MOST_64 | ONE_RANK);
     if (bins < 1 || bins > 64) throw GcnHipFailure(-1, std::string(what) + ": bins must be in 1..64");
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) throw GcnHipFailure(-1, std::string(what) + ": the temperature must be finite and > 0");
+    temperature_check(what, temperature);
 }
 
 void ModelQueries::set_temperature(float t) {
-    if (!(t > 0.f) || !std::isfinite(t)) throw GcnHipFailure(-1, "set_temperature: the temperature must be finite and > 0");
+    temperature_check("set_temperature", t);
     if (t != 1.f) require("set_temperature", SINGLE_LABEL | AT_MOST_64);
     temperature_ = t;
 }

@@ -18,6 +18,7 @@ MODULAR, HOST_MASKS, TIMERS, NO_GRAPH, EVAL_LANE, NO_EVAL_LANE, NO_REPLICATE_L1,
 # (65536 and 262144 are retired flag bits: not to be reused)
 TIMER_NAMES = ["train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw", "graphsum_bw",
                "loss_fw", "relu_fw", "relu_bw", "dropout_fw", "dropout_bw", "adam", "comm", "graphsum_wide"]
+BETA_MAX = np.float32(8e37)           # GCNHIP_BETA_MAX of include/gcnhip_driver.h: the largest beta = 1 / T the kernels accept
 
 
 class GcnHostError(RuntimeError):
@@ -478,8 +479,13 @@ class HipGCNModel:
             raise GcnHostError(f"{what}: at most 64 classes, this model has {self.params.output_dim}")
         if bins is not None and (int(bins) != bins or not 1 <= bins <= 64):
             raise GcnHostError(f"{what}: bins must be an integer in 1..64, got {bins!r}")
-        if temperature is not None and not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
-            raise GcnHostError(f"{what}: the temperature must be finite and > 0, got {temperature!r}")
+        if temperature is not None:
+            # the kernels take the f32 beta = 1 / T and accept it up to BETA_MAX (include/gcnhip_driver.h derives the limit)
+            with np.errstate(all="ignore"):
+                t32 = np.float32(temperature)
+                ok = float(temperature) > 0.0 and np.isfinite(t32) and t32 > 0 and np.float32(1.0) / t32 <= BETA_MAX
+            if not ok:
+                raise GcnHostError(f"{what}: the temperature must be finite and > 0, with 1 / T at most 8e37 (T >= 1.25e-38), got {temperature!r}")
 
     @property
     def temperature(self):

@@ -216,13 +216,19 @@ int gcnhip_cs_correct_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, cons
                            int num_classes, const float *d_sigma, float *g0, int ld_g);
 /* ---- temperature scaling and calibration error (calib.hip; beyond the reference: are the softmax probabilities to be trusted?) ----
  * Row-local passes over log-softmax rows as gcnhip_graphsum_predict writes them: a wave per row, lane j on class j
- * (1 <= num_classes <= 64, rows of any stride >= num_classes).  With l_j = logp[r, j], beta = 1 / T (finite, > 0) and
+ * (1 <= num_classes <= 64, rows of any stride >= num_classes).  With l_j = logp[r, j], beta = 1 / T (0 < beta <= GCNHIP_BETA_MAX, below) and
  * p = softmax(beta . l), formed with the row maximum subtracted; entries with p_j == 0 contribute nothing (a column at -1e4
  * gives no NaN).  The listed rows are d_rows[i], i < n, or 0 .. n - 1 when d_rows == NULL (then n <= n_table); ids outside
  * [0, n_table) and, where truth is an argument, rows whose truth[r] is outside [0, C) are skipped.  Per-row values are f32;
  * sums over rows are doubles formed in a fixed order (rows in row order per wave, block partials in block order by a one-block
  * finalize launch; no float or double atomics), so two launches give the same bits.  No launch allocates or synchronises.
  * Anything else returns -1 with a message (gcnhip_last_error).
+ * The domain of beta, here and in gcnhip_conformal_scores and gcnhip_attach_gather: 0 < beta <= GCNHIP_BETA_MAX = 8e37, anything
+ * else (NaN included) is refused.  The kernels round s_j = beta . l_j BEFORE they take the row maximum; the largest entry of a
+ * log-softmax row of at most 64 classes is at least -ln 64 = -4.16, so its product stays finite as long as beta <=
+ * FLT_MAX / ln 64 = 3.4028e38 / 4.1589 = 8.18e37 — 8e37 leaves 2 % for the rounding of the row itself.  Above that every s_j of a
+ * constant row is -inf, the maximum is -inf and s_j - max is NaN.  Up to the limit every output on a finite log-softmax row is
+ * NaN-free: an entry whose product overflows to -inf has e_j = 0 (scaled row -inf, a true class there: nll = +inf).
  * gcnhip_calib_nll_rows: d_out[4] = {sum nll_r, sum g_r, sum h_r, rows counted}: nll_r = lse(beta . l) - beta . l_t,
  *   g_r = mu - l_t with mu = sum_j p_j l_j (d nll / d beta), h_r = sum_j p_j (l_j - mu)^2 >= 0 (d2 nll / d beta2, the centred sum).
  * gcnhip_calib_bins_rows (1 <= bins <= 64): per counted row conf = max_j p_j, pred = the largest l_j (lowest column on a tie),
@@ -231,6 +237,7 @@ int gcnhip_cs_correct_rows(gcnhip_ctx *ctx, const float *logp, int ld_logp, cons
  * gcnhip_calib_scale_rows: out_logp[r, :] = beta . l - lse(beta . l) for every listed row inside the table (no truth), and
  *   d_prob[r] = expf(max_j out_logp[r, j]) when d_prob != NULL.  out_logp may be logp (a wave holds its row before it stores);
  *   the listed rows must then be distinct. */
+#define GCNHIP_BETA_MAX 8e37f
 int gcnhip_calib_nll_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
                           int num_classes, float beta, double *d_out);
 int gcnhip_calib_bins_rows(gcnhip_ctx *ctx, const float *logp, int ld, const int32_t *truth, int n_table, const int32_t *d_rows, int n,
@@ -454,7 +461,7 @@ int gcnhip_explain_abs_colsum(gcnhip_ctx *ctx, const float *feat, int ld_f, cons
  * epilogue 0: none.  1: ReLU (v > 0 ? v : 0).  2: predict (dim <= 64 only, otherwise -1 and a message) — d_pred[i] = the column
  * of the largest sum, the LOWEST on a tie; d_prob[i] = its softmax probability; d_logp (may be NULL) [i * ld_logp + c] = the
  * log-softmax row of beta . z, all three by the statements of gcnhip_graphsum_predict, followed at beta != 1 by those of
- * gcnhip_calib_scale_rows on that row (a model temperature T is beta = 1 / T, finite and > 0; the sum of the rescaled row runs
+ * gcnhip_calib_scale_rows on that row (a model temperature T is beta = 1 / T, 0 < beta <= GCNHIP_BETA_MAX; the sum of the rescaled row runs
  * left to right here and in a shuffle tree there, so the two agree within the rounding of one sum, not bit for bit); out may
  * then be NULL, else it receives the logits z themselves.
  * The order of a row's sum depends on that row's own edge list and on dim alone (attach.hip has it): not on m, the row's

@@ -200,7 +200,8 @@ int gcnhost_model_correct_and_smooth(gcnhost_model *m, float alpha_correct, int 
  * with one scalar T, 1 by default; these fit it, measure what it does, and set it.  All work on the log-softmax rows of one
  * evaluation forward kept on the device, with the row-local kernels gcnhip_calib_nll_rows / _bins_rows / _scale_rows, and hold
  * gcnhost_model_predict's contract: the call synchronises first and the training state is untouched.  Single-label models, at most
- * 64 classes, one rank; 1 <= bins <= 64; a temperature is finite and > 0: anything else is refused with a message before any launch.
+ * 64 classes, one rank; 1 <= bins <= 64; a temperature is finite and > 0 with the f32 quotient 1 / T at most GCNHIP_BETA_MAX = 8e37
+ * (T >= 1.25e-38; gcnhip_driver.h derives the limit): anything else is refused with a message before any launch.
  *
  * gcnhost_model_calibration: the rows of `split` (1 train, 2 validation, 3 test), or with split == 0 the `nodes` query (n dataset
  * ids; NULL: every row) scored against the dataset's labels, at `temperature`.  sums[4] = {sum of the rows' negative

@@ -99,6 +99,28 @@ def hard_kinds(C, seed=0):
     return _hard(C, seed)[2]
 
 
+BETAS = (calib_ref.BETA_LO, 0.25, 1.0, 4.0, calib_ref.BETA_HI)      # the ends of calibrate()'s bracket and the betas of the dispatch files
+CS = (1, 2, 5, 41, 63, 64)       # one lane, the smallest tie, the smallest C with every kind, the model's 41, the last lane empty, a full wave
+SPREAD_STEP = 1e-3
+
+
+def hard_logp(C, seed=0):
+    """(logp f32 [R, C], truth int32 [R], kinds): the log-softmax rows a trained model hands to the kernels behind predict() —
+    reference(hard_rows(C))["logp"] rounded to f32, row for row with that table's truth and kinds — and two rows of one further
+    kind, 'spread': logits SPREAD_STEP apart (the classes in order and shuffled, the label on the largest and on the smallest),
+    which beta = 0.01 makes uniform to 1e-5 . C and beta = 100 separates by 0.1 per class.  Every entry is finite (the lowest is
+    -1.9e30) and the table is the same on every call."""
+    z, t, kinds = _hard(C, seed)
+    rng = np.random.default_rng([seed, C, 1])
+    steps = np.arange(C, dtype=np.float64) * SPREAD_STEP
+    shuffled = steps[rng.permutation(C)]
+    z = np.concatenate([z, np.stack([steps, shuffled]).astype(np.float32)])
+    t = np.concatenate([t, np.array([C - 1, int(np.argmin(shuffled))], np.int32)])
+    logp = reference(z, t)["logp"].astype(np.float32)
+    assert np.all(np.isfinite(logp))
+    return logp, t, list(kinds) + ["spread", "spread"]
+
+
 def tame_rows(z):
     """rows whose logits stay below 200 in magnitude: their loss terms are O(100), so a sum over them is not drowned by the
     1e30 of a wide row"""
