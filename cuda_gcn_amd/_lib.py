@@ -133,6 +133,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
     "gcnhip_kmeans_seed": (I, [P, P, I, I, I, P, P, I, I, U64, P, I, P, P, C.c_size_t]),
     "gcnhip_contingency_rows": (I, [P, P, P, I, P, I, I, I, P, P]),
+    "gcnhip_nbr_agreement": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P]),
+    "gcnhip_nbr_agreement_ex": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P, I, I64]),
+    "gcnhip_strata_counts": (I, [P, P, P, P, P, P, I, P, I, I, I, P, P]),
     "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
@@ -266,6 +269,11 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
+    "gcnhost_model_neighbor_agreement": (I, [P, P, I64, I, I, P, I, I64, P, P, P, P, P, P, P]),
+    "gcnhost_model_structure": (I, [P, I, P, I, I, I, I64, P, P, P, P, P, P, P, P, P, P, P]),
+    "gcnhost_structure_metrics": (I, [I, P, P, P, I, P, P, P, P, P, P]),
+    "gcnhost_structure_write": (I, [C.c_char_p, I, I, P, P, P, P, P, P, P]),
+    "gcnhost_structure_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P, P, P, P, P, P, P]),
     "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),
     "gcnhost_model_feature_importance": (I, [P, I, P, I, C.c_size_t, P, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),

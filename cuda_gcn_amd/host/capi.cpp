@@ -17,6 +17,7 @@
 #include "report.h"
 #include "calibration.h"
 #include "kmeans.h"
+#include "structure.h"
 #include "conformal.h"
 #include "ranking.h"
 #include "thresholds.h"
@@ -354,6 +355,93 @@ int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double
         const double v[9] = {r.purity, r.homogeneity, r.completeness, r.v_measure, r.nmi, r.ari, r.entropy_classes, r.entropy_clusters, (double)r.rows};
         std::copy(v, v + 9, summary);
     }
+    return 0;
+}
+int gcnhost_model_neighbor_agreement(gcnhost_model *m, const int32_t *labels, int64_t n_labels, int num_classes, int split, const int *nodes, int n,
+                                     int64_t capacity, int32_t *deg, int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals,
+                                     int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_neighbor_agreement: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.structure_rows("neighbor_agreement", num_classes, 1, false, split, nodes, n);
+        if ((deg || same || known) && listed > capacity)
+            throw GcnHipFailure(-1, "neighbor_agreement: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Structure r = q.neighbor_agreement(labels, n_labels, num_classes, split, nodes, n, deg, same, known, mix, class_rows, totals);
+        if (info) { info[0] = r.rows; info[1] = r.skipped; }
+    })
+}
+int gcnhost_model_structure(gcnhost_model *m, int split, const int *nodes, int n, int bins, int predicted, int64_t capacity, int32_t *deg, int32_t *same,
+                            int32_t *known, int64_t *mix_truth, int64_t *class_rows_truth, int64_t *totals_truth, int64_t *mix_pred,
+                            int64_t *class_rows_pred, int64_t *totals_pred, int64_t *strata, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_structure: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.structure_rows("structure", m->gcn->params.output_dim, bins, predicted != 0, split, nodes, n);
+        if ((deg || same || known) && listed > capacity)
+            throw GcnHipFailure(-1, "structure: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Structure r = q.structure(split, nodes, n, bins, predicted != 0, deg, same, known, mix_truth, class_rows_truth, totals_truth,
+                                                      mix_pred, class_rows_pred, totals_pred, strata);
+        if (info) { info[0] = r.rows; info[1] = r.skipped; info[2] = r.unlabelled; }
+    })
+}
+int gcnhost_structure_metrics(int num_classes, const int64_t *mix, const int64_t *class_rows, const int64_t *totals, int bins, const int64_t *strata,
+                              double *summary, double *class_homophily, double *compatibility, double *by_degree, double *by_agreement) {
+    StructureMetrics r;
+    StrataTables t;
+    if (gcn_structure_metrics(num_classes, mix, class_rows, totals, &r, &g_err) != 0) return -1;
+    if (strata && gcn_strata_tables(bins, strata, &t, &g_err) != 0) return -1;
+    if (summary) {
+        const double v[8] = {r.edge_homophily, r.node_homophily, r.adjusted_homophily, r.class_insensitive_homophily,
+                             (double)r.edges, (double)r.rows_with_known, (double)r.labelled_rows, (double)t.rows};
+        std::copy(v, v + 8, summary);
+    }
+    if (class_homophily) std::copy(r.class_homophily.begin(), r.class_homophily.end(), class_homophily);
+    if (compatibility) std::copy(r.compatibility.begin(), r.compatibility.end(), compatibility);
+    auto rows_out = [](const std::vector<StrataRow> &rows, double *out) {
+        for (size_t b = 0; out && b < rows.size(); b++) {
+            const double v[5] = {rows[b].lo, rows[b].hi, (double)rows[b].rows, (double)rows[b].correct, rows[b].accuracy};
+            std::copy(v, v + 5, out + 5 * b);
+        }
+    };
+    if (strata) { rows_out(t.by_degree, by_degree); rows_out(t.by_agreement, by_agreement); }
+    return 0;
+}
+int gcnhost_structure_write(const char *path, int num_classes, int bins, const int64_t *totals_truth, const int64_t *totals_pred,
+                            const int64_t *class_rows_truth, const int64_t *class_rows_pred, const int64_t *mix_truth, const int64_t *mix_pred,
+                            const int64_t *strata) {
+    if (!path || !totals_truth || !totals_pred || !class_rows_truth || !class_rows_pred || !mix_truth || !mix_pred || !strata || num_classes < 1 ||
+        num_classes > STRUCTURE_MAX_CLASSES || bins < 1 || bins > STRUCTURE_MAX_BINS) {
+        g_err = "structure_write: invalid argument (1..64 classes, 1..32 bins, every table)";
+        return -1;
+    }
+    StructureCounts c;
+    const size_t C = (size_t)num_classes, cells = (size_t)STRUCTURE_DEGREE_BUCKETS * (bins + 1) * 2;
+    c.num_classes = num_classes; c.bins = bins;
+    std::copy(totals_truth, totals_truth + 8, c.totals_truth);
+    std::copy(totals_pred, totals_pred + 8, c.totals_pred);
+    c.class_rows_truth.assign(class_rows_truth, class_rows_truth + C);
+    c.class_rows_pred.assign(class_rows_pred, class_rows_pred + C);
+    c.mix_truth.assign(mix_truth, mix_truth + C * C);
+    c.mix_pred.assign(mix_pred, mix_pred + C * C);
+    c.strata.assign(strata, strata + cells);
+    return gcn_structure_write(path, c, &g_err);
+}
+int gcnhost_structure_read(const char *path, int *num_classes, int *bins, int64_t *totals_truth, int64_t *totals_pred, int64_t *class_rows_truth,
+                           int64_t *class_rows_pred, int64_t *mix_truth, int64_t *mix_pred, int64_t *strata) {
+    if (!path || !num_classes || !bins || !totals_truth || !totals_pred || !class_rows_truth || !class_rows_pred || !mix_truth || !mix_pred || !strata) {
+        g_err = "structure_read: invalid argument";
+        return -1;
+    }
+    StructureCounts c;
+    if (gcn_structure_read(path, &c, &g_err) != 0) return -1;
+    *num_classes = c.num_classes; *bins = c.bins;
+    std::copy(c.totals_truth, c.totals_truth + 8, totals_truth);
+    std::copy(c.totals_pred, c.totals_pred + 8, totals_pred);
+    std::copy(c.class_rows_truth.begin(), c.class_rows_truth.end(), class_rows_truth);
+    std::copy(c.class_rows_pred.begin(), c.class_rows_pred.end(), class_rows_pred);
+    std::copy(c.mix_truth.begin(), c.mix_truth.end(), mix_truth);
+    std::copy(c.mix_pred.begin(), c.mix_pred.end(), mix_pred);
+    std::copy(c.strata.begin(), c.strata.end(), strata);
     return 0;
 }
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,

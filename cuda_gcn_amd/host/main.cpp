@@ -111,6 +111,14 @@
 //                            `clusters=<k> cluster_iters=<n> cluster_inertia=<x> cluster_nmi=<a> cluster_ari=<b> cluster_purity=<c>`,
 //                            the last three of the TEST split's nodes against their labels (host/kmeans.h).  The file gets one
 //                            line per node in id order: `node cluster dist2` (%.9g).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
+// Label structure (beyond the reference; ModelQueries::structure, kernels in csrc/structure.hip, measures in host/structure.h),
+// after the test line and the steps above.  One GPU, a single-label model with at most 64 classes:
+//   GCN_STRUCTURE=<file>     homophily of the graph and of the model's predictions over the nodes of the TEST split, and the
+//                            accuracy by degree and by neighbourhood agreement in GCN_STRUCTURE_BINS agreement buckets (default
+//                            10, 1..32).  One line is printed: `edge_homophily=<a> node_homophily=<b> adjusted_homophily=<c>
+//                            class_insensitive_homophily=<d> pred_edge_homophily=<e>` (the first four of the labels, the last of
+//                            the predicted classes).  The file gets the two strata tables, both mixing matrices and the integers
+//                            they come from (host/structure.h).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
 // Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
 // and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
 //   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
@@ -149,6 +157,7 @@
 #include "labels.h"
 #include "parser.h"
 #include "ranking.h"
+#include "structure.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -370,6 +379,21 @@ int main(int argc, char **argv) {
                                                                                    : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_CLUSTER " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *structure_path = getenv("GCN_STRUCTURE");
+    if (structure_path && !*structure_path) structure_path = nullptr;
+    const int structure_bins = env_int("GCN_STRUCTURE_BINS", 10);
+    if (structure_path) {
+        const char *why = multilabel_path                                        ? "compares one predicted class per node (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                           ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.output_dim > STRUCTURE_MAX_CLASSES            ? "takes at most 64 classes"
+                          : structure_bins < 1 || structure_bins > STRUCTURE_MAX_BINS ? "needs GCN_STRUCTURE_BINS in 1..32"
+                                                                                 : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_STRUCTURE " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -699,6 +723,27 @@ int main(int argc, char **argv) {
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the clusters to ") + cluster_path);
                 fprintf(stderr, "gcn-hip: %d clusters of %d nodes (%d iterations%s, seed %llu) written to %s\n", K, N, r.iters_run,
                         r.converged ? ", converged" : "", (unsigned long long)r.seed, cluster_path);
+            }
+            if (structure_path) {                              // one rank (checked above): the test split
+                const int C = params.output_dim;
+                StructureCounts sc;
+                sc.num_classes = C; sc.bins = structure_bins;
+                sc.class_rows_truth.assign((size_t)C, 0); sc.class_rows_pred.assign((size_t)C, 0);
+                sc.mix_truth.assign((size_t)C * C, 0); sc.mix_pred.assign((size_t)C * C, 0);
+                sc.strata.assign((size_t)STRUCTURE_DEGREE_BUCKETS * (structure_bins + 1) * 2, 0);
+                const ModelQueries::Structure r =
+                    gcn.queries().structure(3, nullptr, 0, structure_bins, true, nullptr, nullptr, nullptr, sc.mix_truth.data(), sc.class_rows_truth.data(),
+                                            sc.totals_truth, sc.mix_pred.data(), sc.class_rows_pred.data(), sc.totals_pred, sc.strata.data());
+                StructureMetrics mt, mp;
+                std::string err;
+                if (gcn_structure_metrics(C, sc.mix_truth.data(), sc.class_rows_truth.data(), sc.totals_truth, &mt, &err) != 0 ||
+                    gcn_structure_metrics(C, sc.mix_pred.data(), sc.class_rows_pred.data(), sc.totals_pred, &mp, &err) != 0 ||
+                    gcn_structure_write(structure_path, sc, &err) != 0)
+                    throw GcnHipFailure(-1, "gcn-hip: " + err);
+                printf("edge_homophily=%.6f node_homophily=%.6f adjusted_homophily=%.6f class_insensitive_homophily=%.6f pred_edge_homophily=%.6f\n",
+                       mt.edge_homophily, mt.node_homophily, mt.adjusted_homophily, mt.class_insensitive_homophily, mp.edge_homophily);
+                fprintf(stderr, "gcn-hip: the label structure of %lld test nodes (%d agreement buckets) written to %s\n", (long long)r.rows, structure_bins,
+                        structure_path);
             }
             if (explain_path) {                                // one rank (checked above)
                 const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -321,9 +321,41 @@ public:
                   const uint64_t *seed, size_t scratch_bytes, int32_t *assign, float *dist2, float *centers, int32_t *sizes, int32_t *seed_pos,
                   double *history, int64_t *contingency);
 
+    // Label structure of the graph (csrc/structure.hip has the definitions; host/structure_query.cpp the bodies; host/structure.h
+    // turns the integers into homophily measures and strata tables): WHERE on the graph a labelling agrees with itself, and where
+    // the model is right.  Arrays are in DATASET node order.  Rows: the nodes of `split` (1..3) in ascending dataset id, or with
+    // split == 0 the `nodes` query (dataset ids in the order given, repeats counted as often as listed; NULL: every node in id
+    // order); the mapping to local rows and back goes through query_rows and node_id().  The adjacency walked is the model's own
+    // object with its stored rows (self loop included, as the loader made them).
+    //   neighbor_agreement: `labels` is ANY int32 array [n_labels = num_nodes] — the dataset's labels, predict()'s output,
+    //   cluster()'s assign — with x known when 0 <= x < num_classes <= 64.  It needs neither weights nor a forward and takes
+    //   single- and multi-label models alike: sync(), the labels to local row order on the host and up, one gcnhip_nbr_agreement
+    //   launch.  deg / same / known [rows] by list position (each may be NULL), mix [C x C] (may be NULL), class_rows [C],
+    //   totals [8].
+    //   structure: sync(); the agreement launch on the dataset's labels; with `predicted` one evaluation forward with the
+    //   prediction epilogue over every row (forward_predict(NULL, false)), the agreement launch on the predictions, and one
+    //   gcnhip_strata_counts launch with agreement measured on the TRUTH: strata [32 x (bins + 1) x 2].  Without `predicted` the
+    //   three *_pred outputs and strata are left as they are.  deg / same / known: the truth's, by list position.
+    // Only mix (twice), class_rows, totals and strata cross to the host, and with per-position outputs asked for three int32 per
+    // list position.  predict()'s contract: the metrics ring, the current split, variable 6 and the captured epoch graph are
+    // untouched; a train_epoch() after it has the same bits as one without it.  Scratch lives in the arena; nothing is allocated
+    // until first use.  Refused with a message before any launch: more than one rank (column labels would need an exchange), more
+    // than 64 classes, bins outside 1..32, a split outside 0..3, a node id outside the graph, a label array of another length
+    // than num_nodes, and for structure with `predicted` a multi-label model.
+    struct Structure {
+        int64_t rows = 0, skipped = 0, unlabelled = 0;         // listed; outside the adjacency (none from a checked query); strata's
+    };
+    // the refusals alone, and the number of rows the query lists (a caller sizes its arrays by it); touches no device state
+    int64_t structure_rows(const char *what, int num_classes, int bins, bool predicted, int split, const int *nodes, int n);
+    Structure neighbor_agreement(const int32_t *labels, int64_t n_labels, int num_classes, int split, const int *nodes, int n, int32_t *deg,
+                                 int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals);
+    Structure structure(int split, const int *nodes, int n, int bins, bool predicted, int32_t *deg, int32_t *same, int32_t *known, int64_t *mix_truth,
+                        int64_t *class_rows_truth, int64_t *totals_truth, int64_t *mix_pred, int64_t *class_rows_pred, int64_t *totals_pred,
+                        int64_t *strata);
+
 private:
     HipGCN &m;
-    DeviceArena arena;                                         // every device buffer of a query
+    DeviceArena arena;                                       // every device buffer of a query
     // Device scratch that grows and never shrinks: need(n) returns room for n elements (for one when n == 0: a rank without
     // rows), allocated on first use and again, contents not kept, when n exceeds the capacity.  An allocation that throws leaves
     // capacity 0 and NULL behind.  Zeroed: a new block is cleared (tables whose padding no launch writes but a download may read).
@@ -422,6 +454,14 @@ private:
     Scratch<double> d_km_inertia{&arena};
     Scratch<unsigned char> d_km_scratch{&arena};
     std::vector<int> kmeans_list(const char *what, int split, const int *nodes, int &n);
+    // neighbor_agreement / structure: the listed rows, the labels by local row (the last launch's), the per-position counts
+    // {deg | same | known} of the truth and of the second labelling, {mix [C x C] | class_rows [C] | totals [8] | skipped} and
+    // {strata | unlabelled} as int64
+    Scratch<int32_t> d_st_rows{&arena}, d_st_lab{&arena}, d_st_per{&arena}, d_st_per2{&arena};
+    Scratch<int64_t> d_st_counts{&arena}, d_st_strata{&arena};
+    struct AgreementOut { int32_t *deg, *same, *known; int64_t *mix, *class_rows, *totals; };
+    // one launch on `d_lab` (local rows) over the uploaded list and the copies to the host; returns the skipped positions
+    int64_t agreement_launch(const int32_t *d_lab, int C, const int32_t *d_rows, int n, int32_t *d_per, const AgreementOut &out);
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

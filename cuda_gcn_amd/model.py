@@ -866,6 +866,94 @@ class HipGCNModel:
             out.update(cluster_report(cont))
         return out
 
+    # ---- label structure of the graph: homophily, class mixing, accuracy by degree and by neighbourhood agreement, on the GPU
+    def _structure_query(self, what, split, nodes):
+        """argument checks that need no GPU; returns (split code, node ids int32 or None, n, capacity)"""
+        if split is not None and nodes is not None:
+            raise GcnHostError(f"{what}: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"{what}: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if nodes is None:
+            return int(split or 0), None, 0, self.params.num_nodes
+        q = np.ascontiguousarray(nodes, np.int32).ravel()
+        return 0, (q if q.size else np.zeros(1, np.int32)), int(q.size), int(q.size)
+
+    def neighbor_agreement(self, labels, num_classes=None, split=None, nodes=None, per_node=False):
+        """How far a labelling agrees with itself over the model's graph, counted on the GPU in one walk over the adjacency's index
+        stream (csrc/structure.hip has the definitions).  labels: ANY int array [num_nodes] in dataset node order — the dataset's
+        labels, predict()'s output, cluster()["assign"] — with x known when 0 <= x < num_classes (None: the model's classes; at
+        most 64).  Rows: the nodes of `split` in ascending id, or the `nodes` query (dataset ids, repeats counted as often as
+        listed), or with both None every node.  Per listed node: deg = its stored neighbours without the self loop, known = those
+        with a known label, same = those of them with the node's own label.  Returns structure_metrics() of the counts
+        (edge_homophily, node_homophily, adjusted_homophily, class_insensitive_homophily, class_homophily [C], compatibility
+        [C, C], ...) plus mix int64 [C, C], class_rows int64 [C], totals int64 [8], rows, and with per_node=True deg / same / known
+        int32 [rows] by list position.  Needs neither weights nor a forward; single- and multi-label models alike; one rank.
+        Training state is not touched."""
+        what = "neighbor_agreement"
+        c = self.params.output_dim if num_classes is None else num_classes
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c <= 64:
+            raise GcnHostError(f"{what}: num_classes must be an integer in 1..64, got {c!r}")
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.ndim != 1 or lab.size != self.params.num_nodes:
+            raise GcnHostError(f"{what}: labels must be an int array of shape ({self.params.num_nodes},), got {lab.dtype} {lab.shape}")
+        lab = np.ascontiguousarray(np.clip(lab.astype(np.int64), -1, 2**31 - 1), np.int32)
+        code, q, n, cap = self._structure_query(what, split, nodes)
+        c = int(c)
+        per = [np.zeros(max(cap, 1), np.int32) for _ in range(3)] if per_node else [None] * 3
+        mix, rows_c, totals, info = np.zeros((c, c), np.int64), np.zeros(c, np.int64), np.zeros(8, np.int64), np.zeros(2, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_neighbor_agreement(
+            self.h, lab.ctypes.data, lab.size, c, code, q.ctypes.data if q is not None else None, n, cap,
+            *[a.ctypes.data if a is not None else None for a in per], mix.ctypes.data, rows_c.ctypes.data, totals.ctypes.data, info.ctypes.data), what)
+        out = structure_metrics(mix, rows_c, totals)
+        out.update(mix=mix, class_rows=rows_c, totals=totals, rows=int(info[0]))
+        if per_node:
+            out.update(deg=per[0][:out["rows"]].copy(), same=per[1][:out["rows"]].copy(), known=per[2][:out["rows"]].copy())
+        return out
+
+    def structure_report(self, split=None, nodes=None, bins=10, predicted=True, per_node=False):
+        """Where on the graph the model is right: the label structure of the graph it was given, of its own predictions, and its
+        accuracy by degree and by neighbourhood agreement — the two stratifications of a GCN's errors.  Rows as
+        neighbor_agreement() takes them.  One agreement launch on the dataset's labels; with predicted=True (single-label models)
+        one evaluation forward, one agreement launch on the predicted classes and one strata launch with agreement measured on
+        the TRUTH.  Returns a dict: truth and pred (None without predicted), each structure_metrics() of that labelling plus
+        mix, class_rows, totals; strata int64 [32, bins + 1, 2] = (rows, rows predicted right) per degree bucket (0: degree 0,
+        b: 2^(b-1) .. 2^b - 1) and agreement bucket (a < bins: a / bins <= same / known < (a + 1) / bins, the last closed at 1;
+        bins: no labelled neighbour); by_degree / by_agreement: lists of dict(lo, hi, rows, correct, accuracy);
+        pred_vs_truth_edge_homophily = pred's edge homophily minus the truth's (above 0: the predictions are smoother over the
+        edges than the labels are); rows, unlabelled; with per_node=True deg / same / known int32 [rows] of the truth by list
+        position.  Only the count tables cross to the host.  One rank, at most 64 classes.  Training state is not touched."""
+        what = "structure_report"
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= 32:
+            raise GcnHostError(f"{what}: bins must be an integer in 1..32, got {bins!r}")
+        if predicted and self.multilabel:
+            raise GcnHostError(f"{what}: predicted=True takes a single-label model (one predicted class per node)")
+        code, q, n, cap = self._structure_query(what, split, nodes)
+        c, bins = self.params.output_dim, int(bins)
+        if c > 64:
+            raise GcnHostError(f"{what}: at most 64 classes, this model has {c}")
+        per = [np.zeros(max(cap, 1), np.int32) for _ in range(3)] if per_node else [None] * 3
+        tabs = [(np.zeros((c, c), np.int64), np.zeros(c, np.int64), np.zeros(8, np.int64)) for _ in range(2)]
+        strata, info = np.zeros((32, bins + 1, 2), np.int64), np.zeros(3, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_structure(
+            self.h, code, q.ctypes.data if q is not None else None, n, bins, int(bool(predicted)), cap,
+            *[a.ctypes.data if a is not None else None for a in per], *[a.ctypes.data for a in tabs[0]], *[a.ctypes.data for a in tabs[1]],
+            strata.ctypes.data, info.ctypes.data), what)
+
+        def side(t, with_strata):
+            d = structure_metrics(t[0], t[1], t[2], strata if with_strata else None, bins if with_strata else None)
+            d.update(mix=t[0], class_rows=t[1], totals=t[2])
+            return d
+        truth = side(tabs[0], bool(predicted))
+        out = dict(truth=truth, pred=None, strata=None, by_degree=None, by_agreement=None, pred_vs_truth_edge_homophily=None, bins=bins,
+                   rows=int(info[0]), unlabelled=int(info[2]))
+        if predicted:
+            out.update(by_degree=truth.pop("by_degree"), by_agreement=truth.pop("by_agreement"), strata=strata, pred=side(tabs[1], False))
+            truth.pop("strata_rows", None)
+            out["pred_vs_truth_edge_homophily"] = out["pred"]["edge_homophily"] - truth["edge_homophily"]
+        if per_node:
+            out.update(deg=per[0][:out["rows"]].copy(), same=per[1][:out["rows"]].copy(), known=per[2][:out["rows"]].copy())
+        return out
+
     # ---- explaining a logit: neighbour, hidden-unit and feature shares, on the GPU
     def _explain_args(self, what, nodes, classes=None):
         """argument checks that need no GPU; returns (node ids int32 or None, classes int32 or None)"""
@@ -1162,6 +1250,83 @@ def cluster_report(contingency):
     out = {name: float(v) for name, v in zip(names, s)}
     out["rows"] = int(s[8])
     return out
+
+
+def _structure_tables(what, mix, class_rows, totals=None, strata=None, bins=None):
+    m = np.ascontiguousarray(mix, np.int64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or not 1 <= m.shape[0] <= 64:
+        raise GcnHostError(f"{what}: mix must be a [C, C] table with 1 <= C <= 64, got shape {m.shape}")
+    c = m.shape[0]
+    r = np.ascontiguousarray(class_rows, np.int64)
+    if r.shape != (c,):
+        raise GcnHostError(f"{what}: class_rows must have shape ({c},), got {r.shape}")
+    t = None
+    if totals is not None:
+        t = np.ascontiguousarray(totals, np.int64)
+        if t.shape != (8,):
+            raise GcnHostError(f"{what}: totals must have shape (8,), got {t.shape}")
+    st = None
+    if strata is not None:
+        st = np.ascontiguousarray(strata, np.int64)
+        b = st.shape[1] - 1 if st.ndim == 3 else -1
+        bins = b if bins is None else bins
+        if st.ndim != 3 or not 1 <= bins <= 32 or st.shape != (32, bins + 1, 2):
+            raise GcnHostError(f"{what}: strata must have shape (32, bins + 1, 2) with 1 <= bins <= 32, got {st.shape} with bins = {bins!r}")
+    return m, r, t, st, (int(bins) if st is not None else 0)
+
+
+def structure_metrics(mix, class_rows, totals=None, strata=None, bins=None):
+    """The label structure of a graph from integer counts — host only, no GPU; the one place the measures are derived
+    (host/structure.h has the formulas).  mix int [C, C] (entries from a row labelled a to a neighbour labelled b), class_rows int
+    [C], totals int [8] (None: node_homophily is 0), strata int [32, bins + 1, 2] (None: no tables).  Returns a dict of float64:
+    edge_homophily, node_homophily, adjusted_homophily (Platonov et al., 2023), class_insensitive_homophily (Lim et al., 2021),
+    class_homophily [C], compatibility [C, C] (the row-normalised mix; a zero row stays zero), and the integers edges,
+    rows_with_known, labelled_rows; with strata also strata_rows and by_degree / by_agreement: lists of dict(lo, hi, rows, correct,
+    accuracy) (the bucket without a labelled neighbour has lo = hi = -1).  A zero denominator gives 0, never NaN.  A negative
+    count or a mismatched shape raises GcnHostError."""
+    what = "structure_metrics"
+    m, r, t, st, bins = _structure_tables(what, mix, class_rows, totals, strata, bins)
+    c = m.shape[0]
+    lib = _lib.gcnhost()
+    s, ch, comp = np.zeros(8, np.float64), np.zeros(c, np.float64), np.zeros((c, c), np.float64)
+    bd, ba = np.zeros((32, 5), np.float64), np.zeros((bins + 1, 5), np.float64)
+    _ck(lib, lib.gcnhost_structure_metrics(c, m.ctypes.data, r.ctypes.data, t.ctypes.data if t is not None else None, bins,
+                                           st.ctypes.data if st is not None else None, s.ctypes.data, ch.ctypes.data, comp.ctypes.data,
+                                           bd.ctypes.data, ba.ctypes.data), what)
+    out = dict(edge_homophily=float(s[0]), node_homophily=float(s[1]), adjusted_homophily=float(s[2]), class_insensitive_homophily=float(s[3]),
+               class_homophily=ch, compatibility=comp, edges=int(s[4]), rows_with_known=int(s[5]), labelled_rows=int(s[6]))
+    if st is not None:
+        rows = lambda tab: [dict(lo=float(x[0]), hi=float(x[1]), rows=int(x[2]), correct=int(x[3]), accuracy=float(x[4])) for x in tab]
+        out.update(strata_rows=int(s[7]), by_degree=rows(bd), by_agreement=rows(ba))
+    return out
+
+
+def write_structure_report(path, report):
+    """structure_report()'s integers (a report made with predicted=True) as the text file gcn-hip writes for GCN_STRUCTURE"""
+    what = "write_structure_report"
+    if report.get("pred") is None or report.get("strata") is None:
+        raise GcnHostError(f"{what}: a report made with predicted=True")
+    t, p = report["truth"], report["pred"]
+    m, r, tt, st, bins = _structure_tables(what, t["mix"], t["class_rows"], t["totals"], report["strata"], None)
+    m2, r2, tp, _, _ = _structure_tables(what, p["mix"], p["class_rows"], p["totals"])
+    if m2.shape != m.shape:
+        raise GcnHostError(f"{what}: the two mixing tables have shapes {m.shape} and {m2.shape}")
+    lib = _lib.gcnhost()
+    _ck(lib, lib.gcnhost_structure_write(os.fspath(path).encode(), m.shape[0], bins, tt.ctypes.data, tp.ctypes.data, r.ctypes.data, r2.ctypes.data,
+                                         m.ctypes.data, m2.ctypes.data, st.ctypes.data), what)
+
+
+def read_structure_report(path):
+    """the integers of a structure report file: dict(num_classes, bins, truth=dict(mix, class_rows, totals), pred=..., strata)"""
+    lib = _lib.gcnhost()
+    c, b = C.c_int(), C.c_int()
+    tt, tp, rt, rp = np.zeros(8, np.int64), np.zeros(8, np.int64), np.zeros(64, np.int64), np.zeros(64, np.int64)
+    mt, mp, st = np.zeros(64 * 64, np.int64), np.zeros(64 * 64, np.int64), np.zeros(32 * 33 * 2, np.int64)
+    _ck(lib, lib.gcnhost_structure_read(os.fspath(path).encode(), C.byref(c), C.byref(b), tt.ctypes.data, tp.ctypes.data, rt.ctypes.data, rp.ctypes.data,
+                                        mt.ctypes.data, mp.ctypes.data, st.ctypes.data), "read_structure_report")
+    c, b = c.value, b.value
+    return dict(num_classes=c, bins=b, truth=dict(mix=mt[:c * c].reshape(c, c).copy(), class_rows=rt[:c].copy(), totals=tt),
+                pred=dict(mix=mp[:c * c].reshape(c, c).copy(), class_rows=rp[:c].copy(), totals=tp), strata=st[:32 * (b + 1) * 2].reshape(32, b + 1, 2).copy())
 
 
 def calibration_report(count, correct, conf_sum):

@@ -718,6 +718,58 @@ class Device:
             self._embed_fail("gcnhip_contingency_rows", rc)
         return cb.download()[:int(k) * int(num_classes)].reshape(int(k), int(num_classes)), int(kb.download()[0])
 
+    # ---- label structure of a graph (csrc/structure.hip): every output is uploaded as garbage, the calls zero their own
+    def nbr_agreement(self, g, lab, num_classes, rows=None, n=None, want=("deg", "same", "known", "mix"), group=0, flush_every=0):
+        """gcnhip_nbr_agreement(_ex) on a Graph: dict(deg, same, known int32 [n] by list position, mix int64 [C, C], class_rows int64
+        [C], totals int64 [8], skipped) — the outputs not named in `want` are passed as NULL and come back as None.  rows: int32
+        list of rows (None: positions 0 .. n - 1, n default the graph's rows).  group / flush_every: the lane group per row and
+        the flush interval of the LDS histogram (0: the library's choice; anything else goes through gcnhip_nbr_agreement_ex)."""
+        c = int(num_classes)
+        lab = np.ascontiguousarray(lab, np.int32).ravel()
+        assert lab.size == g.n_cols, (lab.size, g.n_cols)
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        n = (g.n_rows if n is None else int(n)) if r is None else int(r.size)
+        rb = None if r is None else self.buf(r if n > 0 else np.zeros(1, np.int32))
+        lb = self.buf(lab if lab.size else np.zeros(1, np.int32))
+        per = {k: (self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)) if k in want else None) for k in ("deg", "same", "known")}
+        cc = max(c, 1) if 1 <= c <= 64 else 1
+        mb = self.buf(np.full(cc * cc, 0x5A5A5A5A5A5A5A5A, np.int64)) if "mix" in want else None
+        cb, tb, sb = self.buf(np.full(cc, -777, np.int64)), self.buf(np.full(8, -777, np.int64)), self.buf(np.full(1, -777, np.int64))
+        args = (self.ctx, g.h, lb.ptr, c, rb.ptr if rb else None, n, per["deg"].ptr if per["deg"] else None, per["same"].ptr if per["same"] else None,
+                per["known"].ptr if per["known"] else None, mb.ptr if mb else None, cb.ptr, tb.ptr, sb.ptr)
+        if group or flush_every:
+            rc = self.lib.gcnhip_nbr_agreement_ex(*args, int(group), int(flush_every))
+        else:
+            rc = self.lib.gcnhip_nbr_agreement(*args)
+        if rc != 0:
+            self._embed_fail("gcnhip_nbr_agreement", rc)
+        out = {k: (b.download()[:n] if b is not None else None) for k, b in per.items()}
+        out.update(mix=mb.download().reshape(c, c) if mb else None, class_rows=cb.download(), totals=tb.download(), skipped=int(sb.download()[0]))
+        return out
+
+    def strata_counts(self, deg, same, known, pred, truth, num_classes, bins, rows=None):
+        """gcnhip_strata_counts: (strata int64 [32, bins + 1, 2], unlabelled) — pred and truth by row, deg / same / known by list
+        position (rows None: position i is row i)"""
+        pred, truth = np.ascontiguousarray(pred, np.int32).ravel(), np.ascontiguousarray(truth, np.int32).ravel()
+        assert pred.size == truth.size
+        d, s, k = (np.ascontiguousarray(a, np.int32).ravel() for a in (deg, same, known))
+        n = int(d.size)
+        assert s.size == n and k.size == n
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        assert r is None or r.size == n
+        one = np.zeros(1, np.int32)
+        db, sb, kb = (self.buf(a if n else one) for a in (d, s, k))
+        pb, tb = self.buf(pred if pred.size else one), self.buf(truth if truth.size else one)
+        rb = None if r is None else self.buf(r if n else one)
+        b = int(bins)
+        cells = 32 * (b + 1) * 2 if 1 <= b <= 32 else 64
+        ob, ub = self.buf(np.full(cells, 0x5A5A5A5A5A5A5A5A, np.int64)), self.buf(np.full(1, -777, np.int64))
+        rc = self.lib.gcnhip_strata_counts(self.ctx, db.ptr, sb.ptr, kb.ptr, pb.ptr, tb.ptr, int(truth.size), rb.ptr if rb else None, n, int(num_classes), b,
+                                           ob.ptr, ub.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_strata_counts", rc)
+        return ob.download().reshape(32, b + 1, 2), int(ub.download()[0])
+
     # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
     def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,
                       store=True):

@@ -413,6 +413,35 @@ int gcnhip_kmeans_seed(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        int n, int k, uint64_t stream_seed, float *centers, int ldm, int32_t *seed_pos, void *scratch, size_t scratch_bytes);
 int gcnhip_contingency_rows(gcnhip_ctx *ctx, const int32_t *assign, const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int k,
                             int num_classes, int32_t *counts, int32_t *skipped);
+/* ---- label structure of the graph (structure.hip; beyond the reference: WHERE on the graph a labelling agrees with itself) ----
+ * g: an adjacency object with its stored rows (self loop included, repeated entries counted as often as stored, one-way entries
+ * allowed).  lab: device int32, one entry per COLUMN of g; label x is known when 0 <= x < num_classes, 1 <= num_classes <= 64.
+ * d_rows: a device int32 list of n rows, repeats counted as often as listed, NULL: position i is row i; a position whose row is
+ * outside [0, n_rows) counts in *skipped and nowhere else.  For position i with row v and its non-loop entries u (u != v):
+ * deg[i] = their number; with lab[v] known, known[i] = those with lab[u] known, same[i] = those of them with lab[u] == lab[v],
+ * mix[lab[v] * C + lab[u]] += 1 for each of them and class_rows[lab[v]] += 1; with lab[v] unknown known[i] = same[i] = 0.
+ * deg / same / known: int32 [n] by list position, each may be NULL; mix: int64 [C x C], may be NULL; class_rows: int64 [C];
+ * totals: int64 [8] = {listed rows in range, labelled rows, rows with known > 0, sum deg, sum known, sum same, self entries seen,
+ * ratio_sum}, ratio_sum = the sum over rows with known > 0 of floor(same . 2^32 / known) in 64-bit integers (node homophily =
+ * ratio_sum / 2^32 / rows with known > 0); skipped: one int64.  All device memory; the call zeroes them itself, allocates
+ * nothing, synchronises nothing, and adds with integer atomics only: the same bits from every launch.
+ * gcnhip_nbr_agreement_ex: the same launch with the lane group per row (0: by the mean stored row length; 4, 16, 64) and the
+ * number of walked entries after which a wave empties its workgroup's LDS histogram (0: 2^26, the largest allowed) given.
+ * gcnhip_strata_counts: pred and truth are indexed by ROW ([n_truth]), deg / same / known by list position.  db = 0 when
+ * deg <= 0, else 1 + floor(log2 deg); ab = bins when known <= 0, else min(bins - 1, floor(same . bins / known)) in 64-bit
+ * integers; strata: int64 [32 x (bins + 1) x 2], strata[(db * (bins + 1) + ab) * 2 + {0, 1}] = the positions whose truth is
+ * known and, of them, those with pred == truth; *unlabelled = the positions whose truth is outside [0, num_classes); a position
+ * whose row is outside [0, n_truth) counts nowhere.  1 <= bins <= 32.
+ * Refused with -1 and a message (gcnhip_last_error) before any launch: a NULL required pointer, n < 0, num_classes outside
+ * 1..64, bins outside 1..32. */
+int gcnhip_nbr_agreement(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *lab, int num_classes, const int32_t *d_rows, int n,
+                         int32_t *deg, int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals, int64_t *skipped);
+int gcnhip_nbr_agreement_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *lab, int num_classes, const int32_t *d_rows, int n,
+                            int32_t *deg, int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals, int64_t *skipped,
+                            int group, int64_t flush_every);
+int gcnhip_strata_counts(gcnhip_ctx *ctx, const int32_t *deg, const int32_t *same, const int32_t *known, const int32_t *pred,
+                         const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int num_classes, int bins, int64_t *strata,
+                         int64_t *unlabelled);
 /* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
  * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
  * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and

@@ -383,6 +383,40 @@ int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, i
                          float *centers, int32_t *sizes, int32_t *seed_pos, double *history, int64_t *contingency, int64_t *info, double *inertia,
                          uint64_t *seed_used);
 int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary);
+/* Label structure of the graph (ModelQueries::neighbor_agreement / structure, host/queries.h; kernels and definitions in
+ * csrc/structure.hip; measures in host/structure.h).  Arrays are in DATASET node order.  Rows: the nodes of `split` (1 train,
+ * 2 validation, 3 test) in ascending id, or with split == 0 the `nodes` query (n dataset ids in the order given, repeats counted
+ * as often as listed; NULL: every node in id order).
+ * gcnhost_model_neighbor_agreement: labels int32 [n_labels = num_nodes], any labelling with x known when 0 <= x < num_classes <= 64;
+ *   no weights, no forward, single- and multi-label models alike.  deg / same / known (each may be NULL; laid out for `capacity`
+ *   rows, at least the rows listed) by list position, mix [C x C] (may be NULL), class_rows [C], totals [8] (int64; the kernel
+ *   file lists them), info [2] = {rows listed, positions outside the adjacency}.
+ * gcnhost_model_structure: the agreement of the dataset's labels (deg / same / known, mix_truth, class_rows_truth, totals_truth)
+ *   and, with predicted != 0, one evaluation forward, the agreement of the predicted classes (mix_pred, class_rows_pred,
+ *   totals_pred) and strata [32 x (bins + 1) x 2] = (rows, rows predicted right) by degree bucket and by the bucket of the
+ *   TRUTH's agreement; info [3] = {rows listed, positions outside the adjacency, listed rows without a label}.  C is the model's.
+ * predict's contract: training state is not touched.  Refused with a message before any launch: several ranks, more than 64
+ * classes, bins outside 1..32, a bad split or node id, a label array of another length, and with predicted a multi-label model.
+ * gcnhost_structure_metrics (host/structure.h; no GPU): from mix [C x C], class_rows [C], totals [8] (may be NULL) — summary [8] =
+ *   {edge_homophily, node_homophily, adjusted_homophily, class_insensitive_homophily, edges, rows with a labelled neighbour,
+ *   labelled rows, strata rows}, class_homophily [C], compatibility [C x C]; from strata (may be NULL, then bins is ignored) —
+ *   by_degree [32 x 5] and by_agreement [(bins + 1) x 5], rows of {lo, hi, rows, correct, accuracy}.  Each output may be NULL.
+ *   A zero denominator gives 0, never NaN; a negative count is an error.
+ * gcnhost_structure_write / _read: the text report gcn-hip writes for GCN_STRUCTURE (the integers, and derived from them the
+ *   metrics and the two tables).  The reader's arrays are laid out for 64 classes and 32 bins. */
+int gcnhost_model_neighbor_agreement(gcnhost_model *m, const int32_t *labels, int64_t n_labels, int num_classes, int split, const int *nodes, int n,
+                                     int64_t capacity, int32_t *deg, int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals,
+                                     int64_t *info);
+int gcnhost_model_structure(gcnhost_model *m, int split, const int *nodes, int n, int bins, int predicted, int64_t capacity, int32_t *deg, int32_t *same,
+                            int32_t *known, int64_t *mix_truth, int64_t *class_rows_truth, int64_t *totals_truth, int64_t *mix_pred,
+                            int64_t *class_rows_pred, int64_t *totals_pred, int64_t *strata, int64_t *info);
+int gcnhost_structure_metrics(int num_classes, const int64_t *mix, const int64_t *class_rows, const int64_t *totals, int bins, const int64_t *strata,
+                              double *summary, double *class_homophily, double *compatibility, double *by_degree, double *by_agreement);
+int gcnhost_structure_write(const char *path, int num_classes, int bins, const int64_t *totals_truth, const int64_t *totals_pred,
+                            const int64_t *class_rows_truth, const int64_t *class_rows_pred, const int64_t *mix_truth, const int64_t *mix_pred,
+                            const int64_t *strata);
+int gcnhost_structure_read(const char *path, int *num_classes, int *bins, int64_t *totals_truth, int64_t *totals_pred, int64_t *class_rows_truth,
+                           int64_t *class_rows_pred, int64_t *mix_truth, int64_t *mix_pred, int64_t *strata);
 /* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
  * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
  * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
