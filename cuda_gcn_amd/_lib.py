@@ -133,6 +133,10 @@ GCNHIP_SYMBOLS = {
     "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
     "gcnhip_kmeans_seed": (I, [P, P, I, I, I, P, P, I, I, U64, P, I, P, P, C.c_size_t]),
     "gcnhip_contingency_rows": (I, [P, P, P, I, P, I, I, I, P, P]),
+    "gcnhip_pca_plan": (I, [I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_pca_mean": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
+    "gcnhip_pca_scatter": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
+    "gcnhip_pca_project": (I, [P, P, I, I, I, P, P, I, P, P, I, I, P, P, I]),
     "gcnhip_nbr_agreement": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P]),
     "gcnhip_nbr_agreement_ex": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P, I, I64]),
     "gcnhip_strata_counts": (I, [P, P, P, P, P, P, I, P, I, I, I, P, P]),
@@ -269,6 +273,10 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
+    "gcnhost_sym_eigen": (I, [P, I, P, P]),
+    "gcnhost_pca_from_scatter": (I, [P, P, I64, I, I, I, P, P, P, P, C.POINTER(I)]),
+    "gcnhost_model_pca_fit": (I, [P, I, I, P, I, I, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),
+    "gcnhost_model_pca_project": (I, [P, I, I, P, P, P, I, P, I, P]),
     "gcnhost_model_neighbor_agreement": (I, [P, P, I64, I, I, P, I, I64, P, P, P, P, P, P, P]),
     "gcnhost_model_structure": (I, [P, I, P, I, I, I, I64, P, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_structure_metrics": (I, [I, P, P, P, I, P, P, P, P, P, P]),

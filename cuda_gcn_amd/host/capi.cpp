@@ -17,6 +17,7 @@
 #include "report.h"
 #include "calibration.h"
 #include "kmeans.h"
+#include "pca.h"
 #include "structure.h"
 #include "conformal.h"
 #include "ranking.h"
@@ -356,6 +357,44 @@ int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double
         std::copy(v, v + 9, summary);
     }
     return 0;
+}
+int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }
+int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
+                             double *explained, double *scale, int *rank) {
+    PcaFit f;
+    if (gcn_pca_from_scatter(S, mean, rows, h, k, whiten != 0, &f, &g_err) != 0) return -1;
+    const size_t n = (size_t)h;
+    if (eigenvalues) std::copy(f.eigenvalues.begin(), f.eigenvalues.end(), eigenvalues);
+    if (components)
+        for (size_t j = 0; j < n; j++)
+            for (size_t a = 0; a < n; a++) components[j * n + a] = f.components[a * n + j];
+    if (explained) {
+        std::copy(f.explained_variance.begin(), f.explained_variance.end(), explained);
+        std::copy(f.explained_variance_ratio.begin(), f.explained_variance_ratio.end(), explained + n);
+        std::copy(f.singular_values.begin(), f.singular_values.end(), explained + 2 * n);
+    }
+    if (scale && whiten) std::copy(f.scale.begin(), f.scale.end(), scale);
+    if (rank) *rank = f.rank;
+    return 0;
+}
+int gcnhost_model_pca_fit(gcnhost_model *m, int k, int split, const int *nodes, int n, int normalize, int center, int whiten, size_t scratch_bytes,
+                          int64_t capacity, double *mean, double *scatter, double *eigenvalues, double *components, double *explained, double *scale,
+                          float *coords, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_pca_fit: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.pca_rows(k, split, nodes, n);
+        if (coords && listed > capacity)
+            throw GcnHipFailure(-1, "pca: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Pca r = q.pca_fit(k, split, nodes, n, normalize != 0, center != 0, whiten != 0, scratch_bytes, mean, scatter, eigenvalues,
+                                              components, explained, scale, coords);
+        if (info) { info[0] = r.rows; info[1] = r.rank; info[2] = r.k; }
+    })
+}
+int gcnhost_model_pca_project(gcnhost_model *m, int width, int k, const double *mean, const double *components, const double *scale, int normalize,
+                              const int *nodes, int n, float *out) {
+    if (!m) { g_err = "gcnhost_model_pca_project: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().pca_project(width, k, mean, components, scale, normalize != 0, nodes, n, out); })
 }
 int gcnhost_model_neighbor_agreement(gcnhost_model *m, const int32_t *labels, int64_t n_labels, int num_classes, int split, const int *nodes, int n,
                                      int64_t capacity, int32_t *deg, int32_t *same, int32_t *known, int64_t *mix, int64_t *class_rows, int64_t *totals,

@@ -126,6 +126,14 @@
 //                            ids, the self loop among them) and by input feature column, largest first, ties by ascending id or
 //                            column (%.9g); then one line per class, `class c nodes=<n> | f:mean x10`: the ten columns with the
 //                            largest mean |share| over the test nodes explained for that class.
+// Principal components (beyond the reference; ModelQueries::pca_fit, sums in csrc/pca.hip, the eigenproblem in host/pca.h), after
+// the test line and every step above.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
+//   GCN_PCA=<file>           principal component analysis of the unit rows of the hidden layer of EVERY node (centred): the
+//                            float64 mean and scatter matrix on the GPU, the eigenproblem on the host, the projection onto the
+//                            leading GCN_PCA_K components (default 2, 1..hidden_dim) on the GPU.  One line is printed:
+//                            `pca_components=<k> pca_rows=<n> pca_rank=<r> pca_explained_variance_ratio=<a>,<b>,...` (k values,
+//                            %.6f).  The file gets one line per node in id order: `node y1 ... yk` (%.9g).  Works with
+//                            GCN_LOAD_WEIGHTS and 0 epochs.
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -379,6 +387,22 @@ int main(int argc, char **argv) {
                                                                                    : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_CLUSTER " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *pca_path = getenv("GCN_PCA");
+    if (pca_path && !*pca_path) pca_path = nullptr;
+    const int pca_k = env_int("GCN_PCA_K", 2);
+    if (pca_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1                 ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                  ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)            ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : pca_k < 1 || pca_k > params.hidden_dim   ? "needs GCN_PCA_K in 1..hidden_dim"
+                          : params.num_nodes < 2                     ? "needs at least 2 nodes"
+                                                                     : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_PCA " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -817,6 +841,26 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the new nodes' predictions to ") + new_predict_path);
                 fprintf(stderr, "gcn-hip: predictions of %d new nodes (ids %d..%d) written to %s\n", n_new, N, N + n_new - 1, new_predict_path);
+            }
+            if (pca_path) {                                    // one rank (checked above): every node, rows by node id
+                const int N = params.num_nodes, h = params.hidden_dim, K = pca_k;
+                std::vector<float> y((size_t)N * K);
+                std::vector<double> expl((size_t)3 * h);
+                const ModelQueries::Pca r = gcn.queries().pca_fit(K, 0, nullptr, N, true, true, false, 0, nullptr, nullptr, nullptr, nullptr, expl.data(),
+                                                                  nullptr, y.data());
+                printf("pca_components=%d pca_rows=%lld pca_rank=%d pca_explained_variance_ratio=", K, (long long)r.rows, r.rank);
+                for (int j = 0; j < K; j++) printf("%s%.6f", j ? "," : "", expl[(size_t)h + j]);
+                printf("\n");
+                FILE *f = fopen(pca_path, "w");
+                bool ok = f != nullptr;
+                for (int i = 0; ok && i < N; i++) {
+                    ok = fprintf(f, "%d", i) > 0;
+                    for (int j = 0; ok && j < K; j++) ok = fprintf(f, " %.9g", y[(size_t)i * K + j]) > 0;
+                    ok = ok && fputc('\n', f) != EOF;
+                }
+                if (f && fclose(f) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the principal coordinates to ") + pca_path);
+                fprintf(stderr, "gcn-hip: %d principal coordinates of %d nodes (rank %d of %d) written to %s\n", K, N, r.rank, h, pca_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

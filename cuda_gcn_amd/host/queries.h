@@ -321,6 +321,34 @@ public:
                   const uint64_t *seed, size_t scratch_bytes, int32_t *assign, float *dist2, float *centers, int32_t *sizes, int32_t *seed_pos,
                   double *history, int64_t *contingency);
 
+    // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
+    // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
+    // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
+    // `nodes` query (dataset ids in the order given, repeats counted as often as listed; NULL: every node in id order) — list
+    // order is part of the definition of the sums.
+    //   pca_fit: sync(); embed_forward (variable 3 rewritten, as by every forward; with `normalize` its inverse norms); with
+    //   `center` one gcnhip_pca_mean; one gcnhip_pca_scatter; h + h . h doubles to the host; gcn_pca_from_scatter; with `coords`
+    //   one gcnhip_pca_project of the listed rows onto the leading k components (with `whiten` scaled to unit sample variance, 0
+    //   past the rank) and n . k floats to the host.  Outputs, each may be NULL: mean [h] (zeros without `center`), scatter
+    //   [h x h], eigenvalues [h], components [h x h] (ROW j = component j), explained [3 x h] = {explained_variance |
+    //   explained_variance_ratio | singular_values}, scale [k] (written with `whiten` only), coords [rows x k] by list position.
+    //   pca_project: a fit's arrays — width, k, mean [width] (NULL: none), components [k x width] rows, scale [k] (NULL: none) —
+    //   applied to the `nodes` query at the CURRENT weights: sync(), embed_forward, one gcnhip_pca_project.  Nothing is cached.
+    // predict()'s contract: the metrics ring, the current split, variable 6 and the captured epoch graph are untouched.  Scratch
+    // lives in the arena; nothing is allocated until first use.  Refused with a message before any launch: more than one rank,
+    // bf16 tables, a hidden width above 256, k outside 1..hidden, fewer than 2 listed rows, a split outside 0..3, a node id outside
+    // the graph; for pca_project a fit of another width or one that is not finite.
+    struct Pca {
+        int k = 0, rank = 0;
+        int64_t rows = 0;
+    };
+    // the refusals alone, and the number of rows the query lists (a caller sizes its arrays by it); touches no device state
+    int64_t pca_rows(int k, int split, const int *nodes, int n, std::vector<int> *rows = nullptr);   // rows: the local rows listed
+    Pca pca_fit(int k, int split, const int *nodes, int n, bool normalize, bool center, bool whiten, size_t scratch_bytes, double *mean, double *scatter,
+                double *eigenvalues, double *components, double *explained, double *scale, float *coords);
+    int64_t pca_project(int width, int k, const double *mean, const double *components, const double *scale, bool normalize, const int *nodes, int n,
+                        float *out);
+
     // Label structure of the graph (csrc/structure.hip has the definitions; host/structure_query.cpp the bodies; host/structure.h
     // turns the integers into homophily measures and strata tables): WHERE on the graph a labelling agrees with itself, and where
     // the model is right.  Arrays are in DATASET node order.  Rows: the nodes of `split` (1..3) in ascending dataset id, or with
@@ -454,6 +482,12 @@ private:
     Scratch<double> d_km_inertia{&arena};
     Scratch<unsigned char> d_km_scratch{&arena};
     std::vector<int> kmeans_list(const char *what, int split, const int *nodes, int &n);
+    // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
+    // a projection, its coordinates, the sums' scratch
+    Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};
+    Scratch<double> d_pca_stats{&arena}, d_pca_basis{&arena};
+    Scratch<float> d_pca_out{&arena};
+    Scratch<unsigned char> d_pca_scratch{&arena};
     // neighbor_agreement / structure: the listed rows, the labels by local row (the last launch's), the per-position counts
     // {deg | same | known} of the truth and of the second labelling, {mix [C x C] | class_rows [C] | totals [8] | skipped} and
     // {strata | unlabelled} as int64

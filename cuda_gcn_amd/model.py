@@ -866,6 +866,79 @@ class HipGCNModel:
             out.update(cluster_report(cont))
         return out
 
+    # ---- principal components of the hidden layer: coordinates, spectrum and whitening, on the GPU
+    def _pca_query(self, what, split, nodes):
+        if self.params.hidden_dim > 256:
+            raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+        if split is not None and nodes is not None:
+            raise GcnHostError(f"{what}: give a split or a node query, not both")
+        if split is not None and split not in (1, 2, 3):
+            raise GcnHostError(f"{what}: split is 1 (train), 2 (validation) or 3 (test), got {split!r}")
+        if nodes is None:
+            return None, 0, self.params.num_nodes
+        q = np.ascontiguousarray(nodes, np.int32).ravel()
+        return (q if q.size else np.zeros(1, np.int32)), int(q.size), int(q.size)
+
+    def pca(self, k=2, split=None, nodes=None, normalize=True, center=True, whiten=False, coords=True, return_scatter=False, scratch_bytes=0):
+        """Principal component analysis of the rows embed() exports, run where they lie: one evaluation forward, the float64 mean
+        and the float64 scatter matrix of the listed rows on the GPU (the f64 MFMA, a summation order fixed by the data: the same
+        bits on every run), hidden + hidden^2 doubles to the host, the symmetric eigenproblem there (sym_eigen), and the
+        projection of the rows onto the leading k components on the GPU.  Rows: the nodes of `split` in ascending id, or the
+        `nodes` query (dataset ids in the order given, repeats counted as often as listed), or with both None every node in id
+        order.  normalize=True analyses unit rows (see cluster()); center=False analyses the uncentred Gram matrix; whiten=True
+        scales every coordinate to unit sample variance (0 for a component past the rank).  Returns a dict: mean float64 [h],
+        components float64 [k, h] (unit rows, the entry of largest magnitude positive), eigenvalues float64 [h] (descending,
+        clipped at 0), explained_variance, explained_variance_ratio, singular_values float64 [h], rank, rows, normalize, center,
+        whiten, scale (float64 [k] with whiten, else None), coords f32 [rows, k] by list position (None with coords=False) and
+        with return_scatter=True scatter float64 [h, h].  pca_transform() applies the fit to other nodes.  One rank, hidden width
+        at most 256, f32 tables, at least 2 rows.  Training state is not touched."""
+        what = "pca"
+        q, n, cap = self._pca_query(what, split, nodes)
+        h = self.params.hidden_dim
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= h:
+            raise GcnHostError(f"{what}: k must be an integer in 1..{h}, got {k!r}")
+        k = int(k)
+        mean, ev, comp, expl = np.zeros(h, np.float64), np.zeros(h, np.float64), np.zeros((h, h), np.float64), np.zeros((3, h), np.float64)
+        scat = np.zeros((h, h), np.float64) if return_scatter else None
+        scale = np.zeros(k, np.float64) if whiten else None
+        y = np.zeros(max(cap, 1) * k, np.float32) if coords else None
+        info = np.zeros(3, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_pca_fit(
+            self.h, k, int(split or 0), q.ctypes.data if q is not None else None, n, int(bool(normalize)), int(bool(center)), int(bool(whiten)),
+            int(scratch_bytes), cap, mean.ctypes.data, scat.ctypes.data if return_scatter else None, ev.ctypes.data, comp.ctypes.data,
+            expl.ctypes.data, scale.ctypes.data if whiten else None, y.ctypes.data if coords else None, info.ctypes.data), what)
+        rows = int(info[0])
+        out = dict(mean=mean, components=comp[:k].copy(), eigenvalues=ev, explained_variance=expl[0].copy(), explained_variance_ratio=expl[1].copy(),
+                   singular_values=expl[2].copy(), rank=int(info[1]), rows=rows, normalize=bool(normalize), center=bool(center), whiten=bool(whiten),
+                   scale=scale, coords=y[:rows * k].reshape(rows, k).copy() if coords else None)
+        if return_scatter:
+            out["scatter"] = scat
+        return out
+
+    def pca_transform(self, fit, nodes=None):
+        """f32 [n, k] — the listed nodes (None: every node in id order) projected with a fit pca() returned, at the CURRENT
+        weights: one evaluation forward and one projection launch on the GPU; nothing is cached.  A fit on the training split
+        places every node.  Refused when the fit has another width than the hidden layer or holds a value that is not finite."""
+        what = "pca_transform"
+        q, n, cap = self._pca_query(what, None, nodes)
+        comp = np.ascontiguousarray(fit["components"], np.float64)
+        if comp.ndim != 2:
+            raise GcnHostError(f"{what}: components must be a [k, hidden] array, got shape {comp.shape}")
+        k, width = comp.shape
+        mean = np.ascontiguousarray(fit["mean"], np.float64).ravel() if fit.get("center", True) else None
+        if mean is not None and mean.size != width:
+            raise GcnHostError(f"{what}: the mean has {mean.size} entries, the components {width}")
+        scale = fit.get("scale") if fit.get("whiten", False) else None
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, np.float64).ravel()
+            if scale.size != k:
+                raise GcnHostError(f"{what}: the scale has {scale.size} entries for {k} components")
+        y = np.zeros((max(cap, 1), max(k, 1)), np.float32)
+        _ck(self.lib, self.lib.gcnhost_model_pca_project(
+            self.h, int(width), int(k), mean.ctypes.data if mean is not None else None, comp.ctypes.data, scale.ctypes.data if scale is not None else None,
+            int(bool(fit.get("normalize", True))), q.ctypes.data if q is not None else None, n, y.ctypes.data), what)
+        return y[:cap]
+
     # ---- label structure of the graph: homophily, class mixing, accuracy by degree and by neighbourhood agreement, on the GPU
     def _structure_query(self, what, split, nodes):
         """argument checks that need no GPU; returns (split code, node ids int32 or None, n, capacity)"""
@@ -1250,6 +1323,44 @@ def cluster_report(contingency):
     out = {name: float(v) for name, v in zip(names, s)}
     out["rows"] = int(s[8])
     return out
+
+
+def sym_eigen(S):
+    """(eigenvalues float64 [h] descending, vectors float64 [h, h] with COLUMN j the unit vector of eigenvalue j, its entry of
+    largest magnitude positive) of a symmetric float64 matrix, 1 <= h <= 256 — host only, no GPU: cyclic Jacobi (host/pca.h).  A
+    matrix that is not square, not finite or not symmetric bit for bit raises GcnHostError."""
+    a = np.ascontiguousarray(S, np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise GcnHostError(f"sym_eigen: a square matrix, got shape {a.shape}")
+    h = a.shape[0]
+    lib = _lib.gcnhost()
+    lam, v = np.zeros(max(h, 1), np.float64), np.zeros((max(h, 1), max(h, 1)), np.float64)
+    _ck(lib, lib.gcnhost_sym_eigen((a if a.size else np.zeros(1)).ctypes.data, h, lam.ctypes.data, v.ctypes.data), "sym_eigen")
+    return lam, v
+
+
+def pca_from_scatter(scatter, mean, rows, k=None, whiten=False):
+    """Everything a principal component analysis derives from the scatter matrix [h, h] of `rows` centred rows — host only, no
+    GPU; the one place it is derived (host/pca.h has the formulas).  Returns a dict of float64: eigenvalues [h] (descending,
+    clipped at 0), components [k, h] (k None: h), explained_variance, explained_variance_ratio (0 when the spectrum is 0),
+    singular_values [h], rank, rows, and with whiten=True scale [k] (0 past the rank).  Never NaN or inf."""
+    a = np.ascontiguousarray(scatter, np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise GcnHostError(f"pca_from_scatter: a square matrix, got shape {a.shape}")
+    h = a.shape[0]
+    k = h if k is None else int(k)
+    m = None if mean is None else np.ascontiguousarray(mean, np.float64).ravel()
+    if m is not None and m.size != h:
+        raise GcnHostError(f"pca_from_scatter: the mean has {m.size} entries, the matrix {h} rows")
+    lib = _lib.gcnhost()
+    hh = max(h, 1)
+    ev, comp, expl, scale = np.zeros(hh, np.float64), np.zeros((hh, hh), np.float64), np.zeros((3, hh), np.float64), np.zeros(max(k, 1), np.float64)
+    rank = C.c_int()
+    _ck(lib, lib.gcnhost_pca_from_scatter((a if a.size else np.zeros(1)).ctypes.data, m.ctypes.data if m is not None else None, int(rows), h, k,
+                                          int(bool(whiten)), ev.ctypes.data, comp.ctypes.data, expl.ctypes.data, scale.ctypes.data, C.byref(rank)),
+        "pca_from_scatter")
+    return dict(eigenvalues=ev, components=comp[:k].copy(), explained_variance=expl[0].copy(), explained_variance_ratio=expl[1].copy(),
+                singular_values=expl[2].copy(), rank=rank.value, rows=int(rows), scale=scale if whiten else None)
 
 
 def _structure_tables(what, mix, class_rows, totals=None, strata=None, bins=None):

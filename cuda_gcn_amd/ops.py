@@ -718,6 +718,65 @@ class Device:
             self._embed_fail("gcnhip_contingency_rows", rc)
         return cb.download()[:int(k) * int(num_classes)].reshape(int(k), int(num_classes)), int(kb.download()[0])
 
+    # ---- principal components of the rows of a table (csrc/pca.hip): the table is uploaded with its row stride and NaN padding,
+    # every output as garbage
+    def pca_plan(self, n, dim):
+        """gcnhip_pca_plan: dict(bytes_full, bytes_min) of device scratch for pca_mean / pca_scatter"""
+        a, b = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_pca_plan(int(n), int(dim), C.byref(a), C.byref(b))
+        if rc != 0:
+            self._embed_fail("gcnhip_pca_plan", rc)
+        return dict(bytes_full=a.value, bytes_min=b.value)
+
+    def _pca_scratch(self, n, dim, scratch_bytes):
+        sbytes = self.pca_plan(n, dim)["bytes_full"] if scratch_bytes is None else int(scratch_bytes)
+        return self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32)), sbytes
+
+    def pca_mean(self, table, rows=None, inv_norm=None, ld=None, scratch_bytes=None):
+        """gcnhip_pca_mean: (mean float64 [dim], count) — the float64 mean of the listed rows (None: every row) and the number of
+        list positions that name a row of the table"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        sb, sbytes = self._pca_scratch(n, dim, scratch_bytes)
+        mb, cb = self.buf(np.full(dim, np.nan, np.float64)), self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_pca_mean(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, mb.ptr, cb.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_pca_mean", rc)
+        return mb.download(), int(cb.download()[0])
+
+    def pca_scatter(self, table, mean=None, rows=None, inv_norm=None, ld=None, scratch_bytes=None):
+        """gcnhip_pca_scatter: float64 [dim, dim] = sum over the listed rows of c c^T, c = (double)x - mean (mean None: x)"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        sb, sbytes = self._pca_scratch(n, dim, scratch_bytes)
+        mb = None if mean is None else self.buf(np.ascontiguousarray(mean, np.float64).ravel())
+        ob = self.buf(np.full(dim * dim, np.nan, np.float64))
+        rc = self.lib.gcnhip_pca_scatter(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, mb.ptr if mb else None,
+                                         ob.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_pca_scatter", rc)
+        return ob.download().reshape(dim, dim)
+
+    def pca_project(self, table, components, mean=None, scale=None, rows=None, inv_norm=None, ld=None, ldv=None, ldy=None):
+        """gcnhip_pca_project: f32 [n, k] = (float)(scale[j] . sum_a c[i, a] . components[j, a]); components float64 [k, dim] (ROW j
+        = component j; uploaded as the basis [dim x ldv] with NaN padding); a list position outside the table gives a NaN row"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        comp = np.ascontiguousarray(components, np.float64)
+        k = comp.shape[0]
+        ldv, ldy = int(ldv or k), int(ldy or k)
+        basis = np.full((comp.shape[1], max(ldv, 1)), np.nan, np.float64)
+        basis[:, :min(k, ldv)] = comp.T[:, :min(k, ldv)]
+        vb = self.buf(basis)
+        mb = None if mean is None else self.buf(np.ascontiguousarray(mean, np.float64).ravel())
+        cb = None if scale is None else self.buf(np.ascontiguousarray(scale, np.float64).ravel())
+        ob = self.buf(np.full((max(n, 1), max(ldy, 1)), 12345.0, np.float32))
+        rc = self.lib.gcnhip_pca_project(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, mb.ptr if mb else None,
+                                         vb.ptr, ldv, k, cb.ptr if cb else None, ob.ptr, ldy)
+        if rc != 0:
+            self._embed_fail("gcnhip_pca_project", rc)
+        return ob.download().reshape(max(n, 1), max(ldy, 1))[:n, :k].copy()
+
     # ---- label structure of a graph (csrc/structure.hip): every output is uploaded as garbage, the calls zero their own
     def nbr_agreement(self, g, lab, num_classes, rows=None, n=None, want=("deg", "same", "known", "mix"), group=0, flush_every=0):
         """gcnhip_nbr_agreement(_ex) on a Graph: dict(deg, same, known int32 [n] by list position, mix int64 [C, C], class_rows int64

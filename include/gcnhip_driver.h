@@ -413,6 +413,28 @@ int gcnhip_kmeans_seed(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        int n, int k, uint64_t stream_seed, float *centers, int ldm, int32_t *seed_pos, void *scratch, size_t scratch_bytes);
 int gcnhip_contingency_rows(gcnhip_ctx *ctx, const int32_t *assign, const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int k,
                             int num_classes, int32_t *counts, int32_t *skipped);
+/* ---- principal components of the rows of a table (pca.hip; beyond the reference: the coordinates of what a GCN learns) ----
+ * The table contract and the row lists of the k-means calls: a list position whose row is outside the table is skipped and
+ * leaves a NaN row in a projection.  x_i[a] = T[r][a] . inv_norm[r] rounded to f32 (inv_norm == NULL: T[r][a]).  No launch
+ * allocates or synchronises, none uses a float atomic; every output's bits are a function of the arguments' contents alone.
+ * The list is cut into parts of 1024 positions; a part's partial is accumulated in ascending position, the partials are added
+ * from +0 in ascending part order; a call handles as many parts per launch as its scratch holds.
+ * gcnhip_pca_plan: *bytes_full = max(ceil(n / 1024), 1) . T . 2048 and *bytes_min = T . 2048 bytes of device scratch for either
+ *   call below, T = t (t + 1) / 2, t = ceil(dim / 16); each may be NULL.
+ * gcnhip_pca_mean: mean[a] (device float64 [dim]) = (the float64 sum of (double)x_i[a] over the valid positions) / count;
+ *   *count (device int32) = the valid positions; count == 0 gives NaN.
+ * gcnhip_pca_scatter: scatter (device float64 [dim x dim]), S[a][b] = sum_i c_ia . c_ib with c_ia = (double)x_i[a] - mean[a]
+ *   (mean == NULL: x, the uncentred Gram matrix), products and sums in float64 on the f64 MFMA, four consecutive positions per
+ *   instruction.  Tile pairs on or above the diagonal are computed and mirrored: S is symmetric bit for bit.
+ * gcnhip_pca_project: out[i][j] (f32 [n x ldy]) = (float)(scale[j] . sum_a c_ia . basis[a . ldv + j]) for j < k <= dim, one
+ *   float64 fma chain in ascending a; basis: device float64 [dim x ldv]; scale: device float64 [k] or NULL (no factor). */
+int gcnhip_pca_plan(int n, int dim, size_t *bytes_full, size_t *bytes_min);
+int gcnhip_pca_mean(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows, int n,
+                    double *mean, int32_t *count, void *scratch, size_t scratch_bytes);
+int gcnhip_pca_scatter(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                       int n, const double *mean, double *scatter, void *scratch, size_t scratch_bytes);
+int gcnhip_pca_project(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                       int n, const double *mean, const double *basis, int ldv, int k, const double *scale, float *out, int ldy);
 /* ---- label structure of the graph (structure.hip; beyond the reference: WHERE on the graph a labelling agrees with itself) ----
  * g: an adjacency object with its stored rows (self loop included, repeated entries counted as often as stored, one-way entries
  * allowed).  lab: device int32, one entry per COLUMN of g; label x is known when 0 <= x < num_classes, 1 <= num_classes <= 64.

@@ -383,6 +383,34 @@ int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, i
                          float *centers, int32_t *sizes, int32_t *seed_pos, double *history, int64_t *contingency, int64_t *info, double *inertia,
                          uint64_t *seed_used);
 int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary);
+/* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
+ * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
+ * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
+ *   lambda [h] descending; V [h x h], V[a * h + j] = entry a of the unit vector of lambda[j], its entry of largest magnitude positive
+ *   (the lowest index on equal magnitude).  Cyclic Jacobi.
+ * gcnhost_pca_from_scatter (no GPU): from the scatter matrix of `rows` >= 2 centred rows — eigenvalues [h] = max(lambda, 0)
+ *   descending, components [h x h] with ROW j = component j, explained [3 x h] = {lambda / (rows - 1) | lambda_j / sum(lambda), 0
+ *   when the sum is 0 | sqrt(lambda)}, *rank = the number of lambda_j > h . 2^-52 . lambda_1, and with whiten != 0 scale [k] =
+ *   1 / sqrt(lambda_j / (rows - 1)), 0 past the rank.  Never NaN or inf.  mean (may be NULL) is checked to be finite.  Each
+ *   output may be NULL.
+ * gcnhost_model_pca_fit: one evaluation forward, with center != 0 the float64 mean, the float64 scatter matrix on the device,
+ *   h + h . h doubles to the host, the eigenproblem there, and with coords the projection of the listed rows onto the leading k
+ *   components on the device: coords [rows x k] f32 (laid out for `capacity` rows, at least the rows listed).  mean [h] (zeros without center), scatter [h x h], eigenvalues, components,
+ *   explained, scale as above, each may be NULL; info [3] = {rows, rank, k}.  scratch_bytes: the sums' device scratch (0: one
+ *   launch; less: more launches, the same bits).
+ * gcnhost_model_pca_project: a fit's arrays (width, k, mean [width] or NULL, components [k x width] rows, scale [k] or NULL)
+ *   applied to the `nodes` query (NULL: every node) at the current weights: out [n x k].  Nothing is cached.
+ * embed's contract: training state is not touched.  Refused with a message before any launch: several ranks, bf16 tables, a
+ * hidden width above 256, k outside 1..hidden, fewer than 2 rows listed, a bad split or node id, a fit of another width or one
+ * that is not finite. */
+int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V);
+int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
+                             double *explained, double *scale, int *rank);
+int gcnhost_model_pca_fit(gcnhost_model *m, int k, int split, const int *nodes, int n, int normalize, int center, int whiten, size_t scratch_bytes,
+                          int64_t capacity, double *mean, double *scatter, double *eigenvalues, double *components, double *explained, double *scale,
+                          float *coords, int64_t *info);
+int gcnhost_model_pca_project(gcnhost_model *m, int width, int k, const double *mean, const double *components, const double *scale, int normalize,
+                              const int *nodes, int n, float *out);
 /* Label structure of the graph (ModelQueries::neighbor_agreement / structure, host/queries.h; kernels and definitions in
  * csrc/structure.hip; measures in host/structure.h).  Arrays are in DATASET node order.  Rows: the nodes of `split` (1 train,
  * 2 validation, 3 test) in ascending id, or with split == 0 the `nodes` query (n dataset ids in the order given, repeats counted
