@@ -140,6 +140,11 @@ GCNHIP_SYMBOLS = {
     "gcnhip_nbr_agreement": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P]),
     "gcnhip_nbr_agreement_ex": (I, [P, P, P, I, P, I, P, P, P, P, P, P, P, I, I64]),
     "gcnhip_strata_counts": (I, [P, P, P, P, P, P, I, P, I, I, I, P, P]),
+    "gcnhip_hop_distance": (I, [P, P, P, I, I, P, P, P, C.POINTER(I), P, I, C.POINTER(I64)]),
+    "gcnhip_hop_distance_ex": (I, [P, P, P, I, I, P, P, P, C.POINTER(I), P, I, C.POINTER(I64), I, I]),
+    "gcnhip_components": (I, [P, P, P, P, C.POINTER(I)]),
+    "gcnhip_component_counts": (I, [P, P, P, I, P, P, P]),
+    "gcnhip_distance_strata": (I, [P, P, P, P, P, I, P, I, I, I, P, P]),
     "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
@@ -282,6 +287,12 @@ GCNHOST_SYMBOLS = {
     "gcnhost_structure_metrics": (I, [I, P, P, P, I, P, P, P, P, P, P]),
     "gcnhost_structure_write": (I, [C.c_char_p, I, I, P, P, P, P, P, P, P]),
     "gcnhost_structure_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P, P, P, P, P, P, P]),
+    "gcnhost_model_label_distance": (I, [P, I, P, I, I, P, I, I, I64, P, P, P, I, P]),
+    "gcnhost_model_components": (I, [P, I, P, I, I, P, I, I64, P, P, P, P]),
+    "gcnhost_model_reach": (I, [P, I, P, I, I, P, I, I, I, I64, P, P, P, P, P, P, I, P]),
+    "gcnhost_reach_metrics": (I, [P, I, I, P, P, P]),
+    "gcnhost_reach_write": (I, [C.c_char_p, I, I, P, P, P, I64, P]),
+    "gcnhost_reach_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P, P, P, I64, C.POINTER(I64), P]),
     "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),
     "gcnhost_model_feature_importance": (I, [P, I, P, I, C.c_size_t, P, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),

@@ -19,6 +19,7 @@
 #include "kmeans.h"
 #include "pca.h"
 #include "structure.h"
+#include "reach.h"
 #include "conformal.h"
 #include "ranking.h"
 #include "thresholds.h"
@@ -480,6 +481,90 @@ int gcnhost_structure_read(const char *path, int *num_classes, int *bins, int64_
     std::copy(c.class_rows_pred.begin(), c.class_rows_pred.end(), class_rows_pred);
     std::copy(c.mix_truth.begin(), c.mix_truth.end(), mix_truth);
     std::copy(c.mix_pred.begin(), c.mix_pred.end(), mix_pred);
+    std::copy(c.strata.begin(), c.strata.end(), strata);
+    return 0;
+}
+int gcnhost_model_label_distance(gcnhost_model *m, int source_mask, const int *source_nodes, int n_sources, int split, const int *nodes, int n,
+                                 int max_hops, int64_t capacity, int32_t *dist, int32_t *nearest, int64_t *level_counts, int level_capacity,
+                                 int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_label_distance: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.reach_rows("label_distance", split, nodes, n, source_mask, source_nodes, n_sources, max_hops, 1, false);
+        if ((dist || nearest) && listed > capacity)
+            throw GcnHipFailure(-1, "label_distance: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Reach r = q.label_distance(source_mask, source_nodes, n_sources, split, nodes, n, max_hops, dist, nearest, level_counts, level_capacity);
+        if (info) { info[0] = r.rows; info[1] = r.sources; info[2] = r.skipped; info[3] = r.unreachable; info[4] = r.levels; }
+    })
+}
+int gcnhost_model_components(gcnhost_model *m, int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources,
+                             int64_t capacity, int32_t *component, int32_t *size, int64_t *totals, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_components: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.reach_rows("components", split, nodes, n, source_mask, source_nodes, n_sources, 0, 1, false);
+        if ((component || size) && listed > capacity)
+            throw GcnHipFailure(-1, "components: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Reach r = q.components(split, nodes, n, source_mask, source_nodes, n_sources, component, size, totals);
+        if (info) { info[0] = r.rows; info[1] = r.rounds; }
+    })
+}
+int gcnhost_model_reach(gcnhost_model *m, int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int hops,
+                        int predicted, int64_t capacity, int32_t *dist, int32_t *nearest, int32_t *component, int64_t *strata, int64_t *totals,
+                        int64_t *level_counts, int level_capacity, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_reach: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.reach_rows("reach", split, nodes, n, source_mask, source_nodes, n_sources, 0, hops, predicted != 0);
+        if ((dist || nearest || component) && listed > capacity)
+            throw GcnHipFailure(-1, "reach: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Reach r = q.reach(split, nodes, n, source_mask, source_nodes, n_sources, hops, predicted != 0, dist, nearest, component, strata,
+                                              totals, level_counts, level_capacity);
+        if (info) {
+            info[0] = r.rows; info[1] = r.sources; info[2] = r.skipped; info[3] = r.unlabelled; info[4] = r.unreachable; info[5] = r.levels;
+            info[6] = r.rounds;
+        }
+    })
+}
+int gcnhost_reach_metrics(const int64_t *strata, int hops, int layers, double *by_distance, double *groups, double *summary) {
+    ReachMetrics r;
+    if (gcn_reach_metrics(strata, hops, layers, &r, &g_err) != 0) return -1;
+    auto row_out = [](const ReachRow &x, double *out) {
+        const double v[6] = {(double)x.rows, (double)x.labelled, (double)x.correct, (double)x.nearest_correct, x.accuracy, x.nearest_accuracy};
+        std::copy(v, v + 6, out);
+    };
+    for (size_t b = 0; by_distance && b < r.by_distance.size(); b++) row_out(r.by_distance[b], by_distance + 6 * b);
+    if (groups) { row_out(r.inside, groups); row_out(r.outside, groups + 6); row_out(r.all, groups + 12); }
+    if (summary) { summary[0] = (double)r.unreachable; summary[1] = r.unreachable_share; }
+    return 0;
+}
+int gcnhost_reach_write(const char *path, int hops, int layers, const int64_t *info, const int64_t *totals, const int64_t *level_counts, int64_t n_levels,
+                        const int64_t *strata) {
+    if (!path || !info || !totals || !level_counts || !strata || hops < 1 || hops > REACH_MAX_HOPS || n_levels < 1 || n_levels > ((int64_t)1 << 31)) {
+        g_err = "reach_write: invalid argument (1..32 hops, every table, at least the count of level 0)";
+        return -1;
+    }
+    ReachCounts c;
+    c.hops = hops; c.layers = layers;
+    c.sources = info[0]; c.unlabelled = info[1]; c.rounds = info[2];
+    std::copy(totals, totals + 6, c.totals);
+    c.level_counts.assign(level_counts, level_counts + n_levels);
+    c.strata.assign(strata, strata + (size_t)(hops + 2) * 4);
+    return gcn_reach_write(path, c, &g_err);
+}
+int gcnhost_reach_read(const char *path, int *hops, int *layers, int64_t *info, int64_t *totals, int64_t *level_counts, int64_t level_capacity,
+                       int64_t *n_levels, int64_t *strata) {
+    if (!path || !hops || !layers || !info || !totals || !n_levels || !strata || level_capacity < 0 || (level_capacity > 0 && !level_counts)) {
+        g_err = "reach_read: invalid argument";
+        return -1;
+    }
+    ReachCounts c;
+    if (gcn_reach_read(path, &c, &g_err) != 0) return -1;
+    *hops = c.hops; *layers = c.layers;
+    info[0] = c.sources; info[1] = c.unlabelled; info[2] = c.rounds;
+    std::copy(c.totals, c.totals + 6, totals);
+    *n_levels = (int64_t)c.level_counts.size();
+    for (size_t i = 0; i < c.level_counts.size() && (int64_t)i < level_capacity; i++) level_counts[i] = c.level_counts[i];
     std::copy(c.strata.begin(), c.strata.end(), strata);
     return 0;
 }

@@ -119,6 +119,16 @@
 //                            class_insensitive_homophily=<d> pred_edge_homophily=<e>` (the first four of the labels, the last of
 //                            the predicted classes).  The file gets the two strata tables, both mixing matrices and the integers
 //                            they come from (host/structure.h).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
+// Reach of the labels (beyond the reference; ModelQueries::reach, kernels in csrc/reach.hip, measures in host/reach.h), after the
+// test line and the steps above.  One GPU, a single-label model:
+//   GCN_REACH=<file>         how far the nodes of the TEST split are from the TRAINING split's labels (hops along the stored rows,
+//                            breadth-first on the GPU), the weak components of the graph, and the accuracy by that distance in
+//                            GCN_REACH_HOPS exact distances (default 8, 1..32).  One line is printed: `reach_sources=<n>
+//                            reach_levels=<n> reach_unreachable=<n> reach_outside_two_hops=<n> acc_inside_two_hops=<a>
+//                            acc_outside_two_hops=<b> nearest_label_acc=<c> components=<n> largest_component=<n>
+//                            unseeded_components=<n> unseeded_nodes=<n>` ("two hops" is min(2, GCN_REACH_HOPS - 1)).  The file
+//                            gets the per-distance table, the totals and the integers they come from (host/reach.h).  Works with
+//                            GCN_LOAD_WEIGHTS and 0 epochs.
 // Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
 // and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
 //   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
@@ -166,6 +176,7 @@
 #include "parser.h"
 #include "ranking.h"
 #include "structure.h"
+#include "reach.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -418,6 +429,20 @@ int main(int argc, char **argv) {
                                                                                  : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_STRUCTURE " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *reach_path = getenv("GCN_REACH");
+    if (reach_path && !*reach_path) reach_path = nullptr;
+    const int reach_hops = env_int("GCN_REACH_HOPS", 8);
+    if (reach_path) {
+        const char *why = multilabel_path                                  ? "compares one predicted class per node (GCN_MULTILABEL is set)"
+                          : env_int("GCN_GPUS", 1) > 1                     ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : reach_hops < 1 || reach_hops > REACH_MAX_HOPS  ? "needs GCN_REACH_HOPS in 1..32"
+                                                                           : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_REACH " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -768,6 +793,27 @@ int main(int argc, char **argv) {
                        mt.edge_homophily, mt.node_homophily, mt.adjusted_homophily, mt.class_insensitive_homophily, mp.edge_homophily);
                 fprintf(stderr, "gcn-hip: the label structure of %lld test nodes (%d agreement buckets) written to %s\n", (long long)r.rows, structure_bins,
                         structure_path);
+            }
+            if (reach_path) {                                  // one rank (checked above): the test split from the training split
+                ReachCounts rc;
+                rc.hops = reach_hops; rc.layers = gcn_reach_layers(reach_hops);
+                rc.strata.assign((size_t)(reach_hops + 2) * 4, 0);
+                rc.level_counts.assign((size_t)params.num_nodes + 1, 0);
+                const ModelQueries::Reach r = gcn.queries().reach(3, nullptr, 0, 1 << 1, nullptr, 0, reach_hops, true, nullptr, nullptr, nullptr,
+                                                                  rc.strata.data(), rc.totals, rc.level_counts.data(), (int)rc.level_counts.size());
+                rc.level_counts.resize((size_t)r.levels + 1);
+                rc.sources = r.sources; rc.unlabelled = r.unlabelled; rc.rounds = r.rounds;
+                ReachMetrics rm;
+                std::string err;
+                if (gcn_reach_metrics(rc.strata.data(), rc.hops, rc.layers, &rm, &err) != 0 || gcn_reach_write(reach_path, rc, &err) != 0)
+                    throw GcnHipFailure(-1, "gcn-hip: " + err);
+                printf("reach_sources=%lld reach_levels=%d reach_unreachable=%lld reach_outside_two_hops=%lld acc_inside_two_hops=%.6f "
+                       "acc_outside_two_hops=%.6f nearest_label_acc=%.6f components=%lld largest_component=%lld unseeded_components=%lld "
+                       "unseeded_nodes=%lld\n",
+                       (long long)r.sources, r.levels, (long long)rm.unreachable, (long long)rm.outside.rows, rm.inside.accuracy, rm.outside.accuracy,
+                       rm.all.nearest_accuracy, (long long)rc.totals[1], (long long)rc.totals[2], (long long)rc.totals[3], (long long)rc.totals[4]);
+                fprintf(stderr, "gcn-hip: the reach of %lld test nodes from %lld training nodes (%d distances) written to %s\n", (long long)r.rows,
+                        (long long)r.sources, reach_hops, reach_path);
             }
             if (explain_path) {                                // one rank (checked above)
                 const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph, the reach of the labels.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -381,6 +381,46 @@ public:
                         int64_t *class_rows_truth, int64_t *totals_truth, int64_t *mix_pred, int64_t *class_rows_pred, int64_t *totals_pred,
                         int64_t *strata);
 
+    // Reach of the labels (csrc/reach.hip has the definitions; host/reach_query.cpp the bodies; host/reach.h turns the strata into
+    // accuracy by distance): HOW FAR every node is from the labelled nodes the model learns from, which nodes hang together, and
+    // how the accuracy falls with that distance.  Arrays are in DATASET node order.  Rows: the nodes of `split` (1..3) in
+    // ascending dataset id, or with split == 0 the `nodes` query (dataset ids in the order given, repeats counted as often as
+    // listed; NULL: every node in id order).  SOURCES (and the marks of components): the nodes of the splits in `source_mask`
+    // (bit s = split s, 2 = the training split), or with source_mask == 0 the n_sources dataset ids of `source_nodes` (repeats
+    // allowed, none: no source).  The adjacency walked is the model's own object with its stored rows; the distance follows the
+    // direction of an aggregation (row v gathers from the entries it lists), the components are weak.  One rank only, and there
+    // a row is a node: the traversal's tie rule — the LOWEST ROW among the sources at the same distance — is by local row, which
+    // without a forced node order is the dataset id; nearest and component are mapped to dataset ids through node_id().
+    //   label_distance: sync(); one gcnhip_hop_distance over the whole graph (max_hops 0: no limit).  dist / nearest [rows] by list
+    //   position (nearest may be NULL, and is then not computed: a row stops at its first hit); level_counts [capacity] as the
+    //   kernel call fills it.
+    //   components: sync(); gcnhip_components and gcnhip_component_counts with the sources as marks.  component / size [rows] by
+    //   list position (each may be NULL): the component's smallest row as a dataset id, and its number of nodes; totals [6].
+    //   reach: sync(); with `predicted` one evaluation forward with the prediction epilogue over every row (forward_predict(NULL,
+    //   false)); the traversal from the sources without a hop limit, with nearest; the components with the sources as marks; one
+    //   gcnhip_distance_strata over the listed rows against the dataset's labels: strata [(hops + 2) x 4].  dist / nearest /
+    //   component [rows] by list position, each may be NULL.
+    // Only the strata, the totals and the level counts cross to the host, and with per-position outputs asked for one int32 array
+    // of every local row each.  predict()'s contract: the metrics ring, the current split, variable 6 and the captured epoch graph
+    // are untouched; a train_epoch() after it has the same bits as one without it.  Scratch lives in the arena; nothing is
+    // allocated until first use.  Single- and multi-label models alike, except reach with `predicted`.  Refused with a message
+    // before any launch: more than one rank (the traversal would need an exchange per level), a split outside 0..3, a source mask
+    // with other bits than 1..3, a node id outside the graph, max_hops < 0, hops outside 1..32, and for reach with `predicted` a
+    // multi-label model.
+    struct Reach {
+        int64_t rows = 0, sources = 0, skipped = 0, unlabelled = 0, unreachable = 0;   // listed; rows that became sources; ...; listed with dist -1
+        int levels = 0, rounds = 0;
+    };
+    // the refusals alone, and the number of rows the query lists (a caller sizes its arrays by it); touches no device state
+    int64_t reach_rows(const char *what, int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int max_hops,
+                       int hops, bool predicted);
+    Reach label_distance(int source_mask, const int *source_nodes, int n_sources, int split, const int *nodes, int n, int max_hops, int32_t *dist,
+                         int32_t *nearest, int64_t *level_counts, int capacity);
+    Reach components(int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int32_t *component, int32_t *size,
+                     int64_t *totals);
+    Reach reach(int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int hops, bool predicted, int32_t *dist,
+                int32_t *nearest, int32_t *component, int64_t *strata, int64_t *totals, int64_t *level_counts, int capacity);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                       // every device buffer of a query
@@ -496,6 +536,18 @@ private:
     struct AgreementOut { int32_t *deg, *same, *known; int64_t *mix, *class_rows, *totals; };
     // one launch on `d_lab` (local rows) over the uploaded list and the copies to the host; returns the skipped positions
     int64_t agreement_launch(const int32_t *d_lab, int C, const int32_t *d_rows, int n, int32_t *d_per, const AgreementOut &out);
+
+    // label_distance / components / reach: the listed rows, the source rows and their flag per row, dist / nearest / comp / size /
+    // marked [local rows], {the kernels' scratch [64] | totals [6] | strata [(hops + 2) x 4] | unlabelled} as int64
+    Scratch<int32_t> d_rc_rows{&arena}, d_rc_seeds{&arena}, d_rc_mark{&arena}, d_rc_dist{&arena}, d_rc_nearest{&arena}, d_rc_comp{&arena},
+        d_rc_size{&arena}, d_rc_marked{&arena};
+    Scratch<int64_t> d_rc_counts{&arena};
+    std::vector<int> reach_sources(const char *what, int source_mask, const int *source_nodes, int n_sources);
+    // the traversal from `sources` (local rows) into d_rc_dist (and d_rc_nearest); the components into d_rc_comp / _size / _marked
+    void reach_traverse(const std::vector<int> &sources, int max_hops, bool want_nearest, int64_t *level_counts, int capacity, Reach &res);
+    void reach_components(const std::vector<int> &sources, int64_t *totals, Reach &res);
+    // one int32 per local row to the host, picked at the listed rows; as_node: rows >= 0 become dataset ids
+    void reach_pick(const int32_t *d_per_row, const std::vector<int> &rows, bool as_node, int32_t *out);
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

@@ -1027,6 +1027,99 @@ class HipGCNModel:
             out.update(deg=per[0][:out["rows"]].copy(), same=per[1][:out["rows"]].copy(), known=per[2][:out["rows"]].copy())
         return out
 
+    # ---- reach of the labels: hops to the nearest labelled node, weak components, accuracy by that distance, on the GPU
+    def _reach_sources(self, what, splits, source_nodes):
+        """argument checks that need no GPU; returns (split mask, node ids int32 or None, n)"""
+        if source_nodes is not None:
+            s = np.ascontiguousarray(source_nodes, np.int32).ravel()
+            return 0, (s if s.size else np.zeros(1, np.int32)), int(s.size)
+        splits = (splits,) if isinstance(splits, (int, np.integer)) and not isinstance(splits, bool) else tuple(splits)
+        if not splits or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s not in (1, 2, 3) for s in splits):
+            raise GcnHostError(f"{what}: the source splits are 1 (train), 2 (validation), 3 (test), got {splits!r}")
+        return sum({1 << int(s) for s in splits}), None, 0
+
+    def label_distance(self, sources=(1,), source_nodes=None, split=None, nodes=None, max_hops=0, nearest=False):
+        """How many hops every listed node is from the nearest source, found on the GPU by a level-synchronous breadth-first
+        search over the model's adjacency (csrc/reach.hip has the definitions).  Sources: the nodes of the splits in `sources`
+        (default: the training split), or the dataset ids in `source_nodes` (repeats allowed, an empty list: no source).  Rows:
+        the nodes of `split` in ascending id, or the `nodes` query (dataset ids, repeats counted as often as listed), or with
+        both None every node.  The distance follows an aggregation: a node gathers from the entries its stored row lists, so
+        dist = 1 + the smallest dist among them, 0 for a source, -1 when no source reaches the node (or none within max_hops; 0:
+        no limit) — the reach of label_propagation(), and for dist <= 2 of the two-layer model itself.  Returns a dict: dist int32
+        [rows]; nearest int32 [rows] with nearest=True, else None: the source at distance dist with the lowest row (the node id,
+        unless the model was given a node order), -1 when unreachable; levels (the largest distance in the graph), level_counts
+        int64 [levels + 1] (nodes of the WHOLE graph per distance), unreachable (listed rows with dist -1), sources, rows.
+        Single- and multi-label models alike; one rank.  Training state is not touched."""
+        what = "label_distance"
+        if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or max_hops < 0:
+            raise GcnHostError(f"{what}: max_hops must be an integer >= 0 (0: no limit), got {max_hops!r}")
+        mask, s, ns = self._reach_sources(what, sources, source_nodes)
+        code, q, n, cap = self._structure_query(what, split, nodes)
+        dist = np.zeros(max(cap, 1), np.int32)
+        near = np.zeros(max(cap, 1), np.int32) if nearest else None
+        lc, info = np.zeros(self.params.num_nodes + 1, np.int64), np.zeros(5, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_label_distance(
+            self.h, mask, s.ctypes.data if s is not None else None, ns, code, q.ctypes.data if q is not None else None, n, int(max_hops), cap,
+            dist.ctypes.data, near.ctypes.data if nearest else None, lc.ctypes.data, lc.size, info.ctypes.data), what)
+        rows, levels = int(info[0]), int(info[4])
+        return dict(dist=dist[:rows].copy(), nearest=near[:rows].copy() if nearest else None, levels=levels, level_counts=lc[:levels + 1].copy(),
+                    unreachable=int(info[3]), sources=int(info[1]), rows=rows)
+
+    def components(self, split=None, nodes=None, marked=(1,), marked_nodes=None):
+        """The weakly connected components of the model's adjacency, labelled on the GPU (min-label hooking and pointer jumping,
+        csrc/reach.hip): every stored entry joins its two ends, whichever row stores it.  Rows as label_distance() takes them.
+        marked: the splits whose nodes count as marks (default: the training split), or marked_nodes: dataset ids — a component
+        without a marked node holds no label to learn from.  Returns a dict: component int32 [rows] (the smallest node of the
+        component) and size int32 [rows] per listed node; n_components, largest, unmarked_components, unmarked_nodes, marked_rows
+        (of the WHOLE graph), rounds, rows.  Single- and multi-label models alike; one rank.  Training state is not touched."""
+        what = "components"
+        mask, s, ns = self._reach_sources(what, marked, marked_nodes)
+        code, q, n, cap = self._structure_query(what, split, nodes)
+        comp, size = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        totals, info = np.zeros(6, np.int64), np.zeros(2, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_components(
+            self.h, code, q.ctypes.data if q is not None else None, n, mask, s.ctypes.data if s is not None else None, ns, cap, comp.ctypes.data,
+            size.ctypes.data, totals.ctypes.data, info.ctypes.data), what)
+        rows = int(info[0])
+        return dict(component=comp[:rows].copy(), size=size[:rows].copy(), n_components=int(totals[1]), largest=int(totals[2]),
+                    unmarked_components=int(totals[3]), unmarked_nodes=int(totals[4]), marked_rows=int(totals[5]), totals=totals, rounds=int(info[1]),
+                    rows=rows)
+
+    def reach_report(self, split=3, nodes=None, sources=(1,), source_nodes=None, hops=8, predicted=True, per_node=False):
+        """How far the listed nodes (default: the test split) are from the labels the model learns from, and how its accuracy
+        falls with that distance.  One traversal from the sources (label_distance() with nearest), the components with the sources
+        as marks, with predicted=True (single-label models) one evaluation forward, and one strata launch.  Returns
+        reach_metrics() of the strata — by_distance: a list of dict(rows, labelled, correct, nearest_correct, accuracy,
+        nearest_label_accuracy) per bucket (b < hops: distance b; hops: further away; hops + 1: unreachable);
+        inside_receptive_field / outside_receptive_field: the same over the rows within `layers` = min(2, hops - 1) hops and over
+        the rest; all; unreachable, unreachable_share; nearest_label_accuracy ("copy the label of the nearest source") — plus the
+        integers: strata int64 [hops + 2, 4], totals int64 [6], n_components, largest, unmarked_components, unmarked_nodes, levels,
+        level_counts, sources, rounds, rows, unlabelled; with per_node=True dist / nearest / component int32 [rows].  Without
+        predicted the `correct` counts are 0.  Only the count tables cross to the host.  One rank.  Training state is not touched."""
+        what = "reach_report"
+        if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= hops <= 32:
+            raise GcnHostError(f"{what}: hops must be an integer in 1..32, got {hops!r}")
+        if predicted and self.multilabel:
+            raise GcnHostError(f"{what}: predicted=True takes a single-label model (one predicted class per node)")
+        mask, s, ns = self._reach_sources(what, sources, source_nodes)
+        code, q, n, cap = self._structure_query(what, None if nodes is not None else split, nodes)
+        hops = int(hops)
+        per = [np.zeros(max(cap, 1), np.int32) for _ in range(3)] if per_node else [None] * 3
+        strata, totals = np.zeros((hops + 2, 4), np.int64), np.zeros(6, np.int64)
+        lc, info = np.zeros(self.params.num_nodes + 1, np.int64), np.zeros(7, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_reach(
+            self.h, code, q.ctypes.data if q is not None else None, n, mask, s.ctypes.data if s is not None else None, ns, hops, int(bool(predicted)), cap,
+            *[a.ctypes.data if a is not None else None for a in per], strata.ctypes.data, totals.ctypes.data, lc.ctypes.data, lc.size,
+            info.ctypes.data), what)
+        rows, levels = int(info[0]), int(info[5])
+        out = reach_metrics(strata, hops, min(2, hops - 1))
+        out.update(strata=strata, totals=totals, n_components=int(totals[1]), largest=int(totals[2]), unmarked_components=int(totals[3]),
+                   unmarked_nodes=int(totals[4]), levels=levels, level_counts=lc[:levels + 1].copy(), sources=int(info[1]), rounds=int(info[6]),
+                   rows=rows, unlabelled=int(info[3]), predicted=bool(predicted))
+        if per_node:
+            out.update(dist=per[0][:rows].copy(), nearest=per[1][:rows].copy(), component=per[2][:rows].copy())
+        return out
+
     # ---- explaining a logit: neighbour, hidden-unit and feature shares, on the GPU
     def _explain_args(self, what, nodes, classes=None):
         """argument checks that need no GPU; returns (node ids int32 or None, classes int32 or None)"""
@@ -1438,6 +1531,66 @@ def read_structure_report(path):
     c, b = c.value, b.value
     return dict(num_classes=c, bins=b, truth=dict(mix=mt[:c * c].reshape(c, c).copy(), class_rows=rt[:c].copy(), totals=tt),
                 pred=dict(mix=mp[:c * c].reshape(c, c).copy(), class_rows=rp[:c].copy(), totals=tp), strata=st[:32 * (b + 1) * 2].reshape(32, b + 1, 2).copy())
+
+
+def _reach_strata(what, strata, hops):
+    st = np.ascontiguousarray(strata, np.int64)
+    if hops is None and st.ndim == 2:
+        hops = st.shape[0] - 2
+    if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= hops <= 32 or st.shape != (hops + 2, 4):
+        raise GcnHostError(f"{what}: strata must have shape (hops + 2, 4) with 1 <= hops <= 32, got {st.shape} with hops = {hops!r}")
+    return st, int(hops)
+
+
+def reach_metrics(strata, hops=None, layers=2):
+    """Accuracy by distance from the labels out of integer counts — host only, no GPU; the one place the measures are derived
+    (host/reach.h).  strata int [hops + 2, 4]: per bucket (b < hops: distance b; hops: further away; hops + 1: unreachable) the
+    rows listed, those with a label, of those the ones predicted right, of those the ones whose nearest source carries their
+    label.  layers: the depth of the model, 0 <= layers < hops: a row within `layers` hops is inside the receptive field.  Returns
+    a dict: by_distance (a list of dict(rows, labelled, correct, nearest_correct, accuracy, nearest_label_accuracy)),
+    inside_receptive_field, outside_receptive_field, all (the same keys), unreachable, unreachable_share, nearest_label_accuracy
+    (over all rows), hops, layers.  A zero denominator gives 0, never NaN.  A negative or inconsistent count, or a mismatched
+    shape, raises GcnHostError."""
+    what = "reach_metrics"
+    st, hops = _reach_strata(what, strata, hops)
+    if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)):
+        raise GcnHostError(f"{what}: layers must be an integer in 0..hops - 1, got {layers!r}")
+    lib = _lib.gcnhost()
+    bd, gr, sm = np.zeros((hops + 2, 6), np.float64), np.zeros((3, 6), np.float64), np.zeros(2, np.float64)
+    _ck(lib, lib.gcnhost_reach_metrics(st.ctypes.data, hops, int(layers), bd.ctypes.data, gr.ctypes.data, sm.ctypes.data), what)
+    row = lambda x: dict(rows=int(x[0]), labelled=int(x[1]), correct=int(x[2]), nearest_correct=int(x[3]), accuracy=float(x[4]),
+                         nearest_label_accuracy=float(x[5]))
+    return dict(by_distance=[row(x) for x in bd], inside_receptive_field=row(gr[0]), outside_receptive_field=row(gr[1]), all=row(gr[2]),
+                unreachable=int(sm[0]), unreachable_share=float(sm[1]), nearest_label_accuracy=float(gr[2][5]), hops=hops, layers=int(layers))
+
+
+def write_reach_report(path, report):
+    """reach_report()'s integers as the text file gcn-hip writes for GCN_REACH"""
+    what = "write_reach_report"
+    st, hops = _reach_strata(what, report["strata"], report.get("hops"))
+    totals, lc = np.ascontiguousarray(report["totals"], np.int64), np.ascontiguousarray(report["level_counts"], np.int64)
+    if totals.shape != (6,) or lc.ndim != 1 or lc.size < 1:
+        raise GcnHostError(f"{what}: totals must have shape (6,) and level_counts at least one entry, got {totals.shape} and {lc.shape}")
+    info = np.array([report.get("sources", 0), report.get("unlabelled", 0), report.get("rounds", 0)], np.int64)
+    lib = _lib.gcnhost()
+    _ck(lib, lib.gcnhost_reach_write(os.fspath(path).encode(), hops, int(report.get("layers", min(2, hops - 1))), info.ctypes.data, totals.ctypes.data,
+                                     lc.ctypes.data, lc.size, st.ctypes.data), what)
+
+
+def read_reach_report(path):
+    """the integers of a reach report file: dict(hops, layers, strata, totals, level_counts, levels, sources, unlabelled, rounds)"""
+    lib = _lib.gcnhost()
+    h, la, nl = C.c_int(), C.c_int(), C.c_int64()
+    info, totals, st = np.zeros(3, np.int64), np.zeros(6, np.int64), np.zeros(34 * 4, np.int64)
+    fn = os.fspath(path).encode()
+    _ck(lib, lib.gcnhost_reach_read(fn, C.byref(h), C.byref(la), info.ctypes.data, totals.ctypes.data, None, 0, C.byref(nl), st.ctypes.data),
+        "read_reach_report")
+    lc = np.zeros(nl.value, np.int64)
+    _ck(lib, lib.gcnhost_reach_read(fn, C.byref(h), C.byref(la), info.ctypes.data, totals.ctypes.data, lc.ctypes.data, lc.size, C.byref(nl), st.ctypes.data),
+        "read_reach_report")
+    hops = h.value
+    return dict(hops=hops, layers=la.value, strata=st[:(hops + 2) * 4].reshape(hops + 2, 4).copy(), totals=totals, level_counts=lc, levels=int(lc.size) - 1,
+                sources=int(info[0]), unlabelled=int(info[1]), rounds=int(info[2]))
 
 
 def calibration_report(count, correct, conf_sum):

@@ -829,6 +829,82 @@ class Device:
             self._embed_fail("gcnhip_strata_counts", rc)
         return ob.download().reshape(32, b + 1, 2), int(ub.download()[0])
 
+    # ---- reach of a seed set and components (csrc/reach.hip): every output is uploaded as garbage, the calls write all of it
+    REACH_SCRATCH = 64
+
+    def hop_distance(self, g, seeds, max_hops=0, nearest=True, capacity=None, group=0, levels_per_sync=0):
+        """gcnhip_hop_distance(_ex) on a Graph: dict(dist int32 [n_rows], nearest int32 [n_rows] or None, levels, level_counts int64
+        [levels + 1] (cut at `capacity` entries when given), skipped).  group / levels_per_sync: the lane group per row and the
+        level launches between two read-backs (0: the library's choice; anything else goes through gcnhip_hop_distance_ex)."""
+        s = np.ascontiguousarray(seeds, np.int32).ravel()
+        n = g.n_rows
+        sb = self.buf(s if s.size else np.zeros(1, np.int32))
+        db = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32))
+        nb = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)) if nearest else None
+        scratch = self.buf(np.full(self.REACH_SCRATCH, -777, np.int64))
+        cap = n + 1 if capacity is None else int(capacity)
+        counts = np.full(max(cap, 1), -777, np.int64)
+        levels, skipped = C.c_int(-777), C.c_int64(-777)
+        args = (self.ctx, g.h, sb.ptr, int(s.size), int(max_hops), db.ptr, nb.ptr if nb else None, scratch.ptr, C.byref(levels),
+                counts.ctypes.data if cap > 0 else None, cap, C.byref(skipped))
+        if group or levels_per_sync:
+            rc = self.lib.gcnhip_hop_distance_ex(*args, int(group), int(levels_per_sync) if levels_per_sync else 8)
+        else:
+            rc = self.lib.gcnhip_hop_distance(*args)
+        if rc != 0:
+            self._embed_fail("gcnhip_hop_distance", rc)
+        assert capacity is not None or not counts[levels.value + 1:cap].any()
+        return dict(dist=db.download()[:n], nearest=nb.download()[:n] if nb else None, levels=levels.value,
+                    level_counts=counts[:min(levels.value + 1, cap)].copy(), skipped=skipped.value)
+
+    def components(self, g):
+        """gcnhip_components on a Graph: (comp int32 [n_rows], rounds)"""
+        n = g.n_rows
+        cb = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32))
+        scratch = self.buf(np.full(self.REACH_SCRATCH, -777, np.int64))
+        rounds = C.c_int(-777)
+        rc = self.lib.gcnhip_components(self.ctx, g.h, cb.ptr, scratch.ptr, C.byref(rounds))
+        if rc != 0:
+            self._embed_fail("gcnhip_components", rc)
+        return cb.download()[:n], rounds.value
+
+    def component_counts(self, comp, mark=None):
+        """gcnhip_component_counts: (size int32 [n], marked int32 [n], totals int64 [6])"""
+        c = np.ascontiguousarray(comp, np.int32).ravel()
+        n = int(c.size)
+        one = np.zeros(1, np.int32)
+        cb = self.buf(c if n else one)
+        mb = None if mark is None else self.buf(np.ascontiguousarray(mark, np.int32).ravel() if n else one)
+        assert mark is None or np.size(mark) == n
+        sb, kb = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)), self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32))
+        tb = self.buf(np.full(6, -777, np.int64))
+        rc = self.lib.gcnhip_component_counts(self.ctx, cb.ptr, mb.ptr if mb else None, n, sb.ptr, kb.ptr, tb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_component_counts", rc)
+        return sb.download()[:n], kb.download()[:n], tb.download()
+
+    def distance_strata(self, dist, truth, num_classes, hops, nearest=None, pred=None, rows=None):
+        """gcnhip_distance_strata: (strata int64 [hops + 2, 4], unlabelled) — dist / nearest / pred / truth by row, rows None:
+        position i is row i"""
+        d, t = np.ascontiguousarray(dist, np.int32).ravel(), np.ascontiguousarray(truth, np.int32).ravel()
+        n_rows = int(d.size)
+        assert t.size == n_rows
+        one = np.zeros(1, np.int32)
+        up = lambda a: None if a is None else self.buf(np.ascontiguousarray(a, np.int32).ravel() if np.size(a) else one)
+        assert all(a is None or np.size(a) == n_rows for a in (nearest, pred))
+        db, tb, nb, pb = up(d), up(t), up(nearest), up(pred)
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        n = n_rows if r is None else int(r.size)
+        rb = up(r)
+        h = int(hops)
+        cells = (h + 2) * 4 if 1 <= h <= 32 else 8
+        ob, ub = self.buf(np.full(cells, 0x5A5A5A5A5A5A5A5A, np.int64)), self.buf(np.full(1, -777, np.int64))
+        rc = self.lib.gcnhip_distance_strata(self.ctx, db.ptr, nb.ptr if nb else None, pb.ptr if pb else None, tb.ptr, n_rows, rb.ptr if rb else None, n,
+                                             int(num_classes), h, ob.ptr, ub.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_distance_strata", rc)
+        return ob.download().reshape(h + 2, 4), int(ub.download()[0])
+
     # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
     def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,
                       store=True):

@@ -464,6 +464,47 @@ int gcnhip_nbr_agreement_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_
 int gcnhip_strata_counts(gcnhip_ctx *ctx, const int32_t *deg, const int32_t *same, const int32_t *known, const int32_t *pred,
                          const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int num_classes, int bins, int64_t *strata,
                          int64_t *unlabelled);
+/* ---- reach of a seed set and connected components (reach.hip; beyond the reference: HOW FAR a row is from what it learns from) ----
+ * g: a SQUARE adjacency object with its stored rows (one-way, repeated and unsorted entries allowed; an entry outside the graph is
+ * passed over).  All integer work: the same bits from every launch, lane group and batching.
+ * gcnhip_hop_distance: d_seeds: a device int32 list of n_seeds rows, repeats allowed; a seed outside [0, n_rows) counts in *skipped
+ * and nowhere else.  dist: device int32 [n_rows]: 0 for a seed, else 1 + min dist[u] over the stored entries u != v of ROW v (row v
+ * gathers from the entries it lists; no transpose is used), -1 when no seed reaches v or none within max_hops (0: no limit).
+ * nearest: device int32 [n_rows], may be NULL: the lowest row index among the seeds at distance dist[v] from v, -1 with dist -1.
+ * scratch: device int64 [GCNHIP_REACH_SCRATCH].  HOST outputs: *levels = the largest distance assigned, level_counts[d] = the rows
+ * with distance d for d < capacity (the rest of [0, capacity) zero; may be NULL with capacity 0), *skipped.  One level is one
+ * launch; no launch waits on another workgroup.  UNLIKE most entry points here the call SYNCHRONISES the context's stream: once
+ * after the seeding and once per levels_per_sync level launches, to read the counters of newly reached rows and stop at the first
+ * empty level (launches behind it change nothing).  It allocates nothing.
+ * gcnhip_hop_distance_ex: the same with the lane group per row (0: by the mean stored row length; 4, 16, 64) and levels_per_sync
+ * (1..64; the plain call uses 8) given.
+ * gcnhip_components: comp: device int32 [n_rows] = the smallest row index in the row's WEAKLY connected component (every stored
+ * entry u != v joins u and v, whichever row stores it).  Min-label hooking with atomicMin and pointer jumping; the call ends after
+ * a round whose hooking pass found equal labels on every stored entry.  *rounds (host) = the rounds run, that one included.
+ * scratch as above.  SYNCHRONISES the stream once per round (4 bytes read back); allocates nothing.
+ * gcnhip_component_counts: comp and mark (int32 flag per row, NULL: no row is marked) [n_rows]; size / marked: device int32
+ * [n_rows], size[r] = rows with comp == r, marked[r] = those with mark != 0; totals: device int64 [6] = {rows with comp in range,
+ * components, largest size, components without a marked row, rows in those components, marked rows}.  Zeroes its outputs,
+ * allocates nothing, synchronises nothing.
+ * gcnhip_distance_strata: dist, nearest (may be NULL), pred (may be NULL), truth: device int32 [n_rows], indexed by ROW; d_rows: n
+ * positions (NULL: position i is row i), a row outside [0, n_rows) counts nowhere.  Bucket b = dist for 0 <= dist < hops, hops
+ * for dist >= hops, hops + 1 for dist < 0.  strata: device int64 [(hops + 2) x 4], per bucket {positions listed, those whose truth
+ * is known (0 <= truth < num_classes), of those pred == truth, of those the nearest row has a known truth equal to theirs};
+ * *unlabelled (device int64) = the listed positions without a known truth.  Zeroes its outputs, allocates nothing, synchronises
+ * nothing.
+ * Refused with -1 and a message (gcnhip_last_error) before any launch: a NULL required pointer, a negative count, a non-square
+ * object, a lane group other than 0 / 4 / 16 / 64, levels_per_sync outside 1..64, hops outside 1..32, num_classes < 1. */
+#define GCNHIP_REACH_SCRATCH 64
+int gcnhip_hop_distance(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *d_seeds, int n_seeds, int max_hops, int32_t *dist,
+                        int32_t *nearest, int64_t *scratch, int *levels, int64_t *level_counts, int capacity, int64_t *skipped);
+int gcnhip_hop_distance_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *d_seeds, int n_seeds, int max_hops, int32_t *dist,
+                           int32_t *nearest, int64_t *scratch, int *levels, int64_t *level_counts, int capacity, int64_t *skipped, int group,
+                           int levels_per_sync);
+int gcnhip_components(gcnhip_ctx *ctx, const gcnhip_graph *g, int32_t *comp, int64_t *scratch, int *rounds);
+int gcnhip_component_counts(gcnhip_ctx *ctx, const int32_t *comp, const int32_t *mark, int n_rows, int32_t *size, int32_t *marked,
+                            int64_t *totals);
+int gcnhip_distance_strata(gcnhip_ctx *ctx, const int32_t *dist, const int32_t *nearest, const int32_t *pred, const int32_t *truth,
+                           int n_rows, const int32_t *d_rows, int n, int num_classes, int hops, int64_t *strata, int64_t *unlabelled);
 /* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
  * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
  * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and

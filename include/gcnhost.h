@@ -445,6 +445,45 @@ int gcnhost_structure_write(const char *path, int num_classes, int bins, const i
                             const int64_t *strata);
 int gcnhost_structure_read(const char *path, int *num_classes, int *bins, int64_t *totals_truth, int64_t *totals_pred, int64_t *class_rows_truth,
                            int64_t *class_rows_pred, int64_t *mix_truth, int64_t *mix_pred, int64_t *strata);
+/* Reach of the labels (ModelQueries::label_distance / components / reach, host/queries.h; kernels and definitions in
+ * csrc/reach.hip; measures in host/reach.h).  Arrays are in DATASET node order.  Rows: the nodes of `split` (1 train, 2 validation,
+ * 3 test) in ascending id, or with split == 0 the `nodes` query (n dataset ids in the order given, repeats counted as often as
+ * listed; NULL: every node in id order).  Sources (the marks of components): the nodes of the splits in source_mask (bit s = split
+ * s; 2 = the training split), or with source_mask == 0 the n_sources ids of source_nodes.  One rank; single- and multi-label
+ * models alike (gcnhost_model_reach with predicted != 0: single-label only).  Per-position arrays are laid out for `capacity`
+ * rows, at least the rows listed; each may be NULL.  nearest and component are dataset ids; a tie between sources at the same
+ * distance goes to the lowest local row (the dataset id unless the model was given a node order).
+ * gcnhost_model_label_distance: dist / nearest [rows] (nearest NULL: not computed), level_counts [level_capacity] (rows per
+ *   distance, zero past the last level), info [5] = {rows listed, rows that became sources, source positions outside the graph,
+ *   listed rows no source reaches (within max_hops; 0: no limit), levels}.
+ * gcnhost_model_components: component / size [rows] = the smallest node of the row's weak component and its number of nodes,
+ *   totals [6] = {rows, components, largest, components without a source, rows in those, source rows}, info [2] = {rows listed,
+ *   rounds}.
+ * gcnhost_model_reach: with predicted != 0 one evaluation forward; the traversal; the components; strata [(hops + 2) x 4] = per
+ *   distance bucket (b < hops: distance b; hops: further; hops + 1: unreachable) {rows, labelled, predicted right, nearest
+ *   source has the row's label}; totals [6]; level_counts; info [7] = {rows listed, sources, skipped, listed rows without a
+ *   label, listed rows unreachable, levels, rounds}.
+ * predict's contract: training state is not touched.  Refused with a message before any launch: several ranks, a bad split, source
+ * mask or node id, max_hops < 0, hops outside 1..32, and with predicted a multi-label model.
+ * gcnhost_reach_metrics (host/reach.h; no GPU): by_distance [(hops + 2) x 6] and groups [3 x 6] (inside the receptive field =
+ *   buckets 0 .. layers, outside it, all), rows of {rows, labelled, correct, nearest_correct, accuracy, nearest_label_accuracy};
+ *   summary [2] = {unreachable, unreachable share}.  0 <= layers < hops.  Each output may be NULL.  A zero denominator gives 0,
+ *   never NaN; a negative or inconsistent count is an error.
+ * gcnhost_reach_write / _read: the text report gcn-hip writes for GCN_REACH; info [3] = {sources, unlabelled, rounds}; the reader
+ *   copies at most level_capacity level counts and tells their number in *n_levels. */
+int gcnhost_model_label_distance(gcnhost_model *m, int source_mask, const int *source_nodes, int n_sources, int split, const int *nodes, int n,
+                                 int max_hops, int64_t capacity, int32_t *dist, int32_t *nearest, int64_t *level_counts, int level_capacity,
+                                 int64_t *info);
+int gcnhost_model_components(gcnhost_model *m, int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources,
+                             int64_t capacity, int32_t *component, int32_t *size, int64_t *totals, int64_t *info);
+int gcnhost_model_reach(gcnhost_model *m, int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int hops,
+                        int predicted, int64_t capacity, int32_t *dist, int32_t *nearest, int32_t *component, int64_t *strata, int64_t *totals,
+                        int64_t *level_counts, int level_capacity, int64_t *info);
+int gcnhost_reach_metrics(const int64_t *strata, int hops, int layers, double *by_distance, double *groups, double *summary);
+int gcnhost_reach_write(const char *path, int hops, int layers, const int64_t *info, const int64_t *totals, const int64_t *level_counts,
+                        int64_t n_levels, const int64_t *strata);
+int gcnhost_reach_read(const char *path, int *hops, int *layers, int64_t *info, int64_t *totals, int64_t *level_counts, int64_t level_capacity,
+                       int64_t *n_levels, int64_t *strata);
 /* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
  * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
  * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
