@@ -133,6 +133,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
     "gcnhip_kmeans_seed": (I, [P, P, I, I, I, P, P, I, I, U64, P, I, P, P, C.c_size_t]),
     "gcnhip_contingency_rows": (I, [P, P, P, I, P, I, I, I, P, P]),
+    "gcnhip_silhouette_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_silhouette_sums": (I, [P, P, I, I, I, P, P, I, P, I, P, P, P, C.c_size_t]),
+    "gcnhip_silhouette_rows": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P, P]),
     "gcnhip_pca_plan": (I, [I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_pca_mean": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
     "gcnhip_pca_scatter": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
@@ -278,6 +281,7 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
+    "gcnhost_model_silhouette": (I, [P, I, P, I, P, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),
     "gcnhost_sym_eigen": (I, [P, I, P, P]),
     "gcnhost_pca_from_scatter": (I, [P, P, I64, I, I, I, P, P, P, P, C.POINTER(I)]),
     "gcnhost_model_pca_fit": (I, [P, I, I, P, I, I, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),

@@ -24,26 +24,20 @@
 // gcnhip_kmeans_seed     k-means++ (Arthur & Vassilvitskii, 2007) without a prefix sum: drawing i with probability d2min[i] / sum
 //   is taking the smallest of the exponential variates -log(u_i) / d2min[i] — a commutative min over (key, position).
 // gcnhip_contingency_rows  integer counts by LDS histogram and integer atomics.
-#include "common.h"
+#include "bucket.h"
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int KM_MAX_DIM = 256, KM_MAX_K = 256, KM_MAX_C = 64;
+constexpr int KM_MAX_DIM = 256, KM_MAX_C = 64;     // KM_MAX_K, KM_CHUNK and the bucketing kernels: bucket.h
 constexpr int KM_RT = 64;                         // list positions per tile of the assign kernel
 constexpr int KM_CT = 64;                         // centres per LDS tile
-constexpr int KM_CHUNK = 1024;                    // positions per histogram chunk (part of the definition of the sums' order)
 constexpr int KM_SEG = 128;                       // members per segment (part of the definition)
 constexpr int KM_MIN_SEGS = 64;                   // the smallest batch of segment partials
 constexpr int KM_SEED_PARTS = 1024;               // workgroups of a seeding step at most
 constexpr int KM_SEED_ROWS = 8;                   // list positions a wave of a seeding step has in flight (a power of two)
-
-__device__ inline int list_row(const int32_t *__restrict__ d_rows, int i, int n_table) {
-    const int r = d_rows ? d_rows[i] : i;
-    return r >= 0 && r < n_table ? r : -1;
-}
 
 // ---- assign ---------------------------------------------------------------------------------------------------------------
 
@@ -158,103 +152,6 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float *__restr
 
 // ---- update ---------------------------------------------------------------------------------------------------------------
 
-// a member: a position whose centre is in [0, k) and whose row is in the table
-__device__ inline int member_centre(const int32_t *__restrict__ assign, const int32_t *__restrict__ d_rows, int i, int n, int n_table, int k) {
-    if (i >= n) return -1;
-    const int c = assign[i];
-    return c >= 0 && c < k && list_row(d_rows, i, n_table) >= 0 ? c : -1;
-}
-
-// block = chunk: hist[chunk][c] = members of centre c in the chunk; dpart[chunk] = the chunk's sum of dist2 over members
-__global__ __launch_bounds__(256) void kmeans_hist_kernel(const int32_t *__restrict__ assign, const int32_t *__restrict__ d_rows,
-                                                          const float *__restrict__ dist2, int n, int n_table, int k,
-                                                          int32_t *__restrict__ hist, double *__restrict__ dpart) {
-    __shared__ int cnt[KM_MAX_K];
-    __shared__ double red[256];
-    const int chunk = blockIdx.x, t = threadIdx.x;
-    cnt[t] = 0;
-    __syncthreads();
-    double s = 0.0;
-    for (int b = 0; b < KM_CHUNK / 256; b++) {
-        const int i = chunk * KM_CHUNK + b * 256 + t;
-        const int c = member_centre(assign, d_rows, i, n, n_table, k);
-        if (c >= 0) {
-            atomicAdd(&cnt[c], 1);
-            if (dist2) s += (double)dist2[i];
-        }
-    }
-    red[t] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    if (t < k) hist[(size_t)chunk * k + t] = cnt[t];
-    if (t == 0) dpart[chunk] = red[0];
-}
-
-// one block: hist -> the chunk's offset inside its centre; sizes, cstart [k + 1] (first slot of a centre in the member list),
-// segstart [k + 1] (first segment of a centre)
-__global__ __launch_bounds__(256) void kmeans_scan_kernel(int32_t *__restrict__ hist, int n_chunks, int k, int32_t *__restrict__ sizes,
-                                                          int32_t *__restrict__ cstart, int32_t *__restrict__ segstart) {
-    __shared__ int tot[KM_MAX_K];
-    const int c = threadIdx.x;
-    if (c < k) {
-        int run = 0;
-#pragma unroll 8
-        for (int ch = 0; ch < n_chunks; ch++) {
-            const int v = hist[(size_t)ch * k + c];
-            hist[(size_t)ch * k + c] = run;
-            run += v;
-        }
-        tot[c] = run;
-        sizes[c] = run;
-    }
-    __syncthreads();
-    if (c == 0) {
-        int a = 0, s = 0;
-        for (int j = 0; j < k; j++) {
-            cstart[j] = a;
-            segstart[j] = s;
-            a += tot[j];
-            s += (tot[j] + KM_SEG - 1) / KM_SEG;
-        }
-        cstart[k] = a;
-        segstart[k] = s;
-    }
-}
-
-// a wave per chunk: its positions go, in order, to the next free slots of their centres
-__global__ __launch_bounds__(64) void kmeans_scatter_kernel(const int32_t *__restrict__ assign, const int32_t *__restrict__ d_rows, int n,
-                                                            int n_table, int k, const int32_t *__restrict__ hist,
-                                                            const int32_t *__restrict__ cstart, int32_t *__restrict__ order) {
-    __shared__ int next[KM_MAX_K];
-    const int chunk = blockIdx.x, lane = threadIdx.x;
-    for (int c = lane; c < k; c += WAVE) next[c] = cstart[c] + hist[(size_t)chunk * k + c];
-    __syncthreads();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    for (int b = 0; b < KM_CHUNK / WAVE; b++) {
-        const int i = chunk * KM_CHUNK + b * WAVE + lane;
-        const int c = member_centre(assign, d_rows, i, n, n_table, k);
-        unsigned long long left = __ballot(c >= 0), mine = 0;
-        while (left) {                                          // one round per distinct centre among the 64 positions
-            const int lead = __ffsll(left) - 1;
-            const int cl = __shfl(c, lead, WAVE);
-            const unsigned long long same = __ballot(c == cl);
-            if (c == cl) mine = same;
-            left &= ~same;
-        }
-        int base = 0;
-        if (c >= 0) base = next[c];
-        __syncthreads();
-        if (c >= 0) {
-            order[base + __popcll(mine & below)] = i;
-            if ((mine >> lane) >> 1 == 0) next[c] = base + __popcll(mine);    // the group's last lane
-        }
-        __syncthreads();
-    }
-}
-
 // a wave per (segment, slab of 64 columns): the segment's members in order, one float64 chain per column
 __global__ __launch_bounds__(256) void kmeans_segsum_kernel(const float *__restrict__ table, int ld, int n_table, int dim,
                                                             const float *__restrict__ inv_norm, const int32_t *__restrict__ d_rows,
@@ -266,12 +163,7 @@ __global__ __launch_bounds__(256) void kmeans_segsum_kernel(const float *__restr
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int seg = seg0 + g / slabs, slab = g % slabs;
     if (seg >= seg1 || seg >= segstart[k]) return;              // the same for every lane of the wave
-    int lo = 0, hi = k - 1;                                     // the last centre whose first segment is <= seg and that has one
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (segstart[mid] <= seg) lo = mid; else hi = mid - 1;
-    }
-    const int c = lo;
+    const int c = segment_key(segstart, k, seg);
     const int first = cstart[c] + (seg - segstart[c]) * KM_SEG;
     const int count = min(KM_SEG, cstart[c + 1] - first);
     const int col = slab * WAVE + lane;
@@ -572,7 +464,7 @@ int gcnhip_kmeans_update(gcnhip_ctx *c, const float *table, int ld, int n_table,
     GCNHIP_TRY(hipMemsetAsync(acc, 0, (size_t)k * dim * sizeof(double), c->stream));
     kmeans_hist_kernel<<<L.n_chunks, 256, 0, c->stream>>>(assign, d_rows, dist2, n, n_table, k, hist, dpart);
     GCNHIP_LAUNCH_CHECK();
-    kmeans_scan_kernel<<<1, 256, 0, c->stream>>>(hist, L.n_chunks, k, sizes, cstart, segstart);
+    kmeans_scan_kernel<<<1, 256, 0, c->stream>>>(hist, L.n_chunks, k, KM_SEG, sizes, cstart, segstart);
     GCNHIP_LAUNCH_CHECK();
     if (n > 0) {
         kmeans_scatter_kernel<<<L.n_chunks, 64, 0, c->stream>>>(assign, d_rows, n, n_table, k, hist, cstart, order);

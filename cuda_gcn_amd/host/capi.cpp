@@ -359,6 +359,17 @@ int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double
     }
     return 0;
 }
+int gcnhost_model_silhouette(gcnhost_model *m, int split, const int *nodes, int n, const int32_t *labels, int k, int normalize, size_t scratch_bytes,
+                             int64_t capacity, double *s, double *a, double *b, int32_t *neighbor, double *cluster_mean, int32_t *sizes,
+                             int64_t *info, double *score) {
+    if (!m) { g_err = "gcnhost_model_silhouette: invalid argument"; return -1; }
+    API_TRY({
+        const ModelQueries::Silhouette r =
+            m->gcn->queries().silhouette(split, nodes, n, labels, capacity, k, normalize != 0, scratch_bytes, s, a, b, neighbor, cluster_mean, sizes);
+        if (info) { info[0] = r.rows; info[1] = r.points; info[2] = r.excluded; info[3] = r.nonempty; info[4] = r.defined ? 1 : 0; }
+        if (score) *score = r.score;
+    })
+}
 int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }
 int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
                              double *explained, double *scale, int *rank) {

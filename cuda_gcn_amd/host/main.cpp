@@ -111,6 +111,10 @@
 //                            `clusters=<k> cluster_iters=<n> cluster_inertia=<x> cluster_nmi=<a> cluster_ari=<b> cluster_purity=<c>`,
 //                            the last three of the TEST split's nodes against their labels (host/kmeans.h).  The file gets one
 //                            line per node in id order: `node cluster dist2` (%.9g).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
+//   GCN_CLUSTER_SILHOUETTE=<file>  with GCN_CLUSTER (refused without it): the silhouette widths of that clustering over every
+//                            node (ModelQueries::silhouette, kernels in csrc/silhouette.hip).  One further line is printed:
+//                            `silhouette=<score> silhouette_min_cluster=<lowest cluster mean> silhouette_negative=<share of
+//                            points with s < 0>`.  The file gets one line per node in id order: `node cluster s neighbor` (%.9g).
 // Label structure (beyond the reference; ModelQueries::structure, kernels in csrc/structure.hip, measures in host/structure.h),
 // after the test line and the steps above.  One GPU, a single-label model with at most 64 classes:
 //   GCN_STRUCTURE=<file>     homophily of the graph and of the model's predictions over the nodes of the TEST split, and the
@@ -400,6 +404,12 @@ int main(int argc, char **argv) {
             std::cerr << "gcn-hip: GCN_CLUSTER " << why << std::endl;
             return EXIT_FAILURE;
         }
+    }
+    const char *silhouette_path = getenv("GCN_CLUSTER_SILHOUETTE");
+    if (silhouette_path && !*silhouette_path) silhouette_path = nullptr;
+    if (silhouette_path && !cluster_path) {
+        std::cerr << "gcn-hip: GCN_CLUSTER_SILHOUETTE needs GCN_CLUSTER (it measures the clustering that makes)" << std::endl;
+        return EXIT_FAILURE;
     }
 
     const char *pca_path = getenv("GCN_PCA");
@@ -772,6 +782,27 @@ int main(int argc, char **argv) {
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the clusters to ") + cluster_path);
                 fprintf(stderr, "gcn-hip: %d clusters of %d nodes (%d iterations%s, seed %llu) written to %s\n", K, N, r.iters_run,
                         r.converged ? ", converged" : "", (unsigned long long)r.seed, cluster_path);
+                if (silhouette_path) {                         // the clustering just made, over every node
+                    std::vector<double> s((size_t)std::max(N, 1)), cmean((size_t)K);
+                    std::vector<int32_t> nb((size_t)std::max(N, 1)), sizes((size_t)K);
+                    const ModelQueries::Silhouette sr = gcn.queries().silhouette(0, nullptr, N, assign.data(), N, K, true, 0, s.data(), nullptr, nullptr,
+                                                                                 nb.data(), cmean.data(), sizes.data());
+                    double lowest = 0.0;
+                    bool any = false;
+                    for (int c = 0; c < K; c++)
+                        if (sizes[c] > 0 && (!any || cmean[c] < lowest)) { lowest = cmean[c]; any = true; }
+                    int64_t negative = 0;
+                    for (int i = 0; i < N; i++) negative += s[i] < 0.0;
+                    printf("silhouette=%.9g silhouette_min_cluster=%.9g silhouette_negative=%.6f\n", sr.score, lowest,
+                           sr.points > 0 ? (double)negative / (double)sr.points : 0.0);
+                    FILE *g = fopen(silhouette_path, "w");
+                    bool good = g != nullptr;
+                    for (int i = 0; good && i < N; i++) good = fprintf(g, "%d %d %.9g %d\n", i, assign[i], s[i], nb[i]) > 0;
+                    if (g && fclose(g) != 0) good = false;
+                    if (!good) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the silhouette widths to ") + silhouette_path);
+                    fprintf(stderr, "gcn-hip: the silhouette widths of %lld points in %d clusters written to %s\n", (long long)sr.points, sr.nonempty,
+                            silhouette_path);
+                }
             }
             if (structure_path) {                              // one rank (checked above): the test split
                 const int C = params.output_dim;

@@ -321,6 +321,32 @@ public:
                   const uint64_t *seed, size_t scratch_bytes, int32_t *assign, float *dist2, float *centers, int32_t *sizes, int32_t *seed_pos,
                   double *history, int64_t *contingency);
 
+    // Silhouette widths of a labelling of the hidden layer (Rousseeuw, 1987; csrc/silhouette.hip has the definitions and the order
+    // of the sums; host/silhouette_query.cpp the body): how well every listed node sits in its group compared with the next-best
+    // group, in the Euclidean geometry of the rows embed() exports.  Rows as kmeans lists them: the nodes of `split` (1..3) in
+    // ascending dataset id, or with split == 0 the `nodes` query (dataset ids in the order given, a repeat is a point of its own;
+    // NULL: every node in id order).  labels [n_labels] by LIST POSITION — what kmeans() returns as assign for the same arguments —
+    // a label outside [0, k) takes its position out of the points (s = a = b = NaN, neighbor = -1, counted in `excluded`).
+    // Steps: sync(); embed_forward (variable 3 rewritten, as by every forward; with `normalize` its inverse norms); the list and
+    // the labels up; one gcnhip_silhouette_sums with the scratch capped at scratch_bytes (0: SILHOUETTE_SCRATCH_DEFAULT; never
+    // below the plan's minimum — fewer bytes, more launches, the same bits); one gcnhip_silhouette_rows.  Outputs, each may be
+    // NULL: s / a / b (float64) and neighbor (int32) [rows] by list position, cluster_mean [k] (the mean of s over the points of a
+    // label, 0 for an empty one), sizes [k].  score = the mean of s over the points (0 without points).  Nothing is cached.
+    // predict()'s contract: the metrics ring, the current split, variable 6 and the captured epoch graph are untouched.  Refused
+    // with a message before any launch: more than one rank, bf16 tables, a hidden width above 256, k outside 1..256, a split
+    // outside 0..3, a node id outside the graph, labels of another length than the list.
+    struct Silhouette {
+        int64_t rows = 0, points = 0, excluded = 0;
+        int nonempty = 0;
+        bool defined = false;                                  // at least two non-empty labels
+        double score = 0;
+    };
+    static constexpr size_t SILHOUETTE_SCRATCH_DEFAULT = (size_t)256 << 20;
+    // the refusals alone, and the number of rows the query lists; touches no device state
+    int64_t silhouette_rows(int k, int split, const int *nodes, int n, const int32_t *labels, int64_t n_labels, std::vector<int> *rows = nullptr);
+    Silhouette silhouette(int split, const int *nodes, int n, const int32_t *labels, int64_t n_labels, int k, bool normalize, size_t scratch_bytes,
+                          double *s, double *a, double *b, int32_t *neighbor, double *cluster_mean, int32_t *sizes);
+
     // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
     // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
     // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
@@ -522,6 +548,11 @@ private:
     Scratch<double> d_km_inertia{&arena};
     Scratch<unsigned char> d_km_scratch{&arena};
     std::vector<int> kmeans_list(const char *what, int split, const int *nodes, int &n);
+    // silhouette: {rows | labels | neighbor [n] | sizes [k] | counts [3]}, the sums [n x k], {s | a | b [n] | cluster_sum [k] |
+    // total}, the sums' scratch
+    Scratch<int32_t> d_sil_int{&arena};
+    Scratch<double> d_sil_sums{&arena}, d_sil_out{&arena};
+    Scratch<unsigned char> d_sil_scratch{&arena};
     // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
     // a projection, its coordinates, the sums' scratch
     Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};

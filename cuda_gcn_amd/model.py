@@ -866,6 +866,49 @@ class HipGCNModel:
             out.update(cluster_report(cont))
         return out
 
+    # ---- silhouette widths of a clustering of the hidden layer: is this k a good one, which nodes sit badly, on the GPU
+    def silhouette(self, labels, k=None, split=None, nodes=None, normalize=True, per_node=True, scratch_bytes=0):
+        """Silhouette widths (Rousseeuw, 1987; scikit-learn's silhouette_samples, euclidean) of a labelling of the rows embed()
+        exports, computed where they lie: one evaluation forward, then for every listed row its summed distance to the points of
+        every label — an n x n x hidden product on the exact-f32 MFMA with a correctly rounded square root behind every entry,
+        added in float64 in an order fixed by the data: the same bits on every run and with every scratch size.  Rows: the nodes
+        of `split` in ascending id, or the `nodes` query (dataset ids in the order given, a repeat is a point of its own), or
+        with both None every node in id order.  labels: int [n] by LIST POSITION, exactly what cluster(split=..., nodes=...)
+        ["assign"] is for the same arguments; k: None = labels.max() + 1.  A label outside [0, k) takes its position out of the
+        points.  normalize=True measures unit rows, for the reason cluster() does (row_scale()).  Returns a dict: score (the mean
+        width over the points), cluster_mean float64 [k] (0 for an empty label), sizes int32 [k], points, excluded, defined (at
+        least two non-empty labels; otherwise every width is 0), and with per_node=True s, a, b float64 [n] (the width, the mean
+        distance inside the own label, the lowest mean distance to another label) and neighbor int32 [n] (that label, the
+        lowest on equal means; -1 when none); NaN / -1 at an excluded position.  scratch_bytes caps the device scratch of the
+        sums (0: 256 MiB; less: more launches, the same bits).  One rank, hidden width at most 256, f32 tables.  Training state
+        is not touched and nothing is cached."""
+        what = "silhouette"
+        q, n, cap = self._pca_query(what, split, nodes)
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or lab.ndim != 1:
+            raise GcnHostError(f"{what}: labels must be a one-dimensional integer array, got {lab.dtype} {lab.shape}")
+        if k is None:
+            k = int(lab.max()) + 1 if lab.size else 1
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 256:
+            raise GcnHostError(f"{what}: k must be an integer in 1..256, got {k!r}")
+        if split is None and lab.size != cap:
+            raise GcnHostError(f"{what}: the query lists {cap} rows, the labels are {lab.size}")
+        lab = np.ascontiguousarray(np.clip(lab, -1, 256), np.int32)
+        m = int(lab.size)
+        k = int(k)
+        lp = lab if m else np.zeros(1, np.int32)
+        s, a, b = (np.zeros(max(m, 1), np.float64) for _ in range(3)) if per_node else (None, None, None)
+        nb = np.zeros(max(m, 1), np.int32) if per_node else None
+        cmean, sizes, info, score = np.zeros(k, np.float64), np.zeros(k, np.int32), np.zeros(5, np.int64), C.c_double()
+        _ck(self.lib, self.lib.gcnhost_model_silhouette(
+            self.h, int(split or 0), q.ctypes.data if q is not None else None, n, lp.ctypes.data, k, int(bool(normalize)), int(scratch_bytes), m,
+            s.ctypes.data if per_node else None, a.ctypes.data if per_node else None, b.ctypes.data if per_node else None,
+            nb.ctypes.data if per_node else None, cmean.ctypes.data, sizes.ctypes.data, info.ctypes.data, C.byref(score)), what)
+        out = dict(score=score.value, cluster_mean=cmean, sizes=sizes, points=int(info[1]), excluded=int(info[2]), defined=bool(info[4]))
+        if per_node:
+            out.update(s=s[:m], a=a[:m], b=b[:m], neighbor=nb[:m])
+        return out
+
     # ---- principal components of the hidden layer: coordinates, spectrum and whitening, on the GPU
     def _pca_query(self, what, split, nodes):
         if self.params.hidden_dim > 256:
@@ -1416,6 +1459,24 @@ def cluster_report(contingency):
     out = {name: float(v) for name, v in zip(names, s)}
     out["rows"] = int(s[8])
     return out
+
+
+def read_silhouette(path):
+    """The file gcn-hip writes with GCN_CLUSTER_SILHOUETTE, one line `node cluster s neighbor` per node: a dict of node int32 [n],
+    cluster int32 [n], s float64 [n] (NaN for a node outside the points), neighbor int32 [n].  Needs no GPU."""
+    node, cluster, s, nb = [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) != 4:
+                    raise ValueError
+                node.append(int(p[0])), cluster.append(int(p[1])), s.append(float(p[2])), nb.append(int(p[3]))
+            except ValueError:
+                raise GcnHostError(f"read_silhouette: {path}:{no}: expected `node cluster s neighbor`, got {line.strip()!r}") from None
+    return dict(node=np.array(node, np.int32), cluster=np.array(cluster, np.int32), s=np.array(s, np.float64), neighbor=np.array(nb, np.int32))
 
 
 def sym_eigen(S):

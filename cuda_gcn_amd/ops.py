@@ -718,6 +718,58 @@ class Device:
             self._embed_fail("gcnhip_contingency_rows", rc)
         return cb.download()[:int(k) * int(num_classes)].reshape(int(k), int(num_classes)), int(kb.download()[0])
 
+    # ---- silhouette widths of a labelling of a table's rows (csrc/silhouette.hip)
+    def silhouette_plan(self, n, k, dim):
+        """gcnhip_silhouette_plan: dict(bytes, bytes_min) of device scratch for gcnhip_silhouette_sums"""
+        a, b = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_silhouette_plan(int(n), int(k), int(dim), C.byref(a), C.byref(b))
+        if rc != 0:
+            self._embed_fail("gcnhip_silhouette_plan", rc)
+        return dict(bytes=a.value, bytes_min=b.value)
+
+    def silhouette_sums(self, table, labels, k, rows=None, inv_norm=None, ld=None, scratch_bytes=None):
+        """gcnhip_silhouette_sums: (sums float64 [n, k], sizes int32 [k]) — sums[i, c] = the sum of the Euclidean distances from list
+        position i to the points of label c (the pair (i, i) left out by position); 0 in the row of a position that is no point.
+        scratch_bytes: the caller's scratch (None: gcnhip_silhouette_plan's bytes).  The outputs are uploaded as garbage."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        k = int(k)
+        lab = np.ascontiguousarray(labels, np.int32).ravel()
+        assert lab.size == n, (lab.size, n)
+        lb = self.buf(lab if n else np.zeros(1, np.int32))
+        sbytes = self.silhouette_plan(n, k, dim)["bytes"] if scratch_bytes is None else int(scratch_bytes)
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        ob = self.buf(np.full(max(n * max(k, 1), 1), np.nan, np.float64))
+        zb = self.buf(np.full(max(k, 1), -777, np.int32))
+        rc = self.lib.gcnhip_silhouette_sums(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, lb.ptr, k, ob.ptr,
+                                             zb.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_silhouette_sums", rc)
+        return ob.download()[:n * k].reshape(n, k), zb.download()[:k]
+
+    def silhouette_rows(self, sums, labels, sizes, n_table, rows=None):
+        """gcnhip_silhouette_rows: dict(s, a, b float64 [n], neighbor int32 [n], cluster_sum float64 [k], total, points, excluded,
+        nonempty) from the sums and sizes of silhouette_sums; NaN / -1 at a position that is no point."""
+        sums = np.ascontiguousarray(sums, np.float64)
+        n, k = sums.shape
+        rb, n_list = self._kmeans_rows(rows, int(n_table))
+        lab = np.ascontiguousarray(labels, np.int32).ravel()
+        assert lab.size == n == n_list, (lab.size, n, n_list)
+        ub = self.buf(sums.ravel() if sums.size else np.zeros(1, np.float64))
+        lb = self.buf(lab if n else np.zeros(1, np.int32))
+        zb = self.buf(np.ascontiguousarray(sizes, np.int32).ravel())
+        sb, ab, bb = (self.buf(np.full(max(n, 1), 7.5, np.float64)) for _ in range(3))
+        nbb = self.buf(np.full(max(n, 1), 12345, np.int32))
+        cb, tb = self.buf(np.full(k, np.nan, np.float64)), self.buf(np.full(1, np.nan, np.float64))
+        kb = self.buf(np.full(3, -777, np.int32))
+        rc = self.lib.gcnhip_silhouette_rows(self.ctx, ub.ptr, lb.ptr, zb.ptr, rb.ptr if rb else None, int(n_table), n, k, sb.ptr, ab.ptr, bb.ptr,
+                                             nbb.ptr, cb.ptr, tb.ptr, kb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_silhouette_rows", rc)
+        cnt = kb.download()
+        return dict(s=sb.download()[:n], a=ab.download()[:n], b=bb.download()[:n], neighbor=nbb.download()[:n], cluster_sum=cb.download()[:k],
+                    total=float(tb.download()[0]), points=int(cnt[0]), excluded=int(cnt[1]), nonempty=int(cnt[2]))
+
     # ---- principal components of the rows of a table (csrc/pca.hip): the table is uploaded with its row stride and NaN padding,
     # every output as garbage
     def pca_plan(self, n, dim):

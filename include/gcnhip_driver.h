@@ -413,6 +413,32 @@ int gcnhip_kmeans_seed(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        int n, int k, uint64_t stream_seed, float *centers, int ldm, int32_t *seed_pos, void *scratch, size_t scratch_bytes);
 int gcnhip_contingency_rows(gcnhip_ctx *ctx, const int32_t *assign, const int32_t *truth, int n_truth, const int32_t *d_rows, int n, int k,
                             int num_classes, int32_t *counts, int32_t *skipped);
+/* ---- silhouette widths of a labelling of a table's rows (silhouette.hip; beyond the reference: how well a grouping fits) ----
+ * The table contract and the row lists of the k-means calls.  labels: device int32 [n] by list position.  The POINTS are the
+ * positions with a label in [0, k), 1 <= k <= 256, and a row in the table; two positions that name one row are two points.
+ * d(i, j) = sqrtf(max(0, (xn_i + xn_j) - 2 . dot_f32(x^_i, x^_j))) with x^ = x . inv_norm[r] rounded to f32 (inv_norm == NULL: x),
+ * xn = (sumsq_f32(T[r]) . inv_norm[r]) . inv_norm[r] as gcnhip_kmeans_assign forms it, the dot on the exact-f32 MFMA, sqrtf
+ * correctly rounded.  No launch allocates or synchronises, none uses a float atomic; every output's bits are a function of the
+ * arguments' contents alone (not of launch geometry, scratch size or batching); anything else returns -1 with a message.
+ * gcnhip_silhouette_plan: the bytes of device scratch gcnhip_silhouette_sums takes for every position in one batch (*bytes) and
+ *   the least it works with (*bytes_min: batches of 64 positions, more launches, the same bits); each may be NULL.  No GPU.
+ * gcnhip_silhouette_sums: sums [n x k] float64, sums[i . k + c] = S(i, c) = the sum of d(i, j) over the points j of label c, the
+ *   pair (i, i) left out by POSITION.  The members of a label are taken in ascending position, in segments of 512 members; inside
+ *   a segment in tiles of 64: of a tile, member m goes to partial (m mod 16) / 4, each partial a float64 chain in ascending m
+ *   that runs on through the segment's tiles; the segment's sum is (p0 + p1) + (p2 + p3); the segments of a label are added in
+ *   order from +0.  The row of a position that is no point is written as 0.  sizes [k] int32: the points of every label.
+ * gcnhip_silhouette_rows: row-local, from sums and sizes.  With A = labels[i]: a[i] = S(i, A) / (n_A - 1), 0 when n_A = 1;
+ *   b[i] = the least S(i, c) / n_c over c != A with n_c > 0, neighbor[i] that c, the lowest on equal means; s[i] = (b - a) /
+ *   max(a, b), 0 when n_A = 1 or max(a, b) = 0 — each ONE float64 expression.  Fewer than two non-empty labels: b = 0, s = 0,
+ *   neighbor = -1.  A position that is no point: s = a = b = NaN, neighbor = -1.  cluster_sum [k] and *total (device float64):
+ *   the sums of s over the points of a label and over all points; thread t of 256 adds positions t, t + 256, .. in order, then a
+ *   fixed tree.  counts (device int32 [3]) = {points, positions that are no point, non-empty labels}. */
+int gcnhip_silhouette_plan(int n, int k, int dim, size_t *bytes, size_t *bytes_min);
+int gcnhip_silhouette_sums(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
+                           int n, const int32_t *labels, int k, double *sums, int32_t *sizes, void *scratch, size_t scratch_bytes);
+int gcnhip_silhouette_rows(gcnhip_ctx *ctx, const double *sums, const int32_t *labels, const int32_t *sizes, const int32_t *d_rows,
+                           int n_table, int n, int k, double *s, double *a, double *b, int32_t *neighbor, double *cluster_sum,
+                           double *total, int32_t *counts);
 /* ---- principal components of the rows of a table (pca.hip; beyond the reference: the coordinates of what a GCN learns) ----
  * The table contract and the row lists of the k-means calls: a list position whose row is outside the table is skipped and
  * leaves a NaN row in a projection.  x_i[a] = T[r][a] . inv_norm[r] rounded to f32 (inv_norm == NULL: T[r][a]).  No launch

@@ -383,6 +383,22 @@ int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, i
                          float *centers, int32_t *sizes, int32_t *seed_pos, double *history, int64_t *contingency, int64_t *info, double *inertia,
                          uint64_t *seed_used);
 int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary);
+/* Silhouette widths of a labelling of the hidden layer (ModelQueries::silhouette, host/queries.h; kernels and definitions in
+ * csrc/silhouette.hip): for every listed row a = its mean Euclidean distance to the other points of its label, b = the lowest
+ * mean distance to the points of another label, neighbor = that label, s = (b - a) / max(a, b).  Rows as for
+ * gcnhost_model_kmeans, a repeat being a point of its own.  labels: int32 by LIST POSITION (what gcnhost_model_kmeans writes as
+ * assign for the same arguments); `capacity` is their number and the length the per-row outputs are laid out for: it must
+ * equal the rows listed.  A label outside [0, k) takes its position out: s = a = b = NaN, neighbor = -1.  normalize as for
+ * gcnhost_model_kmeans.  scratch_bytes: the cap on the sums' device scratch (0: 256 MiB; less: more launches, the same bits).
+ * Outputs, each may be NULL: s / a / b float64 [capacity], neighbor int32 [capacity], cluster_mean float64 [k] (0 for an empty
+ * label), sizes int32 [k], info [5] = {rows listed, points, excluded, non-empty labels, defined (at least two of them)},
+ * *score = the mean of s over the points.  With fewer than two non-empty labels every s is 0 and every neighbor -1; nothing is
+ * NaN or inf for a point.  embed's contract: training state is not touched, nothing is cached.  Refused with a message before
+ * any launch: several ranks, bf16 tables, a hidden width above 256, k outside 1..256, a bad split or node id, labels of
+ * another length than the list. */
+int gcnhost_model_silhouette(gcnhost_model *m, int split, const int *nodes, int n, const int32_t *labels, int k, int normalize, size_t scratch_bytes,
+                             int64_t capacity, double *s, double *a, double *b, int32_t *neighbor, double *cluster_mean, int32_t *sizes,
+                             int64_t *info, double *score);
 /* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
  * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
  * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
