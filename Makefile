@@ -23,6 +23,9 @@ $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(wildcard $(PKG)/csrc/*.h) $(wildcard include/
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# tsne.hip's f32 entry arithmetic is kept off the packed-f32 instructions
+$(OBJDIR)/tsne.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(LIBDIR)/libgcnhip.so: $(KOBJ)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(KOBJ) -o $@

@@ -136,6 +136,11 @@ GCNHIP_SYMBOLS = {
     "gcnhip_silhouette_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_silhouette_sums": (I, [P, P, I, I, I, P, P, I, P, I, P, P, P, C.c_size_t]),
     "gcnhip_silhouette_rows": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P, P]),
+    "gcnhip_tsne_plan": (I, [I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_tsne_pack": (I, [P, P, I, I, I, P, P, I, P, C.c_size_t, P]),
+    "gcnhip_tsne_bandwidths": (I, [P, P, I, I, I, C.c_double, P, P, P, P, P, C.c_size_t]),
+    "gcnhip_tsne_gradient": (I, [P, P, I, I, P, I, I, P, P, C.c_size_t]),
+    "gcnhip_tsne_update": (I, [P, P, I, I, I, P, C.c_double, C.c_double, C.c_double, I, P, P, P, P]),
     "gcnhip_pca_plan": (I, [I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_pca_mean": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
     "gcnhip_pca_scatter": (I, [P, P, I, I, I, P, P, I, P, P, P, C.c_size_t]),
@@ -282,6 +287,7 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
     "gcnhost_model_silhouette": (I, [P, I, P, I, P, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),
+    "gcnhost_model_tsne": (I, [P, I, I, P, I, P, I, C.c_double, I, C.c_double, I, C.c_double, I, P, I, C.c_size_t, I64, P, P, P, P, P]),
     "gcnhost_sym_eigen": (I, [P, I, P, P]),
     "gcnhost_pca_from_scatter": (I, [P, P, I64, I, I, I, P, P, P, P, C.POINTER(I)]),
     "gcnhost_model_pca_fit": (I, [P, I, I, P, I, I, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),

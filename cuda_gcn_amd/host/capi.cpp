@@ -370,6 +370,22 @@ int gcnhost_model_silhouette(gcnhost_model *m, int split, const int *nodes, int 
         if (score) *score = r.score;
     })
 }
+int gcnhost_model_tsne(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, double perplexity, int iters,
+                       double exaggeration, int exaggeration_iters, double learning_rate, int normalize, const double *init, int kl_every,
+                       size_t scratch_bytes, int64_t capacity, float *coords, double *beta, double *history, int64_t *info, double *result) {
+    if (!m) { g_err = "gcnhost_model_tsne: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.tsne_rows(k, split, nodes, n, data, data_dim, iters);
+        if (listed != capacity)
+            throw GcnHipFailure(-1, "tsne: the query lists " + std::to_string(listed) + " rows, the start and the outputs are laid out for " +
+                                        std::to_string(capacity));
+        const ModelQueries::Tsne r = q.tsne(k, split, nodes, n, data, data_dim, perplexity, iters, exaggeration, exaggeration_iters, learning_rate,
+                                            normalize != 0, init, kl_every, scratch_bytes, coords, beta, history);
+        if (info) { info[0] = r.rows; info[1] = r.points; info[2] = r.unconverged; info[3] = r.history_rows; }
+        if (result) { result[0] = r.kl; result[1] = r.learning_rate; }
+    })
+}
 int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }
 int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
                              double *explained, double *scale, int *rank) {

@@ -148,6 +148,14 @@
 //                            `pca_components=<k> pca_rows=<n> pca_rank=<r> pca_explained_variance_ratio=<a>,<b>,...` (k values,
 //                            %.6f).  The file gets one line per node in id order: `node y1 ... yk` (%.9g).  Works with
 //                            GCN_LOAD_WEIGHTS and 0 epochs.
+// The t-SNE map (beyond the reference; ModelQueries::tsne, kernels in csrc/tsne.hip), after the principal components.  One GPU,
+// hidden_dim at most 256, f32 tables:
+//   GCN_TSNE=<file>          exact t-SNE in two dimensions of the unit rows of the hidden layer of the TEST nodes, from the start
+//                            pca gives (its first coordinate scaled to a standard deviation of 1e-4), with GCN_TSNE_PERPLEXITY
+//                            (default 30) and GCN_TSNE_ITERS iterations (default 1000), matrix-free on the GPU.  One line is
+//                            printed: `tsne_rows=<n> tsne_perplexity=<p> tsne_iters=<i> tsne_kl=<KL at the last gradient>
+//                            tsne_unconverged=<bandwidths not found>`.  The file gets one line per test node in id order:
+//                            `node y1 y2` (%.9g).
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -424,6 +432,24 @@ int main(int argc, char **argv) {
                                                                      : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_PCA " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *tsne_path = getenv("GCN_TSNE");
+    if (tsne_path && !*tsne_path) tsne_path = nullptr;
+    const int tsne_iters = env_int("GCN_TSNE_ITERS", 1000);
+    const double tsne_perplexity = getenv("GCN_TSNE_PERPLEXITY") ? atof(getenv("GCN_TSNE_PERPLEXITY")) : 30.0;
+    if (tsne_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1        ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256         ? "takes a hidden width of at most 256"
+                          : params.hidden_dim < 2           ? "takes a hidden width of at least 2 (its start is a two-dimensional pca)"
+                          : env_int("GCN_BF16_TABLES", 0)   ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : tsne_iters < 1                  ? "needs GCN_TSNE_ITERS of at least 1"
+                          : !(tsne_perplexity >= 1.0)       ? "needs GCN_TSNE_PERPLEXITY of at least 1"
+                                                            : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_TSNE " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -938,6 +964,35 @@ int main(int argc, char **argv) {
                 if (f && fclose(f) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the principal coordinates to ") + pca_path);
                 fprintf(stderr, "gcn-hip: %d principal coordinates of %d nodes (rank %d of %d) written to %s\n", K, N, r.rank, h, pca_path);
+            }
+            if (tsne_path) {                                   // one rank (checked above): the test nodes in id order
+                ModelQueries &q = gcn.queries();
+                std::vector<int> local;
+                const int64_t n = q.tsne_rows(2, 3, nullptr, 0, nullptr, 0, tsne_iters, &local);
+                std::vector<int> ids;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) ids.push_back(i);
+                if (n < 1 || (int64_t)ids.size() != n) throw GcnHipFailure(-1, "gcn-hip: GCN_TSNE found no test nodes to map");
+                std::vector<float> pc((size_t)n * 2), y((size_t)n * 2);
+                q.pca_fit(2, 3, nullptr, 0, true, true, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pc.data());
+                double mean = 0.0, var = 0.0;
+                for (int64_t i = 0; i < n; i++) mean += (double)pc[2 * i];
+                mean /= (double)n;
+                for (int64_t i = 0; i < n; i++) var += ((double)pc[2 * i] - mean) * ((double)pc[2 * i] - mean);
+                const double sd = std::sqrt(var / (double)n);
+                const double f = (double)(float)(sd > 0.0 ? 1e-4 / sd : 1.0);    // an f32 factor, as model.py's tsne() forms it
+                std::vector<double> y0((size_t)n * 2);
+                for (size_t e = 0; e < y0.size(); e++) y0[e] = (double)pc[e] * f;
+                const ModelQueries::Tsne r =
+                    q.tsne(2, 3, nullptr, 0, nullptr, 0, tsne_perplexity, tsne_iters, 12.0, 250, -1.0, true, y0.data(), 50, 0, y.data(), nullptr, nullptr);
+                printf("tsne_rows=%lld tsne_perplexity=%.9g tsne_iters=%d tsne_kl=%.9g tsne_unconverged=%lld\n", (long long)r.rows, tsne_perplexity,
+                       tsne_iters, r.kl, (long long)r.unconverged);
+                FILE *f2 = fopen(tsne_path, "w");
+                bool ok = f2 != nullptr;
+                for (int64_t i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %.9g %.9g\n", ids[(size_t)i], y[2 * i], y[2 * i + 1]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the t-SNE map to ") + tsne_path);
+                fprintf(stderr, "gcn-hip: the t-SNE map of %lld test nodes written to %s\n", (long long)n, tsne_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

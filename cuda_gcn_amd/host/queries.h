@@ -347,6 +347,27 @@ public:
     Silhouette silhouette(int split, const int *nodes, int n, const int32_t *labels, int64_t n_labels, int k, bool normalize, size_t scratch_bytes,
                           double *s, double *a, double *b, int32_t *neighbor, double *cluster_mean, int32_t *sizes);
 
+    // Exact t-SNE map of the hidden layer (van der Maaten & Hinton, 2008; include/gcnhip_driver.h has the definitions, csrc/tsne.hip
+    // the kernels, host/tsne_query.cpp the body).  Rows as kmeans lists them, a repeat being a point of its own; or with `data`
+    // (f32 [n x data_dim], data_dim <= 256, split == 0 and nodes == NULL) those rows instead of the embeddings.  Steps: sync();
+    // embed_forward; gcnhip_tsne_pack; gcnhip_tsne_bandwidths; `iters` times {gcnhip_tsne_gradient, gcnhip_tsne_update} with
+    // momentum 0.5 and `exaggeration` for the first exaggeration_iters iterations, then 0.8 and 1, no readback inside the loop; KL
+    // and the gradient norm of iterations kl_every - 1, 2 kl_every - 1, .. and of the last land in a device history read once at
+    // the end.  init [rows x k] float64 is the start.  learning_rate <= 0: max(points / exaggeration / 4, 50).  Outputs, each may
+    // be NULL: coords f32 [rows x k] by list position (NaN where the position is no point), beta float64 [rows], history [(iters /
+    // kl_every + 1) x 3] = (iteration, KL, gradient norm).  Training state is untouched and nothing is cached.  Refused with a
+    // message before any launch: more than one rank, bf16 tables, a width above 256, k other than 2 or 3, a bad split or node id,
+    // iters < 1; after the pack: a perplexity outside [1, points - 1).
+    struct Tsne {
+        int64_t rows = 0, points = 0, unconverged = 0, history_rows = 0;
+        double kl = 0, learning_rate = 0;
+    };
+    static constexpr size_t TSNE_SCRATCH_DEFAULT = (size_t)256 << 20;
+    int64_t tsne_rows(int k, int split, const int *nodes, int n, const float *data, int data_dim, int iters, std::vector<int> *rows = nullptr);
+    Tsne tsne(int k, int split, const int *nodes, int n, const float *data, int data_dim, double perplexity, int iters, double exaggeration,
+              int exaggeration_iters, double learning_rate, bool normalize, const double *init, int kl_every, size_t scratch_bytes, float *coords,
+              double *beta, double *history);
+
     // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
     // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
     // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
@@ -553,6 +574,12 @@ private:
     Scratch<int32_t> d_sil_int{&arena};
     Scratch<double> d_sil_sums{&arena}, d_sil_out{&arena};
     Scratch<unsigned char> d_sil_scratch{&arena};
+    // tsne: the listed rows (or the caller's table), {points | unconverged}, the pack, the scratch, {state [3 n k] | rowsums [9 n] |
+    // beta, 1 / Z [n] | history}, {y [n k] | m [n]}
+    Scratch<int32_t> d_ts_rows{&arena}, d_ts_count{&arena};
+    Scratch<unsigned char> d_ts_pack{&arena}, d_ts_scratch{&arena};
+    Scratch<double> d_ts_f64{&arena};
+    Scratch<float> d_ts_f32{&arena}, d_ts_data{&arena};
     // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
     // a projection, its coordinates, the sums' scratch
     Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};

@@ -958,6 +958,65 @@ class HipGCNModel:
             out["scatter"] = scat
         return out
 
+    # ---- the t-SNE map of the hidden layer: the standard picture of a trained GCN, on the GPU
+    def tsne(self, k=2, split=None, nodes=None, perplexity=30.0, iters=1000, exaggeration=12.0, exaggeration_iters=250, learning_rate="auto",
+             init="pca", normalize=True, data=None, kl_every=50, scratch_bytes=0):
+        """Exact t-SNE (van der Maaten & Hinton, 2008; scikit-learn's TSNE(method="exact") rules) of the rows embed() exports, run
+        where they lie and matrix-free: one evaluation forward, the rows packed once, every row's bandwidth searched in float64, then
+        `iters` iterations each of which recomputes every high-dimensional distance on the exact-f32 MFMA and turns it into p_ij in
+        registers — P is never stored, float64 sums in an order fixed by the data, the same bits on every run and with every
+        scratch size, no readback inside the loop.  Rows: the nodes of `split` in ascending id, or the `nodes` query (a repeat is a
+        point of its own), or with both None every node in id order.  k is 2 or 3.  init: "pca" (the first k coordinates of pca()
+        of the same rows, scaled so that the first has a standard deviation of 1e-4) or a float [n, k] array.  data: any float [n,
+        d <= 256] array mapped instead of the embeddings, for instance pca(k=50)["coords"].  learning_rate "auto" is max(points /
+        exaggeration / 4, 50); momentum is 0.5 and the exaggeration `exaggeration` for the first exaggeration_iters iterations,
+        then 0.8 and 1.  Returns a dict: coords f32 [n, k] by list position, kl (at the last gradient), history float64 [rows, 3] =
+        (iteration, kl, grad_norm) every kl_every iterations and at the last, beta float64 [n], unconverged, points,
+        learning_rate.  One rank, f32 tables, width at most 256.  Training state is not touched and nothing is cached."""
+        what = "tsne"
+        if isinstance(k, bool) or k not in (2, 3):
+            raise GcnHostError(f"{what}: k must be 2 or 3, got {k!r}")
+        if isinstance(iters, bool) or int(iters) != iters or iters < 1:
+            raise GcnHostError(f"{what}: iters must be an integer >= 1, got {iters!r}")
+        k, iters, kl_every = int(k), int(iters), max(int(kl_every), 1)
+        if data is not None:
+            if split is not None or nodes is not None:
+                raise GcnHostError(f"{what}: with data the rows are the data's: no split and no node query")
+            d = np.ascontiguousarray(data, np.float32)
+            if d.ndim != 2 or not 1 <= d.shape[1] <= 256 or d.shape[0] < 1:
+                raise GcnHostError(f"{what}: data must be a float [n, d <= 256] array, got shape {d.shape}")
+            q, n, cap = None, int(d.shape[0]), int(d.shape[0])
+        else:
+            d = None
+            q, n, cap = self._pca_query(what, split, nodes)
+        if isinstance(init, str):
+            if init != "pca":
+                raise GcnHostError(f"{what}: init is 'pca' or a float [n, k] array, got {init!r}")
+            if d is None:
+                y0 = self.pca(k=k, split=split, nodes=nodes, normalize=normalize)["coords"].astype(np.float64)
+            else:
+                c = d.astype(np.float64) - d.astype(np.float64).mean(axis=0)
+                y0 = c @ np.linalg.svd(c, full_matrices=False)[2][:k].T if d.shape[1] >= k else np.pad(c, ((0, 0), (0, k - d.shape[1])))
+            sd = np.nanstd(y0[:, 0])
+            y0 = y0 * float(np.float32(1e-4 / sd if sd > 0 else 1.0))      # an f32 factor: the command line forms the same start
+        else:
+            y0 = np.asarray(init, np.float64)
+        if split is not None and y0.ndim == 2:
+            cap = y0.shape[0]                                     # the library checks it against the split's rows
+        if y0.shape != (cap, k):
+            raise GcnHostError(f"{what}: the start must have shape ({cap}, {k}), got {y0.shape}")
+        y0 = np.ascontiguousarray(y0, np.float64)
+        lr = -1.0 if learning_rate == "auto" else float(learning_rate)
+        coords, beta = np.zeros((cap, k), np.float32), np.zeros(cap, np.float64)
+        hist, info, res = np.zeros((iters // kl_every + 1, 3), np.float64), np.zeros(4, np.int64), np.zeros(2, np.float64)
+        _ck(self.lib, self.lib.gcnhost_model_tsne(
+            self.h, k, int(split or 0), q.ctypes.data if q is not None else None, n, d.ctypes.data if d is not None else None,
+            int(d.shape[1]) if d is not None else 0, float(perplexity), iters, float(exaggeration), int(exaggeration_iters), lr, int(bool(normalize)),
+            y0.ctypes.data, kl_every, int(scratch_bytes), cap, coords.ctypes.data, beta.ctypes.data, hist.ctypes.data, info.ctypes.data,
+            res.ctypes.data), what)
+        return dict(coords=coords, kl=float(res[0]), history=hist[:int(info[3])].copy(), beta=beta, unconverged=int(info[2]), points=int(info[1]),
+                    learning_rate=float(res[1]))
+
     def pca_transform(self, fit, nodes=None):
         """f32 [n, k] — the listed nodes (None: every node in id order) projected with a fit pca() returned, at the CURRENT
         weights: one evaluation forward and one projection launch on the GPU; nothing is cached.  A fit on the training split
@@ -1477,6 +1536,24 @@ def read_silhouette(path):
             except ValueError:
                 raise GcnHostError(f"read_silhouette: {path}:{no}: expected `node cluster s neighbor`, got {line.strip()!r}") from None
     return dict(node=np.array(node, np.int32), cluster=np.array(cluster, np.int32), s=np.array(s, np.float64), neighbor=np.array(nb, np.int32))
+
+
+def read_tsne(path):
+    """The file gcn-hip writes with GCN_TSNE, one line `node y1 .. yk` per mapped node: a dict of node int32 [n] and coords float64
+    [n, k].  Needs no GPU."""
+    node, rows = [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) not in (3, 4) or (rows and len(p) - 1 != len(rows[0])):
+                    raise ValueError
+                node.append(int(p[0])), rows.append([float(v) for v in p[1:]])
+            except ValueError:
+                raise GcnHostError(f"read_tsne: {path}:{no}: expected `node y1 .. yk` with k = 2 or 3, got {line.strip()!r}") from None
+    return dict(node=np.array(node, np.int32), coords=np.array(rows, np.float64).reshape(len(rows), -1))
 
 
 def sym_eigen(S):

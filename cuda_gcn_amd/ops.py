@@ -770,6 +770,100 @@ class Device:
         return dict(s=sb.download()[:n], a=ab.download()[:n], b=bb.download()[:n], neighbor=nbb.download()[:n], cluster_sum=cb.download()[:k],
                     total=float(tb.download()[0]), points=int(cnt[0]), excluded=int(cnt[1]), nonempty=int(cnt[2]))
 
+    # ---- exact t-SNE of a table's rows (csrc/tsne.hip): every buffer is uploaded as garbage
+    def tsne_plan(self, n, dim):
+        """gcnhip_tsne_plan: dict(pack_bytes, bytes, bytes_min) — the packed image and the device scratch of the bandwidth and
+        gradient calls"""
+        p, a, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_tsne_plan(int(n), int(dim), C.byref(p), C.byref(a), C.byref(b))
+        if rc != 0:
+            self._embed_fail("gcnhip_tsne_plan", rc)
+        return dict(pack_bytes=p.value, bytes=a.value, bytes_min=b.value)
+
+    def tsne_pack(self, table, rows=None, inv_norm=None, ld=None, scratch_bytes=None):
+        """gcnhip_tsne_pack: the pack of the listed rows (None: every row) as a dict the other tsne calls take: pack and scratch
+        buffers, n, dim, points.  scratch_bytes: the caller's scratch for the later calls (None: gcnhip_tsne_plan's bytes)."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        plan = self.tsne_plan(n, dim)
+        sbytes = plan["bytes"] if scratch_bytes is None else int(scratch_bytes)
+        pb = self.buf(np.full(plan["pack_bytes"] // 4, 0x7fc12345, np.uint32))
+        cb = self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_tsne_pack(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, pb.ptr, plan["pack_bytes"],
+                                       cb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_tsne_pack", rc)
+        return dict(pack=pb, n=n, dim=dim, points=int(cb.download()[0]), scratch=self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32)),
+                    scratch_bytes=sbytes)
+
+    def tsne_bandwidths(self, pk, perplexity):
+        """gcnhip_tsne_bandwidths on a pack: dict(beta float64 [n], m f32 [n], inv_z float64 [n], unconverged); NaN where the
+        position is no point.  The pack gets the f32 copies the gradient reads."""
+        n = pk["n"]
+        bb, zb = self.buf(np.full(n, 7.5, np.float64)), self.buf(np.full(n, 7.5, np.float64))
+        mb, ub = self.buf(np.full(n, 7.5, np.float32)), self.buf(np.full(1, -777, np.int32))
+        rc = self.lib.gcnhip_tsne_bandwidths(self.ctx, pk["pack"].ptr, n, pk["dim"], pk["points"], float(perplexity), bb.ptr, mb.ptr, zb.ptr, ub.ptr,
+                                             pk["scratch"].ptr, pk["scratch_bytes"])
+        if rc != 0:
+            self._embed_fail("gcnhip_tsne_bandwidths", rc)
+        return dict(beta=bb.download(), m=mb.download(), inv_z=zb.download(), unconverged=int(ub.download()[0]))
+
+    def _tsne_y(self, pk, y):
+        y = np.ascontiguousarray(y, np.float64)
+        if y.ndim != 2 or y.shape[0] != pk["n"]:
+            raise GcnHipError(f"tsne: the start must be [{pk['n']}, k], got {y.shape}")
+        return y, int(y.shape[1])
+
+    def tsne_gradient(self, pk, y, exaggeration=1.0, want_kl=True):
+        """one evaluation at y [n, k] on a pack that has its bandwidths (gcnhip_tsne_gradient, then gcnhip_tsne_update without the
+        update): dict(grad float64 [n, k], zq, kl, grad_norm).  The kernels see y rounded to f32."""
+        y, k = self._tsne_y(pk, y)
+        n = pk["n"]
+        yb = self.buf(y.astype(np.float32))
+        sb = self.buf(np.full(n * 9, np.nan, np.float64))
+        rc = self.lib.gcnhip_tsne_gradient(self.ctx, pk["pack"].ptr, n, pk["dim"], yb.ptr, k, int(bool(want_kl)), sb.ptr, pk["scratch"].ptr,
+                                           pk["scratch_bytes"])
+        if rc != 0:
+            self._embed_fail("gcnhip_tsne_gradient", rc)
+        gb, tb = self.buf(np.full(n * k, 7.5, np.float64)), self.buf(np.full(3, np.nan, np.float64))
+        rc = self.lib.gcnhip_tsne_update(self.ctx, pk["pack"].ptr, n, pk["dim"], k, sb.ptr, float(exaggeration), 0.0, 0.0, 0, None, None, gb.ptr, tb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_tsne_update", rc)
+        st = tb.download()
+        return dict(grad=gb.download().reshape(n, k), zq=float(st[2]), kl=float(st[0]), grad_norm=float(st[1]))
+
+    def tsne_run(self, table, init, perplexity=30.0, iters=1000, exaggeration=12.0, exaggeration_iters=250, learning_rate="auto", kl_every=50, rows=None,
+                 inv_norm=None, ld=None, scratch_bytes=None):
+        """exact t-SNE of the listed rows from the start init [n, k]: pack, bandwidths, then `iters` times gradient and update with
+        nothing read back in between.  dict(coords f32 [n, k], kl, history [rows, 3] = (iteration, kl, grad_norm) of iterations
+        kl_every - 1, 2 kl_every - 1, .. and the last, beta, unconverged, points, learning_rate)."""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=scratch_bytes)
+        bw = self.tsne_bandwidths(pk, perplexity)
+        y, k = self._tsne_y(pk, init)
+        n, iters, kl_every = pk["n"], int(iters), max(int(kl_every), 1)
+        lr = max(pk["points"] / float(exaggeration) / 4.0, 50.0) if learning_rate == "auto" else float(learning_rate)
+        state = self.buf(np.concatenate([y.ravel(), np.zeros(n * k), np.ones(n * k)]))
+        yb = self.buf(y.astype(np.float32))
+        sb = self.buf(np.full(n * 9, np.nan, np.float64))
+        hb = self.buf(np.full((iters // kl_every + 1) * 3, np.nan, np.float64))
+        its = []
+        for it in range(iters):
+            early, record = it < exaggeration_iters, (it + 1) % kl_every == 0 or it == iters - 1
+            rc = self.lib.gcnhip_tsne_gradient(self.ctx, pk["pack"].ptr, n, pk["dim"], yb.ptr, k, int(record), sb.ptr, pk["scratch"].ptr,
+                                               pk["scratch_bytes"])
+            if rc != 0:
+                self._embed_fail("gcnhip_tsne_gradient", rc)
+            rc = self.lib.gcnhip_tsne_update(self.ctx, pk["pack"].ptr, n, pk["dim"], k, sb.ptr, float(exaggeration) if early else 1.0,
+                                             0.5 if early else 0.8, lr, 1, state.ptr, yb.ptr, None, hb.ptr + 24 * len(its) if record else None)
+            if rc != 0:
+                self._embed_fail("gcnhip_tsne_update", rc)
+            if record:
+                its.append(it)
+        h = hb.download().reshape(-1, 3)[:len(its)]
+        hist = np.column_stack([np.asarray(its, np.float64), h[:, 0], h[:, 1]])
+        return dict(coords=yb.download().reshape(n, k), kl=float(hist[-1, 1]), history=hist, beta=bw["beta"], unconverged=bw["unconverged"],
+                    points=pk["points"], learning_rate=lr)
+
     # ---- principal components of the rows of a table (csrc/pca.hip): the table is uploaded with its row stride and NaN padding,
     # every output as garbage
     def pca_plan(self, n, dim):

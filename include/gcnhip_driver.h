@@ -439,6 +439,48 @@ int gcnhip_silhouette_sums(gcnhip_ctx *ctx, const float *table, int ld, int n_ta
 int gcnhip_silhouette_rows(gcnhip_ctx *ctx, const double *sums, const int32_t *labels, const int32_t *sizes, const int32_t *d_rows,
                            int n_table, int n, int k, double *s, double *a, double *b, int32_t *neighbor, double *cluster_sum,
                            double *total, int32_t *counts);
+/* ---- exact t-SNE of a table's rows (tsne.hip; beyond the reference: the map of what a GCN learns; van der Maaten & Hinton, 2008,
+ * scikit-learn's TSNE(method="exact") rules), matrix-free: P is never stored, n is bounded by time and not by an n^2 buffer ----
+ * Table, row list, scaling and points are gcnhip_silhouette_sums': f32 [n_table x ld], 1 <= dim <= 256; d_rows or NULL; inv_norm
+ *   or NULL; two positions that name one row are two points; a position without a row in the table is no point, its outputs NaN.
+ * d2(i, j) = max(0, (xn_i + xn_j) - 2 . dot_f32(x^_i, x^_j)): silhouette's d without the square root.  The self pair is left out by
+ *   POSITION.  m_i = the least d2(i, j) over the points j != i.
+ * e_i(j) = exp(-beta_i (d2(i, j) - m_i)), Z_i = sum_j e_i(j); beta_i is where H_i = ln Z_i + beta_i sum_j (d2 - m_i) e_i(j) / Z_i
+ *   equals ln(perplexity), searched as scikit-learn does: from 1, doubled or halved until bracketed, then bisected, at most 100
+ *   evaluations, stopped at |H - ln perplexity| <= 1e-5; in float64 on the f32 d2, with the float64 exp.  A row that never gets
+ *   there keeps the last beta that was evaluated (and its Z) and is counted in *unconverged.  Subtracting m_i keeps an outlier's Z
+ *   from underflowing: part of the definition.
+ * p_ij = (e_i(j) / Z_i + e_j(i) / Z_j) / (2 n_points), formed in f32 from the f32 copies of beta, m and 1 / Z, two expf per pair.
+ * Low side: k is 2 or 3; w_ij = 1 / (1 + |y_i - y_j|^2) in f32; Zq = sum_{i != j} w_ij.
+ * grad_i = 4 (exaggeration . sum_j p_ij w_ij (y_i - y_j) - (sum_j w_ij^2 (y_i - y_j)) / Zq);  KL = sum p_ij ln(p_ij Zq / w_ij) over
+ *   the pairs with p_ij > 0, at exaggeration 1 whatever the gradient's is.
+ * Update, per coordinate (scikit-learn's): gain + 0.2 where update . grad < 0, otherwise gain . 0.8, at least 0.01; update =
+ *   momentum . update - learning_rate . gain . grad; y += update.  The caller picks momentum and exaggeration per iteration (0.5
+ *   and 12 for the first 250, then 0.8 and 1) and the iteration count; nothing reads back inside the loop.
+ * Order: the columns of a row are cut into parts of 2048 positions; inside a part, column j goes to float64 chain (j mod 16) / 4
+ *   in ascending j; a part's sum is (c0 + c1) + (c2 + c3); a row's parts are added in order from +0; sums over positions: thread t
+ *   of 256 adds positions t, t + 256, .. and then a fixed tree.  No launch allocates or synchronises, none uses a float atomic;
+ *   every output's bits are a function of the arguments' contents alone; anything else returns -1 with a message.
+ * gcnhip_tsne_plan: *pack_bytes of the packed image, *bytes of scratch for every row in one batch and *bytes_min, the least
+ *   (batches of 64 rows, more launches, the same bits), for gcnhip_tsne_bandwidths and _gradient alike; each may be NULL.  No GPU.
+ * gcnhip_tsne_pack: the listed rows once into `pack` (contiguous, zero-padded x^, xn, which positions are points); *n_points
+ *   (device int32) = the points.
+ * gcnhip_tsne_bandwidths: beta, inv_z (float64 [n]) and m (f32 [n]) by position, their f32 copies into the pack, *unconverged
+ *   (device int32).  perplexity must be in [1, n_points - 1).  The [rows x n] d2 slab of a batch is formed on the MFMA in scratch.
+ * gcnhip_tsne_gradient: at y (f32 [n x k]) the row sums (float64 [n x 9]): {sum p w dy [3] | sum w^2 dy [3] | sum w | sum p
+ *   ln(p / w) | sum p}; the last two only with want_kl (a logarithm per pair), otherwise 0.  pack must have its bandwidths.
+ * gcnhip_tsne_update: from the row sums Zq, KL and the gradient; stats (device float64 [3], or NULL) = {KL, |grad|_2, Zq}; grad
+ *   (float64 [n x k], or NULL); with apply != 0 the update rule on state = {y | update | gain} (float64 [3][n x k]) and y = (float)
+ *   of the new state.  One launch. */
+int gcnhip_tsne_plan(int n, int dim, size_t *pack_bytes, size_t *bytes, size_t *bytes_min);
+int gcnhip_tsne_pack(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows, int n,
+                     void *pack, size_t pack_bytes, int32_t *n_points);
+int gcnhip_tsne_bandwidths(gcnhip_ctx *ctx, void *pack, int n, int dim, int n_points, double perplexity, double *beta, float *m,
+                           double *inv_z, int32_t *unconverged, void *scratch, size_t scratch_bytes);
+int gcnhip_tsne_gradient(gcnhip_ctx *ctx, const void *pack, int n, int dim, const float *y, int k, int want_kl, double *rowsums,
+                         void *scratch, size_t scratch_bytes);
+int gcnhip_tsne_update(gcnhip_ctx *ctx, const void *pack, int n, int dim, int k, const double *rowsums, double exaggeration,
+                       double momentum, double learning_rate, int apply, double *state, float *y, double *grad, double *stats);
 /* ---- principal components of the rows of a table (pca.hip; beyond the reference: the coordinates of what a GCN learns) ----
  * The table contract and the row lists of the k-means calls: a list position whose row is outside the table is skipped and
  * leaves a NaN row in a projection.  x_i[a] = T[r][a] . inv_norm[r] rounded to f32 (inv_norm == NULL: T[r][a]).  No launch

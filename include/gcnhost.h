@@ -399,6 +399,20 @@ int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double
 int gcnhost_model_silhouette(gcnhost_model *m, int split, const int *nodes, int n, const int32_t *labels, int k, int normalize, size_t scratch_bytes,
                              int64_t capacity, double *s, double *a, double *b, int32_t *neighbor, double *cluster_mean, int32_t *sizes,
                              int64_t *info, double *score);
+/* Exact t-SNE map of the hidden layer (ModelQueries::tsne, host/queries.h; definitions in include/gcnhip_driver.h, kernels in
+ * csrc/tsne.hip).  Rows as for gcnhost_model_kmeans, a repeat being a point of its own; with data (f32 [n x data_dim], data_dim
+ * <= 256, split 0, nodes NULL) those n rows instead of the embeddings.  k is 2 or 3.  init: float64 [capacity x k], the start;
+ * capacity must equal the rows listed.  learning_rate <= 0: max(points / exaggeration / 4, 50).  Momentum is 0.5 and the
+ * exaggeration `exaggeration` for the first exaggeration_iters iterations, then 0.8 and 1; the iteration count is fixed.
+ * scratch_bytes: the cap on the device scratch (0: 256 MiB; less: more launches, the same bits).  Outputs, each may be NULL:
+ * coords f32 [capacity x k] (NaN at a position that is no point), beta float64 [capacity], history float64 [(iters / kl_every + 1)
+ * x 3] = (iteration, KL, gradient norm) of iterations kl_every - 1, 2 kl_every - 1, .. and the last, info [4] = {rows listed,
+ * points, unconverged bandwidths, history rows}, result [2] = {KL at the last gradient, the learning rate used}.  embed's
+ * contract: training state is not touched, nothing is cached.  Refused with a message: several ranks, bf16 tables, a width above
+ * 256, k other than 2 or 3, a bad split or node id, iters < 1, a perplexity outside [1, points - 1). */
+int gcnhost_model_tsne(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, double perplexity, int iters,
+                       double exaggeration, int exaggeration_iters, double learning_rate, int normalize, const double *init, int kl_every,
+                       size_t scratch_bytes, int64_t capacity, float *coords, double *beta, double *history, int64_t *info, double *result);
 /* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
  * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
  * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
