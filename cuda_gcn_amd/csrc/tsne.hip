@@ -22,41 +22,17 @@
 // tsne_fold_kernel        a row's part partials in part order.  tsne_step_kernel: one workgroup, thread t of 256 adds positions t,
 //   t + 256, .. and then a fixed tree (Zq, KL, the gradient norm), and applies the update rule.
 #include "bucket.h"
+#include "tsne_pack.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int TS_MAX_DIM = 256;
-constexpr int TS_RT = 64;                         // list positions per row tile
 constexpr int TS_CT = 64;                         // positions per column tile
 constexpr int TS_PART = 2048;                     // positions per column part (part of the definition of the sums' order)
 constexpr int TS_NACC = 9;                        // {p w dy [3] | w^2 dy [3] | w | p ln(p / w) | p}
-constexpr int TS_HDR = 256;                       // bytes of the pack's header: int32 [0] = the points
 enum { TS_SLAB = 0, TS_GRAD = 1 };
-
-static int ts_dp(int dim) { return dim <= 16 ? 16 : dim <= 32 ? 32 : dim <= 64 ? 64 : dim <= 128 ? 128 : 256; }
-static int ts_npad(int n) { return std::max(ceil_div(n, TS_RT), 1) * TS_RT; }
-
-struct TsPack {
-    int32_t *hdr;
-    float *X;
-    float4 *S;
-    int32_t *valid;
-    size_t bytes;
-};
-static TsPack ts_pack(void *pack, int n, int dim) {
-    const size_t n_pad = (size_t)ts_npad(n), dp = (size_t)ts_dp(dim);
-    unsigned char *b = (unsigned char *)pack;
-    TsPack P;
-    P.hdr = (int32_t *)b;
-    P.X = (float *)(b + TS_HDR);
-    P.S = (float4 *)(b + TS_HDR + n_pad * dp * sizeof(float));
-    P.valid = (int32_t *)(b + TS_HDR + n_pad * dp * sizeof(float) + n_pad * sizeof(float4));
-    P.bytes = TS_HDR + n_pad * dp * sizeof(float) + n_pad * sizeof(float4) + n_pad * sizeof(int32_t);
-    return P;
-}
 
 // a wave per position of the padded list: x^ zero-padded to dp, xn by sil_stage's order (columns lane, lane + 64, .., then the tree)
 __global__ __launch_bounds__(256) void tsne_pack_kernel(const float *__restrict__ table, int ld, int n_table, int dim, int dp,

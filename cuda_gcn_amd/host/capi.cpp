@@ -386,6 +386,35 @@ int gcnhost_model_tsne(gcnhost_model *m, int k, int split, const int *nodes, int
         if (result) { result[0] = r.kl; result[1] = r.learning_rate; }
     })
 }
+int gcnhost_model_dbscan(gcnhost_model *m, double eps, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim,
+                         int normalize, int64_t capacity, int32_t *labels, uint8_t *core, int32_t *count, int32_t *sizes, int64_t *contingency,
+                         int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_dbscan: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.dbscan_rows("dbscan", split, nodes, n, data, data_dim, &eps, 1, min_samples);
+        if (listed > capacity)
+            throw GcnHipFailure(-1, "dbscan: the query lists " + std::to_string(listed) + " rows, the outputs have room for " + std::to_string(capacity));
+        const ModelQueries::Dbscan r = q.dbscan(eps, min_samples, split, nodes, n, data, data_dim, normalize != 0, labels, core, count, sizes, contingency);
+        if (info) {
+            info[0] = r.rows; info[1] = r.points; info[2] = r.core; info[3] = r.border; info[4] = r.noise; info[5] = r.clusters; info[6] = r.rounds;
+            info[7] = r.contingency_rows; info[8] = r.skipped;
+        }
+    })
+}
+int gcnhost_model_neighbor_counts(gcnhost_model *m, const double *eps, int n_eps, int split, const int *nodes, int n, const float *data, int data_dim,
+                                  int normalize, int64_t capacity, int32_t *count, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_neighbor_counts: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.dbscan_rows("neighbor_counts", split, nodes, n, data, data_dim, eps, n_eps, 1);
+        if (listed > capacity)
+            throw GcnHipFailure(-1, "neighbor_counts: the query lists " + std::to_string(listed) + " rows, the output has room for " +
+                                        std::to_string(capacity));
+        const ModelQueries::Dbscan r = q.neighbor_counts(eps, n_eps, split, nodes, n, data, data_dim, normalize != 0, count);
+        if (info) { info[0] = r.rows; info[1] = r.points; }
+    })
+}
 int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }
 int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
                              double *explained, double *scale, int *rank) {

@@ -156,6 +156,13 @@
 //                            printed: `tsne_rows=<n> tsne_perplexity=<p> tsne_iters=<i> tsne_kl=<KL at the last gradient>
 //                            tsne_unconverged=<bandwidths not found>`.  The file gets one line per test node in id order:
 //                            `node y1 y2` (%.9g).
+// DBSCAN of the embeddings (beyond the reference; ModelQueries::dbscan, kernels in csrc/dbscan.hip), after the t-SNE map.  One GPU,
+// hidden_dim at most 256, f32 tables:
+//   GCN_DBSCAN=<file>        the density clusters of the unit rows of the hidden layer of the TEST nodes at the radius
+//                            GCN_DBSCAN_EPS (euclidean, default 0.5) with GCN_DBSCAN_MIN_SAMPLES (default 5), matrix-free on the
+//                            GPU.  One line is printed: `dbscan_eps=<e> dbscan_min_samples=<m> dbscan_clusters=<k> dbscan_core=<n>
+//                            dbscan_border=<n> dbscan_noise=<n>`.  The file gets one line per test node in id order: `node label
+//                            core count` (label -1: noise; count: the nodes within eps, itself included).
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -450,6 +457,23 @@ int main(int argc, char **argv) {
                                                             : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_TSNE " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *dbscan_path = getenv("GCN_DBSCAN");
+    if (dbscan_path && !*dbscan_path) dbscan_path = nullptr;
+    const int dbscan_min_samples = env_int("GCN_DBSCAN_MIN_SAMPLES", 5);
+    const double dbscan_eps = getenv("GCN_DBSCAN_EPS") ? atof(getenv("GCN_DBSCAN_EPS")) : 0.5;
+    if (dbscan_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1                        ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                         ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                   ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : dbscan_min_samples < 1                          ? "needs GCN_DBSCAN_MIN_SAMPLES of at least 1"
+                          : !(dbscan_eps > 0.0) || !std::isfinite(dbscan_eps) ? "needs a finite GCN_DBSCAN_EPS above 0"
+                                                                            : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_DBSCAN " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -993,6 +1017,27 @@ int main(int argc, char **argv) {
                 if (f2 && fclose(f2) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the t-SNE map to ") + tsne_path);
                 fprintf(stderr, "gcn-hip: the t-SNE map of %lld test nodes written to %s\n", (long long)n, tsne_path);
+            }
+            if (dbscan_path) {                                 // one rank (checked above): the test nodes in id order
+                ModelQueries &q = gcn.queries();
+                std::vector<int> ids;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) ids.push_back(i);
+                const size_t n = ids.size();
+                if (n < 1) throw GcnHipFailure(-1, "gcn-hip: GCN_DBSCAN found no test nodes to cluster");
+                std::vector<int32_t> label(n), count(n);
+                std::vector<uint8_t> core(n);
+                const ModelQueries::Dbscan r = q.dbscan(dbscan_eps, dbscan_min_samples, 3, nullptr, 0, nullptr, 0, true, label.data(), core.data(),
+                                                        count.data(), nullptr, nullptr);
+                if ((size_t)r.rows != n) throw GcnHipFailure(-1, "gcn-hip: GCN_DBSCAN listed other rows than the test nodes");
+                printf("dbscan_eps=%.9g dbscan_min_samples=%d dbscan_clusters=%lld dbscan_core=%lld dbscan_border=%lld dbscan_noise=%lld\n", dbscan_eps,
+                       dbscan_min_samples, (long long)r.clusters, (long long)r.core, (long long)r.border, (long long)r.noise);
+                FILE *f2 = fopen(dbscan_path, "w");
+                bool ok = f2 != nullptr;
+                for (size_t i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %d %d %d\n", ids[i], label[i], (int)core[i], count[i]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the DBSCAN labels to ") + dbscan_path);
+                fprintf(stderr, "gcn-hip: the DBSCAN labels of %zu test nodes written to %s\n", n, dbscan_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

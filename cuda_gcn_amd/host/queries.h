@@ -368,6 +368,28 @@ public:
               int exaggeration_iters, double learning_rate, bool normalize, const double *init, int kl_every, size_t scratch_bytes, float *coords,
               double *beta, double *history);
 
+    // DBSCAN of the hidden layer (Ester et al., 1996; include/gcnhip_driver.h has the definitions, csrc/dbscan.hip the kernels,
+    // host/dbscan_query.cpp the bodies): how many dense groups the embeddings hold and which rows belong to none.  Rows and `data`
+    // as for tsne.  Steps: sync(); embed_forward; gcnhip_tsne_pack; gcnhip_dbscan_counts (one walk, E radii); for dbscan also
+    // gcnhip_dbscan_cores and rounds of gcnhip_dbscan_link, enqueued DBSCAN_BATCH at a time with their `changed` flags read back
+    // together, until the first round that hooked nothing; then gcnhip_dbscan_labels.  Outputs of dbscan, each may be NULL: labels
+    // int32 / core uint8 / count int32 / sizes int32 [rows] by list position (sizes: the first `clusters` entries), contingency
+    // [clusters x C] against the dataset's labels (filled when given, the rows are nodes and 1 <= clusters <= 256: then
+    // contingency_rows = clusters; gcnhip_contingency_rows skips the noise).  neighbor_counts: count int32 [E x rows].  Training
+    // state is untouched, the query owns its device buffers and nothing is cached.  Refused with a message before any launch: more
+    // than one rank, bf16 tables, a width above 256, E outside 1..8, an eps that is not finite and above 0, min_samples < 1, a bad
+    // split or node id.
+    struct Dbscan {
+        int64_t rows = 0, points = 0, core = 0, border = 0, noise = 0, clusters = 0, rounds = 0, contingency_rows = 0, skipped = 0;
+    };
+    static constexpr int DBSCAN_BATCH = 4;
+    int64_t dbscan_rows(const char *what, int split, const int *nodes, int n, const float *data, int data_dim, const double *eps, int n_eps,
+                        int min_samples, std::vector<int> *rows = nullptr);
+    Dbscan dbscan(double eps, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim, bool normalize, int32_t *labels,
+                  uint8_t *core, int32_t *count, int32_t *sizes, int64_t *contingency);
+    Dbscan neighbor_counts(const double *eps, int n_eps, int split, const int *nodes, int n, const float *data, int data_dim, bool normalize,
+                           int32_t *count);
+
     // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
     // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
     // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
@@ -580,6 +602,14 @@ private:
     Scratch<unsigned char> d_ts_pack{&arena}, d_ts_scratch{&arena};
     Scratch<double> d_ts_f64{&arena};
     Scratch<float> d_ts_f32{&arena}, d_ts_data{&arena};
+    // dbscan / neighbor_counts: {rows | count [E x n] | labels | sizes [n] | totals [5] | points | flags}, the contingency, the pack,
+    // the state, the core bytes, the caller's table
+    Scratch<int32_t> d_db_int{&arena}, d_db_cont{&arena};
+    Scratch<unsigned char> d_db_pack{&arena}, d_db_state{&arena}, d_db_core{&arena};
+    Scratch<float> d_db_data{&arena};
+    // the body of both: min_samples == 0 stops after the counts
+    Dbscan dbscan_run(const char *what, const double *eps, int n_eps, int min_samples, int split, const int *nodes, int n, const float *data,
+                      int data_dim, bool normalize, int32_t *labels, uint8_t *core, int32_t *count, int32_t *sizes, int64_t *contingency);
     // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
     // a projection, its coordinates, the sums' scratch
     Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};

@@ -1017,6 +1017,72 @@ class HipGCNModel:
         return dict(coords=coords, kl=float(res[0]), history=hist[:int(info[3])].copy(), beta=beta, unconverged=int(info[2]), points=int(info[1]),
                     learning_rate=float(res[1]))
 
+    # ---- DBSCAN of the hidden layer: how many dense groups there are, and which nodes belong to none, on the GPU
+    def _dbscan_rows(self, what, split, nodes, data):
+        if data is not None:
+            if split is not None or nodes is not None:
+                raise GcnHostError(f"{what}: with data the rows are the data's: no split and no node query")
+            d = np.ascontiguousarray(data, np.float32)
+            if d.ndim != 2 or not 1 <= d.shape[1] <= 256 or d.shape[0] < 1:
+                raise GcnHostError(f"{what}: data must be a float [n, d <= 256] array, got shape {d.shape}")
+            return d, None, int(d.shape[0]), int(d.shape[0])
+        q, n, cap = self._pca_query(what, split, nodes)
+        return None, q, n, cap                                # (a split lists at most num_nodes rows: info[0] tells how many)
+
+    def dbscan(self, eps, min_samples=5, split=None, nodes=None, normalize=True, data=None, report=True):
+        """DBSCAN (Ester et al., 1996; scikit-learn's DBSCAN, euclidean) of the rows embed() exports, run where they lie and
+        matrix-free: one evaluation forward, the rows packed once, then walks over the tile pairs of the upper triangle that
+        recompute every squared distance on the exact-f32 MFMA and keep only integers — one walk for the neighbour counts, then
+        rounds of component labelling over the core points until a round hooks nothing.  No n x n matrix exists, and the answer
+        is exact: the same labels on every run, equal to scikit-learn's `labels_` element for element wherever no distance lies
+        within f32 rounding of eps.  Rows: the nodes of `split` in ascending id, or the `nodes` query (a repeat is a point of its
+        own), or with both None every node in id order; data: any float [n, d <= 256] array instead of the embeddings.  Returns a
+        dict: labels int32 [n] (-1: noise), core bool [n], counts int32 [n] (neighbours within eps, the node itself included),
+        n_clusters, sizes int32 [n_clusters], n_core, n_border, n_noise, points, rounds.  With report=True on a single-label model
+        with at most 64 classes, when 1 <= n_clusters <= 256 and the rows are nodes, also contingency int64 [n_clusters, C] over
+        the non-noise points, counted on the GPU, skipped, and cluster_report()'s scores.  normalize=True clusters unit rows (see
+        cluster()).  One rank, f32 tables, width at most 256.  Training state is not touched and nothing is cached."""
+        what = "dbscan"
+        if isinstance(min_samples, bool) or int(min_samples) != min_samples or min_samples < 1:
+            raise GcnHostError(f"{what}: min_samples must be at least 1, got {min_samples!r}")
+        if not (np.isfinite(eps) and eps > 0):
+            raise GcnHostError(f"{what}: eps must be finite and above 0, got {eps!r}")
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        c = self.params.output_dim
+        want_report = bool(report) and d is None and not self.multilabel and c <= 64
+        m = max(cap, 1)
+        labels, core, count, sizes = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        cont, info = (np.zeros((256, c), np.int64) if want_report else None), np.zeros(9, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_dbscan(
+            self.h, float(eps), int(min_samples), int(split or 0), q.ctypes.data if q is not None else None, n,
+            d.ctypes.data if d is not None else None, int(d.shape[1]) if d is not None else 0, int(bool(normalize)), cap, labels.ctypes.data,
+            core.ctypes.data, count.ctypes.data, sizes.ctypes.data, cont.ctypes.data if want_report else None, info.ctypes.data), what)
+        k, cap = int(info[5]), int(info[0])
+        out = dict(labels=labels[:cap], core=core[:cap].astype(bool), counts=count[:cap], n_clusters=k, sizes=sizes[:k].copy(), n_core=int(info[2]),
+                   n_border=int(info[3]), n_noise=int(info[4]), points=int(info[1]), rounds=int(info[6]))
+        if want_report and int(info[7]) == k and k >= 1:
+            out.update(contingency=cont.ravel()[:k * c].reshape(k, c).copy(), skipped=int(info[8]))
+            out.update(cluster_report(out["contingency"]))
+        return out
+
+    def neighbor_counts(self, eps_list, split=None, nodes=None, normalize=True, data=None):
+        """int32 [E, n] — for each of 1..8 radii and each listed row the rows within that distance of it, itself included (0 where
+        the position is no point): dbscan()'s count walk alone, E compares per distance, so that one walk prices a sweep of eps.
+        Rows, normalize and data as for dbscan()."""
+        what = "neighbor_counts"
+        e = np.ascontiguousarray(np.atleast_1d(eps_list), np.float64).ravel()
+        if not 1 <= e.size <= 8:
+            raise GcnHostError(f"{what}: between 1 and 8 radii, got {e.size}")
+        if not np.all(np.isfinite(e) & (e > 0)):
+            raise GcnHostError(f"{what}: eps must be finite and above 0, got {e.tolist()}")
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        count, info = np.zeros((e.size, max(cap, 1)), np.int32), np.zeros(2, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_neighbor_counts(
+            self.h, e.ctypes.data, int(e.size), int(split or 0), q.ctypes.data if q is not None else None, n,
+            d.ctypes.data if d is not None else None, int(d.shape[1]) if d is not None else 0, int(bool(normalize)), cap, count.ctypes.data,
+            info.ctypes.data), what)
+        return count.ravel()[:e.size * int(info[0])].reshape(e.size, int(info[0])).copy()
+
     def pca_transform(self, fit, nodes=None):
         """f32 [n, k] — the listed nodes (None: every node in id order) projected with a fit pca() returned, at the CURRENT
         weights: one evaluation forward and one projection launch on the GPU; nothing is cached.  A fit on the training split
@@ -1554,6 +1620,28 @@ def read_tsne(path):
             except ValueError:
                 raise GcnHostError(f"read_tsne: {path}:{no}: expected `node y1 .. yk` with k = 2 or 3, got {line.strip()!r}") from None
     return dict(node=np.array(node, np.int32), coords=np.array(rows, np.float64).reshape(len(rows), -1))
+
+
+def read_dbscan(path):
+    """The file gcn-hip writes with GCN_DBSCAN, one line `node label core count` per node: a dict of node, label (-1: noise), count
+    int32 [n] and core bool [n].  Needs no GPU."""
+    cols = [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) != 4:
+                    raise ValueError
+                v = [int(x) for x in p]
+                if v[1] < -1 or v[2] not in (0, 1) or v[3] < 0:
+                    raise ValueError
+            except ValueError:
+                raise GcnHostError(f"read_dbscan: {path}:{no}: expected `node label core count`, got {line.strip()!r}") from None
+            [c.append(x) for c, x in zip(cols, v)]
+    node, label, core, count = (np.array(c, np.int32) for c in cols)
+    return dict(node=node, label=label, core=core.astype(bool), count=count)
 
 
 def sym_eigen(S):

@@ -864,6 +864,62 @@ class Device:
         return dict(coords=yb.download().reshape(n, k), kl=float(hist[-1, 1]), history=hist, beta=bw["beta"], unconverged=bw["unconverged"],
                     points=pk["points"], learning_rate=lr)
 
+    # ---- DBSCAN of a table's rows (csrc/dbscan.hip) on the pack tsne_pack makes: every buffer is uploaded as garbage
+    def dbscan_plan(self, n, dim):
+        """gcnhip_dbscan_plan: dict(pack_bytes, state_bytes)"""
+        p, s = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_dbscan_plan(int(n), int(dim), C.byref(p), C.byref(s))
+        if rc != 0:
+            self._embed_fail("gcnhip_dbscan_plan", rc)
+        return dict(pack_bytes=p.value, state_bytes=s.value)
+
+    def _dbscan_counts(self, pk, eps_list):
+        e = np.ascontiguousarray(eps_list, np.float64).ravel()
+        cb = self.buf(np.full(max(e.size, 1) * pk["n"], -777, np.int32))
+        rc = self.lib.gcnhip_dbscan_counts(self.ctx, pk["pack"].ptr, pk["n"], pk["dim"], e.ctypes.data, int(e.size), cb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_dbscan_counts", rc)
+        return cb
+
+    def dbscan_counts(self, table, eps_list, rows=None, inv_norm=None, ld=None):
+        """gcnhip_dbscan_counts: int32 [E, n] — per radius and list position the rows within eps of it, itself included; 0 where the
+        position is no point"""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        return self._dbscan_counts(pk, eps_list).download().reshape(-1, pk["n"])
+
+    def dbscan_run(self, table, eps, min_samples=5, rows=None, inv_norm=None, ld=None, batch=4):
+        """DBSCAN of the listed rows: pack, counts, cores, then rounds of gcnhip_dbscan_link, `batch` enqueued at a time, until the
+        first that hooked nothing, then the labels.  dict(labels int32 [n], core bool [n], counts int32 [n], sizes int32
+        [n_clusters], n_clusters, n_core, n_border, n_noise, points, rounds)."""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        n, dim = pk["n"], pk["dim"]
+        cb = self._dbscan_counts(pk, [eps])
+        sbytes = self.dbscan_plan(n, dim)["state_bytes"]
+        sb = self.buf(np.full(sbytes // 4, 0x7fc12345, np.uint32))
+        rc = self.lib.gcnhip_dbscan_cores(self.ctx, pk["pack"].ptr, n, dim, cb.ptr, int(min_samples), sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_dbscan_cores", rc)
+        fb = self.buf(np.full(int(batch), -777, np.int32))
+        rounds, settled = 0, False
+        while not settled:
+            for r in range(int(batch)):
+                rc = self.lib.gcnhip_dbscan_link(self.ctx, pk["pack"].ptr, n, dim, float(eps), sb.ptr, sbytes, fb.ptr + 4 * r)
+                if rc != 0:
+                    self._embed_fail("gcnhip_dbscan_link", rc)
+            for f in fb.download():
+                rounds += 1
+                if f == 0:
+                    settled = True
+                    break
+        lb, kb = self.buf(np.full(n, -777, np.int32)), self.buf(np.full(n, 0x5A, np.uint8))
+        zb, tb = self.buf(np.full(n, -777, np.int32)), self.buf(np.full(5, -777, np.int32))
+        rc = self.lib.gcnhip_dbscan_labels(self.ctx, pk["pack"].ptr, n, dim, sb.ptr, sbytes, lb.ptr, kb.ptr, zb.ptr, tb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_dbscan_labels", rc)
+        t = tb.download()
+        return dict(labels=lb.download(), core=kb.download().astype(bool), counts=cb.download(), sizes=zb.download()[:int(t[4])].copy(),
+                    n_clusters=int(t[4]), n_core=int(t[1]), n_border=int(t[2]), n_noise=int(t[3]), points=int(t[0]), rounds=rounds)
+
     # ---- principal components of the rows of a table (csrc/pca.hip): the table is uploaded with its row stride and NaN padding,
     # every output as garbage
     def pca_plan(self, n, dim):

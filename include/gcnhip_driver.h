@@ -481,6 +481,38 @@ int gcnhip_tsne_gradient(gcnhip_ctx *ctx, const void *pack, int n, int dim, cons
                          void *scratch, size_t scratch_bytes);
 int gcnhip_tsne_update(gcnhip_ctx *ctx, const void *pack, int n, int dim, int k, const double *rowsums, double exaggeration,
                        double momentum, double learning_rate, int apply, double *state, float *y, double *grad, double *stats);
+/* ---- DBSCAN of a table's rows (dbscan.hip; beyond the reference: how many dense groups the embeddings hold and which rows belong
+ * to none; Ester et al., 1996, scikit-learn's DBSCAN labels element for element), matrix-free: no n x n slab exists ----
+ * Table, row list, scaling and points are gcnhip_silhouette_sums'; the rows are read from the PACK gcnhip_tsne_pack makes of them
+ *   (gcnhip_dbscan_plan's pack_bytes are gcnhip_tsne_plan's).  d2(i, j) is t-SNE's: max(0, (xn_i + xn_j) - 2 . dot_f32(x^_i, x^_j)),
+ *   the dot on v_mfma_f32_16x16x4_f32 in column order.
+ * eps2 = (float)(eps . eps), the product in double.  j is in the neighbourhood of i when both are points and d2(i, j) <= eps2; i is
+ *   in its own neighbourhood BY POSITION.  Each unordered pair {i, j} is evaluated ONCE (with the larger position as the column) and
+ *   the result used for both ends: the relation is symmetric whatever the rounding.
+ * count[e][i] = the size of the neighbourhood of i at eps[e], 1 <= E <= 8 radii in one walk; 0 where i is no point.
+ * core[i] = count[i] >= min_samples (min_samples >= 1).  A cluster is a connected component of the core points under the relation;
+ *   comp[i] of a core point is the smallest position of its component.  A non-core point with a core point in its neighbourhood is
+ *   a BORDER point and takes the smallest comp among those core points (what scikit-learn's visiting order gives).  Every other
+ *   point is NOISE, label -1; so is a position that is no point.  Clusters are numbered 0 .. n_clusters - 1 in ascending comp.
+ * Rounds: a round hooks, for every neighbouring pair of core points whose roots differ, the larger root under the smaller
+ *   (atomicMin), reading the roots the round started with; the next round starts by following the hooks to their end.  The round
+ *   that hooks nothing leaves *changed at 0: its border slots are the answer.  A round after that one changes nothing.
+ * No launch allocates or synchronises, none uses a float atomic (integer atomicAdd / atomicMin / atomicOr only); every output's bits
+ *   are a function of the arguments' contents alone; anything else returns -1 with a message.
+ * gcnhip_dbscan_plan: *pack_bytes of the packed image and *state_bytes of the labelling state; each may be NULL.  No GPU.
+ * gcnhip_dbscan_counts: count (device int32 [E x n]) at the radii eps (HOST float64 [E], each finite and above 0).
+ * gcnhip_dbscan_cores: from count (device int32 [n], the radius the rounds will use) and min_samples the core flags, every tile's
+ *   core count and the start of the labelling (every position its own root) into state.
+ * gcnhip_dbscan_link: one round at eps on a state gcnhip_dbscan_cores started; *changed (device int32) = 1 when it hooked.
+ * gcnhip_dbscan_labels: after the round that left *changed at 0: labels (int32 [n]), core (uint8 [n]), sizes (int32, room for n,
+ *   the first n_clusters are the answer, the rest 0), counts (int32 [5]) = {points, core, border, noise, clusters}. */
+int gcnhip_dbscan_plan(int n, int dim, size_t *pack_bytes, size_t *state_bytes);
+int gcnhip_dbscan_counts(gcnhip_ctx *ctx, const void *pack, int n, int dim, const double *eps, int n_eps, int32_t *count);
+int gcnhip_dbscan_cores(gcnhip_ctx *ctx, const void *pack, int n, int dim, const int32_t *count, int min_samples, void *state,
+                        size_t state_bytes);
+int gcnhip_dbscan_link(gcnhip_ctx *ctx, const void *pack, int n, int dim, double eps, void *state, size_t state_bytes, int32_t *changed);
+int gcnhip_dbscan_labels(gcnhip_ctx *ctx, const void *pack, int n, int dim, const void *state, size_t state_bytes, int32_t *labels,
+                         uint8_t *core, int32_t *sizes, int32_t *counts);
 /* ---- principal components of the rows of a table (pca.hip; beyond the reference: the coordinates of what a GCN learns) ----
  * The table contract and the row lists of the k-means calls: a list position whose row is outside the table is skipped and
  * leaves a NaN row in a projection.  x_i[a] = T[r][a] . inv_norm[r] rounded to f32 (inv_norm == NULL: T[r][a]).  No launch

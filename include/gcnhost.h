@@ -413,6 +413,23 @@ int gcnhost_model_silhouette(gcnhost_model *m, int split, const int *nodes, int 
 int gcnhost_model_tsne(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, double perplexity, int iters,
                        double exaggeration, int exaggeration_iters, double learning_rate, int normalize, const double *init, int kl_every,
                        size_t scratch_bytes, int64_t capacity, float *coords, double *beta, double *history, int64_t *info, double *result);
+/* DBSCAN of the hidden layer (ModelQueries::dbscan / neighbor_counts, host/queries.h; definitions in include/gcnhip_driver.h,
+ * kernels in csrc/dbscan.hip).  Rows and `data` as for gcnhost_model_tsne; capacity: the rows the outputs have room for, at least the rows listed.  eps finite and
+ * above 0, min_samples >= 1, 1 <= n_eps <= 8.  Outputs of gcnhost_model_dbscan, each may be NULL: labels int32 [capacity] (-1:
+ * noise, or a position that is no point; otherwise scikit-learn's DBSCAN label), core uint8 [capacity], count int32 [capacity] (the
+ * neighbourhood sizes at eps, the point itself included), sizes int32 [capacity] (the first `clusters` entries), contingency int64
+ * [clusters x output_dim] against the dataset's labels — give room for 256 x output_dim, on a single-label model with at most 64
+ * classes and no `data`; it is filled when 1 <= clusters <= 256 (info[7] = its rows, else 0; info[8] = the positions it skipped,
+ * the noise among them) — and info [9] = {rows listed, points, core, border, noise, clusters, rounds, contingency rows, skipped}.
+ * gcnhost_model_neighbor_counts: count int32 [n_eps x rows listed], contiguous, in room for n_eps x capacity; info [2] = {rows listed,
+ * points}: one walk prices a sweep of radii.
+ * embed's contract: training state is not touched, nothing is cached.  Refused with a message: several ranks, bf16 tables, a width
+ * above 256, n_eps outside 1..8, a bad eps or min_samples, a bad split or node id. */
+int gcnhost_model_dbscan(gcnhost_model *m, double eps, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim,
+                         int normalize, int64_t capacity, int32_t *labels, uint8_t *core, int32_t *count, int32_t *sizes, int64_t *contingency,
+                         int64_t *info);
+int gcnhost_model_neighbor_counts(gcnhost_model *m, const double *eps, int n_eps, int split, const int *nodes, int n, const float *data,
+                                  int data_dim, int normalize, int64_t capacity, int32_t *count, int64_t *info);
 /* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
  * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
  * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
