@@ -415,6 +415,29 @@ int gcnhost_model_neighbor_counts(gcnhost_model *m, const double *eps, int n_eps
         if (info) { info[0] = r.rows; info[1] = r.points; }
     })
 }
+int gcnhost_map_quality_metrics(const int64_t *sums, int64_t points, int k, double *out) { return gcn_map_quality_metrics(sums, points, k, out, &g_err); }
+int gcnhost_model_knn(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, int normalize, int64_t capacity,
+                      int32_t *ids, int32_t *pos, float *d2, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_knn: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.mapq_rows("knn", k, split, nodes, n, data, data_dim);
+        if (listed > capacity)
+            throw GcnHipFailure(-1, "knn: the query lists " + std::to_string(listed) + " rows, the outputs have room for " + std::to_string(capacity));
+        const ModelQueries::Knn r = q.knn(k, split, nodes, n, data, data_dim, normalize != 0, ids, pos, d2);
+        if (info) { info[0] = r.rows; info[1] = r.points; }
+    })
+}
+int gcnhost_model_map_quality(gcnhost_model *m, const float *coords, int64_t coords_rows, int coords_dim, int k, int split, const int *nodes, int n,
+                              const float *data, int data_dim, int normalize, int32_t *per_node, int64_t *info, double *scores) {
+    if (!m) { g_err = "gcnhost_model_map_quality: invalid argument"; return -1; }
+    API_TRY({
+        const ModelQueries::MapQuality r =
+            m->gcn->queries().map_quality(coords, coords_rows, coords_dim, k, split, nodes, n, data, data_dim, normalize != 0, per_node);
+        if (info) { info[0] = r.rows; info[1] = r.points; info[2] = r.sums[0]; info[3] = r.sums[1]; info[4] = r.sums[2]; }
+        if (scores) { scores[0] = r.trustworthiness; scores[1] = r.continuity; scores[2] = r.knn_overlap; }
+    })
+}
 int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }
 int gcnhost_pca_from_scatter(const double *S, const double *mean, int64_t rows, int h, int k, int whiten, double *eigenvalues, double *components,
                              double *explained, double *scale, int *rank) {

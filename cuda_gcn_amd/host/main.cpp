@@ -156,6 +156,11 @@
 //                            printed: `tsne_rows=<n> tsne_perplexity=<p> tsne_iters=<i> tsne_kl=<KL at the last gradient>
 //                            tsne_unconverged=<bandwidths not found>`.  The file gets one line per test node in id order:
 //                            `node y1 y2` (%.9g).
+//   GCN_TSNE_QUALITY=<file>  with GCN_TSNE: can that map be believed?  ModelQueries::map_quality (kernels in csrc/mapq.hip) of the map
+//                            against the rows it maps at k = GCN_TSNE_QUALITY_K (default 10, 1..32) nearest neighbours.  After the
+//                            `tsne_rows=` line one more is printed: `tsne_quality_k=<k> tsne_trustworthiness=<T> tsne_continuity=<C>
+//                            tsne_knn_overlap=<O>`.  The file gets one line per test node in id order: `node trust_penalty
+//                            cont_penalty shared`.
 // DBSCAN of the embeddings (beyond the reference; ModelQueries::dbscan, kernels in csrc/dbscan.hip), after the t-SNE map.  One GPU,
 // hidden_dim at most 256, f32 tables:
 //   GCN_DBSCAN=<file>        the density clusters of the unit rows of the hidden layer of the TEST nodes at the radius
@@ -457,6 +462,19 @@ int main(int argc, char **argv) {
                                                             : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_TSNE " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *tsne_quality_path = getenv("GCN_TSNE_QUALITY");
+    if (tsne_quality_path && !*tsne_quality_path) tsne_quality_path = nullptr;
+    const int tsne_quality_k = env_int("GCN_TSNE_QUALITY_K", 10);
+    if (tsne_quality_path) {
+        const char *why = !tsne_path                                   ? "needs GCN_TSNE (it scores that map)"
+                          : tsne_quality_k < 1 || tsne_quality_k > 32 ? "needs GCN_TSNE_QUALITY_K in 1..32"
+                                                                       : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_TSNE_QUALITY " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -1017,6 +1035,19 @@ int main(int argc, char **argv) {
                 if (f2 && fclose(f2) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the t-SNE map to ") + tsne_path);
                 fprintf(stderr, "gcn-hip: the t-SNE map of %lld test nodes written to %s\n", (long long)n, tsne_path);
+                if (tsne_quality_path) {                       // the same rows, the same unit scaling as the map's input
+                    std::vector<int32_t> per((size_t)n * 3);
+                    const ModelQueries::MapQuality mq = q.map_quality(y.data(), n, 2, tsne_quality_k, 3, nullptr, 0, nullptr, 0, true, per.data());
+                    printf("tsne_quality_k=%d tsne_trustworthiness=%.9g tsne_continuity=%.9g tsne_knn_overlap=%.9g\n", tsne_quality_k, mq.trustworthiness,
+                           mq.continuity, mq.knn_overlap);
+                    FILE *f3 = fopen(tsne_quality_path, "w");
+                    ok = f3 != nullptr;
+                    for (int64_t i = 0; ok && i < n; i++)
+                        ok = fprintf(f3, "%d %d %d %d\n", ids[(size_t)i], per[3 * i], per[3 * i + 1], per[3 * i + 2]) > 0;
+                    if (f3 && fclose(f3) != 0) ok = false;
+                    if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the map quality to ") + tsne_quality_path);
+                    fprintf(stderr, "gcn-hip: the map quality of %lld test nodes written to %s\n", (long long)n, tsne_quality_path);
+                }
             }
             if (dbscan_path) {                                 // one rank (checked above): the test nodes in id order
                 ModelQueries &q = gcn.queries();

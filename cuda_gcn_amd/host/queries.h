@@ -18,6 +18,7 @@
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <string>
 #include <vector>
 #include "device_arena.h"
 
@@ -390,6 +391,34 @@ public:
     Dbscan neighbor_counts(const double *eps, int n_eps, int split, const int *nodes, int n, const float *data, int data_dim, bool normalize,
                            int32_t *count);
 
+    // Map quality (Venna & Kaski, 2001; scikit-learn's trustworthiness; include/gcnhip_driver.h has the definitions, csrc/mapq.hip the
+    // kernels, host/mapq_query.cpp the bodies): the exact euclidean k nearest neighbours of the listed rows among the listed rows,
+    // and whether a map of them — tsne()'s or pca()'s coords for the same arguments, by list position — keeps those neighbourhoods.
+    // Rows and `data` as for dbscan, with its refusals.
+    //   knn: sync(); embed_forward; gcnhip_tsne_pack; one gcnhip_knn_rows.  ids / pos int32 and d2 f32 [rows x k] by list position (each
+    //   may be NULL): dataset node ids (with data: positions) and LIST POSITIONS, nearest first, -1 / -1 / +inf where the position is
+    //   no point.
+    //   map_quality: two packs (the input space, and coords f32 [coords_rows x coords_dim] as a table of its own), two
+    //   gcnhip_knn_rows, two gcnhip_nbr_ranks (the map's neighbours ranked in the input space, the input space's on the map), one
+    //   gcnhip_mapq_sums.  Only the four totals cross to the host, and with per_node (int32 [rows x 3] = trust penalty, continuity
+    //   penalty, shared neighbours) that table; gcn_map_quality_metrics derives the three scores from the totals.
+    // Training state is untouched, the query owns its device buffers and nothing is cached.  Refused with a message before any
+    // launch: what dbscan refuses for its rows, k outside 1..32, fewer than 2 k + 1 rows, coords of a width outside 1..256 or of
+    // another row count than the list; after the walks, by both calls: fewer than 2 k + 1 points; by map_quality: a listed row
+    // that is no point (the map's positions all are).
+    struct Knn {
+        int64_t rows = 0, points = 0;
+    };
+    struct MapQuality {
+        int64_t rows = 0, points = 0, sums[3] = {0, 0, 0};     // sums: trust penalty, continuity penalty, shared neighbours
+        int k = 0;
+        double trustworthiness = 0, continuity = 0, knn_overlap = 0;
+    };
+    int64_t mapq_rows(const char *what, int k, int split, const int *nodes, int n, const float *data, int data_dim, std::vector<int> *rows = nullptr);
+    Knn knn(int k, int split, const int *nodes, int n, const float *data, int data_dim, bool normalize, int32_t *ids, int32_t *pos, float *d2);
+    MapQuality map_quality(const float *coords, int64_t coords_rows, int coords_dim, int k, int split, const int *nodes, int n, const float *data,
+                           int data_dim, bool normalize, int32_t *per_node);
+
     // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
     // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
     // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
@@ -610,6 +639,15 @@ private:
     // the body of both: min_samples == 0 stops after the counts
     Dbscan dbscan_run(const char *what, const double *eps, int n_eps, int min_samples, int split, const int *nodes, int n, const float *data,
                       int data_dim, bool normalize, int32_t *labels, uint8_t *core, int32_t *count, int32_t *sizes, int64_t *contingency);
+    // knn / map_quality: {rows | points | the kNN lists and rank tables | per node}, the distances, the totals, the packs of the
+    // input space and of the map, the caller's table, the map
+    Scratch<int32_t> d_mq_int{&arena};
+    Scratch<float> d_mq_d2{&arena}, d_mq_data{&arena}, d_mq_coords{&arena};
+    Scratch<int64_t> d_mq_totals{&arena};
+    Scratch<unsigned char> d_mq_pack[2] = {{&arena}, {&arena}};
+    void mapq_points(const char *what, int k, int64_t points) const;
+    int mapq_pack(const std::vector<int> &rows, int n, int k, const float *data, int data_dim, bool normalize, Scratch<unsigned char> &pack,
+                  int32_t *d_rows, int32_t *d_points);
     // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
     // a projection, its coordinates, the sums' scratch
     Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};
@@ -682,3 +720,8 @@ private:
     // the forward, the scores launch and the blend of both calls; returns the table the rows are read from (row stride *ld)
     const float *conformal_table(const ScoredRows &q, int method, float lam, int k_reg, float diffusion, int *ld);
 };
+
+// The three scores from the integer sums {trust penalty, continuity penalty, shared neighbours} over `points` points at k — the one
+// place they are derived; host only.  out [3] = {trustworthiness, continuity, kNN overlap} in float64, never NaN.  -1 with *err: k
+// outside 1..32, fewer than 2 k + 1 points, a sum outside its range.
+int gcn_map_quality_metrics(const int64_t *sums, int64_t points, int k, double *out, std::string *err);

@@ -1083,6 +1083,55 @@ class HipGCNModel:
             info.ctypes.data), what)
         return count.ravel()[:e.size * int(info[0])].reshape(e.size, int(info[0])).copy()
 
+    # ---- map quality: the exact nearest neighbours of the hidden layer, and whether a map of it keeps them, on the GPU
+    def knn(self, k=10, split=None, nodes=None, normalize=True, data=None):
+        """The exact euclidean k nearest neighbours (1 <= k <= 32) of every listed row among the listed rows, of the rows embed()
+        exports, found where they lie and matrix-free: one evaluation forward, the rows packed once, one walk that recomputes every
+        squared distance on the exact-f32 MFMA and keeps each row's k smallest (distance, position) keys — no n x n matrix exists,
+        and the lists have the same bits on every run.  Rows, normalize and data as for dbscan(); at least 2 k + 1 rows.  Returns a
+        dict: ids int32 [n, k] (node ids, nearest first; with data: positions), positions int32 [n, k] (list positions), d2 f32
+        [n, k] (squared distances), points; -1 / -1 / +inf where the position is no point."""
+        what = "knn"
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 32:
+            raise GcnHostError(f"{what}: k must be an integer in 1..32, got {k!r}")
+        k = int(k)
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        ids, pos = np.full((max(cap, 1), k), -1, np.int32), np.full((max(cap, 1), k), -1, np.int32)
+        d2, info = np.zeros((max(cap, 1), k), np.float32), np.zeros(2, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_knn(
+            self.h, k, int(split or 0), q.ctypes.data if q is not None else None, n, d.ctypes.data if d is not None else None,
+            int(d.shape[1]) if d is not None else 0, int(bool(normalize)), cap, ids.ctypes.data, pos.ctypes.data, d2.ctypes.data,
+            info.ctypes.data), what)
+        rows = int(info[0])
+        ids, pos, d2 = (a.ravel()[:rows * k].reshape(rows, k).copy() for a in (ids, pos, d2))
+        return dict(ids=ids, positions=pos, d2=d2, points=int(info[1]))
+
+    def map_quality(self, coords, k=10, split=None, nodes=None, normalize=True, data=None, per_node=True):
+        """Can a map of the embeddings be believed?  coords [n, d <= 256] by list position — what tsne(...)["coords"] or
+        pca(...)["coords"] is for the same split / nodes / normalize / data — is compared with the rows it maps by their exact k
+        nearest neighbours (1 <= k <= 32, k below half the points): trustworthiness (Venna & Kaski, 2001; scikit-learn's
+        trustworthiness: are the map's neighbours neighbours in the input space?), continuity (the same the other way round) and
+        knn_overlap (the mean share of a row's k neighbours the two spaces have in common).  Two kNN walks and two rank walks on the
+        exact-f32 MFMA, matrix-free; everything that leaves the GPU is an integer, so the scores have the same bits on every run.
+        Returns a dict: trustworthiness, continuity, knn_overlap, points, k, and with per_node=True trust_penalty, cont_penalty,
+        shared int32 [n].  One rank, f32 tables, width at most 256.  Training state is not touched and nothing is cached."""
+        what = "map_quality"
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 32:
+            raise GcnHostError(f"{what}: k must be an integer in 1..32, got {k!r}")
+        y = np.ascontiguousarray(coords, np.float32)
+        if y.ndim != 2 or not 1 <= y.shape[1] <= 256:
+            raise GcnHostError(f"{what}: coords must be a float [n, d <= 256] array, got shape {y.shape}")
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        per, info, scores = np.zeros((max(y.shape[0], 1), 3), np.int32), np.zeros(5, np.int64), np.zeros(3, np.float64)
+        _ck(self.lib, self.lib.gcnhost_model_map_quality(
+            self.h, y.ctypes.data, int(y.shape[0]), int(y.shape[1]), int(k), int(split or 0), q.ctypes.data if q is not None else None, n,
+            d.ctypes.data if d is not None else None, int(d.shape[1]) if d is not None else 0, int(bool(normalize)),
+            per.ctypes.data if per_node else None, info.ctypes.data, scores.ctypes.data), what)
+        out = dict(trustworthiness=float(scores[0]), continuity=float(scores[1]), knn_overlap=float(scores[2]), points=int(info[1]), k=int(k))
+        if per_node:
+            out.update(trust_penalty=per[:, 0].copy(), cont_penalty=per[:, 1].copy(), shared=per[:, 2].copy())
+        return out
+
     def pca_transform(self, fit, nodes=None):
         """f32 [n, k] — the listed nodes (None: every node in id order) projected with a fit pca() returned, at the CURRENT
         weights: one evaluation forward and one projection launch on the GPU; nothing is cached.  A fit on the training split
@@ -1566,6 +1615,19 @@ def conformal_quantile(scores, alpha, labels=None, num_classes=None):
 
 
 KEY_KMEANS = 0xE7037ED1A0B428DB           # host/module.h: the stream of cluster()'s seeding draws is its seed ^ this
+
+
+def map_quality_metrics(sums, points, k):
+    """Trustworthiness, continuity and kNN overlap from the integer sums (trust penalty, continuity penalty, shared neighbours) over
+    `points` points at k — host only, no GPU; the one place they are derived (include/gcnhip_driver.h has the formulas).  Never
+    NaN.  k outside 1..32, fewer than 2 k + 1 points or a sum outside its range raise GcnHostError."""
+    s = np.ascontiguousarray(sums, np.int64).ravel()
+    if s.size != 3:
+        raise GcnHostError(f"map_quality_metrics: three sums, got {s.size}")
+    lib = _lib.gcnhost()
+    out = np.zeros(3, np.float64)
+    _ck(lib, lib.gcnhost_map_quality_metrics(s.ctypes.data, int(points), int(k), out.ctypes.data), "map_quality_metrics")
+    return dict(trustworthiness=float(out[0]), continuity=float(out[1]), knn_overlap=float(out[2]))
 
 
 def cluster_report(contingency):

@@ -920,6 +920,79 @@ class Device:
         return dict(labels=lb.download(), core=kb.download().astype(bool), counts=cb.download(), sizes=zb.download()[:int(t[4])].copy(),
                     n_clusters=int(t[4]), n_core=int(t[1]), n_border=int(t[2]), n_noise=int(t[3]), points=int(t[0]), rounds=rounds)
 
+    # ---- map quality (csrc/mapq.hip) on the pack tsne_pack makes: exact kNN lists, ranks of given neighbours, the penalty sums;
+    # every output is uploaded as garbage
+    def mapq_plan(self, n, dim, k):
+        """gcnhip_mapq_plan: dict(pack_bytes, scratch_bytes)"""
+        p, s = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_mapq_plan(int(n), int(dim), int(k), C.byref(p), C.byref(s))
+        if rc != 0:
+            self._embed_fail("gcnhip_mapq_plan", rc)
+        return dict(pack_bytes=p.value, scratch_bytes=s.value)
+
+    def _knn_rows(self, pk, k):
+        n, k = pk["n"], int(k)
+        pb, db = self.buf(np.full(n * max(k, 1), -777, np.int32)), self.buf(np.full(n * max(k, 1), np.nan, np.float32))
+        rc = self.lib.gcnhip_knn_rows(self.ctx, pk["pack"].ptr, n, pk["dim"], k, pb.ptr, db.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_knn_rows", rc)
+        return pb, db
+
+    def _nbr_ranks(self, pk, k, targets_buf):
+        rb = self.buf(np.full(pk["n"] * int(k), -777, np.int32))
+        rc = self.lib.gcnhip_nbr_ranks(self.ctx, pk["pack"].ptr, pk["n"], pk["dim"], int(k), targets_buf.ptr, rb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_nbr_ranks", rc)
+        return rb
+
+    def knn_rows(self, table, k, rows=None, inv_norm=None, ld=None):
+        """gcnhip_knn_rows: dict(pos int32 [n, k], d2 f32 [n, k], points) — per list position the k nearest other points of the list
+        by (squared euclidean distance, position), nearest first; -1 / +inf where the position is no point and past the candidates"""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        pb, db = self._knn_rows(pk, k)
+        return dict(pos=pb.download().reshape(pk["n"], -1), d2=db.download().reshape(pk["n"], -1), points=pk["points"])
+
+    def nbr_ranks(self, table, targets, rows=None, inv_norm=None, ld=None):
+        """gcnhip_nbr_ranks: int32 [n, k] — the rank (1: nearest) that position targets[i, t] holds among the points other than i in
+        row i's order by (distance, position); 0 where i or the target is no point"""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        t = np.ascontiguousarray(targets, np.int32)
+        if t.ndim != 2 or t.shape[0] != pk["n"]:
+            raise GcnHipError(f"nbr_ranks: targets must be [{pk['n']}, k], got {t.shape}")
+        return self._nbr_ranks(pk, t.shape[1], self.buf(t)).download().reshape(t.shape)
+
+    def nbr_d2(self, table, targets, rows=None, inv_norm=None, ld=None):
+        """gcnhip_nbr_d2: f32 [n, k] — d2(i, targets[i, t]) as the rank walk forms its thresholds; NaN where i or the target is no point"""
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        t = np.ascontiguousarray(targets, np.int32)
+        db = self.buf(np.full(t.size, 7.5, np.float32))
+        rc = self.lib.gcnhip_nbr_d2(self.ctx, pk["pack"].ptr, pk["n"], pk["dim"], t.shape[1], self.buf(t).ptr, db.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_nbr_d2", rc)
+        return db.download().reshape(t.shape)
+
+    def map_quality_run(self, x_table, y_table, k, rows=None, inv_norm=None):
+        """How well the rows of y_table (a map) keep the neighbourhoods of the same rows of x_table: two packs, two kNN walks, two rank
+        walks (the map's neighbours ranked in x, x's neighbours ranked in the map) and gcnhip_mapq_sums.  dict(knn_x, knn_y, rank_x,
+        rank_y int32 [n, k], per_position int32 [n, 3] = (trust_penalty, cont_penalty, shared), totals int64 [4] = their sums and the
+        points, trustworthiness, continuity, knn_overlap from model.map_quality_metrics)."""
+        from .model import map_quality_metrics
+        k = int(k)
+        px = self.tsne_pack(x_table, rows=rows, inv_norm=inv_norm, scratch_bytes=16)
+        py = self.tsne_pack(y_table, rows=rows, scratch_bytes=16)
+        n = px["n"]
+        (kx, _), (ky, _) = self._knn_rows(px, k), self._knn_rows(py, k)
+        rx, ry = self._nbr_ranks(px, k, ky), self._nbr_ranks(py, k, kx)
+        pb, tb = self.buf(np.full(n * 3, -777, np.int32)), self.buf(np.full(4, -777, np.int64))
+        rc = self.lib.gcnhip_mapq_sums(self.ctx, px["pack"].ptr, px["dim"], py["pack"].ptr, py["dim"], n, k, kx.ptr, ky.ptr, rx.ptr, ry.ptr, pb.ptr, tb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_mapq_sums", rc)
+        tot = tb.download()
+        out = dict(knn_x=kx.download().reshape(n, k), knn_y=ky.download().reshape(n, k), rank_x=rx.download().reshape(n, k),
+                   rank_y=ry.download().reshape(n, k), per_position=pb.download().reshape(n, 3), totals=tot)
+        out.update(map_quality_metrics(tot[:3], int(tot[3]), k))
+        return out
+
     # ---- principal components of the rows of a table (csrc/pca.hip): the table is uploaded with its row stride and NaN padding,
     # every output as garbage
     def pca_plan(self, n, dim):

@@ -513,6 +513,39 @@ int gcnhip_dbscan_cores(gcnhip_ctx *ctx, const void *pack, int n, int dim, const
 int gcnhip_dbscan_link(gcnhip_ctx *ctx, const void *pack, int n, int dim, double eps, void *state, size_t state_bytes, int32_t *changed);
 int gcnhip_dbscan_labels(gcnhip_ctx *ctx, const void *pack, int n, int dim, const void *state, size_t state_bytes, int32_t *labels,
                          uint8_t *core, int32_t *sizes, int32_t *counts);
+/* ---- map quality (mapq.hip; beyond the reference: can a drawing of the embeddings be believed?): the exact euclidean k nearest
+ * neighbours of every listed row among the listed rows, the rank of given neighbours in a space's distance order, and from both
+ * trustworthiness and continuity (Venna & Kaski, 2001; scikit-learn's trustworthiness) and the kNN overlap, matrix-free ----
+ * A list of n positions is packed by gcnhip_tsne_pack (gcnhip_mapq_plan's pack_bytes are gcnhip_tsne_plan's); a position that names
+ *   a row outside the table is no POINT and takes part in nothing.  d2_S(i, l) in space S is DBSCAN's: max(0, (xn_i + xn_l) - 2 .
+ *   dot_f32(x^_i, x^_l)), the dot on v_mfma_f32_16x16x4_f32 in column order, with i as the ROW: d2(i, l) and d2(l, i) may differ in
+ *   the last bit, and each row orders its own candidates.
+ * key_S(i, l) = (the bits of d2_S(i, l) as uint32) << 32 | l: a non-negative float's bits keep its order, so the keys order the
+ *   candidates of row i totally, by distance and then by position.  Position i itself is never a candidate.
+ * N_k^S(i) = the k points l != i of smallest key, in ascending key order.  1 <= k <= 32, n <= 2^26.
+ * r_S(i, j) = 1 + #{points l outside {i, j} : key_S(i, l) < key_S(i, j)}: 1 for the nearest neighbour.
+ * With m points, X the input space and Y the map:
+ *   trustworthiness T(k) = 1 - 2 / (m k (2 m - 3 k - 1)) . sum_i sum_{j in N_k^Y(i)} max(r_X(i, j) - k, 0);
+ *   continuity C(k): the same with X and Y exchanged;  overlap = sum_i |N_k^X(i) & N_k^Y(i)| / (m k);  all three need k < m / 2.
+ * Everything a launch writes is an integer (or the f32 d2 of a kept key): the same bits on every launch, no order of summation to
+ *   define.  No launch allocates or synchronises, none uses a float atomic; anything else returns -1 with a message.
+ * gcnhip_mapq_plan: *pack_bytes of the packed image and *scratch_bytes, the room a walk whose columns are cut into parts would need
+ *   for its per-part lists: 0, every row tile walks all of its columns.  Each may be NULL.  No GPU.
+ * gcnhip_knn_rows: pos (device int32 [n x k]) and d2 (device f32 [n x k]) = N_k(i) and its distances; -1 / +inf in the row of a
+ *   position that is no point and in every slot past the m - 1 candidates.
+ * gcnhip_nbr_ranks: rank (device int32 [n x k]) = r(i, targets[i, t]) for targets (device int32 [n x k], positions, -1: none); 0
+ *   where i or the target is no point.  The target's key is formed by the walk's own MFMA chain: the rank of N_k(i)[t] is t + 1.
+ * gcnhip_nbr_d2: the threshold phase of gcnhip_nbr_ranks alone: d2 (device f32 [n x k]) = d2(i, targets[i, t]) with the walk's own bits
+ *   (what gcnhip_knn_rows returns for its own lists), NaN where i or the target is no point.
+ * gcnhip_mapq_sums: knn_x / knn_y = N_k^X / N_k^Y, rank_x = r_X of knn_y's entries, rank_y = r_Y of knn_x's; per_position (device
+ *   int32 [n x 3]) = {sum_t max(rank_x - k, 0), sum_t max(rank_y - k, 0), |N_k^X(i) & N_k^Y(i)|}, zeros where the position is no
+ *   point of both packs; totals (device int64 [4]) = the three column sums and the points. */
+int gcnhip_mapq_plan(int n, int dim, int k, size_t *pack_bytes, size_t *scratch_bytes);
+int gcnhip_knn_rows(gcnhip_ctx *ctx, const void *pack, int n, int dim, int k, int32_t *pos, float *d2);
+int gcnhip_nbr_ranks(gcnhip_ctx *ctx, const void *pack, int n, int dim, int k, const int32_t *targets, int32_t *rank);
+int gcnhip_nbr_d2(gcnhip_ctx *ctx, const void *pack, int n, int dim, int k, const int32_t *targets, float *d2);
+int gcnhip_mapq_sums(gcnhip_ctx *ctx, const void *pack_x, int dim_x, const void *pack_y, int dim_y, int n, int k, const int32_t *knn_x,
+                     const int32_t *knn_y, const int32_t *rank_x, const int32_t *rank_y, int32_t *per_position, int64_t *totals);
 /* ---- principal components of the rows of a table (pca.hip; beyond the reference: the coordinates of what a GCN learns) ----
  * The table contract and the row lists of the k-means calls: a list position whose row is outside the table is skipped and
  * leaves a NaN row in a projection.  x_i[a] = T[r][a] . inv_norm[r] rounded to f32 (inv_norm == NULL: T[r][a]).  No launch

@@ -430,6 +430,23 @@ int gcnhost_model_dbscan(gcnhost_model *m, double eps, int min_samples, int spli
                          int64_t *info);
 int gcnhost_model_neighbor_counts(gcnhost_model *m, const double *eps, int n_eps, int split, const int *nodes, int n, const float *data,
                                   int data_dim, int normalize, int64_t capacity, int32_t *count, int64_t *info);
+/* Map quality (ModelQueries::knn / map_quality, host/queries.h; definitions in include/gcnhip_driver.h, kernels in csrc/mapq.hip).
+ * Rows and `data` as for gcnhost_model_dbscan; 1 <= k <= 32 and at least 2 k + 1 rows.
+ * gcnhost_map_quality_metrics (no GPU): sums int64 [3] = {trust penalty, continuity penalty, shared neighbours} over `points` points
+ *   at k -> out float64 [3] = {trustworthiness, continuity, kNN overlap}; never NaN; refused when k is outside 1..32, points < 2 k + 1
+ *   or a sum is outside its range.
+ * gcnhost_model_knn: ids / pos int32 and d2 f32 [rows listed x k] in room for capacity x k (each may be NULL): per list position its
+ *   k nearest other points by (squared euclidean distance, position), nearest first, as dataset node ids (with data: positions),
+ *   as LIST POSITIONS, and the distances; -1 / -1 / +inf where the position is no point.  info [2] = {rows listed, points}.
+ * gcnhost_model_map_quality: coords f32 [coords_rows x coords_dim], the map by list position (coords_rows must equal the rows
+ *   listed, 1 <= coords_dim <= 256).  per_node int32 [coords_rows x 3] (may be NULL) = {trust penalty, continuity penalty, shared
+ *   neighbours}; info [5] = {rows listed, points, the three sums}; scores float64 [3] = {trustworthiness, continuity, kNN overlap}.
+ * embed's contract: training state is not touched, nothing is cached. */
+int gcnhost_map_quality_metrics(const int64_t *sums, int64_t points, int k, double *out);
+int gcnhost_model_knn(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, int normalize, int64_t capacity,
+                      int32_t *ids, int32_t *pos, float *d2, int64_t *info);
+int gcnhost_model_map_quality(gcnhost_model *m, const float *coords, int64_t coords_rows, int coords_dim, int k, int split, const int *nodes, int n,
+                              const float *data, int data_dim, int normalize, int32_t *per_node, int64_t *info, double *scores);
 /* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
  * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
  * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
