@@ -163,6 +163,12 @@ GCNHIP_SYMBOLS = {
     "gcnhip_components": (I, [P, P, P, P, C.POINTER(I)]),
     "gcnhip_component_counts": (I, [P, P, P, I, P, P, P]),
     "gcnhip_distance_strata": (I, [P, P, P, P, P, I, P, I, I, I, P, P]),
+    "gcnhip_overlap_plan": (I, [P, C.POINTER(I64)]),
+    "gcnhip_overlap_sets": (I, [P, P, P, P, P, I64]),
+    "gcnhip_overlap_rows": (I, [P, P, P, P, P, I, P, P, P, P]),
+    "gcnhip_overlap_rows_ex": (I, [P, P, P, P, P, I, P, P, P, P, I, I, I, I]),
+    "gcnhip_overlap_pairs": (I, [P, P, P, P, P, P, I, P, P, P, P, P]),
+    "gcnhip_overlap_pairs_ex": (I, [P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I]),
     "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
@@ -318,6 +324,11 @@ GCNHOST_SYMBOLS = {
     "gcnhost_reach_metrics": (I, [P, I, I, P, P, P]),
     "gcnhost_reach_write": (I, [C.c_char_p, I, I, P, P, P, I64, P]),
     "gcnhost_reach_read": (I, [C.c_char_p, C.POINTER(I), C.POINTER(I), P, P, P, I64, C.POINTER(I64), P]),
+    "gcnhost_model_clustering": (I, [P, I, P, I, I64, P, P, P, P]),
+    "gcnhost_model_link_overlap": (I, [P, P, P, I, I, P, P, P, P, P, P]),
+    "gcnhost_overlap_metrics": (I, [P, P, P, I64, P, P]),
+    "gcnhost_triangles_write": (I, [C.c_char_p, P, P, P, P, I64]),
+    "gcnhost_triangles_read": (I, [C.c_char_p, P, P, P, P, P, I64, C.POINTER(I64)]),
     "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),
     "gcnhost_model_feature_importance": (I, [P, I, P, I, C.c_size_t, P, P]),
     "gcnhost_calibration_report": (I, [I, P, P, P, P, P, P]),

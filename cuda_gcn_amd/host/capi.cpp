@@ -20,6 +20,7 @@
 #include "pca.h"
 #include "structure.h"
 #include "reach.h"
+#include "overlap.h"
 #include "conformal.h"
 #include "ranking.h"
 #include "thresholds.h"
@@ -645,6 +646,57 @@ int gcnhost_reach_read(const char *path, int *hops, int *layers, int64_t *info, 
     *n_levels = (int64_t)c.level_counts.size();
     for (size_t i = 0; i < c.level_counts.size() && (int64_t)i < level_capacity; i++) level_counts[i] = c.level_counts[i];
     std::copy(c.strata.begin(), c.strata.end(), strata);
+    return 0;
+}
+int gcnhost_model_clustering(gcnhost_model *m, int split, const int *nodes, int n, int64_t capacity, int64_t *t2, int32_t *deg, int64_t *totals,
+                             int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_clustering: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.reach_rows("clustering", split, nodes, n, 0, nullptr, 0, 0, 1, false);
+        if ((t2 || deg) && listed > capacity)
+            throw GcnHipFailure(-1, "clustering: the query lists " + std::to_string(listed) + " rows, the arrays are laid out for " + std::to_string(capacity));
+        const ModelQueries::Overlap r = q.clustering(split, nodes, n, t2, deg, totals);
+        if (info) { info[0] = r.rows; info[1] = r.skipped; }
+    })
+}
+int gcnhost_model_link_overlap(gcnhost_model *m, const int *src, const int *dst, int n, int weight_mask, int32_t *cn, int32_t *un, int64_t *pa,
+                               int64_t *aa, int64_t *ra, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_link_overlap: invalid argument"; return -1; }
+    API_TRY({
+        const ModelQueries::Overlap r = m->gcn->queries().link_overlap(src, dst, n, weight_mask, cn, un, pa, aa, ra);
+        if (info) { info[0] = r.rows; info[1] = r.skipped; }
+    })
+}
+int gcnhost_overlap_metrics(const int64_t *totals, const int64_t *t2, const int32_t *deg, int64_t n, double *summary, double *clustering) {
+    OverlapMetrics r;
+    if (gcn_overlap_metrics(totals, &r, &g_err) != 0) return -1;
+    if (n < 0 || (n > 0 && clustering && (!t2 || !deg))) { g_err = "overlap_metrics: invalid argument"; return -1; }
+    for (int64_t i = 0; clustering && i < n; i++) {
+        if (t2[i] < 0 || deg[i] < 0) { g_err = "overlap_metrics: a negative count"; return -1; }
+        clustering[i] = gcn_overlap_coefficient(t2[i], deg[i]);
+    }
+    if (summary) { summary[0] = (double)r.triangles; summary[1] = r.transitivity; summary[2] = r.avg_clustering; }
+    return 0;
+}
+int gcnhost_triangles_write(const char *path, const int32_t *node, const int32_t *deg, const int64_t *t2, const int64_t *totals, int64_t n) {
+    if (!path || !totals || n < 0 || (n > 0 && (!node || !deg || !t2))) { g_err = "triangles_write: invalid argument"; return -1; }
+    TriangleReport r;
+    std::copy(totals, totals + 8, r.totals);
+    r.node.assign(node, node + n); r.deg.assign(deg, deg + n); r.t2.assign(t2, t2 + n);
+    return gcn_triangles_write(path, r, &g_err);
+}
+int gcnhost_triangles_read(const char *path, int32_t *node, int32_t *deg, int64_t *t2, double *clustering, int64_t *totals, int64_t capacity,
+                           int64_t *n) {
+    if (!path || !n || capacity < 0 || (capacity > 0 && (!node || !deg || !t2))) { g_err = "triangles_read: invalid argument"; return -1; }
+    TriangleReport r;
+    if (gcn_triangles_read(path, &r, &g_err) != 0) return -1;
+    *n = (int64_t)r.node.size();
+    if (totals) std::copy(r.totals, r.totals + 8, totals);
+    for (size_t i = 0; i < r.node.size() && (int64_t)i < capacity; i++) {
+        node[i] = r.node[i]; deg[i] = r.deg[i]; t2[i] = r.t2[i];
+        if (clustering) clustering[i] = gcn_overlap_coefficient(r.t2[i], r.deg[i]);
+    }
     return 0;
 }
 int gcnhost_calibration_report(int bins, const int64_t *count, const int64_t *correct, const double *conf_sum, double *accuracy,

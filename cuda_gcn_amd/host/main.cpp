@@ -133,6 +133,12 @@
 //                            unseeded_components=<n> unseeded_nodes=<n>` ("two hops" is min(2, GCN_REACH_HOPS - 1)).  The file
 //                            gets the per-distance table, the totals and the integers they come from (host/reach.h).  Works with
 //                            GCN_LOAD_WEIGHTS and 0 epochs.
+// Neighbourhood overlap (beyond the reference; ModelQueries::clustering, kernels in csrc/overlap.hip, measures in host/overlap.h),
+// after the test line and the steps above.  One GPU; single- and multi-label models alike:
+//   GCN_TRIANGLES=<file>     the closed wedges t2 (twice the triangles) and the local clustering coefficient of every node of the
+//                            TEST split, counted on the GPU by intersecting neighbour sets.  One line is printed: `triangles=<n>
+//                            transitivity=<t> avg_clustering=<c>` (over the test nodes).  The file gets `node deg t2 clustering`
+//                            per test node behind the totals (host/overlap.h).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
 // Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
 // and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
 //   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
@@ -201,6 +207,7 @@
 #include "ranking.h"
 #include "structure.h"
 #include "reach.h"
+#include "overlap.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -523,6 +530,13 @@ int main(int argc, char **argv) {
             std::cerr << "gcn-hip: GCN_REACH " << why << std::endl;
             return EXIT_FAILURE;
         }
+    }
+
+    const char *triangles_path = getenv("GCN_TRIANGLES");
+    if (triangles_path && !*triangles_path) triangles_path = nullptr;
+    if (triangles_path && env_int("GCN_GPUS", 1) > 1) {
+        std::cerr << "gcn-hip: GCN_TRIANGLES runs on one GPU (GCN_GPUS is above 1)" << std::endl;
+        return EXIT_FAILURE;
     }
 
     const char *explain_path = getenv("GCN_EXPLAIN");
@@ -913,6 +927,20 @@ int main(int argc, char **argv) {
                        rm.all.nearest_accuracy, (long long)rc.totals[1], (long long)rc.totals[2], (long long)rc.totals[3], (long long)rc.totals[4]);
                 fprintf(stderr, "gcn-hip: the reach of %lld test nodes from %lld training nodes (%d distances) written to %s\n", (long long)r.rows,
                         (long long)r.sources, reach_hops, reach_path);
+            }
+            if (triangles_path) {                              // one rank (checked above): the test split
+                TriangleReport tr;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) tr.node.push_back(i);
+                tr.deg.assign(tr.node.size(), 0);
+                tr.t2.assign(tr.node.size(), 0);
+                const ModelQueries::Overlap r = gcn.queries().clustering(3, nullptr, 0, tr.t2.data(), tr.deg.data(), tr.totals);
+                OverlapMetrics om;
+                std::string err;
+                if ((size_t)r.rows != tr.node.size() || gcn_overlap_metrics(tr.totals, &om, &err) != 0 || gcn_triangles_write(triangles_path, tr, &err) != 0)
+                    throw GcnHipFailure(-1, "gcn-hip: " + (err.empty() ? std::string("GCN_TRIANGLES: the test split changed size") : err));
+                printf("triangles=%lld transitivity=%.6f avg_clustering=%.6f\n", (long long)om.triangles, om.transitivity, om.avg_clustering);
+                fprintf(stderr, "gcn-hip: the triangles of %lld test nodes written to %s\n", (long long)r.rows, triangles_path);
             }
             if (explain_path) {                                // one rank (checked above)
                 const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph, the reach of the labels.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph, the reach of the labels, neighbourhood overlap.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -519,6 +519,24 @@ public:
     Reach reach(int split, const int *nodes, int n, int source_mask, const int *source_nodes, int n_sources, int hops, bool predicted, int32_t *dist,
                 int32_t *nearest, int32_t *component, int64_t *strata, int64_t *totals, int64_t *level_counts, int capacity);
 
+    // Neighbourhood overlap (csrc/overlap.hip has the definitions; host/overlap_query.cpp the bodies; host/overlap.h turns the
+    // totals into triangles, transitivity and the mean clustering coefficient, and the pair counts into link scores).  The
+    // adjacency is the model's own object with its stored rows; the neighbour sets are rebuilt per call (gcnhip_overlap_sets) and
+    // nothing is cached.  Rows as the reach queries take them; arrays in list order.  One rank.
+    //   clustering: sync(); the canonical pass; one gcnhip_overlap_rows over the listed rows.  t2 int64 / deg int32 [rows] (each
+    //   may be NULL), totals [8].
+    //   link_overlap: sync(); the canonical pass; the set lengths cross to the host once (one int32 per node), where the
+    //   fixed-point tables of the weights in `weight_mask` (OVERLAP_ADAMIC_ADAR | OVERLAP_RESOURCE_ALLOCATION) are built; one
+    //   gcnhip_overlap_pairs per weight (one without any).  src / dst: n dataset ids each.  cn / un int32, pa (d(a) d(b)), aa / ra
+    //   (the weighted sums, to be divided by 2^32) int64 [n]; each may be NULL.
+    // Needs neither weights nor a forward; single- and multi-label models alike; training state is untouched.  Refused with a
+    // message before any launch: more than one rank, a split outside 0..3, a node id outside the graph, a weight mask with other bits.
+    struct Overlap {
+        int64_t rows = 0, skipped = 0;
+    };
+    Overlap clustering(int split, const int *nodes, int n, int64_t *t2, int32_t *deg, int64_t *totals);
+    Overlap link_overlap(const int *src, const int *dst, int n, int weight_mask, int32_t *cn, int32_t *un, int64_t *pa, int64_t *aa, int64_t *ra);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                       // every device buffer of a query
@@ -674,6 +692,12 @@ private:
     void reach_components(const std::vector<int> &sources, int64_t *totals, Reach &res);
     // one int32 per local row to the host, picked at the listed rows; as_node: rows >= 0 become dataset ids
     void reach_pick(const int32_t *d_per_row, const std::vector<int> &rows, bool as_node, int32_t *out);
+
+    // clustering / link_overlap: the sets (set_idx [nnz], set_len [local rows]), the sort's scratch, {rows | src | dst | deg | cn |
+    // un} as int32, {t2 | wsum | wt | totals [8] | skipped} as int64
+    Scratch<int32_t> d_ov_idx{&arena}, d_ov_len{&arena}, d_ov_sort{&arena}, d_ov_int{&arena};
+    Scratch<int64_t> d_ov_long{&arena};
+    void overlap_sets();                                       // the canonical pass into d_ov_idx / d_ov_len
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

@@ -1157,6 +1157,55 @@ class HipGCNModel:
         return y[:cap]
 
     # ---- label structure of the graph: homophily, class mixing, accuracy by degree and by neighbourhood agreement, on the GPU
+    # ---- neighbourhood overlap: triangles, clustering coefficients and common-neighbour link scores, counted on the GPU
+    def clustering(self, split=None, nodes=None, per_node=True):
+        """Triangles and local clustering coefficients over the model's adjacency, counted on the GPU by intersecting neighbour sets
+        (csrc/overlap.hip has the definitions): the set of a node is the distinct entries of its stored row without itself, t2 its
+        closed wedges (twice its triangles on a symmetric graph), the coefficient t2 / (d (d - 1)), 0 below two neighbours.  Rows:
+        the nodes of `split` in ascending id, or the `nodes` query (dataset ids, repeats counted as often as listed), or with both
+        None every node.  Returns overlap_metrics() of the totals (triangles, transitivity, avg_clustering) plus totals int64 [8],
+        rows, and with per_node t2 int64, deg int32 and clustering float64 [rows].  The sets are rebuilt per call.  Needs neither
+        weights nor a forward; single- and multi-label models alike; one rank.  Training state is not touched."""
+        what = "clustering"
+        code, q, n, cap = self._structure_query(what, split, nodes)
+        t2, deg = (np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)) if per_node else (None, None)
+        totals, info = np.zeros(8, np.int64), np.zeros(2, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_clustering(self.h, code, q.ctypes.data if q is not None else None, n, cap, t2.ctypes.data if per_node else None,
+                                                        deg.ctypes.data if per_node else None, totals.ctypes.data, info.ctypes.data), what)
+        rows = int(info[0])
+        out = overlap_metrics(totals, t2[:rows], deg[:rows]) if per_node else overlap_metrics(totals)
+        out.update(totals=totals, rows=rows)
+        if per_node:
+            out.update(t2=t2[:rows].copy(), deg=deg[:rows].copy())
+        return out
+
+    def link_overlap(self, src, dst, weights=("adamic_adar", "resource_allocation")):
+        """The neighbourhood baselines of link prediction for the pairs (src[i], dst[i]) of dataset ids, counted on the GPU
+        (csrc/overlap.hip): common = |S(a) & S(b)|, jaccard = common / |S(a) | S(b)| (0 for two empty sets), preferential_attachment
+        = d(a) d(b), and per name in `weights` the sum over the common neighbours w of 1 / ln d(w) (adamic_adar) or 1 / d(w)
+        (resource_allocation), summed as exact integers over a 2^-32 fixed-point table: within common . 2^-33 of the float64 sum
+        and the same bits on every run.  a == b is allowed.  Returns a dict of arrays [pairs].  score_edges() is the embedding-based
+        counterpart.  Needs neither weights nor a forward; one rank.  Training state is not touched."""
+        what = "link_overlap"
+        kinds = {"adamic_adar": 1, "resource_allocation": 2}
+        weights = (weights,) if isinstance(weights, str) else tuple(weights)
+        if any(w not in kinds for w in weights):
+            raise GcnHostError(f"{what}: the weights are 'adamic_adar' and 'resource_allocation', got {weights!r}")
+        s, d = np.ascontiguousarray(src, np.int32).ravel(), np.ascontiguousarray(dst, np.int32).ravel()
+        if s.size != d.size:
+            raise GcnHostError(f"{what}: src and dst list {s.size} and {d.size} nodes")
+        n = int(s.size)
+        cn, un = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        pa, aa, ra, info = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64), np.zeros(2, np.int64)
+        one = np.zeros(1, np.int32)
+        _ck(self.lib, self.lib.gcnhost_model_link_overlap(self.h, (s if n else one).ctypes.data, (d if n else one).ctypes.data, n, sum({kinds[w] for w in weights}),
+                                                          cn.ctypes.data, un.ctypes.data, pa.ctypes.data, aa.ctypes.data, ra.ctypes.data, info.ctypes.data), what)
+        cn, un = cn[:n], un[:n]
+        out = dict(common=cn.copy(), jaccard=np.divide(cn, un, out=np.zeros(n, np.float64), where=un > 0), preferential_attachment=pa[:n].copy())
+        for w in weights:
+            out[w] = (aa if w == "adamic_adar" else ra)[:n] / 2.0 ** 32
+        return out
+
     def _structure_query(self, what, split, nodes):
         """argument checks that need no GPU; returns (split code, node ids int32 or None, n, capacity)"""
         if split is not None and nodes is not None:
@@ -1828,6 +1877,53 @@ def _reach_strata(what, strata, hops):
     if isinstance(hops, bool) or not isinstance(hops, (int, np.integer)) or not 1 <= hops <= 32 or st.shape != (hops + 2, 4):
         raise GcnHostError(f"{what}: strata must have shape (hops + 2, 4) with 1 <= hops <= 32, got {st.shape} with hops = {hops!r}")
     return st, int(hops)
+
+
+def overlap_metrics(totals, t2=None, deg=None):
+    """Triangles, transitivity and the mean clustering coefficient out of the integer totals of a row query — host only, no GPU;
+    the one place they are derived (host/overlap.h).  totals int [8] = {rows, rows with d >= 2, sum d, sum d (d - 1), sum t2, max t2,
+    max d, ratio_sum}.  Returns dict(triangles = sum t2 // 6, transitivity = sum t2 / sum D, avg_clustering = ratio_sum / 2^32 /
+    rows), and with t2 and deg [n] also clustering float64 [n] = t2 / (d (d - 1)), 0 when d < 2.  A zero denominator gives 0, never
+    NaN.  A negative count or a mismatched shape raises GcnHostError."""
+    what = "overlap_metrics"
+    t = np.ascontiguousarray(totals, np.int64).ravel()
+    if t.size != 8 or (t2 is None) != (deg is None):
+        raise GcnHostError(f"{what}: totals holds 8 integers, and t2 and deg come together")
+    lib = _lib.gcnhost()
+    s = np.zeros(3, np.float64)
+    if t2 is None:
+        _ck(lib, lib.gcnhost_overlap_metrics(t.ctypes.data, None, None, 0, s.ctypes.data, None), what)
+        return dict(triangles=int(s[0]), transitivity=float(s[1]), avg_clustering=float(s[2]))
+    a, d = np.ascontiguousarray(t2, np.int64).ravel(), np.ascontiguousarray(deg, np.int32).ravel()
+    if a.size != d.size:
+        raise GcnHostError(f"{what}: t2 and deg list {a.size} and {d.size} rows")
+    c = np.zeros(max(a.size, 1), np.float64)
+    _ck(lib, lib.gcnhost_overlap_metrics(t.ctypes.data, a.ctypes.data, d.ctypes.data, a.size, s.ctypes.data, c.ctypes.data), what)
+    return dict(triangles=int(s[0]), transitivity=float(s[1]), avg_clustering=float(s[2]), clustering=c[:a.size])
+
+
+def write_triangles(path, node, deg, t2, totals):
+    """the text report gcn-hip writes for GCN_TRIANGLES: `node deg t2 clustering` per listed node behind the totals"""
+    lib = _lib.gcnhost()
+    v, d, a = np.ascontiguousarray(node, np.int32).ravel(), np.ascontiguousarray(deg, np.int32).ravel(), np.ascontiguousarray(t2, np.int64).ravel()
+    t = np.ascontiguousarray(totals, np.int64).ravel()
+    if not (v.size == d.size == a.size) or t.size != 8:
+        raise GcnHostError("write_triangles: node, deg and t2 list the same rows, totals holds 8 integers")
+    _ck(lib, lib.gcnhost_triangles_write(os.fspath(path).encode(), v.ctypes.data, d.ctypes.data, a.ctypes.data, t.ctypes.data, v.size), "write_triangles")
+
+
+def read_triangles(path):
+    """a triangle report file without a GPU: dict(node, deg int32, t2 int64, clustering float64 [rows], totals int64 [8]) plus
+    overlap_metrics() of the totals"""
+    lib = _lib.gcnhost()
+    fn, n, totals = os.fspath(path).encode(), C.c_int64(), np.zeros(8, np.int64)
+    _ck(lib, lib.gcnhost_triangles_read(fn, None, None, None, None, totals.ctypes.data, 0, C.byref(n)), "read_triangles")
+    k = max(n.value, 1)
+    v, d, a, c = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int64), np.zeros(k, np.float64)
+    _ck(lib, lib.gcnhost_triangles_read(fn, v.ctypes.data, d.ctypes.data, a.ctypes.data, c.ctypes.data, totals.ctypes.data, k, C.byref(n)), "read_triangles")
+    out = overlap_metrics(totals)
+    out.update(node=v[:n.value], deg=d[:n.value], t2=a[:n.value], clustering=c[:n.value], totals=totals)
+    return out
 
 
 def reach_metrics(strata, hops=None, layers=2):

@@ -1180,6 +1180,66 @@ class Device:
             self._embed_fail("gcnhip_distance_strata", rc)
         return ob.download().reshape(h + 2, 4), int(ub.download()[0])
 
+    # ---- neighbourhood overlap (csrc/overlap.hip): every output is uploaded as garbage, the calls write all of it
+    def overlap_sets(self, g):
+        """gcnhip_overlap_plan + gcnhip_overlap_sets on a Graph: (set_idx Buf int32 [nnz], set_len Buf int32 [n_rows]) — row v's sorted
+        set is set_idx[indptr[v] : indptr[v] + set_len[v]]"""
+        need = C.c_int64(-777)
+        rc = self.lib.gcnhip_overlap_plan(g.h, C.byref(need))
+        if rc != 0:
+            self._embed_fail("gcnhip_overlap_plan", rc)
+        nr, nnz = C.c_int(), C.c_int()
+        _ck(self.lib, self.lib.gcnhip_graph_arrays(g.h, None, None, None, C.byref(nr), C.byref(nnz)), "graph_arrays")
+        ib = self.buf(np.full(max(nnz.value, 1), 0x5A5A5A5A, np.int32))
+        lb = self.buf(np.full(max(nr.value, 1), 0x5A5A5A5A, np.int32))
+        sb = self.buf(np.full(max(need.value // 4, 4), 0x5A5A5A5A, np.int32))
+        rc = self.lib.gcnhip_overlap_sets(self.ctx, g.h, ib.ptr, lb.ptr, sb.ptr, need.value)
+        if rc != 0:
+            self._embed_fail("gcnhip_overlap_sets", rc)
+        return ib, lb
+
+    def overlap_rows(self, g, sets, rows=None, n=None, want=("t2", "deg"), group=0, wg_cut=0, slice=0, bitmap=1):
+        """gcnhip_overlap_rows(_ex) on a Graph and the (set_idx, set_len) of overlap_sets: dict(t2 int64 [n], deg int32 [n] by list
+        position, totals int64 [8], skipped); outputs not named in `want` are passed as NULL and come back as None.  group / wg_cut
+        / slice / bitmap: anything but the defaults goes through gcnhip_overlap_rows_ex."""
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()
+        n = (g.n_rows if n is None else int(n)) if r is None else int(r.size)
+        rb = None if r is None else self.buf(r if n > 0 else np.zeros(1, np.int32))
+        tb = self.buf(np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, np.int64)) if "t2" in want else None
+        db = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)) if "deg" in want else None
+        ob, kb = self.buf(np.full(8, -777, np.int64)), self.buf(np.full(1, -777, np.int64))
+        args = (self.ctx, g.h, sets[0].ptr, sets[1].ptr, rb.ptr if rb else None, n, tb.ptr if tb else None, db.ptr if db else None, ob.ptr, kb.ptr)
+        if group or wg_cut or slice or bitmap != 1:
+            rc = self.lib.gcnhip_overlap_rows_ex(*args, int(group), int(wg_cut), int(slice), int(bitmap))
+        else:
+            rc = self.lib.gcnhip_overlap_rows(*args)
+        if rc != 0:
+            self._embed_fail("gcnhip_overlap_rows", rc)
+        return dict(t2=tb.download()[:n] if tb else None, deg=db.download()[:n] if db else None, totals=ob.download(), skipped=int(kb.download()[0]))
+
+    def overlap_pairs(self, g, sets, src, dst, wt=None, want=("cn", "un", "wsum"), group=0, wg_cut=0, slice=0, bitmap=1):
+        """gcnhip_overlap_pairs(_ex): dict(cn, un int32 [n], wsum int64 [n], skipped); wt: int64 per column or None"""
+        s, d = np.ascontiguousarray(src, np.int32).ravel(), np.ascontiguousarray(dst, np.int32).ravel()
+        n = int(s.size)
+        assert d.size == n
+        one = np.zeros(1, np.int32)
+        sb, eb = self.buf(s if n else one), self.buf(d if n else one)
+        wb = None if wt is None else self.buf(np.ascontiguousarray(wt, np.int64).ravel())
+        cb = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)) if "cn" in want else None
+        ub = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)) if "un" in want else None
+        xb = self.buf(np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, np.int64)) if "wsum" in want else None
+        kb = self.buf(np.full(1, -777, np.int64))
+        args = (self.ctx, g.h, sets[0].ptr, sets[1].ptr, sb.ptr, eb.ptr, n, wb.ptr if wb else None, cb.ptr if cb else None, ub.ptr if ub else None,
+                xb.ptr if xb else None, kb.ptr)
+        if group or wg_cut or slice or bitmap != 1:
+            rc = self.lib.gcnhip_overlap_pairs_ex(*args, int(group), int(wg_cut), int(slice), int(bitmap))
+        else:
+            rc = self.lib.gcnhip_overlap_pairs(*args)
+        if rc != 0:
+            self._embed_fail("gcnhip_overlap_pairs", rc)
+        return dict(cn=cb.download()[:n] if cb else None, un=ub.download()[:n] if ub else None, wsum=xb.download()[:n] if xb else None,
+                    skipped=int(kb.download()[0]))
+
     # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
     def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,
                       store=True):

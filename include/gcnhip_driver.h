@@ -638,6 +638,40 @@ int gcnhip_component_counts(gcnhip_ctx *ctx, const int32_t *comp, const int32_t 
                             int64_t *totals);
 int gcnhip_distance_strata(gcnhip_ctx *ctx, const int32_t *dist, const int32_t *nearest, const int32_t *pred, const int32_t *truth,
                            int n_rows, const int32_t *d_rows, int n, int num_classes, int hops, int64_t *strata, int64_t *unlabelled);
+/* ---- neighbourhood overlap (overlap.hip; beyond the reference: triangles, clustering coefficients, common-neighbour link scores) ----
+ * g: an adjacency object with its stored rows (unsorted, repeated, self and one-way entries allowed), square or with columns beyond
+ * its rows that name no row (n_cols >= n_rows).  All integer work: the same bits from every launch, lane group and cut.
+ * NEIGHBOUR SET S(v) = the distinct u stored in row v with u != v and 0 <= u < n_rows; d(v) = |S(v)|; no transpose is built.
+ * t2(v) = sum over u in S(v) of |S(v) n S(u)| (twice the triangles through v on a symmetric graph); D(v) = d(v) (d(v) - 1); the
+ * local clustering coefficient is t2 / D, 0 when d < 2.  A pair (a, b), a == b allowed: cn = |S(a) n S(b)|, un = d(a) + d(b) - cn,
+ * wsum = sum over w in S(a) n S(b) of wt[w] (int64 per column, NULL: 0; exact modulo 2^64).
+ * gcnhip_overlap_plan: *scratch_bytes (host) = what gcnhip_overlap_sets needs: the longest row above 4096 stored entries as u32.
+ * gcnhip_overlap_sets: set_idx device int32 [nnz], 16-byte aligned; set_len device int32 [n_rows]: row v's sorted set goes to
+ *   set_idx[indptr[v] .. indptr[v] + set_len[v]) (the rest of the row's extent is unspecified).  Rows of up to 64 stored entries
+ *   are sorted by a wave, up to 4096 by a workgroup in LDS, longer ones one after the other by gcnhip_sort_segments_u32.
+ * gcnhip_overlap_rows: n positions, d_rows[i] the row of position i (NULL: row i, n <= n_rows; repeats count as often as listed; a
+ *   row outside [0, n_rows) counts in *skipped and gives zeros).  t2 device int64 [n], deg device int32 [n] (each may be NULL);
+ *   totals device int64 [8] = {listed rows in range, rows with d >= 2, sum d, sum D, sum t2, max t2, max d, ratio_sum}, ratio_sum =
+ *   the sum over rows with d >= 2 of floor(t2 . 2^32 / D); skipped device int64 [1].
+ * gcnhip_overlap_pairs: src / dst device int32 [n_pairs]; cn / un device int32, wsum device int64 [n_pairs] (each may be NULL); a
+ *   pair with an end outside [0, n_rows) gives zeros and counts in *skipped.
+ * The _ex forms take the lane group per row or pair (0: by the mean stored row length; 4, 16, 64), the set length above which a
+ * row goes to the whole workgroup and the LDS slice of a lane group in entries (0: the defaults, 32 x group each) and bitmap
+ * (1: workgroup rows use an LDS bitmap when it fits; 0: never).  Every call zeroes its totals, allocates nothing and synchronises
+ * nothing.  Refused with -1 and a message (gcnhip_last_error) before any launch: a NULL required pointer, a negative count, fewer
+ * columns than rows, a row of 2^24 or more stored entries, a set_idx that is not 16-byte aligned, too little scratch, a lane group
+ * other than 0 / 4 / 16 / 64, a negative cut or slice, slices beyond the device's LDS. */
+int gcnhip_overlap_plan(const gcnhip_graph *g, int64_t *scratch_bytes);
+int gcnhip_overlap_sets(gcnhip_ctx *ctx, const gcnhip_graph *g, int32_t *set_idx, int32_t *set_len, void *scratch, int64_t scratch_bytes);
+int gcnhip_overlap_rows(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *set_idx, const int32_t *set_len, const int32_t *d_rows, int n,
+                        int64_t *t2, int32_t *deg, int64_t *totals, int64_t *skipped);
+int gcnhip_overlap_rows_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *set_idx, const int32_t *set_len, const int32_t *d_rows, int n,
+                           int64_t *t2, int32_t *deg, int64_t *totals, int64_t *skipped, int group, int wg_cut, int slice, int bitmap);
+int gcnhip_overlap_pairs(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *set_idx, const int32_t *set_len, const int32_t *src,
+                         const int32_t *dst, int n_pairs, const int64_t *wt, int32_t *cn, int32_t *un, int64_t *wsum, int64_t *skipped);
+int gcnhip_overlap_pairs_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *set_idx, const int32_t *set_len, const int32_t *src,
+                            const int32_t *dst, int n_pairs, const int64_t *wt, int32_t *cn, int32_t *un, int64_t *wsum, int64_t *skipped,
+                            int group, int wg_cut, int slice, int bitmap);
 /* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
  * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
  * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and

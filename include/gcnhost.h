@@ -548,6 +548,26 @@ int gcnhost_reach_write(const char *path, int hops, int layers, const int64_t *i
                         int64_t n_levels, const int64_t *strata);
 int gcnhost_reach_read(const char *path, int *hops, int *layers, int64_t *info, int64_t *totals, int64_t *level_counts, int64_t level_capacity,
                        int64_t *n_levels, int64_t *strata);
+/* Neighbourhood overlap (ModelQueries::clustering / link_overlap, host/queries.h; kernels and definitions in csrc/overlap.hip;
+ * measures in host/overlap.h).  The neighbour set of a node is the distinct entries of its stored row without itself; t2 = the
+ * closed wedges of a node (twice its triangles on a symmetric graph).  Rows as the reach queries take them; one rank; single- and
+ * multi-label models alike; no weights and no forward are needed; training state is not touched.
+ * gcnhost_model_clustering: t2 int64 / deg int32 [rows] by list position (each may be NULL; laid out for `capacity` rows), totals
+ *   [8] = {rows, rows with d >= 2, sum d, sum d (d - 1), sum t2, max t2, max d, ratio_sum}, info [2] = {rows listed, skipped}.
+ * gcnhost_model_link_overlap: src / dst: n dataset ids each; weight_mask: 1 adamic_adar | 2 resource_allocation; cn / un int32,
+ *   pa = d(a) d(b), aa / ra int64 [n] (a weighted score is its sum / 2^32); each may be NULL; info [2] = {pairs, skipped}.
+ * gcnhost_overlap_metrics (no GPU): summary [3] = {triangles = sum t2 / 6, transitivity = sum t2 / sum D, avg_clustering =
+ *   ratio_sum / 2^32 / rows}; clustering [n] = t2 / (d (d - 1)), 0 when d < 2 (NULL: not wanted).  A zero denominator gives 0.
+ * gcnhost_triangles_write / _read: the text report gcn-hip writes for GCN_TRIANGLES (`node deg t2 clustering` per line); the reader
+ *   copies at most `capacity` rows and tells their number in *n. */
+int gcnhost_model_clustering(gcnhost_model *m, int split, const int *nodes, int n, int64_t capacity, int64_t *t2, int32_t *deg, int64_t *totals,
+                             int64_t *info);
+int gcnhost_model_link_overlap(gcnhost_model *m, const int *src, const int *dst, int n, int weight_mask, int32_t *cn, int32_t *un, int64_t *pa,
+                               int64_t *aa, int64_t *ra, int64_t *info);
+int gcnhost_overlap_metrics(const int64_t *totals, const int64_t *t2, const int32_t *deg, int64_t n, double *summary, double *clustering);
+int gcnhost_triangles_write(const char *path, const int32_t *node, const int32_t *deg, const int64_t *t2, const int64_t *totals, int64_t n);
+int gcnhost_triangles_read(const char *path, int32_t *node, int32_t *deg, int64_t *t2, double *clustering, int64_t *totals, int64_t capacity,
+                           int64_t *n);
 /* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
  * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
  * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
