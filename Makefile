@@ -23,8 +23,8 @@ $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(wildcard $(PKG)/csrc/*.h) $(wildcard include/
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# the f32 entry arithmetic of tsne.hip, dbscan.hip and mapq.hip is kept off the packed-f32 instructions (overlap.hip has none)
-$(OBJDIR)/tsne.o $(OBJDIR)/dbscan.o $(OBJDIR)/mapq.o $(OBJDIR)/overlap.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# the f32 entry arithmetic of tsne.hip, dbscan.hip, mapq.hip and hdbscan.hip is kept off the packed-f32 instructions (overlap.hip has none)
+$(OBJDIR)/tsne.o $(OBJDIR)/dbscan.o $(OBJDIR)/mapq.o $(OBJDIR)/hdbscan.o $(OBJDIR)/overlap.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIBDIR)/libgcnhip.so: $(KOBJ)
 	@mkdir -p $(LIBDIR)

@@ -146,6 +146,10 @@ GCNHIP_SYMBOLS = {
     "gcnhip_dbscan_cores": (I, [P, P, I, I, P, I, P, C.c_size_t]),
     "gcnhip_dbscan_link": (I, [P, P, I, I, C.c_double, P, C.c_size_t, P]),
     "gcnhip_dbscan_labels": (I, [P, P, I, I, P, C.c_size_t, P, P, P, P]),
+    "gcnhip_hdbscan_plan": (I, [I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_hdbscan_start": (I, [P, P, I, I, P, I, P, C.c_size_t]),
+    "gcnhip_hdbscan_nearest": (I, [P, P, I, I, P, C.c_size_t]),
+    "gcnhip_hdbscan_merge": (I, [P, P, I, I, P, C.c_size_t, P, P]),
     "gcnhip_mapq_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_knn_rows": (I, [P, P, I, I, I, P, P]),
     "gcnhip_nbr_ranks": (I, [P, P, I, I, I, P, P]),
@@ -306,6 +310,9 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_tsne": (I, [P, I, I, P, I, P, I, C.c_double, I, C.c_double, I, C.c_double, I, P, I, C.c_size_t, I64, P, P, P, P, P]),
     "gcnhost_model_dbscan": (I, [P, C.c_double, I, I, P, I, P, I, I, I64, P, P, P, P, P, P]),
     "gcnhost_model_neighbor_counts": (I, [P, P, I, I, P, I, P, I, I, I64, P, P]),
+    "gcnhost_hdbscan_tree": (I, [P, P, P, I64, I64, I, I, I, P, P, P, P]),
+    "gcnhost_hdbscan_cut": (I, [P, P, P, I64, I64, C.c_double, I, P, P]),
+    "gcnhost_model_hdbscan": (I, [P, I, I, I, P, I, P, I, I, I, I, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_map_quality_metrics": (I, [P, I64, I, P]),
     "gcnhost_model_knn": (I, [P, I, I, P, I, P, I, I, I64, P, P, P, P]),
     "gcnhost_model_map_quality": (I, [P, P, I64, I, I, I, P, I, P, I, I, P, P, P]),

@@ -17,6 +17,7 @@
 #include "report.h"
 #include "calibration.h"
 #include "kmeans.h"
+#include "hdbscan.h"
 #include "pca.h"
 #include "structure.h"
 #include "reach.h"
@@ -437,6 +438,31 @@ int gcnhost_model_map_quality(gcnhost_model *m, const float *coords, int64_t coo
             m->gcn->queries().map_quality(coords, coords_rows, coords_dim, k, split, nodes, n, data, data_dim, normalize != 0, per_node);
         if (info) { info[0] = r.rows; info[1] = r.points; info[2] = r.sums[0]; info[3] = r.sums[1]; info[4] = r.sums[2]; }
         if (scores) { scores[0] = r.trustworthiness; scores[1] = r.continuity; scores[2] = r.knn_overlap; }
+    })
+}
+int gcnhost_hdbscan_tree(const int32_t *lo, const int32_t *hi, const double *d2, int64_t edges, int64_t n, int min_cluster_size, int leaf,
+                         int allow_single_cluster, int32_t *labels, double *probabilities, double *linkage, int64_t *info) {
+    return gcn_hdbscan_tree(lo, hi, d2, edges, n, min_cluster_size, leaf != 0, allow_single_cluster != 0, labels, probabilities, linkage, info, &g_err);
+}
+int gcnhost_hdbscan_cut(const int32_t *lo, const int32_t *hi, const double *d2, int64_t edges, int64_t n, double distance, int min_cluster_size,
+                        int32_t *labels, int64_t *info) {
+    return gcn_hdbscan_cut(lo, hi, d2, edges, n, distance, min_cluster_size, labels, info, &g_err);
+}
+int gcnhost_model_hdbscan(gcnhost_model *m, int min_cluster_size, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim,
+                          int normalize, int leaf, int allow_single_cluster, int64_t capacity, int32_t *labels, double *probabilities, float *core2,
+                          int32_t *mst_lo, int32_t *mst_hi, float *mst_d2, double *linkage, int32_t *sizes, int64_t *contingency, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_hdbscan: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t listed = q.hdbscan_rows(min_cluster_size, min_samples, split, nodes, n, data, data_dim);
+        if (listed > capacity)
+            throw GcnHipFailure(-1, "hdbscan: the query lists " + std::to_string(listed) + " rows, the outputs have room for " + std::to_string(capacity));
+        const ModelQueries::Hdbscan r = q.hdbscan(min_cluster_size, min_samples, split, nodes, n, data, data_dim, normalize != 0, leaf != 0,
+                                                  allow_single_cluster != 0, labels, probabilities, core2, mst_lo, mst_hi, mst_d2, linkage, sizes, contingency);
+        if (info) {
+            info[0] = r.rows; info[1] = r.points; info[2] = r.clusters; info[3] = r.noise; info[4] = r.rounds; info[5] = r.edges;
+            info[6] = r.contingency_rows; info[7] = r.skipped;
+        }
     })
 }
 int gcnhost_sym_eigen(const double *S, int h, double *lambda, double *V) { return gcn_sym_eigen(S, h, lambda, V, &g_err); }

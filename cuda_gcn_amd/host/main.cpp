@@ -174,6 +174,13 @@
 //                            GPU.  One line is printed: `dbscan_eps=<e> dbscan_min_samples=<m> dbscan_clusters=<k> dbscan_core=<n>
 //                            dbscan_border=<n> dbscan_noise=<n>`.  The file gets one line per test node in id order: `node label
 //                            core count` (label -1: noise; count: the nodes within eps, itself included).
+// HDBSCAN of the embeddings (beyond the reference; ModelQueries::hdbscan, kernels in csrc/hdbscan.hip, the tree's reading in
+// host/hdbscan.h), after the DBSCAN labels.  One GPU, hidden_dim at most 256, f32 tables, at most 65536 test nodes:
+//   GCN_HDBSCAN=<file>       the density clusters of the unit rows of the hidden layer of the TEST nodes without a radius, with
+//                            GCN_HDBSCAN_MIN_CLUSTER_SIZE (default 5) and GCN_HDBSCAN_MIN_SAMPLES (default: the cluster size; 1..33).
+//                            One line is printed: `hdbscan_min_cluster_size=<m> hdbscan_min_samples=<s> hdbscan_clusters=<k>
+//                            hdbscan_noise=<n> hdbscan_rounds=<r>`.  The file gets one line per test node in id order: `node label
+//                            probability` (label -1: noise; %.17g).
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -499,6 +506,23 @@ int main(int argc, char **argv) {
                                                                             : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_DBSCAN " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *hdbscan_path = getenv("GCN_HDBSCAN");
+    if (hdbscan_path && !*hdbscan_path) hdbscan_path = nullptr;
+    const int hdbscan_min_cluster_size = env_int("GCN_HDBSCAN_MIN_CLUSTER_SIZE", 5);
+    const int hdbscan_min_samples = env_int("GCN_HDBSCAN_MIN_SAMPLES", hdbscan_min_cluster_size);
+    if (hdbscan_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1                                 ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                                  ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                            ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : hdbscan_min_cluster_size < 2                             ? "needs GCN_HDBSCAN_MIN_CLUSTER_SIZE of at least 2"
+                          : hdbscan_min_samples < 1 || hdbscan_min_samples > 33      ? "needs GCN_HDBSCAN_MIN_SAMPLES in 1..33"
+                                                                                     : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_HDBSCAN " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -1097,6 +1121,27 @@ int main(int argc, char **argv) {
                 if (f2 && fclose(f2) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the DBSCAN labels to ") + dbscan_path);
                 fprintf(stderr, "gcn-hip: the DBSCAN labels of %zu test nodes written to %s\n", n, dbscan_path);
+            }
+            if (hdbscan_path) {                                // one rank (checked above): the test nodes in id order
+                ModelQueries &q = gcn.queries();
+                std::vector<int> ids;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) ids.push_back(i);
+                const size_t n = ids.size();
+                if (n < 1) throw GcnHipFailure(-1, "gcn-hip: GCN_HDBSCAN found no test nodes to cluster");
+                std::vector<int32_t> label(n);
+                std::vector<double> prob(n);
+                const ModelQueries::Hdbscan r = q.hdbscan(hdbscan_min_cluster_size, hdbscan_min_samples, 3, nullptr, 0, nullptr, 0, true, false, false,
+                                                          label.data(), prob.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+                if ((size_t)r.rows != n) throw GcnHipFailure(-1, "gcn-hip: GCN_HDBSCAN listed other rows than the test nodes");
+                printf("hdbscan_min_cluster_size=%d hdbscan_min_samples=%d hdbscan_clusters=%lld hdbscan_noise=%lld hdbscan_rounds=%lld\n",
+                       hdbscan_min_cluster_size, hdbscan_min_samples, (long long)r.clusters, (long long)r.noise, (long long)r.rounds);
+                FILE *f2 = fopen(hdbscan_path, "w");
+                bool ok = f2 != nullptr;
+                for (size_t i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %d %.17g\n", ids[i], label[i], prob[i]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the HDBSCAN labels to ") + hdbscan_path);
+                fprintf(stderr, "gcn-hip: the HDBSCAN labels of %zu test nodes written to %s\n", n, hdbscan_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

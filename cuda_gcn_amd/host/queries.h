@@ -419,6 +419,29 @@ public:
     MapQuality map_quality(const float *coords, int64_t coords_rows, int coords_dim, int k, int split, const int *nodes, int n, const float *data,
                            int data_dim, bool normalize, int32_t *per_node);
 
+    // HDBSCAN of the hidden layer (Campello, Moulavi & Sander, 2013; include/gcnhip_driver.h has the definitions of the tree,
+    // csrc/hdbscan.hip the kernels, host/hdbscan.h what is derived from the tree, host/hdbscan_query.cpp the body): the density
+    // clusters without a radius.  Rows and `data` as for dbscan.  Steps: sync(); embed_forward; gcnhip_tsne_pack; gcnhip_knn_rows at
+    // k = min_samples - 1 when that is above 0; gcnhip_hdbscan_start; Boruvka rounds of gcnhip_hdbscan_nearest and _merge, enqueued
+    // HDBSCAN_BATCH at a time with their counts read back together, until one component is left; the edge list to the host, sorted by
+    // (w, lo, hi); gcn_hdbscan_tree.  Outputs, each may be NULL: labels int32 / probabilities float64 / core2 f32 / sizes int32 [rows]
+    // by list position (sizes: the first `clusters` entries), mst_lo / mst_hi int32 and mst_d2 f32 [rows] (the first `edges` entries,
+    // sorted), linkage float64 [(rows - 1) x 4] (the first `edges` rows), contingency [clusters x C] against the dataset's labels over
+    // the non-noise points (filled when given, the rows are nodes and 1 <= clusters <= 256: then contingency_rows = clusters).
+    // Training state is untouched, the query owns its device buffers and nothing is cached.  Refused with a message before any
+    // launch: what dbscan refuses for its rows, min_cluster_size < 2, min_samples outside 1..33, more than 65536 rows, fewer rows
+    // (after the pack: points) than 2 (min_samples - 1) + 1.
+    struct Hdbscan {
+        int64_t rows = 0, points = 0, clusters = 0, noise = 0, rounds = 0, edges = 0, contingency_rows = 0, skipped = 0;
+    };
+    static constexpr int HDBSCAN_BATCH = 2;
+    static constexpr int64_t HDBSCAN_MAX_ROWS = 65536;
+    int64_t hdbscan_rows(int min_cluster_size, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim,
+                         std::vector<int> *rows = nullptr);
+    Hdbscan hdbscan(int min_cluster_size, int min_samples, int split, const int *nodes, int n, const float *data, int data_dim, bool normalize,
+                    bool leaf, bool allow_single_cluster, int32_t *labels, double *probabilities, float *core2, int32_t *mst_lo, int32_t *mst_hi,
+                    float *mst_d2, double *linkage, int32_t *sizes, int64_t *contingency);
+
     // Principal components of the hidden layer (Pearson, 1901; Hotelling, 1933): the rows embed() exports, reduced where they lie
     // (csrc/pca.hip has the definitions of the sums; host/pca.h the eigenproblem and what is derived from it; host/pca_query.cpp
     // the bodies).  Rows as kmeans lists them: the nodes of `split` (1..3) in ascending dataset id, or with split == 0 the
@@ -666,6 +689,12 @@ private:
     void mapq_points(const char *what, int k, int64_t points) const;
     int mapq_pack(const std::vector<int> &rows, int n, int k, const float *data, int data_dim, bool normalize, Scratch<unsigned char> &pack,
                   int32_t *d_rows, int32_t *d_points);
+    // hdbscan: {rows | labels | edges [3 x n] | knn positions | points | counts}, the contingency, the pack, the rounds' state, the
+    // kNN distances, the caller's table
+    Scratch<int32_t> d_hd_int{&arena}, d_hd_cont{&arena};
+    Scratch<unsigned char> d_hd_pack{&arena}, d_hd_state{&arena};
+    Scratch<float> d_hd_f32{&arena}, d_hd_data{&arena};
+    void hdbscan_points(int min_samples, int64_t have, const char *what) const;
     // pca_fit / pca_project: the listed rows, the valid count, {mean [h] | scatter [h x h]}, {mean | basis [h x k] | scale [k]} of
     // a projection, its coordinates, the sums' scratch
     Scratch<int32_t> d_pca_rows{&arena}, d_pca_count{&arena};

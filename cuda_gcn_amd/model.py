@@ -1132,6 +1132,51 @@ class HipGCNModel:
             out.update(trust_penalty=per[:, 0].copy(), cont_penalty=per[:, 1].copy(), shared=per[:, 2].copy())
         return out
 
+    def hdbscan(self, min_cluster_size=5, min_samples=None, split=None, nodes=None, normalize=True, data=None, cluster_selection_method="eom",
+                allow_single_cluster=False, report=True):
+        """HDBSCAN (Campello, Moulavi & Sander, 2013; scikit-learn's HDBSCAN, euclidean) of the rows embed() exports: dbscan() without
+        an eps.  Run where the rows lie and matrix-free: one evaluation forward, the rows packed once, the core distances from the
+        exact kNN walk at k = min_samples - 1 (scikit-learn's rule: the point counts itself; None: min_cluster_size), then the
+        minimum spanning tree of the complete mutual-reachability graph by Boruvka rounds — each recomputes every squared distance
+        on the exact-f32 MFMA over the tile pairs of the upper triangle and keeps a 64-bit arg-min per row and column; no edge
+        weight is stored.  Edges are ordered by (weight bits, lo, hi), so the tree is unique and has the same bits on every run.
+        The host derives scikit-learn's answer from the sorted tree (hdbscan_tree()).  Rows, normalize and data as for dbscan();
+        at most 65536 rows, 1 <= min_samples <= 33.  Returns a dict: labels int32 [n] (-1: noise), probabilities float64 [n],
+        n_clusters, sizes int32 [n_clusters], n_noise, points, rounds, core_distance float64 [n], mst (lo, hi int32 and distance
+        float64 [points - 1], sorted; d2 the squared weights the kernels formed), linkage float64 [points - 1, 4] (scipy's
+        format over the points in ascending list position), n; hdbscan_cut(result, distance) gives the DBSCAN* labels at any
+        radius from the same tree.  With report=True on a single-label model with at most 64 classes, when 1 <= n_clusters <= 256
+        and the rows are nodes, also contingency int64 [n_clusters, C] over the non-noise points, counted on the GPU, skipped, and
+        cluster_report()'s scores.  One rank, f32 tables, width at most 256.  Training state is not touched and nothing is cached."""
+        what = "hdbscan"
+        if cluster_selection_method not in ("eom", "leaf"):
+            raise GcnHostError(f"{what}: cluster_selection_method is 'eom' or 'leaf', got {cluster_selection_method!r}")
+        ms = min_cluster_size if min_samples is None else min_samples
+        for name, v in (("min_cluster_size", min_cluster_size), ("min_samples", ms)):
+            if isinstance(v, bool) or int(v) != v:
+                raise GcnHostError(f"{what}: {name} must be an integer, got {v!r}")
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        c = self.params.output_dim
+        want_report = bool(report) and d is None and not self.multilabel and c <= 64
+        m = max(cap, 1)
+        labels, prob, core2, sizes = np.zeros(m, np.int32), np.zeros(m, np.float64), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        lo, hi, w, link = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros((m, 4), np.float64)
+        cont, info = (np.zeros((256, c), np.int64) if want_report else None), np.zeros(8, np.int64)
+        _ck(self.lib, self.lib.gcnhost_model_hdbscan(
+            self.h, int(min_cluster_size), int(ms), int(split or 0), q.ctypes.data if q is not None else None, n,
+            d.ctypes.data if d is not None else None, int(d.shape[1]) if d is not None else 0, int(bool(normalize)),
+            int(cluster_selection_method == "leaf"), int(bool(allow_single_cluster)), cap, labels.ctypes.data, prob.ctypes.data, core2.ctypes.data,
+            lo.ctypes.data, hi.ctypes.data, w.ctypes.data, link.ctypes.data, sizes.ctypes.data, cont.ctypes.data if want_report else None,
+            info.ctypes.data), what)
+        k, cap, e = int(info[2]), int(info[0]), int(info[5])
+        out = dict(labels=labels[:cap], probabilities=prob[:cap], n_clusters=k, sizes=sizes[:k].copy(), n_noise=int(info[3]), points=int(info[1]),
+                   rounds=int(info[4]), core_distance=np.sqrt(core2[:cap].astype(np.float64)), n=cap,
+                   mst=dict(lo=lo[:e].copy(), hi=hi[:e].copy(), distance=np.sqrt(w[:e].astype(np.float64)), d2=w[:e].astype(np.float64)), linkage=link[:e].copy())
+        if want_report and int(info[6]) == k and k >= 1:
+            out.update(contingency=cont.ravel()[:k * c].reshape(k, c).copy(), skipped=int(info[7]))
+            out.update(cluster_report(out["contingency"]))
+        return out
+
     def pca_transform(self, fit, nodes=None):
         """f32 [n, k] — the listed nodes (None: every node in id order) projected with a fit pca() returned, at the CURRENT
         weights: one evaluation forward and one projection launch on the GPU; nothing is cached.  A fit on the training split
@@ -1753,6 +1798,68 @@ def read_dbscan(path):
             [c.append(x) for c, x in zip(cols, v)]
     node, label, core, count = (np.array(c, np.int32) for c in cols)
     return dict(node=node, label=label, core=core.astype(bool), count=count)
+
+
+def _hdbscan_edges(what, lo, hi, d2):
+    lo, hi, d2 = np.ascontiguousarray(lo, np.int32).ravel(), np.ascontiguousarray(hi, np.int32).ravel(), np.ascontiguousarray(d2, np.float64).ravel()
+    if not lo.size == hi.size == d2.size:
+        raise GcnHostError(f"{what}: lo, hi and d2 of one length, got {lo.size}, {hi.size}, {d2.size}")
+    return lo, hi, d2
+
+
+def hdbscan_tree(lo, hi, d2, n, min_cluster_size=5, cluster_selection_method="eom", allow_single_cluster=False):
+    """scikit-learn's HDBSCAN answer from a minimum spanning tree — host only, no GPU; the one place it is derived (host/hdbscan.h has
+    the rules).  lo, hi, d2: the tree's edges over list positions 0 .. n - 1 with their SQUARED weights, sorted by ascending d2
+    (ops.Device.hdbscan_mst gives them).  A position no edge touches is no point.  Returns a dict: labels int32 [n] (-1: noise),
+    probabilities float64 [n], n_clusters, n_noise, points, linkage float64 [edges, 4] (scipy's format over the points in ascending
+    position, distances as sqrt(d2)), n and mst (lo, hi, d2) for hdbscan_cut().  Rows that are no sorted tree raise GcnHostError."""
+    what = "hdbscan_tree"
+    if cluster_selection_method not in ("eom", "leaf"):
+        raise GcnHostError(f"{what}: cluster_selection_method is 'eom' or 'leaf', got {cluster_selection_method!r}")
+    lo, hi, d2 = _hdbscan_edges(what, lo, hi, d2)
+    n = int(n)
+    lib = _lib.gcnhost()
+    labels, prob, link, info = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64), np.zeros((max(lo.size, 1), 4), np.float64), np.zeros(3, np.int64)
+    _ck(lib, lib.gcnhost_hdbscan_tree(lo.ctypes.data, hi.ctypes.data, d2.ctypes.data, lo.size, n, int(min_cluster_size),
+                                      int(cluster_selection_method == "leaf"), int(bool(allow_single_cluster)), labels.ctypes.data, prob.ctypes.data,
+                                      link.ctypes.data, info.ctypes.data), what)
+    return dict(labels=labels[:n], probabilities=prob[:n], n_clusters=int(info[1]), n_noise=int(info[2]), points=int(info[0]),
+                linkage=link[:lo.size], n=n, mst=dict(lo=lo, hi=hi, d2=d2))
+
+
+def hdbscan_cut(tree, distance, min_cluster_size=5):
+    """int32 [n] — the DBSCAN* labels at the radius `distance` from the tree of hdbscan() or hdbscan_tree() (scikit-learn's
+    dbscan_clustering): the groups joined by edges shorter than `distance`, those below min_cluster_size noise (-1).  One tree
+    prices a sweep of eps.  Host only, no GPU."""
+    what = "hdbscan_cut"
+    lo, hi, d2 = _hdbscan_edges(what, tree["mst"]["lo"], tree["mst"]["hi"], tree["mst"]["d2"])
+    n = int(tree["n"])
+    lib = _lib.gcnhost()
+    labels = np.zeros(max(n, 1), np.int32)
+    _ck(lib, lib.gcnhost_hdbscan_cut(lo.ctypes.data, hi.ctypes.data, d2.ctypes.data, lo.size, n, float(distance), int(min_cluster_size), labels.ctypes.data,
+                                     None), what)
+    return labels[:n]
+
+
+def read_hdbscan(path):
+    """The file gcn-hip writes with GCN_HDBSCAN, one line `node label probability` per node: a dict of node, label (-1: noise) int32
+    [n] and probability float64 [n].  Needs no GPU."""
+    node, label, prob = [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) != 3:
+                    raise ValueError
+                v = int(p[0]), int(p[1]), float(p[2])
+                if v[1] < -1 or not 0.0 <= v[2] <= 1.0:
+                    raise ValueError
+            except ValueError:
+                raise GcnHostError(f"read_hdbscan: {path}:{no}: expected `node label probability`, got {line.strip()!r}") from None
+            [c.append(x) for c, x in zip((node, label, prob), v)]
+    return dict(node=np.array(node, np.int32), label=np.array(label, np.int32), probability=np.array(prob, np.float64))
 
 
 def sym_eigen(S):

@@ -920,6 +920,53 @@ class Device:
         return dict(labels=lb.download(), core=kb.download().astype(bool), counts=cb.download(), sizes=zb.download()[:int(t[4])].copy(),
                     n_clusters=int(t[4]), n_core=int(t[1]), n_border=int(t[2]), n_noise=int(t[3]), points=int(t[0]), rounds=rounds)
 
+    # ---- HDBSCAN's minimum spanning tree (csrc/hdbscan.hip) on the pack tsne_pack makes: every buffer is uploaded as garbage
+    def hdbscan_plan(self, n, dim):
+        """gcnhip_hdbscan_plan: dict(pack_bytes, state_bytes)"""
+        p, s = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_hdbscan_plan(int(n), int(dim), C.byref(p), C.byref(s))
+        if rc != 0:
+            self._embed_fail("gcnhip_hdbscan_plan", rc)
+        return dict(pack_bytes=p.value, state_bytes=s.value)
+
+    def hdbscan_mst(self, table, min_samples=5, rows=None, inv_norm=None, ld=None, batch=2):
+        """the minimum spanning tree of the listed rows under w(i, j) = max(d2(i, j), core2[i], core2[j]) and the order (w, lo, hi):
+        pack, gcnhip_knn_rows at k = min_samples - 1, gcnhip_hdbscan_start, then rounds of gcnhip_hdbscan_nearest and _merge, `batch`
+        enqueued at a time, until one component is left.  dict(lo, hi int32 [points - 1], d2 f32 (w) — sorted by (w, lo, hi) —
+        core2 f32 [n], points, rounds)."""
+        if isinstance(min_samples, bool) or int(min_samples) != min_samples or not 1 <= min_samples <= 33:
+            raise GcnHipError(f"hdbscan_mst: min_samples must be in 1..33, got {min_samples!r}")
+        pk = self.tsne_pack(table, rows=rows, inv_norm=inv_norm, ld=ld, scratch_bytes=16)
+        n, dim, k = pk["n"], pk["dim"], int(min_samples) - 1
+        if pk["points"] < 2 * k + 1:
+            raise GcnHipError(f"hdbscan_mst: at least 2 (min_samples - 1) + 1 = {2 * k + 1} points, got {pk['points']}")
+        sbytes = self.hdbscan_plan(n, dim)["state_bytes"]
+        sb = self.buf(np.full(sbytes // 4, 0x7fc12345, np.uint32))
+        db = self._knn_rows(pk, k)[1] if k else None
+        rc = self.lib.gcnhip_hdbscan_start(self.ctx, pk["pack"].ptr, n, dim, db.ptr if k else None, k, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_hdbscan_start", rc)
+        eb, cb = self.buf(np.full(3 * n, -777, np.int32)), self.buf(np.full(2 * int(batch), -777, np.int32))
+        rounds, comps, edges = 0, pk["points"], 0
+        while comps > 1:
+            for r in range(int(batch)):
+                rc = self.lib.gcnhip_hdbscan_nearest(self.ctx, pk["pack"].ptr, n, dim, sb.ptr, sbytes)
+                if rc != 0:
+                    self._embed_fail("gcnhip_hdbscan_nearest", rc)
+                rc = self.lib.gcnhip_hdbscan_merge(self.ctx, pk["pack"].ptr, n, dim, sb.ptr, sbytes, eb.ptr, cb.ptr + 8 * r)
+                if rc != 0:
+                    self._embed_fail("gcnhip_hdbscan_merge", rc)
+            for c, e in cb.download().reshape(-1, 2):
+                if int(c) >= comps:
+                    raise GcnHipError(f"hdbscan_mst: a round left {int(c)} of {comps} components")
+                rounds, comps, edges = rounds + 1, int(c), int(e)
+                if comps <= 1:
+                    break
+        e = eb.download().reshape(3, n)[:, :edges]
+        order = np.lexsort((e[1], e[0], e[2].view(np.uint32)))
+        core2 = db.download().reshape(n, k)[:, -1].copy() if k else np.zeros(n, np.float32)
+        return dict(lo=e[0][order], hi=e[1][order], d2=e[2][order].view(np.float32), core2=core2, points=pk["points"], rounds=rounds)
+
     # ---- map quality (csrc/mapq.hip) on the pack tsne_pack makes: exact kNN lists, ranks of given neighbours, the penalty sums;
     # every output is uploaded as garbage
     def mapq_plan(self, n, dim, k):

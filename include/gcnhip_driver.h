@@ -513,6 +513,36 @@ int gcnhip_dbscan_cores(gcnhip_ctx *ctx, const void *pack, int n, int dim, const
 int gcnhip_dbscan_link(gcnhip_ctx *ctx, const void *pack, int n, int dim, double eps, void *state, size_t state_bytes, int32_t *changed);
 int gcnhip_dbscan_labels(gcnhip_ctx *ctx, const void *pack, int n, int dim, const void *state, size_t state_bytes, int32_t *labels,
                          uint8_t *core, int32_t *sizes, int32_t *counts);
+/* ---- HDBSCAN's minimum spanning tree of a table's rows (hdbscan.hip; beyond the reference: the density clusters without an eps;
+ * Campello, Moulavi & Sander, 2013, scikit-learn's HDBSCAN), by Boruvka rounds and matrix-free: no edge weight is ever stored ----
+ * Table, row list, scaling, points and the pack are gcnhip_dbscan_counts' (gcnhip_hdbscan_plan's pack_bytes are gcnhip_tsne_plan's).
+ *   All arithmetic is on SQUARED distances: the maximum and the order are monotone, the caller takes square roots at the end.
+ * core2[i] = the d2 to the (min_samples - 1)-th nearest OTHER point (scikit-learn's rule: its core distance counts the point
+ *   itself), 0 for min_samples = 1: column k - 1 of gcnhip_knn_rows' d2 at k = min_samples - 1, so 1 <= min_samples <= 33.
+ * w(i, j) = max(d2(i, j), core2[i], core2[j]), d2 as DBSCAN forms it: fmaxf((xn_i + xn_j) - 2 . dot_f32(x^_i, x^_j), 0) on
+ *   v_mfma_f32_16x16x4_f32 in column order.  Each unordered pair of points is evaluated ONCE, with the larger position as the column,
+ *   and the result used for both ends.
+ * Edges carry the strict total order (bits of w, min(i, j), max(i, j)) on list positions.  Under it the minimum spanning tree is
+ *   unique; that tree is the answer.  Positions that are no point are in no edge: `points` points give points - 1 edges.
+ * At most 65536 positions: a root's choice packs (w bits << 32 | lo << 16 | hi) into one 64-bit key.  A longer list is refused.
+ * A round: gcnhip_hdbscan_nearest gives every point its lightest edge that leaves its component; gcnhip_hdbscan_merge lets every
+ *   component choose the lightest of its points' edges, appends each chosen edge ONCE (two components that chose each other chose
+ *   the same edge: the smaller root emits it), hangs the larger root under the smaller (every other root under the one it chose),
+ *   follows the hooks to their end and refreshes every tile's {min, max} component.  The components at least halve per round:
+ *   at most ceil(log2 points) rounds.  A round at one component changes nothing.  The order of the edges a round appends is
+ *   whatever the atomics give: sort the list by (w, lo, hi) for an answer with the same bits on every run.
+ * No launch allocates or synchronises, none uses a float atomic (u64 atomicMin and int32 atomicAdd only); anything else returns -1
+ *   with a message.
+ * gcnhip_hdbscan_plan: *pack_bytes of the packed image and *state_bytes of the rounds' state; each may be NULL.  No GPU.
+ * gcnhip_hdbscan_start: knn_d2 (device f32 [n x k], gcnhip_knn_rows' d2; NULL: every core2 is 0) into the state, every position its
+ *   own component, no edge yet.
+ * gcnhip_hdbscan_nearest, then gcnhip_hdbscan_merge: one round.  edges (device int32 [3 x n] = {lo [n] | hi [n] | bits of w [n]}, the
+ *   same buffer every round), counts (device int32 [2]) = {components, edges} after the round. */
+int gcnhip_hdbscan_plan(int n, int dim, size_t *pack_bytes, size_t *state_bytes);
+int gcnhip_hdbscan_start(gcnhip_ctx *ctx, const void *pack, int n, int dim, const float *knn_d2, int k, void *state, size_t state_bytes);
+int gcnhip_hdbscan_nearest(gcnhip_ctx *ctx, const void *pack, int n, int dim, void *state, size_t state_bytes);
+int gcnhip_hdbscan_merge(gcnhip_ctx *ctx, const void *pack, int n, int dim, void *state, size_t state_bytes, int32_t *edges,
+                         int32_t *counts);
 /* ---- map quality (mapq.hip; beyond the reference: can a drawing of the embeddings be believed?): the exact euclidean k nearest
  * neighbours of every listed row among the listed rows, the rank of given neighbours in a space's distance order, and from both
  * trustworthiness and continuity (Venna & Kaski, 2001; scikit-learn's trustworthiness) and the kNN overlap, matrix-free ----

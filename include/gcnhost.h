@@ -447,6 +447,30 @@ int gcnhost_model_knn(gcnhost_model *m, int k, int split, const int *nodes, int 
                       int32_t *ids, int32_t *pos, float *d2, int64_t *info);
 int gcnhost_model_map_quality(gcnhost_model *m, const float *coords, int64_t coords_rows, int coords_dim, int k, int split, const int *nodes, int n,
                               const float *data, int data_dim, int normalize, int32_t *per_node, int64_t *info, double *scores);
+/* HDBSCAN of the hidden layer (ModelQueries::hdbscan, host/queries.h; the tree's definitions in include/gcnhip_driver.h, kernels in
+ * csrc/hdbscan.hip; what is derived from the tree in host/hdbscan.h).
+ * gcnhost_hdbscan_tree (no GPU): from `edges` rows (lo, hi, d2) of a minimum spanning tree over list positions 0 .. n - 1, sorted by
+ * ascending d2 (squared distances, float64), scikit-learn's HDBSCAN answer for min_cluster_size >= 2: labels int32 [n] (-1: noise, or a
+ * position no edge touches), probabilities float64 [n], linkage float64 [edges x 4] in scipy's format over the points in ascending
+ * position (may be NULL), info [3] = {points, clusters, noise points}.  leaf: the leaves of the condensed tree instead of excess of
+ * mass.  -1 with a message when the rows are no sorted tree.
+ * gcnhost_hdbscan_cut (no GPU): the DBSCAN* labels of the same tree at `distance` (scikit-learn's dbscan_clustering): the clusters
+ * of the edges with sqrt(d2) < distance, those below min_cluster_size noise.
+ * gcnhost_model_hdbscan: rows and `data` as for gcnhost_model_dbscan; capacity: the rows the outputs have room for.  min_samples in
+ * 1..33 (the caller resolves "as min_cluster_size").  Outputs, each may be NULL: labels int32 / probabilities float64 / core2 f32 (the
+ * squared core distances) / sizes int32 [capacity]; mst_lo, mst_hi int32 and mst_d2 f32 [capacity] (the first info[5] entries, sorted by
+ * (d2, lo, hi)); linkage float64 [capacity x 4]; contingency int64 with room for 256 x output_dim, filled over the non-noise points when
+ * 1 <= clusters <= 256 on node rows; info [8] = {rows listed, points, clusters, noise, rounds, edges, contingency rows, skipped}.
+ * embed's contract: training state is not touched, nothing is cached.  Refused with a message: what gcnhost_model_dbscan refuses
+ * for its rows, min_cluster_size < 2, min_samples outside 1..33, more than 65536 rows, fewer than 2 (min_samples - 1) + 1 points. */
+int gcnhost_hdbscan_tree(const int32_t *lo, const int32_t *hi, const double *d2, int64_t edges, int64_t n, int min_cluster_size, int leaf,
+                         int allow_single_cluster, int32_t *labels, double *probabilities, double *linkage, int64_t *info);
+int gcnhost_hdbscan_cut(const int32_t *lo, const int32_t *hi, const double *d2, int64_t edges, int64_t n, double distance, int min_cluster_size,
+                        int32_t *labels, int64_t *info);
+int gcnhost_model_hdbscan(gcnhost_model *m, int min_cluster_size, int min_samples, int split, const int *nodes, int n, const float *data,
+                          int data_dim, int normalize, int leaf, int allow_single_cluster, int64_t capacity, int32_t *labels, double *probabilities,
+                          float *core2, int32_t *mst_lo, int32_t *mst_hi, float *mst_d2, double *linkage, int32_t *sizes, int64_t *contingency,
+                          int64_t *info);
 /* Principal components of the hidden layer (ModelQueries::pca_fit / pca_project, host/queries.h; sums in csrc/pca.hip; the
  * eigenproblem in host/pca.h).  Rows as for gcnhost_model_kmeans, repeats counted as often as listed.
  * gcnhost_sym_eigen (no GPU): S [h x h] float64, 1 <= h <= 256, finite and symmetric bit for bit (else -1 with a message);
