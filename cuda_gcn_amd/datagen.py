@@ -241,6 +241,28 @@ def edge_homophily(ds):
     return float((ds["label"][src[m]] == ds["label"][gi[m]]).mean())
 
 
+def hold_out_edges(ds, fraction, seed=DEFAULT_SEED):
+    """(dataset, (src, dst)) — `ds` without a random share `fraction` of its undirected edges, and those edges as int32 arrays with
+    src < dst: the honest input of HipGCNModel.link_ranks (train on what remains, rank what was taken).  Every stored entry of a
+    held-out edge goes, in both directions; self loops always stay.  Deterministic in (ds, fraction, seed); the other arrays of
+    the dataset are shared, not copied."""
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"hold_out_edges: fraction must be in [0, 1], got {fraction!r}")
+    N = int(ds["num_nodes"])
+    gp, gi = np.asarray(ds["g_indptr"], np.int64), np.asarray(ds["g_indices"], np.int64)
+    row = np.repeat(np.arange(N, dtype=np.int64), np.diff(gp))
+    key = np.minimum(row, gi) * N + np.maximum(row, gi)
+    edges = np.unique(key[row != gi])
+    rng = np.random.default_rng(seed)
+    held = np.sort(rng.choice(edges, size=int(round(fraction * edges.size)), replace=False))
+    keep = (row == gi) | ~np.isin(key, held)
+    indptr = np.zeros(N + 1, np.int64)
+    np.cumsum(np.bincount(row[keep], minlength=N), out=indptr[1:])
+    out = dict(ds)
+    out.update(g_indptr=indptr.astype(np.int32), g_indices=gi[keep].astype(np.int32))
+    return out, ((held // N).astype(np.int32), (held % N).astype(np.int32))
+
+
 def write_text(ds, root: str, name: str | None = None):
     """Write ``root/<name>.graph/.split/.svmlight`` in the reference's formats
     (parser.cpp:20-103).  Values are printed with 9 significant digits so they

@@ -18,6 +18,7 @@
 #include "calibration.h"
 #include "kmeans.h"
 #include "hdbscan.h"
+#include "linkrank.h"
 #include "pca.h"
 #include "structure.h"
 #include "reach.h"
@@ -317,6 +318,19 @@ int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int 
 int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out) {
     if (!m) { g_err = "gcnhost_model_score_pairs: invalid argument"; return -1; }
     API_TRY({ m->gcn->queries().score_pairs(src, dst, n_pairs, metric, out); })
+}
+int gcnhost_model_link_ranks(gcnhost_model *m, const int *src, const int *dst, int n, int metric, int filtered, int exclude_self, int32_t *above,
+                             int32_t *equal) {
+    if (!m) { g_err = "gcnhost_model_link_ranks: invalid argument"; return -1; }
+    API_TRY({ m->gcn->queries().link_ranks(src, dst, n, metric, filtered != 0, exclude_self != 0, above, equal); })
+}
+int gcnhost_link_rank_metrics(const int32_t *above, const int32_t *equal, int64_t n, const int *ks, int n_ks, double *rank, double *summary,
+                              double *hits, int64_t *info) {
+    LinkRankMetrics r;
+    if (gcn_link_rank_metrics(above, equal, n, ks, n_ks, rank, hits, &r, &g_err) != 0) return -1;
+    if (summary) { summary[0] = r.mrr; summary[1] = r.mean_rank; }
+    if (info) { info[0] = r.queries; info[1] = r.invalid; }
+    return 0;
 }
 int gcnhost_model_explain(gcnhost_model *m, const int *nodes, const int *classes, int n, size_t feat_scratch_bytes, int32_t *out_class, float *logit,
                           float *hidden, float *feat, int64_t *nbr_ptr, int32_t *nbr_ids, float *nbr_values, int64_t *nbr_total) {

@@ -139,6 +139,13 @@
 //                            TEST split, counted on the GPU by intersecting neighbour sets.  One line is printed: `triangles=<n>
 //                            transitivity=<t> avg_clustering=<c>` (over the test nodes).  The file gets `node deg t2 clustering`
 //                            per test node behind the totals (host/overlap.h).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
+// Link prediction ranks (beyond the reference; ModelQueries::link_ranks, kernels in csrc/linkrank.hip, metrics in host/linkrank.h),
+// after the test line and the steps above.  One GPU, hidden_dim at most 256, f32 tables:
+//   GCN_LINK_EDGES=<file>    with GCN_LINK_RANKS=<file>: every line `src dst` of the first file is a held-out edge, ranked among all
+//                            nodes by the dot product of the hidden rows (GCN_LINK_METRIC=cosine: the cosine), filtered by the graph's
+//                            own edges, the node itself excluded.  One line is printed: `link_queries=<n> link_mrr=<m>
+//                            link_mean_rank=<r> link_hits@10=<h>`.  The second file gets `src dst above equal` per query (-1 -1: an id
+//                            that is no node).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
 // Explanations (beyond the reference; ModelQueries::explain / feature_importance, kernels in csrc/explain.hip), after the test line
 // and the steps above; stdout is unchanged.  One GPU, hidden_dim at most 256, f32 tables; single- and multi-label models alike:
 //   GCN_EXPLAIN=<file>       one line per node of the TEST split in id order: `node class logit | id:share x5 | f:share x5` — the
@@ -215,6 +222,7 @@
 #include "structure.h"
 #include "reach.h"
 #include "overlap.h"
+#include "linkrank.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -561,6 +569,37 @@ int main(int argc, char **argv) {
     if (triangles_path && env_int("GCN_GPUS", 1) > 1) {
         std::cerr << "gcn-hip: GCN_TRIANGLES runs on one GPU (GCN_GPUS is above 1)" << std::endl;
         return EXIT_FAILURE;
+    }
+
+    const char *link_edges_path = getenv("GCN_LINK_EDGES"), *link_ranks_path = getenv("GCN_LINK_RANKS");
+    if (link_edges_path && !*link_edges_path) link_edges_path = nullptr;
+    if (link_ranks_path && !*link_ranks_path) link_ranks_path = nullptr;
+    std::vector<int> link_src, link_dst;
+    const bool link_cosine = getenv("GCN_LINK_METRIC") && std::string(getenv("GCN_LINK_METRIC")) == "cosine";
+    if (link_edges_path || link_ranks_path) {
+        const char *why = !link_edges_path || !link_ranks_path ? "come together (the edges to rank, the file for the counts)"
+                          : env_int("GCN_GPUS", 1) > 1         ? "run on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256            ? "take a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)      ? "need f32 tables (GCN_BF16_TABLES is set)"
+                                                               : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_LINK_EDGES and GCN_LINK_RANKS " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+        FILE *f = fopen(link_edges_path, "r");                 // read and checked before the GPU is touched
+        long long a = 0, b = 0;
+        int got = 0;
+        while (f && (got = fscanf(f, "%lld %lld", &a, &b)) == 2) {
+            const auto id = [](long long v) { return v < -1 || v > 0x7fffffffLL ? -1 : (int)v; };   // no node: the query is answered -1 -1
+            link_src.push_back(id(a));
+            link_dst.push_back(id(b));
+        }
+        const bool bad = !f || got != EOF;
+        if (f) fclose(f);
+        if (bad) {
+            std::cerr << "gcn-hip: GCN_LINK_EDGES: " << link_edges_path << " is not a readable file of `src dst` lines" << std::endl;
+            return EXIT_FAILURE;
+        }
     }
 
     const char *explain_path = getenv("GCN_EXPLAIN");
@@ -965,6 +1004,24 @@ int main(int argc, char **argv) {
                     throw GcnHipFailure(-1, "gcn-hip: " + (err.empty() ? std::string("GCN_TRIANGLES: the test split changed size") : err));
                 printf("triangles=%lld transitivity=%.6f avg_clustering=%.6f\n", (long long)om.triangles, om.transitivity, om.avg_clustering);
                 fprintf(stderr, "gcn-hip: the triangles of %lld test nodes written to %s\n", (long long)r.rows, triangles_path);
+            }
+            if (link_ranks_path) {                             // one rank (checked above): the listed edges, filtered, the node itself excluded
+                const int n = (int)link_src.size();
+                std::vector<int32_t> above(std::max(n, 1)), equal(std::max(n, 1));
+                gcn.queries().link_ranks(link_src.data(), link_dst.data(), n, link_cosine ? ModelQueries::METRIC_COSINE : ModelQueries::METRIC_DOT, true,
+                                         true, above.data(), equal.data());
+                const int ks[1] = {10};
+                double hits[1] = {0};
+                LinkRankMetrics lm;
+                std::string err;
+                if (gcn_link_rank_metrics(above.data(), equal.data(), n, ks, 1, nullptr, hits, &lm, &err) != 0) throw GcnHipFailure(-1, "gcn-hip: " + err);
+                printf("link_queries=%lld link_mrr=%.6f link_mean_rank=%.3f link_hits@10=%.6f\n", (long long)lm.queries, lm.mrr, lm.mean_rank, hits[0]);
+                FILE *f2 = fopen(link_ranks_path, "w");
+                bool ok = f2 != nullptr;
+                for (int i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %d %d %d\n", link_src[i], link_dst[i], above[i], equal[i]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the link ranks to ") + link_ranks_path);
+                fprintf(stderr, "gcn-hip: the ranks of %d edges (%s, filtered) written to %s\n", n, link_cosine ? "cosine" : "dot", link_ranks_path);
             }
             if (explain_path) {                                // one rank (checked above)
                 const int h = params.hidden_dim, F = params.input_dim, C = params.output_dim;

@@ -1,6 +1,6 @@
 // queries.h — what a caller asks of a trained model (beyond the reference, which only prints accuracy): prediction, per-class
 // evaluation, label propagation and Correct & Smooth, temperature scaling, node embeddings, explanations, conformal prediction
-// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph, the reach of the labels, neighbourhood overlap.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
+// sets, ranking metrics, multi-label decision thresholds, prediction for nodes the dataset did not hold, Monte Carlo dropout, k-means on the embeddings, the label structure of the graph, the reach of the labels, neighbourhood overlap, link prediction ranks.  ModelQueries owns every device buffer and every piece of host state these calls need, in an arena of its own on the model's main context: nothing is allocated until the
 // first query, and HipGCN::release() frees all of it by destroying this one object.
 //
 // It holds a HipGCN & and is a friend of it.  What it uses, and all it uses:
@@ -560,6 +560,22 @@ public:
     Overlap clustering(int split, const int *nodes, int n, int64_t *t2, int32_t *deg, int64_t *totals);
     Overlap link_overlap(const int *src, const int *dst, int n, int weight_mask, int32_t *cn, int32_t *un, int64_t *pa, int64_t *aa, int64_t *ra);
 
+    // Link prediction ranks (include/gcnhip_driver.h has the definitions, csrc/linkrank.hip the kernels, host/linkrank_query.cpp the
+    // body, host/linkrank.h the metrics): how good the embedding scores of similar() / score_pairs() are as a link scorer.  Query i
+    // is a held-out edge (src[i], dst[i]) of dataset ids; its candidates are every node except dst[i], src[i] with exclude_self, and
+    // with `filtered` the neighbour set S(src[i]) of the model's adjacency (the canonical sets of the overlap pass, rebuilt per call).
+    // above / equal int32 [n]: the candidates scoring above / equal to the edge itself; -1 / -1 for a query with an id that is no
+    // node (counted in `invalid`, not refused: a list of held-out edges is scored as a whole).  Steps: sync(); embed_forward (with
+    // METRIC_COSINE its inverse norms); with `filtered` the canonical pass; one gcnhip_link_ranks; 2 n integers to the host.  Ranking
+    // (d, s) as well as (s, d) is two queries.  embed()'s contract: training state is untouched, variable 3 is rewritten as by every
+    // forward, nothing is cached.  Refused with a message before any launch: what similar() refuses (more than one rank, a hidden
+    // width above 256, an unknown metric), n < 0, a NULL array.
+    struct LinkRanks {
+        int64_t queries = 0, invalid = 0;
+        int chunk_rows = 0, n_chunks = 0;
+    };
+    LinkRanks link_ranks(const int *src, const int *dst, int n, int metric, bool filtered, bool exclude_self, int32_t *above, int32_t *equal);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                       // every device buffer of a query
@@ -727,6 +743,9 @@ private:
     Scratch<int32_t> d_ov_idx{&arena}, d_ov_len{&arena}, d_ov_sort{&arena}, d_ov_int{&arena};
     Scratch<int64_t> d_ov_long{&arena};
     void overlap_sets();                                       // the canonical pass into d_ov_idx / d_ov_len
+    // link_ranks: {src | dst | above | equal} by list position, the thresholds (the filter sets are the overlap pass's)
+    Scratch<int32_t> d_lr_int{&arena};
+    Scratch<float> d_lr_thr{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

@@ -791,6 +791,31 @@ class HipGCNModel:
                                                          out.ctypes.data), "score_edges")
         return out[:s.size]
 
+    def link_ranks(self, src, dst, metric="dot", filtered=True, exclude_self=True, ks=(1, 10, 50, 100)):
+        """How good score_edges() is as a link scorer: the rank every held-out edge (src[i], dst[i]) takes among all nodes c as a
+        candidate end, by the metric's score of (src[i], c) against that of the edge itself.  Candidates: every node except dst[i],
+        src[i] (exclude_self) and, with filtered=True, the nodes src[i] already links to in the model's graph (the filtered setting:
+        known edges do not count against a query).  The n x N x hidden product, the compare and the count run on the GPU
+        (csrc/linkrank.hip) with exact ties: equal embedding rows land in `equal`, and the integers are the same on every run.
+        Returns a dict: above, equal (int32 [n]; -1 where an id is no node), rank (float64, the realistic rank 1 + above + equal / 2,
+        NaN where invalid), mrr, mean_rank, hits ({k: share of queries with rank <= k}), queries, invalid — the metrics are
+        link_rank_metrics() of the integers.  Ranking (d, s) as well as (s, d) is two queries.  One rank, f32 tables, hidden width at
+        most 256.  Training state is not touched."""
+        what = "link_ranks"
+        if metric not in self.METRICS:
+            raise GcnHostError(f"{what}: the metric is 'dot' or 'cosine', got {metric!r}")
+        ks = _link_ks(what, ks)
+        s, d = np.ascontiguousarray(src, np.int32).ravel(), np.ascontiguousarray(dst, np.int32).ravel()
+        if s.size != d.size:
+            raise GcnHostError(f"{what}: {s.size} sources for {d.size} destinations")
+        n = int(s.size)
+        above, equal, z = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(1, np.int32)
+        _ck(self.lib, self.lib.gcnhost_model_link_ranks(self.h, (s if n else z).ctypes.data, (d if n else z).ctypes.data, n, self.METRICS[metric],
+                                                        int(bool(filtered)), int(bool(exclude_self)), above.ctypes.data, equal.ctypes.data), what)
+        out = link_rank_metrics(above[:n], equal[:n], ks)
+        out.update(above=above[:n].copy(), equal=equal[:n].copy())
+        return out
+
     # ---- k-means on the hidden layer: groups of nodes, on the GPU
     def _cluster_args(self, k, split, nodes, iters, init, seed):
         """argument checks that need no GPU; returns (k, init code, init positions or None, init centres or None)"""
@@ -2007,6 +2032,57 @@ def overlap_metrics(totals, t2=None, deg=None):
     c = np.zeros(max(a.size, 1), np.float64)
     _ck(lib, lib.gcnhost_overlap_metrics(t.ctypes.data, a.ctypes.data, d.ctypes.data, a.size, s.ctypes.data, c.ctypes.data), what)
     return dict(triangles=int(s[0]), transitivity=float(s[1]), avg_clustering=float(s[2]), clustering=c[:a.size])
+
+
+def _link_ks(what, ks):
+    ks = (ks,) if isinstance(ks, (int, np.integer)) and not isinstance(ks, bool) else tuple(ks)
+    if any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
+        raise GcnHostError(f"{what}: every k of Hits@K is an integer of at least 1, got {ks!r}")
+    return tuple(int(k) for k in ks)
+
+
+def link_rank_metrics(above, equal, ks=(1, 10, 50, 100)):
+    """MRR, mean rank and Hits@K out of the integer counts of a rank query — host only, no GPU; the one place they are derived
+    (host/linkrank.h).  rank = 1 + above + equal / 2 (the realistic rank of OGB and PyKEEN); a query with a count below 0 (an end
+    outside the table) is left out and counted in `invalid`; float64 sums in list order; no query gives 0, never NaN.  Returns
+    dict(rank float64 [n] (NaN where left out), mrr, mean_rank, hits {k: share with rank <= k}, queries, invalid)."""
+    what = "link_rank_metrics"
+    ks = _link_ks(what, ks)
+    a, e = np.ascontiguousarray(above, np.int32).ravel(), np.ascontiguousarray(equal, np.int32).ravel()
+    if a.size != e.size:
+        raise GcnHostError(f"{what}: above and equal list {a.size} and {e.size} queries")
+    lib = _lib.gcnhost()
+    n = int(a.size)
+    rank, s, hits, info = np.zeros(max(n, 1), np.float64), np.zeros(2, np.float64), np.zeros(max(len(ks), 1), np.float64), np.zeros(2, np.int64)
+    kk = np.array(ks if ks else (1,), np.int32)
+    _ck(lib, lib.gcnhost_link_rank_metrics(a.ctypes.data, e.ctypes.data, n, kk.ctypes.data, len(ks), rank.ctypes.data, s.ctypes.data, hits.ctypes.data,
+                                           info.ctypes.data), what)
+    return dict(rank=rank[:n], mrr=float(s[0]), mean_rank=float(s[1]), hits={k: float(hits[j]) for j, k in enumerate(ks)}, queries=int(info[0]),
+                invalid=int(info[1]))
+
+
+def read_link_ranks(path, ks=(1, 10, 50, 100)):
+    """The file gcn-hip writes with GCN_LINK_RANKS, one line `src dst above equal` per query: dict(src, dst, above, equal int32 [n])
+    plus link_rank_metrics() of the counts.  Needs no GPU."""
+    cols = [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) != 4:
+                    raise ValueError
+                v = [int(x) for x in p]
+                if v[2] < -1 or v[3] < -1:
+                    raise ValueError
+            except ValueError:
+                raise GcnHostError(f"read_link_ranks: {path}:{no}: expected `src dst above equal`, got {line.strip()!r}") from None
+            [c.append(x) for c, x in zip(cols, v)]
+    src, dst, above, equal = (np.array(c, np.int32) for c in cols)
+    out = link_rank_metrics(above, equal, ks)
+    out.update(src=src, dst=dst, above=above, equal=equal)
+    return out
 
 
 def write_triangles(path, node, deg, t2, totals):

@@ -632,6 +632,56 @@ class Device:
             self._embed_fail("gcnhip_embed_rows", rc)
         return ob.download()[:n, :dim]
 
+    # ---- link prediction ranks (csrc/linkrank.hip): the table as above; every output and the scratch are uploaded as garbage
+    def link_rank_plan(self, n_table, nq, chunk_rows=0):
+        """gcnhip_link_rank_plan: dict(chunk_rows, n_chunks, scratch_bytes) of a gcnhip_link_ranks call"""
+        rows, chunks, sbytes = C.c_int(), C.c_int(), C.c_size_t()
+        rc = self.lib.gcnhip_link_rank_plan(int(n_table), int(nq), int(chunk_rows), C.byref(rows), C.byref(chunks), C.byref(sbytes))
+        if rc != 0:
+            self._embed_fail("gcnhip_link_rank_plan", rc)
+        return dict(chunk_rows=rows.value, n_chunks=chunks.value, scratch_bytes=sbytes.value)
+
+    def _link_queries(self, src, dst):
+        s, d = np.ascontiguousarray(src, np.int32).ravel(), np.ascontiguousarray(dst, np.int32).ravel()
+        if s.size != d.size:
+            raise GcnHipError(f"link queries: {s.size} sources for {d.size} destinations")
+        nq = int(s.size)
+        return self.buf(s if nq else np.zeros(1, np.int32)), self.buf(d if nq else np.zeros(1, np.int32)), nq
+
+    def link_thresholds(self, table, src, dst, inv_norm=None, ld=None):
+        """gcnhip_link_thresholds: f32 [nq] = score(src[i], dst[i]) with the bits link_ranks compares against; NaN for a query with an
+        end outside the table"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        sb, db, nq = self._link_queries(src, dst)
+        ob = self.buf(np.full(max(nq, 1), -777.0, np.float32))
+        rc = self.lib.gcnhip_link_thresholds(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, sb.ptr, db.ptr, nq, ob.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_link_thresholds", rc)
+        return ob.download()[:nq]
+
+    def link_ranks(self, table, src, dst, inv_norm=None, x_ptr=None, x_ids=None, exclude_self=True, chunk_rows=0, ld=None, plan=False,
+                   x_len=None, launches=3):
+        """gcnhip_link_ranks: (above, equal) int32 [nq] — among the rows c of `table` other than dst[i], src[i] (exclude_self) and the
+        members of the filter set of row src[i] (x_ptr [n_table + 1], x_ids sorted per row; x_len: the rows' lengths when they are
+        shorter than their extent), how many score above and how many equal to score(src[i], dst[i]); -1 / -1 for a query with an end
+        outside the table.  plan=True: a third value, link_rank_plan's dict for this call."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        sb, db, nq = self._link_queries(src, dst)
+        pb = None if x_ptr is None else self.buf(np.ascontiguousarray(x_ptr, np.int32))
+        ids = None if x_ids is None else np.ascontiguousarray(x_ids, np.int32).ravel()
+        ib = None if ids is None else self.buf(ids if ids.size else np.zeros(1, np.int32))
+        lb = None if x_len is None else self.buf(np.ascontiguousarray(x_len, np.int32))
+        info = self.link_rank_plan(n_table, nq, chunk_rows)
+        sc = self.buf(np.full(max(info["scratch_bytes"] // 4, 1), 0x7fc12345, np.uint32))
+        ab, eb = self.buf(np.full(max(nq, 1), 12345, np.int32)), self.buf(np.full(max(nq, 1), 12345, np.int32))
+        rc = self.lib.gcnhip_link_ranks(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, sb.ptr, db.ptr, nq, pb.ptr if pb else None,
+                                        lb.ptr if lb else None, ib.ptr if ib else None, int(bool(exclude_self)), int(chunk_rows), sc.ptr,
+                                        info["scratch_bytes"], int(launches), ab.ptr, eb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_link_ranks", rc)
+        out = ab.download()[:nq], eb.download()[:nq]
+        return out + (info,) if plan else out
+
     # ---- k-means on the rows of a table (csrc/kmeans.hip): table and centres are uploaded with their row strides and NaN padding
     def _kmeans_rows(self, rows, n_table):
         r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()

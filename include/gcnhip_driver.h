@@ -376,6 +376,32 @@ int gcnhip_pair_scores(gcnhip_ctx *ctx, const float *table, int ld, int n_table,
                        const int32_t *dst, int n_pairs, float *out);
 int gcnhip_embed_rows(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows,
                       int n, float *out, int ld_out);
+/* ---- link prediction ranks (linkrank.hip; beyond the reference: how good a link scorer is, matrix-free) ----
+ * The table contract and score(q, c) of the embedding calls above; every dot product of these calls is one MFMA chain in one fixed
+ * column order, so equal rows give equal scores and a score's bits do not depend on where the walk meets it.
+ * Query i = (s_i, d_i) = (src[i], dst[i]), device int32, repeats allowed.  t_i = score(s_i, d_i).  The candidate set C_i is every
+ * table row c except d_i, s_i when exclude_self != 0, and the members of the filter set of row s_i — each removed once, whichever
+ * of these it is.  above[i] = #{c in C_i : score(s_i, c) > t_i}, equal[i] = #{c in C_i : score(s_i, c) == t_i}, device int32 [nq];
+ * a query with s_i or d_i outside [0, n_table) gets -1 / -1.  The realistic rank is 1 + above + equal / 2 (the caller's).  A NaN
+ * score is above and equal to nothing.
+ * The filter: x_ptr device int32 [n_table + 1] (NULL: none), x_ids device int32; the set of row r is x_ids[x_ptr[r] .. x_ptr[r + 1]),
+ * or with x_len (device int32 [n_table]) x_ids[x_ptr[r] .. x_ptr[r] + x_len[r]) — the form gcnhip_overlap_sets leaves with the
+ * adjacency's row pointers.  Per row the ids are ascending and distinct; an id outside [0, n_table) is ignored; ids are compared,
+ * never used as an index.
+ * gcnhip_link_rank_plan (no GPU): the candidate rows per workgroup (chunk_rows 0: gcnhip_topk_plan's choice), the chunks, and the
+ *   bytes of device scratch gcnhip_link_ranks takes (the thresholds).
+ * gcnhip_link_thresholds: thr[i] = t_i f32 with the bits the walk sees at entry (s_i, d_i); NaN for a query that is none.
+ * gcnhip_link_ranks: launches 3 = the threshold launch (it also starts the counts) and the walk; 1 or 2 = only the one or the
+ *   other, for timing them apart (2 alone adds to whatever the counts hold).  The counts leave by int32 atomicAdd: every chunking
+ *   and two launches give the same integers.  No launch allocates or synchronises.
+ * Refused with -1 and a message (gcnhip_last_error) before any launch: dim outside 1..256, ld < dim, an empty table, a NULL
+ * table, list or output, a negative count, x_ptr without x_ids, too little scratch, more than 65535 chunks. */
+int gcnhip_link_rank_plan(int n_table, int nq, int chunk_rows, int *chunk_rows_used, int *n_chunks, size_t *scratch_bytes);
+int gcnhip_link_thresholds(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *src,
+                           const int32_t *dst, int nq, float *thr);
+int gcnhip_link_ranks(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *src,
+                      const int32_t *dst, int nq, const int32_t *x_ptr, const int32_t *x_len, const int32_t *x_ids, int exclude_self,
+                      int chunk_rows, void *scratch, size_t scratch_bytes, int launches, int32_t *above, int32_t *equal);
 /* ---- k-means on the rows of a table (kmeans.hip; beyond the reference: grouping what a GCN learns, where it lies) ----
  * The table contract of the embedding calls.  d_rows: a device int32 list of n rows, repeats allowed, NULL: rows 0 .. n - 1
  * (then n <= n_table); a list position whose row is outside the table takes no part.  The row used is x^ = x . inv_norm[r]

@@ -363,6 +363,19 @@ int gcnhost_thresholds_write(const char *path, int num_classes, const float *thr
 int gcnhost_model_embed(gcnhost_model *m, const int *nodes, int n, float *out, int normalize);
 int gcnhost_model_similar(gcnhost_model *m, const int *nodes, int n, int k, int metric, int exclude_self, int32_t *out_id, float *out_score);
 int gcnhost_model_score_pairs(gcnhost_model *m, const int *src, const int *dst, int n_pairs, int metric, float *out);
+/* Link prediction ranks (ModelQueries::link_ranks, host/queries.h; definitions in include/gcnhip_driver.h, kernels in
+ * csrc/linkrank.hip; the metrics in host/linkrank.h): the rank of held-out edges under the scores above.
+ * gcnhost_model_link_ranks: query i = (src[i], dst[i]), dataset ids; its candidates are every node except dst[i], src[i] when
+ *   exclude_self != 0 and, when filtered != 0, the distinct neighbours of src[i] in the model's adjacency.  above / equal int32 [n]: the
+ *   candidates scoring above / equal to the pair itself, -1 / -1 where an id is no node.  Exact integers: the same on every run.  The
+ *   embedding calls' limits and refusals; training state is not touched.
+ * gcnhost_link_rank_metrics (no GPU): rank_i = 1 + above_i + equal_i / 2 over the queries with both counts >= 0, float64 sums in
+ *   list order: rank [n] (may be NULL; NaN where left out), summary [2] = {MRR, mean rank}, hits [n_ks] = the share with rank <= ks[j],
+ *   info [2] = {queries counted, left out}; no query counted: zeros.  -1 with a message: n < 0, a NULL array, a k below 1. */
+int gcnhost_model_link_ranks(gcnhost_model *m, const int *src, const int *dst, int n, int metric, int filtered, int exclude_self, int32_t *above,
+                             int32_t *equal);
+int gcnhost_link_rank_metrics(const int32_t *above, const int32_t *equal, int64_t n, const int *ks, int n_ks, double *rank, double *summary,
+                              double *hits, int64_t *info);
 /* k-means on the hidden layer (ModelQueries::kmeans, host/queries.h; kernels in csrc/kmeans.hip): the rows gcnhost_model_embed
  * exports, grouped on the device.  Rows: the nodes of `split` (1 train, 2 validation, 3 test) in ascending id, or with split == 0
  * the `nodes` query (n dataset ids in the order given, repeats allowed; NULL: every node in id order).  normalize != 0: unit
