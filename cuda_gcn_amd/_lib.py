@@ -131,6 +131,10 @@ GCNHIP_SYMBOLS = {
     "gcnhip_link_rank_plan": (I, [I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(C.c_size_t)]),
     "gcnhip_link_thresholds": (I, [P, P, I, I, I, P, P, P, I, P]),
     "gcnhip_link_ranks": (I, [P, P, I, I, I, P, P, P, I, P, P, P, I, I, P, C.c_size_t, I, P, P]),
+    "gcnhip_gmm_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_gmm_estep": (I, [P, P, I, I, I, P, P, I, P, P, P, I, P, I, P, P, P, P, P, P, C.c_size_t]),
+    "gcnhip_gmm_mstep": (I, [P, P, I, I, I, P, P, I, P, P, P, P, I, I, I, P, P, C.c_size_t]),
+    "gcnhip_gmm_finalize": (I, [P, P, I, I, I, I, C.c_double, P, P, P, P, P, I, P]),
     "gcnhip_kmeans_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_kmeans_assign": (I, [P, P, I, I, I, P, P, I, P, I, P, I, P, P, P, P]),
     "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
@@ -309,6 +313,10 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_score_pairs": (I, [P, P, P, I, I, P]),
     "gcnhost_model_link_ranks": (I, [P, P, P, I, I, I, I, P, P]),
     "gcnhost_link_rank_metrics": (I, [P, P, I64, P, I, P, P, P, P]),
+    "gcnhost_model_gmm": (I, [P, I, I, P, I, P, I, I, C.c_double, I, C.c_double, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P, P,
+                              P, P]),
+    "gcnhost_model_gmm_score": (I, [P, I, I, P, P, P, P, I, P, I, P, I, I, I64, P, P, P, P, P]),
+    "gcnhost_gmm_information": (I, [C.c_double, I64, I, I, I, P]),
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
     "gcnhost_model_silhouette": (I, [P, I, P, I, P, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),

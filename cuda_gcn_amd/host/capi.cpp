@@ -19,6 +19,7 @@
 #include "kmeans.h"
 #include "hdbscan.h"
 #include "linkrank.h"
+#include "gmm.h"
 #include "pca.h"
 #include "structure.h"
 #include "reach.h"
@@ -365,6 +366,38 @@ int gcnhost_model_kmeans(gcnhost_model *m, int k, int split, const int *nodes, i
         if (inertia) *inertia = r.inertia;
         if (seed_used) *seed_used = r.seed;
     })
+}
+int gcnhost_model_gmm(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, int iters, double tol, int spherical,
+                      double reg_covar, int normalize, int init, const int *init_pos, const float *init_means, const uint64_t *seed, size_t scratch_bytes,
+                      int64_t capacity, float *weights, float *means, float *variances, int32_t *assign, float *max_resp, float *log_likelihood,
+                      float *resp, double *sizes, float *shift, double *history, int64_t *contingency, int64_t *info, double *result) {
+    if (!m) { g_err = "gcnhost_model_gmm: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const ModelQueries::Gmm r = q.gmm(k, split, nodes, n, data, data_dim, iters, tol, spherical != 0, reg_covar, normalize != 0, init, init_pos, init_means,
+                                          seed, scratch_bytes, weights, means, variances, assign, max_resp, log_likelihood, resp, sizes, shift, history,
+                                          contingency, capacity < 0 ? 0 : capacity);
+        if (info) { info[0] = r.rows; info[1] = r.iters_run; info[2] = r.converged ? 1 : 0; info[3] = r.skipped; }
+        if (result) *result = r.lower_bound;
+    })
+}
+int gcnhost_model_gmm_score(gcnhost_model *m, int k, int width, const float *weights, const float *means, const float *variances, const float *shift,
+                            int split, const int *nodes, int n, const float *data, int data_dim, int normalize, int64_t capacity,
+                            float *log_likelihood, int32_t *assign, float *max_resp, float *resp, int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_gmm_score: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const int64_t rows = q.gmm_score(k, width, weights, means, variances, shift, split, nodes, n, data, data_dim, normalize != 0, log_likelihood, assign,
+                                         max_resp, resp, capacity < 0 ? 0 : capacity);
+        if (info) info[0] = rows;
+    })
+}
+int gcnhost_gmm_information(double lower_bound, int64_t points, int k, int dim, int spherical, double *out) {
+    GmmInformation r;
+    if (!out) { g_err = "gmm_information: invalid argument"; return -1; }
+    if (gcn_gmm_information(lower_bound, points, k, dim, spherical != 0, &r, &g_err) != 0) return -1;
+    out[0] = (double)r.n_parameters; out[1] = r.bic; out[2] = r.aic;
+    return 0;
 }
 int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary) {
     ClusterReport r;

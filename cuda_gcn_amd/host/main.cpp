@@ -188,6 +188,14 @@
 //                            One line is printed: `hdbscan_min_cluster_size=<m> hdbscan_min_samples=<s> hdbscan_clusters=<k>
 //                            hdbscan_noise=<n> hdbscan_rounds=<r>`.  The file gets one line per test node in id order: `node label
 //                            probability` (label -1: noise; %.17g).
+// Gaussian mixture of the embeddings (beyond the reference; ModelQueries::gmm, kernels in csrc/gmm.hip, the criteria in host/gmm.h),
+// after the HDBSCAN labels.  One GPU, hidden_dim at most 256, f32 tables:
+//   GCN_GMM=<file>           a mixture of GCN_GMM_K components (default: the number of classes, 1..256) with GCN_GMM_COV=diag
+//                            (default) or spherical covariances, fitted to the unit rows of the hidden layer of the TEST nodes from
+//                            the k-means clustering in at most GCN_GMM_ITERS iterations (default 100, tol 1e-3).  One line is
+//                            printed: `gmm_components=<k> gmm_iters=<t> gmm_converged=<0|1> gmm_lower_bound=<lb> gmm_bic=<b>
+//                            gmm_aic=<a>`.  The file gets one line per test node in id order: `node component max_resp
+//                            log_likelihood` (%.9g: f32 exactly).
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -223,6 +231,7 @@
 #include "reach.h"
 #include "overlap.h"
 #include "linkrank.h"
+#include "gmm.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -531,6 +540,24 @@ int main(int argc, char **argv) {
                                                                                      : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_HDBSCAN " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *gmm_path = getenv("GCN_GMM");
+    if (gmm_path && !*gmm_path) gmm_path = nullptr;
+    const int gmm_k = env_int("GCN_GMM_K", params.output_dim), gmm_iters = env_int("GCN_GMM_ITERS", 100);
+    const std::string gmm_cov = getenv("GCN_GMM_COV") && *getenv("GCN_GMM_COV") ? getenv("GCN_GMM_COV") : "diag";
+    if (gmm_path) {
+        const char *why = env_int("GCN_GPUS", 1) > 1                       ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                        ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                  ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : gmm_k < 1 || gmm_k > 256                       ? "needs GCN_GMM_K in 1..256"
+                          : gmm_iters < 1                                  ? "needs GCN_GMM_ITERS of at least 1"
+                          : gmm_cov != "diag" && gmm_cov != "spherical"    ? "needs GCN_GMM_COV=diag or spherical"
+                                                                           : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_GMM " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -1199,6 +1226,32 @@ int main(int argc, char **argv) {
                 if (f2 && fclose(f2) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the HDBSCAN labels to ") + hdbscan_path);
                 fprintf(stderr, "gcn-hip: the HDBSCAN labels of %zu test nodes written to %s\n", n, hdbscan_path);
+            }
+            if (gmm_path) {                                    // one rank (checked above): the test nodes in id order
+                ModelQueries &q = gcn.queries();
+                std::vector<int> ids;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == 3) ids.push_back(i);
+                const size_t n = ids.size();
+                if (n < 1) throw GcnHipFailure(-1, "gcn-hip: GCN_GMM found no test nodes to fit");
+                std::vector<int32_t> comp(n);
+                std::vector<float> mr(n), ll(n);
+                const bool spherical = gmm_cov == "spherical";
+                const ModelQueries::Gmm r = q.gmm(gmm_k, 3, nullptr, 0, nullptr, 0, gmm_iters, 1e-3, spherical, 1e-6, true, ModelQueries::GMM_INIT_KMEANS,
+                                                  nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, comp.data(), mr.data(), ll.data(), nullptr,
+                                                  nullptr, nullptr, nullptr, nullptr);
+                if ((size_t)r.rows != n) throw GcnHipFailure(-1, "gcn-hip: GCN_GMM listed other rows than the test nodes");
+                GmmInformation inf;
+                std::string err;
+                if (gcn_gmm_information(r.lower_bound, r.rows, gmm_k, params.hidden_dim, spherical, &inf, &err) != 0) throw GcnHipFailure(-1, "gcn-hip: " + err);
+                printf("gmm_components=%d gmm_iters=%d gmm_converged=%d gmm_lower_bound=%.17g gmm_bic=%.17g gmm_aic=%.17g\n", gmm_k, r.iters_run,
+                       (int)r.converged, r.lower_bound, inf.bic, inf.aic);
+                FILE *f2 = fopen(gmm_path, "w");
+                bool ok = f2 != nullptr;
+                for (size_t i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %d %.9g %.9g\n", ids[i], comp[i], mr[i], ll[i]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the mixture's components to ") + gmm_path);
+                fprintf(stderr, "gcn-hip: the mixture components of %zu test nodes written to %s\n", n, gmm_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

@@ -576,6 +576,47 @@ public:
     };
     LinkRanks link_ranks(const int *src, const int *dst, int n, int metric, bool filtered, bool exclude_self, int32_t *above, int32_t *equal);
 
+    // Gaussian mixture of the hidden layer by expectation maximisation (Dempster, Laird & Rubin, 1977; scikit-learn's GaussianMixture
+    // with diagonal or spherical covariances; include/gcnhip_driver.h has the definitions, csrc/gmm.hip the kernels and every order of
+    // summation, host/gmm_query.cpp the bodies, host/gmm.h the information criteria): soft clusters, a density per node, a likelihood
+    // to compare k by.  Rows and `data` as for dbscan, a repeat being a point of its own.
+    //   gmm: with GMM_INIT_KMEANS the existing kmeans() (k-means++ on the stream seed, 100 iterations at most; not with data); sync();
+    //   embed_forward; the shift = the f32-rounded gcnhip_pca_mean of the listed rows; the first responsibilities are a hard assignment
+    //   — the clustering's, or gcnhip_kmeans_assign to the nearest of the rows at k list positions (GMM_INIT_POSITIONS) or of k given
+    //   means (GMM_INIT_MEANS) — through gcnhip_gmm_mstep's indicator form and gcnhip_gmm_finalize; then at most `iters` times
+    //   {gcnhip_gmm_estep, gcnhip_gmm_mstep, gcnhip_gmm_finalize} until the lower bound (the mean of log p(x_i), read back as one
+    //   double per iteration) changes by less than tol.  scratch_bytes (0: GMM_SCRATCH_DEFAULT) caps the log joint [rows x k] plus the
+    //   M-step's partials; when the log joint does not fit, the E-step runs again per batch of parts in front of the M-step batch that
+    //   needs it: the same bits.  The fit handed back is weights [k], means / variances [k x width] (the shift added back once) and
+    //   shift [width]; one more E-step under exactly these numbers gives log_likelihood / assign / max_resp [rows] by list position
+    //   and, when asked for, resp [rows x k] — so gmm_score() of the same rows repeats them bit for bit.  sizes [k] float64 = N_c of
+    //   the last M-step, history [iters x 2] = (iteration, lower bound), contingency [k x C] of assign against the dataset's labels
+    //   (gcnhip_contingency_rows; nodes of a single-label model with at most 64 classes).  Each output may be NULL.
+    //   gmm_score: sync(); embed_forward; the operands from the given fit; one gcnhip_gmm_estep of the listed rows.  Nothing is cached.
+    // Training state is untouched.  Refused with a message before any launch: more than one rank, bf16 tables, a width above 256, k
+    // outside 1..256 or above the rows listed, iters < 1, tol < 0 or not finite, reg_covar <= 0 or not finite, a bad split, node id or
+    // init; for gmm_score a fit of another width or one that is not finite; with capacity >= 0, more rows listed than the outputs hold.
+    enum GmmInit { GMM_INIT_KMEANS = 0, GMM_INIT_POSITIONS = 1, GMM_INIT_MEANS = 2 };
+    struct Gmm {
+        int k = 0, iters_run = 0;
+        bool converged = false;
+        int64_t rows = 0, skipped = 0;
+        double lower_bound = 0;
+        uint64_t seed = 0;
+    };
+    static constexpr size_t GMM_SCRATCH_DEFAULT = (size_t)256 << 20;
+    // the refusals alone, and the number of rows the query lists; touches no device state
+    int64_t gmm_check(int k, int split, const int *nodes, int n, const float *data, int data_dim, int iters, double tol, double reg_covar, int init,
+                      const int *init_pos, const float *init_means, std::vector<int> *rows = nullptr);
+    int64_t gmm_rows(const char *what, int k, int split, const int *nodes, int n, const float *data, int data_dim, std::vector<int> *rows = nullptr);
+    Gmm gmm(int k, int split, const int *nodes, int n, const float *data, int data_dim, int iters, double tol, bool spherical, double reg_covar,
+            bool normalize, int init, const int *init_pos, const float *init_means, const uint64_t *seed, size_t scratch_bytes, float *weights,
+            float *means, float *variances, int32_t *assign, float *max_resp, float *log_likelihood, float *resp, double *sizes, float *shift,
+            double *history, int64_t *contingency, int64_t capacity = -1);
+    int64_t gmm_score(int k, int width, const float *weights, const float *means, const float *variances, const float *shift, int split,
+                      const int *nodes, int n, const float *data, int data_dim, bool normalize, float *log_likelihood, int32_t *assign, float *max_resp,
+                      float *resp, int64_t capacity = -1);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                       // every device buffer of a query
@@ -746,6 +787,13 @@ private:
     // link_ranks: {src | dst | above | equal} by list position, the thresholds (the filter sets are the overlap pass's)
     Scratch<int32_t> d_lr_int{&arena};
     Scratch<float> d_lr_thr{&arena};
+    // gmm / gmm_score: {rows | assign}, {shift | mu' | var | prec | mprec | weights | cst | lse | max_resp}, the operands of a fit handed
+    // back, {sums | the lower bounds | the mean}, {the E-step's partials | the log joint | the M-step's partials}, the log joint of
+    // resp, the caller's table
+    Scratch<int32_t> d_gm_int{&arena};
+    Scratch<float> d_gm_f32{&arena}, d_gm_fit{&arena}, d_gm_resp{&arena}, d_gm_data{&arena};
+    Scratch<double> d_gm_f64{&arena};
+    Scratch<unsigned char> d_gm_scratch{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);
@@ -778,6 +826,11 @@ private:
     std::vector<int> embed_query(const char *what, const int *nodes, int &n);            // dataset ids (NULL: all) -> local rows
     struct EmbedTable { const float *data; int ld, rows, dim; const float *inv_norm; };
     EmbedTable embed_forward(bool norms);                      // the hidden matrix where variable 3 keeps it (and its inverse norms)
+    // gmm / gmm_score: the table of a query with its list uploaded; one E-step under a fit as it is handed back, and the copies
+    EmbedTable gmm_table(const std::vector<int> &rows, const float *data, int data_dim, bool normalize, int32_t *d_rows);
+    void gmm_estep_fit(const EmbedTable &t, const int32_t *d_rows, int n, int k, const float *weights, const float *means, const float *variances,
+                       const float *shift, float *d_lse, int32_t *d_assign, float *d_max_resp, float *log_likelihood, int32_t *assign, float *max_resp,
+                       float *resp);
     void explain_check(const char *what, bool default_classes) const;
     const std::vector<int> &explain_indptr();
     // the forward of an explanation: variable 3 rewritten; cls = the given classes (checked) or each row's highest logit

@@ -891,6 +891,113 @@ class HipGCNModel:
             out.update(cluster_report(cont))
         return out
 
+    # ---- a Gaussian mixture of the hidden layer: soft clusters, a density per node, BIC / AIC, on the GPU
+    def _gmm_args(self, what, k, iters, tol, covariance_type, reg_covar, init, seed, dim):
+        """argument checks that need no GPU; returns (k, init code, init positions or None, init means or None)"""
+        if covariance_type not in GMM_COVARIANCES:
+            raise GcnHostError(f"{what}: covariance_type is 'diag' or 'spherical' ('full' and 'tied' need a Cholesky per component and are "
+                               f"not built), got {covariance_type!r}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 256:
+            raise GcnHostError(f"{what}: k must be an integer in 1..256, got {k!r}")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+            raise GcnHostError(f"{what}: iters must be an integer >= 1, got {iters!r}")
+        number = (int, float, np.integer, np.floating)
+        if isinstance(tol, bool) or not isinstance(tol, number) or not (np.isfinite(tol) and tol >= 0):
+            raise GcnHostError(f"{what}: tol must be finite and at least 0, got {tol!r}")
+        if isinstance(reg_covar, bool) or not isinstance(reg_covar, number) or not (np.isfinite(reg_covar) and reg_covar > 0):
+            raise GcnHostError(f"{what}: reg_covar must be finite and above 0, got {reg_covar!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64):
+            raise GcnHostError(f"{what}: the seed is an integer in [0, 2^64), got {seed!r}")
+        if isinstance(init, str):
+            if init != "kmeans":
+                raise GcnHostError(f"{what}: init is 'kmeans', an int array of k row positions or a float [k, {dim}] array, got {init!r}")
+            return int(k), 0, None, None
+        arr = np.asarray(init)
+        if arr.dtype.kind in "iu":
+            if arr.shape != (k,):
+                raise GcnHostError(f"{what}: init positions must have shape ({k},), got {arr.shape}")
+            return int(k), 1, np.ascontiguousarray(arr, np.int32), None
+        if arr.dtype.kind != "f" or arr.shape != (k, dim):
+            raise GcnHostError(f"{what}: init means must be a float array of shape ({k}, {dim}), got {arr.dtype} {arr.shape}")
+        return int(k), 2, None, np.ascontiguousarray(arr, np.float32)
+
+    def gmm(self, k, split=None, nodes=None, iters=100, tol=1e-3, covariance_type="diag", reg_covar=1e-6, normalize=True, init="kmeans", seed=None,
+            data=None, report=True, resp=False, scratch_bytes=0):
+        """A Gaussian mixture (scikit-learn's GaussianMixture, covariance_type "diag" or "spherical") of the rows embed() exports, fitted
+        where they lie by expectation maximisation: the E-step is one n x k x 2 hidden product on the exact-f32 MFMA with the
+        log-sum-exp behind it in registers, the M-step a float64-MFMA reduction along the rows in an order fixed by the data — the same
+        bits on every run and with every scratch size.  Rows, normalize and data as for dbscan().  init: "kmeans" (cluster()'s path,
+        `seed` as there), an int array of k list positions, or a float [k, width] array of means; the first M-step takes the hard
+        assignment to them.  WITH data= THE DEFAULT init IS REFUSED: cluster() runs on the model's rows only, so pass positions or
+        means with data.  Stops when the lower bound (the mean of log p(x_i)) changes by less than tol, or after iters.
+        Returns a dict: weights f32 [k], means, variances f32 [k, width] (spherical: the same value along a row), shift f32 [width]
+        (the rows' mean, which the kernels work relative to), assign int32 [n] (the largest responsibility, lowest component on a tie),
+        max_resp, log_likelihood f32 [n] (log p(x_i) under the returned fit; gmm_score() repeats it bit for bit), lower_bound, history
+        float64 [iters_run, 2] = (iteration, lower_bound), iters_run, converged, sizes float64 [k] (N_c), points, n_parameters, bic,
+        aic (gmm_information() of lower_bound), k, covariance_type, normalize; with resp=True resp f32 [n, k] (exp(lj - lse) of the
+        returned log joint formed on the host in float64: within an f32 ulp of, not bit for bit, the device expf the M-step used); with report=True on
+        the nodes of a single-label model with at most 64 classes also contingency, skipped and cluster_report()'s scores of assign.
+        scratch_bytes caps the device scratch (0: 256 MiB).  One rank, f32 tables, width at most 256, k at most the rows listed.
+        Training state is not touched."""
+        what = "gmm"
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        dim = int(d.shape[1]) if d is not None else self.params.hidden_dim
+        k, code, ipos, imeans = self._gmm_args(what, k, iters, tol, covariance_type, reg_covar, init, seed, dim)
+        c = self.params.output_dim
+        want_report = bool(report) and d is None and not self.multilabel and c <= 64
+        m = max(cap, 1)
+        weights, means, variances, shift = np.zeros(k, np.float32), np.zeros((k, dim), np.float32), np.zeros((k, dim), np.float32), np.zeros(dim, np.float32)
+        assign, max_resp, ll = np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        r = np.zeros((m, k), np.float32) if resp else None
+        sizes, hist = np.zeros(k, np.float64), np.zeros((int(iters), 2), np.float64)
+        cont = np.zeros((k, c), np.int64) if want_report else None
+        info, lb = np.zeros(4, np.int64), C.c_double()
+        sp = C.c_uint64(int(seed)) if seed is not None else None
+        _ck(self.lib, self.lib.gcnhost_model_gmm(
+            self.h, k, int(split or 0), q.ctypes.data if q is not None else None, n, d.ctypes.data if d is not None else None,
+            dim if d is not None else 0, int(iters), float(tol), GMM_COVARIANCES[covariance_type], float(reg_covar), int(bool(normalize)), code,
+            ipos.ctypes.data if ipos is not None else None, imeans.ctypes.data if imeans is not None else None,
+            C.byref(sp) if sp is not None else None, int(scratch_bytes), cap, weights.ctypes.data, means.ctypes.data, variances.ctypes.data,
+            assign.ctypes.data, max_resp.ctypes.data, ll.ctypes.data, r.ctypes.data if resp else None, sizes.ctypes.data, shift.ctypes.data,
+            hist.ctypes.data, cont.ctypes.data if want_report else None, info.ctypes.data, C.byref(lb)), what)
+        rows, run = int(info[0]), int(info[1])
+        out = dict(weights=weights, means=means, variances=variances, shift=shift, assign=assign[:rows].copy(), max_resp=max_resp[:rows].copy(),
+                   log_likelihood=ll[:rows].copy(), lower_bound=lb.value, history=hist[:run].copy(), iters_run=run, converged=bool(info[2]),
+                   sizes=sizes, points=rows, k=k, covariance_type=covariance_type, normalize=bool(normalize))
+        out.update(gmm_information(lb.value, rows, k, dim, covariance_type))
+        if resp:
+            out["resp"] = r.ravel()[:rows * k].reshape(rows, k).copy()
+        if want_report:
+            out.update(contingency=cont, skipped=int(info[3]))
+            out.update(cluster_report(cont))
+        return out
+
+    def gmm_score(self, fit, split=None, nodes=None, data=None, resp=False):
+        """One E-step of other rows under a mixture gmm() fitted, at the current weights: dict(log_likelihood f32 [n] — the density
+        score of every listed row, an anomaly score under the distribution the fit saw —, assign int32 [n], max_resp f32 [n] and with
+        resp=True resp f32 [n, k]).  Rows and data as for gmm(); the fit's normalize is used.  Nothing is cached."""
+        what = "gmm_score"
+        try:
+            w, mu, var, sh = (np.ascontiguousarray(fit[key], np.float32) for key in ("weights", "means", "variances", "shift"))
+        except (KeyError, TypeError, ValueError):
+            raise GcnHostError(f"{what}: the fit is the dict gmm() returns (weights, means, variances, shift)") from None
+        if mu.ndim != 2 or var.shape != mu.shape or w.shape != (mu.shape[0],) or sh.shape != (mu.shape[1],) or not 1 <= mu.shape[0] <= 256:
+            raise GcnHostError(f"{what}: the fit's arrays do not fit together: weights {w.shape}, means {mu.shape}, variances {var.shape}, shift {sh.shape}")
+        d, q, n, cap = self._dbscan_rows(what, split, nodes, data)
+        k, dim = mu.shape
+        m = max(cap, 1)
+        assign, max_resp, ll, info = np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(1, np.int64)
+        r = np.zeros((m, k), np.float32) if resp else None
+        _ck(self.lib, self.lib.gcnhost_model_gmm_score(
+            self.h, k, dim, w.ctypes.data, mu.ctypes.data, var.ctypes.data, sh.ctypes.data, int(split or 0), q.ctypes.data if q is not None else None, n,
+            d.ctypes.data if d is not None else None, dim if d is not None else 0, int(bool(fit.get("normalize", True))), cap, ll.ctypes.data,
+            assign.ctypes.data, max_resp.ctypes.data, r.ctypes.data if resp else None, info.ctypes.data), what)
+        rows = int(info[0])
+        out = dict(log_likelihood=ll[:rows].copy(), assign=assign[:rows].copy(), max_resp=max_resp[:rows].copy())
+        if resp:
+            out["resp"] = r.ravel()[:rows * k].reshape(rows, k).copy()
+        return out
+
     # ---- silhouette widths of a clustering of the hidden layer: is this k a good one, which nodes sit badly, on the GPU
     def silhouette(self, labels, k=None, split=None, nodes=None, normalize=True, per_node=True, scratch_bytes=0):
         """Silhouette widths (Rousseeuw, 1987; scikit-learn's silhouette_samples, euclidean) of a labelling of the rows embed()
@@ -1765,6 +1872,41 @@ def cluster_report(contingency):
     out = {name: float(v) for name, v in zip(names, s)}
     out["rows"] = int(s[8])
     return out
+
+
+GMM_COVARIANCES = {"diag": 0, "spherical": 1}
+
+
+def gmm_information(lower_bound, points, k, dim, covariance_type="diag"):
+    """The information criteria of a fitted mixture — host only, no GPU; the one place they are derived (host/gmm.h), scikit-learn's
+    definitions: dict(n_parameters, bic, aic) with 2 k dim + k - 1 free parameters ("diag") or k dim + 2 k - 1 ("spherical"),
+    bic = -2 n lb + p log n, aic = -2 n lb + 2 p for the mean log-likelihood lb of n = points rows."""
+    what = "gmm_information"
+    if covariance_type not in GMM_COVARIANCES:
+        raise GcnHostError(f"{what}: covariance_type is 'diag' or 'spherical' ('full' and 'tied' are not built), got {covariance_type!r}")
+    lib = _lib.gcnhost()
+    out = np.zeros(3, np.float64)
+    _ck(lib, lib.gcnhost_gmm_information(float(lower_bound), int(points), int(k), int(dim), GMM_COVARIANCES[covariance_type], out.ctypes.data), what)
+    return dict(n_parameters=int(out[0]), bic=float(out[1]), aic=float(out[2]))
+
+
+def read_gmm(path):
+    """A mixture's per-node file, one line `node component max_resp log_likelihood` per node: a dict of node, component int32 [n],
+    max_resp and log_likelihood float64 [n].  Needs no GPU."""
+    node, comp, mr, ll = [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            try:
+                if len(p) != 4 or int(p[1]) < 0:
+                    raise ValueError
+                node.append(int(p[0])), comp.append(int(p[1])), mr.append(float(p[2])), ll.append(float(p[3]))
+            except ValueError:
+                raise GcnHostError(f"read_gmm: {path}:{no}: expected `node component max_resp log_likelihood`, got {line.strip()!r}") from None
+    return dict(node=np.array(node, np.int32), component=np.array(comp, np.int32), max_resp=np.array(mr, np.float64),
+                log_likelihood=np.array(ll, np.float64))
 
 
 def read_silhouette(path):

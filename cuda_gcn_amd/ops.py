@@ -682,6 +682,76 @@ class Device:
         out = ab.download()[:nq], eb.download()[:nq]
         return out + (info,) if plan else out
 
+    # ---- Gaussian mixture of the rows of a table (csrc/gmm.hip): table and operands are uploaded with their row strides and NaN
+    # padding, every output and the scratch as garbage
+    def gmm_plan(self, n, k, dim):
+        """gcnhip_gmm_plan: dict(estep_bytes, mstep_bytes, mstep_bytes_min) of device scratch"""
+        a, b, s = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_gmm_plan(int(n), int(k), int(dim), C.byref(a), C.byref(b), C.byref(s))
+        if rc != 0:
+            self._embed_fail("gcnhip_gmm_plan", rc)
+        return dict(estep_bytes=a.value, mstep_bytes=b.value, mstep_bytes_min=s.value)
+
+    def gmm_estep(self, table, shift, prec, mprec, cst, rows=None, inv_norm=None, ld=None, ldc=None, want_lj=True):
+        """gcnhip_gmm_estep: dict(lj f32 [n, k] or None, lse f32 [n], assign int32 [n], max_resp f32 [n], lse_sum float) of the listed rows
+        (None: every row) under the operands prec / mprec f32 [k, dim], cst f32 [k] on rows shifted by shift f32 [dim]"""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        prec, mprec = np.ascontiguousarray(prec, np.float32), np.ascontiguousarray(mprec, np.float32)
+        k, ldc = prec.shape[0], int(ldc or dim)
+        pb, qb = self.padded(prec, ldc), self.padded(mprec, ldc)
+        cb, hb = self.buf(np.ascontiguousarray(cst, np.float32).ravel()), self.buf(np.ascontiguousarray(shift, np.float32).ravel())
+        rb, n = self._kmeans_rows(rows, n_table)
+        sbytes = self.gmm_plan(n, k, dim)["estep_bytes"] if 1 <= k <= 256 else 1024
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        jb = self.buf(np.full(max(n * k, 1), 7.5, np.float32)) if want_lj else None
+        lb, mb = self.buf(np.full(max(n, 1), 7.5, np.float32)), self.buf(np.full(max(n, 1), 7.5, np.float32))
+        ab, ub = self.buf(np.full(max(n, 1), 12345, np.int32)), self.buf(np.full(1, np.nan, np.float64))
+        rc = self.lib.gcnhip_gmm_estep(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, hb.ptr, pb.ptr, qb.ptr,
+                                       ldc, cb.ptr, k, lb.ptr, ab.ptr, mb.ptr, jb.ptr if jb else None, ub.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_gmm_estep", rc)
+        return dict(lj=jb.download()[:n * k].reshape(n, k) if jb else None, lse=lb.download()[:n], assign=ab.download()[:n],
+                    max_resp=mb.download()[:n], lse_sum=float(ub.download()[0]))
+
+    def gmm_mstep(self, table, shift, k, lj=None, lse=None, assign=None, rows=None, inv_norm=None, ld=None, scratch_bytes=None):
+        """gcnhip_gmm_mstep: float64 [k, 1 + 2 dim] = {N | S1 | S2} of the listed rows with r = expf(lj - lse), or with lj None the
+        indicator of assign.  scratch_bytes: the caller's scratch (None: gcnhip_gmm_plan's mstep_bytes)."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        k = int(k)
+        hb = self.buf(np.ascontiguousarray(shift, np.float32).ravel())
+        jb = None if lj is None else self.buf(np.ascontiguousarray(lj, np.float32).ravel() if n else np.zeros(1, np.float32))
+        lb = None if lse is None else self.buf(np.ascontiguousarray(lse, np.float32).ravel() if n else np.zeros(1, np.float32))
+        ab = None if assign is None else self.buf(np.ascontiguousarray(assign, np.int32).ravel() if n else np.zeros(1, np.int32))
+        sbytes = self.gmm_plan(n, k, dim)["mstep_bytes"] if scratch_bytes is None else int(scratch_bytes)
+        sb = self.buf(np.full(max(sbytes // 4, 4), 0x7fc12345, np.uint32))
+        ob = self.buf(np.full(max(k, 1) * (1 + 2 * dim), np.nan, np.float64))
+        rc = self.lib.gcnhip_gmm_mstep(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, hb.ptr,
+                                       jb.ptr if jb else None, lb.ptr if lb else None, ab.ptr if ab else None, k, 0, n, ob.ptr, sb.ptr, sbytes)
+        if rc != 0:
+            self._embed_fail("gcnhip_gmm_mstep", rc)
+        return ob.download().reshape(k, 1 + 2 * dim)
+
+    def gmm_finalize(self, sums, n, mu, var, weights, prec=None, mprec=None, cst=None, spherical=False, reg_covar=1e-6, ldc=None):
+        """gcnhip_gmm_finalize: dict(mu, var, prec, mprec f32 [k, dim], weights, cst f32 [k]) from sums float64 [k, 1 + 2 dim] over n
+        positions (a component that is not fitted keeps what is given); sums None: the operands of mu / var / weights as given"""
+        mu, var = np.ascontiguousarray(mu, np.float32), np.ascontiguousarray(var, np.float32)
+        k, dim = mu.shape
+        ldc = int(ldc or dim)
+        nan2 = np.full((k, dim), np.nan, np.float32)
+        mb, vb = self.padded(mu, ldc), self.padded(var, ldc)
+        pb = self.padded(nan2 if prec is None else np.ascontiguousarray(prec, np.float32), ldc)
+        qb = self.padded(nan2 if mprec is None else np.ascontiguousarray(mprec, np.float32), ldc)
+        wb = self.buf(np.ascontiguousarray(weights, np.float32).ravel())
+        cb = self.buf(np.full(k, np.nan, np.float32) if cst is None else np.ascontiguousarray(cst, np.float32).ravel())
+        sb = None if sums is None else self.buf(np.ascontiguousarray(sums, np.float64).ravel())
+        rc = self.lib.gcnhip_gmm_finalize(self.ctx, sb.ptr if sb else None, int(n), k, dim, int(bool(spherical)), float(reg_covar), mb.ptr, vb.ptr, wb.ptr,
+                                          pb.ptr, qb.ptr, ldc, cb.ptr)
+        if rc != 0:
+            self._embed_fail("gcnhip_gmm_finalize", rc)
+        return dict(mu=mb.download()[:, :dim].copy(), var=vb.download()[:, :dim].copy(), prec=pb.download()[:, :dim].copy(),
+                    mprec=qb.download()[:, :dim].copy(), weights=wb.download(), cst=cb.download())
+
     # ---- k-means on the rows of a table (csrc/kmeans.hip): table and centres are uploaded with their row strides and NaN padding
     def _kmeans_rows(self, rows, n_table):
         r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()

@@ -402,6 +402,36 @@ int gcnhip_link_thresholds(gcnhip_ctx *ctx, const float *table, int ld, int n_ta
 int gcnhip_link_ranks(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *src,
                       const int32_t *dst, int nq, const int32_t *x_ptr, const int32_t *x_len, const int32_t *x_ids, int exclude_self,
                       int chunk_rows, void *scratch, size_t scratch_bytes, int launches, int32_t *above, int32_t *equal);
+/* ---- Gaussian mixture of the rows of a table (gmm.hip; beyond the reference: soft clusters and a density of what a GCN learns) ----
+ * The table contract, d_rows and inv_norm of the k-means calls below.  Everything works on the shifted row x'[j] = (x[r][j] .
+ * inv_norm[r]) - shift[j] (two rounded f32 operations; shift: device f32 [dim], the caller's — the f32-rounded mean of the rows), and
+ * means are kept shifted, mu' = mu - shift.  A component c, 1 <= k <= 256, is mu' / var f32 [k x ldc], weights f32 [k] and the
+ * operands finalize derives from them: prec = 1 / var, mprec = mu' / var [k x ldc], cst[c] = log w_c - (sum_j (mu'^2 / var + log var) +
+ * dim log 2 pi) / 2, float64 inside, rounded to f32 once.  No launch allocates or synchronises, none uses a float atomic; every
+ * output's bits are a function of the arguments' contents alone (gmm.hip's header fixes every order of summation).
+ * gcnhip_gmm_plan (no GPU): the bytes of device scratch the E-step's sum takes, and the M-step's (*mstep_bytes: one batch; down to
+ *   *mstep_bytes_min: more launches, the same bits); each may be NULL.
+ * gcnhip_gmm_estep: lj[i][c] = cst[c] - q(i, c) / 2 (the log joint; q = sum_j x'^2 prec - 2 x' mprec, one f32-MFMA chain), lse[i] =
+ *   log sum_c exp lj, assign[i] = argmax_c lj (the lowest c on a tie), max_resp[i] = exp(lj_max - lse); lj f32 [n x k] may be NULL.
+ *   *lse_sum (device float64, may be NULL; then scratch may be) = the sum of lse over the points by a fixed tree.  A position whose
+ *   row is outside the table: lj, lse, max_resp NaN, assign -1, in no sum.
+ * gcnhip_gmm_mstep: sums float64 [k x (1 + 2 dim)] = {N_c | S1_c | S2_c} over positions [pos0, pos1) with r = expf(lj - lse), or with
+ *   lj == NULL the indicator of assign; on the f64 MFMA.  lj points at position pos0, lse and assign at position 0.  pos0 == 0 starts
+ *   the sums from zero, pos0 > 0 adds to them; pos0 and pos1 lie on parts of 1024 positions (pos1 also at n).
+ * gcnhip_gmm_finalize: from sums: w = N / sum N, mu' = S1 / N, var = max(S2 / N - mu'^2, 0) + reg_covar (spherical != 0: the row's mean
+ *   in every column) into mu / var / weights, and the operands; N_c < 10 . 2^-52 . n: the component keeps mu', var and its operands
+ *   and gets weight 0 and cst -inf.  sums == NULL: the operands from mu / var / weights as they lie.
+ * Refused with -1 and a message (gcnhip_last_error) before any launch: dim outside 1..256, k outside 1..256, a stride below dim, a
+ * NULL array, too little or unaligned scratch, positions off the parts, a reg_covar that is not finite and above 0. */
+int gcnhip_gmm_plan(int n, int k, int dim, size_t *estep_bytes, size_t *mstep_bytes, size_t *mstep_bytes_min);
+int gcnhip_gmm_estep(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows, int n,
+                     const float *shift, const float *prec, const float *mprec, int ldc, const float *cst, int k, float *lse, int32_t *assign,
+                     float *max_resp, float *lj, double *lse_sum, void *scratch, size_t scratch_bytes);
+int gcnhip_gmm_mstep(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows, int n,
+                     const float *shift, const float *lj, const float *lse, const int32_t *assign, int k, int pos0, int pos1, double *sums,
+                     void *scratch, size_t scratch_bytes);
+int gcnhip_gmm_finalize(gcnhip_ctx *ctx, const double *sums, int n, int k, int dim, int spherical, double reg_covar, float *mu, float *var,
+                        float *weights, float *prec, float *mprec, int ldc, float *cst);
 /* ---- k-means on the rows of a table (kmeans.hip; beyond the reference: grouping what a GCN learns, where it lies) ----
  * The table contract of the embedding calls.  d_rows: a device int32 list of n rows, repeats allowed, NULL: rows 0 .. n - 1
  * (then n <= n_table); a list position whose row is outside the table takes no part.  The row used is x^ = x . inv_norm[r]

@@ -376,6 +376,32 @@ int gcnhost_model_link_ranks(gcnhost_model *m, const int *src, const int *dst, i
                              int32_t *equal);
 int gcnhost_link_rank_metrics(const int32_t *above, const int32_t *equal, int64_t n, const int *ks, int n_ks, double *rank, double *summary,
                               double *hits, int64_t *info);
+/* Gaussian mixture of the hidden layer (ModelQueries::gmm / gmm_score, host/queries.h; definitions in include/gcnhip_driver.h,
+ * kernels in csrc/gmm.hip, the criteria in host/gmm.h): soft clusters, a log-likelihood per node, BIC / AIC.  Rows: the nodes of
+ * `split` in ascending id, or with split == 0 the `nodes` query (NULL: every node), or `data` f32 [n x data_dim <= 256] rows instead
+ * of the embeddings.  spherical != 0: one variance per component, else one per component and column.  init: 0 = the k-means of
+ * gcnhost_model_kmeans (k-means++ on *seed, NULL: the model's; not with data); 1 = init_pos [k] list positions; 2 = init_means
+ * [k x width]; the first M-step takes the hard assignment to them.  At most `iters` E / M steps, until the lower bound (the mean
+ * of log p(x_i)) changes by less than tol.  scratch_bytes caps the device scratch (0: 256 MiB; less: more launches, the same bits).
+ * Outputs, each may be NULL: weights [k], means / variances [k x width], assign / max_resp / log_likelihood (laid out for `capacity`
+ * rows, at least the rows listed; under the returned fit), resp [capacity x k], sizes [k] float64 (N_c of the last M-step), shift
+ * [width], history [iters x 2] = (iteration, lower bound), contingency [k x num_classes] of assign against the dataset's labels,
+ * info [4] = {rows listed, iterations run, converged, rows the table skipped}, *result = the last lower bound.
+ * gcnhost_model_gmm_score: one E-step of other rows under a fit (k, width and the four arrays gcnhost_model_gmm returned) at the
+ *   current weights; the same rows under the same weights repeat the fit's log_likelihood bit for bit.  info [1] = {rows listed}.
+ * gcnhost_gmm_information (no GPU): out [3] = {free parameters, BIC, AIC} (2 k dim + k - 1 parameters, spherical k dim + 2 k - 1;
+ *   bic = -2 n lb + p log n, aic = -2 n lb + 2 p).
+ * Training state is not touched.  Refused with a message before any launch: several ranks, bf16 tables, a width above 256, k outside
+ * 1..256 or above the rows listed, iters < 1, tol < 0 or not finite, reg_covar <= 0 or not finite, a bad split, init, position or
+ * node id, a fit of another width or one that is not finite. */
+int gcnhost_model_gmm(gcnhost_model *m, int k, int split, const int *nodes, int n, const float *data, int data_dim, int iters, double tol, int spherical,
+                      double reg_covar, int normalize, int init, const int *init_pos, const float *init_means, const uint64_t *seed, size_t scratch_bytes,
+                      int64_t capacity, float *weights, float *means, float *variances, int32_t *assign, float *max_resp, float *log_likelihood,
+                      float *resp, double *sizes, float *shift, double *history, int64_t *contingency, int64_t *info, double *result);
+int gcnhost_model_gmm_score(gcnhost_model *m, int k, int width, const float *weights, const float *means, const float *variances, const float *shift,
+                            int split, const int *nodes, int n, const float *data, int data_dim, int normalize, int64_t capacity,
+                            float *log_likelihood, int32_t *assign, float *max_resp, float *resp, int64_t *info);
+int gcnhost_gmm_information(double lower_bound, int64_t points, int k, int dim, int spherical, double *out);
 /* k-means on the hidden layer (ModelQueries::kmeans, host/queries.h; kernels in csrc/kmeans.hip): the rows gcnhost_model_embed
  * exports, grouped on the device.  Rows: the nodes of `split` (1 train, 2 validation, 3 test) in ascending id, or with split == 0
  * the `nodes` query (n dataset ids in the order given, repeats allowed; NULL: every node in id order).  normalize != 0: unit
