@@ -135,6 +135,9 @@ GCNHIP_SYMBOLS = {
     "gcnhip_gmm_estep": (I, [P, P, I, I, I, P, P, I, P, P, P, I, P, I, P, P, P, P, P, P, C.c_size_t]),
     "gcnhip_gmm_mstep": (I, [P, P, I, I, I, P, P, I, P, P, P, P, I, I, I, P, P, C.c_size_t]),
     "gcnhip_gmm_finalize": (I, [P, P, I, I, I, I, C.c_double, P, P, P, P, P, I, P]),
+    "gcnhip_mmd_plan": (I, [I, I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gcnhip_mmd_walk": (I, [P, P, I, I, I, P, P, I, P, C.c_float, P, I, I, P, C.c_size_t]),
+    "gcnhip_mmd_fold": (I, [P, I, I, I, I, P, C.c_size_t, P, P, P]),
     "gcnhip_kmeans_plan": (I, [I, I, I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "gcnhip_kmeans_assign": (I, [P, P, I, I, I, P, P, I, P, I, P, I, P, P, P, P]),
     "gcnhip_kmeans_update": (I, [P, P, I, I, I, P, P, I, P, P, I, P, I, P, P, P, P, C.c_size_t]),
@@ -317,6 +320,8 @@ GCNHOST_SYMBOLS = {
                               P, P]),
     "gcnhost_model_gmm_score": (I, [P, I, I, P, P, P, P, I, P, I, P, I, I, I64, P, P, P, P, P]),
     "gcnhost_gmm_information": (I, [C.c_double, I64, I, I, I, P]),
+    "gcnhost_model_mmd": (I, [P, P, I, I, P, I, I, P, I, P, I, I, C.c_size_t, P, P, P, P]),
+    "gcnhost_mmd_stats": (I, [P, I, I64, I64, P, P, P]),
     "gcnhost_model_kmeans": (I, [P, I, I, P, I, I, I, I, P, P, P, C.c_size_t, I64, P, P, P, P, P, P, P, P, P, P]),
     "gcnhost_cluster_report": (I, [I, I, P, P]),
     "gcnhost_model_silhouette": (I, [P, I, P, I, P, I, I, C.c_size_t, I64, P, P, P, P, P, P, P, P]),

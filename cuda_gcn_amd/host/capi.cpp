@@ -20,6 +20,7 @@
 #include "hdbscan.h"
 #include "linkrank.h"
 #include "gmm.h"
+#include "mmd.h"
 #include "pca.h"
 #include "structure.h"
 #include "reach.h"
@@ -397,6 +398,22 @@ int gcnhost_gmm_information(double lower_bound, int64_t points, int k, int dim, 
     if (!out) { g_err = "gmm_information: invalid argument"; return -1; }
     if (gcn_gmm_information(lower_bound, points, k, dim, spherical != 0, &r, &g_err) != 0) return -1;
     out[0] = (double)r.n_parameters; out[1] = r.bic; out[2] = r.aic;
+    return 0;
+}
+int gcnhost_model_mmd(gcnhost_model *m, const int *nodes, int n, int m_a, const float *data, int data_dim, int normalize, const double *gamma, int n_gamma,
+                      const uint8_t *perm_bits, int permutations, int want_witness, size_t scratch_bytes, double *sums, float *witness, double *gamma_used,
+                      int64_t *info) {
+    if (!m) { g_err = "gcnhost_model_mmd: invalid argument"; return -1; }
+    API_TRY({
+        ModelQueries &q = m->gcn->queries();
+        const ModelQueries::Mmd r = q.mmd(nodes, n, m_a, data, data_dim, normalize != 0, gamma, n_gamma, perm_bits, permutations, want_witness != 0,
+                                          scratch_bytes, sums, witness, gamma_used);
+        if (info) { info[0] = r.rows; info[1] = r.m; info[2] = r.rest; info[3] = r.n_gamma; }
+    })
+}
+int gcnhost_mmd_stats(const double *sums, int cols, int64_t m, int64_t rest, double *biased, double *unbiased, double *p_value) {
+    if (!sums || cols < 1) { g_err = "mmd_stats: invalid argument (at least one column, two groups that are not empty)"; return -1; }
+    if (gcn_mmd_stats(sums, sums + cols, sums + 2 * (size_t)cols, cols, m, rest, biased, unbiased, p_value, &g_err) != 0) return -1;
     return 0;
 }
 int gcnhost_cluster_report(int k, int num_classes, const int64_t *counts, double *summary) {

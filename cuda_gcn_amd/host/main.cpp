@@ -196,6 +196,14 @@
 //                            printed: `gmm_components=<k> gmm_iters=<t> gmm_converged=<0|1> gmm_lower_bound=<lb> gmm_bic=<b>
 //                            gmm_aic=<a>`.  The file gets one line per test node in id order: `node component max_resp
 //                            log_likelihood` (%.9g: f32 exactly).
+// Kernel two-sample test between two splits (beyond the reference; ModelQueries::mmd, kernels in csrc/mmd.hip, the statistics in
+// host/mmd.h), after the mixture.  One GPU, hidden_dim at most 256, f32 tables:
+//   GCN_MMD=<file>           MMD^2 (RBF kernel) between the unit rows of the hidden layer of the nodes of the two splits
+//                            GCN_MMD_SPLITS=a,b (default 1,3: train against test) with GCN_MMD_GAMMA (default: 1 / the mean squared
+//                            distance of two distinct rows) and a permutation test of GCN_MMD_PERMS permutations (default 200; drawn
+//                            by mt19937_64 on GCN_SEED with a Fisher-Yates shuffle).  One line is printed: `mmd2=<biased>
+//                            mmd2_unbiased=<u> p=<p> gamma=<g>` (%.17g).  The file gets one line per row, group A's in id order and then
+//                            group B's: `node group witness` (group 0: A, 1: B; %.9g: f32 exactly).
 // Multi-label training (beyond the reference):
 //   GCN_MULTILABEL=<file>    the truth is the label file (host/labels.h: one line per node, comma-separated class ids), read and
 //                            checked before the GPU is touched; output_dim = its number of classes (largest id + 1).  The loss is
@@ -209,11 +217,14 @@
 //                            format; the loss columns are the weighted loss.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <iostream>
+#include <numeric>
+#include <random>
 #include <string>
 #include <thread>
 #include <unistd.h>
@@ -232,6 +243,7 @@
 #include "overlap.h"
 #include "linkrank.h"
 #include "gmm.h"
+#include "mmd.h"
 #include "report.h"
 #include "thresholds.h"
 
@@ -558,6 +570,28 @@ int main(int argc, char **argv) {
                                                                            : nullptr;
         if (why) {
             std::cerr << "gcn-hip: GCN_GMM " << why << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+
+    const char *mmd_path = getenv("GCN_MMD");
+    if (mmd_path && !*mmd_path) mmd_path = nullptr;
+    const int mmd_perms = env_int("GCN_MMD_PERMS", 200);
+    const double mmd_gamma = getenv("GCN_MMD_GAMMA") && *getenv("GCN_MMD_GAMMA") ? atof(getenv("GCN_MMD_GAMMA")) : 0.0;   // 0: the default
+    int mmd_a = 1, mmd_b = 3;
+    if (mmd_path) {
+        const char *sp = getenv("GCN_MMD_SPLITS");
+        const bool parsed = !sp || !*sp || sscanf(sp, "%d,%d", &mmd_a, &mmd_b) == 2;
+        const char *why = env_int("GCN_GPUS", 1) > 1                                              ? "runs on one GPU (GCN_GPUS is above 1)"
+                          : params.hidden_dim > 256                                               ? "takes a hidden width of at most 256"
+                          : env_int("GCN_BF16_TABLES", 0)                                         ? "needs f32 tables (GCN_BF16_TABLES is set)"
+                          : !parsed || mmd_a < 1 || mmd_a > 3 || mmd_b < 1 || mmd_b > 3 || mmd_a == mmd_b ? "needs GCN_MMD_SPLITS=a,b with two different splits of 1..3"
+                          : mmd_perms < 0                                                         ? "needs GCN_MMD_PERMS of at least 0"
+                          : getenv("GCN_MMD_GAMMA") && *getenv("GCN_MMD_GAMMA") && (!(mmd_gamma > 0.0) || !std::isfinite(mmd_gamma))
+                              ? "needs a GCN_MMD_GAMMA that is finite and above 0"
+                              : nullptr;
+        if (why) {
+            std::cerr << "gcn-hip: GCN_MMD " << why << std::endl;
             return EXIT_FAILURE;
         }
     }
@@ -1252,6 +1286,42 @@ int main(int argc, char **argv) {
                 if (f2 && fclose(f2) != 0) ok = false;
                 if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the mixture's components to ") + gmm_path);
                 fprintf(stderr, "gcn-hip: the mixture components of %zu test nodes written to %s\n", n, gmm_path);
+            }
+            if (mmd_path) {                                    // one rank (checked above): split a's nodes in id order, then split b's
+                ModelQueries &q = gcn.queries();
+                std::vector<int> ids;
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == mmd_a) ids.push_back(i);
+                const int m_a = (int)ids.size();
+                for (int i = 0; i < params.num_nodes; i++)
+                    if (data.split[i] == mmd_b) ids.push_back(i);
+                const size_t n = ids.size();
+                const int pb = (mmd_perms + 7) / 8;
+                std::vector<uint8_t> bits(n * (size_t)std::max(pb, 1), 0);
+                std::mt19937_64 rng((uint64_t)base.seed);
+                std::vector<uint32_t> order(n);
+                for (int p = 0; p < mmd_perms; p++) {          // the first m_a of a shuffled list are the permutation's group A
+                    std::iota(order.begin(), order.end(), 0u);
+                    for (size_t i = n; i > 1; i--) std::swap(order[i - 1], order[rng() % i]);
+                    for (int i = 0; i < m_a; i++) bits[order[i] * (size_t)pb + (p >> 3)] |= (uint8_t)(1 << (p & 7));
+                }
+                const int cols = 1 + mmd_perms;
+                std::vector<double> sums(3 * (size_t)cols), biased(cols), unbiased(cols);
+                std::vector<float> wit(n);
+                double used = 0, p_value = 0;
+                const ModelQueries::Mmd r = q.mmd(ids.data(), (int)n, m_a, nullptr, 0, true, mmd_gamma > 0.0 ? &mmd_gamma : nullptr, mmd_gamma > 0.0 ? 1 : 0,
+                                                  bits.data(), mmd_perms, true, 0, sums.data(), wit.data(), &used);
+                std::string err;
+                if (gcn_mmd_stats(sums.data(), sums.data() + cols, sums.data() + 2 * (size_t)cols, cols, r.m, r.rest, biased.data(), unbiased.data(), &p_value,
+                                  &err) != 0)
+                    throw GcnHipFailure(-1, "gcn-hip: " + err);
+                printf("mmd2=%.17g mmd2_unbiased=%.17g p=%.17g gamma=%.17g\n", biased[0], unbiased[0], p_value, used);
+                FILE *f2 = fopen(mmd_path, "w");
+                bool ok = f2 != nullptr;
+                for (size_t i = 0; ok && i < n; i++) ok = fprintf(f2, "%d %d %.9g\n", ids[i], (int)i < m_a ? 0 : 1, wit[i]) > 0;
+                if (f2 && fclose(f2) != 0) ok = false;
+                if (!ok) throw GcnHipFailure(-1, std::string("gcn-hip: could not write the witness to ") + mmd_path);
+                fprintf(stderr, "gcn-hip: the witness of %zu nodes (splits %d and %d) written to %s\n", n, mmd_a, mmd_b, mmd_path);
             }
             if ((o.flags & HIPGCN_TIMERS) && rank == 0) {
                 static const char *names[] = {"train", "test", "matmul_fw", "matmul_bw", "spmatmul_fw", "spmatmul_bw", "graphsum_fw",

@@ -617,6 +617,31 @@ public:
                       const int *nodes, int n, const float *data, int data_dim, bool normalize, float *log_likelihood, int32_t *assign, float *max_resp,
                       float *resp, int64_t capacity = -1);
 
+    // Kernel two-sample sums of two groups of rows of the hidden layer (MMD^2 with the RBF kernel and a permutation test; Gretton et
+    // al., 2012; include/gcnhip_driver.h has the definitions, csrc/mmd.hip the kernels and every order of summation, host/mmd_query.cpp
+    // the body, host/mmd.h the statistics): do the rows trained on and the rows predicted on come from one distribution in the space
+    // the class layer sees?  The list is `nodes` [n] (dataset ids), group A its first m_a entries and group B the rest, or `data` f32
+    // [n x data_dim <= 256] rows instead of the embeddings.  sync(); embed_forward; the list; the shift = the f32-rounded
+    // gcnhip_pca_mean of the listed rows; gamma [n_gamma <= 4], or with n_gamma == 0 the default (n - 1) / (2 trace(gcnhip_pca_scatter))
+    // = 1 / the mean squared distance of two distinct rows; then per gamma and per chunk of at most 254 permutations gcnhip_mmd_walk and
+    // gcnhip_mmd_fold on S = {ones | group A | the chunk's permuted groups}.  perm_bits: host uint8 [n x ceil(permutations / 8)], bit
+    // (p & 7) of byte p >> 3 of position i = i is in permutation p's group A (the caller draws them: nothing here is random).
+    // Outputs, each may be NULL: sums float64 [gammas x 3 x (1 + permutations)] = {AA | AB | BB} of the observed groups and then of each
+    // permutation (gcn_mmd_stats takes them), witness f32 [gammas x n] by list position, gamma_used [gammas] (the f32 value, widened).
+    // scratch_bytes caps a walk's device scratch (0: MMD_SCRATCH_DEFAULT; less: more launches, the same bits).  Training state is
+    // untouched, nothing is cached.  Refused with a message before any launch: more than one rank, bf16 tables, a width above 256, an
+    // empty group, a gamma that is not finite and above 0, more than 4 of them, permutations < 0, a node in both groups or outside the graph.
+    struct Mmd {
+        int64_t rows = 0, m = 0, rest = 0;
+        int n_gamma = 0;
+    };
+    static constexpr size_t MMD_SCRATCH_DEFAULT = (size_t)256 << 20;
+    static constexpr int MMD_CHUNK = 254, MMD_MAX_GAMMAS = 4;
+    int64_t mmd_check(const int *nodes, int n, int m_a, const float *data, int data_dim, const double *gamma, int n_gamma, const uint8_t *perm_bits,
+                      int permutations, std::vector<int> *rows = nullptr);
+    Mmd mmd(const int *nodes, int n, int m_a, const float *data, int data_dim, bool normalize, const double *gamma, int n_gamma, const uint8_t *perm_bits,
+            int permutations, bool want_witness, size_t scratch_bytes, double *sums, float *witness, double *gamma_used);
+
 private:
     HipGCN &m;
     DeviceArena arena;                                       // every device buffer of a query
@@ -794,6 +819,11 @@ private:
     Scratch<float> d_gm_f32{&arena}, d_gm_fit{&arena}, d_gm_resp{&arena}, d_gm_data{&arena};
     Scratch<double> d_gm_f64{&arena};
     Scratch<unsigned char> d_gm_scratch{&arena};
+    // mmd: {rows | counts}, {shift | witness}, {mean | scatter | sums}, the membership bits, the walk's scratch, the caller's table
+    Scratch<int32_t> d_mmd_int{&arena};
+    Scratch<float> d_mmd_f32{&arena}, d_mmd_data{&arena};
+    Scratch<double> d_mmd_f64{&arena};
+    Scratch<unsigned char> d_mmd_bits{&arena}, d_mmd_scratch{&arena};
 
     void query_rows(const char *what, const int *nodes, int n, std::vector<int> &rows);   // dataset ids -> local rows
     const gcnhip_rowset *query_subset(const std::vector<int> &rows);

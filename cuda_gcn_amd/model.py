@@ -119,7 +119,8 @@ class HipGCNModel:
                                                      int(rank), int(world), nccl_id, self._ag, self._ar, None)
             _ck(lib, rc, "gcnhost_model_create_multilabel")
         self.h = h
-        self._keep = None           # the C++ side copied everything it needs
+        self._split = k[5]          # mmd() lists the nodes of two splits here, where it draws the permutations
+        self._keep = None           # the C++ side copied everything else it needs
 
     def train_epoch(self):
         a, b = C.c_float(), C.c_float()
@@ -996,6 +997,94 @@ class HipGCNModel:
         out = dict(log_likelihood=ll[:rows].copy(), assign=assign[:rows].copy(), max_resp=max_resp[:rows].copy())
         if resp:
             out["resp"] = r.ravel()[:rows * k].reshape(rows, k).copy()
+        return out
+
+    # ---- kernel two-sample test of two groups of rows of the hidden layer: do they come from one distribution? on the GPU
+    def _mmd_args(self, what, gamma, permutations, seed, a=None, b=None):
+        """argument checks that need no GPU; returns (gammas float64 array or None, permutations)"""
+        if isinstance(permutations, bool) or not isinstance(permutations, (int, np.integer)) or permutations < 0:
+            raise GcnHostError(f"{what}: permutations must be an integer >= 0, got {permutations!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64):
+            raise GcnHostError(f"{what}: the seed is an integer in [0, 2^64), got {seed!r}")
+        g = None
+        if gamma is not None:
+            try:
+                g = np.atleast_1d(np.asarray(gamma, np.float64)).ravel()
+            except (TypeError, ValueError):
+                raise GcnHostError(f"{what}: gamma is a float or a list of at most 4 floats, got {gamma!r}") from None
+            if isinstance(gamma, bool) or not 1 <= g.size <= 4:
+                raise GcnHostError(f"{what}: gamma is a float or a list of at most 4 floats, got {gamma!r}")
+            if not np.all(np.isfinite(g) & (g > 0)):
+                raise GcnHostError(f"{what}: gamma must be finite and above 0, got {gamma!r}")
+        if a is not None and b is not None:
+            if a.size < 1 or b.size < 1:
+                raise GcnHostError(f"{what}: an empty group ({a.size} and {b.size} rows)")
+            both = np.intersect1d(a, b)
+            if both.size:
+                raise GcnHostError(f"{what}: the groups overlap: node {int(both[0])} is in both")
+        return g, int(permutations)
+
+    def mmd(self, split_a=1, split_b=3, nodes_a=None, nodes_b=None, gamma=None, permutations=200, seed=None, normalize=True, data=None, groups=None,
+            witness=True, scratch_bytes=0):
+        """The kernel two-sample test (MMD^2 with the RBF kernel k = exp(-gamma |x - y|^2); Gretton et al., 2012) between two groups
+        of the rows embed() exports, with a permutation test — do the rows trained on and the rows predicted on come from one
+        distribution in the space the class layer sees?  Matrix-free on the GPU: tiles of the n x n kernel matrix are formed on the
+        exact-f32 MFMA and multiplied, in the registers they land in, with the 0/1 membership matrix of every permutation at once;
+        the same bits on every run and with every scratch size.  Groups: the nodes of split_a and split_b (1 train, 2 validation, 3
+        test), or nodes_a / nodes_b (dataset ids; they must not overlap), or data: any float [n, d <= 256] array with groups [n]
+        (non-zero: group A).  gamma: a float or a list of at most 4 (one walk each); None: 1 / the mean squared distance of two
+        distinct rows.  The permutations are drawn here with numpy.random.default_rng(seed) (seed None: the model's stream seed) and
+        uploaded as bits; the kernels draw nothing.  Returns a dict: mmd2_biased, mmd2_unbiased (self pairs removed; NaN when a group
+        has one row), p_value = (1 + #{null >= mmd2_biased}) / (1 + permutations), null float64 [permutations] (the biased statistic
+        of every permutation), gamma (the f32 value used), each with a leading axis when gamma is a list; m, n (the rows of A and B),
+        permutations; with witness=True witness f32 [m + n] = mean_A k(x, .) - mean_B k(x, .) at every row of the list (A's rows first;
+        where the groups differ) and nodes (the ids of the list, or with data its positions).  scratch_bytes caps the device scratch
+        (0: 256 MiB).  One rank, f32 tables, width at most 256.  Training state is not touched."""
+        what = "mmd"
+        if data is not None:
+            if nodes_a is not None or nodes_b is not None:
+                raise GcnHostError(f"{what}: with data the rows are the data's: no node query")
+            d = np.ascontiguousarray(data, np.float32)
+            if d.ndim != 2 or not 1 <= d.shape[1] <= 256 or d.shape[0] < 1:
+                raise GcnHostError(f"{what}: data must be a float [n, d <= 256] array, got shape {d.shape}")
+            if groups is None or np.asarray(groups).shape != (d.shape[0],):
+                raise GcnHostError(f"{what}: with data, groups is an array of {d.shape[0]} flags (non-zero: group A)")
+            flag = np.asarray(groups) != 0
+            a, b = np.flatnonzero(flag).astype(np.int32), np.flatnonzero(~flag).astype(np.int32)
+        else:
+            if self.params.hidden_dim > 256:
+                raise GcnHostError(f"{what}: a hidden width of at most 256, this model has {self.params.hidden_dim}")
+            d, split = None, self._split
+            for s in (split_a if nodes_a is None else 1, split_b if nodes_b is None else 1):
+                if s not in (1, 2, 3):
+                    raise GcnHostError(f"{what}: a split is 1 (train), 2 (validation) or 3 (test), got {s!r}")
+            a = np.flatnonzero(split == split_a).astype(np.int32) if nodes_a is None else np.ascontiguousarray(nodes_a, np.int32).ravel()
+            b = np.flatnonzero(split == split_b).astype(np.int32) if nodes_b is None else np.ascontiguousarray(nodes_b, np.int32).ravel()
+        g, perms = self._mmd_args(what, gamma, permutations, seed, a, b)
+        ids = np.concatenate([a, b])
+        m, n = int(a.size), int(ids.size)
+        if d is not None:
+            d = np.ascontiguousarray(d[ids])
+        rng = np.random.default_rng(self.stream_seed if seed is None else int(seed))
+        member = np.zeros((n, perms), bool)
+        for p in range(perms):
+            member[rng.permutation(n)[:m], p] = True
+        bits = np.packbits(member, axis=1, bitorder="little") if perms else np.zeros((n, 1), np.uint8)
+        ng = 1 if g is None else int(g.size)
+        sums, used, info = np.zeros((ng, 3, 1 + perms), np.float64), np.zeros(ng, np.float64), np.zeros(4, np.int64)
+        wit = np.zeros((ng, n), np.float32) if witness else None
+        _ck(self.lib, self.lib.gcnhost_model_mmd(
+            self.h, ids.ctypes.data if d is None else None, n, m, d.ctypes.data if d is not None else None, int(d.shape[1]) if d is not None else 0,
+            int(bool(normalize)), g.ctypes.data if g is not None else None, 0 if g is None else ng, bits.ctypes.data, perms, int(bool(witness)),
+            int(scratch_bytes), sums.ctypes.data, wit.ctypes.data if witness else None, used.ctypes.data, info.ctypes.data), what)
+        stats = [mmd_stats(sums[i], int(info[1]), int(info[2])) for i in range(ng)]
+        many = gamma is not None and np.ndim(gamma) > 0
+        pick = (lambda v: np.array(v)) if many else (lambda v: v[0])
+        out = dict(mmd2_biased=pick([float(s["biased"][0]) for s in stats]), mmd2_unbiased=pick([float(s["unbiased"][0]) for s in stats]),
+                   p_value=pick([s["p_value"] for s in stats]), null=pick([s["biased"][1:].copy() for s in stats]), gamma=pick([float(v) for v in used]),
+                   m=int(info[1]), n=int(info[2]), permutations=perms)
+        if witness:
+            out.update(witness=wit if many else wit[0], nodes=ids)
         return out
 
     # ---- silhouette widths of a clustering of the hidden layer: is this k a good one, which nodes sit badly, on the GPU
@@ -1888,6 +1977,22 @@ def gmm_information(lower_bound, points, k, dim, covariance_type="diag"):
     out = np.zeros(3, np.float64)
     _ck(lib, lib.gcnhost_gmm_information(float(lower_bound), int(points), int(k), int(dim), GMM_COVARIANCES[covariance_type], out.ctypes.data), what)
     return dict(n_parameters=int(out[0]), bic=float(out[1]), aic=float(out[2]))
+
+
+def mmd_stats(sums, m, n):
+    """The kernel two-sample statistics from the sums the GPU leaves — host only, no GPU; the one place they are derived (host/mmd.h).
+    sums float64 [3, cols] = {AA | AB | BB}: the sums of k over the ordered pairs inside group A (m rows), across, and inside group B
+    (n rows), self pairs included and worth 1; column 0 the observed groups, the rest permuted ones.  Returns dict(biased float64
+    [cols] = AA / m^2 + BB / n^2 - 2 AB / (m n), unbiased float64 [cols] (self pairs removed; NaN when a group has one row: it has no
+    pair of distinct rows), p_value = (1 + #{b >= 1 : biased[b] >= biased[0]}) / cols)."""
+    s = np.ascontiguousarray(sums, np.float64)
+    if s.ndim != 2 or s.shape[0] != 3 or s.shape[1] < 1:
+        raise GcnHostError(f"mmd_stats: sums must be a float64 [3, cols >= 1] array, got shape {s.shape}")
+    lib = _lib.gcnhost()
+    cols = int(s.shape[1])
+    biased, unbiased, p = np.zeros(cols, np.float64), np.zeros(cols, np.float64), C.c_double()
+    _ck(lib, lib.gcnhost_mmd_stats(s.ctypes.data, cols, int(m), int(n), biased.ctypes.data, unbiased.ctypes.data, C.byref(p)), "mmd_stats")
+    return dict(biased=biased, unbiased=unbiased, p_value=p.value)
 
 
 def read_gmm(path):

@@ -752,6 +752,44 @@ class Device:
         return dict(mu=mb.download()[:, :dim].copy(), var=vb.download()[:, :dim].copy(), prec=pb.download()[:, :dim].copy(),
                     mprec=qb.download()[:, :dim].copy(), weights=wb.download(), cst=cb.download())
 
+    # ---- kernel two-sample sums of the rows of a table (csrc/mmd.hip): the table is uploaded with its row stride and NaN padding,
+    # every output and the scratch as garbage
+    def mmd_plan(self, n, dim, bp, want_witness=False):
+        """gcnhip_mmd_plan: dict(bytes, bytes_min) of device scratch"""
+        a, b = C.c_size_t(), C.c_size_t()
+        rc = self.lib.gcnhip_mmd_plan(int(n), int(dim), int(bp), int(bool(want_witness)), C.byref(a), C.byref(b))
+        if rc != 0:
+            self._embed_fail("gcnhip_mmd_plan", rc)
+        return dict(bytes=a.value, bytes_min=b.value)
+
+    def mmd_walk(self, table, shift, gamma, member, rows=None, inv_norm=None, ld=None, want_witness=False, scratch_bytes=None):
+        """gcnhip_mmd_walk and gcnhip_mmd_fold: dict(sums float64 [3, Bp] = {AA | AB | BB} per column of member, points, m, witness f32
+        [n] or None) of the listed rows (None: every row) shifted by shift f32 [dim] under k = exp(-gamma d2).  member: 0/1 [n, Bp],
+        column 0 ones, column 1 group A, the rest permuted groups; Bp a multiple of 16 in 16..256.  scratch_bytes: the caller's
+        scratch (None: gcnhip_mmd_plan's bytes)."""
+        tb, nb, n_table, dim, ld = self._embed_inputs(table, ld, inv_norm)
+        rb, n = self._kmeans_rows(rows, n_table)
+        member = np.asarray(member) != 0
+        bp = int(member.shape[1])
+        bits = np.packbits(member, axis=1, bitorder="little") if bp % 8 == 0 else member.astype(np.uint8)
+        bb = self.buf(np.ascontiguousarray(bits).ravel() if n else np.zeros(4, np.uint8))
+        hb = self.buf(np.ascontiguousarray(shift, np.float32).ravel())
+        sbytes = scratch_bytes
+        if sbytes is None:
+            sbytes = self.mmd_plan(n, dim, bp, want_witness)["bytes"] if bp % 16 == 0 and 16 <= bp <= 256 and 1 <= dim <= 256 else 1024
+        sb = self.buf(np.full(max(int(sbytes) // 4, 4), 0x7fc12345, np.uint32))
+        ob, cb = self.buf(np.full(3 * max(bp, 1), np.nan, np.float64)), self.buf(np.full(2, -777, np.int32))
+        wb = self.buf(np.full(max(n, 1), 7.5, np.float32)) if want_witness else None
+        rc = self.lib.gcnhip_mmd_walk(self.ctx, tb.ptr, ld, n_table, dim, nb.ptr if nb else None, rb.ptr if rb else None, n, hb.ptr, float(gamma),
+                                      bb.ptr, bp, int(bool(want_witness)), sb.ptr, int(sbytes))
+        if rc != 0:
+            self._embed_fail("gcnhip_mmd_walk", rc)
+        rc = self.lib.gcnhip_mmd_fold(self.ctx, n, dim, bp, int(bool(want_witness)), sb.ptr, int(sbytes), ob.ptr, cb.ptr, wb.ptr if wb else None)
+        if rc != 0:
+            self._embed_fail("gcnhip_mmd_fold", rc)
+        counts = cb.download()
+        return dict(sums=ob.download().reshape(3, bp), points=int(counts[0]), m=int(counts[1]), witness=wb.download()[:n] if wb else None)
+
     # ---- k-means on the rows of a table (csrc/kmeans.hip): table and centres are uploaded with their row strides and NaN padding
     def _kmeans_rows(self, rows, n_table):
         r = None if rows is None else np.ascontiguousarray(rows, np.int32).ravel()

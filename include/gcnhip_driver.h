@@ -432,6 +432,33 @@ int gcnhip_gmm_mstep(gcnhip_ctx *ctx, const float *table, int ld, int n_table, i
                      void *scratch, size_t scratch_bytes);
 int gcnhip_gmm_finalize(gcnhip_ctx *ctx, const double *sums, int n, int k, int dim, int spherical, double reg_covar, float *mu, float *var,
                         float *weights, float *prec, float *mprec, int ldc, float *cst);
+/* ---- Kernel two-sample sums of the rows of a table (mmd.hip; beyond the reference: do two groups of nodes come from one
+ * distribution in the space the class layer sees?  MMD^2 of Gretton et al., 2012, with a permutation test) ----
+ * Rows: the table contract, d_rows and inv_norm of the silhouette calls: two positions that name one row are two points, a position
+ * whose row is outside the table is no point.  Operands: x'[j] = (x[r][j] . inv_norm[r]) - shift[j], two rounded f32 operations
+ * (shift: device f32 [dim], the caller's — the f32-rounded float64 mean of gcnhip_pca_mean; the kernel is translation invariant, the
+ * shift only removes cancellation).  d2(i, j) = max(xn_i + xn_j - 2 x'_i . x'_j, 0), the dot the f32 fma chain in column order;
+ * k(i, j) = expf(-gamma . d2), and exactly 1 for a self pair (the same list position).
+ * Membership: bits, device uint8 [n x Bp / 8], bit (b & 7) of byte b >> 3 of position i = S[i][b] (numpy.packbits, bitorder "little").
+ * Column 0 is all ones, column 1 the observed group A, columns 2.. permuted groups; Bp is a multiple of 16 in 16..256, callers chunk
+ * more permutations.  What is no point counts with all bits zero, and its k is 0.
+ * Per column b, float64: T_b[q] = sum_r k(q, r) S[r][b], R = T_0, AA_b = sum_{q in A_b} T_b[q], AB_b = sum_{q not in A_b} T_b[q],
+ * BB_b = sum_{q not in A_b} (R[q] - T_b[q]); the witness f[q] = T_1[q] / m - (R[q] - T_1[q]) / n', m = the points of column 1, n' =
+ * the other points.  mmd.hip's header fixes every order of summation; no launch draws a random number, allocates, synchronises or
+ * uses a float atomic: every output's bits are a function of the arguments' contents alone.
+ * gcnhip_mmd_plan (no GPU): the bytes of device scratch of a call that walks every part of 1024 positions in one launch (*bytes) and
+ *   the least (*bytes_min: one part per launch, the same bits); each may be NULL.
+ * gcnhip_mmd_walk: packs the operands, walks the n x n kernel entries in tiles on the f32 MFMA with the product K . S fused behind
+ *   them, and adds each launch's partials onto running sums in the scratch.  want_witness != 0 keeps T_0 and T_1 per position too.
+ * gcnhip_mmd_fold: hands what the walk left in the same scratch (same n, dim, Bp, want_witness): sums float64 [3 x Bp] = {AA | AB |
+ *   BB}, counts int32 [2] = {points, m}, and with want_witness witness f32 [n] (NaN for what is no point).
+ * Refused with -1 and a message (gcnhip_last_error) before any launch: dim outside 1..256, a Bp that is no multiple of 16 in 16..256,
+ * a stride below dim, a gamma that is negative or not finite, a NULL array, too little or unaligned scratch. */
+int gcnhip_mmd_plan(int n, int dim, int Bp, int want_witness, size_t *bytes, size_t *bytes_min);
+int gcnhip_mmd_walk(gcnhip_ctx *ctx, const float *table, int ld, int n_table, int dim, const float *inv_norm, const int32_t *d_rows, int n,
+                    const float *shift, float gamma, const uint8_t *bits, int Bp, int want_witness, void *scratch, size_t scratch_bytes);
+int gcnhip_mmd_fold(gcnhip_ctx *ctx, int n, int dim, int Bp, int want_witness, const void *scratch, size_t scratch_bytes, double *sums,
+                    int32_t *counts, float *witness);
 /* ---- k-means on the rows of a table (kmeans.hip; beyond the reference: grouping what a GCN learns, where it lies) ----
  * The table contract of the embedding calls.  d_rows: a device int32 list of n rows, repeats allowed, NULL: rows 0 .. n - 1
  * (then n <= n_table); a list position whose row is outside the table takes no part.  The row used is x^ = x . inv_norm[r]

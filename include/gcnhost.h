@@ -402,6 +402,24 @@ int gcnhost_model_gmm_score(gcnhost_model *m, int k, int width, const float *wei
                             int split, const int *nodes, int n, const float *data, int data_dim, int normalize, int64_t capacity,
                             float *log_likelihood, int32_t *assign, float *max_resp, float *resp, int64_t *info);
 int gcnhost_gmm_information(double lower_bound, int64_t points, int k, int dim, int spherical, double *out);
+/* Kernel two-sample test of two groups of rows of the hidden layer (ModelQueries::mmd, host/queries.h; definitions in
+ * include/gcnhip_driver.h, kernels in csrc/mmd.hip, the statistics in host/mmd.h): MMD^2 with the RBF kernel and a permutation test.
+ * The list is `nodes` [n] (dataset ids): group A its first m_a entries, group B the rest; or `data` f32 [n x data_dim <= 256] rows
+ * instead of the embeddings (nodes NULL).  gamma [n_gamma <= 4]; n_gamma == 0: 1 / the mean squared distance of two distinct rows.
+ * perm_bits: uint8 [n x ceil(permutations / 8)], bit (p & 7) of byte p >> 3 of position i = i is in permutation p's group A; the
+ * caller draws the permutations, nothing here is random.  scratch_bytes caps the device scratch (0: 256 MiB; less: more launches,
+ * the same bits).  Outputs, each may be NULL: sums float64 [gammas x 3 x (1 + permutations)] = {AA | AB | BB}, the observed groups
+ * first, witness f32 [gammas x n] by list position (want_witness != 0), gamma_used [gammas], info [4] = {rows, the points of group A,
+ * of group B, gammas}.
+ * gcnhost_mmd_stats (no GPU): from sums [3 x cols] of one gamma and the two counts: biased [cols] = AA / m^2 + BB / n'^2 - 2 AB / (m n'),
+ *   unbiased [cols] with the self pairs removed analytically (NaN when a group has one point: no pair of distinct points), *p_value =
+ *   (1 + #{b >= 1 : biased[b] >= biased[0]}) / cols.
+ * Training state is not touched.  Refused with a message before any launch: several ranks, bf16 tables, a width above 256, an empty
+ * group, a gamma that is not finite and above 0, more than 4 of them, permutations < 0, a node in both groups or outside the graph. */
+int gcnhost_model_mmd(gcnhost_model *m, const int *nodes, int n, int m_a, const float *data, int data_dim, int normalize, const double *gamma, int n_gamma,
+                      const uint8_t *perm_bits, int permutations, int want_witness, size_t scratch_bytes, double *sums, float *witness, double *gamma_used,
+                      int64_t *info);
+int gcnhost_mmd_stats(const double *sums, int cols, int64_t m, int64_t rest, double *biased, double *unbiased, double *p_value);
 /* k-means on the hidden layer (ModelQueries::kmeans, host/queries.h; kernels in csrc/kmeans.hip): the rows gcnhost_model_embed
  * exports, grouped on the device.  Rows: the nodes of `split` (1 train, 2 validation, 3 test) in ascending id, or with split == 0
  * the `nodes` query (n dataset ids in the order given, repeats allowed; NULL: every node in id order).  normalize != 0: unit
