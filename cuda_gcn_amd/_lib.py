@@ -183,6 +183,11 @@ GCNHIP_SYMBOLS = {
     "gcnhip_overlap_rows_ex": (I, [P, P, P, P, P, I, P, P, P, P, I, I, I, I]),
     "gcnhip_overlap_pairs": (I, [P, P, P, P, P, P, I, P, P, P, P, P]),
     "gcnhip_overlap_pairs_ex": (I, [P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I]),
+    "gcnhip_louvain_plan": (I, [I, I64, C.POINTER(I64)]),
+    "gcnhip_louvain_level": (I, [P, I, I64, P, P, P, P, P, I, P, P, P, P, I64]),
+    "gcnhip_louvain_level_ex": (I, [P, I, I64, P, P, P, P, P, I, P, P, P, P, I64, I, I, I]),
+    "gcnhip_louvain_coarsen": (I, [P, I, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I]),
+    "gcnhip_louvain_compose": (I, [P, P, I, P, I]),
     "gcnhip_explain_hops": (I, [P, P, P, P, I, P, I, I, P, I, I, I, P, P, I, P, P, P, I64]),
     "gcnhip_explain_features_agg": (I, [P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I, I, P, I]),
     "gcnhip_explain_features_walk": (I, [P, P, P, P, P, I, P, I, I, P, I, I, P, I, I, P, I]),
@@ -352,6 +357,8 @@ GCNHOST_SYMBOLS = {
     "gcnhost_model_clustering": (I, [P, I, P, I, I64, P, P, P, P]),
     "gcnhost_model_link_overlap": (I, [P, P, P, I, I, P, P, P, P, P, P]),
     "gcnhost_overlap_metrics": (I, [P, P, P, I64, P, P]),
+    "gcnhost_model_communities": (I, [P, I, I, P, P, P, I, P, P]),
+    "gcnhost_modularity_from_sums": (C.c_double, [I64, I64]),
     "gcnhost_triangles_write": (I, [C.c_char_p, P, P, P, P, I64]),
     "gcnhost_triangles_read": (I, [C.c_char_p, P, P, P, P, P, I64, C.POINTER(I64)]),
     "gcnhost_model_explain": (I, [P, P, P, I, C.c_size_t, P, P, P, P, P, P, P, C.POINTER(I64)]),

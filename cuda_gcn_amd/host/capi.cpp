@@ -758,6 +758,20 @@ int gcnhost_model_link_overlap(gcnhost_model *m, const int *src, const int *dst,
         if (info) { info[0] = r.rows; info[1] = r.skipped; }
     })
 }
+int gcnhost_model_communities(gcnhost_model *m, int max_levels, int max_sweeps, int32_t *labels, int64_t *records, int32_t *level_labels,
+                              int level_capacity, int64_t *contingency, int64_t *info) {
+    if (!m || !records || !info || level_capacity < 0) { g_err = "gcnhost_model_communities: invalid argument"; return -1; }
+    API_TRY({
+        const LouvainRun r = m->gcn->queries().communities(max_levels, max_sweeps, labels, level_labels, level_capacity, contingency);
+        int64_t moved = 0;
+        for (size_t i = 0; i < r.levels.size(); i++) {
+            records[3 * i] = r.levels[i].vertices; records[3 * i + 1] = r.levels[i].sweeps; records[3 * i + 2] = r.levels[i].numerator;
+            moved += i + 1 < r.levels.size() || r.communities < r.levels[i].vertices;
+        }
+        info[0] = (int64_t)r.levels.size(); info[1] = r.communities; info[2] = r.numerator; info[3] = r.m2; info[4] = moved; info[5] = r.contingency_rows; info[6] = r.skipped;
+    })
+}
+double gcnhost_modularity_from_sums(int64_t numerator, int64_t m2) { return gcn_modularity_from_sums(numerator, m2); }
 int gcnhost_overlap_metrics(const int64_t *totals, const int64_t *t2, const int32_t *deg, int64_t n, double *summary, double *clustering) {
     OverlapMetrics r;
     if (gcn_overlap_metrics(totals, &r, &g_err) != 0) return -1;

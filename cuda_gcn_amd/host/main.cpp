@@ -139,6 +139,11 @@
 //                            TEST split, counted on the GPU by intersecting neighbour sets.  One line is printed: `triangles=<n>
 //                            transitivity=<t> avg_clustering=<c>` (over the test nodes).  The file gets `node deg t2 clustering`
 //                            per test node behind the totals (host/overlap.h).  Works with GCN_LOAD_WEIGHTS and 0 epochs.
+// Louvain communities of the adjacency (beyond the reference; ModelQueries::communities, kernels and definitions in
+// csrc/louvain.hip, the report in host/louvain.h), after the test line and the steps above.  One GPU; no weights are needed:
+//   GCN_COMMUNITIES=<file>   multi-level Louvain over every node (32 levels, 100 sweeps a level at most).  One line is printed:
+//                            `communities=<k> modularity=<Q> louvain_levels=<l> louvain_sweeps=<s>`.  The file gets a header, a line
+//                            `# Q <Q> numerator <n> m2 <m>` and `node community` per node.  Works with GCN_LOAD_WEIGHTS and 0 epochs.
 // Link prediction ranks (beyond the reference; ModelQueries::link_ranks, kernels in csrc/linkrank.hip, metrics in host/linkrank.h),
 // after the test line and the steps above.  One GPU, hidden_dim at most 256, f32 tables:
 //   GCN_LINK_EDGES=<file>    with GCN_LINK_RANKS=<file>: every line `src dst` of the first file is a held-out edge, ranked among all
@@ -632,6 +637,13 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
 
+    const char *communities_path = getenv("GCN_COMMUNITIES");
+    if (communities_path && !*communities_path) communities_path = nullptr;
+    if (communities_path && env_int("GCN_GPUS", 1) > 1) {
+        std::cerr << "gcn-hip: GCN_COMMUNITIES runs on one GPU (GCN_GPUS is above 1)" << std::endl;
+        return EXIT_FAILURE;
+    }
+
     const char *link_edges_path = getenv("GCN_LINK_EDGES"), *link_ranks_path = getenv("GCN_LINK_RANKS");
     if (link_edges_path && !*link_edges_path) link_edges_path = nullptr;
     if (link_ranks_path && !*link_ranks_path) link_ranks_path = nullptr;
@@ -1065,6 +1077,17 @@ int main(int argc, char **argv) {
                     throw GcnHipFailure(-1, "gcn-hip: " + (err.empty() ? std::string("GCN_TRIANGLES: the test split changed size") : err));
                 printf("triangles=%lld transitivity=%.6f avg_clustering=%.6f\n", (long long)om.triangles, om.transitivity, om.avg_clustering);
                 fprintf(stderr, "gcn-hip: the triangles of %lld test nodes written to %s\n", (long long)r.rows, triangles_path);
+            }
+            if (communities_path) {                            // one rank (checked above): every node
+                std::vector<int32_t> labels((size_t)params.num_nodes);
+                const LouvainRun run = gcn.queries().communities(32, 100, labels.data(), nullptr, 0, nullptr);
+                std::string err;
+                if (gcn_communities_write(communities_path, run, labels, &err) != 0) throw GcnHipFailure(-1, "gcn-hip: " + err);
+                long long sweeps = 0;
+                for (const LouvainLevel &l : run.levels) sweeps += l.sweeps;
+                printf("communities=%lld modularity=%.6f louvain_levels=%zu louvain_sweeps=%lld\n", (long long)run.communities,
+                       gcn_modularity_from_sums(run.numerator, run.m2), run.levels.size(), sweeps);
+                fprintf(stderr, "gcn-hip: the communities of %d nodes written to %s\n", params.num_nodes, communities_path);
             }
             if (link_ranks_path) {                             // one rank (checked above): the listed edges, filtered, the node itself excluded
                 const int n = (int)link_src.size();

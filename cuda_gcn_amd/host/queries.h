@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 #include "device_arena.h"
+#include "louvain.h"
 
 class HipGCN;
 
@@ -560,6 +561,16 @@ public:
     Overlap clustering(int split, const int *nodes, int n, int64_t *t2, int32_t *deg, int64_t *totals);
     Overlap link_overlap(const int *src, const int *dst, int n, int weight_mask, int32_t *cn, int32_t *un, int64_t *pa, int64_t *aa, int64_t *ra);
 
+    // Louvain communities of the model's adjacency (csrc/louvain.hip has the definitions and the kernels, host/louvain_query.cpp
+    // the body, host/louvain.h the modularity): sync(); the canonical pass of the overlap queries; then level after level
+    // (gcnhip_louvain_level, gcnhip_louvain_coarsen, gcnhip_louvain_compose) until a level moves nothing or max_levels ran.  labels
+    // int32 [nodes] by dataset id (may be NULL); level_labels (may be NULL) int32 [level_capacity x nodes]: the composed labelling
+    // behind every level that moved; contingency (may be NULL) int64 with room for 256 x output_dim: the communities against the
+    // dataset's labels (gcnhip_contingency_rows), filled on a single-label model with at most 64 classes when there are at most 256
+    // communities (then contingency_rows = communities).  Needs neither weights nor a forward; training state is untouched.  Refused before any launch:
+    // more than one rank, max_levels < 1, max_sweeps < 0, a model that renumbered its nodes.
+    LouvainRun communities(int max_levels, int max_sweeps, int32_t *labels, int32_t *level_labels, int level_capacity, int64_t *contingency);
+
     // Link prediction ranks (include/gcnhip_driver.h has the definitions, csrc/linkrank.hip the kernels, host/linkrank_query.cpp the
     // body, host/linkrank.h the metrics): how good the embedding scores of similar() / score_pairs() are as a link scorer.  Query i
     // is a held-out edge (src[i], dst[i]) of dataset ids; its candidates are every node except dst[i], src[i] with exclude_self, and
@@ -809,6 +820,9 @@ private:
     Scratch<int32_t> d_ov_idx{&arena}, d_ov_len{&arena}, d_ov_sort{&arena}, d_ov_int{&arena};
     Scratch<int64_t> d_ov_long{&arena};
     void overlap_sets();                                       // the canonical pass into d_ov_idx / d_ov_len
+    // communities: {labels | comm | label | two coarse levels}, {tot | the coarse self weights}, the kernels' scratch
+    Scratch<int32_t> d_lv_int{&arena};
+    Scratch<int64_t> d_lv_long{&arena}, d_lv_scratch{&arena};
     // link_ranks: {src | dst | above | equal} by list position, the thresholds (the filter sets are the overlap pass's)
     Scratch<int32_t> d_lr_int{&arena};
     Scratch<float> d_lr_thr{&arena};

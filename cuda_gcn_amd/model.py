@@ -1472,6 +1472,45 @@ class HipGCNModel:
             out[w] = (aa if w == "adamic_adar" else ra)[:n] / 2.0 ** 32
         return out
 
+    def communities(self, max_levels=32, max_sweeps=100, report=True, levels=False):
+        """The modularity communities of the model's adjacency: multi-level Louvain (Blondel et al., 2008) on the GPU with
+        synchronous, deterministic moves decided in exact integers (csrc/louvain.hip has the definitions), so every run and every
+        launch shape gives the same labels.  The graph is the neighbour sets of clustering(): the distinct entries of a node's
+        stored row without itself, no transpose built — a one-way entry counts in one row only, and `modularity` is the textbook
+        modularity exactly when the stored graph is symmetric; nothing checks that.  A node with an empty set stays alone.
+        Returns a dict: labels int32 [num_nodes] by dataset id (communities numbered by ascending smallest member — ready for
+        neighbor_agreement(labels=...), silhouette(labels=...)), communities, modularity, numerator, m2 (modularity =
+        modularity_from_sums(numerator, m2)), level_records [(vertices, sweeps, modularity)] per level run.  report=True on a
+        single-label model with at most 64 classes and at most 256 communities: also contingency int64 [communities, C] against
+        the dataset's labels, counted on the GPU, skipped and cluster_report()'s scores.  levels=True: also level_labels, the
+        labelling behind every level that moved.  Needs neither weights nor a forward; one rank.  Training state is not touched."""
+        what = "communities"
+        for name, v, lo in (("max_levels", max_levels, 1), ("max_sweeps", max_sweeps, 0)):
+            if isinstance(v, bool) or int(v) != v or v < lo or v > 1 << 20:
+                raise GcnHostError(f"{what}: {name} must be an integer from {lo}, got {v!r}")
+        n, c = self.params.num_nodes, self.params.output_dim
+        want_report = bool(report) and not self.multilabel and c <= 64
+        labels, records, info = np.zeros(max(n, 1), np.int32), np.zeros((int(max_levels), 3), np.int64), np.zeros(7, np.int64)
+        cont = np.zeros((256, c), np.int64) if want_report else None
+        room = min(int(max_levels), 16)                            # labellings kept per call; a run that kept more levels is run again
+        while True:
+            per_level = np.zeros((room, max(n, 1)), np.int32) if levels else None
+            _ck(self.lib, self.lib.gcnhost_model_communities(self.h, int(max_levels), int(max_sweeps), labels.ctypes.data, records.ctypes.data,
+                                                             per_level.ctypes.data if levels else None, room, cont.ctypes.data if want_report else None,
+                                                             info.ctypes.data), what)
+            if not levels or int(info[4]) <= room:
+                break
+            room = int(info[4])
+        run, k, m2 = int(info[0]), int(info[1]), int(info[3])
+        out = dict(labels=labels[:n], communities=k, modularity=modularity_from_sums(int(info[2]), m2), numerator=int(info[2]), m2=m2,
+                   level_records=[(int(v), int(sw), modularity_from_sums(int(num), m2)) for v, sw, num in records[:run]])
+        if levels:
+            out["level_labels"] = [per_level[i, :n].copy() for i in range(int(info[4]))]
+        if want_report and int(info[5]) == k and k >= 1:
+            out.update(contingency=cont.ravel()[:k * c].reshape(k, c).copy(), skipped=int(info[6]))
+            out.update(cluster_report(out["contingency"]))
+        return out
+
     def _structure_query(self, what, split, nodes):
         """argument checks that need no GPU; returns (split code, node ids int32 or None, n, capacity)"""
         if split is not None and nodes is not None:
@@ -1945,6 +1984,15 @@ def map_quality_metrics(sums, points, k):
     return dict(trustworthiness=float(out[0]), continuity=float(out[1]), knn_overlap=float(out[2]))
 
 
+def modularity_from_sums(numerator, m2):
+    """Q = numerator / m2^2 in float64 from the exact integer sums of communities() (numerator = M2 . sum in - sum tot^2, m2 = the
+    stored set entries); 0 when m2 is 0 — host only"""
+    numerator, m2 = int(numerator), int(m2)
+    if m2 < 0:
+        raise GcnHostError(f"modularity_from_sums: m2 is a count, got {m2}")
+    return float(numerator) / (float(m2) * float(m2)) if m2 else 0.0
+
+
 def cluster_report(contingency):
     """The scores of a clustering against class labels from the integer table contingency [k, C] (rows: clusters) — host only,
     no GPU; the one place they are derived (host/kmeans.h has the formulas).  Returns a dict of float64: purity, homogeneity,
@@ -2340,6 +2388,24 @@ def write_triangles(path, node, deg, t2, totals):
     if not (v.size == d.size == a.size) or t.size != 8:
         raise GcnHostError("write_triangles: node, deg and t2 list the same rows, totals holds 8 integers")
     _ck(lib, lib.gcnhost_triangles_write(os.fspath(path).encode(), v.ctypes.data, d.ctypes.data, a.ctypes.data, t.ctypes.data, v.size), "write_triangles")
+
+
+def read_communities(path):
+    """The report `gcn-hip` writes for GCN_COMMUNITIES: dict(node int32 [n], labels int32 [n], communities, levels, modularity (the
+    float64 the program formed), numerator, m2) — host only"""
+    try:
+        with open(path) as f:
+            lines = f.read().splitlines()
+    except OSError as e:
+        raise GcnHostError(f"read_communities: cannot open {path}") from e
+    head, sums = (lines[0].split() if lines else []), (lines[1].split() if len(lines) > 1 else [])
+    if head[:3] != ["gcn-communities", "1", "nodes"] or len(head) != 8 or sums[:2] != ["#", "Q"] or len(sums) != 7:
+        raise GcnHostError(f"read_communities: {path} does not start with a gcn-communities 1 header")
+    rows = np.array([ln.split() for ln in lines[2:] if ln and not ln.startswith("#")], np.int64).reshape(-1, 2)
+    if rows.shape[0] != int(head[3]):
+        raise GcnHostError(f"read_communities: {path} is not a complete communities report")
+    return dict(node=rows[:, 0].astype(np.int32), labels=rows[:, 1].astype(np.int32), communities=int(head[5]), levels=int(head[7]),
+                modularity=float(sums[2]), numerator=int(sums[4]), m2=int(sums[6]))
 
 
 def read_triangles(path):

@@ -77,6 +77,13 @@ class Buf:
             pass
 
 
+class _DevPtr:
+    """a device array somebody else owns (an adjacency object's row pointers)"""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+
 class Device:
     """one GPU context (device + stream + scratch)"""
 
@@ -1444,6 +1451,70 @@ class Device:
             self._embed_fail("gcnhip_overlap_pairs", rc)
         return dict(cn=cb.download()[:n] if cb else None, un=ub.download()[:n] if ub else None, wsum=xb.download()[:n] if xb else None,
                     skipped=int(kb.download()[0]))
+
+    # ---- Louvain communities (csrc/louvain.hip): every output is uploaded as garbage, the calls write all of it.  A level is a
+    # dict(n, entries, ptr, len, idx, w, self_w) of device arrays (anything with .ptr; len / w / self_w may be None)
+    def louvain_level0(self, g, sets):
+        """level 0 on a Graph and the (set_idx, set_len) of overlap_sets: the object's own row pointers, w = 1, self_w = 0"""
+        pp, nr, nnz = C.c_void_p(), C.c_int(), C.c_int()
+        _ck(self.lib, self.lib.gcnhip_graph_arrays(g.h, C.byref(pp), None, None, C.byref(nr), C.byref(nnz)), "graph_arrays")
+        return dict(n=nr.value, entries=nnz.value, ptr=_DevPtr(pp.value), len=sets[1], idx=sets[0], w=None, self_w=None)
+
+    def louvain_upload(self, ptr, idx, w=None, self_w=None, length=None):
+        """a level from host arrays"""
+        ptr, idx = np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(idx, np.int32)
+        up = lambda a, t: None if a is None else self.buf(np.ascontiguousarray(a, t) if np.size(a) else np.zeros(1, t))
+        return dict(n=ptr.size - 1, entries=int(ptr[-1]), ptr=self.buf(ptr), len=up(length, np.int32), idx=up(idx, np.int32), w=up(w, np.uint32),
+                    self_w=up(self_w, np.int64))
+
+    def _louvain_scratch(self, lv):
+        need = C.c_int64(-777)
+        rc = self.lib.gcnhip_louvain_plan(lv["n"], lv["entries"], C.byref(need))
+        if rc != 0:
+            self._embed_fail("gcnhip_louvain_plan", rc)
+        return self.buf(np.full(need.value // 4, 0x5A5A5A5A, np.int32)), need.value
+
+    @staticmethod
+    def _louvain_args(lv):
+        return (lv["n"], lv["entries"]) + tuple(lv[k].ptr if lv[k] is not None else None for k in ("ptr", "len", "idx", "w", "self_w"))
+
+    def louvain_level(self, lv, max_sweeps=100, group=0, wg_cut=0, table=0):
+        """gcnhip_louvain_level(_ex): dict(comm Buf int32 [n], tot Buf int64 [n], sweeps, moved, num, m2, wg_rows, long_rows);
+        group / wg_cut / table: anything but the defaults goes through gcnhip_louvain_level_ex"""
+        n = lv["n"]
+        cb, tb = self.buf(np.full(max(n, 1), 0x5A5A5A5A, np.int32)), self.buf(np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, np.int64))
+        sb, need = self._louvain_scratch(lv)
+        info = np.full(8, -777, np.int64)
+        args = (self.ctx,) + self._louvain_args(lv) + (int(max_sweeps), cb.ptr, tb.ptr, info.ctypes.data, sb.ptr, need)
+        if group or wg_cut or table:
+            rc = self.lib.gcnhip_louvain_level_ex(*args, int(group), int(wg_cut), int(table))
+        else:
+            rc = self.lib.gcnhip_louvain_level(*args)
+        if rc != 0:
+            self._embed_fail("gcnhip_louvain_level", rc)
+        return dict(comm=cb, tot=tb, sweeps=int(info[0]), moved=bool(info[1]), num=int(info[2]), m2=int(info[3]), wg_rows=int(info[4]),
+                    long_rows=int(info[5]))
+
+    def louvain_coarsen(self, lv, comm, table=0):
+        """gcnhip_louvain_coarsen on a level and the comm Buf of louvain_level: (label Buf int32 [n], the coarse level with its
+        ragged rows: ptr / len / idx / w / self_w)"""
+        n, e = lv["n"], max(lv["entries"], 1)
+        i32 = lambda m: self.buf(np.full(max(m, 1), 0x5A5A5A5A, np.int32))
+        lb, pb, nb, ib = i32(n), i32(n + 1), i32(n), i32(e)
+        wb, fb = self.buf(np.full(e, 0x5A5A5A5A, np.uint32)), self.buf(np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, np.int64))
+        sb, need = self._louvain_scratch(lv)
+        info = np.full(2, -777, np.int64)
+        rc = self.lib.gcnhip_louvain_coarsen(self.ctx, *self._louvain_args(lv), comm.ptr, lb.ptr, pb.ptr, nb.ptr, ib.ptr, wb.ptr, fb.ptr, info.ctypes.data,
+                                             sb.ptr, need, int(table))
+        if rc != 0:
+            self._embed_fail("gcnhip_louvain_coarsen", rc)
+        return lb, dict(n=int(info[0]), entries=int(info[1]), ptr=pb, len=nb, idx=ib, w=wb, self_w=fb)
+
+    def louvain_compose(self, labels, n, label, n_label):
+        """gcnhip_louvain_compose: labels[i] = label[labels[i]] in place (Bufs)"""
+        rc = self.lib.gcnhip_louvain_compose(self.ctx, labels.ptr, int(n), label.ptr, int(n_label))
+        if rc != 0:
+            self._embed_fail("gcnhip_louvain_compose", rc)
 
     # ---- new nodes attached to a trained graph (csrc/attach.hip): tables are uploaded with their row stride and NaN padding
     def attach_gather(self, ptr, col, coef, table_a, table_b, epilogue="none", beta=1.0, ld_a=None, ld_b=None, ld_out=None, logp=False,

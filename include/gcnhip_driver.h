@@ -785,6 +785,39 @@ int gcnhip_overlap_pairs(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *
 int gcnhip_overlap_pairs_ex(gcnhip_ctx *ctx, const gcnhip_graph *g, const int32_t *set_idx, const int32_t *set_len, const int32_t *src,
                             const int32_t *dst, int n_pairs, const int64_t *wt, int32_t *cn, int32_t *un, int64_t *wsum, int64_t *skipped,
                             int group, int wg_cut, int slice, int bitmap);
+/* ---- Louvain communities (louvain.hip; beyond the reference: the graph's own grouping, in exact integers) ----
+ * A LEVEL is a weighted graph on n vertices: ptr device int32 [n + 1]; len device int32 [n] (NULL: ptr[v + 1] - ptr[v]), row v is
+ * idx[ptr[v] .. ptr[v] + len[v]) — the form gcnhip_overlap_sets leaves; idx distinct per row without the self entry; w device uint32
+ * > 0 (NULL: 1); self_w device int64 [n] (NULL: 0).  `entries` (host) bounds the extent ptr[n] and is below 2^31.  louvain.hip's
+ * header has the definitions (k, M2, tot, in, num = M2 . sum in - sum tot^2, the synchronous sweep, its undo, the coarsening).
+ * gcnhip_louvain_plan: *scratch_bytes (host) for a level of n vertices and `entries`, no GPU needed: with r(x) = x rounded up to 16
+ *   and T the smallest power of two >= 2 max(1, min(entries, n)): max(64 + 2 r(8 n) + 5 r(4 n) + 2 r(4 T), 64 + 8 r(4 (n + 1))).
+ * gcnhip_louvain_level: one level from singletons to its end.  comm device int32 [n], tot device int64 [n] (tot by community
+ *   label; 0 for a label without members); info host int64 [8] = {sweeps run, 1 when a sweep was kept, num, M2, rows left to a
+ *   workgroup, rows on the global-memory table, sum in, sum tot^2}.  Reads three scalars back per sweep.
+ * gcnhip_louvain_level_ex: also the lane group (0: by entries / n; 4, 16, 64), the row length above which a row goes to a workgroup
+ *   (0: half the group's share of 4096 LDS slots; never above it) and the workgroup's table in slots (0: the largest power of two
+ *   the device's LDS holds, at most 16384; else a power of two from 256 up to that); rows longer than half of it use the table in
+ *   the scratch, one after another.
+ * gcnhip_louvain_coarsen: label device int32 [n] = every vertex's community renumbered by ascending smallest member; the coarse
+ *   level c_ptr int32 [n + 1] (entries past the coarse vertices repeat the extent), c_len int32 [n], c_idx int32 / c_w uint32
+ *   [entries], c_self int64 [n]: row C has room for min(sum of its members' row lengths, coarse vertices - 1) entries and holds
+ *   c_len[C], sorted.  info host int64 [2] = {coarse vertices, extent}.  table as above (0: the default): a coarse row whose room is
+ *   above half of it is merged in a dense array in the scratch.  Synchronises once, before the merge launches, for info and the
+ *   LDS the merge needs (sized by the largest room it meets, as the level call sizes the workgroup launch by its longest row).
+ * gcnhip_louvain_compose: labels[i] = label[labels[i]] for i < n (a value outside [0, n_label) is left).
+ * Nothing is allocated.  Refused with -1 and a message before any launch: a NULL required pointer, a negative count, 2^31 entries
+ * or more, min(entries, n) of 2^30 or more (a row that long would need a table past 32-bit slots), a lane group other than 0 / 4 / 16 / 64, a negative cut, a table that is no such power of two, too little scratch. */
+int gcnhip_louvain_plan(int n, int64_t entries, int64_t *scratch_bytes);
+int gcnhip_louvain_level(gcnhip_ctx *ctx, int n, int64_t entries, const int32_t *ptr, const int32_t *len, const int32_t *idx, const uint32_t *w,
+                         const int64_t *self_w, int max_sweeps, int32_t *comm, int64_t *tot, int64_t *info, void *scratch, int64_t scratch_bytes);
+int gcnhip_louvain_level_ex(gcnhip_ctx *ctx, int n, int64_t entries, const int32_t *ptr, const int32_t *len, const int32_t *idx, const uint32_t *w,
+                            const int64_t *self_w, int max_sweeps, int32_t *comm, int64_t *tot, int64_t *info, void *scratch, int64_t scratch_bytes,
+                            int group, int wg_cut, int table);
+int gcnhip_louvain_coarsen(gcnhip_ctx *ctx, int n, int64_t entries, const int32_t *ptr, const int32_t *len, const int32_t *idx, const uint32_t *w,
+                           const int64_t *self_w, const int32_t *comm, int32_t *label, int32_t *c_ptr, int32_t *c_len, int32_t *c_idx, uint32_t *c_w,
+                           int64_t *c_self, int64_t *info, void *scratch, int64_t scratch_bytes, int table);
+int gcnhip_louvain_compose(gcnhip_ctx *ctx, int32_t *labels, int n, const int32_t *label, int n_label);
 /* ---- explaining a logit (explain.hip; beyond the reference: WHY the model answers what it answers) ----
  * The network is Z = A^ . (ReLU(A^ . X . W1) . W2) without bias, so with the ReLU gates of a forward fixed a logit is a plain sum
  * that splits without approximation ("gradient x input" is a decomposition here).  One query = a row v of the adjacency object and

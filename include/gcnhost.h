@@ -649,6 +649,18 @@ int gcnhost_overlap_metrics(const int64_t *totals, const int64_t *t2, const int3
 int gcnhost_triangles_write(const char *path, const int32_t *node, const int32_t *deg, const int64_t *t2, const int64_t *totals, int64_t n);
 int gcnhost_triangles_read(const char *path, int32_t *node, int32_t *deg, int64_t *t2, double *clustering, int64_t *totals, int64_t capacity,
                            int64_t *n);
+/* Louvain communities of the model's adjacency (ModelQueries::communities, host/queries.h; definitions and kernels in
+ * csrc/louvain.hip; the modularity in host/louvain.h): multi-level Louvain with synchronous, deterministic moves in exact integers,
+ * on the neighbour sets of the overlap queries (no transpose: the textbook modularity exactly when the stored graph is symmetric).
+ * labels int32 [nodes] by dataset id (may be NULL): communities numbered by ascending smallest member.  records int64
+ * [max_levels x 3] = {vertices, sweeps, numerator} per level run.  level_labels (may be NULL) int32 [level_capacity x nodes]: the
+ * composed labelling behind the first level_capacity levels that moved.  contingency (may be NULL) int64 with room for 256 x output_dim: communities
+ * against the dataset's labels, filled on a single-label model with at most 64 classes and at most 256 communities.  info int64 [7]
+ * = {levels run, communities, numerator, M2, levels that moved, contingency rows, skipped}.
+ * gcnhost_modularity_from_sums (no GPU): numerator / M2^2 in float64, 0 when M2 = 0. */
+int gcnhost_model_communities(gcnhost_model *m, int max_levels, int max_sweeps, int32_t *labels, int64_t *records, int32_t *level_labels,
+                              int level_capacity, int64_t *contingency, int64_t *info);
+double gcnhost_modularity_from_sums(int64_t numerator, int64_t m2);
 /* Explaining a logit (ModelQueries::explain / feature_importance, host/queries.h; kernels in csrc/explain.hip).  The network is
  * Z = A^ . (ReLU(A^ . X . W1) . W2) without bias: with the ReLU gates of a forward fixed, the logit of (node, class) is a plain sum
  * that splits exactly by the neighbour a term came through (one share per stored edge of the node's row, self loop included, a
